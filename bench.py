@@ -8,7 +8,7 @@ One *step* = one complete pass of the hot path over the workload, inputs already
             all-gather of the runs (RCCL send/recv, one peer per xGMI link), genome deal, upper-triangle join,
             all-to-all of the mirrored cells, K-order.  Same dataset at every N: "scaling": "strong".
 Outputs (all per-genome Scores blocks) stay in HBM; `host_path` in the same line is SURVEY.md §8d's wall time
-(host arrays in -> every Scores block on the host, PCIe both ways) measured by this run at N = 1.
+(host arrays in -> every Scores block on the host, PCIe both ways) measured by a --full run at N = 1.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (torch.distributed.run on 127.0.0.1) BEFORE anything touches a GPU; under torchrun it is one of the ranks.
@@ -18,11 +18,24 @@ With fewer than N GPUs visible (a one-GPU box) the ranks share device 0 and use 
 Workload: BASELINE.json configs[2], the canonical 64-genome set — the stand-in of BASELINE.md §4 (64 genomes x 750
 genes x 370 aa, 25 % substitutions, seed 6401; the real Mycoplasma .faa cannot be fetched offline); `--faa FILE` runs a
 real file.  value = N*(N-1) ordered gene pairs / seconds per step (the reference scores every row
-gene against all N columns).  `scale_set` repeats the measurement on configs[3] (128 x 4000 x 300, the set BASELINE.json
-shards over 8 GPUs) at the same N, so that a 1/2/4/8 series has a workload large enough to show scaling
-(`--no-scale-set` skips it).
+gene against all N columns).
 
-Extra objects on the JSON line:
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the outputs when
+`--dump-outputs DIR` is given, and prints the line: the contract fields, `config`, `lookups_per_s` and the rooflines of the
+join launch and of the whole step, all taken from the timed steps themselves.  `--full` adds everything that takes runs of its
+own: `stage_ms` (one more step with per-stage events), the measured `roofline.traffic`, `host_path`, `host_path_native`,
+`pipeline`, `scale_set` and `cpu_baseline`; the `--no-*` options leave single items of it out.
+
+`--dump-outputs DIR` writes what a caller of the timed path receives after the last timed step: every genome's Scores block
+(PangeneNative.generate_scores_part), each field concatenated over the genomes in genome order, as DIR/<field>.npy, plus
+DIR/scoresCount.npy (cells per genome).  Floats stay float32; integer fields are stored as float32 where every value is
+exact in it, float64 otherwise.  Above 64 MB in all, every field is cut to a fixed sample (seed 0) of its flattened
+elements, whose positions go to DIR/<field>.index.npy.
+
+`scale_set` (--full) repeats the measurement on configs[3] (128 x 4000 x 300, the set BASELINE.json shards over 8 GPUs) at
+the same N, so that a 1/2/4/8 series has a workload large enough to show scaling (`--no-scale-set` skips it).
+
+Extra objects on the JSON line (`roofline.traffic` measured and `cpu_baseline` only with --full):
   roofline             dominant kernel = K-join; achieved = algorithmic bytes of the join launch (8 B per lookup as the
                        reference counts them + 20 B per emitted cell + 8 B per (gene, genome) maximum) / its HIP-event
                        duration measured inside the library on the launch stream.  `traffic` = HBM bytes of the same
@@ -53,6 +66,37 @@ sys.path.insert(0, str(ROOT))
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SCALE_SET = "synthetic_128x4000x300"
+DUMP_LIMIT = 64_000_000  # bytes of all --dump-outputs files together
+NPY_HEADER = 128         # bytes of a .npy header (format 1.0, one-dimensional or two-dimensional array)
+
+
+def write_outputs(blocks, out_dir):
+    """--dump-outputs: {genome: Scores.as_dict()} -> out_dir/<field>.npy (module docstring)."""
+    from pandelos_amd.scores import FIELDS
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    order = sorted(blocks)
+    arrays = {"scoresCount": np.array([blocks[g]["scoresCount"] for g in order], np.float64)}
+    for f in FIELDS:
+        a = np.concatenate([np.asarray(blocks[g][f]) for g in order])
+        if a.dtype.kind in "iu":
+            exact = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) <= 1 << 24
+            a = a.astype(np.float32 if exact else np.float64)
+        arrays[f] = a
+    total = sum(a.nbytes + NPY_HEADER for a in arrays.values())
+    if total > DUMP_LIMIT:
+        # the same share of every field, its sampled positions (float64) counted in; scoresCount (G values) stays whole
+        fields = list(FIELDS)
+        room = DUMP_LIMIT - arrays["scoresCount"].nbytes - NPY_HEADER * (2 * len(fields) + 1)
+        share = room / sum(arrays[f].size * (arrays[f].itemsize + 8) for f in fields)
+        rng = np.random.default_rng(0)
+        for name in fields:
+            a = arrays[name].reshape(-1)
+            idx = np.sort(rng.choice(a.size, size=int(a.size * share), replace=False))
+            arrays[name] = a[idx]
+            arrays[name + ".index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def cpu_baseline(gs, k, pairs, max_threads):
@@ -185,7 +229,21 @@ class Runner:
             dist.barrier()
         self.torch.cuda.synchronize()
 
-    def measure(self, steps, warmup, coll_dev):
+    def outputs(self):
+        """What a caller of the timed path receives: every genome's Scores block, {genome: Scores.as_dict()}; N > 1: each rank
+        reads the genomes it scored and rank 0 gathers them (None on the other ranks)."""
+        mine = range(self.gs.genomes) if self.dp is None else self.dp.my_genomes()
+        blocks = {g: self.nat.generate_scores_part(g).as_dict() for g in mine}
+        if self.dp is None:
+            return blocks
+        import torch.distributed as dist
+        parts = [None] * self.n_gpus if self.rank == 0 else None
+        dist.gather_object(blocks, parts, dst=0)
+        return {g: b for p in parts for g, b in p.items()} if self.rank == 0 else None
+
+    def measure(self, steps, warmup, coll_dev, dump_dir=None, stages=True):
+        """Warm-up, the timed steps, then (dump_dir) the outputs of the last timed step and (stages) one more step with
+        per-stage events for stage_ms."""
         from pandelos_amd import distributed as D
         for _ in range(warmup):
             self.step()
@@ -205,9 +263,15 @@ class Runner:
         self.sync()
         elapsed = D.all_reduce_max(time.perf_counter() - t0, device=coll_dev)
         sec_per_step = elapsed / max(steps, 1)
-        self.nat.set_option("stage_timers", 1)      # one more step, untimed, for the per-stage breakdown (stage_ms)
-        self.step()
-        self.sync()
+        if dump_dir is not None:
+            blocks = self.outputs()
+            if blocks is not None:
+                write_outputs(blocks, dump_dir)
+            del blocks
+        if stages:
+            self.nat.set_option("stage_timers", 1)  # one more step, untimed, for the per-stage breakdown (stage_ms)
+            self.step()
+            self.sync()
         gs, cost, tm = self.gs, self.nat.cost, self.nat.timings()
         mean = lambda v: sum(v) / len(v) if v else 0.0
         # algorithmic bytes of this rank's join launch (SURVEY.md §8d join terms; lookups as the reference counts them)
@@ -219,6 +283,10 @@ class Runner:
         bytes_alg_total = (cost.residues + 16.0 * cost.kmer_occurrences + 16.0 * cost.dictionary_records +
                            8.0 * p_total + 20.0 * z_total + 8.0 * gs.genes * gs.genomes)
         pairs = float(gs.genes) * float(gs.genes - 1)
+        out = {"pairs": pairs, "sec_per_step": sec_per_step, "cost": cost, "join_bytes": join_bytes, "join_s": join_s,
+               "bytes_alg_total": bytes_alg_total, "z_total": z_total, "p_total": p_total, "walked": walked}
+        if not stages:
+            return out
         stage = {"preprocess": mean(pre_ms), "score": mean(score_ms), "hist": tm["hist_ms"], "rank": tm["rank_ms"],
                  "sort_rank": tm["sort_rank_ms"], "dict": tm["dict_ms"], "sort_seq": tm["sort_seq_ms"], "ranges": tm["ranges_ms"],
                  "join": tm["join_ms"], "join_overflow": tm["join_overflow_ms"], "order": tm["order_ms"],
@@ -228,8 +296,8 @@ class Runner:
                           "dist_score_finish": tm["dist_score_finish_ms"], "range_lists_by": "senders" if self.dp.sender_ranges else "owners",
                           "exchange_dictionary_wall": mean(xd), "exchange_ranges_wall": mean(xr), "exchange_cells_wall": mean(xc),
                           "outbox_cells_rank0": tm["outbox_cells"]})
-        return {"pairs": pairs, "sec_per_step": sec_per_step, "cost": cost, "stage_ms": stage, "join_bytes": join_bytes, "join_s": join_s,
-                "bytes_alg_total": bytes_alg_total, "z_total": z_total, "p_total": p_total, "walked": walked}
+        out["stage_ms"] = stage
+        return out
 
     def host_path(self, iters):
         """SURVEY.md §8d wall time: host arrays -> dictionary -> scores -> every genome's Scores block on the host.  One host
@@ -307,13 +375,19 @@ def main():
     ap.add_argument("--config", default="mycoplasma64_standin")
     ap.add_argument("--faa", default=None, help="run a real .faa instead of the synthetic stand-in")
     ap.add_argument("--k", type=int, default=0, help="override k (default: calculate_k)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scale-set", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also stage_ms, roofline.traffic, host_path(_native), pipeline, scale_set and cpu_baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Scores blocks of the last timed step as DIR/<field>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave cpu_baseline out")
+    ap.add_argument("--no-scale-set", action="store_true", help="(--full) leave scale_set out")
+    ap.add_argument("--no-host-path", action="store_true", help="(--full) leave host_path, host_path_native and pipeline out")
+    ap.add_argument("--no-traffic", action="store_true", help="(--full) skip the two rocprofv3 --pmc child passes that measure roofline.traffic")
     ap.add_argument("--cpu-threads", type=int, default=64)
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="pdl_set_option on every context (experiments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -361,7 +435,7 @@ def main():
         data_kind = "synthetic"
     k = args.k or calculate_k(gs.residues)
     run.load(gs, k)
-    m = run.measure(args.steps, args.warmup, coll_dev)
+    m = run.measure(args.steps, args.warmup, coll_dev, dump_dir=args.dump_outputs, stages=args.full)
     cost = m["cost"]
     achieved = m["join_bytes"] / m["join_s"] / 1e9 if m["join_s"] > 0 else 0.0
     whole = m["bytes_alg_total"] / m["sec_per_step"] / 1e9
@@ -369,8 +443,8 @@ def main():
     # HBM-side traffic of the join launch from the committed PMC profile of this workload (FETCH_SIZE / WRITE_SIZE
     # are collected in separate rocprofv3 --pmc passes, corrected as MI355X_MICROARCH.md prescribes; see
     # profiles/*_pmc_traffic_join.json).  null when no profile of this workload/sharding is on file.
-    traffic, traffic_src = None, None
-    if n_gpus == 1 and not args.faa:
+    traffic, traffic_src = None, (None if args.full else "not measured: runs of its own, --full")
+    if args.full and n_gpus == 1 and not args.faa:
         if not args.no_traffic:
             traffic, traffic_src = measure_traffic(args.config, args.option)
         if traffic is None:
@@ -405,9 +479,8 @@ def main():
                    "dictionary_records": int(cost.dictionary_records), "lookups": int(m["p_total"]),
                    "lookups_walked": int(m["walked"]), "emitted_cells": int(m["z_total"]),
                    "cells_per_row": m["z_total"] / max(gs.genes, 1), "sharding": sharding},
-        "timed_region": "inputs and outputs resident in HBM (host_path = SURVEY §8d host-to-host wall time); timed steps carry the HIP events of the two totals and of the join only, stage_ms comes from one more step outside the timed region",
+        "timed_region": "inputs and outputs resident in HBM (host_path = SURVEY §8d host-to-host wall time); timed steps carry the HIP events of the two totals and of the join only, stage_ms (--full) comes from one more step outside the timed region",
         "lookups_per_s": m["p_total"] / m["sec_per_step"],
-        "stage_ms": m["stage_ms"],
         "roofline": {"bound": "hbm", "kernel": "k_join_part / k_join_lds (+k_join_hbm): every tier of the join, one event pair", "achieved": achieved, "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
                      "bytes_per_launch": m["join_bytes"], "launch_ms": m["join_s"] * 1e3},
@@ -415,9 +488,11 @@ def main():
                                 "frac": whole / (HBM_PEAK_GBPS * n_gpus), "bytes_alg": m["bytes_alg_total"],
                                 "formula": "1*R + 16*M + 16*U + 8*P + 20*Z + 8*N*G (SURVEY.md §8d)"},
     }
+    if args.full:
+        out["stage_ms"] = m["stage_ms"]
     if rehearsal:
         out["rehearsal"] = True
-    if n_gpus == 1 and not args.no_host_path:
+    if args.full and n_gpus == 1 and not args.no_host_path:
         hp = run.host_path(9)
         hp["value"] = m["pairs"] / (hp["ms"] / 1e3)
         hp["unit"] = "gene-pairs/s"
@@ -441,7 +516,7 @@ def main():
     run.close()
 
     # ---- the set BASELINE.json shards over 8 GPUs, at this N ------------------------------------------------------
-    if not args.no_scale_set and not args.faa and args.config != SCALE_SET:
+    if args.full and not args.no_scale_set and not args.faa and args.config != SCALE_SET:
         shape = CONFIGS[SCALE_SET]
         gs2 = make_gene_set(**shape)
         k2 = calculate_k(gs2.residues)
@@ -459,7 +534,7 @@ def main():
         del gs2
 
     if rank == 0:
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(gs, k, m["pairs"], args.cpu_threads)
             except Exception as e:  # the baseline must never take the measurement down

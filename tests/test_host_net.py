@@ -6,8 +6,6 @@ netclu_ng.py in the build container).  GPU: the whole path .faa -> .net on the d
 which makes the gene families (.clus) identical too.  NOTE: nothing of the reference pins the Java host (no JVM here, no
 reference tests): these fixtures pin our reading of it, not the Java itself."""
 import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -65,18 +63,21 @@ def test_java_hashmap_order_and_double_format():
         assert PH._java_double_str(np.array([v], np.float64))[0] == s
 
 
-@pytest.mark.skipif(not Path("/root/reference/netclu_ng.py").exists(), reason="reference scripts not present")
 def test_clus_from_product_net_equals_fixture(tmp_path):
-    """pandelos.sh:76-79 on our .net: the reference's netclu_ng.py + grep/sed/sort/uniq."""
+    """pandelos.sh:76-79 on our .net: de-clustering + grep/sed/sort/uniq, through pandelos_amd/netclu.py (the restatement of
+    the reference's netclu_ng.py that tests/test_netclu.py pins to it); the .clus fixture is the reference script's output."""
+    from pandelos_amd import netclu
     name = "synth_5x60x80_k3"
     shape, k = CASES[name]
     gs = make_gene_set(**shape)
     faa, net = tmp_path / "in.faa", tmp_path / "out.net"
     gs.write_faa(faa)
     net.write_text("".join(PH.run(_OracleNative(gs, k), gs.genomes)))
-    p = subprocess.run([sys.executable, "/root/reference/netclu_ng.py", str(faa), str(net)], capture_output=True, text=True, check=True)
-    fams = sorted({l.replace("F{ ", "").replace("}", "").replace(" ;", "") for l in p.stdout.splitlines() if "F{ " in l})
-    assert "".join(f + "\n" for f in fams) == (NET / f"{name}.clus").read_text()
+    names, genome_of = netclu.read_names(faa)
+    fams, singles = netclu.families(names, genome_of, netclu.read_net(net))
+    text = netclu.clus_text(names, fams, singles)
+    assert text == (NET / f"{name}.clus").read_text()
+    fams = text.splitlines()
     planted = {}
     for i, f in enumerate(gs.family_of):
         planted.setdefault(int(f), []).append(i)

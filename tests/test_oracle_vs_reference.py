@@ -1,56 +1,95 @@
 """Pins the oracle against the reference's own library.cpp on fresh random inputs.
-Needs oracle/_ref (built only where /root/reference exists) — skipped elsewhere."""
-import numpy as np
+Every test compares the oracle with the reference's results recorded in tests/golden/reference_sets.json
+(make_golden_reference_sets.py); where oracle/_ref is built, the reference also runs live and must reproduce them."""
+import hashlib
+import json
+
 import pytest
 
 from oracle import binding as ob
 from pandelos_amd.synth import make_gene_set
 from tests import helpers as H
 
-pytestmark = pytest.mark.skipif(not ob.have_reference(), reason="oracle/_ref not built (no /root/reference)")
-
-
-@pytest.mark.parametrize("shape,k", [
+RANDOM_SETS = [
     (dict(genomes=3, genes_per_genome=40, mean_len=60, sub_rate=0.15, seed=101), 2),
     (dict(genomes=6, genes_per_genome=80, mean_len=50, sub_rate=0.05, seed=102), 3),
     (dict(genomes=9, genes_per_genome=300, mean_len=120, sub_rate=0.2, seed=103), 4),
     (dict(genomes=4, genes_per_genome=50, mean_len=90, sub_rate=0.1, seed=104), 15),
     (dict(genomes=4, genes_per_genome=50, mean_len=90, sub_rate=0.1, seed=104), 20),
-])
-def test_oracle_equals_reference_on_random_sets(tmp_path, shape, k):
-    gs = make_gene_set(**shape)
+]
+WRAPPED_SETS = [(22, 15), (24, 14), (11, 19)]
+THREADS_SET = (dict(genomes=6, genes_per_genome=80, mean_len=50, sub_rate=0.05, seed=102), 3)
+
+
+def _recorded(name):
+    return json.loads((H.GOLDEN / "reference_sets.json").read_text())[name]
+
+
+def random_set_id(shape, k):
+    return "random_{genomes}x{genes_per_genome}x{mean_len}_seed{seed}".format(**shape) + f"_k{k}"
+
+
+def wrapped_set_id(letters, k):
+    return f"wrapped_{letters}letters_k{k}"
+
+
+def _digests(per_genome):
+    return [{f: hashlib.sha256(H.raw(b[f]).tobytes()).hexdigest() for f in H.FIELDS} for b in per_genome]
+
+
+def _reference(gs, k, tmp_path, rec, threads=1):
+    """The reference's results on gs: a live run where oracle/_ref is built (checked against the record), else the record."""
+    if not ob.have_reference():
+        return rec
     faa = tmp_path / "in.faa"
     gs.write_faa(faa)
-    info = ob.run_harness(ob.REF_SO, faa, k, dump=tmp_path / "ref.bin")
-    ref = ob.read_dump(tmp_path / "ref.bin")
+    dump = tmp_path / f"ref{threads}.bin"
+    info = ob.run_harness(ob.REF_SO, faa, k, threads=threads, dump=dump)
+    ref = ob.read_dump(dump)
+    live = {"total_cost": info["total_cost"], "hash_fallback": bool(info["hash_fallback"]), "genome_cost": [info["genome_cost"][g] for g in range(ref["genomes"])],
+            "scoresCount": [int(len(b["scores"])) for b in ref["per_genome"]],
+            "dump_sha256": hashlib.sha256(dump.read_bytes()).hexdigest(), "sha256": _digests(ref["per_genome"])}
+    assert live == rec, "the reference build no longer reproduces tests/golden/reference_sets.json"
+    return live
+
+
+def _assert_oracle_reproduces(o, rec, label):
+    assert o.total_cost == rec["total_cost"] and o.hash_fallback == rec["hash_fallback"]
+    got = [o.scores(g) for g in range(o.genomes)]
+    assert [int(d["scoresCount"]) for d in got] == rec["scoresCount"], label
+    for g, (have, want) in enumerate(zip(_digests(got), rec["sha256"])):
+        for f in H.FIELDS:
+            assert have[f] == want[f], f"{label} genome {g} field {f}"
+
+
+@pytest.mark.parametrize("shape,k", RANDOM_SETS)
+def test_oracle_equals_reference_on_random_sets(tmp_path, shape, k):
+    gs = make_gene_set(**shape)
+    rec = _reference(gs, k, tmp_path, _recorded(random_set_id(shape, k)))
     o = ob.Oracle(gs.residues, gs.offsets, gs.genome_of, k)
-    assert o.total_cost == info["total_cost"]
-    assert o.hash_fallback == info["hash_fallback"]
-    for g in range(ref["genomes"]):
-        assert o.genome_cost(g) == info["genome_cost"][g]
-        H.assert_scores_equal(o.scores(g), ref["per_genome"][g], f"genome {g}")
+    for g in range(o.genomes):
+        assert o.genome_cost(g) == rec["genome_cost"][g]
+    _assert_oracle_reproduces(o, rec, random_set_id(shape, k))
 
 
-@pytest.mark.parametrize("letters,k", [(22, 15), (24, 14), (11, 19)])
+@pytest.mark.parametrize("letters,k", WRAPPED_SETS)
 def test_oracle_equals_reference_where_ranks_wrap_unnoticed(tmp_path, letters, k):
     """B^k > 2^64 but rank_init's overflow test lets it through (it compares wrapped products): no hashing, the ranks are the
     polynomial mod 2^64 and rank_byte_order comes from the wrapped B^k.  The oracle restates exactly that."""
     gs = H.wrapped_rank_set(letters, seed=letters * 100 + k)
-    faa = tmp_path / "in.faa"
-    gs.write_faa(faa)
-    info = ob.run_harness(ob.REF_SO, faa, k, dump=tmp_path / "ref.bin")
-    ref = ob.read_dump(tmp_path / "ref.bin")
+    rec = _reference(gs, k, tmp_path, _recorded(wrapped_set_id(letters, k)))
     o = ob.Oracle(gs.residues, gs.offsets, gs.genome_of, k)
-    assert letters ** k >= 1 << 64 and not info["hash_fallback"] and not o.hash_fallback
-    assert o.total_cost == info["total_cost"] and info["total_cost"] > 0
-    for g in range(ref["genomes"]):
-        H.assert_scores_equal(o.scores(g), ref["per_genome"][g], f"genome {g}")
+    assert letters ** k >= 1 << 64 and not rec["hash_fallback"] and not o.hash_fallback
+    assert rec["total_cost"] > 0
+    _assert_oracle_reproduces(o, rec, wrapped_set_id(letters, k))
 
 
 def test_reference_is_thread_safe_in_harness(tmp_path):
-    gs = make_gene_set(genomes=6, genes_per_genome=80, mean_len=50, sub_rate=0.05, seed=102)
-    faa = tmp_path / "in.faa"
-    gs.write_faa(faa)
-    ob.run_harness(ob.REF_SO, faa, 3, threads=1, dump=tmp_path / "a.bin")
-    ob.run_harness(ob.REF_SO, faa, 3, threads=4, dump=tmp_path / "b.bin")
-    assert (tmp_path / "a.bin").read_bytes() == (tmp_path / "b.bin").read_bytes()
+    """One thread and four give the same dump byte for byte (live where oracle/_ref is built; else the recorded runs), and
+    the oracle reproduces it."""
+    shape, k = THREADS_SET
+    gs = make_gene_set(**shape)
+    one = _reference(gs, k, tmp_path, _recorded("threads1_" + random_set_id(shape, k)), threads=1)
+    four = _reference(gs, k, tmp_path, _recorded("threads4_" + random_set_id(shape, k)), threads=4)
+    assert one["dump_sha256"] == four["dump_sha256"] and one == four
+    _assert_oracle_reproduces(ob.Oracle(gs.residues, gs.offsets, gs.genome_of, k), one, "threads")

@@ -6,7 +6,7 @@ tag=${1:-rXX}
 export TMPDIR=/tmp
 out=gpurun_out
 mkdir -p $out
-python3 bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err || exit 1
+python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err || exit 1
 rocprofv3 --kernel-trace --stats -d $out/ks --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-scale-set --no-host-path --no-traffic > $out/ks.log 2>&1 || exit 1
 cp "$(find $out/ks -name '*kernel_stats.csv' | sort | tail -1)" $out/${tag}_bench_default_kernel_stats.csv; rm -rf $out/ks
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pf --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-scale-set --no-host-path --no-traffic > $out/pf.log 2>&1 || exit 1
