@@ -199,6 +199,29 @@ typedef struct {
 PDL_API int pdl_compute_edges(pdl_ctx *, uint32_t genome, pdl_edges *out);
 PDL_API void pdl_free_edges(pdl_edges *);
 
+/* ---- query: one new genome against the dictionary already built (no rebuild) --------------------------------------
+ * Returns the block computeScores(G) (library.cpp:409-527, marshalled as :542-603) returns for the UNION run: the base genes
+ * 0..N-1 in base order, then the n_query genes of residues/offsets as genome G (ids N..N+n_query-1), same k.  rows = n_query,
+ * genomes = G+1, sequences = N+n_query; first_seq_genome == G for every cell; PDL_FLAG_CANONICAL_ORDER orders each row by
+ * column.  Only that task's block: the other genomes' maxima would change in a full run and are not produced.  The base
+ * context is left as it was (scores, edges, dictionary, costs, timings); queries are independent of each other; the query's
+ * buffers are reused and released at the next preprocess or destroy.  Free `out` with pdl_free_scores.
+ * PDL_ERR_STATE: no preprocess, only_complexity, a multi-GPU context, or low_memory released the sorted k-mer stream.
+ * PDL_ERR_ARGUMENT: n_query == 0, NULL pointers, decreasing offsets.  PDL_ERR_UNSUPPORTED: a query byte the base's alphabet
+ * lacks (the union would have another rank table, library.cpp:96-119; the message names the byte), genes of 2^20 k-mers or
+ * more, or union sizes past the base build's limits (2^32 residues, 31-bit gene ids). */
+typedef struct {
+    uint64_t residues, kmer_occurrences;   /* of the query */
+    uint64_t records;          /* unique (rank, query gene) records */
+    uint64_t matched_records;  /* query records whose k-mer (rank) the base dictionary holds; a record whose union group gains a
+                                  base record only through the union's last-record fold does not count: that record's k-mer differs */
+    uint64_t genome_cost;      /* "Genome G cost" of the union run (library.cpp:327,535-538) */
+    float device_ms;           /* device time of the call: the sum of its stretches of device work (HIP event pairs), without the
+                                  host's reads in between (the record count and staging bound; whether a row left the LDS table) */
+} pdl_query_info;
+PDL_API int pdl_query_scores(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n_query+1] */,
+                             uint32_t n_query, pdl_scores *out, pdl_query_info *info /* may be NULL */);
+
 /* Number of emitted cells per genome after pdl_score_all ([G], 0 for genomes outside the shard) */
 PDL_API int pdl_scores_counts(pdl_ctx *, uint32_t *out_counts);
 

@@ -76,6 +76,7 @@ void pdl_destroy(pdl_ctx *c) {
     (void) hipSetDevice(c->device);
     (void) hipStreamSynchronize(c->stream);
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
+    for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
@@ -148,6 +149,7 @@ int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int onl
     PDL_GUARD_BEGIN
     PDL_HIP(hipSetDevice(c->device));
     c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;      // the genome shard, if one was set, stays in force
+    c->qb.release();
     c->N = n; c->R = n_res;
     c->U = c->Ushared = c->NG = c->P = c->M = 0;
     if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
@@ -696,6 +698,28 @@ int pdl_get_dictionary(pdl_ctx *c, uint64_t *ranks, uint32_t *seqs, uint32_t *co
         if (seqs) seqs[u] = post[u].x;
         if (counts) counts[u] = post[u].y & 0x7fffffffu;       // (complexity-only mode leaves the group-head bit in place)
     }
+    return PDL_OK;
+    PDL_GUARD_END(c)
+}
+
+int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_scores *out, pdl_query_info *info) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out) memset(out, 0, sizeof(*out));
+    if (info) memset(info, 0, sizeof(*info));
+    PDL_GUARD_BEGIN
+    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores before pdl_preprocess");
+    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: the context was preprocessed with only_complexity");
+    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: not available on a multi-GPU context");
+    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
+        PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: the sorted k-mer stream was released (option low_memory)");
+    if (!out || !offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL pointer");
+    if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: no query gene");
+    for (uint32_t i = 0; i < n_query; i++)
+        if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: offsets decrease at gene %u", i);
+    if (!residues && offsets[n_query] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL residues");
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_run_query(c, residues, offsets, n_query, out, info);
     return PDL_OK;
     PDL_GUARD_END(c)
 }

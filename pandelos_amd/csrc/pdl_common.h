@@ -281,6 +281,23 @@ struct pdl_ctx {
     uint64_t n_inbox = 0;
     uint32_t order_grid1 = 0;
 
+    // pdl_query_scores (pdl_query.h): the query's own buffers, reused across queries, released at the next preprocess or destroy
+    struct QueryBufs {
+        DevBuf res, off, koff, kseq, keys_a, keys_b, vals_a, vals_b, recpos, post, desc, gkey, rec_sorted, row_lookups, row_off,
+               fold, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells, hbm;
+        bool hbm_clean = false;                      // hbm holds hbm_slots tables laid out for hbm_cols columns, in their clean state
+        uint32_t hbm_cols = 0, hbm_slots = 0;
+        const uint32_t *rec_sorted_at = nullptr;     // (inside rec_sorted: the half the gene sort left its output in)
+        hipEvent_t ev[6] = {};                       // start / end of up to three stretches of device work
+        void release() {
+            DevBuf *all[] = {&res, &off, &koff, &kseq, &keys_a, &keys_b, &vals_a, &vals_b, &recpos, &post, &desc, &gkey, &rec_sorted,
+                             &row_lookups, &row_off, &fold, &ctl, &MS, &CM, &row_base, &row_cnt, &fin_off, &rowid, &overflow, &st, &cells, &hbm};
+            for (DevBuf *b : all) b->release();
+            hbm_clean = false; hbm_cols = hbm_slots = 0; rec_sorted_at = nullptr;
+        }
+    } qb;
+    uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
+
     pdl_timings tm{};
     EventPair ev[16];
     uint8_t *pin = nullptr;       // pinned host scratch for the small device->host reads (true async DMA, no staging copy)
@@ -417,6 +434,12 @@ void pdl_run_bbh_all(pdl_ctx *c);
 void pdl_ensure_costs(pdl_ctx *c);
 void pdl_input_arrived(pdl_ctx *c);      // deferred device input: waits for the genome ids / offset ends and checks them
 void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on the host
+// K-query (pdl_query.h): K-rank + K-sort + K-rle of the query genes with the base's rank parameters (pdl_dict.hip); the records
+// land in (recpos, post), their count at d_u; returns the buffer that holds the sorted keys
+const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
+                                 uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
+                                 uint64_t *d_u);
+void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
 inline uint2 *pdl_postings(const pdl_ctx *c) { return c->post_ext ? c->post_ext : c->post.as<uint2>(); }
 
 // event helpers

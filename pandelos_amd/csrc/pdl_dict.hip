@@ -1160,6 +1160,7 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     }
     if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "offsets must ascend from 0 to the residue count (%llu)", (unsigned long long) c->R);
     rank_init_host(c->rp, counters, kvalue);
+    for (int i = 0; i < 256; i++) c->alpha_present[i] = counters[i] ? 1 : 0;
     c->M = M;
     c->only_complexity = only_complexity;
     if (M == 0) PDL_FAIL(PDL_ERR_EMPTY, "no gene is at least k=%d residues long: the dictionary is empty", kvalue);
@@ -1500,6 +1501,31 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
         c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
         if (c->ranges8 == nullptr) {}        // (packed ranges live in `scratch`: it stays)
     }
+}
+
+template <class KeyT>
+static const void *query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
+                                    uint64_t n_res, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint32_t *recpos,
+                                    uint2 *post, uint64_t *d_u) {
+    hipStream_t st = c->stream;
+    if (c->rp.hash_fallback) {
+        if constexpr (sizeof(KeyT) == 8)
+            hipLaunchKernelGGL(k_rank_hash<0>, dim3((n + 255) / 256), dim3(256), 0, st, res, off, kmer_off, n, c->rp, keys_in, vals_in, (uint32_t *) nullptr);
+    } else {
+        const uint64_t tiles = (m + RANK_TILE - 1) / RANK_TILE;
+        hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, res, off, kmer_off, n, m, n_res, c->rp,
+                           keys_in, vals_in, 0u, (uint32_t *) nullptr);
+    }
+    PDL_HIP(hipGetLastError());
+    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+    scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_out}, RecScatter<KeyT>{keys_out, vals_out, m, recpos, post}, d_u);
+    return keys_out;
+}
+const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
+                                 uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
+                                 uint64_t *d_u) {
+    if (c->key64) return query_dictionary<uint64_t>(c, res, off, kmer_off, n, m, n_res, (uint64_t *) keys_a, (uint64_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
+    return query_dictionary<uint32_t>(c, res, off, kmer_off, n, m, n_res, (uint32_t *) keys_a, (uint32_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
 }
 
 void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity) {

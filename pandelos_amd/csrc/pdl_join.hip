@@ -1923,3 +1923,5 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
     c->scored = true;
     c->dist_stage = 4;
 }
+
+#include "pdl_query.h"           // K-query: one new genome against this dictionary (pdl_query_scores)

@@ -1,0 +1,659 @@
+// pdl_query.h — K-query: one new genome scored against the dictionary that is already in HBM (pdl_query_scores,
+// include/pandelos_amd.h), included from pdl_join.hip behind the join and K-order, whose finalize and ordering it reuses.
+//
+// Contract: the block computeScores(G) (library.cpp:409-527) returns for the UNION run — base genes 0..N-1, then the n query
+// genes as genome G with ids N..N+n-1, same k.  The base context is only read.
+//
+//   Q-alpha  k_q_alpha          query bytes against the base's letter-presence table (an absent letter changes the union's
+//                               rank table, library.cpp:96-119): the smallest offending byte
+//   Q-dict   pdl_query_dictionary (pdl_dict.hip)   K-rank with the base's RankParams, K-sort, K-rle: query records
+//                               (rank, gene, count) in (rank, gene) order
+//   Q-fold   k_q_fold           one thread: the base's last-record fold (k_fold_last_record) and the union's (Q1 below)
+//   Q-match  k_q_match          per query record: its union group as base slice(s) + query slice(s), binary searches
+//   Q-rows   gene sort of the records (pdl_sort_pairs) + k_q_row_off: each query gene's records, in rank order
+//   Q-join   k_q_join           one workgroup per query gene, LDS hash keyed by column; rows whose columns do not fit go to
+//            k_q_join_hbm       the same row program on direct-addressed tables in HBM
+//   Q-order  k_order_rows_wave / k_order_rows   the reference's emission order (chunk, first group, column)
+//
+// Match.  The base postings are rank-group major: the rank of post[u] is keys_b[recpos[u]] (what pdl_get_dictionary reads).
+// They are in rank order except for ONE record: when the base's last record (rank bmax) was alone in its rank,
+// k_fold_last_record moved it into the group before it (rank r2), at its gene-order place.  Every rank of [gs, U) is r2
+// except that record p, so a search for a rank below r2 runs over [0, gs), rank r2 is [gs, U) (minus p where the union
+// does not fold it), rank bmax is {p}.  Binary search rather than a merge-path join: the query holds 1/(G+1) of the
+// records, so log2(U) dependent probes per query record cost less than a pass over the whole dictionary.
+//
+// Q1 of the union (library.cpp:297-306).  The union's last record L (largest rank, then largest gene) joins the group of
+// the largest rank below it when it is alone in its rank.  With qmax = largest query rank:
+//   qmax > bmax, alone   L is the last query record qL; it joins the group of max(bmax, second query rank) — case (a);
+//                        a base record p that the base had folded is an ordinary group of rank bmax again — case (b)
+//   qmax >= bmax         otherwise no union fold; p (if folded) is again ordinary — cases (b), (d)
+//   qmax <  bmax         L is the base's last record; if it was alone it joins max(r2, qmax): a query group when qmax > r2
+//                        (p leaves [gs, U)) — case (c) — or r2 as in the base
+// A group is described by {base slice, base record skipped, extra base record, query slice, extra query record}.
+#pragma once
+#include "pdl_sort.h"
+
+constexpr uint32_t Q_NONE = 0xffffffffu;
+
+struct QDesc {              // one query record's union group
+    uint32_t blo, bhi;      // base postings [blo, bhi) ...
+    uint32_t bskip;         // ... without this one (Q_NONE: none)
+    uint32_t bextra;        // one more base posting (Q_NONE: none)
+    uint32_t qlo, qhi;      // query records [qlo, qhi)
+    uint32_t qextra;        // one more query record (Q_NONE: none)
+    uint32_t key;           // order of the group among the row's groups (monotone in the group's rank)
+};
+__device__ __forceinline__ uint32_t q_size(const QDesc &d) {
+    return (d.bhi - d.blo) - (d.bskip != Q_NONE ? 1u : 0u) + (d.bextra != Q_NONE ? 1u : 0u) + (d.qhi - d.qlo) + (d.qextra != Q_NONE ? 1u : 0u);
+}
+
+struct QFold {
+    unsigned long long bmax, r2, tgt, extra_target;
+    uint32_t folded;        // the base folded its last record p into the group of rank r2 = [gs, U)
+    uint32_t gs, p;
+    uint32_t skip_p;        // in the union p is not part of [gs, U)
+    uint32_t qL;            // query record the union folds into the group of rank tgt (Q_NONE: none)
+    uint32_t has_extra;     // p joins the query group of rank extra_target
+};
+
+// control words of a query (u64): 0 records | 1 256 - smallest absent byte (0: none) | 2 genome cost | 3 matched records |
+// 4 staging bound | 5 overflow rows | 6 staging cursor | 7 emitted cells | 8 order: wide rows | 9 rows that may overflow (more
+// lookups than the LDS table holds keys)
+constexpr uint32_t Q_CTL_WORDS = 16;
+
+// *bad = max(256 - byte) over the absent bytes (0: none), i.e. 256 - the smallest absent byte
+struct QAlphaArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; unsigned long long *bad; };
+__global__ __launch_bounds__(256) void k_q_alpha(QAlphaArgs a) {
+    uint32_t worst = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
+        const uint32_t b = a.res[i];
+        if (!((a.present[b >> 5] >> (b & 31)) & 1u)) worst = max(worst, 256u - b);
+    }
+    if (worst) atomicMax(a.bad, (unsigned long long) worst);
+}
+
+template <class KeyT> struct QView {
+    const KeyT *bkeys; const uint32_t *brecpos; const uint32_t *bvals; const uint2 *post; uint32_t U; uint64_t M;
+    const KeyT *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
+    __device__ unsigned long long brank(uint32_t u) const { return (unsigned long long) bkeys[brecpos[u]]; }
+    __device__ unsigned long long qrank(uint32_t j) const { return (unsigned long long) qkeys[qrecpos[j]]; }
+    // first u in [lo, hi) with rank(u) >= v (UPPER: > v); ranks ascend over the range
+    template <bool UPPER> __device__ uint32_t bbound(uint32_t lo, uint32_t hi, unsigned long long v) const {
+        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = brank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
+        return lo;
+    }
+    template <bool UPPER> __device__ uint32_t qbound(uint32_t lo, uint32_t hi, unsigned long long v) const {
+        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = qrank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
+        return lo;
+    }
+};
+
+// One thread: the folds of the base and of the union (see the head of this file).
+template <class KeyT>
+__global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    QFold f{};
+    f.p = Q_NONE; f.qL = Q_NONE;
+    const uint32_t Uq = (uint32_t) ctl[0];
+    const uint32_t U = v.U;
+    f.bmax = (unsigned long long) v.bkeys[v.M - 1];
+    bool lonely = U == 1;                 // the base's last record is alone in its rank (U == 1: nothing to fold it into)
+    bool has_r2 = false;
+    if (U == 1) f.p = 0;
+    else {
+        const unsigned long long rl = v.brank(U - 1), rl2 = v.brank(U - 2);
+        f.folded = (rl != f.bmax || rl2 != f.bmax) ? 1u : 0u;
+        if (f.folded) {
+            lonely = has_r2 = true;
+            f.r2 = rl != f.bmax ? rl : rl2;
+            f.gs = v.template bbound<false>(0, U, f.r2);          // (p ranks above r2: the predicate rank < r2 stays monotone)
+            const uint32_t gl = v.bvals[v.M - 1];                 // gene of the folded record; [gs, U) ascends by gene, p included
+            uint32_t lo = f.gs, hi = U;
+            while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (v.post[m].x < gl) lo = m + 1; else hi = m; }
+            if (v.brank(lo) != f.bmax) lo++;                      // the r2 record of the same gene sits in front of p
+            f.p = lo;
+        }
+    }
+    const unsigned long long qmax = v.qrank(Uq - 1);
+    const bool alone = Uq == 1 || v.qrank(Uq - 2) != qmax;
+    if (qmax > f.bmax) {
+        f.skip_p = f.folded;
+        if (alone) {
+            f.qL = Uq - 1;
+            const unsigned long long q2 = Uq >= 2 ? v.qrank(Uq - 2) : 0ull;
+            f.tgt = (Uq >= 2 && q2 > f.bmax) ? q2 : f.bmax;
+        }
+    } else if (qmax == f.bmax) {
+        f.skip_p = f.folded;
+    } else if (lonely && (!has_r2 || qmax > f.r2)) {
+        f.skip_p = f.folded; f.has_extra = 1; f.extra_target = qmax;
+    }
+    *out = f;
+}
+
+struct QMatchOut {
+    QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
+    unsigned long long *ctl;
+};
+template <class KeyT>
+__global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf, QMatchOut o, uint64_t bound) {
+    const QFold f = *pf;
+    const uint32_t Uq = (uint32_t) o.ctl[0];
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    unsigned long long cost = 0, matched = 0;
+    if (j < Uq && j < bound) {
+        const unsigned long long r = v.qrank(j);
+        const unsigned long long eff = j == f.qL ? f.tgt : r;
+        QDesc d;
+        d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
+        if (f.folded) {
+            if (eff < f.r2) { d.blo = v.template bbound<false>(0, f.gs, eff); d.bhi = v.template bbound<true>(d.blo, f.gs, eff); }
+            else if (eff == f.r2) { d.blo = f.gs; d.bhi = v.U; if (f.skip_p) d.bskip = f.p; }
+            else if (eff == f.bmax) { d.blo = f.p; d.bhi = f.p + 1; }
+        } else {
+            d.blo = v.template bbound<false>(0, v.U, eff); d.bhi = v.template bbound<true>(d.blo, v.U, eff);
+        }
+        if (f.has_extra && eff == f.extra_target) d.bextra = f.p;
+        const uint32_t qn = f.qL != Q_NONE ? Uq - 1 : Uq;
+        d.qlo = v.template qbound<false>(0, qn, eff); d.qhi = v.template qbound<true>(d.qlo, qn, eff);
+        if (f.qL != Q_NONE && eff == f.tgt) d.qextra = f.qL;
+        d.key = 2u * d.qlo + (d.qhi > d.qlo ? 1u : 0u);
+        const uint32_t sz = q_size(d);
+        o.desc[j] = d;
+        const uint32_t gene = v.qpost[j].x;
+        o.gene_key[j] = gene;
+        if (sz >= 2) { cost = sz; atomicAdd(&o.row_lookups[gene], sz); }
+        matched = (j != f.qL && d.bhi > d.blo) ? 1ull : 0ull;
+    }
+#pragma unroll
+    for (int s = PDL_WAVE / 2; s > 0; s >>= 1) { cost += __shfl_down(cost, s, PDL_WAVE); matched += __shfl_down(matched, s, PDL_WAVE); }
+    if ((threadIdx.x & (PDL_WAVE - 1)) == 0) {
+        if (cost) atomicAdd(&o.ctl[2], cost);
+        if (matched) atomicAdd(&o.ctl[3], matched);
+    }
+}
+
+// row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns)
+// row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns); rows whose
+// lookups exceed `limit` (they may claim more columns than the LDS table of the join holds)
+__global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, const unsigned long long *ctl, uint32_t n, uint32_t *row_off,
+                                                   const uint32_t *row_lookups, uint32_t n_cols, uint32_t limit, unsigned long long *bound,
+                                                   unsigned long long *wide) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t Uq = (uint32_t) ctl[0];
+    unsigned long long b = 0, w = 0;
+    if (g <= n) {
+        uint32_t lo = 0, hi = Uq;
+        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (gene_sorted[m] < g) lo = m + 1; else hi = m; }
+        row_off[g] = lo;
+        if (g < n) { b = min(row_lookups[g], n_cols); w = row_lookups[g] > limit ? 1ull : 0ull; }
+    }
+#pragma unroll
+    for (int s = PDL_WAVE / 2; s > 0; s >>= 1) { b += __shfl_down(b, s, PDL_WAVE); w += __shfl_down(w, s, PDL_WAVE); }
+    if ((threadIdx.x & (PDL_WAVE - 1)) == 0) {
+        if (b) atomicAdd(bound, b);
+        if (w) atomicAdd(wide, w);
+    }
+}
+
+// ---- Q-join ------------------------------------------------------------------------------------------------------------
+constexpr int QJ_T = 256;
+constexpr uint32_t QJ_HT_BITS = 12, QJ_HT = 1u << QJ_HT_BITS;
+constexpr uint32_t QJ_LIMIT = QJ_HT - 2 * QJ_T;         // keys a row may claim before it goes to the HBM tables (< HT: probes end)
+constexpr uint32_t QJ_SLOTS = QJ_HT / QJ_T;
+constexpr int QH_WG = 16;                               // workgroups (each with its own tables) of the HBM kernel, at most
+
+struct QJoinArgs {
+    const uint2 *post, *qpost;
+    const QDesc *desc;
+    const uint32_t *rec_sorted;     // record indices, grouped by gene, rank order inside
+    const uint32_t *row_off;        // [n + 1]
+    const uint32_t *kseq_b, *kseq_q, *genome_b;
+    uint32_t N, n, G1, k;           // G1 = G + 1 genomes of the union
+    float *MS, *CM;                 // [n][G1], [N + n]
+    uint32_t *row_base, *row_cnt;
+    float *st_score, *st_perc, *st_tr;
+    uint32_t *st_col, *st_first;
+    unsigned long long *cell_cursor;
+    uint32_t *overflow_rows;
+    unsigned long long *n_overflow;
+    uint8_t *hbm;                   // HBM kernel: per workgroup w, at w * 16 * (N + n) bytes: acc u64[N + n] | first u32[N + n] | touched u32[N + n]
+};
+
+// member m of a union group -> {column, count}
+__device__ __forceinline__ uint2 q_member(const QJoinArgs &a, const QDesc &d, uint32_t m) {
+    const uint32_t nb = (d.bhi - d.blo) - (d.bskip != Q_NONE ? 1u : 0u) + (d.bextra != Q_NONE ? 1u : 0u);
+    if (m < nb) {
+        uint32_t u;
+        if (d.bextra != Q_NONE && m == nb - 1) u = d.bextra;
+        else { u = d.blo + m; if (d.bskip != Q_NONE && u >= d.bskip) u++; }
+        const uint2 b = a.post[u];
+        return make_uint2(b.x, b.y & 0x7fffffffu);
+    }
+    m -= nb;
+    const uint32_t j = m < d.qhi - d.qlo ? d.qlo + m : d.qextra;
+    const uint2 q = a.qpost[j];
+    return make_uint2(a.N + q.x, q.y & 0x7fffffffu);
+}
+
+// Walk the row's groups in chunks of QJ_T records: sizes scanned in LDS, then the chunk's lookups as one flat index space.
+// add(col, packed sums, group key) returns false when the row must leave the table.
+template <class AddF>
+__device__ __forceinline__ void q_walk_row(const QJoinArgs &a, uint32_t g, QDesc *s_d, uint32_t *s_cnt, uint32_t *s_pre, uint32_t *s_stop, AddF add) {
+    const uint32_t r0 = a.row_off[g], r1 = a.row_off[g + 1], row = a.N + g;
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1), wave = threadIdx.x / PDL_WAVE;
+    for (uint32_t c0 = r0; c0 < r1; c0 += QJ_T) {
+        uint32_t sz = 0;
+        const uint32_t ri = c0 + threadIdx.x;
+        if (ri < r1) {
+            const uint32_t j = a.rec_sorted[ri];
+            const QDesc d = a.desc[j];
+            sz = q_size(d);
+            if (sz < 2) sz = 0;
+            s_d[threadIdx.x] = d;
+            s_cnt[threadIdx.x] = a.qpost[j].y & 0x7fffffffu;
+        }
+        // exclusive scan of the sizes: inside the wave by shuffles, then the four wave totals
+        uint32_t incl = sz;
+#pragma unroll
+        for (int s = 1; s < PDL_WAVE; s <<= 1) { const uint32_t t = __shfl_up(incl, s, PDL_WAVE); if ((int) lane >= s) incl += t; }
+        if (lane == PDL_WAVE - 1) s_pre[QJ_T + 1 + wave] = incl;
+        pdl_sync();
+        uint32_t off = 0;
+        for (uint32_t w = 0; w < wave; w++) off += s_pre[QJ_T + 1 + w];
+        s_pre[threadIdx.x] = off + incl - sz;
+        if (threadIdx.x == QJ_T - 1) s_pre[QJ_T] = off + incl;
+        pdl_sync();
+        const uint32_t total = s_pre[QJ_T];
+        for (uint32_t t = threadIdx.x; t < total; t += QJ_T) {
+            if (*(volatile uint32_t *) s_stop) break;
+            uint32_t lo = 0, hi = QJ_T;                   // last record i with s_pre[i] <= t
+            while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (s_pre[m] <= t) lo = m; else hi = m; }
+            const QDesc &d = s_d[lo];
+            const uint2 mc = q_member(a, d, t - s_pre[lo]);
+            if (mc.x == row) continue;                    // the self cell is zeroed (library.cpp:485-487): never emitted
+            const uint32_t my = s_cnt[lo];
+            const unsigned long long packed = (unsigned long long) min(mc.y, my) | ((unsigned long long) my << 21) | ((unsigned long long) mc.y << 42);
+            if (!add(mc.x, packed, d.key)) { *s_stop = 1u; break; }
+        }
+        pdl_sync();
+        if (*s_stop) return;
+    }
+}
+
+// finalize one cell (library.cpp:493-517) and the two maxima (:405-407,513); returns the score (0: not emitted)
+__device__ __forceinline__ float q_finalize(const QJoinArgs &a, uint32_t g, uint32_t col, unsigned long long acc, float &perc, float &tr) {
+    const uint32_t my_k = a.kseq_q[g];
+    const uint32_t other_k = col < a.N ? a.kseq_b[col] : a.kseq_q[col - a.N];
+    const float threshold = 1.0f / (2.0f * (float) a.k);
+    const float score = finalize_cell(acc, my_k, other_k, threshold, perc, tr);
+    if (score > 0.0f) {
+        const uint32_t genome = col < a.N ? a.genome_b[col] : a.G1 - 1;
+        atomicMax(reinterpret_cast<uint32_t *>(a.MS) + (size_t) g * a.G1 + genome, __float_as_uint(score));    // non-negative: bit order = value order
+        atomicMax(reinterpret_cast<uint32_t *>(a.CM) + col, __float_as_uint(score));
+    }
+    return score;
+}
+
+__global__ __launch_bounds__(QJ_T) void k_q_join(QJoinArgs a) {
+    __shared__ uint32_t s_key[QJ_HT], s_first[QJ_HT];
+    __shared__ unsigned long long s_acc[QJ_HT];
+    __shared__ QDesc s_d[QJ_T];
+    __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
+    __shared__ uint32_t s_nkeys, s_stop, s_ncell;
+    __shared__ unsigned long long s_cbase;
+    const uint32_t g = blockIdx.x;
+    if (a.row_off[g] == a.row_off[g + 1]) {               // (uniform) no k-mer, no cell
+        if (threadIdx.x == 0) { a.row_cnt[g] = 0; a.row_base[g] = 0; }
+        return;
+    }
+    for (uint32_t i = threadIdx.x; i < QJ_HT; i += QJ_T) { s_key[i] = EMPTY_KEY; s_first[i] = 0xffffffffu; s_acc[i] = 0; }
+    if (threadIdx.x == 0) { s_nkeys = 0; s_stop = 0; s_ncell = 0; }
+    pdl_sync();
+    q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
+        uint32_t h = (col * 2654435761u) >> (32 - QJ_HT_BITS);
+        for (;;) {
+            const uint32_t k = *(volatile uint32_t *) &s_key[h];
+            if (k == col) break;
+            if (k == EMPTY_KEY) {
+                if (*(volatile uint32_t *) &s_nkeys >= QJ_LIMIT) return false;
+                const uint32_t old = atomicCAS(&s_key[h], EMPTY_KEY, col);
+                if (old == EMPTY_KEY) { atomicAdd(&s_nkeys, 1u); break; }
+                if (old == col) break;
+            }
+            h = (h + 1) & (QJ_HT - 1);
+        }
+        atomicAdd(&s_acc[h], packed);
+        atomicMin(&s_first[h], key);
+        return true;
+    });
+    if (s_stop) {                                         // (uniform: read after the walk's last barrier) more columns than the table holds
+        if (threadIdx.x == 0) {
+            const unsigned long long i = atomicAdd(a.n_overflow, 1ull);
+            a.overflow_rows[i] = g;
+            a.row_cnt[g] = 0; a.row_base[g] = 0;
+        }
+        return;
+    }
+    float sc[QJ_SLOTS], pc[QJ_SLOTS], tc[QJ_SLOTS];
+    uint32_t at[QJ_SLOTS];
+#pragma unroll
+    for (uint32_t s = 0; s < QJ_SLOTS; s++) {
+        const uint32_t i = s * QJ_T + threadIdx.x;
+        at[s] = Q_NONE; sc[s] = 0.f; pc[s] = 0.f; tc[s] = 0.f;
+        const uint32_t col = s_key[i];
+        if (col != EMPTY_KEY) {
+            sc[s] = q_finalize(a, g, col, s_acc[i], pc[s], tc[s]);
+            if (sc[s] > 0.0f) at[s] = atomicAdd(&s_ncell, 1u);
+        }
+    }
+    pdl_sync();
+    if (threadIdx.x == 0) {
+        s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
+        a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
+    }
+    pdl_sync();
+#pragma unroll
+    for (uint32_t s = 0; s < QJ_SLOTS; s++) {
+        if (at[s] == Q_NONE) continue;
+        const uint32_t i = s * QJ_T + threadIdx.x;
+        const uint64_t o = s_cbase + at[s];
+        a.st_score[o] = sc[s]; a.st_perc[o] = pc[s]; a.st_tr[o] = tc[s];
+        a.st_col[o] = s_key[i]; a.st_first[o] = s_first[i];
+    }
+}
+
+// The rows k_q_join handed on: the same row program with one dense table per workgroup in HBM (all zero / all-ones first
+// between rows: every touched entry is reset by the pass that emits it).  Launched only when a row did overflow; the tables are
+// allocated then, and cleared again whenever the column count they were laid out for is not this query's.
+__global__ __launch_bounds__(QJ_T) void k_q_join_hbm(QJoinArgs a) {
+    __shared__ QDesc s_d[QJ_T];
+    __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
+    __shared__ uint32_t s_stop, s_ntouch, s_ncell, s_emit;
+    __shared__ unsigned long long s_cbase;
+    const uint32_t n_cols = a.N + a.n;
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(a.hbm + (size_t) blockIdx.x * n_cols * 16);
+    uint32_t *first = reinterpret_cast<uint32_t *>(acc + n_cols);
+    uint32_t *touched = first + n_cols;
+    const uint32_t n_over = (uint32_t) *a.n_overflow;
+    for (uint32_t w = blockIdx.x; w < n_over; w += gridDim.x) {
+        const uint32_t g = a.overflow_rows[w];
+        if (threadIdx.x == 0) { s_stop = 0; s_ntouch = 0; s_ncell = 0; s_emit = 0; }
+        pdl_sync();
+        q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
+            const uint32_t old = atomicMin(&first[col], key);
+            if (old == 0xffffffffu) touched[atomicAdd(&s_ntouch, 1u)] = col;
+            atomicAdd(&acc[col], packed);
+            return true;
+        });
+        __threadfence();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        pdl_sync();
+        const uint32_t nt = s_ntouch;
+        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // count (the maxima are taken here, once per cell)
+            const uint32_t col = ld_agent(&touched[i]);
+            float p, t;
+            if (q_finalize(a, g, col, ld_agent(&acc[col]), p, t) > 0.0f) atomicAdd(&s_ncell, 1u);
+        }
+        pdl_sync();
+        if (threadIdx.x == 0) {
+            s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
+            a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
+        }
+        pdl_sync();
+        const float threshold = 1.0f / (2.0f * (float) a.k);
+        const uint32_t my_k = a.kseq_q[g];
+        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // write, and leave the entries clean
+            const uint32_t col = ld_agent(&touched[i]);
+            const unsigned long long v = ld_agent(&acc[col]);
+            const uint32_t key = ld_agent(&first[col]);
+            float p, t;
+            const float score = finalize_cell(v, my_k, col < a.N ? a.kseq_b[col] : a.kseq_q[col - a.N], threshold, p, t);
+            if (score > 0.0f) {
+                const uint64_t o = s_cbase + atomicAdd(&s_emit, 1u);
+                a.st_score[o] = score; a.st_perc[o] = p; a.st_tr[o] = t; a.st_col[o] = col; a.st_first[o] = key;
+            }
+            acc[col] = 0ull; first[col] = 0xffffffffu;
+        }
+        __threadfence();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        pdl_sync();
+    }
+}
+
+// the HBM tables of `slots` workgroups laid out for n_cols columns, in the state k_q_join_hbm leaves them: acc 0, first all ones
+__global__ __launch_bounds__(256) void k_q_hbm_clear(uint8_t *hbm, uint32_t n_cols, uint32_t slots) {
+    const uint64_t total = (uint64_t) n_cols * slots;
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t) gridDim.x * 256) {
+        const uint64_t w = i / n_cols, col = i - w * n_cols;
+        unsigned long long *acc = reinterpret_cast<unsigned long long *>(hbm + w * n_cols * 16);
+        acc[col] = 0ull;
+        reinterpret_cast<uint32_t *>(acc + n_cols)[col] = 0xffffffffu;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_q_rowids(uint32_t *ids, uint32_t base, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ids[i] = base + i;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+template <class KeyT>
+static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
+    QView<KeyT> v;
+    v.bkeys = c->keys_b.as<KeyT>(); v.brecpos = c->recpos.as<uint32_t>(); v.bvals = c->vals_b.as<uint32_t>(); v.post = c->post.as<uint2>();
+    v.U = (uint32_t) c->U; v.M = c->M;
+    v.qkeys = static_cast<const KeyT *>(qkeys); v.qrecpos = c->qb.recpos.as<uint32_t>(); v.qpost = c->qb.post.as<uint2>();
+    return v;
+}
+
+void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info) {
+    hipStream_t st = c->stream;
+    auto &q = c->qb;
+    const uint32_t N = c->N, G = c->G, G1 = G + 1, k = c->rp.k;
+    const uint64_t NC64 = (uint64_t) N + n;
+    if (NC64 >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu genes in the union exceed the 31-bit gene ids", (unsigned long long) NC64);
+    const uint32_t NC = (uint32_t) NC64;
+    const uint64_t r0 = offsets[0], Rq = offsets[n] - r0;
+    if (c->R + Rq >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the union need 64-bit stream positions");
+    if (c->max_kseq >= (1ull << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a base gene of %llu k-mers: queries need genes below 2^20 k-mers", (unsigned long long) c->max_kseq);
+    std::vector<uint64_t> h_off(n + 1), h_koff(n + 1);
+    std::vector<uint32_t> h_kseq(n);
+    uint64_t Mq = 0;
+    for (uint32_t g = 0; g < n; g++) {
+        const uint64_t len = offsets[g + 1] - offsets[g];
+        h_off[g] = offsets[g] - r0;
+        h_koff[g] = Mq;
+        h_kseq[g] = len >= k ? (uint32_t) std::min<uint64_t>(len - k + 1, 0xffffffffull) : 0u;
+        if (h_kseq[g] >= (1u << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query gene %u has %u k-mers: queries need genes below 2^20 k-mers", g, h_kseq[g]);
+        Mq += h_kseq[g];
+    }
+    h_off[n] = Rq; h_koff[n] = Mq;
+    if (Mq >= 0x7ffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu query k-mers exceed the 31-bit record positions", (unsigned long long) Mq);
+    // device time = the stretches of device work between the host's reads, each between an event pair
+    for (int i = 0; i < 6; i++) if (!q.ev[i]) PDL_HIP(hipEventCreate(&q.ev[i]));
+    int span = 0;
+    auto span_begin = [&]() { PDL_HIP(hipEventRecord(q.ev[2 * span], st)); };
+    auto span_end = [&]() { PDL_HIP(hipEventRecord(q.ev[2 * span + 1], st)); span++; };
+    span_begin();
+
+    // Q-alpha
+    q.ctl.alloc(Q_CTL_WORDS * sizeof(uint64_t));
+    unsigned long long *ctl = q.ctl.as<unsigned long long>();
+    PDL_HIP(hipMemsetAsync(ctl, 0, Q_CTL_WORDS * sizeof(uint64_t), st));
+    q.res.alloc(Rq); q.off.alloc((n + 1) * 8ull); q.koff.alloc((n + 1) * 8ull); q.kseq.alloc(n * 4ull);
+    if (Rq) PDL_HIP(hipMemcpyAsync(q.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.off.p, h_off.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.koff.p, h_koff.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
+    if (Rq) {
+        QAlphaArgs aa{};
+        aa.res = q.res.as<uint8_t>(); aa.n = Rq; aa.bad = ctl + 1;
+        for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
+        hipLaunchKernelGGL(k_q_alpha, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
+        PDL_HIP(hipGetLastError());
+    }
+
+    // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look below)
+    const void *qkeys = nullptr;
+    if (Mq) {
+        const size_t kb = c->key64 ? 8 : 4;
+        q.keys_a.alloc(Mq * kb); q.keys_b.alloc(Mq * kb); q.vals_a.alloc(Mq * 4); q.vals_b.alloc(Mq * 4);
+        q.recpos.alloc((Mq + 1) * 4); q.post.alloc(Mq * 8);
+        qkeys = pdl_query_dictionary(c, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, Mq, Rq, q.keys_a.p, q.keys_b.p,
+                                     q.vals_a.as<uint32_t>(), q.vals_b.as<uint32_t>(), q.recpos.as<uint32_t>(), q.post.as<uint2>(),
+                                     reinterpret_cast<uint64_t *>(ctl));
+        q.fold.alloc(sizeof(QFold)); q.desc.alloc(Mq * sizeof(QDesc)); q.gkey.alloc(Mq * 8); q.rec_sorted.alloc(Mq * 8);
+        q.row_lookups.alloc(n * 4ull); q.row_off.alloc((n + 1) * 4ull);
+        PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
+        QMatchOut mo{q.desc.as<QDesc>(), q.gkey.as<uint32_t>(), q.row_lookups.as<uint32_t>(), ctl};
+        const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
+        if (c->key64) {
+            const QView<uint64_t> v = q_view<uint64_t>(c, qkeys);
+            hipLaunchKernelGGL(k_q_fold<uint64_t>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
+            hipLaunchKernelGGL(k_q_match<uint64_t>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
+        } else {
+            const QView<uint32_t> v = q_view<uint32_t>(c, qkeys);
+            hipLaunchKernelGGL(k_q_fold<uint32_t>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
+            hipLaunchKernelGGL(k_q_match<uint32_t>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
+        }
+        PDL_HIP(hipGetLastError());
+        // each gene's records in rank order: a stable sort of the record indices by gene (the records are in (rank, gene) order)
+        uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
+        uint32_t *ix_in = q.rec_sorted.as<uint32_t>(), *ix_out = ix_in + Mq;
+        pdl_sort_pairs<uint32_t, uint32_t>(c, gk_in, gk_out, ix_in, ix_out, Mq, std::max<uint32_t>(1, bit_length64(n)), true,
+                                           reinterpret_cast<const uint64_t *>(ctl), 0, true);
+        hipLaunchKernelGGL(k_q_row_off, dim3((n + 1 + 255) / 256), dim3(256), 0, st, gk_out, (const unsigned long long *) ctl, n,
+                           q.row_off.as<uint32_t>(), (const uint32_t *) q.row_lookups.as<uint32_t>(), NC, QJ_LIMIT, ctl + 4, ctl + 9);
+        PDL_HIP(hipGetLastError());
+        q.rec_sorted_at = ix_out;
+    }
+    uint64_t h_ctl[10] = {};
+    span_end();
+    {
+        PinRead rd(c);
+        const uint64_t *pc = rd.add<uint64_t>(ctl, 10);
+        rd.sync();
+        memcpy(h_ctl, pc, sizeof(h_ctl));
+    }
+    span_begin();
+    if (h_ctl[1]) {
+        const uint32_t b = 256u - (uint32_t) h_ctl[1];
+        PDL_FAIL(PDL_ERR_UNSUPPORTED, "query byte 0x%02x ('%c') is not in the base's alphabet: the union would rank k-mers differently", b,
+                 (b >= 32 && b < 127) ? (char) b : '?');
+    }
+    const uint64_t Uq = h_ctl[0], cost = h_ctl[2], matched = h_ctl[3], bound = h_ctl[4], may_overflow = h_ctl[9];
+    if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);
+
+    // Q-join, Q-order
+    q.MS.alloc((size_t) n * G1 * 4); q.CM.alloc((size_t) NC * 4);
+    PDL_HIP(hipMemsetAsync(q.MS.p, 0, (size_t) n * G1 * 4, st));
+    PDL_HIP(hipMemsetAsync(q.CM.p, 0, (size_t) NC * 4, st));
+    uint64_t Z = 0;
+    if (Uq) {
+        q.row_base.alloc(n * 4ull); q.row_cnt.alloc(n * 4ull); q.fin_off.alloc((n + 1) * 4ull); q.rowid.alloc(n * 4ull); q.overflow.alloc(n * 4ull);
+        q.st.alloc(std::max<uint64_t>(bound, 1) * 20); q.cells.alloc(std::max<uint64_t>(bound, 1) * 20);
+        hipLaunchKernelGGL(k_q_rowids, dim3((n + 255) / 256), dim3(256), 0, st, q.rowid.as<uint32_t>(), N, n);
+        const uint64_t cap = std::max<uint64_t>(bound, 1);
+        QJoinArgs a{};
+        a.post = c->post.as<uint2>(); a.qpost = q.post.as<uint2>(); a.desc = q.desc.as<QDesc>();
+        a.rec_sorted = q.rec_sorted_at; a.row_off = q.row_off.as<uint32_t>();
+        a.kseq_b = c->kseq_len.as<uint32_t>(); a.kseq_q = q.kseq.as<uint32_t>(); a.genome_b = c->d_gen;
+        a.N = N; a.n = n; a.G1 = G1; a.k = k;
+        a.MS = q.MS.as<float>(); a.CM = q.CM.as<float>();
+        a.row_base = q.row_base.as<uint32_t>(); a.row_cnt = q.row_cnt.as<uint32_t>();
+        float *stf = q.st.as<float>();
+        a.st_score = stf; a.st_perc = stf + cap; a.st_tr = stf + 2 * cap;
+        a.st_col = reinterpret_cast<uint32_t *>(stf + 3 * cap); a.st_first = reinterpret_cast<uint32_t *>(stf + 4 * cap);
+        a.cell_cursor = ctl + 6; a.overflow_rows = q.overflow.as<uint32_t>(); a.n_overflow = ctl + 5;
+        hipLaunchKernelGGL(k_q_join, dim3(n), dim3(QJ_T), 0, st, a);
+        PDL_HIP(hipGetLastError());
+        if (may_overflow) {      // some row has more lookups than the LDS table holds keys: did it leave the table?
+            uint64_t n_over = 0;
+            span_end();
+            {
+                PinRead rd(c);
+                const uint64_t *pc = rd.add<uint64_t>(ctl + 5, 1);
+                rd.sync();
+                n_over = pc[0];
+            }
+            span_begin();
+            if (n_over) {
+                // tables for min(overflow rows, QH_WG) workgroups, laid out for THIS query's column count: tables cleaned for another
+                // count (another query) are cleared again — their layout is that of the other count
+                const uint32_t W = (uint32_t) std::min<uint64_t>(n_over, QH_WG);
+                if (!q.hbm_clean || q.hbm_cols != NC || q.hbm_slots < W) {
+                    q.hbm.alloc((size_t) W * NC * 16);
+                    hipLaunchKernelGGL(k_q_hbm_clear, dim3((uint32_t) std::min<uint64_t>(((uint64_t) W * NC + 255) / 256, 4096)), dim3(256), 0, st,
+                                       q.hbm.as<uint8_t>(), NC, W);
+                    q.hbm_cols = NC; q.hbm_slots = W; q.hbm_clean = true;
+                }
+                a.hbm = q.hbm.as<uint8_t>();
+                hipLaunchKernelGGL(k_q_join_hbm, dim3(W), dim3(QJ_T), 0, st, a);
+                PDL_HIP(hipGetLastError());
+            }
+        }
+        scan_and_apply(c, n, RowCntFlag{q.row_cnt.as<uint32_t>(), nullptr}, FinOffApply{q.fin_off.as<uint32_t>()}, reinterpret_cast<uint64_t *>(ctl + 7));
+        OrderArgs o{};
+        o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = q.fin_off.as<uint32_t>(); o.task_rows = q.rowid.as<uint32_t>();
+        o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
+        float *cf = q.cells.as<float>();
+        o.c_score = cf; o.c_perc = cf + cap; o.c_tr = cf + 2 * cap;
+        o.c_row = reinterpret_cast<int32_t *>(cf + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cf + 4 * cap);
+        o.n_rows = n; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = NC < (1u << 22) ? 1u : 0u;
+        o.wide_rows = reinterpret_cast<uint32_t *>(ctl + 8);
+        const uint32_t cus = c->cus > 0 ? (uint32_t) c->cus : 256u;
+        hipLaunchKernelGGL(k_order_rows_wave, dim3((n + 3) / 4), dim3(256), 0, st, o);
+        hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n, cus * 8)), dim3(ORDER_THREADS), 0, st, o);
+        PDL_HIP(hipGetLastError());
+        span_end();
+        uint64_t h2[3];
+        {
+            PinRead rd(c);
+            const uint64_t *pc = rd.add<uint64_t>(ctl + 5, 3);
+            rd.sync();
+            memcpy(h2, pc, sizeof(h2));
+        }
+        Z = h2[2];
+        if (Z > bound || h2[1] > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) h2[1], (unsigned long long) bound);
+    } else {
+        span_end();
+    }
+
+    // Q-copy: the block as library.cpp:542-603 marshals it
+    pdl_scores r{};
+    r.scoresCount = (uint32_t) Z; r.rows = n; r.genomes = G1; r.sequences = NC;
+    auto xm = [](size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) throw std::bad_alloc(); return p; };
+    try {
+        r.scores = (float *) xm(Z * 4); r.percs = (float *) xm(Z * 4); r.tr_percs = (float *) xm(Z * 4);
+        r.row = (int32_t *) xm(Z * 4); r.column = (int32_t *) xm(Z * 4);
+        r.first_seq_genome = (int32_t *) xm(Z * 4); r.second_seq_genome = (int32_t *) xm(Z * 4);
+        r.max_genome_score = (float *) xm((size_t) n * G1 * 4); r.max_genome_score_col = (float *) xm((size_t) NC * 4);
+        r.scoresMaxMappings = (int32_t *) xm((size_t) NC * 4);
+        if (Z) {
+            const uint64_t cap = std::max<uint64_t>(bound, 1);
+            const float *cf = q.cells.as<float>();
+            void *dst[5] = {r.scores, r.percs, r.tr_percs, r.row, r.column};
+            for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(dst[i], cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
+        }
+        PDL_HIP(hipMemcpyAsync(r.max_genome_score, q.MS.p, (size_t) n * G1 * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(r.max_genome_score_col, q.CM.p, (size_t) NC * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipStreamSynchronize(st));
+    } catch (...) { pdl_free_scores(&r); throw; }
+    for (uint64_t i = 0; i < Z; i++) {
+        r.first_seq_genome[i] = (int32_t) G;
+        const uint32_t col = (uint32_t) r.column[i];
+        r.second_seq_genome[i] = col < N ? (int32_t) c->h_genome_of[col] : (int32_t) G;
+    }
+    for (uint32_t i = 0; i < N; i++) r.scoresMaxMappings[i] = 0x7fffffff;
+    for (uint32_t g = 0; g < n; g++) r.scoresMaxMappings[N + g] = (int32_t) g;
+    *out = r;
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->residues = Rq; info->kmer_occurrences = Mq; info->records = Uq; info->matched_records = matched; info->genome_cost = cost;
+        for (int i = 0; i < span; i++) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, q.ev[2 * i], q.ev[2 * i + 1]) == hipSuccess) info->device_ms += ms;
+        }
+    }
+}

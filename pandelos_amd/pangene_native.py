@@ -136,6 +136,31 @@ class PangeneNative:
         ignored step_size in the reference (library.cpp:454)."""
         s = _lib.PdlScores()
         self._check(self._lib.pdl_compute_scores(self._ctx, int(genome), C.byref(s)))
+        return self._take_scores(s)
+
+    def query_scores(self, residues, offsets) -> Scores:
+        """One new genome against this dictionary, without a rebuild (``pdl_query_scores``): the Scores block of genome
+        G = ``cost.genomes`` in the union run, with these genes appended as ids N..N+n-1.  ``last_query_info`` then holds
+        the call's sizes, "Genome G cost" (``genome_cost``) and device time as a dict."""
+        res = np.ascontiguousarray(residues, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or len(off) < 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n_query + 1 entries")
+        s, info = _lib.PdlScores(), _lib.PdlQueryInfo()
+        self._check(self._lib.pdl_query_scores(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data,
+                                               len(off) - 1, C.byref(s), C.byref(info)))
+        self.last_query_info = info.as_dict()
+        return self._take_scores(s)
+
+    def query_idata(self, data: PangeneIData) -> Scores:
+        """``query_scores`` for the genes of a ``PangeneIData`` that holds exactly one genome."""
+        residues, offsets, genome_of = data.flatten()
+        n_genomes = len(np.unique(genome_of))
+        if n_genomes != 1:
+            raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
+        return self.query_scores(residues, offsets)
+
+    def _take_scores(self, s) -> Scores:
         try:
             z, rows, g, n = s.scoresCount, s.rows, s.genomes, s.sequences
             out = Scores(
