@@ -108,8 +108,8 @@ void pdl_run_bbh_all(pdl_ctx *c) {
     int32_t *src1 = c->e_src.as<int32_t>(), *dst1 = c->e_dst.as<int32_t>(); float *sc1 = c->e_score.as<float>();
     int32_t *src2 = src1 + 2 * Z, *dst2 = dst1 + 2 * Z; float *sc2 = sc1 + 2 * Z;
     uint64_t *d_scal = c->scalars.as<uint64_t>();
-    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, src1, dst1, sc1, pre1, 2}, d_scal + 13);
-    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, src2, dst2, sc2, pre2, 1}, d_scal + 14);
+    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, src1, dst1, sc1, pre1, 2}, d_scal + PDL_CTL_EDGES_1);
+    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, src2, dst2, sc2, pre2, 1}, d_scal + PDL_CTL_EDGES_2);
     // cells of each kind before every genome block: prefix at the block's first cell (the totals close the lists)
     uint64_t tot[2];
     std::vector<uint32_t> h1(S + 1), h2(S + 1);
@@ -119,10 +119,10 @@ void pdl_run_bbh_all(pdl_ctx *c) {
     hipLaunchKernelGGL(k_pick_prefixes, dim3((S + 1 + 255) / 256), dim3(256), 0, st, pre1, pre2, d_at, S + 1, (uint32_t) Z, d_pick);
     {
         PinRead rd(c);
-        const uint64_t *pt = rd.add<uint64_t>(d_scal + 13, 2);
+        const uint64_t *pt = rd.add<uint64_t>(d_scal + PDL_CTL_EDGES_1, PDL_CTL_EDGES_2 - PDL_CTL_EDGES_1 + 1);
         const uint32_t *pp = rd.add<uint32_t>(d_pick, 2 * ((size_t) S + 1));
         rd.sync();
-        tot[0] = pt[0]; tot[1] = pt[1];
+        tot[0] = pt[0]; tot[1] = pt[PDL_CTL_EDGES_2 - PDL_CTL_EDGES_1];
         for (uint32_t i = 0; i <= S; i++) {
             const bool past = c->h_cell_off[i] >= Z;
             h1[i] = past ? (uint32_t) tot[0] : pp[i];

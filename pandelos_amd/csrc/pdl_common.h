@@ -35,8 +35,73 @@ __device__ __forceinline__ void pdl_sync() {
 }
 #endif
 
-// layout of the control block (pdl_ctx::scalars, u64 words): scalars | residue histogram | per-genome cost
-constexpr size_t PDL_CTL_HIST = 16, PDL_CTL_GCOST = 16 + 256;
+// ---- layout of the control block (pdl_ctx::scalars, u64 words): totals [16] | residue histogram [256] | per-genome cost ------
+// Every use of a word is queued on the context's one stream, so two lives of a word cannot overlap as long as the later one
+// starts behind the last kernel or read of the earlier one: each alias below says which stage that is.  A scan STORES its
+// total (no clearing needed); the atomically added words are cleared by the stage that is about to add to them.
+enum : size_t {
+    PDL_CTL_RECORDS = 0,        // U: total of the dedup scan (K-rle); a multi-GPU finish uploads the gathered dictionary's count here
+    PDL_CTL_FREE_1 = 1,         // no stage uses it; cleared / uploaded with its neighbours
+    PDL_CTL_RANGES = 2,         // ranges built (total of the tile counts); sender-built lists: the tuples a rank received
+    PDL_CTL_BAD_OFFSETS = 3,    // K-len: extra total of its apply functor (offsets that do not ascend)
+    PDL_CTL_KSEQ_SUM = 4,       // k_genome_cost: sum of the genes' k-mer counts ...
+    PDL_CTL_KMERS = 5,          // M: total of K-len's scan
+    PDL_CTL_EMITTED = 6,        // K-order: emitted cells (total of the row-count scan)
+    PDL_CTL_KSEQ_MAX = 7,       // ... their maximum ...
+    PDL_CTL_KSEQ_NMIN = 8,      // ... and ~minimum (a max of complements, so that it starts at zero like the rest)
+    PDL_CTL_MIRRORED = 9,       // K-order: mirrored cells (total of the mirror-count scan)
+    PDL_CTL_COUNTERS = 10,      // GroupTileArgs::counters [4] of the range build:
+    PDL_CTL_SHARED = 10,        //   [0] records in groups of two or more (U')
+    PDL_CTL_GROUPS = 11,        //   [1] such groups
+    PDL_CTL_OWN_COST = 12,      //   [2] lookups of this context's genes ("Total cost")
+    PDL_CTL_REPEATS = 13,       //   [3] records whose k-mer repeats inside its gene
+    PDL_CTL_SCAN_TOTAL = 15,    // total of every radix pass of pdl_sort_pairs: the sort runs in the middle of the range build, so
+                                // no word the build keeps until its read at the end may live here
+    PDL_CTL_LAST = 15,
+
+    // second lives.  The range build's counters (10-13) are read by the host at the end of stage_ranges_and_costs /
+    // pdl_run_dist_ranges; everything below that shares them runs before the build clears them or after that read.
+    PDL_CTL_SLICE_COUNTERS = 12,// [4], 12-15: dist_slice_pipeline's COUNT pass (only its per-genome sums are wanted); behind the slice's
+                                // sort, before the finish clears MIRRORED..LAST
+    PDL_CTL_OUTBOX_TOTAL = 12,  // total of the outbox scan (pdl_run_dist_score_begin): scoring, the build has been read
+    PDL_CTL_EDGES_1 = 13,       // K-bbh: totals of its two edge scans; runs on a scored context
+    PDL_CTL_EDGES_2 = 14,
+    PDL_CTL_LAZY_KSEQ_SUM = 13, // pdl_ensure_costs: where k_genome_cost's three statistics go when only its per-genome sums are
+    PDL_CTL_LAZY_KSEQ_MAX = 14, //   wanted (max, ~min: 14, 15); after a build, with no sort in flight
+    PDL_CTL_SELECT_TOTAL = 15,  // total of the multi-GPU selection scan, between K-rank and the slice's sort
+
+    PDL_CTL_HIST = 16,          // residue histogram [256]
+    PDL_CTL_GCOST = 16 + 256,   // per-genome cost [G] (+ [G] lookups above the diagonal, multi-GPU)
+};
+
+// ---- layout of pdl_ctx::join_ctr (u32 words): cursors and counters of one scoring pass, cleared by score_join ---------------
+// A tier draws rows through its cursor and lists the rows it hands on; the count of that list is the next tier's work size.
+enum : uint32_t {
+    PDL_JC_CURSOR_T1 = 0,       // cursor of tier 1
+    PDL_JC_ROWS_T2 = 1,         // rows tier 1 handed to tier 2
+    PDL_JC_CURSOR_T2 = 2,
+    PDL_JC_ROWS_T3 = 3,         // rows tier 2 handed to tier 3 (a dataset of very long genes: all rows, uploaded)
+    PDL_JC_CELLS = 4,           // u64 (words 4-5): staging cells reserved
+    PDL_JC_ERRORS = 6,          // internal consistency violations (join, inbox filing)
+    PDL_JC_CURSOR_T3 = 7,
+    PDL_JC_WIDE_ROWS = 9,       // rows of more than 256 cells seen by K-order
+    PDL_JC_RELOADS = 10,        // entries of the put-aside lists that had to be loaded again
+    PDL_JC_CURSOR_T0 = 11,      // cursor of tier 0 (the partition tier)
+    PDL_JC_ROWS_T0B = 12,       // rows it handed to its second form
+    PDL_JC_CURSOR_T0B = 13,
+    PDL_JC_ROWS_T1 = 14,        // rows the second form handed to tier 1
+    PDL_JC_WORDS = 16,          // (whole 16-byte words: cleared as uint4)
+};
+// What k_gather_u32 appends to the gathered cell offsets (fin_off -> task_off) for the one read after K-order.  Words 0-7 and
+// RELOADS sit where join_ctr has them, so one reader (JoinCounters) serves this tail and a direct read of join_ctr.
+enum : uint32_t {
+    PDL_JT_CTR_WORDS = 8,       // join_ctr[0..8) as they are
+    PDL_JT_EMITTED = 8,         // u64 (words 8-9): scalars[PDL_CTL_EMITTED]
+    PDL_JT_RELOADS = PDL_JC_RELOADS,
+    PDL_JT_ROWS_T1 = 11,        // join_ctr[PDL_JC_ROWS_T1]
+    PDL_JT_WORDS = 12,
+};
+static_assert(PDL_JC_ROWS_T1 < PDL_JC_WORDS && PDL_JC_RELOADS < PDL_JT_WORDS && PDL_JC_CURSOR_T3 + 1 == PDL_JT_CTR_WORDS, "join counter layout");
 
 // ---- error plumbing -------------------------------------------------------------------------
 struct pdl_error {
@@ -181,7 +246,7 @@ struct pdl_ctx {
     bool reshard_pending = false;         // pdl_set_genome_shard named genomes the range lists on the device do not cover: they are built before the next scoring pass
     bool opt_onepass_scan = false;        // scans in one launch (decoupled look-back) instead of three: measured 3-10 % slower per scan on MI355X, kept as an option
     DevBuf scratch;       // transient buffers of the range build
-    DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*)
+    DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*, above)
 
     // genome / task layout (host and device)
     std::vector<uint32_t> h_genome_of;
@@ -215,7 +280,7 @@ struct pdl_ctx {
     uint64_t st_cap = 0;
     DevBuf c_score, c_perc, c_tr, c_row, c_col;          // final cells, task order + emission order
     uint64_t Z = 0;
-    DevBuf join_ctr;      // u32 [8] cursors/counters of the join
+    DevBuf join_ctr;      // u32 [PDL_JC_WORDS] cursors / counters of the join (PDL_JC_*)
     DevBuf overflow_rows; // u32 [n_task_rows]
     DevBuf gene_info;             // uint4 [N] {k-mers, genome, task position, shard-local genome}: one load per candidate column in finalize
     DevBuf join_defer;            // filter tiers of the join: per workgroup, the first sightings put aside
@@ -227,7 +292,7 @@ struct pdl_ctx {
     std::vector<uint32_t> h_fin;
     bool tasks_ready = false;  // task layout uploaded for the current shard
     DevBuf scratch2;      // small transient device scratch (interval histogram, per-genome lookups)
-    DevBuf task_off;      // u32 [shard+1] task offsets | gathered cell offsets + 8 counters + cell total
+    DevBuf task_off;      // u32 [shard+1] task offsets | gathered cell offsets + the counters behind them (PDL_JT_*)
     int cus = 0;
     uint32_t occ_tier1[5] = {0, 0, 0, 0, 0};
     uint32_t occ_tier0 = 0, occ_tier0b = 0;
@@ -441,6 +506,15 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t *d_u);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
 inline uint2 *pdl_postings(const pdl_ctx *c) { return c->post_ext ? c->post_ext : c->post.as<uint2>(); }
+
+// compute units of the context's device (looked up once; 256 where the runtime does not say)
+inline int pdl_cus(pdl_ctx *c) {
+    if (c->cus <= 0) {
+        hipDeviceProp_t prop;
+        c->cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    return c->cus;
+}
 
 // event helpers
 enum { EV_HIST, EV_RANK, EV_SORT1, EV_DICT, EV_SORT2, EV_RANGES, EV_JOIN, EV_JOIN_OVF, EV_ORDER, EV_PRE_TOTAL, EV_SCORE_TOTAL,

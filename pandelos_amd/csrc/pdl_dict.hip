@@ -1116,18 +1116,25 @@ __global__ __launch_bounds__(256) void k_genome_cost(const unsigned long long *_
     if (threadIdx.x == 0 && s_sum) { atomicAdd(sum_kseq, s_sum); atomicMax(max_kseq, s_max); atomicMax(min_kseq, ~s_min); }   // min kept as a max of complements: zero-initialised like the rest
 }
 
+// K-cost: cost[] summed per genome into scalars[PDL_CTL_GCOST ..]; the k-mer statistics of the genes it adds up on the way
+// go to scalars[w_sum] (sum), scalars[w_max] (max) and the word behind that (~min)
+static void launch_genome_cost(pdl_ctx *c, size_t w_sum, size_t w_max) {
+    static_assert(PDL_CTL_KSEQ_NMIN == PDL_CTL_KSEQ_MAX + 1 && PDL_CTL_LAZY_KSEQ_MAX + 1 <= PDL_CTL_LAST, "~min sits behind max");
+    unsigned long long *d_scal = c->scalars.as<unsigned long long>();
+    hipLaunchKernelGGL(k_genome_cost, dim3(std::min<uint32_t>((c->N + 255) / 256, 128)), dim3(256), 0, c->stream, c->cost.as<unsigned long long>(),
+                       c->kseq_len.as<uint32_t>(), c->d_gen, c->N, d_scal + PDL_CTL_GCOST, d_scal + w_sum, d_scal + w_max, d_scal + w_max + 1);
+    PDL_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------------------------
-// Host side of the stages.  Control block words (c->scalars, u64): 0 U | 1 groups of any size | 2 ranges built |
-// 3 bad-offsets flag | 4 sum kseq | 5 M | 6 emitted cells | 7 max kseq | 8 ~min kseq | 9 mirrored cells |
-// 10 U' | 11 shared groups | 12 lookups of this context's genes | 13 records whose k-mer repeats inside its gene | 15 sort scratch | PDL_CTL_HIST.. histogram | PDL_CTL_GCOST.. per-genome cost
+// Host side of the stages.  The words of the control block (c->scalars) are declared in pdl_common.h (PDL_CTL_*).
 // ------------------------------------------------------------------------------------------------
 
 // K-hist + K-len + the rank table; leaves M, the rank parameters and the key width in the context.
 static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complexity) {
     hipStream_t st = c->stream;
     if (kvalue <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
-    // control block: scalars[16] | residue histogram[256] | per-genome cost[G] (+ [G] lookups above the diagonal, multi-GPU)
-    // — one allocation, one clearing fill, one device->host copy whenever the host looks
+    // control block (PDL_CTL_*) — one allocation, one clearing fill, one device->host copy whenever the host looks
     // (device input whose genome ids are still on their way to the host: G is not known yet, at most N)
     const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) (c->layout_deferred ? c->N : c->G);
     c->scalars.alloc(ctl_words * sizeof(uint64_t));
@@ -1141,7 +1148,7 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     c->cost.alloc((size_t) c->N * sizeof(uint64_t));
     scan_and_apply(c, c->N, KseqFlag{c->d_off, (uint32_t) kvalue},
                    KseqApply{c->kseq_len.as<uint32_t>(), c->kmer_off.as<uint64_t>(), c->cost.as<unsigned long long>(), c->d_off, c->R,
-                             reinterpret_cast<unsigned long long *>(d_scal + 3)}, d_scal + 5, c->kmer_off.as<uint64_t>() + c->N);
+                             reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_BAD_OFFSETS)}, d_scal + PDL_CTL_KMERS, c->kmer_off.as<uint64_t>() + c->N);
     if (c->layout_deferred) pdl_input_arrived(c);        // offsets[0] = 0 and offsets[N] = R checked before anything indexes residues
     if (c->R) {
         uint32_t blocks = (uint32_t) std::min<uint64_t>((c->R / 64 + HIST_THREADS - 1) / HIST_THREADS + 1, 2048);
@@ -1156,7 +1163,7 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
         ev_end(c, EV_HIST);
         rd.sync();
         memcpy(counters, pc + PDL_CTL_HIST, sizeof(counters));
-        M = pc[5]; bad = pc[3];
+        M = pc[PDL_CTL_KMERS]; bad = pc[PDL_CTL_BAD_OFFSETS];
     }
     if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "offsets must ascend from 0 to the residue count (%llu)", (unsigned long long) c->R);
     rank_init_host(c->rp, counters, kvalue);
@@ -1194,7 +1201,7 @@ static void stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shif
 }
 
 // K-sort + K-rle over the first m elements of (keys_in, vals_in): records into c->post / recpos.
-// d_scal[0] receives the record count.
+// scalars[PDL_CTL_RECORDS] receives the record count.
 template <class KeyT>
 static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint64_t m) {
     uint64_t *d_scal = c->scalars.as<uint64_t>();
@@ -1210,7 +1217,7 @@ static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint
     c->recpos.alloc((m + 1) * sizeof(uint32_t));
     c->post.alloc(m * sizeof(uint2));                           // U <= m records (sized before U is known)
     scan_and_apply(c, m, RecHead<KeyT>{skeys, svals},
-                   RecScatter<KeyT>{skeys, svals, m, c->recpos.as<uint32_t>(), c->post.as<uint2>()}, d_scal + 0);
+                   RecScatter<KeyT>{skeys, svals, m, c->recpos.as<uint32_t>(), c->post.as<uint2>()}, d_scal + PDL_CTL_RECORDS);
 }
 
 // Launch helpers of k_group_waves.  group_tiles_plan sizes the grid and the scratch: tile_sums[tiles] | th_first[tiles] |
@@ -1218,13 +1225,7 @@ static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint
 static uint32_t group_tiles_plan(pdl_ctx *c, GroupTileArgs &a) {
     const uint64_t tiles = (a.n_bound + GW_TILE - 1) / GW_TILE;
     if (tiles > 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "dictionary of %llu records exceeds the grid limit", (unsigned long long) a.n_bound);
-    int cus = c->cus;
-    if (cus <= 0) {
-        cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
-        c->cus = cus;
-    }
+    const int cus = pdl_cus(c);
     a.n_blocks = (uint32_t) ((tiles + PDL_WAVE - 1) / PDL_WAVE);
     const uint32_t grid = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((tiles + GW_WAVES - 1) / GW_WAVES, (uint64_t) cus * 8));
     c->scan_tmp.alloc(((size_t) tiles * 3 + a.n_blocks + 1) * sizeof(uint32_t));
@@ -1240,18 +1241,18 @@ static void launch_group_tiles(pdl_ctx *c, const GroupTileArgs &a, uint32_t grid
 }
 
 // K-groups + K-ranges + K-cost over the dictionary (postings with head bits; `bound` records at most, the count is at
-// d_scal[0]).  mode 0: whole groups for the shard's genes | 1: upper ranges, every gene | 2: upper ranges, the shard's genes.
+// scalars[PDL_CTL_RECORDS]).  mode 0: whole groups for the shard's genes | 1: upper ranges, every gene | 2: upper ranges, the shard's genes.
 static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool only_complexity) {
     hipStream_t st = c->stream;
     c->costs_ready = true; c->ranges8 = nullptr;
     uint64_t *d_scal = c->scalars.as<uint64_t>();
-    const uint64_t *d_u = d_scal + 0;
+    const uint64_t *d_u = d_scal + PDL_CTL_RECORDS;
     uint2 *post = pdl_postings(c);
     GroupTileArgs ga{};
     ga.post = post; ga.n_bound = bound; ga.d_n = d_u;
     const uint32_t grid = group_tiles_plan(c, ga);
     ga.cost = c->cost.as<unsigned long long>();
-    ga.counters = reinterpret_cast<unsigned long long *>(d_scal + 10);
+    ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
     ga.genome_of = c->d_gen; ga.n_genomes = c->G;
     hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, st, post, c->post_ext ? (uint32_t *) nullptr : c->recpos.as<uint32_t>(), d_u);
     if (only_complexity) {                   // (cost[] was zeroed by K-len's apply, the counters with the control block)
@@ -1318,7 +1319,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
         // to put them back when the ranges are built again for another shard of genomes (pdl_run_reshard)
         c->head_bits.alloc(((bound + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
         ga.head_bits = c->head_bits.as<unsigned long long>();
-        const uint64_t *d_us = d_scal + 2;       // ranges built = the total of the tile counts
+        const uint64_t *d_us = d_scal + PDL_CTL_RANGES;       // ranges built = the total of the tile counts
         // single-GPU build with packed ranges: the tuples are filed by the low byte of their gene by the kernel that makes
         // them (the first pass of the gene sort without a trip through HBM in between)
         const bool fused = mode == 1 && packed;
@@ -1331,7 +1332,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             ga.tile_sums = offs + table; ga.th_first = ga.tile_sums + tiles; ga.th_last = ga.th_first + tiles; ga.chunk_sums = nullptr;
             const uint32_t grid4 = std::max<uint32_t>(1, std::min<uint32_t>(n_tiles4, (uint32_t) c->cus * 8));
             hipLaunchKernelGGL(k_range_count_hist, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
-            pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + 2);
+            pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + PDL_CTL_RANGES);
             hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, k2b, pay_b);
             PDL_HIP(hipGetLastError());
         } else {
@@ -1343,7 +1344,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             PDL_HIP(hipGetLastError());
         }
         hipLaunchKernelGGL(k_tile_prefix, dim3((ga.n_blocks + 3) / 4), dim3(256), 0, st, ga.tile_sums, ga.d_n, ga.n_bound, ga.chunk_sums, ga.n_blocks);
-        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + 2, (uint64_t *) nullptr);
+        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + PDL_CTL_RANGES, (uint64_t *) nullptr);
         if (exact) {                         // the shard's range count, then buffers of that size
             if (!c->tasks_ready) pdl_prepare_tasks(c);       // host work + small uploads while the device counts
             PinRead rd(c);
@@ -1390,14 +1391,9 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
     }
 
     // K-cost
-    unsigned long long *d_gcost = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);
-    hipLaunchKernelGGL(k_genome_cost, dim3(std::min<uint32_t>((c->N + 255) / 256, 128)), dim3(256), 0, st, c->cost.as<unsigned long long>(),
-                       c->kseq_len.as<uint32_t>(), c->d_gen, c->N, d_gcost,
-                       reinterpret_cast<unsigned long long *>(d_scal + 4), reinterpret_cast<unsigned long long *>(d_scal + 7),
-                       reinterpret_cast<unsigned long long *>(d_scal + 8));
-    PDL_HIP(hipGetLastError());
+    launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);
 
-    uint64_t tail[12] = {0}, tail_own = 0, tail_rep = 0;
+    uint64_t own_cost = 0;
     {
         PinRead rd(c);                       // one copy: the whole control block
         const uint64_t *pt = rd.add<uint64_t>(d_scal, PDL_CTL_GCOST + (size_t) c->G);
@@ -1405,19 +1401,18 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
         rd.sync();
         lookback_check(c, lbe);
         c->h_genome_cost.assign(pt + PDL_CTL_GCOST, pt + PDL_CTL_GCOST + c->G);     // (a shard, one rank of several: its own genomes only)
-        memcpy(tail, pt, sizeof(tail));
-        tail_own = pt[12]; tail_rep = pt[13];
+        c->U = pt[PDL_CTL_RECORDS];
+        c->Ushared = pt[PDL_CTL_SHARED];
+        c->Urepeat = pt[PDL_CTL_REPEATS];
+        c->NG = pt[PDL_CTL_GROUPS];
+        c->sum_kseq = pt[PDL_CTL_KSEQ_SUM];
+        c->max_kseq = pt[PDL_CTL_KSEQ_MAX];
+        c->min_kseq = pt[PDL_CTL_KSEQ_NMIN] == 0 ? 1 : ~pt[PDL_CTL_KSEQ_NMIN];
+        own_cost = pt[PDL_CTL_OWN_COST];
     }
-    c->U = tail[0];
-    c->Ushared = tail[10];
-    c->Urepeat = tail_rep;
-    c->NG = tail[11];
-    c->sum_kseq = tail[4];
-    c->max_kseq = tail[7];
-    c->min_kseq = tail[8] == 0 ? 1 : ~tail[8];
     c->P = 0;
     if (c->costs_ready) for (uint64_t v : c->h_genome_cost) c->P += v;
-    else c->P = tail_own;                     // packed ranges: "Total cost" straight from the WRITE pass; per-gene / per-genome costs on demand
+    else c->P = own_cost;                     // packed ranges: "Total cost" straight from the WRITE pass; per-gene / per-genome costs on demand
 }
 
 // ---- the ranges again, for another shard of genomes, on the dictionary that is there ---------------------------------------------
@@ -1438,14 +1433,14 @@ void pdl_run_reshard(pdl_ctx *c) {
     const uint32_t n = (uint32_t) c->U;
     ev_begin(c, EV_PRE_TOTAL);
     hipLaunchKernelGGL(k_restore_heads, dim3((n + 255) / 256), dim3(256), 0, st, c->post.as<uint2>(), c->head_bits.as<unsigned long long>(), n);
-    PDL_HIP(hipMemsetAsync(d_scal + 2, 0, sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + 10, 0, 6 * sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_RANGES, 0, sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_COUNTERS, 0, (PDL_CTL_LAST - PDL_CTL_COUNTERS + 1) * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), st));
     // (k_genome_cost adds the k-mer statistics of all genes up once more: they are taken from the first build)
     const uint64_t sum_kseq = c->sum_kseq, max_kseq = c->max_kseq, min_kseq = c->min_kseq;
-    PDL_HIP(hipMemsetAsync(d_scal + 4, 0, sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + 7, 0, 2 * sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_SUM, 0, sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_MAX, 0, (PDL_CTL_KSEQ_NMIN - PDL_CTL_KSEQ_MAX + 1) * sizeof(uint64_t), st));
     c->dict_shard = c->shard;
     c->tasks_ready = false;
     ev_begin(c, EV_DICT); ev_end(c, EV_DICT);
@@ -1469,11 +1464,7 @@ void pdl_ensure_costs(pdl_ctx *c) {
     hipLaunchKernelGGL(k_gene_costs_lazy, dim3((n + 255) / 256), dim3(256), 0, st, pdl_postings(c), c->head_bits.as<unsigned long long>(), n,
                        c->cost.as<unsigned long long>());
     // per genome (the kseq statistics it also adds up go to scratch words)
-    hipLaunchKernelGGL(k_genome_cost, dim3(std::min<uint32_t>((c->N + 255) / 256, 128)), dim3(256), 0, st, c->cost.as<unsigned long long>(),
-                       c->kseq_len.as<uint32_t>(), c->d_gen, c->N, reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST),
-                       reinterpret_cast<unsigned long long *>(d_scal + 13), reinterpret_cast<unsigned long long *>(d_scal + 14),
-                       reinterpret_cast<unsigned long long *>(d_scal + 15));
-    PDL_HIP(hipGetLastError());
+    launch_genome_cost(c, PDL_CTL_LAZY_KSEQ_SUM, PDL_CTL_LAZY_KSEQ_MAX);
     PinRead rd(c);
     const uint64_t *pg = rd.add<uint64_t>(d_scal + PDL_CTL_GCOST, c->G);
     rd.sync();
@@ -1594,7 +1585,7 @@ static void dist_slice_pipeline(pdl_ctx *c) {
     KeyT *sel_k = c->keys_b.as<KeyT>();
     uint32_t *sel_v = c->vals_b.as<uint32_t>();
     scan_and_apply(c, M, SelFlag<KeyT>{c->keys_a.as<KeyT>(), shift, b_lo, b_hi},
-                   SelApply<KeyT>{c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>(), sel_k, sel_v}, d_scal + 15);
+                   SelApply<KeyT>{c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>(), sel_k, sel_v}, d_scal + PDL_CTL_SELECT_TOTAL);
     // 4. sort + dedup 1/W of the stream; the group-head flag rides in bit 31 of the count
     c->U_slice = 0;
     if (m_own) {
@@ -1606,14 +1597,14 @@ static void dist_slice_pipeline(pdl_ctx *c) {
         // never straddle runs): the fold is made here, on the run, and travels with it (it is idempotent: the finish that
         // looks at the gathered dictionary finds nothing left to do; a last run of ONE record is left to that finish).
         if ((int) me == c->dist_tail)
-            hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, st, c->post.as<uint2>(), c->recpos.as<uint32_t>(), d_scal + 0);
+            hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, st, c->post.as<uint2>(), c->recpos.as<uint32_t>(), d_scal + PDL_CTL_RECORDS);
         // every genome's lookups inside this run (groups never straddle runs), as the reference counts them and above the
         // diagonal: summed over the ranks the former are "Genome g cost" (exact when the fold above was made), the latter the
         // weights of the genome deal
         GroupTileArgs ga{};
-        ga.post = c->post.as<uint2>(); ga.n_bound = m_own; ga.d_n = d_scal + 0;
+        ga.post = c->post.as<uint2>(); ga.n_bound = m_own; ga.d_n = d_scal + PDL_CTL_RECORDS;
         const uint32_t grid = group_tiles_plan(c, ga);
-        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + 12);      // (scratch words: the real counters come from the finish)
+        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_SLICE_COUNTERS);      // (scratch words: the real counters come from the finish)
         ga.genome_of = c->d_gen; ga.n_genomes = c->G;
         ga.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);             // scratch here, cleared again by the finish
         ga.g_upper = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST) + c->G;
@@ -1637,7 +1628,7 @@ void pdl_run_dist_begin(pdl_ctx *c, int kvalue) {
     c->dist_sender = false;
     if (c->M_slice) {
         PinRead rd(c);
-        const uint64_t *pu = rd.add<uint64_t>(c->scalars.as<uint64_t>(), 1);
+        const uint64_t *pu = rd.add<uint64_t>(c->scalars.as<uint64_t>() + PDL_CTL_RECORDS, 1);
         const uint64_t *pw = rd.add<uint64_t>(c->scalars.as<uint64_t>() + PDL_CTL_GCOST + c->G, c->G);
         const uint64_t *pf = rd.add<uint64_t>(c->scalars.as<uint64_t>() + PDL_CTL_GCOST, c->G);
         rd.sync();
@@ -1677,15 +1668,15 @@ void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {
     ev_begin(c, EV_DIST_FINISH);
     if (total == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dictionary");
     if (total >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a dictionary of %llu records needs 64-bit record indices", (unsigned long long) total);
-    // the record count of the whole dictionary goes where the kernels expect it (d_scal[0]); the other counters and the
+    // the record count of the whole dictionary goes where the kernels expect it (PDL_CTL_RECORDS); the other counters and the
     // per-genome words restart
     uint64_t *h_u = reinterpret_cast<uint64_t *>(c->pin);       // (pinned scratch; rewritten only by the next PinRead, which comes after a sync)
     if (!h_u) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
     h_u[0] = total;
-    PDL_HIP(hipMemcpyAsync(d_scal + 0, h_u, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    // (words 3-8 belong to K-len and stay: bad-offsets flag, kseq sums, M)
-    PDL_HIP(hipMemsetAsync(d_scal + 1, 0, 2 * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + 9, 0, 7 * sizeof(uint64_t), st));
+    PDL_HIP(hipMemcpyAsync(d_scal + PDL_CTL_RECORDS, h_u, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // (BAD_OFFSETS .. KSEQ_NMIN belong to K-len and stay: bad-offsets flag, kseq sums, M)
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_FREE_1, 0, (PDL_CTL_RANGES - PDL_CTL_FREE_1 + 1) * sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_MIRRORED, 0, (PDL_CTL_LAST - PDL_CTL_MIRRORED + 1) * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
     // genomes -> ranks by longest-processing-time on each genome's lookups above the diagonal: the caller's sum of the
     // runs' weights, or — without one — an exact pass over the gathered dictionary first
@@ -1781,22 +1772,22 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
     hipLaunchKernelGGL(k_gene_owner, dim3((c->N + 255) / 256), dim3(256), 0, st, c->d_gen, c->owner_of_genome.as<uint32_t>(), c->N, c->seq_owner.as<uint8_t>());
     const uint64_t n_run = c->U_slice;
     if (n_run) {
-        PDL_HIP(hipMemsetAsync(d_scal + 2, 0, sizeof(uint64_t), st));
-        PDL_HIP(hipMemsetAsync(d_scal + 10, 0, 4 * sizeof(uint64_t), st));
+        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_RANGES, 0, sizeof(uint64_t), st));
+        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_COUNTERS, 0, (PDL_CTL_REPEATS - PDL_CTL_COUNTERS + 1) * sizeof(uint64_t), st));
         GroupTileArgs ga{};
-        ga.post = c->post.as<uint2>(); ga.n_bound = n_run; ga.d_n = d_scal + 0;       // (the run's record count is still where K-rle left it)
+        ga.post = c->post.as<uint2>(); ga.n_bound = n_run; ga.d_n = d_scal + PDL_CTL_RECORDS;       // (the run's record count is still where K-rle left it)
         const uint32_t grid = group_tiles_plan(c, ga);
         ga.cost = c->cost.as<unsigned long long>();
-        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + 10);
+        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
         ga.genome_of = c->d_gen; ga.n_genomes = c->G;
         hipLaunchKernelGGL(k_range_count<1>, dim3(grid), dim3(GW_THREADS), 0, st, ga);
         hipLaunchKernelGGL(k_tile_prefix, dim3((ga.n_blocks + 3) / 4), dim3(256), 0, st, ga.tile_sums, ga.d_n, ga.n_bound, ga.chunk_sums, ga.n_blocks);
-        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + 2, (uint64_t *) nullptr);
+        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + PDL_CTL_RANGES, (uint64_t *) nullptr);
         PDL_HIP(hipGetLastError());
         uint64_t n_t = 0;
         {
             PinRead rd(c);
-            const uint64_t *pn = rd.add<uint64_t>(d_scal + 2, 1);
+            const uint64_t *pn = rd.add<uint64_t>(d_scal + PDL_CTL_RANGES, 1);
             rd.sync();
             n_t = pn[0];
         }
@@ -1809,18 +1800,19 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
         ga.key2 = k2a; ga.tuples = nullptr; ga.pay8 = pay_a; ga.pos_base = (uint32_t) base;
         launch_group_tiles<1, 1, false, false>(c, ga, grid);
         if (n_t) {
-            hipLaunchKernelGGL(k_owner_keys, dim3((uint32_t) std::min<uint64_t>((n_t + 255) / 256, (uint64_t) c->cus * 16)), dim3(256), 0, st, k2a, d_scal + 2, c->seq_owner.as<uint8_t>());
+            hipLaunchKernelGGL(k_owner_keys, dim3((uint32_t) std::min<uint64_t>((n_t + 255) / 256, (uint64_t) c->cus * 16)), dim3(256), 0, st, k2a, d_scal + PDL_CTL_RANGES, c->seq_owner.as<uint8_t>());
             pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_t, 32, false, nullptr, 24, true);      // -> (k2b, pay_b), by destination
             c->tuple_off.alloc(((size_t) W + 1) * sizeof(uint32_t));
-            hipLaunchKernelGGL(k_seq_offsets, dim3((W + 1 + 255) / 256), dim3(256), 0, st, k2b, d_scal + 2, W, c->tuple_off.as<uint32_t>(), 24u, 0xffu);
+            hipLaunchKernelGGL(k_seq_offsets, dim3((W + 1 + 255) / 256), dim3(256), 0, st, k2b, d_scal + PDL_CTL_RANGES, W, c->tuple_off.as<uint32_t>(), 24u, 0xffu);
             PDL_HIP(hipGetLastError());
             c->dist_out_keys = k2b; c->dist_out_ranges = pay_b; c->dist_out_total = n_t;
         }
         PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(d_scal + 10, 4);
+        const uint64_t *pc = rd.add<uint64_t>(d_scal + PDL_CTL_COUNTERS, PDL_CTL_REPEATS - PDL_CTL_COUNTERS + 1);
         const uint32_t *po = n_t ? rd.add<uint32_t>(c->tuple_off.as<uint32_t>(), W + 1) : nullptr;
         rd.sync();
-        c->dist_run_counters[0] = pc[0]; c->dist_run_counters[1] = pc[1]; c->dist_run_counters[2] = pc[3];
+        c->dist_run_counters[0] = pc[PDL_CTL_SHARED - PDL_CTL_COUNTERS]; c->dist_run_counters[1] = pc[PDL_CTL_GROUPS - PDL_CTL_COUNTERS];
+        c->dist_run_counters[2] = pc[PDL_CTL_REPEATS - PDL_CTL_COUNTERS];
         if (po) {
             for (uint32_t r = 0; r < W; r++) c->h_tuple_counts[r] = po[r + 1] - po[r];
             if (po[W] != n_t) PDL_FAIL(PDL_ERR_DEVICE, "range tuples: %llu made, %u filed", (unsigned long long) n_t, po[W]);
@@ -1841,11 +1833,11 @@ void pdl_run_dist_finish_ranges(pdl_ctx *c, uint64_t total, uint32_t *d_keys, un
     if (n_in >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 range tuples for one rank");
     uint64_t *h_u = reinterpret_cast<uint64_t *>(c->pin);       // (pinned scratch; rewritten only by the next PinRead, which comes after a sync)
     if (!h_u) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
-    h_u[0] = total; h_u[1] = 0; h_u[2] = n_in;
-    PDL_HIP(hipMemcpyAsync(d_scal + 0, h_u, 3 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemsetAsync(d_scal + 4, 0, sizeof(uint64_t), st));          // (k_genome_cost adds the k-mer statistics up: sum, max, ~min)
-    PDL_HIP(hipMemsetAsync(d_scal + 7, 0, 2 * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + 9, 0, 7 * sizeof(uint64_t), st));
+    h_u[PDL_CTL_RECORDS] = total; h_u[PDL_CTL_FREE_1] = 0; h_u[PDL_CTL_RANGES] = n_in;
+    PDL_HIP(hipMemcpyAsync(d_scal + PDL_CTL_RECORDS, h_u, (PDL_CTL_RANGES - PDL_CTL_RECORDS + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_SUM, 0, sizeof(uint64_t), st));          // (k_genome_cost adds the k-mer statistics up: sum, max, ~min)
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_MAX, 0, (PDL_CTL_KSEQ_NMIN - PDL_CTL_KSEQ_MAX + 1) * sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_MIRRORED, 0, (PDL_CTL_LAST - PDL_CTL_MIRRORED + 1) * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), st));
     ev_begin(c, EV_SORT2);
@@ -1862,25 +1854,21 @@ void pdl_run_dist_finish_ranges(pdl_ctx *c, uint64_t total, uint32_t *d_keys, un
     ev_end(c, EV_SORT2);
     ev_begin(c, EV_RANGES);
     c->ranges8 = reinterpret_cast<const uint2 *>(n_in ? pay_b : c->scratch.as<unsigned long long>());
-    hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, st, n_in ? k2b : reinterpret_cast<uint32_t *>(c->scratch.p), d_scal + 2, c->N,
+    hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, st, n_in ? k2b : reinterpret_cast<uint32_t *>(c->scratch.p), d_scal + PDL_CTL_RANGES, c->N,
                        c->seq_off.as<uint32_t>(), 0u, 0xffffffu);
     PDL_HIP(hipGetLastError());
     ev_end(c, EV_RANGES);
     c->upper_only = true;
     // the k-mer statistics of the genes (the per-gene costs are all zero here: what it adds up per genome is not used)
-    hipLaunchKernelGGL(k_genome_cost, dim3(std::min<uint32_t>((c->N + 255) / 256, 128)), dim3(256), 0, st, c->cost.as<unsigned long long>(),
-                       c->kseq_len.as<uint32_t>(), c->d_gen, c->N, reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST),
-                       reinterpret_cast<unsigned long long *>(d_scal + 4), reinterpret_cast<unsigned long long *>(d_scal + 7),
-                       reinterpret_cast<unsigned long long *>(d_scal + 8));
-    PDL_HIP(hipGetLastError());
+    launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);
     if (!c->tasks_ready) pdl_prepare_tasks(c);           // host work + small uploads while the device sorts
     {
         PinRead rd(c);
-        const uint64_t *pt = rd.add<uint64_t>(d_scal, 9);
+        const uint64_t *pt = rd.add<uint64_t>(d_scal, PDL_CTL_KSEQ_NMIN + 1);
         const uint32_t *lbe = lookback_error_word(c, rd);
         rd.sync();
         lookback_check(c, lbe);
-        c->sum_kseq = pt[4]; c->max_kseq = pt[7]; c->min_kseq = pt[8] == 0 ? 1 : ~pt[8];
+        c->sum_kseq = pt[PDL_CTL_KSEQ_SUM]; c->max_kseq = pt[PDL_CTL_KSEQ_MAX]; c->min_kseq = pt[PDL_CTL_KSEQ_NMIN] == 0 ? 1 : ~pt[PDL_CTL_KSEQ_NMIN];
     }
     c->U = total; c->Ushared = sums[0]; c->NG = sums[1]; c->Urepeat = sums[2];
     c->P = 0;

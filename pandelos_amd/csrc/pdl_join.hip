@@ -1318,15 +1318,15 @@ struct FinOffApply {
     uint32_t *fin_off;
     __device__ void operator()(uint64_t p, uint32_t, uint32_t prefix) const { fin_off[p] = prefix; }
 };
-// dst[0..n) = src[idx[..]]; then the 8 join counters and the emitted-cell total (u64 as two words) are appended, so the
-// host fetches everything it wants to know after a scoring pass with ONE copy
+// dst[0..n) = src[idx[..]]; then the join counters and the emitted-cell total (u64 as two words) are appended (PDL_JT_*), so
+// the host fetches everything it wants to know after a scoring pass with ONE copy
 __global__ void k_gather_u32(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t *dst, const uint32_t *ctr, const uint32_t *z64) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
-    else if (i < n + 8) dst[i] = ctr[i - n];
-    else if (i < n + 10) dst[i] = z64[i - n - 8];
-    else if (i == n + 10) dst[i] = ctr[10];          // entries of the put-aside lists that had to be loaded again
-    else if (i == n + 11) dst[i] = ctr[14];          // rows the partition tier (both forms) handed to tier 1
+    else if (i < n + PDL_JT_CTR_WORDS) dst[i] = ctr[i - n];
+    else if (i < n + PDL_JT_EMITTED + 2) dst[i] = z64[i - n - PDL_JT_EMITTED];
+    else if (i == n + PDL_JT_RELOADS) dst[i] = ctr[PDL_JC_RELOADS];
+    else if (i == n + PDL_JT_ROWS_T1) dst[i] = ctr[PDL_JC_ROWS_T1];
 }
 
 // Clears up to four arrays in one launch (16-byte words; every separate small fill is a dispatch of its own).
@@ -1383,7 +1383,7 @@ void pdl_prepare_tasks(pdl_ctx *c) {
     }
     memcpy(c->task_pin + words, c->h_task_row_off.data(), (size_t) (S + 1) * 4);
     c->task_blob.alloc(words * sizeof(uint32_t) + 16);
-    if (n_rows) c->task_off.alloc((size_t) (S + 1) * 8 + 96);      // task offsets | gathered cell offsets + 8 counters + cell total
+    if (n_rows) c->task_off.alloc((size_t) (S + 1) * 8 + 96);      // task offsets | gathered cell offsets + PDL_JT_WORDS counters (and room to spare)
     PDL_HIP(hipMemcpyAsync(c->task_blob.p, c->task_pin, words * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_stream));
     if (n_rows) PDL_HIP(hipMemcpyAsync(c->task_off.p, c->task_pin + words, (size_t) (S + 1) * 4, hipMemcpyHostToDevice, c->copy_stream));
     PDL_HIP(hipEventRecord(c->ev_tasks, c->copy_stream));
@@ -1430,13 +1430,7 @@ static ScorePlan score_plan(pdl_ctx *c) {
     pl.mirror = c->upper_only;
     if (pl.mirror && !c->dist && (c->shard_set && S != G))
         PDL_FAIL(PDL_ERR_STATE, "the dictionary was built for all genomes (upper-triangle ranges); a genome shard must be set before pdl_preprocess");
-    int cus = c->cus;
-    if (cus <= 0) {
-        cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess) cus = prop.multiProcessorCount;
-        c->cus = cus;
-    }
+    const int cus = pdl_cus(c);
     // ---- tiers ---------------------------------------------------------------------------------------
     //   1  k_join_lds<FILTER>     small table + "seen twice" bitmap, several rows resident per CU
     //   2  k_join_lds<13,1024>    128-KiB table holding every column a row touches, one row per CU
@@ -1507,7 +1501,7 @@ static void score_alloc_rows(pdl_ctx *c, const ScorePlan &pl) {
     c->MS.alloc((size_t) n_rows * G * sizeof(float) + 16);      // (+16: cleared in whole 16-byte words)
     c->CM.alloc((size_t) S * N * sizeof(float) + 16);
     c->row_base.alloc((size_t) n_rows * 4); c->row_cnt.alloc((size_t) n_rows * 4); c->fin_off.alloc(((size_t) n_rows + 2) * 4);      // (+1: the scan stores its 64-bit total at [n_rows])
-    c->join_ctr.alloc(64);
+    c->join_ctr.alloc(PDL_JC_WORDS * sizeof(uint32_t));
     c->row_desc.alloc((size_t) n_rows * sizeof(uint4));
     c->row_desc2.alloc((size_t) n_rows * sizeof(uint4) * (pl.tier0 ? 3 : 1));      // descriptors of the rows a tier handed on (tier 1 -> 2 | tier 0 -> its second form | that -> 1)
     c->overflow_rows.alloc((size_t) n_rows * 4 * 4);     // list A (tier 1 -> 2), list B (tier 2 -> 3), list S (tier 0 -> its second form), list S2 (that -> tier 1)
@@ -1561,28 +1555,26 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
         ZeroRanges z{};
         z.p[0] = c->MS.as<uint4>(); z.n16[0] = n16((size_t) n_rows * G * sizeof(float));
         z.p[1] = c->CM.as<uint4>(); z.n16[1] = n16((size_t) S * N * sizeof(float));
-        z.p[2] = c->join_ctr.as<uint4>(); z.n16[2] = n16(64);
+        z.p[2] = c->join_ctr.as<uint4>(); z.n16[2] = n16(PDL_JC_WORDS * sizeof(uint32_t));
         z.p[3] = pl.mirror ? c->mirror_cnt.as<uint4>() : nullptr; z.n16[3] = pl.mirror ? n16((size_t) n_rows * 4 * 3) : 0;
         const unsigned long long most = std::max(z.n16[0], z.n16[1]);
         hipLaunchKernelGGL(k_zero_ranges, dim3((uint32_t) std::min<unsigned long long>((most + 255) / 256 + 1, (unsigned long long) c->cus * 16)), dim3(256), 0, st, z);
     }
     JoinArgs a = join_args(c, pl);
-    // counters: 0 cursor tier 1 | 1 rows for tier 2 | 2 cursor tier 2 | 3 rows for tier 3 | 4-5 cell cursor | 6 errors | 7 cursor tier 3 | 9 wide rows seen by K-order
-    //           | 10 put-aside entries loaded again | 11 cursor tier 0 | 12 rows tier 0 handed to its second form | 13 cursor of that | 14 rows it handed to tier 1
     uint32_t *ctr32 = c->join_ctr.as<uint32_t>();
     uint32_t *list_a = c->overflow_rows.as<uint32_t>(), *list_b = list_a + n_rows, *list_s = list_b + n_rows, *list_s2 = list_s + n_rows;
-    a.error_count = ctr32 + 6; a.reload_count = ctr32 + 10;
-    a.cell_cursor = reinterpret_cast<unsigned long long *>(ctr32 + 4);
+    a.error_count = ctr32 + PDL_JC_ERRORS; a.reload_count = ctr32 + PDL_JC_RELOADS;
+    a.cell_cursor = reinterpret_cast<unsigned long long *>(ctr32 + PDL_JC_CELLS);
 
     ev_begin(c, EV_JOIN);
     if (pl.wide) {          // every row straight to tier 3: list B = all task positions
         hipLaunchKernelGGL(k_iota_u32, dim3((n_rows + 255) / 256), dim3(256), 0, st, list_b, n_rows);
-        PDL_HIP(hipMemcpyAsync(ctr32 + 3, &c->n_task_rows, 4, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(ctr32 + PDL_JC_ROWS_T3, &c->n_task_rows, 4, hipMemcpyHostToDevice, st));
     }
     // tier 0 (the partition tier) over every row; what it does not take is listed for tier 1
     a.work = nullptr; a.desc = c->row_desc.as<uint4>(); a.n_work = pl.wide ? 0 : n_rows; a.n_work_ptr = nullptr;
     if (pl.tier0) {
-        a.work_cursor = ctr32 + 11; a.overflow_count = ctr32 + 12; a.overflow_rows = list_s; a.work_batch = PT_BATCH;
+        a.work_cursor = ctr32 + PDL_JC_CURSOR_T0; a.overflow_count = ctr32 + PDL_JC_ROWS_T0B; a.overflow_rows = list_s; a.work_batch = PT_BATCH;
         a.overflow_desc = c->row_desc2.as<uint4>() + n_rows;
 #ifdef PDL_JOIN_PHASES
         static unsigned long long *d_phase0 = nullptr;
@@ -1606,15 +1598,15 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
 #endif
         // ... its second form (512 threads: twice the lookups per cycle) over the rows that alone exceed the first form's cycle,
         // one row per draw; what that cannot hold either is listed for tier 1 (a tier writes the descriptors of the rows it hands on)
-        a.desc = c->row_desc2.as<uint4>() + n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + 12;
-        a.work_cursor = ctr32 + 13; a.overflow_count = ctr32 + 14; a.overflow_rows = list_s2; a.work_batch = 1;
+        a.desc = c->row_desc2.as<uint4>() + n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T0B;
+        a.work_cursor = ctr32 + PDL_JC_CURSOR_T0B; a.overflow_count = ctr32 + PDL_JC_ROWS_T1; a.overflow_rows = list_s2; a.work_batch = 1;
         a.overflow_desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows;
         hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
-        a.desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + 14;
+        a.desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T1;
         c->tm.join_launches += 2;
     }
     // tier 1
-    a.work_cursor = ctr32 + 0; a.overflow_count = ctr32 + 1; a.overflow_rows = list_a; a.overflow_desc = tier1 ? c->row_desc2.as<uint4>() : nullptr;
+    a.work_cursor = ctr32 + PDL_JC_CURSOR_T1; a.overflow_count = ctr32 + PDL_JC_ROWS_T2; a.overflow_rows = list_a; a.overflow_desc = tier1 ? c->row_desc2.as<uint4>() : nullptr;
     a.work_batch = pl.tier0 ? 1 : std::max<uint32_t>(1, std::min<uint32_t>(8, n_rows / (std::max<uint32_t>(pl.grid1, 1) * 8)));      // (behind tier 0: few, long rows)
     if (tier1 >= 9 && tier1 <= 11) {
         // the filter tiers put a row's first sightings aside in a list per workgroup (16 bytes each; rewritten row after row, so
@@ -1652,8 +1644,8 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
     }
 #endif
     // tier 2 over list A (or over everything when tier 1 is off)
-    if (tier1) { a.desc = c->row_desc2.as<uint4>(); a.n_work = 0; a.n_work_ptr = ctr32 + 1; }
-    a.work_cursor = ctr32 + 2; a.overflow_count = ctr32 + 3; a.overflow_rows = list_b; a.overflow_desc = nullptr;      // (tier 3 goes by the task positions)
+    if (tier1) { a.desc = c->row_desc2.as<uint4>(); a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T2; }
+    a.work_cursor = ctr32 + PDL_JC_CURSOR_T2; a.overflow_count = ctr32 + PDL_JC_ROWS_T3; a.overflow_rows = list_b; a.overflow_desc = nullptr;      // (tier 3 goes by the task positions)
     a.work_batch = tier1 ? 1 : std::max<uint32_t>(1, std::min<uint32_t>(8, n_rows / (pl.grid2 * 8)));
     if (pl.wide && !tier1) a.n_work = 0;
     if (pl.tiny_tier2) hipLaunchKernelGGL((k_join_lds<9, 64, false>), dim3(pl.grid2), dim3(64), 0, st, a);
@@ -1662,7 +1654,7 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
     // tier 3 over list B (inside the join's event pair; its own pair is one of the optional stage timers)
     a.hbm_acc = c->glb_table.as<unsigned long long>();
     a.hbm_u32 = reinterpret_cast<uint32_t *>(a.hbm_acc + (size_t) pl.grid3 * N * (pl.wide ? 2 : 1));
-    a.work = list_b; a.n_work = 0; a.n_work_ptr = ctr32 + 3; a.work_cursor = ctr32 + 7; a.work_batch = 1;
+    a.work = list_b; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T3; a.work_cursor = ctr32 + PDL_JC_CURSOR_T3; a.work_batch = 1;
     ev_begin(c, EV_JOIN_OVF);
     c->glb_clean = false;
     if (pl.wide) hipLaunchKernelGGL(k_join_hbm<true>, dim3(pl.grid3), dim3(HBM_THREADS), 0, st, a);
@@ -1671,6 +1663,19 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
     ev_end(c, EV_JOIN_OVF);
     ev_end(c, EV_JOIN);
     c->tm.join_launches += 3;
+}
+
+// What the host reads of the join's counters after a pass, from the first words of join_ctr or of the gathered tail (PDL_JT_*:
+// the same places).  A pass that broke an invariant of its own is an error.
+struct JoinCounters {
+    uint32_t rows_tier2, rows_tier3, reloads;
+    unsigned long long cells;                // staging cells reserved (>= cells staged: chunk tails are unused)
+};
+static JoinCounters join_counters(const uint32_t *w) {
+    if (w[PDL_JC_ERRORS]) PDL_FAIL(PDL_ERR_DEVICE, "join: %u internal consistency violations", w[PDL_JC_ERRORS]);
+    JoinCounters j{w[PDL_JC_ROWS_T2], w[PDL_JC_ROWS_T3], w[PDL_JC_RELOADS], 0};
+    memcpy(&j.cells, w + PDL_JC_CELLS, sizeof(j.cells));
+    return j;
 }
 
 // K-order over the staged cells (+ the n_inbox cells filed at slots st_cap ..), then the one look at the counters.
@@ -1684,12 +1689,12 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
     ev_begin(c, EV_ORDER);
     const uint32_t *d_mcnt = pl.mirror ? c->mirror_cnt.as<uint32_t>() : nullptr;
     // the scan's total (all emitted cells, < 2^32) also closes fin_off: the low word of the u64 lands in fin_off[n_rows]
-    scan_and_apply(c, n_rows, RowCntFlag{c->row_cnt.as<uint32_t>(), d_mcnt}, FinOffApply{c->fin_off.as<uint32_t>()}, d_scal + 6,
+    scan_and_apply(c, n_rows, RowCntFlag{c->row_cnt.as<uint32_t>(), d_mcnt}, FinOffApply{c->fin_off.as<uint32_t>()}, d_scal + PDL_CTL_EMITTED,
                    reinterpret_cast<uint64_t *>(c->fin_off.as<uint32_t>() + n_rows));
     OrderArgs o{};
     if (pl.mirror) {
         uint32_t *m_off = c->mirror_cnt.as<uint32_t>() + n_rows, *m_cur = m_off + n_rows;
-        scan_and_apply(c, n_rows, MirrorCntFlag{d_mcnt}, FinOffApply{m_off}, d_scal + 9);
+        scan_and_apply(c, n_rows, MirrorCntFlag{d_mcnt}, FinOffApply{m_off}, d_scal + PDL_CTL_MIRRORED);
         MirrorArgs ma{};
         ma.row_base = c->row_base.as<uint32_t>(); ma.row_cnt = c->row_cnt.as<uint32_t>(); ma.task_rows = c->task_rows.as<uint32_t>();
         ma.st_score = c->st_score.as<float>(); ma.st_perc = c->st_perc.as<float>(); ma.st_tr = c->st_tr.as<float>();
@@ -1707,7 +1712,7 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
     o.c_score = c->c_score.as<float>(); o.c_perc = c->c_perc.as<float>(); o.c_tr = c->c_tr.as<float>();
     o.c_row = c->c_row.as<int32_t>(); o.c_col = c->c_col.as<int32_t>();
     o.n_rows = n_rows; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = c->N < (1u << 22) ? 1u : 0u;
-    o.wide_rows = ctr32 + 9;                 // (counter block, zero since the clearing launch)
+    o.wide_rows = ctr32 + PDL_JC_WIDE_ROWS;  // (counter block, zero since the clearing launch)
     hipLaunchKernelGGL(k_order_rows_wave, dim3((n_rows + 3) / 4), dim3(256), 0, st, o);
     hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n_rows, (uint32_t) c->cus * 8)), dim3(ORDER_THREADS), 0, st, o);   // rows of more than 256 cells, if any
     PDL_HIP(hipGetLastError());
@@ -1716,36 +1721,34 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
     // first cell of every shard genome = fin_off at its first task row; then the one look at the counters
     uint32_t *d_idx = c->task_off.as<uint32_t>();
     uint32_t *d_out = d_idx + (S + 1);
-    hipLaunchKernelGGL(k_gather_u32, dim3((S + 1 + 12 + 255) / 256), dim3(256), 0, st, c->fin_off.as<uint32_t>(), d_idx, S + 1, d_out,
-                       c->join_ctr.as<uint32_t>(), reinterpret_cast<const uint32_t *>(d_scal + 6));
+    hipLaunchKernelGGL(k_gather_u32, dim3((S + 1 + PDL_JT_WORDS + 255) / 256), dim3(256), 0, st, c->fin_off.as<uint32_t>(), d_idx, S + 1, d_out,
+                       ctr32, reinterpret_cast<const uint32_t *>(d_scal + PDL_CTL_EMITTED));
     c->h_fin.resize(S + 1);
-    uint32_t h_ctr[8];
+    JoinCounters jc;
     uint64_t zsum = 0;
     {
         PinRead rd(c);
-        const uint32_t *pf = rd.add<uint32_t>(d_out, S + 1 + 12);
+        const uint32_t *pf = rd.add<uint32_t>(d_out, S + 1 + PDL_JT_WORDS);
         const uint32_t *lbe = lookback_error_word(c, rd);
         ev_end(c, ev_total);
         rd.sync();
         lookback_check(c, lbe);
         memcpy(c->h_fin.data(), pf, (size_t) (S + 1) * 4);
-        memcpy(h_ctr, pf + S + 1, sizeof(h_ctr));
-        memcpy(&zsum, pf + S + 1 + 8, sizeof(zsum));
-        c->tm.aside_reloads = pf[S + 1 + 10];
-        c->tm.tier1_rows = pl.tier0 ? pf[S + 1 + 11] : (pl.tier1 ? n_rows : 0);
+        const uint32_t *tail = pf + S + 1;
+        memcpy(&zsum, tail + PDL_JT_EMITTED, sizeof(zsum));
+        c->tm.tier1_rows = pl.tier0 ? tail[PDL_JT_ROWS_T1] : (pl.tier1 ? n_rows : 0);
+        c->glb_clean = true;
+        jc = join_counters(tail);
     }
-    c->glb_clean = true;
-    c->tm.overflow_rows = h_ctr[3];
-    c->tm.tier2_rows = pl.tier1 ? h_ctr[1] : n_rows;
-    if (h_ctr[6]) PDL_FAIL(PDL_ERR_DEVICE, "join: %u internal consistency violations", h_ctr[6]);
-    unsigned long long z;                    // staging cells reserved (>= cells staged: chunk tails are unused)
-    memcpy(&z, &h_ctr[4], sizeof(z));
-    if (z <= c->st_cap) {
+    c->tm.aside_reloads = jc.reloads;
+    c->tm.overflow_rows = jc.rows_tier3;
+    c->tm.tier2_rows = pl.tier1 ? jc.rows_tier2 : n_rows;
+    if (jc.cells <= c->st_cap) {
         c->Z = zsum;
         c->tm.emitted_cells = c->Z;
         for (uint32_t i = 0; i <= S; i++) c->h_cell_off[i] = c->h_fin[i];
     }
-    return z;
+    return jc.cells;
 }
 
 // after a join: did a pass with 10-bit tagged put-aside entries see one that had to be loaded again (or does the test switch say so)?
@@ -1754,6 +1757,23 @@ static bool aside_pass_is_suspect(pdl_ctx *c, const ScorePlan &pl) {
     const bool seen = c->tm.aside_reloads != 0 || c->opt_aside_test_reload;
     c->opt_aside_test_reload = false;
     return seen;
+}
+
+// The verdict on a pass, given the staging cells `z` it asked for; a repeat is prepared here (wide entries / the cap asked for).
+// The canary acts: a pass whose 8-byte put-aside entries (10-bit tag) needed a second look is not trusted — a stale
+// entry passes that tag once in 1024 — and is repeated with entries that name row and launch in full, where a reload
+// is exact.  (Never seen outside the test switch: the cost falls on a path that does not fire.)
+enum class PassVerdict { accept, repeat_wide_aside, repeat_with_cap };
+static PassVerdict judge_pass(pdl_ctx *c, ScorePlan &pl, unsigned long long z, unsigned long long &cap, int attempt, int &overflows) {
+    if (aside_pass_is_suspect(c, pl)) {
+        if (attempt > 3) PDL_FAIL(PDL_ERR_DEVICE, "put-aside list: reloads persisted");
+        pl.wide_aside = true; c->tm.aside_repeats++;
+        return PassVerdict::repeat_wide_aside;
+    }
+    if (z <= cap) return PassVerdict::accept;
+    if (++overflows == 2) PDL_FAIL(PDL_ERR_DEVICE, "staging overflow persisted (%llu cells > %llu)", z, cap);
+    cap = z + pl.slack;          // what was asked for plus chunk slack, second and last attempt
+    return PassVerdict::repeat_with_cap;
 }
 
 static unsigned long long first_staging_cap(pdl_ctx *c, const ScorePlan &pl, uint64_t lookups) {
@@ -1788,18 +1808,7 @@ void pdl_run_score_all(pdl_ctx *c) {
         score_alloc_cells(c, pl, cap, 0);
         score_join(c, pl);
         const unsigned long long z = score_order(c, pl, nullptr, 0, EV_SCORE_TOTAL);
-        // The canary acts: a pass whose 8-byte put-aside entries (10-bit tag) needed a second look is not trusted — a stale
-        // entry passes that tag once in 1024 — and is repeated with entries that name row and launch in full, where a reload
-        // is exact.  (Never seen outside the test switch: the cost falls on a path that does not fire.)
-        if (aside_pass_is_suspect(c, pl)) {
-            if (attempt > 3) PDL_FAIL(PDL_ERR_DEVICE, "put-aside list: reloads persisted");
-            pl.wide_aside = true; c->tm.aside_repeats++;
-            ev_begin(c, EV_SCORE_TOTAL);
-            continue;
-        }
-        if (z <= cap) break;
-        if (++overflows == 2) PDL_FAIL(PDL_ERR_DEVICE, "staging overflow persisted (%llu cells > %llu)", z, cap);
-        cap = z + pl.slack;      // what was asked for plus chunk slack, second and last attempt
+        if (judge_pass(c, pl, z, cap, attempt, overflows) == PassVerdict::accept) break;
         ev_begin(c, EV_SCORE_TOTAL);
     }
     c->tm.join_ms = ev_ms(c, EV_JOIN);
@@ -1826,8 +1835,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
     ScorePlan pl = score_plan(c);
     if (!pl.mirror) PDL_FAIL(PDL_ERR_STATE, "multi-GPU scoring needs the upper-triangle range lists of pdl_dist_preprocess_finish");
     score_alloc_rows(c, pl);
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    uint32_t *ctr32 = c->join_ctr.as<uint32_t>();
+    uint64_t *d_outbox_total = c->scalars.as<uint64_t>() + PDL_CTL_OUTBOX_TOTAL;
     // outbox listing: rows are dealt to workgroups in blocks
     const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_rows + 15) / 16, 2048));
     const uint32_t rows_per_block = (n_rows + n_blocks - 1) / n_blocks;
@@ -1847,33 +1855,22 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
         oa.n_rows = n_rows; oa.rows_per_block = rows_per_block; oa.world = W; oa.n_blocks = n_blocks;
         oa.tab = tab; oa.offs = offs;
         hipLaunchKernelGGL(k_outbox<false>, dim3(n_blocks), dim3(256), 0, st, oa);
-        scan_and_apply(c, tab_n, RowCntFlag{tab, nullptr}, FinOffApply{offs}, d_scal + 12);
-        hipLaunchKernelGGL(k_outbox_totals, dim3(1), dim3(PDL_MAX_WORLD + 1 < 128 ? 128 : PDL_MAX_WORLD + 1), 0, st, offs, n_blocks, W, d_scal + 12, d_tot);
+        scan_and_apply(c, tab_n, RowCntFlag{tab, nullptr}, FinOffApply{offs}, d_outbox_total);
+        hipLaunchKernelGGL(k_outbox_totals, dim3(1), dim3(PDL_MAX_WORLD + 1 < 128 ? 128 : PDL_MAX_WORLD + 1), 0, st, offs, n_blocks, W, d_outbox_total, d_tot);
         PDL_HIP(hipGetLastError());
         uint32_t h_tot[PDL_MAX_WORLD + 1];
-        uint32_t h_ctr[8];
+        JoinCounters jc;
         {
             PinRead rd(c);
             const uint32_t *pt = rd.add<uint32_t>(d_tot, W + 1);
-            const uint32_t *pc = rd.add<uint32_t>(ctr32, 12);
+            const uint32_t *pc = rd.add<uint32_t>(c->join_ctr.as<uint32_t>(), PDL_JC_RELOADS + 1);
             rd.sync();
-            memcpy(h_tot, pt, (W + 1) * 4); memcpy(h_ctr, pc, sizeof(h_ctr));
-            c->tm.aside_reloads = pc[10];
+            memcpy(h_tot, pt, (W + 1) * 4);
+            c->glb_clean = true;             // (k_join_hbm has run to its end and left its tables zeroed)
+            jc = join_counters(pc);
         }
-        c->glb_clean = true;                 // (k_join_hbm has run to its end and left its tables zeroed)
-        if (h_ctr[6]) PDL_FAIL(PDL_ERR_DEVICE, "join: %u internal consistency violations", h_ctr[6]);
-        if (aside_pass_is_suspect(c, pl)) {   // (see pdl_run_score_all)
-            if (attempt > 3) PDL_FAIL(PDL_ERR_DEVICE, "put-aside list: reloads persisted");
-            pl.wide_aside = true; c->tm.aside_repeats++;
-            continue;
-        }
-        unsigned long long z;
-        memcpy(&z, &h_ctr[4], sizeof(z));
-        if (z > cap) {
-            if (++overflows == 2) PDL_FAIL(PDL_ERR_DEVICE, "staging overflow persisted (%llu cells > %llu)", z, cap);
-            cap = z + pl.slack;
-            continue;
-        }
+        c->tm.aside_reloads = jc.reloads;
+        if (judge_pass(c, pl, jc.cells, cap, attempt, overflows) != PassVerdict::accept) continue;
         const uint64_t total = h_tot[W];
         for (uint32_t d = 0; d < W; d++) c->h_outbox_counts[d] = (d + 1 < W ? h_tot[d + 1] : total) - h_tot[d];
         c->outbox.alloc(std::max<uint64_t>(total, 1) * sizeof(pdl_dist_cell));
@@ -1911,7 +1908,7 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
         ia.in = d_inbox; ia.n = (uint32_t) n_inbox;
         ia.taskpos_of = c->taskpos_of.as<uint32_t>(); ia.genome_of = c->d_gen; ia.local_genome = c->local_genome.as<uint32_t>();
         ia.mirror_cnt = c->mirror_cnt.as<uint32_t>(); ia.MS = c->MS.as<float>(); ia.CM = c->CM.as<float>();
-        ia.N = c->N; ia.G = c->G; ia.error_count = c->join_ctr.as<uint32_t>() + 6;
+        ia.N = c->N; ia.G = c->G; ia.error_count = c->join_ctr.as<uint32_t>() + PDL_JC_ERRORS;
         hipLaunchKernelGGL(k_inbox_file, dim3((uint32_t) ((n_inbox + 255) / 256)), dim3(256), 0, st, ia);
         PDL_HIP(hipGetLastError());
     }

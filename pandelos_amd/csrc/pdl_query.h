@@ -56,10 +56,21 @@ struct QFold {
     uint32_t has_extra;     // p joins the query group of rank extra_target
 };
 
-// control words of a query (u64): 0 records | 1 256 - smallest absent byte (0: none) | 2 genome cost | 3 matched records |
-// 4 staging bound | 5 overflow rows | 6 staging cursor | 7 emitted cells | 8 order: wide rows | 9 rows that may overflow (more
-// lookups than the LDS table holds keys)
-constexpr uint32_t Q_CTL_WORDS = 16;
+// control words of a query (q.ctl, u64), cleared at the start of every query; each word has one life
+enum : uint32_t {
+    Q_CTL_RECORDS = 0,          // records of the query's dictionary (total of its dedup scan)
+    Q_CTL_BAD_BYTE = 1,         // 256 - smallest byte that is not in the base's alphabet (0: none)
+    Q_CTL_COST = 2,             // genome cost
+    Q_CTL_MATCHED = 3,          // matched records
+    Q_CTL_BOUND = 4,            // staging bound
+    Q_CTL_OVERFLOW_ROWS = 5,    // rows the LDS join handed to the HBM join
+    Q_CTL_CELL_CURSOR = 6,      // staging cursor
+    Q_CTL_EMITTED = 7,          // emitted cells (total of the row-count scan)
+    Q_CTL_WIDE_ROWS = 8,        // order: rows of more than 256 cells
+    Q_CTL_MAY_OVERFLOW = 9,     // rows that may overflow (more lookups than the LDS table holds keys)
+    Q_CTL_USED = 10,
+    Q_CTL_WORDS = 16,
+};
 
 // *bad = max(256 - byte) over the absent bytes (0: none), i.e. 256 - the smallest absent byte
 struct QAlphaArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; unsigned long long *bad; };
@@ -94,7 +105,7 @@ __global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *ou
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     QFold f{};
     f.p = Q_NONE; f.qL = Q_NONE;
-    const uint32_t Uq = (uint32_t) ctl[0];
+    const uint32_t Uq = (uint32_t) ctl[Q_CTL_RECORDS];
     const uint32_t U = v.U;
     f.bmax = (unsigned long long) v.bkeys[v.M - 1];
     bool lonely = U == 1;                 // the base's last record is alone in its rank (U == 1: nothing to fold it into)
@@ -138,7 +149,7 @@ struct QMatchOut {
 template <class KeyT>
 __global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf, QMatchOut o, uint64_t bound) {
     const QFold f = *pf;
-    const uint32_t Uq = (uint32_t) o.ctl[0];
+    const uint32_t Uq = (uint32_t) o.ctl[Q_CTL_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     if (j < Uq && j < bound) {
@@ -168,8 +179,8 @@ __global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf,
 #pragma unroll
     for (int s = PDL_WAVE / 2; s > 0; s >>= 1) { cost += __shfl_down(cost, s, PDL_WAVE); matched += __shfl_down(matched, s, PDL_WAVE); }
     if ((threadIdx.x & (PDL_WAVE - 1)) == 0) {
-        if (cost) atomicAdd(&o.ctl[2], cost);
-        if (matched) atomicAdd(&o.ctl[3], matched);
+        if (cost) atomicAdd(&o.ctl[Q_CTL_COST], cost);
+        if (matched) atomicAdd(&o.ctl[Q_CTL_MATCHED], matched);
     }
 }
 
@@ -180,7 +191,7 @@ __global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, 
                                                    const uint32_t *row_lookups, uint32_t n_cols, uint32_t limit, unsigned long long *bound,
                                                    unsigned long long *wide) {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t Uq = (uint32_t) ctl[0];
+    const uint32_t Uq = (uint32_t) ctl[Q_CTL_RECORDS];
     unsigned long long b = 0, w = 0;
     if (g <= n) {
         uint32_t lo = 0, hi = Uq;
@@ -488,7 +499,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
     if (Rq) {
         QAlphaArgs aa{};
-        aa.res = q.res.as<uint8_t>(); aa.n = Rq; aa.bad = ctl + 1;
+        aa.res = q.res.as<uint8_t>(); aa.n = Rq; aa.bad = ctl + Q_CTL_BAD_BYTE;
         for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
         hipLaunchKernelGGL(k_q_alpha, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
         PDL_HIP(hipGetLastError());
@@ -502,7 +513,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         q.recpos.alloc((Mq + 1) * 4); q.post.alloc(Mq * 8);
         qkeys = pdl_query_dictionary(c, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, Mq, Rq, q.keys_a.p, q.keys_b.p,
                                      q.vals_a.as<uint32_t>(), q.vals_b.as<uint32_t>(), q.recpos.as<uint32_t>(), q.post.as<uint2>(),
-                                     reinterpret_cast<uint64_t *>(ctl));
+                                     reinterpret_cast<uint64_t *>(ctl + Q_CTL_RECORDS));
         q.fold.alloc(sizeof(QFold)); q.desc.alloc(Mq * sizeof(QDesc)); q.gkey.alloc(Mq * 8); q.rec_sorted.alloc(Mq * 8);
         q.row_lookups.alloc(n * 4ull); q.row_off.alloc((n + 1) * 4ull);
         PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
@@ -522,27 +533,28 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
         uint32_t *ix_in = q.rec_sorted.as<uint32_t>(), *ix_out = ix_in + Mq;
         pdl_sort_pairs<uint32_t, uint32_t>(c, gk_in, gk_out, ix_in, ix_out, Mq, std::max<uint32_t>(1, bit_length64(n)), true,
-                                           reinterpret_cast<const uint64_t *>(ctl), 0, true);
+                                           reinterpret_cast<const uint64_t *>(ctl + Q_CTL_RECORDS), 0, true);
         hipLaunchKernelGGL(k_q_row_off, dim3((n + 1 + 255) / 256), dim3(256), 0, st, gk_out, (const unsigned long long *) ctl, n,
-                           q.row_off.as<uint32_t>(), (const uint32_t *) q.row_lookups.as<uint32_t>(), NC, QJ_LIMIT, ctl + 4, ctl + 9);
+                           q.row_off.as<uint32_t>(), (const uint32_t *) q.row_lookups.as<uint32_t>(), NC, QJ_LIMIT, ctl + Q_CTL_BOUND, ctl + Q_CTL_MAY_OVERFLOW);
         PDL_HIP(hipGetLastError());
         q.rec_sorted_at = ix_out;
     }
-    uint64_t h_ctl[10] = {};
+    uint64_t h_ctl[Q_CTL_USED] = {};
     span_end();
     {
         PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(ctl, 10);
+        const uint64_t *pc = rd.add<uint64_t>(ctl, Q_CTL_USED);
         rd.sync();
         memcpy(h_ctl, pc, sizeof(h_ctl));
     }
     span_begin();
-    if (h_ctl[1]) {
-        const uint32_t b = 256u - (uint32_t) h_ctl[1];
+    if (h_ctl[Q_CTL_BAD_BYTE]) {
+        const uint32_t b = 256u - (uint32_t) h_ctl[Q_CTL_BAD_BYTE];
         PDL_FAIL(PDL_ERR_UNSUPPORTED, "query byte 0x%02x ('%c') is not in the base's alphabet: the union would rank k-mers differently", b,
                  (b >= 32 && b < 127) ? (char) b : '?');
     }
-    const uint64_t Uq = h_ctl[0], cost = h_ctl[2], matched = h_ctl[3], bound = h_ctl[4], may_overflow = h_ctl[9];
+    const uint64_t Uq = h_ctl[Q_CTL_RECORDS], cost = h_ctl[Q_CTL_COST], matched = h_ctl[Q_CTL_MATCHED], bound = h_ctl[Q_CTL_BOUND],
+                   may_overflow = h_ctl[Q_CTL_MAY_OVERFLOW];
     if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);
 
     // Q-join, Q-order
@@ -565,7 +577,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         float *stf = q.st.as<float>();
         a.st_score = stf; a.st_perc = stf + cap; a.st_tr = stf + 2 * cap;
         a.st_col = reinterpret_cast<uint32_t *>(stf + 3 * cap); a.st_first = reinterpret_cast<uint32_t *>(stf + 4 * cap);
-        a.cell_cursor = ctl + 6; a.overflow_rows = q.overflow.as<uint32_t>(); a.n_overflow = ctl + 5;
+        a.cell_cursor = ctl + Q_CTL_CELL_CURSOR; a.overflow_rows = q.overflow.as<uint32_t>(); a.n_overflow = ctl + Q_CTL_OVERFLOW_ROWS;
         hipLaunchKernelGGL(k_q_join, dim3(n), dim3(QJ_T), 0, st, a);
         PDL_HIP(hipGetLastError());
         if (may_overflow) {      // some row has more lookups than the LDS table holds keys: did it leave the table?
@@ -573,7 +585,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
             span_end();
             {
                 PinRead rd(c);
-                const uint64_t *pc = rd.add<uint64_t>(ctl + 5, 1);
+                const uint64_t *pc = rd.add<uint64_t>(ctl + Q_CTL_OVERFLOW_ROWS, 1);
                 rd.sync();
                 n_over = pc[0];
             }
@@ -593,7 +605,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
                 PDL_HIP(hipGetLastError());
             }
         }
-        scan_and_apply(c, n, RowCntFlag{q.row_cnt.as<uint32_t>(), nullptr}, FinOffApply{q.fin_off.as<uint32_t>()}, reinterpret_cast<uint64_t *>(ctl + 7));
+        scan_and_apply(c, n, RowCntFlag{q.row_cnt.as<uint32_t>(), nullptr}, FinOffApply{q.fin_off.as<uint32_t>()}, reinterpret_cast<uint64_t *>(ctl + Q_CTL_EMITTED));
         OrderArgs o{};
         o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = q.fin_off.as<uint32_t>(); o.task_rows = q.rowid.as<uint32_t>();
         o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
@@ -601,21 +613,20 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         o.c_score = cf; o.c_perc = cf + cap; o.c_tr = cf + 2 * cap;
         o.c_row = reinterpret_cast<int32_t *>(cf + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cf + 4 * cap);
         o.n_rows = n; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = NC < (1u << 22) ? 1u : 0u;
-        o.wide_rows = reinterpret_cast<uint32_t *>(ctl + 8);
-        const uint32_t cus = c->cus > 0 ? (uint32_t) c->cus : 256u;
+        o.wide_rows = reinterpret_cast<uint32_t *>(ctl + Q_CTL_WIDE_ROWS);
+        const uint32_t cus = (uint32_t) pdl_cus(c);
         hipLaunchKernelGGL(k_order_rows_wave, dim3((n + 3) / 4), dim3(256), 0, st, o);
         hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n, cus * 8)), dim3(ORDER_THREADS), 0, st, o);
         PDL_HIP(hipGetLastError());
         span_end();
-        uint64_t h2[3];
+        uint64_t staged = 0;
         {
             PinRead rd(c);
-            const uint64_t *pc = rd.add<uint64_t>(ctl + 5, 3);
+            const uint64_t *pc = rd.add<uint64_t>(ctl + Q_CTL_OVERFLOW_ROWS, Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1);
             rd.sync();
-            memcpy(h2, pc, sizeof(h2));
+            staged = pc[Q_CTL_CELL_CURSOR - Q_CTL_OVERFLOW_ROWS]; Z = pc[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS];
         }
-        Z = h2[2];
-        if (Z > bound || h2[1] > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) h2[1], (unsigned long long) bound);
+        if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
     } else {
         span_end();
     }

@@ -174,7 +174,7 @@ void pdl_sort_pairs(pdl_ctx *c, KeyT *&keys_in, KeyT *&keys_out, ValT *&vals_in,
     const size_t table = (size_t) RS_BINS * n_tiles;
     c->sort_tmp.alloc(2 * table * sizeof(uint32_t));
     uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table;
-    uint64_t *d_total = c->scalars.as<uint64_t>() + 15;
+    uint64_t *d_total = c->scalars.as<uint64_t>() + PDL_CTL_SCAN_TOTAL;
     const uint32_t passes = (end_bit + 7) / 8;
     for (uint32_t p = begin_bit / 8; p < passes; p++) {
         const uint32_t shift = p * 8;
