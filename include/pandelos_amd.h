@@ -222,6 +222,39 @@ typedef struct {
 PDL_API int pdl_query_scores(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n_query+1] */,
                              uint32_t n_query, pdl_scores *out, pdl_query_info *info /* may be NULL */);
 
+/* ---- append: new genomes join the dictionary already built, by a merge instead of a rebuild ----------------------------
+ * The n genes of residues/offsets become genes N..N+n-1 of the context.  genome_of == NULL: all of them are ONE new genome G.
+ * Otherwise genome_of[i] are union ids G..G+g-1, dense in first-seen order (the rule of PangeneIData.java:56-62 continued); an id
+ * below G (a gene added to an existing genome) or one that skips an id is PDL_ERR_ARGUMENT.
+ * After PDL_OK every observable of the context equals, bit for bit, that of a context on which pdl_preprocess ran with the union
+ * (base genes first, same k, same flags and options): pdl_cost, pdl_get_dictionary, pdl_genome_cost, pdl_sequence_costs,
+ * pdl_get_rank_table, pdl_compute_scores / pdl_score_all / pdl_scores_counts for all G+g genomes, pdl_compute_edges, and later
+ * pdl_query_scores and later appends.  Scores, edges and query buffers of the old context are dropped (as by a preprocess).
+ * pdl_get_timings: the preprocess stage fields describe the append — rank_ms: K-rank of the new genes; sort_rank_ms: their sort
+ * plus the merge pass; dict_ms, sort_seq_ms, ranges_ms: the stages behind the sorted stream, which run over the whole union;
+ * hist_ms 0; preprocess_total_ms = pdl_append_info.device_ms — and the scoring fields start again at zero.
+ * The base's residues are not needed and not touched: the call works after pdl_preprocess, pdl_preprocess_device (the caller's
+ * input buffers may be gone: from here on the context owns its copy of the genome ids) and pdl_preprocess_ingested.  The sorted
+ * k-mer stream of the union is the stable merge of the base's (in HBM) and the new genes' (K-rank + K-sort with the base's rank
+ * table): one pass over it, then the stages behind the sort as in a build.
+ * Refusals, checked BEFORE anything is changed (the context stays exactly as it was: scores, edges, dictionary, costs, timings):
+ * PDL_ERR_STATE before a preprocess, after only_complexity, on a multi-GPU context, with a genome shard in force, or after
+ * low_memory released the sorted k-mer stream; PDL_ERR_ARGUMENT for n == 0, NULL pointers, decreasing offsets, bad genome_of;
+ * PDL_ERR_UNSUPPORTED for a byte the base's alphabet lacks (the union would have another rank table, library.cpp:96-119; the
+ * message names the byte) and for unions past the build's limits (2^32 residues / k-mer positions, 31-bit gene ids).  Appended
+ * genes with no k-mer at all (shorter than k, empty) are legal: they become genes with kseq_len 0.
+ * A device failure in the middle (PDL_ERR_DEVICE) leaves the context un-preprocessed: PDL_ERR_STATE until the next pdl_preprocess. */
+typedef struct {
+    uint64_t residues, kmer_occurrences;   /* of the appended genes */
+    uint64_t records;                      /* their unique (rank, gene) records */
+    float rank_sort_ms;                    /* K-rank + K-sort of the appended genes (0 with option "stage_timers" 0, like merge_ms) */
+    float merge_ms;                        /* the merge pass */
+    float device_ms;                       /* the whole call on the device (the sum of its stretches of device work) */
+} pdl_append_info;
+PDL_API int pdl_append_genomes(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n+1] */,
+                               const uint32_t *genome_of /* [n] or NULL */, uint32_t n,
+                               pdl_cost *out_cost /* may be NULL: the union's */, pdl_append_info *info /* may be NULL */);
+
 /* Number of emitted cells per genome after pdl_score_all ([G], 0 for genomes outside the shard) */
 PDL_API int pdl_scores_counts(pdl_ctx *, uint32_t *out_counts);
 

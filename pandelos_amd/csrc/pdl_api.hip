@@ -77,6 +77,7 @@ void pdl_destroy(pdl_ctx *c) {
     (void) hipStreamSynchronize(c->stream);
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
     for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
@@ -144,6 +145,11 @@ void pdl_finish_layout(pdl_ctx *c) {
     layout_and_shard(c);
 }
 void pdl_set_create_error(const std::string &msg) { g_create_error = msg; }
+void pdl_extend_layout(pdl_ctx *c, const uint32_t *genome_ids, uint32_t n) {
+    c->h_genome_of.insert(c->h_genome_of.end(), genome_ids, genome_ids + n);
+    c->N += n;
+    layout_and_shard(c);
+}
 
 int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
     PDL_GUARD_BEGIN
@@ -720,6 +726,44 @@ int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offset
     if (!residues && offsets[n_query] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL residues");
     PDL_HIP(hipSetDevice(c->device));
     pdl_run_query(c, residues, offsets, n_query, out, info);
+    return PDL_OK;
+    PDL_GUARD_END(c)
+}
+
+int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_of, uint32_t n, pdl_cost *out_cost,
+                       pdl_append_info *info) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (info) memset(info, 0, sizeof(*info));
+    PDL_GUARD_BEGIN
+    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes before pdl_preprocess");
+    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: the context was preprocessed with only_complexity");
+    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: not available on a multi-GPU context");
+    if (c->shard_set || !c->dict_shard.empty()) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: not available with a genome shard in force");
+    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
+        PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: the sorted k-mer stream was released (option low_memory)");
+    if (!offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: NULL pointer");
+    if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: no gene");
+    for (uint32_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: offsets decrease at gene %u", i);
+    if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: NULL residues");
+    // union genome ids: G, G+1, ... in first-seen order (PangeneIData.java:56-62 continued)
+    std::vector<uint32_t> ids(n, c->G);
+    uint32_t g_new = 1;
+    if (genome_of) {
+        g_new = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t g = genome_of[i];
+            if (g < c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: gene %u joins genome %u of the context (new genomes only: ids from %u)", i, g, c->G);
+            if (g - c->G > g_new) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: genome id %u at gene %u is not dense in first-seen order (next new id: %u)", g, i, c->G + g_new);
+            if (g - c->G == g_new) g_new++;
+            ids[i] = g;
+        }
+    }
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_run_append(c, residues, offsets, ids.data(), n, g_new, info);
+    c->preprocessed = true;
+    fill_cost(c, out_cost);
     return PDL_OK;
     PDL_GUARD_END(c)
 }

@@ -196,6 +196,7 @@ struct pdl_ctx {
     const uint64_t *d_off = nullptr;
     const uint32_t *d_gen = nullptr;
     DevBuf in_res, in_off, in_gen;
+    DevBuf own_gen;       // u32 [N] genome ids after an append: the context's own copy (the caller's input may be gone by then)
 
     // device-resident input: genome ids (and the two ends of the offsets) come to the host through this pinned buffer while the
     // first kernels already run; the genome layout is built behind them (pdl_finish_layout)
@@ -361,6 +362,7 @@ struct pdl_ctx {
             hbm_clean = false; hbm_cols = hbm_slots = 0; rec_sorted_at = nullptr;
         }
     } qb;
+    hipEvent_t app_ev[4] = {};        // pdl_append_genomes: start / end of its two stretches of device work
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
 
     pdl_timings tm{};
@@ -505,6 +507,13 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
+void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad);      // k_q_alpha over device bytes (pdl_query.h)
+[[noreturn]] void pdl_fail_absent_byte(uint64_t bad_word, const char *who);                             // ... and the refusal that names the byte
+// K-append (pdl_append.h, pdl_dict.hip): the n genes of residues/offsets become genes N.. of the context; genome_ids [n] are their
+// union genome ids (checked by the caller), n_new_genomes of them new.  pdl_extend_layout (pdl_api.hip): the host's genome layout.
+void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_ids, uint32_t n, uint32_t n_new_genomes,
+                    pdl_append_info *info);
+void pdl_extend_layout(pdl_ctx *c, const uint32_t *genome_ids, uint32_t n);
 inline uint2 *pdl_postings(const pdl_ctx *c) { return c->post_ext ? c->post_ext : c->post.as<uint2>(); }
 
 // compute units of the context's device (looked up once; 256 where the runtime does not say)
@@ -518,11 +527,12 @@ inline int pdl_cus(pdl_ctx *c) {
 
 // event helpers
 enum { EV_HIST, EV_RANK, EV_SORT1, EV_DICT, EV_SORT2, EV_RANGES, EV_JOIN, EV_JOIN_OVF, EV_ORDER, EV_PRE_TOTAL, EV_SCORE_TOTAL,
-       EV_DIST_BEGIN, EV_DIST_FINISH, EV_DIST_SCORE_FINISH, EV_DIST_RANGES, EV_COUNT };
+       EV_DIST_BEGIN, EV_DIST_FINISH, EV_DIST_SCORE_FINISH, EV_DIST_RANGES, EV_MERGE, EV_COUNT };
+static_assert(EV_COUNT <= 16, "pdl_ctx::ev");
 
 // An event record is a marker packet between two dispatches (a few us of idle stream each); the per-stage pairs can be
 // switched off ("stage_timers" 0) when only the totals and the join's launch time are wanted (bench.py's timed loop).
-inline bool ev_is_stage(int i) { return i == EV_HIST || i == EV_RANK || i == EV_SORT1 || i == EV_DICT || i == EV_SORT2 || i == EV_RANGES || i == EV_ORDER || i == EV_JOIN_OVF; }
+inline bool ev_is_stage(int i) { return i == EV_HIST || i == EV_RANK || i == EV_SORT1 || i == EV_DICT || i == EV_SORT2 || i == EV_RANGES || i == EV_ORDER || i == EV_JOIN_OVF || i == EV_MERGE; }
 inline void ev_begin(pdl_ctx *c, int i) {
     c->ev[i].used = false;
     if (!c->opt_stage_timers && ev_is_stage(i)) return;

@@ -19,6 +19,7 @@
 #include "pdl_common.h"
 #include "pdl_scan.h"
 #include "pdl_sort.h"
+#include "pdl_append.h"
 
 #include <algorithm>
 #include <cstring>
@@ -1200,17 +1201,10 @@ static void stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shif
     PDL_HIP(hipGetLastError());
 }
 
-// K-sort + K-rle over the first m elements of (keys_in, vals_in): records into c->post / recpos.
-// scalars[PDL_CTL_RECORDS] receives the record count.
+// K-rle over the sorted stream (keys_b, vals_b)[0 .. m): records into c->post / recpos, their count into scalars[PDL_CTL_RECORDS].
 template <class KeyT>
-static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint64_t m) {
+static void stage_dedup(pdl_ctx *c, uint64_t m) {
     uint64_t *d_scal = c->scalars.as<uint64_t>();
-    ev_begin(c, EV_SORT1);
-    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
-    ev_end(c, EV_SORT1);
-    // remember which physical buffers hold the sorted stream (pdl_get_dictionary reads them)
-    if ((void *) keys_out != c->keys_b.p) { std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes); }
-    if ((void *) vals_out != c->vals_b.p) { std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes); }
     const KeyT *skeys = c->keys_b.as<KeyT>();
     const uint32_t *svals = c->vals_b.as<uint32_t>();
     ev_begin(c, EV_DICT);                                       // (ended by the caller, behind K-groups where it runs them)
@@ -1218,6 +1212,19 @@ static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint
     c->post.alloc(m * sizeof(uint2));                           // U <= m records (sized before U is known)
     scan_and_apply(c, m, RecHead<KeyT>{skeys, svals},
                    RecScatter<KeyT>{skeys, svals, m, c->recpos.as<uint32_t>(), c->post.as<uint2>()}, d_scal + PDL_CTL_RECORDS);
+}
+
+// K-sort + K-rle over the first m elements of (keys_in, vals_in): records into c->post / recpos.
+// scalars[PDL_CTL_RECORDS] receives the record count.
+template <class KeyT>
+static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint64_t m) {
+    ev_begin(c, EV_SORT1);
+    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+    ev_end(c, EV_SORT1);
+    // remember which physical buffers hold the sorted stream (pdl_get_dictionary reads them)
+    if ((void *) keys_out != c->keys_b.p) { std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes); }
+    if ((void *) vals_out != c->vals_b.p) { std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes); }
+    stage_dedup<KeyT>(c, m);
 }
 
 // Launch helpers of k_group_waves.  group_tiles_plan sizes the grid and the scratch: tile_sums[tiles] | th_first[tiles] |
@@ -1494,20 +1501,27 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
     }
 }
 
+// K-rank of genes that are not the context's input (a query, an append) with the context's rank parameters: gene values 0..n-1
+template <class KeyT>
+static void rank_new_genes(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m, uint64_t n_res,
+                           KeyT *keys, uint32_t *vals) {
+    hipStream_t st = c->stream;
+    if (c->rp.hash_fallback) {
+        if constexpr (sizeof(KeyT) == 8)
+            hipLaunchKernelGGL(k_rank_hash<0>, dim3((n + 255) / 256), dim3(256), 0, st, res, off, kmer_off, n, c->rp, keys, vals, (uint32_t *) nullptr);
+    } else {
+        const uint64_t tiles = (m + RANK_TILE - 1) / RANK_TILE;
+        hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, res, off, kmer_off, n, m, n_res, c->rp,
+                           keys, vals, 0u, (uint32_t *) nullptr);
+    }
+    PDL_HIP(hipGetLastError());
+}
+
 template <class KeyT>
 static const void *query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
                                     uint64_t n_res, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint32_t *recpos,
                                     uint2 *post, uint64_t *d_u) {
-    hipStream_t st = c->stream;
-    if (c->rp.hash_fallback) {
-        if constexpr (sizeof(KeyT) == 8)
-            hipLaunchKernelGGL(k_rank_hash<0>, dim3((n + 255) / 256), dim3(256), 0, st, res, off, kmer_off, n, c->rp, keys_in, vals_in, (uint32_t *) nullptr);
-    } else {
-        const uint64_t tiles = (m + RANK_TILE - 1) / RANK_TILE;
-        hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, res, off, kmer_off, n, m, n_res, c->rp,
-                           keys_in, vals_in, 0u, (uint32_t *) nullptr);
-    }
-    PDL_HIP(hipGetLastError());
+    rank_new_genes<KeyT>(c, res, off, kmer_off, n, m, n_res, keys_in, vals_in);
     pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
     scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_out}, RecScatter<KeyT>{keys_out, vals_out, m, recpos, post}, d_u);
     return keys_out;
@@ -1517,6 +1531,152 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t *d_u) {
     if (c->key64) return query_dictionary<uint64_t>(c, res, off, kmer_off, n, m, n_res, (uint64_t *) keys_a, (uint64_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
     return query_dictionary<uint32_t>(c, res, off, kmer_off, n, m, n_res, (uint32_t *) keys_a, (uint32_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K-append (pdl_append_genomes): new genes join the dictionary that is there.
+//
+//   A-alpha   k_q_alpha (pdl_query.h)   the new bytes against the base's letters — the only refusal that needs the device, so
+//                                       it comes first: until the host has read its word the context is untouched
+//   A-len     (host)                    kseq_len / k-mer offsets of the new genes; kseq_len, cost, genome ids grown to N + n
+//   A-dict    k_rank / k_rank_hash + pdl_sort_pairs on the m new k-mers with the base's RankParams (gene values 0..n-1)
+//   A-merge   pdl_merge_streams (pdl_append.h)   (keys_b, vals_b)[M] + the new stream -> the free half of the ping-pong; the
+//                                       new genes' ids get their N there
+//   tail      K-rle over the M + m stream, task layout, K-groups / K-ranges / K-cost: the build's own stages
+//
+// Nothing behind K-rank reads residues, and the stream the tail starts from equals the union's sort (see pdl_append.h), so
+// the context ends up as pdl_preprocess on the union leaves it.
+// ------------------------------------------------------------------------------------------------
+template <class KeyT>
+static void append_sorted_stream(pdl_ctx *c, uint32_t n, uint64_t m, uint64_t n_res, uint32_t n_base, uint64_t m_base) {
+    auto &q = c->qb;
+    KeyT *k_in = q.keys_a.as<KeyT>(), *k_out = q.keys_b.as<KeyT>();
+    uint32_t *v_in = q.vals_a.as<uint32_t>(), *v_out = q.vals_b.as<uint32_t>();
+    ev_begin(c, EV_RANK);
+    rank_new_genes<KeyT>(c, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, m, n_res, k_in, v_in);
+    ev_end(c, EV_RANK);
+    ev_begin(c, EV_SORT1);
+    pdl_sort_pairs<KeyT>(c, k_in, k_out, v_in, v_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+    ev_end(c, EV_SORT1);
+    // what the sort ordered the base by: every bit of a rank — or, for ranks that wrapped unnoticed, the whole bytes its passes went over
+    const uint32_t sorted_bits = c->rp.key_bits == c->rp.rank_bits ? 64u : std::min<uint32_t>(64u, 8u * ((c->rp.rank_bits + 7) / 8));
+    const KeyT mask = sorted_bits >= 8 * sizeof(KeyT) ? (KeyT) ~(KeyT) 0 : (KeyT) (((KeyT) 1 << (sorted_bits & (8 * sizeof(KeyT) - 1))) - 1);
+    ev_begin(c, EV_MERGE);
+    pdl_merge_streams<KeyT>(c->stream, c->keys_b.as<KeyT>(), c->vals_b.as<uint32_t>(), (uint32_t) m_base, k_out, v_out, (uint32_t) m, n_base, mask,
+                            c->scan_tmp.as<uint32_t>(), c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>());
+    ev_end(c, EV_MERGE);
+    std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes);      // the sorted stream is what keys_b / vals_b name
+    std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes);
+}
+
+void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_ids, uint32_t n, uint32_t n_new_genomes,
+                    pdl_append_info *info) {
+    hipStream_t st = c->stream;
+    auto &q = c->qb;
+    const uint32_t N0 = c->N, G0 = c->G, k = c->rp.k;
+    const uint64_t M0 = c->M, U0 = c->U;
+    if ((uint64_t) N0 + n >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu genes in the union exceed the 31-bit gene ids", (unsigned long long) N0 + n);
+    const uint64_t r0 = offsets[0], Rq = offsets[n] - r0;
+    if (c->R + Rq >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the union need 64-bit stream positions");
+    std::vector<uint64_t> h_off(n + 1), h_koff(n + 1);
+    std::vector<uint32_t> h_kseq(n);
+    uint64_t m = 0;
+    for (uint32_t g = 0; g < n; g++) {
+        const uint64_t len = offsets[g + 1] - offsets[g];
+        h_off[g] = offsets[g] - r0;
+        h_koff[g] = m;
+        h_kseq[g] = len >= k ? (uint32_t) (len - k + 1) : 0u;        // (len < 2^32: checked above)
+        m += h_kseq[g];
+    }
+    h_off[n] = Rq; h_koff[n] = m;
+    if (M0 + m >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu k-mers in the union need 64-bit stream positions", (unsigned long long) (M0 + m));
+    for (hipEvent_t &e : c->app_ev) if (!e) PDL_HIP(hipEventCreate(&e));
+
+    // A-alpha (and the new genes on their way to the device): the context is only read
+    PDL_HIP(hipEventRecord(c->app_ev[0], st));
+    q.ctl.alloc(16 * sizeof(uint64_t));
+    unsigned long long *d_bad = q.ctl.as<unsigned long long>();
+    PDL_HIP(hipMemsetAsync(d_bad, 0, sizeof(uint64_t), st));
+    q.res.alloc(Rq + 16); q.off.alloc((n + 1) * 8ull); q.koff.alloc((n + 1) * 8ull); q.kseq.alloc(n * 4ull);
+    if (Rq) PDL_HIP(hipMemcpyAsync(q.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.off.p, h_off.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.koff.p, h_koff.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
+    pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, d_bad);
+    PDL_HIP(hipEventRecord(c->app_ev[1], st));
+    {
+        PinRead rd(c);
+        const uint64_t *pb = rd.add<uint64_t>(d_bad, 1);
+        rd.sync();
+        if (pb[0]) pdl_fail_absent_byte(pb[0], "appended");
+    }
+
+    // from here on the context changes; a failure leaves it un-preprocessed
+    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
+    c->mirror_valid = false; c->edges_valid = false;
+    const uint32_t N1 = N0 + n, G1 = G0 + n_new_genomes;
+    const uint64_t M1 = M0 + m;
+    const size_t kb = c->key64 ? 8 : 4;
+    // A-len: the per-gene arrays grow (k-mer counts keep their contents), the genome ids move into the context's own buffer
+    c->kseq_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
+    c->cost.alloc((size_t) N1 * sizeof(uint64_t));
+    const bool ids_on_device = c->d_gen && (c->d_gen == c->in_gen.p || c->d_gen == c->ing_gen.p);     // (a caller's buffer may be gone: the host copy serves)
+    const bool ids_owned = c->d_gen && c->d_gen == c->own_gen.p;
+    if (ids_owned) c->own_gen.grow_keep((size_t) N1 * sizeof(uint32_t), st); else c->own_gen.alloc((size_t) N1 * sizeof(uint32_t));
+    const uint32_t *old_gen = c->d_gen;
+    pdl_extend_layout(c, genome_ids, n);                  // N, G, h_genome_of, genome rows
+    c->M = M1; c->R += Rq;
+    c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
+    const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
+    c->scalars.alloc(ctl_words * sizeof(uint64_t));
+    if (m) {
+        c->keys_a.alloc(M1 * kb); c->vals_a.alloc(M1 * sizeof(uint32_t));
+        q.keys_a.alloc(m * kb); q.keys_b.alloc(m * kb); q.vals_a.alloc(m * 4); q.vals_b.alloc(m * 4);
+        c->scan_tmp.alloc(pdl_merge_split_words(M1) * sizeof(uint32_t));
+    }
+
+    PDL_HIP(hipEventRecord(c->app_ev[2], st));
+    uint64_t *d_scal = c->scalars.as<uint64_t>();
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
+    PDL_HIP(hipGetLastError());
+    PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
+    if (ids_owned) {
+        PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
+    } else if (ids_on_device) {
+        PDL_HIP(hipMemcpyAsync(c->own_gen.p, old_gen, (size_t) N0 * 4, hipMemcpyDeviceToDevice, st));
+        PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
+    } else {
+        PDL_HIP(hipMemcpyAsync(c->own_gen.p, c->h_genome_of.data(), (size_t) N1 * 4, hipMemcpyHostToDevice, st));
+    }
+    c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
+    if (m) {
+        if (c->key64) append_sorted_stream<uint64_t>(c, n, m, Rq, N0, M0);
+        else append_sorted_stream<uint32_t>(c, n, m, Rq, N0, M0);
+    }
+    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
+    ev_end(c, EV_DICT);
+    pdl_prepare_tasks(c);
+    stage_ranges_and_costs(c, M1, 1, false);
+    PDL_HIP(hipEventRecord(c->app_ev[3], st));
+    PDL_HIP(hipStreamSynchronize(st));
+    if (c->opt_low_memory) {                  // as a build does: what only the build needed goes back
+        c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
+    }
+    float ms0 = 0.f, ms1 = 0.f;
+    (void) hipEventElapsedTime(&ms0, c->app_ev[0], c->app_ev[1]);
+    (void) hipEventElapsedTime(&ms1, c->app_ev[2], c->app_ev[3]);
+    const float rank_ms = ev_ms(c, EV_RANK), sort_ms = ev_ms(c, EV_SORT1), merge_ms = ev_ms(c, EV_MERGE);
+    pdl_timings t{};                          // the preprocess fields describe the append, the scoring fields start again
+    t.rank_ms = rank_ms; t.sort_rank_ms = sort_ms + merge_ms; t.dict_ms = ev_ms(c, EV_DICT);
+    t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
+    t.preprocess_total_ms = ms0 + ms1;
+    c->tm = t;
+    if (info) {
+        info->residues = Rq; info->kmer_occurrences = m;
+        info->records = c->U - U0;            // (a record belongs to one gene: the base's records are all still there)
+        info->rank_sort_ms = rank_ms + sort_ms; info->merge_ms = merge_ms; info->device_ms = ms0 + ms1;
+    }
 }
 
 void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity) {

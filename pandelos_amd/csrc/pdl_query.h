@@ -82,6 +82,21 @@ __global__ __launch_bounds__(256) void k_q_alpha(QAlphaArgs a) {
     }
     if (worst) atomicMax(a.bad, (unsigned long long) worst);
 }
+// Host side of the letter check, shared with the append (pdl_dict.hip): queue k_q_alpha over n device bytes; the word it leaves
+// at d_bad is turned into the refusal by pdl_fail_absent_byte (`who`: "query" / "appended").
+void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad) {
+    if (!n) return;
+    QAlphaArgs aa{};
+    aa.res = d_res; aa.n = n; aa.bad = d_bad;
+    for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
+    hipLaunchKernelGGL(k_q_alpha, dim3((uint32_t) std::min<uint64_t>((n + 255) / 256, 1024)), dim3(256), 0, c->stream, aa);
+    PDL_HIP(hipGetLastError());
+}
+void pdl_fail_absent_byte(uint64_t bad_word, const char *who) {
+    const uint32_t b = 256u - (uint32_t) bad_word;
+    PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s byte 0x%02x ('%c') is not in the base's alphabet: the union would rank k-mers differently", who, b,
+             (b >= 32 && b < 127) ? (char) b : '?');
+}
 
 template <class KeyT> struct QView {
     const KeyT *bkeys; const uint32_t *brecpos; const uint32_t *bvals; const uint2 *post; uint32_t U; uint64_t M;
@@ -497,13 +512,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     PDL_HIP(hipMemcpyAsync(q.off.p, h_off.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
     PDL_HIP(hipMemcpyAsync(q.koff.p, h_koff.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
     PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
-    if (Rq) {
-        QAlphaArgs aa{};
-        aa.res = q.res.as<uint8_t>(); aa.n = Rq; aa.bad = ctl + Q_CTL_BAD_BYTE;
-        for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
-        hipLaunchKernelGGL(k_q_alpha, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
-        PDL_HIP(hipGetLastError());
-    }
+    pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
 
     // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look below)
     const void *qkeys = nullptr;
@@ -548,11 +557,7 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         memcpy(h_ctl, pc, sizeof(h_ctl));
     }
     span_begin();
-    if (h_ctl[Q_CTL_BAD_BYTE]) {
-        const uint32_t b = 256u - (uint32_t) h_ctl[Q_CTL_BAD_BYTE];
-        PDL_FAIL(PDL_ERR_UNSUPPORTED, "query byte 0x%02x ('%c') is not in the base's alphabet: the union would rank k-mers differently", b,
-                 (b >= 32 && b < 127) ? (char) b : '?');
-    }
+    if (h_ctl[Q_CTL_BAD_BYTE]) pdl_fail_absent_byte(h_ctl[Q_CTL_BAD_BYTE], "query");
     const uint64_t Uq = h_ctl[Q_CTL_RECORDS], cost = h_ctl[Q_CTL_COST], matched = h_ctl[Q_CTL_MATCHED], bound = h_ctl[Q_CTL_BOUND],
                    may_overflow = h_ctl[Q_CTL_MAY_OVERFLOW];
     if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);

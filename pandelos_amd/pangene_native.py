@@ -160,6 +160,34 @@ class PangeneNative:
             raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
         return self.query_scores(residues, offsets)
 
+    def append(self, residues, offsets, genome_of=None) -> None:
+        """New genomes join this dictionary by a merge, without a rebuild (``pdl_append_genomes``): the genes become ids
+        N..N+n-1, all of one new genome G = ``cost.genomes`` (``genome_of`` None) or of the union ids ``genome_of`` (G, G+1, ...
+        in first-seen order).  Afterwards the context is the one ``preprocess`` on the union would leave; ``cost`` is the
+        union's and ``last_append_info`` holds the call's sizes and device times as a dict.  A refusal leaves everything as
+        it was."""
+        res = np.ascontiguousarray(residues, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or len(off) < 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n + 1 entries")
+        gen = None
+        if genome_of is not None:
+            gen = np.ascontiguousarray(genome_of, dtype=np.uint32)
+            if gen.shape != (len(off) - 1,):
+                raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "genome_of must hold one id per gene")
+        cost, info = _lib.PdlCost(), _lib.PdlAppendInfo()
+        self._check(self._lib.pdl_append_genomes(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data,
+                                                 gen.ctypes.data if gen is not None and gen.size else None, len(off) - 1,
+                                                 C.byref(cost), C.byref(info)))
+        self.cost = cost
+        self.last_append_info = info.as_dict()
+
+    def append_idata(self, data: PangeneIData) -> None:
+        """``append`` for the genes of a ``PangeneIData`` (one genome or several): its genome ids 0, 1, ... become
+        G, G+1, ... of this context."""
+        residues, offsets, genome_of = data.flatten()
+        self.append(residues, offsets, genome_of + np.uint32(self.cost.genomes))
+
     def _take_scores(self, s) -> Scores:
         try:
             z, rows, g, n = s.scoresCount, s.rows, s.genomes, s.sequences
