@@ -255,6 +255,40 @@ PDL_API int pdl_append_genomes(pdl_ctx *, const uint8_t *residues, const uint64_
                                const uint32_t *genome_of /* [n] or NULL */, uint32_t n,
                                pdl_cost *out_cost /* may be NULL: the union's */, pdl_append_info *info /* may be NULL */);
 
+/* ---- gene families: the network's components and their collisions, on the device, from the edges where they lie --------
+ * What netclu_ng.py does with the .net before Girvan-Newman: the connected components of the gene network (:58-66) and, per
+ * component, whether it holds a collision — two genes of one genome that are not adjacent (get_max_collision, :75-92).  A
+ * component without one is a gene family as it stands; only the colliding ones need the host's split
+ * (pandelos_amd/netclu.py, families_from_components).  Edges are read as netclu_ng.py:41-56 reads them: undirected, a repeated
+ * pair is one edge, a self edge makes its gene a node but is no edge.
+ * pdl_compute_families: over the context's own edges — runs the scoring pass and the best-hit filter on first use, like
+ * pdl_compute_edges, then K-fam over the edges in HBM (no edge crosses PCIe for it).  Cached until the next preprocess, append
+ * or scoring pass; scores, edges, dictionary, costs and pdl_timings are left as they were; after pdl_append_genomes it answers
+ * for the union.  PDL_ERR_STATE before a preprocess, after only_complexity, on a multi-GPU context, and with a genome shard in
+ * force (genome batches, option "low_memory"): the context then does not hold every genome's edges — gather them and use
+ * pdl_families_of_edges: the same kernels over a caller's edge list (host pointers; of the context only the device, the stream
+ * and work buffers are used, no preprocess is needed and the context's own state is not changed).  PDL_ERR_ARGUMENT: NULL
+ * pointers, a gene id that is negative or >= n_sequences (counted on the device BEFORE anything is indexed by an id; an error
+ * return, nothing more).  n_edges == 0 is legal: nodes = families = 0.  Free with pdl_free_families. */
+typedef struct {
+    uint32_t sequences;       /* N */
+    uint32_t nodes;           /* genes with at least one edge (self edges count): len(adj) of netclu.read_net */
+    uint32_t families;        /* F: connected components of the network */
+    uint32_t colliding;       /* components that hold a collision (netclu_ng.py:75-92) */
+    uint32_t *component_of;   /* [N] smallest gene id of the gene's component; its own id for a gene that is no node */
+    uint8_t  *is_node;        /* [N] */
+    uint32_t *family_off;     /* [F+1] into family_genes; families in ascending order of their label */
+    uint32_t *family_genes;   /* [nodes] ascending gene ids inside a family */
+    uint8_t  *collides;       /* [F] */
+    float device_ms;          /* sum of the stretches of device work (HIP event pairs: the id check of a caller's list, then
+                                 everything up to the read of the counts), as pdl_query_info.device_ms; uploads and the copies
+                                 of the arrays to the host are not in it */
+} pdl_families;
+PDL_API int pdl_compute_families(pdl_ctx *, pdl_families *out);
+PDL_API int pdl_families_of_edges(pdl_ctx *, const int32_t *src, const int32_t *dst, uint64_t n_edges,
+                                  const uint32_t *genome_of /* [n_sequences] */, uint32_t n_sequences, pdl_families *out);
+PDL_API void pdl_free_families(pdl_families *);
+
 /* Number of emitted cells per genome after pdl_score_all ([G], 0 for genomes outside the shard) */
 PDL_API int pdl_scores_counts(pdl_ctx *, uint32_t *out_counts);
 

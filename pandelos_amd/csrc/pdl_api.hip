@@ -78,6 +78,7 @@ void pdl_destroy(pdl_ctx *c) {
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
     for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : c->fb.ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
@@ -535,6 +536,78 @@ int pdl_compute_edges(pdl_ctx *c, uint32_t genome, pdl_edges *out) {
     return PDL_OK;
     } catch (const pdl_error &e) { { std::lock_guard<std::mutex> lk(c->mu); c->err = e.msg; } pdl_free_edges(out); return e.code;
     } catch (const std::bad_alloc &) { { std::lock_guard<std::mutex> lk(c->mu); c->err = "host allocation failed"; } pdl_free_edges(out); return PDL_ERR_DEVICE; }
+}
+
+// ---- K-fam (pdl_families.h) -------------------------------------------------------------------------------------------------
+void pdl_free_families(pdl_families *f) {
+    if (!f) return;
+    free(f->component_of); free(f->is_node); free(f->family_off); free(f->family_genes); free(f->collides);
+    memset(f, 0, sizeof(*f));
+}
+
+static void fill_families(const pdl_fam_result &r, pdl_families *out) {
+    out->sequences = r.sequences; out->nodes = r.nodes; out->families = r.families; out->colliding = r.colliding; out->device_ms = r.device_ms;
+    out->component_of = xalloc<uint32_t>(r.component_of.size()); out->is_node = xalloc<uint8_t>(r.is_node.size());
+    out->family_off = xalloc<uint32_t>(r.family_off.size()); out->family_genes = xalloc<uint32_t>(r.family_genes.size());
+    out->collides = xalloc<uint8_t>(r.collides.size());
+    if (!r.component_of.empty()) memcpy(out->component_of, r.component_of.data(), r.component_of.size() * 4);
+    if (!r.is_node.empty()) memcpy(out->is_node, r.is_node.data(), r.is_node.size());
+    memcpy(out->family_off, r.family_off.data(), r.family_off.size() * 4);
+    if (!r.family_genes.empty()) memcpy(out->family_genes, r.family_genes.data(), r.family_genes.size() * 4);
+    if (!r.collides.empty()) memcpy(out->collides, r.collides.data(), r.collides.size());
+}
+
+int pdl_compute_families(pdl_ctx *c, pdl_families *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    try {
+        // the refusals first: nothing of the context has been touched when one of them returns
+        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families before pdl_preprocess");
+        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: the context was preprocessed with only_complexity");
+        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: not available on a multi-GPU context (gather the edges: pdl_families_of_edges)");
+        if (c->shard_set || !c->dict_shard.empty())
+            PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: a genome shard is in force, the context does not hold every genome's edges (gather them: pdl_families_of_edges)");
+        int rc = c->scored ? PDL_OK : score_all_locked(c);
+        if (rc != PDL_OK) return rc;
+        PDL_HIP(hipSetDevice(c->device));
+        if (!c->edges_valid) pdl_run_bbh_all(c);
+        if (!c->fam_valid) pdl_run_families_of_context(c);
+        fill_families(c->fam, out);
+        return PDL_OK;
+    } catch (const pdl_error &e) { c->err = e.msg; c->fam_valid = false; pdl_free_families(out); return e.code;
+    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_families(out); return PDL_ERR_DEVICE; }
+}
+
+int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, uint64_t n_edges, const uint32_t *genome_of, uint32_t n_sequences,
+                          pdl_families *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    try {
+        if ((n_edges && (!src || !dst)) || (n_sequences && !genome_of)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_families_of_edges: NULL pointer");
+        if (n_edges >= 0x7fffffffull || n_sequences >= 0x7fffffffu) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_families_of_edges: 2^31 genes or edges and more");
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_ctx::FamBufs &b = c->fb;
+        uint32_t g_max = 0;
+        for (uint32_t i = 0; i < n_sequences; i++) g_max = std::max(g_max, genome_of[i]);
+        if (n_edges) {
+            b.up_src.alloc(n_edges * 4); b.up_dst.alloc(n_edges * 4);
+            PDL_HIP(hipMemcpyAsync(b.up_src.p, src, n_edges * 4, hipMemcpyHostToDevice, c->stream));
+            PDL_HIP(hipMemcpyAsync(b.up_dst.p, dst, n_edges * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        if (n_sequences) {
+            b.up_gen.alloc((size_t) n_sequences * 4);
+            PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) n_sequences * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        const int32_t *s2[2] = {b.up_src.as<int32_t>(), nullptr}, *d2[2] = {b.up_dst.as<int32_t>(), nullptr};
+        const uint64_t n2[2] = {n_edges, 0};
+        pdl_fam_result r;
+        pdl_run_families(c, s2, d2, n2, false, true, true, b.up_gen.as<uint32_t>(), n_sequences, bit_length64(g_max), r);
+        fill_families(r, out);
+        return PDL_OK;
+    } catch (const pdl_error &e) { c->err = e.msg; pdl_free_families(out); return e.code;
+    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_families(out); return PDL_ERR_DEVICE; }
 }
 
 int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {

@@ -85,6 +85,7 @@ void pdl_run_bbh_all(pdl_ctx *c) {
     c->h_edge_off.assign((size_t) S + 1, 0);
     c->h_edge1.assign((size_t) S + 1, 0);
     c->edges_valid = true;
+    c->fam_valid = false;              // (K-fam's answer was for the edges before these)
     if (Z == 0 || n_rows == 0) { c->n_edges = 0; return; }
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells on one device");
     c->bbh_kind.alloc(Z + 16);
@@ -152,4 +153,17 @@ void pdl_run_bbh_all(pdl_ctx *c) {
     PDL_HIP(hipStreamSynchronize(st));
     c->n_edges1 = n1;
     for (uint32_t i = 0; i <= S; i++) { c->h_edge1[i] = 2ull * h1[i]; c->h_edge_off[i] = h2[i]; }      // phase-1 edge offsets, phase-2 edge offsets
+}
+
+#include "pdl_families.h"        // K-fam: components, families and collision flags from these edges (pdl_compute_families)
+
+// K-fam over the edges K-bbh left in e_src / e_dst: phase 1 at the front (every pair in both directions), phase 2 behind the
+// room of 2 Z phase-1 edges.
+void pdl_run_families_of_context(pdl_ctx *c) {
+    const uint64_t Z = c->h_cell_off.empty() ? 0 : c->h_cell_off.back();
+    const uint64_t n1 = c->n_edges ? c->n_edges1 : 0, n2 = c->n_edges - n1;          // (a context without a cell has no edge list at all)
+    const int32_t *src[2] = {c->e_src.as<int32_t>(), c->e_src.as<int32_t>() + 2 * Z}, *dst[2] = {c->e_dst.as<int32_t>(), c->e_dst.as<int32_t>() + 2 * Z};
+    const uint64_t n[2] = {n1, n2};
+    pdl_run_families(c, src, dst, n, true, false, false, c->d_gen, c->N, bit_length64(c->G ? c->G - 1 : 0), c->fam);
+    c->fam_valid = true;
 }

@@ -69,6 +69,16 @@ enum : size_t {
     PDL_CTL_LAZY_KSEQ_SUM = 13, // pdl_ensure_costs: where k_genome_cost's three statistics go when only its per-genome sums are
     PDL_CTL_LAZY_KSEQ_MAX = 14, //   wanted (max, ~min: 14, 15); after a build, with no sort in flight
     PDL_CTL_SELECT_TOTAL = 15,  // total of the multi-GPU selection scan, between K-rank and the slice's sort
+    // K-fam (pdl_families.h) runs behind K-bbh's read of its totals, or on a caller's edges; k_fam_init clears FIRST..LAST, every
+    // word is read before the call returns, and the sorts in the middle of it keep to SCAN_TOTAL
+    PDL_CTL_FAM_FIRST = 10,
+    PDL_CTL_FAM_BAD_IDS = 10,   // F-check: edges that name a gene id outside [0, N); read before F-cc starts ...
+    PDL_CTL_FAM_RUNS = 10,      // ... then the total of the (label, genome) run scan (nobody reads it)
+    PDL_CTL_FAM_NODES = 11,     // genes that are a node (stored by the family scan's apply functor); NODES..COLLIDING leave in one read
+    PDL_CTL_FAM_FAMILIES = 12,  // F: total of the family scan
+    PDL_CTL_FAM_COLLIDING = 13, // families that hold a collision
+    PDL_CTL_FAM_INTRA = 14,     // a caller's edges: intra-genome edges before de-duplication (total of their compaction, the sort's count)
+    PDL_CTL_FAM_LAST = 14,
 
     PDL_CTL_HIST = 16,          // residue histogram [256]
     PDL_CTL_GCOST = 16 + 256,   // per-genome cost [G] (+ [G] lookups above the diagonal, multi-GPU)
@@ -180,6 +190,14 @@ struct RankParams {
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     bool used = false;
+};
+
+// what one run of K-fam (pdl_families.h) leaves on the host: pdl_families without the C allocation
+struct pdl_fam_result {
+    uint32_t sequences = 0, nodes = 0, families = 0, colliding = 0;
+    std::vector<uint32_t> component_of, family_off, family_genes;
+    std::vector<uint8_t> is_node, collides;
+    float device_ms = 0.f;
 };
 
 // ---- the context --------------------------------------------------------------------------------
@@ -362,6 +380,18 @@ struct pdl_ctx {
             hbm_clean = false; hbm_cols = hbm_slots = 0; rec_sorted_at = nullptr;
         }
     } qb;
+    // K-fam (pdl_families.h): work buffers of a run (grown as needed, shared by pdl_compute_families and pdl_families_of_edges) and
+    // the context's own families, kept on the host until the edges change (pdl_run_bbh_all drops them)
+    struct FamBufs {
+        DevBuf parent, comp, same_deg, is_node, collides, fam_off, fam_of_label, run_off, run_of;
+        DevBuf mk_a, mk_b, mv_a, mv_b;              // F-members: (label, gene) sort
+        DevBuf ck_a, ck_b, cv_a, cv_b;              // F-collide: by genome, then by label
+        DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: intra-genome (lo, hi) keys and the sort's unused values
+        DevBuf up_src, up_dst, up_gen;              // a caller's edges and genome ids on the device
+        hipEvent_t ev[4] = {};                      // start / end of the id check and of the rest
+    } fb;
+    bool fam_valid = false;
+    pdl_fam_result fam;
     hipEvent_t app_ev[4] = {};        // pdl_append_genomes: start / end of its two stretches of device work
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
 
@@ -498,6 +528,10 @@ void pdl_run_dist_score_begin(pdl_ctx *c);
 void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_t n_inbox);
 void pdl_prepare_tasks(pdl_ctx *c);
 void pdl_run_bbh_all(pdl_ctx *c);
+// K-fam (pdl_families.h, pdl_bbh.hip): components, members and collision flags from up to two device edge lists
+void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *const dst[2], const uint64_t n_edges[2], bool mirrored0, bool check_ids,
+                      bool dedupe_intra, const uint32_t *d_gen, uint32_t N, uint32_t genome_bits, pdl_fam_result &out);
+void pdl_run_families_of_context(pdl_ctx *c);       // ... over the context's own edges (K-bbh has run) -> c->fam
 void pdl_ensure_costs(pdl_ctx *c);
 void pdl_input_arrived(pdl_ctx *c);      // deferred device input: waits for the genome ids / offset ends and checks them
 void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on the host

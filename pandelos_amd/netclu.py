@@ -25,7 +25,7 @@ from __future__ import annotations
 
 import sys
 from collections import deque
-from typing import Dict, Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 Adj = Dict[int, Dict[int, None]]          # node -> neighbours, both in insertion order
 
@@ -69,10 +69,12 @@ def view_filter(nodes: Iterable[int], member) -> set:
     return set(n for n in nodes if member(n))
 
 
-def view_adjacency(root: Adj, filt: set) -> Adj:
+def view_adjacency(root: Adj, filt: set, root_len: Optional[int] = None) -> Adj:
     """Nodes and neighbours of the subgraph view in the order networkx iterates them (``FilterAtlas.__iter__``): through the
-    FILTER SET when it is less than half as long as the underlying dict, through the dict otherwise."""
-    order = [n for n in filt if n in root] if 2 * len(filt) < len(root) else [n for n in root if n in filt]
+    FILTER SET when it is less than half as long as the underlying dict, through the dict otherwise.  ``root_len``: the node
+    count of the whole network where ``root`` holds only a part of it (``families_from_components``)."""
+    n_root = len(root) if root_len is None else root_len
+    order = [n for n in filt if n in root] if 2 * len(filt) < n_root else [n for n in root if n in filt]
     out: Adj = {}
     for u in order:
         nb = root[u]
@@ -196,12 +198,12 @@ def max_collision(nodes: Sequence[int], adj: Adj, genome_of: Sequence[str]) -> i
     return worst
 
 
-def split_until_clean(filt: set, root: Adj, genome_of: Sequence[str]) -> List[List[int]]:
+def split_until_clean(filt: set, root: Adj, genome_of: Sequence[str], root_len: Optional[int] = None) -> List[List[int]]:
     """netclu_ng.py:97-111 (``split_until_max_k``) on the subgraph view with node filter ``filt``."""
     out: List[List[int]] = []
-    for com in (sorted(c) for c in girvan_newman_first_level(view_adjacency(root, filt))):
+    for com in (sorted(c) for c in girvan_newman_first_level(view_adjacency(root, filt, root_len))):
         if max_collision(com, root, genome_of) > 0:
-            out += split_until_clean(view_filter(com, filt.__contains__), root, genome_of)      # a view of a view: filter on the root graph
+            out += split_until_clean(view_filter(com, filt.__contains__), root, genome_of, root_len)      # a view of a view: filter on the root graph
         else:
             out.append(com)
     return out
@@ -220,6 +222,40 @@ def families(names: Sequence[str], genome_of: Sequence[str], adj: Adj) -> Tuple[
             fams.append(sorted(part))
             placed.update(part)
     return fams, [g for g in range(len(names)) if g not in placed]
+
+
+def families_from_components(names: Sequence[str], genome_of: Sequence, fam: dict, src, dst,
+                             net_ordered: bool = False) -> Tuple[List[List[int]], List[int]]:
+    """``families`` from the components the device found (``pdl_families`` as ``PangeneNative.generate_families`` returns it:
+    ``family_off``, ``family_genes``, ``collides``, ``is_node``, ``component_of``, ``nodes``) and the edges (``src``, ``dst``) in
+    insertion order.  A clean component is a family as it comes.  The genes of the colliding components are split by
+    ``split_until_clean`` on the sub-network of just those components: its adjacency is filled in ``.net`` line order
+    (``pangenes.net_line_order``), so every component of it has the node and neighbour orders it has in the whole network,
+    and the one place where the whole network's size shows (``view_adjacency``) is handed ``nodes``.  ``net_ordered``: the
+    edges ARE the lines of a ``.net``, in its order (a network read back from disk), so no order is derived."""
+    import numpy as np
+    from .pangenes import net_line_order
+    off, genes = np.asarray(fam["family_off"]), np.asarray(fam["family_genes"])
+    collides, comp_of = np.asarray(fam["collides"]).astype(bool), np.asarray(fam["component_of"])
+    fams: List[List[int]] = [genes[off[f]:off[f + 1]].tolist() for f in np.nonzero(~collides)[0]]
+    if collides.any():
+        src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+        in_bad = np.zeros(len(comp_of), bool)
+        in_bad[genes[off[:-1]][collides]] = True                  # (a family's first gene is its label)
+        order = np.arange(len(src)) if net_ordered else net_line_order(src, dst)
+        order = order[in_bad[comp_of[src[order]]]]
+        sub: Adj = {}
+        for a, b in zip(src[order].tolist(), dst[order].tolist()):      # as read_net fills it
+            if a not in sub:
+                sub[a] = {}
+            if a != b:
+                if b not in sub:
+                    sub[b] = {}
+                sub[a][b] = None
+                sub[b][a] = None
+        for comp in connected_components(sub):
+            fams += [sorted(part) for part in split_until_clean(view_filter(comp, sub.__contains__), sub, genome_of, int(fam["nodes"]))]
+    return fams, np.nonzero(np.asarray(fam["is_node"]) == 0)[0].tolist()
 
 
 def clus_text(names: Sequence[str], fams: Sequence[Sequence[int]], singletons: Sequence[int]) -> str:

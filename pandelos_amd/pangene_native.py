@@ -216,6 +216,41 @@ class PangeneNative:
         finally:
             self._lib.pdl_free_edges(C.byref(e))
 
+    def generate_families(self) -> dict:
+        """K-fam over this context's own edges, where they lie in HBM (``pdl_compute_families``): the network's connected
+        components and their collision flags -> the fields of ``pdl_families`` as a dict (counts as ints, arrays as numpy).
+        ``netclu.families_from_components`` makes the gene families of it.  ``last_families_info`` holds the counts and the
+        device time."""
+        f = _lib.PdlFamilies()
+        self._check(self._lib.pdl_compute_families(self._ctx, C.byref(f)))
+        return self._take_families(f)
+
+    def families_of_edges(self, src, dst, genome_of) -> dict:
+        """The same kernels over a caller's edge list (``pdl_families_of_edges``): gene ids ``src`` / ``dst``, one genome id per
+        gene — a network gathered from genome batches or from several ranks.  Needs no preprocess and leaves the context's own
+        state alone."""
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        d = np.ascontiguousarray(dst, dtype=np.int32)
+        g = np.ascontiguousarray(genome_of, dtype=np.uint32)
+        if s.ndim != 1 or s.shape != d.shape or g.ndim != 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "src and dst must be two vectors of one length, genome_of a vector")
+        f = _lib.PdlFamilies()
+        self._check(self._lib.pdl_families_of_edges(self._ctx, s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, len(s),
+                                                    g.ctypes.data if g.size else None, len(g), C.byref(f)))
+        return self._take_families(f)
+
+    def _take_families(self, f) -> dict:
+        try:
+            n, nodes, fams = f.sequences, f.nodes, f.families
+            out = {"sequences": n, "nodes": nodes, "families": fams, "colliding": f.colliding,
+                   "component_of": _np_copy(f.component_of, np.uint32, n), "is_node": _np_copy(f.is_node, np.uint8, n),
+                   "family_off": _np_copy(f.family_off, np.uint32, fams + 1), "family_genes": _np_copy(f.family_genes, np.uint32, nodes),
+                   "collides": _np_copy(f.collides, np.uint8, fams)}
+            self.last_families_info = {"sequences": n, "nodes": nodes, "families": fams, "colliding": f.colliding, "device_ms": f.device_ms}
+        finally:
+            self._lib.pdl_free_families(C.byref(f))
+        return out
+
     # -- beyond the reference surface (device-resident batch, sharding, introspection) ------------------
     def score_all(self) -> None:
         self._check(self._lib.pdl_score_all(self._ctx))

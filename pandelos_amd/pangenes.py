@@ -82,16 +82,17 @@ def _java_double_str(values: np.ndarray) -> List[str]:
     return out
 
 
-def net_lines(src: np.ndarray, dst: np.ndarray, score: np.ndarray) -> List[str]:
-    """PangeneNet: first insert per (src, dst) wins (TreeSet keyed by dest, :49-62); undirected save (:167-175) walks the
-    sources in java.util.HashMap order (buckets of the final power-of-two table, insertion order inside a bucket) and a
-    source's edges by ascending dest, writing those with src <= dst."""
+def net_line_order(src: np.ndarray, dst: np.ndarray) -> np.ndarray:
+    """Indices into (src, dst), one per line of the saved ``.net`` and in its order.  PangeneNet: first insert per (src, dst)
+    wins (TreeSet keyed by dest, :49-62); undirected save (:167-175) walks the sources in java.util.HashMap order (buckets of
+    the final power-of-two table, insertion order inside a bucket) and a source's edges by ascending dest, writing those with
+    src <= dst."""
     if len(src) == 0:
-        return []
+        return np.zeros(0, np.int64)
     key = (src << 32) | dst
     _, first = np.unique(key, return_index=True)
     first.sort()
-    src, dst, score = src[first], dst[first], score[first]           # one entry per (src, dst), insertion order kept
+    src, dst = src[first], dst[first]                                # one entry per (src, dst), insertion order kept
     usrc, src_first = np.unique(src, return_index=True)              # insertion order of the map keys
     cap = 16
     while len(usrc) > 0.75 * cap:
@@ -101,8 +102,13 @@ def net_lines(src: np.ndarray, dst: np.ndarray, score: np.ndarray) -> List[str]:
     pos = np.empty(int(usrc.max()) + 1, np.int64)
     pos[usrc[np.lexsort((src_first, bucket))]] = np.arange(len(usrc))
     keep = src <= dst
-    src, dst, score = src[keep], dst[keep], score[keep]
-    order = np.lexsort((dst, pos[src]))
+    first, src, dst = first[keep], src[keep], dst[keep]
+    return first[np.lexsort((dst, pos[src]))]
+
+
+def net_lines(src: np.ndarray, dst: np.ndarray, score: np.ndarray) -> List[str]:
+    """The text of the ``.net``: ``net_line_order``'s edges as ``src<TAB>dst<TAB>Double.toString(score)``."""
+    order = net_line_order(src, dst)
     txt = _java_double_str(score[order])
     return [f"{a}\t{b}\t{t}\n" for a, b, t in zip(src[order].tolist(), dst[order].tolist(), txt)]
 
