@@ -255,6 +255,42 @@ PDL_API int pdl_append_genomes(pdl_ctx *, const uint8_t *residues, const uint64_
                                const uint32_t *genome_of /* [n] or NULL */, uint32_t n,
                                pdl_cost *out_cost /* may be NULL: the union's */, pdl_append_info *info /* may be NULL */);
 
+/* ---- remove: genomes leave the dictionary already built, by a compaction instead of a rebuild --------------------------
+ * The genes of the `count` listed genomes leave the context.  After PDL_OK every observable of the context equals, bit for bit,
+ * that of a context on which pdl_preprocess ran with the REMAINING SET: the remaining genes in their input order with ids dense
+ * from 0, the remaining genomes with ids dense in first-seen order (the order they have, closed up), same k, flags and options:
+ * pdl_cost (residues included), pdl_get_dictionary, pdl_get_rank_table, pdl_genome_cost, pdl_sequence_costs, pdl_compute_scores /
+ * pdl_score_all / pdl_scores_counts, pdl_compute_edges, pdl_compute_families, and later queries, appends and removals.  Scores,
+ * edges, families and query buffers of the old context are dropped, as by an append.  Genomes may be interleaved gene by gene,
+ * may be the first, a middle or the last one, and several may go in one call; replace = remove + append, append + remove undoes.
+ * pdl_get_timings: the preprocess stage fields describe the removal — hist_ms and rank_ms 0; sort_rank_ms: the compaction pass over
+ * the sorted k-mer stream (with the gene map and the alphabet check); dict_ms, sort_seq_ms, ranges_ms: the stages behind the sorted
+ * stream, over what remains; preprocess_total_ms = pdl_remove_info.device_ms — and the scoring fields start again at zero.
+ * No residue is needed: the sorted k-mer stream in HBM, sorted by (rank, input position), loses the k-mers of the leaving genes
+ * in one stable pass and the gene ids are renumbered monotonically — the stream pdl_preprocess would sort for the remaining set,
+ * PROVIDED the rank table is the same.
+ * Refusals, checked BEFORE anything is changed (the context stays exactly as it was: scores, edges, dictionary, costs, timings):
+ * PDL_ERR_STATE before a preprocess, after only_complexity, on a multi-GPU context, with a genome shard in force, or after
+ * low_memory released the sorted k-mer stream; PDL_ERR_ARGUMENT for a NULL list, count == 0, an id >= G, an id named twice, every
+ * genome named; PDL_ERR_EMPTY when the remaining genes hold no k-mer (what pdl_preprocess answers for such a set);
+ * PDL_ERR_UNSUPPORTED when the remaining set cannot be shown to have the context's alphabet — if every occurrence of a letter
+ * leaves, the remaining set's rank table differs (library.cpp:96-119).  The proof comes from the keys in HBM: polynomial ranks with
+ * an exact B^k are sum v[c_i] * B^(k-1-i) with dense digits v, so the digits of the keys that stay name letters that are certainly
+ * present; all B of them must show.  A letter that survives only in genes shorter than k is not seen: the refusal is conservative
+ * in that one direction, and the message says so and names the smallest letter not found.  Hashed ranks (hash_fallback) and ranks
+ * that wrapped past 2^64 (22 letters at k = 15 and the like) cannot be decoded and are refused with their own message.  After
+ * PDL_ERR_UNSUPPORTED the caller rebuilds from the remaining genes.
+ * A device failure in the middle (PDL_ERR_DEVICE) leaves the context un-preprocessed: PDL_ERR_STATE until the next pdl_preprocess. */
+typedef struct {
+    uint64_t sequences;                    /* genes that left */
+    uint64_t residues, kmer_occurrences;   /* of those genes */
+    uint64_t records;                      /* their unique (rank, gene) records */
+    float compact_ms;                      /* gene map + compaction pass + alphabet check: the call's first stretch of device work */
+    float device_ms;                       /* the whole call on the device (the sum of its stretches of device work, as pdl_append_info) */
+} pdl_remove_info;
+PDL_API int pdl_remove_genomes(pdl_ctx *, const uint32_t *genomes /* [count] distinct ids < G */, uint32_t count,
+                               pdl_cost *out_cost /* may be NULL: the remaining set's */, pdl_remove_info *info /* may be NULL */);
+
 /* ---- gene families: the network's components and their collisions, on the device, from the edges where they lie --------
  * What netclu_ng.py does with the .net before Girvan-Newman: the connected components of the gene network (:58-66) and, per
  * component, whether it holds a collision — two genes of one genome that are not adjacent (get_max_collision, :75-92).  A

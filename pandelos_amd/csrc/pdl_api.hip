@@ -78,6 +78,7 @@ void pdl_destroy(pdl_ctx *c) {
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
     for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : c->rm.ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->fb.ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
@@ -149,6 +150,11 @@ void pdl_set_create_error(const std::string &msg) { g_create_error = msg; }
 void pdl_extend_layout(pdl_ctx *c, const uint32_t *genome_ids, uint32_t n) {
     c->h_genome_of.insert(c->h_genome_of.end(), genome_ids, genome_ids + n);
     c->N += n;
+    layout_and_shard(c);
+}
+void pdl_replace_layout(pdl_ctx *c, std::vector<uint32_t> &&genome_of) {
+    c->h_genome_of = std::move(genome_of);
+    c->N = (uint32_t) c->h_genome_of.size();
     layout_and_shard(c);
 }
 
@@ -835,6 +841,35 @@ int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offs
     }
     PDL_HIP(hipSetDevice(c->device));
     pdl_run_append(c, residues, offsets, ids.data(), n, g_new, info);
+    c->preprocessed = true;
+    fill_cost(c, out_cost);
+    return PDL_OK;
+    PDL_GUARD_END(c)
+}
+
+int pdl_remove_genomes(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_cost *out_cost, pdl_remove_info *info) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (info) memset(info, 0, sizeof(*info));
+    PDL_GUARD_BEGIN
+    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes before pdl_preprocess");
+    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: the context was preprocessed with only_complexity");
+    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: not available on a multi-GPU context");
+    if (c->shard_set || !c->dict_shard.empty()) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: not available with a genome shard in force");
+    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
+        PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: the sorted k-mer stream was released (option low_memory)");
+    if (!genomes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: NULL pointer");
+    if (count == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: no genome");
+    std::vector<uint8_t> named((size_t) c->G, 0);
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t g = genomes[i];
+        if (g >= c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: genome id %u out of range (%u genomes)", g, c->G);
+        if (named[g]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: genome id %u is named twice", g);
+        named[g] = 1;
+    }
+    if (count == c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: every genome of the context is named (nothing would remain)");
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_run_remove(c, genomes, count, info);
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;

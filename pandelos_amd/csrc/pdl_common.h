@@ -83,6 +83,15 @@ enum : size_t {
     PDL_CTL_HIST = 16,          // residue histogram [256]
     PDL_CTL_GCOST = 16 + 256,   // per-genome cost [G] (+ [G] lookups above the diagonal, multi-GPU)
 };
+// ---- layout of pdl_ctx::rm.ctl (u64 words): what a removal (pdl_remove.h) leaves for the host's one read before the context
+// changes.  A block of its own: a refused removal must not have touched a word of `scalars`.  Cleared by pdl_run_remove.
+enum : size_t {
+    PDL_RM_GENES = 0,           // genes that stay: total of the R-map scan
+    PDL_RM_KMERS = 1,           // their k-mer occurrences: total of the compaction's tile scan
+    PDL_RM_GONE_RESIDUES = 2,   // residues of the genes that leave (added up by R-map)
+    PDL_RM_SEEN = 4,            // u32 [256] (128 words): digit d occurs in a key that stays (R-alpha; every workgroup stores the same 1)
+    PDL_RM_WORDS = 4 + 128,
+};
 
 // ---- layout of pdl_ctx::join_ctr (u32 words): cursors and counters of one scoring pass, cleared by score_join ---------------
 // A tier draws rows through its cursor and lists the rows it hands on; the count of that list is the next tier's work size.
@@ -243,6 +252,7 @@ struct pdl_ctx {
 
     // per sequence
     DevBuf kseq_len;      // u32 [N]
+    DevBuf gene_len;      // u32 [N] residues of each gene (K-len stores it beside kseq_len, which forgets genes shorter than k): a removal's pdl_cost.residues
     DevBuf kmer_off;      // u64 [N+1]
     DevBuf cost;          // u64 [N]   total_visited
     std::vector<uint64_t> h_genome_cost;
@@ -393,6 +403,16 @@ struct pdl_ctx {
     bool fam_valid = false;
     pdl_fam_result fam;
     hipEvent_t app_ev[4] = {};        // pdl_append_genomes: start / end of its two stretches of device work
+    // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
+    struct RemoveBufs {
+        DevBuf gmap;                  // u32 [G] new genome id, RM_GONE for a genome that leaves
+        DevBuf gen_in;                // u32 [N] genome ids, when the context's copy on the device is a caller's buffer that may be gone
+        DevBuf new_id;                // u32 [N] new gene id, RM_GONE for a gene that leaves
+        DevBuf kseq, gen, glen;       // u32 [N'] compacted kseq_len / genome ids / gene_len: they swap places with the context's
+        DevBuf tile;                  // u32 [tiles] k-mers that stay per tile of the stream, then their exclusive scan
+        DevBuf ctl;                   // u64 [PDL_RM_WORDS]
+        hipEvent_t ev[4] = {};        // start / end of its two stretches of device work
+    } rm;
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
 
     pdl_timings tm{};
@@ -548,6 +568,10 @@ void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned l
 void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_ids, uint32_t n, uint32_t n_new_genomes,
                     pdl_append_info *info);
 void pdl_extend_layout(pdl_ctx *c, const uint32_t *genome_ids, uint32_t n);
+// K-remove (pdl_remove.h, pdl_dict.hip): the genes of the `count` listed genomes (distinct ids < G, not all of them: checked by the
+// caller) leave the context.  pdl_replace_layout (pdl_api.hip): the host's genome layout for the genes that stay.
+void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_remove_info *info);
+void pdl_replace_layout(pdl_ctx *c, std::vector<uint32_t> &&genome_of);
 inline uint2 *pdl_postings(const pdl_ctx *c) { return c->post_ext ? c->post_ext : c->post.as<uint2>(); }
 
 // compute units of the context's device (looked up once; 256 where the runtime does not say)

@@ -20,6 +20,7 @@
 #include "pdl_scan.h"
 #include "pdl_sort.h"
 #include "pdl_append.h"
+#include "pdl_remove.h"
 
 #include <algorithm>
 #include <cstring>
@@ -118,11 +119,12 @@ struct KseqFlag {
     }
 };
 struct KseqApply {
-    uint32_t *kseq_len; uint64_t *kmer_off;   // kmer_off as u64 for the API; values < 2^32 (checked on the host)
+    uint32_t *kseq_len; uint32_t *gene_len; uint64_t *kmer_off;   // kmer_off as u64 for the API; values < 2^32 (checked on the host)
     unsigned long long *cost;                 // total_visited starts at zero (spares a fill)
     const uint64_t *off; uint64_t n_res; unsigned long long *bad;    // *bad |= 1 when the offsets are not an ascending cover of [0, n_res]
     __device__ void operator()(uint64_t i, uint32_t f, uint32_t prefix) const {
         kseq_len[i] = f;
+        gene_len[i] = (uint32_t) (off[i + 1] - off[i]);        // (what kseq_len forgets of a gene shorter than k: pdl_remove_genomes' residue count)
         kmer_off[i] = prefix;
         cost[i] = 0;
         if (off[i + 1] < off[i] || off[i + 1] > n_res) atomicOr(bad, 1ull);     // (never taken on valid input)
@@ -1145,10 +1147,11 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     ev_begin(c, EV_HIST);
     // K-len (independent of the histogram, reads the offsets only); its apply step also clears cost[], its total also lands in kmer_off[N]
     c->kseq_len.alloc((size_t) c->N * sizeof(uint32_t));
+    c->gene_len.alloc((size_t) c->N * sizeof(uint32_t));
     c->kmer_off.alloc(((size_t) c->N + 1) * sizeof(uint64_t));
     c->cost.alloc((size_t) c->N * sizeof(uint64_t));
     scan_and_apply(c, c->N, KseqFlag{c->d_off, (uint32_t) kvalue},
-                   KseqApply{c->kseq_len.as<uint32_t>(), c->kmer_off.as<uint64_t>(), c->cost.as<unsigned long long>(), c->d_off, c->R,
+                   KseqApply{c->kseq_len.as<uint32_t>(), c->gene_len.as<uint32_t>(), c->kmer_off.as<uint64_t>(), c->cost.as<unsigned long long>(), c->d_off, c->R,
                              reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_BAD_OFFSETS)}, d_scal + PDL_CTL_KMERS, c->kmer_off.as<uint64_t>() + c->N);
     if (c->layout_deferred) pdl_input_arrived(c);        // offsets[0] = 0 and offsets[N] = R checked before anything indexes residues
     if (c->R) {
@@ -1579,10 +1582,11 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     const uint64_t r0 = offsets[0], Rq = offsets[n] - r0;
     if (c->R + Rq >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the union need 64-bit stream positions");
     std::vector<uint64_t> h_off(n + 1), h_koff(n + 1);
-    std::vector<uint32_t> h_kseq(n);
+    std::vector<uint32_t> h_kseq(n), h_glen(n);
     uint64_t m = 0;
     for (uint32_t g = 0; g < n; g++) {
         const uint64_t len = offsets[g + 1] - offsets[g];
+        h_glen[g] = (uint32_t) len;
         h_off[g] = offsets[g] - r0;
         h_koff[g] = m;
         h_kseq[g] = len >= k ? (uint32_t) (len - k + 1) : 0u;        // (len < 2^32: checked above)
@@ -1619,6 +1623,7 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     const size_t kb = c->key64 ? 8 : 4;
     // A-len: the per-gene arrays grow (k-mer counts keep their contents), the genome ids move into the context's own buffer
     c->kseq_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
+    c->gene_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
     c->cost.alloc((size_t) N1 * sizeof(uint64_t));
     const bool ids_on_device = c->d_gen && (c->d_gen == c->in_gen.p || c->d_gen == c->ing_gen.p);     // (a caller's buffer may be gone: the host copy serves)
     const bool ids_owned = c->d_gen && c->d_gen == c->own_gen.p;
@@ -1641,6 +1646,7 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
     PDL_HIP(hipGetLastError());
     PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
+    PDL_HIP(hipMemcpyAsync(c->gene_len.as<uint32_t>() + N0, h_glen.data(), n * 4ull, hipMemcpyHostToDevice, st));
     if (ids_owned) {
         PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
     } else if (ids_on_device) {
@@ -1676,6 +1682,144 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         info->residues = Rq; info->kmer_occurrences = m;
         info->records = c->U - U0;            // (a record belongs to one gene: the base's records are all still there)
         info->rank_sort_ms = rank_ms + sort_ms; info->merge_ms = merge_ms; info->device_ms = ms0 + ms1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K-remove (pdl_remove_genomes): the genes of some genomes leave the dictionary that is there.
+//
+//   R-map      scan over the genes (pdl_remove.h)      new gene ids, the per-gene arrays closed up, genome ids renumbered
+//   R-compact  pdl_compact_stream (pdl_remove.h)       (keys_b, vals_b)[M] without the leaving genes' k-mers -> the free half of the
+//   + R-alpha                                          ping-pong; the digits of the keys that stay
+//   -- the host's one read: k-mers left (none: PDL_ERR_EMPTY), digits seen (one missing: PDL_ERR_UNSUPPORTED).  Up to here the
+//      context is only read: R-map writes work buffers, the compaction the half of the ping-pong nobody reads --
+//   tail       K-rle over the M' stream, task layout, K-groups / K-ranges / K-cost: the build's own stages
+//
+// The rank table depends on the set's alphabet only (library.cpp:96-119).  A polynomial rank with an exact B^k is
+// sum v[c_i] * B^(k-1-i) with dense digits v, so the digits of the keys that stay name letters the remaining set holds; when
+// they cover all B letters the remaining set's table is the context's, and the stream the tail starts from is the one
+// pdl_preprocess would sort for the remaining set (see pdl_remove.h).  A letter that survives only in genes shorter than k
+// cannot be seen this way: that removal is refused although a rebuild would have agreed.
+// ------------------------------------------------------------------------------------------------
+template <class KeyT>
+static void remove_from_stream(pdl_ctx *c, uint64_t m, const uint32_t *new_id, uint64_t *d_ctl) {
+    pdl_compact_stream<KeyT>(c->stream, c->keys_b.as<KeyT>(), c->vals_b.as<uint32_t>(), new_id, m, c->rm.tile.as<uint32_t>(), c->keys_a.as<KeyT>(),
+                             c->vals_a.as<uint32_t>(), rm_digits(c->rp.k, c->rp.base), reinterpret_cast<uint32_t *>(d_ctl + PDL_RM_SEEN), d_ctl + PDL_RM_KMERS);
+}
+
+void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_remove_info *info) {
+    hipStream_t st = c->stream;
+    auto &r = c->rm;
+    const uint32_t N0 = c->N, G0 = c->G, G1 = G0 - count;
+    const uint64_t M0 = c->M, U0 = c->U;
+    // a key decodes into letters when it is the polynomial itself: no hashing, and B^k fits 64 bits EXACTLY (key_bits == rank_bits
+    // does not say so: 20 letters at k = 15 wrap unnoticed to a 64-bit rank_bits)
+    bool exact = !c->rp.hash_fallback && c->rp.base != 0;
+    unsigned __int128 bk = 1;
+    for (uint32_t i = 0; i < c->rp.k && exact; i++) { bk *= c->rp.base; exact = (bk >> 64) == 0; }
+    if (!exact)
+        PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: the ranks of this set (%u letters, k = %u: %s) cannot be decoded into letters, so the remaining "
+                 "set cannot be shown to have the same alphabet; rebuild from the remaining genes", c->rp.base, c->rp.k,
+                 c->rp.hash_fallback ? "hashed" : "wrapped past 2^64");
+    // genome ids of the remaining set: the order they have, closed up
+    std::vector<uint32_t> gmap((size_t) G0, 0u);
+    for (uint32_t i = 0; i < count; i++) gmap[genomes[i]] = RM_GONE;
+    for (uint32_t g = 0, next = 0; g < G0; g++) if (gmap[g] != RM_GONE) gmap[g] = next++;
+    for (hipEvent_t &e : r.ev) if (!e) PDL_HIP(hipEventCreate(&e));
+
+    // R-map, R-compact, R-alpha: the context is only read
+    PDL_HIP(hipEventRecord(r.ev[0], st));
+    r.ctl.alloc(PDL_RM_WORDS * sizeof(uint64_t));
+    uint64_t *d_ctl = r.ctl.as<uint64_t>();
+    hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, st, d_ctl, (size_t) PDL_RM_WORDS);
+    r.gmap.alloc((size_t) G0 * 4);
+    PDL_HIP(hipMemcpyAsync(r.gmap.p, gmap.data(), (size_t) G0 * 4, hipMemcpyHostToDevice, st));
+    const uint32_t *d_gen = c->d_gen;
+    if (!(d_gen && (d_gen == c->in_gen.p || d_gen == c->ing_gen.p || d_gen == c->own_gen.p))) {      // (a caller's buffer may be gone: the host copy serves)
+        r.gen_in.alloc((size_t) N0 * 4);
+        PDL_HIP(hipMemcpyAsync(r.gen_in.p, c->h_genome_of.data(), (size_t) N0 * 4, hipMemcpyHostToDevice, st));
+        d_gen = r.gen_in.as<uint32_t>();
+    }
+    r.new_id.alloc((size_t) N0 * 4); r.kseq.alloc((size_t) N0 * 4); r.gen.alloc((size_t) N0 * 4); r.glen.alloc((size_t) N0 * 4);
+    r.tile.alloc(pdl_remove_tiles(M0) * sizeof(uint32_t));
+    const size_t kb = c->key64 ? 8 : 4;
+    c->keys_a.alloc(M0 * kb); c->vals_a.alloc(M0 * sizeof(uint32_t));     // (the free half: after an append it is the smaller one)
+    scan_and_apply(c, N0, RmStays{d_gen, r.gmap.as<uint32_t>()},
+                   RmMapApply{d_gen, r.gmap.as<uint32_t>(), c->kseq_len.as<uint32_t>(), c->gene_len.as<uint32_t>(), r.new_id.as<uint32_t>(), r.gen.as<uint32_t>(),
+                              r.kseq.as<uint32_t>(), r.glen.as<uint32_t>(), reinterpret_cast<unsigned long long *>(d_ctl + PDL_RM_GONE_RESIDUES)},
+                   d_ctl + PDL_RM_GENES);
+    if (c->key64) remove_from_stream<uint64_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
+    else remove_from_stream<uint32_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
+    PDL_HIP(hipEventRecord(r.ev[1], st));
+    // the host's side of it while the device works: the genome ids of the genes that stay
+    std::vector<uint32_t> genome_of;
+    genome_of.reserve(N0);
+    for (uint32_t i = 0; i < N0; i++) if (gmap[c->h_genome_of[i]] != RM_GONE) genome_of.push_back(gmap[c->h_genome_of[i]]);
+    const uint32_t N1 = (uint32_t) genome_of.size();
+    uint64_t M1 = 0, gone_residues = 0;
+    {
+        PinRead rd(c);
+        const uint64_t *pc = rd.add<uint64_t>(d_ctl, PDL_RM_WORDS);
+        const uint32_t *lbe = lookback_error_word(c, rd);
+        rd.sync();
+        lookback_check(c, lbe);
+        if (pc[PDL_RM_GENES] != N1) PDL_FAIL(PDL_ERR_DEVICE, "pdl_remove_genomes: %llu genes stay on the device, %u on the host", (unsigned long long) pc[PDL_RM_GENES], N1);
+        M1 = pc[PDL_RM_KMERS]; gone_residues = pc[PDL_RM_GONE_RESIDUES];
+        if (M1 == 0) PDL_FAIL(PDL_ERR_EMPTY, "no gene is at least k=%u residues long: the dictionary is empty", c->rp.k);
+        const uint32_t *seen = reinterpret_cast<const uint32_t *>(pc + PDL_RM_SEEN);
+        for (uint32_t d = 0; d < c->rp.base; d++) {
+            if (seen[d]) continue;
+            int letter = 0;
+            for (int b = 0; b < 256; b++) if (c->alpha_present[b] && c->rp.rank_values[b] == d) { letter = b; break; }
+            PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: no k-mer of the remaining genes holds the letter 0x%02x%s%c%s: without it the remaining set has "
+                     "another rank table (this check is conservative: the letter may survive in a gene shorter than k=%u); rebuild from the remaining genes",
+                     letter, letter >= 0x20 && letter < 0x7f ? " ('" : "", letter >= 0x20 && letter < 0x7f ? (char) letter : ' ',
+                     letter >= 0x20 && letter < 0x7f ? "')" : "", c->rp.k);
+        }
+    }
+
+    // from here on the context changes; a failure leaves it un-preprocessed
+    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
+    c->mirror_valid = false; c->edges_valid = false; c->fam_valid = false;
+    std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes);      // the sorted stream is what keys_b / vals_b name
+    std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes);
+    std::swap(c->kseq_len.p, r.kseq.p); std::swap(c->kseq_len.bytes, r.kseq.bytes);
+    std::swap(c->gene_len.p, r.glen.p); std::swap(c->gene_len.bytes, r.glen.bytes);
+    std::swap(c->own_gen.p, r.gen.p); std::swap(c->own_gen.bytes, r.gen.bytes);             // the context owns the ids from here on, as after an append
+    pdl_replace_layout(c, std::move(genome_of));          // N, G, h_genome_of, genome rows
+    c->M = M1; c->R -= gone_residues;
+    c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
+    const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
+    c->scalars.alloc(ctl_words * sizeof(uint64_t));
+    c->cost.alloc((size_t) N1 * sizeof(uint64_t));
+
+    PDL_HIP(hipEventRecord(r.ev[2], st));
+    uint64_t *d_scal = c->scalars.as<uint64_t>();
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
+    PDL_HIP(hipGetLastError());
+    c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
+    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
+    ev_end(c, EV_DICT);
+    pdl_prepare_tasks(c);
+    stage_ranges_and_costs(c, M1, 1, false);
+    PDL_HIP(hipEventRecord(r.ev[3], st));
+    PDL_HIP(hipStreamSynchronize(st));
+    if (c->opt_low_memory) {                  // as a build does: what only the build needed goes back
+        c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
+    }
+    float ms0 = 0.f, ms1 = 0.f;
+    (void) hipEventElapsedTime(&ms0, r.ev[0], r.ev[1]);
+    (void) hipEventElapsedTime(&ms1, r.ev[2], r.ev[3]);
+    pdl_timings t{};                          // the preprocess fields describe the removal, the scoring fields start again
+    t.sort_rank_ms = ms0; t.dict_ms = ev_ms(c, EV_DICT);
+    t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
+    t.preprocess_total_ms = ms0 + ms1;
+    c->tm = t;
+    if (info) {
+        info->sequences = N0 - N1; info->residues = gone_residues; info->kmer_occurrences = M0 - M1;
+        info->records = U0 - c->U;            // (a record belongs to one gene: the records of the genes that stay are all still there)
+        info->compact_ms = ms0; info->device_ms = ms0 + ms1;
     }
 }
 

@@ -188,6 +188,18 @@ class PangeneNative:
         residues, offsets, genome_of = data.flatten()
         self.append(residues, offsets, genome_of + np.uint32(self.cost.genomes))
 
+    def remove(self, genomes) -> None:
+        """Genomes leave this dictionary by a compaction of the sorted k-mer stream, without a rebuild (``pdl_remove_genomes``):
+        ``genomes`` are distinct ids of this context.  Afterwards the context is the one ``preprocess`` on the remaining set
+        would leave (genes and genomes renumbered densely in their order); ``cost`` is the remaining set's and
+        ``last_remove_info`` holds what left and the device times as a dict.  A refusal leaves everything as it was;
+        ``PDL_ERR_UNSUPPORTED`` (the remaining set's alphabet cannot be proved from the keys) asks for a rebuild."""
+        ids = np.ascontiguousarray(genomes, dtype=np.uint32).reshape(-1)
+        cost, info = _lib.PdlCost(), _lib.PdlRemoveInfo()
+        self._check(self._lib.pdl_remove_genomes(self._ctx, ids.ctypes.data if ids.size else None, len(ids), C.byref(cost), C.byref(info)))
+        self.cost = cost
+        self.last_remove_info = info.as_dict()
+
     def _take_scores(self, s) -> Scores:
         try:
             z, rows, g, n = s.scoresCount, s.rows, s.genomes, s.sequences
