@@ -222,6 +222,32 @@ typedef struct {
 PDL_API int pdl_query_scores(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n_query+1] */,
                              uint32_t n_query, pdl_scores *out, pdl_query_info *info /* may be NULL */);
 
+/* ---- query batch: q new genomes against the dictionary already built, each on its own, in one pass -------------------
+ * The n genes of residues/offsets are cut into n_queries genomes by gene_begin: the genes of query j are
+ * [gene_begin[j], gene_begin[j+1]).  out[j] is, bit for bit and in emission order, the block pdl_query_scores returns for the
+ * genes of query j alone on this context: computeScores(G) of the union of the base and genome j only — its genes are ids
+ * N..N+n_j-1 of genome G in its own block, sequences = N+n_j, genomes = G+1; PDL_FLAG_CANONICAL_ORDER is honoured.  The queries
+ * never see each other (that is an append) and the base context is only read.  info[j] holds query j's own sizes, matched
+ * records and "Genome G cost"; its device_ms is an even share of its chunk's device time.  The stages run once over all genes
+ * of a chunk of consecutive queries; a chunk holds as many queries as option "query_batch_bytes" allows (at least one), the
+ * results do not depend on the chunking.  Free every out[j] with pdl_free_scores.
+ * Every refusal is decided before a block is returned: `out` is left zeroed and the context as it was.
+ * PDL_ERR_STATE: as pdl_query_scores.  PDL_ERR_ARGUMENT: n_queries == 0, n == 0, NULL pointers, decreasing offsets, a gene_begin
+ * that does not start at 0, does not end at n or is not strictly increasing (a query without genes).  PDL_ERR_UNSUPPORTED: a
+ * byte the base's alphabet lacks (the message names the first such query and its smallest absent byte), a gene of 2^20 k-mers
+ * or more, a batch whose residues pass 2^32 with the base's, or N + n_j past the 31-bit gene ids (decided from gene_begin alone,
+ * before offsets is read). */
+typedef struct {
+    uint32_t queries, chunks;  /* queries scored; chunks of consecutive queries the call worked through */
+    float device_ms;           /* device time of the call, as pdl_query_info.device_ms, over all chunks */
+} pdl_query_batch_info;
+PDL_API int pdl_query_batch(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n+1] */,
+                            const uint32_t *gene_begin /* [n_queries+1]: genes of query j = [gene_begin[j], gene_begin[j+1]) */,
+                            uint32_t n, uint32_t n_queries,
+                            pdl_scores *out /* [n_queries], each freed with pdl_free_scores */,
+                            pdl_query_info *info /* [n_queries] or NULL */,
+                            pdl_query_batch_info *binfo /* may be NULL */);
+
 /* ---- append: new genomes join the dictionary already built, by a merge instead of a rebuild ----------------------------
  * The n genes of residues/offsets become genes N..N+n-1 of the context.  genome_of == NULL: all of them are ONE new genome G.
  * Otherwise genome_of[i] are union ids G..G+g-1, dense in first-seen order (the rule of PangeneIData.java:56-62 continued); an id
@@ -348,7 +374,8 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * with rows in flight), "stage_timers" 0|1 (default 1: HIP events around every stage fill the stage
  * fields of pdl_timings; 0: only the totals and the join's launch time are taken — each event pair is two marker packets
  * between dispatches, a few microseconds of idle stream on a two-millisecond step), "low_memory" 0|1 (for genome batches on a large set: the buffers only the dictionary build needed are released after it —
- * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "onepass_scan" 0|1 (prefix scans
+ * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "query_batch_bytes" n > 0
+ * (device bytes one chunk of pdl_query_batch may take before its join, default 2^30), "onepass_scan" 0|1 (prefix scans
  * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "aside_test_reload" 0|1 (test switch: the next scoring pass
  * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs). */
 PDL_API int pdl_set_option(pdl_ctx *, const char *name, int64_t value);
@@ -452,7 +479,7 @@ PDL_API int pdl_copy_device(pdl_ctx *, void *d_dst, const void *d_src, uint64_t 
 PDL_API int pdl_pin_arrived(const uint32_t *pin, const uint32_t *dst_word, const uint32_t *words, uint32_t n, uint32_t flag_word, uint32_t epoch);
 PDL_API uint32_t pdl_pin_checksum(const uint32_t *payload, const uint32_t *dst_word, const uint32_t *words, uint32_t n);
 
-/* Library/build identification, e.g. "pandelos_amd 0.1 gfx950" */
+/* Library/build identification, e.g. "pandelos_amd 0.2 (HIP, gfx950)" */
 PDL_API const char *pdl_version(void);
 
 #ifdef __cplusplus

@@ -94,6 +94,13 @@ class PdlQueryInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PdlQueryBatchInfo(C.Structure):
+    _fields_ = [("queries", C.c_uint32), ("chunks", C.c_uint32), ("device_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PdlAppendInfo(C.Structure):
     _fields_ = [("residues", C.c_uint64), ("kmer_occurrences", C.c_uint64), ("records", C.c_uint64),
                 ("rank_sort_ms", C.c_float), ("merge_ms", C.c_float), ("device_ms", C.c_float)]
@@ -127,7 +134,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_dist_preprocess_ranges", "pdl_dist_preprocess_finish_ranges",
            "pdl_dist_genome_owner", "pdl_dist_score_begin", "pdl_dist_score_finish", "pdl_copy_device",
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
-           "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_append_genomes", "pdl_remove_genomes",
+           "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families")
 
 _lib = None
@@ -179,6 +186,8 @@ def load():
     lib.pdl_copy_device.argtypes = [vp, vp, vp, u64]; lib.pdl_copy_device.restype = i32
     lib.pdl_query_scores.argtypes = [vp, vp, vp, u32, C.POINTER(PdlScores), C.POINTER(PdlQueryInfo)]
     lib.pdl_query_scores.restype = i32
+    lib.pdl_query_batch.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(PdlScores), C.POINTER(PdlQueryInfo), C.POINTER(PdlQueryBatchInfo)]
+    lib.pdl_query_batch.restype = i32
     lib.pdl_append_genomes.argtypes = [vp, vp, vp, vp, u32, C.POINTER(PdlCost), C.POINTER(PdlAppendInfo)]
     lib.pdl_append_genomes.restype = i32
     lib.pdl_remove_genomes.argtypes = [vp, vp, u32, C.POINTER(PdlCost), C.POINTER(PdlRemoveInfo)]

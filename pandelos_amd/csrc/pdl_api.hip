@@ -27,7 +27,7 @@ template <class T> static T *xalloc(size_t n) {
 
 extern "C" {
 
-const char *pdl_version(void) { return "pandelos_amd 0.1 (HIP, gfx950)"; }
+const char *pdl_version(void) { return "pandelos_amd 0.2 (HIP, gfx950)"; }
 
 // The host side of the small-read protocol on plain memory (no device, no context): see PinRead in pdl_common.h.
 int pdl_pin_arrived(const uint32_t *pin, const uint32_t *dst_word, const uint32_t *words, uint32_t n, uint32_t flag_word, uint32_t epoch) {
@@ -77,6 +77,8 @@ void pdl_destroy(pdl_ctx *c) {
     (void) hipStreamSynchronize(c->stream);
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
     for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : c->qbb.ev) if (e) (void) hipEventDestroy(e);
+    if (c->qbb.stage) (void) hipHostFree(c->qbb.stage);
     for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->rm.ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->fb.ev) if (e) (void) hipEventDestroy(e);
@@ -162,7 +164,7 @@ int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int onl
     PDL_GUARD_BEGIN
     PDL_HIP(hipSetDevice(c->device));
     c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;      // the genome shard, if one was set, stays in force
-    c->qb.release();
+    c->qb.release(); c->qbb.release();
     c->N = n; c->R = n_res;
     c->U = c->Ushared = c->NG = c->P = c->M = 0;
     if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
@@ -632,6 +634,11 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     else if (n == "aside_test_reload") c->opt_aside_test_reload = value != 0;
     else if (n == "onepass_scan") c->opt_onepass_scan = value != 0;
     else if (n == "low_memory") c->opt_low_memory = value != 0;
+    else if (n == "query_batch_bytes") {
+        if (value <= 0) { c->err = "query_batch_bytes: a positive byte count"; return PDL_ERR_ARGUMENT; }
+        c->opt_query_batch_bytes = (uint64_t) value;
+        return PDL_OK;        // (no bearing on a scoring pass: the context's scores stay)
+    }
     else { c->err = "unknown option " + n; return PDL_ERR_ARGUMENT; }
     c->scored = false;        // the next scoring call runs with the new setting
     return PDL_OK;
@@ -807,6 +814,50 @@ int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offset
     pdl_run_query(c, residues, offsets, n_query, out, info);
     return PDL_OK;
     PDL_GUARD_END(c)
+}
+
+int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
+                    pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out && n_queries) memset(out, 0, sizeof(*out) * (size_t) n_queries);
+    if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
+    if (binfo) memset(binfo, 0, sizeof(*binfo));
+    try {
+        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch before pdl_preprocess");
+        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: the context was preprocessed with only_complexity");
+        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: not available on a multi-GPU context");
+        if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
+            PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: the sorted k-mer stream was released (option low_memory)");
+        if (n_queries == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query");
+        if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query gene");
+        if (!out || !offsets || !gene_begin) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: NULL pointer");
+        // gene_begin first: the 31-bit id limit is decided from it alone, before a single offset is read
+        if (gene_begin[0] != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin[0] = %u, not 0", gene_begin[0]);
+        for (uint32_t q = 0; q < n_queries; q++)
+            if (gene_begin[q + 1] <= gene_begin[q] || gene_begin[q + 1] > n)
+                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin is not strictly increasing within the %u genes at query %u (a query needs a gene)", n, q);
+        if (gene_begin[n_queries] != n) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin ends at %u, not at the %u genes", gene_begin[n_queries], n);
+        for (uint32_t q = 0; q < n_queries; q++) {
+            const uint64_t nc = (uint64_t) c->N + (gene_begin[q + 1] - gene_begin[q]);
+            if (nc >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu genes in the union exceed the 31-bit gene ids", q, (unsigned long long) nc);
+        }
+        for (uint32_t i = 0; i < n; i++)
+            if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: offsets decrease at gene %u", i);
+        if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: NULL residues");
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_run_query_batch(c, residues, offsets, gene_begin, n, n_queries, out, info, binfo);
+        return PDL_OK;
+    } catch (...) {
+        // a refusal returns no block: what earlier chunks produced goes back, `out` is zero again
+        if (out) for (uint32_t q = 0; q < n_queries; q++) pdl_free_scores(&out[q]);
+        if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
+        if (binfo) memset(binfo, 0, sizeof(*binfo));
+        try { throw; }
+        catch (const pdl_error &e) { c->err = e.msg; return e.code; }
+        catch (const std::bad_alloc &) { c->err = "host allocation failed"; return PDL_ERR_DEVICE; }
+        catch (const std::exception &e) { c->err = e.what(); return PDL_ERR_DEVICE; }
+    }
 }
 
 int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_of, uint32_t n, pdl_cost *out_cost,

@@ -390,6 +390,22 @@ struct pdl_ctx {
             hbm_clean = false; hbm_cols = hbm_slots = 0; rec_sorted_at = nullptr;
         }
     } qb;
+    // pdl_query_batch (pdl_query_batch.h): the buffers of one chunk of queries, reused across chunks and calls, released with qb's
+    // (the HBM tables of the join's last tier and their bookkeeping are qb's: a batch and a single query find each other's clean)
+    struct QueryBatchBufs {
+        DevBuf res, off, koff, kseq, gene_begin, res_begin, gene_query, keys_a, keys_b, vals_a, vals_b, recpos, post, qkey, perm, srank, spost,
+               seg_off, folds, desc, gkey, rec_sorted, row_lookups, row_off, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells;
+        hipEvent_t ev[6] = {};                       // start / end of up to three stretches of device work per chunk
+        uint8_t *stage = nullptr; size_t stage_bytes = 0;     // pinned host staging of a chunk's cells and maxima (the blocks are cut out of it)
+        void release() {
+            if (stage) { (void) hipHostFree(stage); stage = nullptr; stage_bytes = 0; }
+            DevBuf *all[] = {&res, &off, &koff, &kseq, &gene_begin, &res_begin, &gene_query, &keys_a, &keys_b, &vals_a, &vals_b, &recpos, &post, &qkey,
+                             &perm, &srank, &spost, &seg_off, &folds, &desc, &gkey, &rec_sorted, &row_lookups, &row_off, &ctl, &MS, &CM, &row_base,
+                             &row_cnt, &fin_off, &rowid, &overflow, &st, &cells};
+            for (DevBuf *b : all) b->release();
+        }
+    } qbb;
+    uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
     // K-fam (pdl_families.h): work buffers of a run (grown as needed, shared by pdl_compute_families and pdl_families_of_edges) and
     // the context's own families, kept on the host until the edges change (pdl_run_bbh_all drops them)
     struct FamBufs {
@@ -561,6 +577,9 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
+// K-query for a batch (pdl_query_batch.h): q genomes, each scored on its own; gene_begin [n_queries + 1] cuts the n genes
+void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
+                         pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo);
 void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad);      // k_q_alpha over device bytes (pdl_query.h)
 [[noreturn]] void pdl_fail_absent_byte(uint64_t bad_word, const char *who);                             // ... and the refusal that names the byte
 // K-append (pdl_append.h, pdl_dict.hip): the n genes of residues/offsets become genes N.. of the context; genome_ids [n] are their

@@ -1922,3 +1922,4 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
 }
 
 #include "pdl_query.h"           // K-query: one new genome against this dictionary (pdl_query_scores)
+#include "pdl_query_batch.h"     // ... and a batch of them, each on its own (pdl_query_batch)

@@ -223,6 +223,8 @@ __global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, 
 }
 
 // ---- Q-join ------------------------------------------------------------------------------------------------------------
+// (k_q_join and k_q_join_hbm have copies that take their row's arguments per workgroup — k_qb_join / k_qb_join_hbm in
+// pdl_query_batch.h: a change to the row program below belongs there too.)
 constexpr int QJ_T = 256;
 constexpr uint32_t QJ_HT_BITS = 12, QJ_HT = 1u << QJ_HT_BITS;
 constexpr uint32_t QJ_LIMIT = QJ_HT - 2 * QJ_T;         // keys a row may claim before it goes to the HBM tables (< HT: probes end)

@@ -160,6 +160,62 @@ class PangeneNative:
             raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
         return self.query_scores(residues, offsets)
 
+    @staticmethod
+    def pack_queries(queries):
+        """``[(residues, offsets), ...]`` -> (residues, offsets [n + 1], gene_begin [q + 1]) as ``pdl_query_batch`` takes them:
+        the queries' genes one behind the other, ``gene_begin[j]`` the first gene of query j.  Offsets need not start at 0:
+        a query's genes are ``residues[offsets[0]:offsets[-1]]``."""
+        parts, offs, begin = [], [np.zeros(1, np.uint64)], [0]
+        at = 0
+        for j, (residues, offsets) in enumerate(queries):
+            res = np.ascontiguousarray(residues, dtype=np.uint8)
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if off.ndim != 1 or len(off) < 1:
+                raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"query {j}: offsets must hold n + 1 entries")
+            if (np.diff(off.astype(np.int64)) < 0).any() or int(off[-1]) > len(res):
+                raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"query {j}: offsets decrease or pass the residues")
+            lo, hi = int(off[0]), int(off[-1])
+            parts.append(res[lo:hi])
+            offs.append((off[1:].astype(np.int64) - lo + at).astype(np.uint64))
+            at += hi - lo
+            begin.append(begin[-1] + len(off) - 1)
+        res = np.concatenate(parts).astype(np.uint8) if parts else np.zeros(0, np.uint8)
+        return res, np.concatenate(offs).astype(np.uint64), np.asarray(begin, dtype=np.uint32)
+
+    def query_batch(self, queries) -> list:
+        """Many new genomes against this dictionary in one pass, each on its own (``pdl_query_batch``): ``queries`` is a list
+        of ``(residues, offsets)``; -> one ``Scores`` per query, the block ``query_scores`` returns for that genome alone.
+        ``last_query_batch_info`` then holds ``queries`` (the per-query dicts of ``last_query_info``), ``chunks`` and
+        ``device_ms``."""
+        queries = list(queries)
+        res, off, begin = self.pack_queries(queries)
+        q = len(queries)
+        blocks = (_lib.PdlScores * max(q, 1))()
+        infos = (_lib.PdlQueryInfo * max(q, 1))()
+        binfo = _lib.PdlQueryBatchInfo()
+        self._check(self._lib.pdl_query_batch(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data, begin.ctypes.data,
+                                              len(off) - 1, q, blocks, infos, C.byref(binfo)))
+        out = []
+        try:
+            for j in range(q):
+                out.append(self._take_scores(blocks[j]))
+        finally:                                         # (a block that was taken is zero: freeing it again does nothing)
+            for j in range(len(out), q):
+                self._lib.pdl_free_scores(C.byref(blocks[j]))
+        self.last_query_batch_info = {"queries": [infos[j].as_dict() for j in range(q)], "chunks": binfo.chunks, "device_ms": binfo.device_ms}
+        return out
+
+    def query_batch_idata(self, datas) -> list:
+        """``query_batch`` for a list of ``PangeneIData``, each holding exactly one genome."""
+        queries = []
+        for j, data in enumerate(datas):
+            residues, offsets, genome_of = data.flatten()
+            n_genomes = len(np.unique(genome_of))
+            if n_genomes != 1:
+                raise ValueError(f"a query holds exactly one genome, query {j} holds {n_genomes}")
+            queries.append((residues, offsets))
+        return self.query_batch(queries)
+
     def append(self, residues, offsets, genome_of=None) -> None:
         """New genomes join this dictionary by a merge, without a rebuild (``pdl_append_genomes``): the genes become ids
         N..N+n-1, all of one new genome G = ``cost.genomes`` (``genome_of`` None) or of the union ids ``genome_of`` (G, G+1, ...

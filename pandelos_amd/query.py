@@ -39,6 +39,22 @@ def check_query(query: PangeneIData, base_genome_names: Sequence[str]) -> None:
         raise QueryError(f"the query genome '{query.genomeNames[0]}' already names a base genome: its genes would join it")
 
 
+def write_outputs(block, base: PangeneIData, query: PangeneIData, net_path, cells_path=None) -> int:
+    """The `.net` of one query block and, with ``cells_path``, its cells with names; -> edges written."""
+    src, dst, score = bbh_edges(block)
+    with open(net_path, "w") as f:
+        f.writelines(net_lines(src, dst, score))
+    if cells_path:
+        names = list(base.sequenceName) + list(query.sequenceName)
+        genomes = list(base.genomeNames) + [query.genomeNames[0]]
+        with open(cells_path, "w") as f:
+            for r, c, g2, s, p, t in zip(block.row.tolist(), block.column.tolist(), block.second_seq_genome.tolist(),
+                                         block.scores.astype(np.float64).tolist(), block.percs.astype(np.float64).tolist(),
+                                         block.tr_percs.astype(np.float64).tolist()):
+                f.write(f"{names[r]}\t{names[c]}\t{genomes[g2]}\t{s!r}\t{p!r}\t{t!r}\n")
+    return len(src)
+
+
 def main(argv: Sequence[str] | None = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m pandelos_amd.query")
     ap.add_argument("-i", "--input", required=True, help="base set (.faa)")
@@ -64,19 +80,9 @@ def main(argv: Sequence[str] | None = None) -> int:
         info = nat.last_query_info
     finally:
         nat.close()
-    src, dst, score = bbh_edges(block)
-    with open(args.output, "w") as f:
-        f.writelines(net_lines(src, dst, score))
-    if args.cells:
-        names = list(base.sequenceName) + list(query.sequenceName)
-        genomes = list(base.genomeNames) + [query.genomeNames[0]]
-        with open(args.cells, "w") as f:
-            for r, c, g2, s, p, t in zip(block.row.tolist(), block.column.tolist(), block.second_seq_genome.tolist(),
-                                         block.scores.astype(np.float64).tolist(), block.percs.astype(np.float64).tolist(),
-                                         block.tr_percs.astype(np.float64).tolist()):
-                f.write(f"{names[r]}\t{names[c]}\t{genomes[g2]}\t{s!r}\t{p!r}\t{t!r}\n")
+    n_edges = write_outputs(block, base, query, args.output, args.cells)
     print(f"query genome '{query.genomeNames[0]}': {len(query.sequences)} genes against {ing['sequences']} base genes; "
-          f"Genome {ing['genomes']} cost = {info['genome_cost']}; {block.scoresCount} cells, {len(src)} edges -> {args.output}")
+          f"Genome {ing['genomes']} cost = {info['genome_cost']}; {block.scoresCount} cells, {n_edges} edges -> {args.output}")
     return 0
 
 
