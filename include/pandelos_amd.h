@@ -366,6 +366,11 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * PDL_ERR_ARGUMENT.  Options: "join_tier1" 0|9|10|11|20|21 (table of the join's first tier; -1 = default: by genome count),
  * "join_tier0" -1|0|1 (the partition tier in front of tier 1 — several short rows per workgroup cycle, no hash table: -1 = by the
  * average row length, the default; it stays off when "join_tier1" was set by hand unless forced with 1),
+ * "sift_threshold" 0|1 (that tier's sift: 1, the default = a column goes to the table only when the cycle's counter of it reached
+ * what the set's shortest gene would need to emit it — on sets where that threshold is 4 or more; below it, i.e. with a gene of
+ * at most 6k k-mers in the set, the sift is "seen twice" on two bitmaps, as it was before the counters; 0 = the counters with the
+ * threshold forced to 2: a test switch, several times slower on large sets; the scores are the same either way; any other value
+ * is rejected),
  * "join_tiny_tier2" 0|1 (512-slot second tier, so that small test sets reach the HBM-table kernel), "host_mirror" 0|1
  * (pdl_compute_scores slices ONE pinned copy of the whole result (1, default) or copies each genome's block from the
  * device (0); results above 1 GiB always take the second way), "staging_cap" n (cells of staging the first scoring

@@ -324,7 +324,7 @@ struct pdl_ctx {
     DevBuf task_off;      // u32 [shard+1] task offsets | gathered cell offsets + the counters behind them (PDL_JT_*)
     int cus = 0;
     uint32_t occ_tier1[5] = {0, 0, 0, 0, 0};
-    uint32_t occ_tier0 = 0, occ_tier0b = 0;
+    uint32_t occ_tier0[2] = {0, 0}, occ_tier0b[2] = {0, 0};      // [bitmap form, counter form]
 
     // K-bbh (pdl_bbh.hip): network edges of every genome task, on the host after the first pdl_compute_edges
     bool edges_valid = false;
@@ -338,6 +338,7 @@ struct pdl_ctx {
     // tuning / test switches (pdl_set_option)
     int opt_tier1 = -1;           // -1: by genome count
     int opt_tier0 = -1;           // the partition tier in front of tier 1: -1 by row length, 0 off, 1 on
+    int opt_sift_threshold = 1;   // tier 0's sift: 1 = counters against the set's validity threshold (bitmaps where that is below PT_SIFT_T_MIN), 0 = counters at threshold 2 (tests)
     bool opt_tiny_tier2 = false;
     bool opt_stage_timers = true; // per-stage HIP events (pdl_timings' stage fields); the totals and the join's are always taken
     int opt_grid_pct = 0;         // > 0: tier-1 grid as a percentage of what fits the chip (experiments)

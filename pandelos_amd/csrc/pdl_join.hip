@@ -67,6 +67,7 @@ struct JoinArgs {
     uint32_t *work_cursor;         // persistent-workgroup row dispenser (one atomic hands out `work_batch` items:
                                    // a single device-scope word serves only ~90 dequeues/us)
     uint32_t work_batch;
+    uint32_t sift_threshold;       // tier 0: 1 = the sift asks of a column what finalize will ask of it, 0 = two sightings (pdl_set_option "sift_threshold")
     unsigned long long *cell_cursor;
     uint32_t *overflow_count;
     uint32_t *error_count;         // internal consistency violations (must stay 0)
@@ -1408,6 +1409,7 @@ __global__ void k_iota_u32(uint32_t *dst, uint32_t n) { uint32_t i = blockIdx.x 
 struct ScorePlan {
     bool wide, mirror;
     bool tier0;                    // the partition tier runs in front of tier 1 (short rows)
+    bool tier0_cnt;                // ... sifting with counters against the set's threshold (false: with bitmaps, "seen twice")
     uint32_t grid0, grid0b;        // (the second form of the partition tier: 512 threads, the rows that alone exceed the first form's cycle)
     int tier1, occ_slot;
     bool tiny_tier2;
@@ -1468,9 +1470,23 @@ static ScorePlan score_plan(pdl_ctx *c) {
         const bool want = c->opt_tier0 > 0 || (c->opt_tier0 < 0 && c->opt_tier1 < 0 && n_rows >= 12288 && walked / n_rows <= 3000 && c->Urepeat * 5000 <= c->U);      // (fewer rows: the extra launches cost more than the tier saves)
         pl.tier0 = can && want;
         if (pl.tier0) {
-            if (c->occ_tier0 == 0) { c->occ_tier0 = occupancy((const void *) k_join_part<PT_T, PT_WG_PER_CU>, (int) PT_T); c->occ_tier0b = occupancy((const void *) k_join_part<PT_T2, PT_WGS2>, (int) PT_T2); }
-            pl.grid0 = std::min<uint32_t>((n_rows + PT_BATCH - 1) / PT_BATCH, (uint32_t) cus * c->occ_tier0);
-            pl.grid0b = std::min<uint32_t>(n_rows, (uint32_t) cus * c->occ_tier0b);
+            // the sift: counters against the set's threshold clamp(tc_min, 2, 255) (the kernel works it out the same way) where that is
+            // high enough for 12 index bits to beat "seen twice" on 15 (PT_SIFT_T_MIN), bitmaps below it.  "sift_threshold" 0 is the test
+            // switch: the counters at a threshold of 2, whatever the set's.
+            {
+                const float thr = 1.0f / (2.0f * (float) c->rp.k), denom = (float) (int) (uint32_t) std::max<uint64_t>(c->min_kseq, 1);
+                uint32_t t = (uint32_t) (thr * denom);
+                t = t > 2 ? t - 2 : 0;
+                while ((float) (int) t / denom < thr) t++;             // (min_numerator)
+                pl.tier0_cnt = c->opt_sift_threshold == 0 || t >= PT_SIFT_T_MIN;
+            }
+            const int f = pl.tier0_cnt ? 1 : 0;
+            if (c->occ_tier0[f] == 0) {
+                c->occ_tier0[f] = f ? occupancy((const void *) k_join_part<PT_T, PT_WG_PER_CU, true>, (int) PT_T) : occupancy((const void *) k_join_part<PT_T, PT_WG_PER_CU, false>, (int) PT_T);
+                c->occ_tier0b[f] = f ? occupancy((const void *) k_join_part<PT_T2, PT_WGS2, true>, (int) PT_T2) : occupancy((const void *) k_join_part<PT_T2, PT_WGS2, false>, (int) PT_T2);
+            }
+            pl.grid0 = std::min<uint32_t>((n_rows + PT_BATCH - 1) / PT_BATCH, (uint32_t) cus * c->occ_tier0[f]);
+            pl.grid0b = std::min<uint32_t>(n_rows, (uint32_t) cus * c->occ_tier0b[f]);
             if (c->opt_grid_pct > 0) pl.grid0 = std::max<uint32_t>(1, (uint32_t) ((uint64_t) pl.grid0 * (uint32_t) c->opt_grid_pct / 100));
         }
     }
@@ -1537,6 +1553,7 @@ static JoinArgs join_args(pdl_ctx *c, const ScorePlan &pl) {
     a.st_score = c->st_score.as<float>(); a.st_perc = c->st_perc.as<float>(); a.st_tr = c->st_tr.as<float>();
     a.st_col = c->st_col.as<uint32_t>(); a.st_first = c->st_first.as<uint32_t>(); a.st_cap = c->st_cap;
     a.mirror = pl.mirror ? 1u : 0u;
+    a.sift_threshold = c->opt_sift_threshold ? 1u : 0u;
     if (pl.mirror) {
         a.taskpos_of = c->taskpos_of.as<uint32_t>(); a.local_genome = c->local_genome.as<uint32_t>();
         a.mirror_cnt = c->mirror_cnt.as<uint32_t>();
@@ -1582,7 +1599,8 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
         PDL_HIP(hipMemsetAsync(d_phase0, 0, 12 * sizeof(unsigned long long), st));
         a.phase = d_phase0;
 #endif
-        hipLaunchKernelGGL((k_join_part<PT_T, PT_WG_PER_CU>), dim3(pl.grid0), dim3(PT_T), 0, st, a);
+        if (pl.tier0_cnt) hipLaunchKernelGGL((k_join_part<PT_T, PT_WG_PER_CU, true>), dim3(pl.grid0), dim3(PT_T), 0, st, a);
+        else hipLaunchKernelGGL((k_join_part<PT_T, PT_WG_PER_CU, false>), dim3(pl.grid0), dim3(PT_T), 0, st, a);
 #ifdef PDL_JOIN_PHASES
         {   // (the first form only; the timers are thread 0's clock between the barriers: shares of a workgroup's time, other workgroups of the CU run beside it)
             unsigned long long h[12];
@@ -1601,7 +1619,8 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
         a.desc = c->row_desc2.as<uint4>() + n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T0B;
         a.work_cursor = ctr32 + PDL_JC_CURSOR_T0B; a.overflow_count = ctr32 + PDL_JC_ROWS_T1; a.overflow_rows = list_s2; a.work_batch = 1;
         a.overflow_desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows;
-        hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
+        if (pl.tier0_cnt) hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2, true>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
+        else hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2, false>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
         a.desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T1;
         c->tm.join_launches += 2;
     }

@@ -14,12 +14,20 @@
 // them have been seen:
 //
 //   stage     the ranges of all rows of the cycle, one flat lookup space (as the other tiers do for one row)
-//   walk      every lookup marks its column in two 32-Kbit bitmaps: "seen" and — when the bit was already set — "seen twice"
-//   (barrier: the bitmaps are complete)
-//   sift      a lookup whose "seen twice" bit is clear is the ONLY lookup of its column in this cycle.  With both counts 1 it
-//             can never be emitted when no gene involved has <= 2k k-mers (library.cpp:497-500; such rows are not taken
-//             here): it is dropped — the "seen twice" rule of the filter tiers, but decided AFTER all sightings are in: the
-//             first sighting is judged like the second, nothing is put aside, nothing goes to HBM.
+//   walk      every lookup adds 1 to its column's COUNTER: 4096 16-bit counters, two to a word, indexed by the top 12 bits of
+//             h(column) — one LDS add whose result nobody waits for.  A lookup with a count >= 2 on either side (rare) adds the
+//             threshold T instead, so its column is kept whatever else is seen of it.
+//   (barrier: the counters are complete)
+//   sift      a lookup whose counter is below T is dropped.  T = clamp(min(tc_min, min pc_min of the cycle's rows), 2, 255): a
+//             column of light sightings only is emitted when their number reaches the row's pc_min or tc_min (the pre-filter in
+//             finalize; library.cpp:497-500), and a counter is never below the sightings of a column that maps to it — collisions
+//             and the other rows of the cycle only add — so no column that could be emitted is dropped, and all lookups of a kept
+//             column share its counter: its sums are complete.  The floor of 2 is the "seen twice" rule of the filter tiers (no
+//             gene involved has <= 2k k-mers; such rows are not taken here), decided AFTER all sightings are in: the first
+//             sighting is judged like the last, nothing is put aside, nothing goes to HBM.  pdl_set_option "sift_threshold" 0
+//             forces T = 2 on the counters (tests: the same cells, many more survivors).  The counters index 12 bits of h, the
+//             bitmaps they replaced 15: a set whose threshold is below PT_SIFT_T_MIN (one gene of <= 6k k-mers is enough for 3)
+//             gets the kernel's bitmap form (CNT = false), which is the "seen twice" sift as it always was.
 //   add       the others go to a 1024-slot table keyed by (row of the cycle, column).  A slot is ONE word, the smallest key
 //             that reached it (= the column and the first range that touched it: the emission-order key), and one counter:
 //             sightings with both counts 1 in the low half — each adds (1, 1, 1) to the three sums — and the rare ones with
@@ -36,7 +44,7 @@
 #pragma once
 
 constexpr uint32_t PT_T = 256;                           // threads of the kernel's first form (the second, for the rows that exceed its cycle, has PT_T2)
-constexpr uint32_t PT_T2 = 512, PT_WGS2 = 3;             // (85 registers: three workgroups of eight waves per CU)
+constexpr uint32_t PT_T2 = 512, PT_WGS2 = 3;             // (asked for three workgroups of eight waves per CU; at 91-94 registers it gets five waves per SIMD: two)
 constexpr uint32_t PT_RB = 960;                          // ranges staged per cycle (10-bit range index in a key)
 constexpr uint32_t PT_ROWS = 4;                          // rows per cycle
 #ifndef PT_WG_PER_CU
@@ -45,19 +53,31 @@ constexpr uint32_t PT_ROWS = 4;                          // rows per cycle
 constexpr uint32_t PT_NCH = 4, PT_ITERS = PT_WG_PER_CU >= 5 ? 4 : 6;      // chunks of 64 lookups in flight per wave, steps per wave
 constexpr uint32_t PT_KPT = PT_NCH * PT_ITERS;           // keys a lane holds between the walk and the sift
 constexpr uint32_t PT_HEAVY_CAP = 64;                    // lookups with a count >= 2 per cycle
-constexpr uint32_t PT_BM_BITS = PT_WG_PER_CU >= 5 ? 10 : 11, PT_BM_WORDS = 1u << PT_BM_BITS;      // each bitmap: 32 Kbit (64 with four workgroups per CU)
-constexpr uint32_t PT_BM_SHIFT = 22 - PT_BM_BITS;        // word = h >> PT_BM_SHIFT, bit = the five bits below
+constexpr uint32_t PT_BM_BITS = PT_WG_PER_CU >= 5 ? 10 : 11, PT_BM_WORDS = 1u << PT_BM_BITS;      // the sift's counters fill 2 * PT_BM_WORDS words (8 KB; 16 with four workgroups per CU)
+constexpr uint32_t PT_CNT_WORDS = 2 * PT_BM_WORDS;       // 16-bit counters, two to a word: 4096 of them (8192)
+constexpr uint32_t PT_CNT_SHIFT = 22 - (PT_BM_BITS + 2); // counter = h >> PT_CNT_SHIFT: word = counter >> 1, half = counter & 1
+constexpr uint32_t PT_T_MAX = 255;                       // the sift's threshold never exceeds this
+constexpr uint32_t PT_BM_SHIFT = 22 - PT_BM_BITS;        // (bitmaps, for sets of a low threshold) word = h >> PT_BM_SHIFT, bit = the five bits below
+// The counters index 12 bits of h where a bitmap indexes 15: at a low threshold collisions let more through than "seen twice" on the
+// bitmaps does (64-genome set plus one short gene, survivors / table slots per cycle, tools/sift_threshold_sim.py and DESIGN section 4).
+// The set's threshold is clamp(tc_min, 2, 255), known on the host: below PT_SIFT_T_MIN the bitmap form of the kernel is launched.
+#ifndef PT_SIFT_T_MIN
+#define PT_SIFT_T_MIN 4
+#endif
 constexpr uint32_t PT_HT_BITS = 10, PT_HT = 1u << PT_HT_BITS;
 constexpr uint32_t PT_BATCH = 8;                         // rows a workgroup draws from the dispenser at a time
 // h(c) = c * M mod 2^22 with M = 0x9E3779B1 mod 2^22: only the low 22 bits of the multiplier matter, so the product is that of two
 // 24-bit values and v_mul_u32_u24 — a full-rate instruction, where v_mul_lo_u32 takes four times as long — gives the same hash.
 // (The multiplier matters: 0x9E3779 in its place slowed the whole join by a quarter — homologs' gene ids are regularly spaced,
-// and their bits in the two bitmaps collided.)
+// and their bits in the sift's bitmaps collided.)
 constexpr uint32_t PT_HASH_MUL = 0x9E3779B1u & 0x3fffffu;
 constexpr uint32_t pt_inverse(uint32_t m) { uint32_t x = m; for (int i = 0; i < 5; i++) x *= 2u - m * x; return x; }
 constexpr uint32_t PT_HASH_INV = pt_inverse(PT_HASH_MUL);
 static_assert((uint32_t) (PT_HASH_MUL * PT_HASH_INV) == 1u, "multiplicative inverse mod 2^32 (hence mod 2^22)");
 static_assert(PT_RB <= 1022 && PT_RB % PDL_WAVE == 0 && (3 * PT_HT) / 4 + PT_T2 <= CELL_CHUNK, "10-bit range index");
+// a counter takes 1 per light lookup of the cycle (at most PT_KPT * PT_T2 = 8192, all on one counter) and the threshold per listed heavy
+// one (at most PT_HEAVY_CAP of them: a heavy lookup that found no room in the side list adds nothing): it never carries into its neighbour
+static_assert(PT_KPT * PT_T2 + PT_HEAVY_CAP * PT_T_MAX < (1u << 16), "a 16-bit counter cannot overflow");
 
 // low 32 bits of the product of two 24-bit values, in ONE full-rate instruction (the compiler sees through __umul24 once the result is
 // masked — the low bits of a product do not depend on the high bits of its factors — and falls back to the quarter-rate v_mul_lo_u32)
@@ -72,16 +92,23 @@ struct PartRow { uint32_t p, r, kcnt, genome, lg, pc_min, pad0, pad1; };
 // TT threads: 256 (five workgroups per CU, a cycle of 4096 lookups) — every row goes through this form first — or 512 (a cycle of
 // 8192 lookups, for the rows the first form hands on because they alone exceed its cycle: on the 64-genome set 923 rows of
 // 4100-7200 lookups, which the filter tier used to take one per workgroup, a launch as long as its longest row)
-template <uint32_t TT, uint32_t WGS>
+// CNT: the sift's counters and threshold (above); false: two bitmaps, "seen" and "seen twice", on the top 15 bits of h — the sift of
+// threshold 2 with eight times the index space, which the host picks when the set's threshold is below PT_SIFT_T_MIN
+template <uint32_t TT, uint32_t WGS, bool CNT>
 __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
     constexpr uint32_t PT_T = TT, PT_NW = PT_T / PDL_WAVE;
     constexpr uint32_t PT_RPT = (PT_RB + PT_T - 1) / PT_T;              // ranges per thread in the staging loops
     constexpr uint32_t PT_LMAX = PT_KPT * PT_T;                         // lookups per cycle
-    constexpr uint32_t PT_WLIST = (PT_BM_WORDS + PT_RB + 66) / PT_NW;   // surviving keys a wave can list
+    // words behind the counters: the prefixes, later every wave's list.  A list wants four rounds of survivors (256 keys): whole steps of
+    // two keys per lane are drained, up to 127 keys stay, and two rounds must still fit.  The first form's four waves get that from the
+    // prefixes' room; the second form's eight take 4 KB more (35.9 KB: registers hold it at two workgroups per CU, LDS would allow four)
+    // rather than drain half-empty steps.  With bitmaps the list also takes the "seen" bitmap's room, as the prefixes' alone.
+    constexpr uint32_t PT_LIST = !CNT || PT_RB + 66 > PT_NW * PT_NCH * PDL_WAVE ? PT_RB + 66 : PT_NW * PT_NCH * PDL_WAVE;
+    constexpr uint32_t PT_WLIST = (CNT ? PT_LIST : PT_BM_WORDS + PT_LIST) / PT_NW;      // surviving keys a wave can list
     constexpr uint32_t PT_TOUCH_CAP = (3 * PT_HT) / 4 + PT_T;           // every row's part of the table takes keys until it is three quarters full (+ one per thread in flight)
-    static_assert(PT_WLIST >= PT_NCH * PDL_WAVE, "a wave's list holds at least one round of survivors");
-    __shared__ uint32_t s_big[2 * PT_BM_WORDS + PT_RB + 66];   // "seen twice" | "seen" | prefix of the staged ranges' lengths; once the walk is
-                                                               // over the last two are one stretch: every wave's list of surviving keys
+    static_assert(PT_WLIST >= PT_NCH * PDL_WAVE && PT_NCH % 2 == 0, "a wave's list holds four rounds of survivors: room for two is made before every two");
+    __shared__ uint32_t s_big[PT_CNT_WORDS + PT_LIST];         // the sift's counters | prefix of the staged ranges' lengths; once the walk is
+                                                               // over the latter is every wave's list of surviving keys (the counters are still read)
     __shared__ uint32_t s_tkey[PT_HT];                   // table: smallest key + 1 that reached the slot (0: empty)
     __shared__ uint32_t s_tn[PT_HT];                     //        sightings (each adds (1, 1, 1) to the three sums; what a count >= 2 adds beyond that waits in s_heavy)
     __shared__ uint16_t s_touched[PT_TOUCH_CAP];
@@ -99,7 +126,8 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
     const uint32_t n_work = a.n_work_ptr ? *a.n_work_ptr : a.n_work;
     if (n_work == 0) return;
     const uint32_t batch = min(max(a.work_batch, 1u), PT_BATCH);       // rows a workgroup draws at a time (one, for the few long rows of the second form)
-    uint32_t *s_bm2 = s_big, *s_bm1 = s_big + PT_BM_WORDS, *s_cum = s_big + 2 * PT_BM_WORDS;
+    uint32_t *s_cnt = s_big, *s_cum = s_big + PT_CNT_WORDS;
+    uint32_t *s_bm2 = s_big, *s_bm1 = s_big + PT_BM_WORDS;              // (!CNT) "seen twice" | "seen", where the counters are
     for (uint32_t i = tid; i < PT_HT; i += PT_T) { s_tkey[i] = 0; s_tn[i] = 0; }      // cleared once; afterwards every slot is reset by whoever consumes it
     if (tid == 0) { s_nheavy = 0; s_ntouched = 0; s_overflow = 0; s_solo = 0; s_bn = 0; s_bpos = 0; s_chunk_next = 0; s_chunk_end = 0; }
     if (tid < PT_ROWS) { s_tslot[tid] = 0; s_nemit[tid] = 0; }
@@ -180,7 +208,7 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                 rg[q] = a.ranges8[e0 + (i - rb)];
             }
 #pragma unroll
-            for (uint32_t i = 0; i < 2 * PT_BM_WORDS / 4 / PT_T; i++) reinterpret_cast<uint4 *>(s_big)[i * PT_T + tid] = make_uint4(0, 0, 0, 0);      // both bitmaps
+            for (uint32_t i = 0; i < PT_CNT_WORDS / 4 / PT_T; i++) reinterpret_cast<uint4 *>(s_big)[i * PT_T + tid] = make_uint4(0, 0, 0, 0);      // the counters
 #pragma unroll
             for (uint32_t q = 0; q < PT_RPT; q++) {
                 const uint32_t i = tid * PT_RPT + q;
@@ -296,7 +324,19 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
         }
         pdl_sync();
         PT_MARK(2);
-        // ---- walk: one key per lookup, kept in a register; the column marked "seen" / "seen twice" ----------------------------
+        // the sift's threshold: what finalize asks of a column with light sightings only (pcn >= the row's pc_min or tcn >= tc_min,
+        // both counts = the sightings), for the least demanding row of the cycle; never below 2 (a single sighting: rows of
+        // <= 2k k-mers are not taken here)
+        // (a row has min_kseq k-mers at least and min_numerator is monotone, so today no pc_min is below tc_min and the loop changes
+        // nothing: it keeps the rule whole should tc_min ever come from elsewhere)
+        uint32_t sift_t = 2u;
+        if (CNT && a.sift_threshold) {                       // (uniform)
+            sift_t = tc_min;
+#pragma unroll
+            for (uint32_t s = 0; s < PT_ROWS; s++) if (s < ns_keep) sift_t = min(sift_t, uni(s_row[s].pc_min));
+            sift_t = min(max(sift_t, 2u), PT_T_MAX);
+        }
+        // ---- walk: one key per lookup, kept in a register; the column's counter takes 1 -----------------------------------------
         // (lane -> range mapping as in k_join_lds: one coalesced read of the next 64 range starts per step, boundaries by
         // ds_permute + ballot + popcount)
         uint32_t key[PT_KPT];
@@ -368,6 +408,24 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                     }
 #pragma unroll
                     for (uint32_t u = 0; u < PT_NCH; u++) po[u] = a.post[live[u] ? adr[u] : 0u];       // dead lanes read posting 0: no exec juggling
+                    if constexpr (CNT) {
+#pragma unroll
+                        for (uint32_t u = 0; u < PT_NCH; u++) {          // four counter adds in flight, none waited for
+                            const uint32_t h = pt_mul_u24(po[u].x, PT_HASH_MUL) & 0x3fffffu;      // (gene ids have 22 bits here)
+                            key[it * PT_NCH + u] |= h << 10;
+                            const uint32_t ci = h >> PT_CNT_SHIFT;       // (the column alone: the rows of the cycle that meet it count together, and are told apart later)
+                            uint32_t add = 1u;
+                            // a count >= 2 on either side (rare; an own count of 1023 stands for "1023 or more"): the lookup keeps its column in
+                            // whatever else is seen of it (it adds the threshold); it is entered as an ordinary sighting, and what its counts add
+                            // beyond (1, 1, 1) is listed.  No room in the list: the cycle is void, and the counter is left alone (it cannot overflow)
+                            if (live[u] && (po[u].y >= 2u || ((ownhv >> u) & 1u))) {
+                                const uint32_t i = atomicAdd(&s_nheavy, 1u);
+                                add = i < PT_HEAVY_CAP ? sift_t : 0u;
+                                if (i < PT_HEAVY_CAP) s_heavy[i] = make_uint2(key[it * PT_NCH + u], po[u].y);
+                            }
+                            if (live[u]) atomicAdd(&s_cnt[ci >> 1], add << ((ci & 1u) << 4));
+                        }
+                    } else {
                     uint32_t seen[PT_NCH], bit[PT_NCH], wd[PT_NCH];
 #pragma unroll
                     for (uint32_t u = 0; u < PT_NCH; u++) {          // four bitmap atomics in flight
@@ -375,8 +433,7 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                         key[it * PT_NCH + u] |= h << 10;
                         wd[u] = h >> PT_BM_SHIFT; bit[u] = 1u << ((h >> (PT_BM_SHIFT - 5)) & 31u);        // (the column alone: a column two rows of the cycle meet once each survives the sift and is told apart later)
                         seen[u] = live[u] ? atomicOr(&s_bm1[wd[u]], bit[u]) : 0u;
-                        // a count >= 2 on either side (rare; an own count of 1023 stands for "1023 or more"): the lookup survives the sift by
-                        // itself (both bits set); it is entered as an ordinary sighting, and what its counts add beyond (1, 1, 1) is listed
+                        // a count >= 2 on either side: the lookup survives the sift by itself (both bits set); entered and listed as above
                         if (live[u] && (po[u].y >= 2u || ((ownhv >> u) & 1u))) {
                             seen[u] = bit[u];
                             const uint32_t i = atomicAdd(&s_nheavy, 1u);
@@ -385,6 +442,7 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                     }
 #pragma unroll
                     for (uint32_t u = 0; u < PT_NCH; u++) if (seen[u] & bit[u]) atomicOr(&s_bm2[wd[u]], bit[u]);
+                    }
                 }
                 ch += PT_NCH;
             }
@@ -392,36 +450,41 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
         pdl_sync();
         PT_MARK(3);
         // ---- sift + add ------------------------------------------------------------------------------------------------------------------
-        // sift: the lookups that are not alone on their bit are compacted into the wave's list (bm1 and the prefix array are done
+        // sift: the lookups whose counter reached the threshold are compacted into the wave's list (the prefix array is done
         // with); add: the list goes to the table, two keys per lane at a time
-        uint32_t *wlist = s_bm1 + wave * PT_WLIST;
+        uint32_t *wlist = (CNT ? s_cum : s_bm1) + wave * PT_WLIST;      // (with bitmaps "seen" is done with too; "seen twice" is still read)
         uint32_t nsv = 0;                                    // (wave-uniform) keys in the list
         const uint32_t n_heavy = uni(s_nheavy);
         if (n_heavy > PT_HEAVY_CAP) s_overflow = 1;
-        auto drain = [&]() {
+        // (all = false: whole steps of two keys per lane only, taken from the list's end; fewer than one step's worth stay listed)
+        auto drain = [&](bool all) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // the wave reads back the list it has just written
-            for (uint32_t i0 = 0; i0 < nsv; i0 += 2 * PDL_WAVE) {
+            const uint32_t i_lo = all ? 0u : nsv % (2 * PDL_WAVE);
+            for (uint32_t i0 = i_lo; i0 < nsv; i0 += 2 * PDL_WAVE) {
                 const uint32_t ia = i0 + lane, ib = ia + PDL_WAVE;
                 const uint32_t ka = wlist[ia < nsv ? ia : 0u], kb = wlist[ib < nsv ? ib : 0u];          // two independent chains per lane
                 if (ia < nsv) add_one(ka);
                 if (ib < nsv) add_one(kb);
             }
-            nsv = 0;
+            nsv = i_lo;
         };
         {
             const uint32_t nkeys = ch0 < chunks ? min(chunks - ch0, cpw) : 0u;       // keys per lane of this wave (the last chunk may be partial)
 #pragma unroll
             for (uint32_t g = 0; g < PT_ITERS; g++) {
                 if (g * PT_NCH >= nkeys) break;              // (uniform)
-                if (nsv + PT_NCH * PDL_WAVE > PT_WLIST) drain();         // (uniform, rare) no room for another four rounds of survivors: the list goes to the table first
-                uint32_t twice[PT_NCH];
+                if (!CNT && nsv + PT_NCH * PDL_WAVE > PT_WLIST) drain(true);      // (uniform, rare; the bitmaps' list is twice as long and is emptied whole)
+                uint32_t cw[PT_NCH];
 #pragma unroll
-                for (uint32_t u = 0; u < PT_NCH; u++) twice[u] = s_bm2[(key[g * PT_NCH + u] >> (10 + PT_BM_SHIFT)) & (PT_BM_WORDS - 1)];      // four reads in flight
+                for (uint32_t u = 0; u < PT_NCH; u++)        // four reads in flight
+                    cw[u] = CNT ? s_cnt[(key[g * PT_NCH + u] >> (10 + PT_CNT_SHIFT + 1)) & (PT_CNT_WORDS - 1)] : s_bm2[(key[g * PT_NCH + u] >> (10 + PT_BM_SHIFT)) & (PT_BM_WORDS - 1)];
 #pragma unroll
                 for (uint32_t u = 0; u < PT_NCH; u++) {
                     const uint32_t i = g * PT_NCH + u;
                     if (i >= nkeys) break;                   // (uniform)
-                    const bool keep = (ch0 + i) * PDL_WAVE + lane < total && ((twice[u] >> ((key[i] >> (10 + PT_BM_SHIFT - 5)) & 31u)) & 1u);
+                    if (CNT && u % 2 == 0 && nsv + 2 * PDL_WAVE > PT_WLIST) drain(false);       // (uniform) no room for another two rounds of survivors: the list's whole steps go to the table first
+                    const bool keep = (ch0 + i) * PDL_WAVE + lane < total &&
+                                      (CNT ? ((cw[u] >> (((key[i] >> (10 + PT_CNT_SHIFT)) & 1u) << 4)) & 0xffffu) >= sift_t : ((cw[u] >> ((key[i] >> (10 + PT_BM_SHIFT - 5)) & 31u)) & 1u) != 0u);
                     const unsigned long long mk = __ballot(keep);
                     if (keep) wlist[nsv + (uint32_t) __popcll(mk & ((1ull << lane) - 1ull))] = key[i];
                     nsv += (uint32_t) __popcll(mk);
@@ -430,7 +493,7 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
 #endif
                 }
             }
-            drain();
+            drain(true);
         }
         pdl_sync();
         PT_MARK(4);
