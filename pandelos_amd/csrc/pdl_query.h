@@ -98,55 +98,67 @@ void pdl_fail_absent_byte(uint64_t bad_word, const char *who) {
              (b >= 32 && b < 127) ? (char) b : '?');
 }
 
-template <class KeyT> struct QView {
+// first position in [lo, hi) whose rank is >= v (UPPER: > v); rank(position) ascends over the range
+template <bool UPPER, class RankF>
+__device__ __forceinline__ uint32_t q_bound(RankF rank, uint32_t lo, uint32_t hi, unsigned long long v) {
+    while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = rank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
+    return lo;
+}
+
+// The base's postings as the searches see them.  The query records come with a rank accessor of the caller's — position ->
+// rank over the caller's index space: k_q_fold / k_q_match read keys[recpos[j]], the batch (pdl_query_batch.h) its segment copy.
+template <class KeyT> struct QBase {
     const KeyT *bkeys; const uint32_t *brecpos; const uint32_t *bvals; const uint2 *post; uint32_t U; uint64_t M;
-    const KeyT *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
     __device__ unsigned long long brank(uint32_t u) const { return (unsigned long long) bkeys[brecpos[u]]; }
-    __device__ unsigned long long qrank(uint32_t j) const { return (unsigned long long) qkeys[qrecpos[j]]; }
-    // first u in [lo, hi) with rank(u) >= v (UPPER: > v); ranks ascend over the range
     template <bool UPPER> __device__ uint32_t bbound(uint32_t lo, uint32_t hi, unsigned long long v) const {
-        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = brank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
-        return lo;
-    }
-    template <bool UPPER> __device__ uint32_t qbound(uint32_t lo, uint32_t hi, unsigned long long v) const {
-        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = qrank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
-        return lo;
+        return q_bound<UPPER>([&](uint32_t u) { return brank(u); }, lo, hi, v);
     }
 };
+template <class KeyT> struct QView {
+    QBase<KeyT> b;
+    const KeyT *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
+};
 
-// One thread: the folds of the base and of the union (see the head of this file).
+// The base half of the fold (see the head of this file): bmax, and when the base folded its last record: r2, gs, p.
+// lonely: the base's last record is alone in its rank; has_r2: there is a group below it that it was folded into.
 template <class KeyT>
-__global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely, bool &has_r2) {
     QFold f{};
     f.p = Q_NONE; f.qL = Q_NONE;
-    const uint32_t Uq = (uint32_t) ctl[Q_CTL_RECORDS];
-    const uint32_t U = v.U;
-    f.bmax = (unsigned long long) v.bkeys[v.M - 1];
-    bool lonely = U == 1;                 // the base's last record is alone in its rank (U == 1: nothing to fold it into)
-    bool has_r2 = false;
+    const uint32_t U = b.U;
+    f.bmax = (unsigned long long) b.bkeys[b.M - 1];
+    lonely = U == 1;                      // (U == 1: nothing to fold it into)
+    has_r2 = false;
     if (U == 1) f.p = 0;
     else {
-        const unsigned long long rl = v.brank(U - 1), rl2 = v.brank(U - 2);
+        const unsigned long long rl = b.brank(U - 1), rl2 = b.brank(U - 2);
         f.folded = (rl != f.bmax || rl2 != f.bmax) ? 1u : 0u;
         if (f.folded) {
             lonely = has_r2 = true;
             f.r2 = rl != f.bmax ? rl : rl2;
-            f.gs = v.template bbound<false>(0, U, f.r2);          // (p ranks above r2: the predicate rank < r2 stays monotone)
-            const uint32_t gl = v.bvals[v.M - 1];                 // gene of the folded record; [gs, U) ascends by gene, p included
+            f.gs = b.template bbound<false>(0, U, f.r2);          // (p ranks above r2: the predicate rank < r2 stays monotone)
+            const uint32_t gl = b.bvals[b.M - 1];                 // gene of the folded record; [gs, U) ascends by gene, p included
             uint32_t lo = f.gs, hi = U;
-            while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (v.post[m].x < gl) lo = m + 1; else hi = m; }
-            if (v.brank(lo) != f.bmax) lo++;                      // the r2 record of the same gene sits in front of p
+            while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (b.post[m].x < gl) lo = m + 1; else hi = m; }
+            if (b.brank(lo) != f.bmax) lo++;                      // the r2 record of the same gene sits in front of p
             f.p = lo;
         }
     }
-    const unsigned long long qmax = v.qrank(Uq - 1);
-    const bool alone = Uq == 1 || v.qrank(Uq - 2) != qmax;
+    return f;
+}
+
+// The union half: Q1's cases (a)-(d) for the query whose records are the positions [s0, s1) (not empty) of qrank's index
+// space; f.qL is a position of that space.
+template <class RankF>
+__device__ __forceinline__ void q_fold_union(QFold &f, bool lonely, bool has_r2, RankF qrank, uint32_t s0, uint32_t s1) {
+    const uint32_t Uq = s1 - s0;
+    const unsigned long long qmax = qrank(s1 - 1);
+    const bool alone = Uq == 1 || qrank(s1 - 2) != qmax;
     if (qmax > f.bmax) {
         f.skip_p = f.folded;
         if (alone) {
-            f.qL = Uq - 1;
-            const unsigned long long q2 = Uq >= 2 ? v.qrank(Uq - 2) : 0ull;
+            f.qL = s1 - 1;
+            const unsigned long long q2 = Uq >= 2 ? qrank(s1 - 2) : 0ull;
             f.tgt = (Uq >= 2 && q2 > f.bmax) ? q2 : f.bmax;
         }
     } else if (qmax == f.bmax) {
@@ -154,7 +166,39 @@ __global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *ou
     } else if (lonely && (!has_r2 || qmax > f.r2)) {
         f.skip_p = f.folded; f.has_extra = 1; f.extra_target = qmax;
     }
+}
+
+// One thread: the folds of the base and of the union.  Launched only for a query with a k-mer (Mq >= 1), which therefore has a
+// record: q_fold_union's [0, records) is not empty.
+template <class KeyT>
+__global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    bool lonely, has_r2;
+    QFold f = q_fold_base(v.b, lonely, has_r2);
+    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.qkeys[v.qrecpos[j]]; }, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
     *out = f;
+}
+
+// The union group of query record j, one of the records [s0, s1) of its query (positions of qrank's index space).  The key is
+// taken relative to s0: the same for a query on its own and as a segment of a batch.
+template <class KeyT, class RankF>
+__device__ __forceinline__ QDesc q_describe(const QFold &f, const QBase<KeyT> &b, RankF qrank, uint32_t j, uint32_t s0, uint32_t s1) {
+    const unsigned long long eff = j == f.qL ? f.tgt : qrank(j);
+    QDesc d;
+    d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
+    if (f.folded) {
+        if (eff < f.r2) { d.blo = b.template bbound<false>(0, f.gs, eff); d.bhi = b.template bbound<true>(d.blo, f.gs, eff); }
+        else if (eff == f.r2) { d.blo = f.gs; d.bhi = b.U; if (f.skip_p) d.bskip = f.p; }
+        else if (eff == f.bmax) { d.blo = f.p; d.bhi = f.p + 1; }
+    } else {
+        d.blo = b.template bbound<false>(0, b.U, eff); d.bhi = b.template bbound<true>(d.blo, b.U, eff);
+    }
+    if (f.has_extra && eff == f.extra_target) d.bextra = f.p;
+    const uint32_t qn = f.qL != Q_NONE ? s1 - 1 : s1;             // the searches among query records stay inside [s0, s1)
+    d.qlo = q_bound<false>(qrank, s0, qn, eff); d.qhi = q_bound<true>(qrank, d.qlo, qn, eff);
+    if (f.qL != Q_NONE && eff == f.tgt) d.qextra = f.qL;
+    d.key = 2u * (d.qlo - s0) + (d.qhi > d.qlo ? 1u : 0u);
+    return d;
 }
 
 struct QMatchOut {
@@ -168,22 +212,7 @@ __global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf,
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     if (j < Uq && j < bound) {
-        const unsigned long long r = v.qrank(j);
-        const unsigned long long eff = j == f.qL ? f.tgt : r;
-        QDesc d;
-        d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
-        if (f.folded) {
-            if (eff < f.r2) { d.blo = v.template bbound<false>(0, f.gs, eff); d.bhi = v.template bbound<true>(d.blo, f.gs, eff); }
-            else if (eff == f.r2) { d.blo = f.gs; d.bhi = v.U; if (f.skip_p) d.bskip = f.p; }
-            else if (eff == f.bmax) { d.blo = f.p; d.bhi = f.p + 1; }
-        } else {
-            d.blo = v.template bbound<false>(0, v.U, eff); d.bhi = v.template bbound<true>(d.blo, v.U, eff);
-        }
-        if (f.has_extra && eff == f.extra_target) d.bextra = f.p;
-        const uint32_t qn = f.qL != Q_NONE ? Uq - 1 : Uq;
-        d.qlo = v.template qbound<false>(0, qn, eff); d.qhi = v.template qbound<true>(d.qlo, qn, eff);
-        if (f.qL != Q_NONE && eff == f.tgt) d.qextra = f.qL;
-        d.key = 2u * d.qlo + (d.qhi > d.qlo ? 1u : 0u);
+        const QDesc d = q_describe(f, v.b, [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; }, j, 0u, Uq);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
         const uint32_t gene = v.qpost[j].x;
@@ -199,7 +228,6 @@ __global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf,
     }
 }
 
-// row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns)
 // row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns); rows whose
 // lookups exceed `limit` (they may claim more columns than the LDS table of the join holds)
 __global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, const unsigned long long *ctl, uint32_t n, uint32_t *row_off,
@@ -223,8 +251,8 @@ __global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, 
 }
 
 // ---- Q-join ------------------------------------------------------------------------------------------------------------
-// (k_q_join and k_q_join_hbm have copies that take their row's arguments per workgroup — k_qb_join / k_qb_join_hbm in
-// pdl_query_batch.h: a change to the row program below belongs there too.)
+// The row program — q_row_lds, q_row_hbm — is also the batch's: k_qb_join / k_qb_join_hbm (pdl_query_batch.h) hand it the
+// arguments of the row's own query.
 constexpr int QJ_T = 256;
 constexpr uint32_t QJ_HT_BITS = 12, QJ_HT = 1u << QJ_HT_BITS;
 constexpr uint32_t QJ_LIMIT = QJ_HT - 2 * QJ_T;         // keys a row may claim before it goes to the HBM tables (< HT: probes end)
@@ -323,14 +351,15 @@ __device__ __forceinline__ float q_finalize(const QJoinArgs &a, uint32_t g, uint
     return score;
 }
 
-__global__ __launch_bounds__(QJ_T) void k_q_join(QJoinArgs a) {
+// One row on the LDS table: row g of `a` (uniform over the workgroup).  A row whose columns do not fit the table leaves
+// overflow_id — what the HBM kernel of the caller finds the row by — in a.overflow_rows and emits nothing.
+__device__ __forceinline__ void q_row_lds(const QJoinArgs &a, uint32_t g, uint32_t overflow_id) {
     __shared__ uint32_t s_key[QJ_HT], s_first[QJ_HT];
     __shared__ unsigned long long s_acc[QJ_HT];
     __shared__ QDesc s_d[QJ_T];
     __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
     __shared__ uint32_t s_nkeys, s_stop, s_ncell;
     __shared__ unsigned long long s_cbase;
-    const uint32_t g = blockIdx.x;
     if (a.row_off[g] == a.row_off[g + 1]) {               // (uniform) no k-mer, no cell
         if (threadIdx.x == 0) { a.row_cnt[g] = 0; a.row_base[g] = 0; }
         return;
@@ -358,7 +387,7 @@ __global__ __launch_bounds__(QJ_T) void k_q_join(QJoinArgs a) {
     if (s_stop) {                                         // (uniform: read after the walk's last barrier) more columns than the table holds
         if (threadIdx.x == 0) {
             const unsigned long long i = atomicAdd(a.n_overflow, 1ull);
-            a.overflow_rows[i] = g;
+            a.overflow_rows[i] = overflow_id;
             a.row_cnt[g] = 0; a.row_base[g] = 0;
         }
         return;
@@ -391,62 +420,65 @@ __global__ __launch_bounds__(QJ_T) void k_q_join(QJoinArgs a) {
     }
 }
 
-// The rows k_q_join handed on: the same row program with one dense table per workgroup in HBM (all zero / all-ones first
-// between rows: every touched entry is reset by the pass that emits it).  Launched only when a row did overflow; the tables are
-// allocated then, and cleared again whenever the column count they were laid out for is not this query's.
-__global__ __launch_bounds__(QJ_T) void k_q_join_hbm(QJoinArgs a) {
+__global__ __launch_bounds__(QJ_T) void k_q_join(QJoinArgs a) { q_row_lds(a, blockIdx.x, blockIdx.x); }
+
+// One row on a workgroup's dense tables in HBM (acc, first, touched: all zero / all-ones first between rows — every touched
+// entry is reset by the pass that emits it): the walk, the count pass, the emit pass.
+__device__ __forceinline__ void q_row_hbm(const QJoinArgs &a, uint32_t g, unsigned long long *acc, uint32_t *first, uint32_t *touched) {
     __shared__ QDesc s_d[QJ_T];
     __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
     __shared__ uint32_t s_stop, s_ntouch, s_ncell, s_emit;
     __shared__ unsigned long long s_cbase;
+    if (threadIdx.x == 0) { s_stop = 0; s_ntouch = 0; s_ncell = 0; s_emit = 0; }
+    pdl_sync();
+    q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
+        const uint32_t old = atomicMin(&first[col], key);
+        if (old == 0xffffffffu) touched[atomicAdd(&s_ntouch, 1u)] = col;
+        atomicAdd(&acc[col], packed);
+        return true;
+    });
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    pdl_sync();
+    const uint32_t nt = s_ntouch;
+    for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // count (the maxima are taken here, once per cell)
+        const uint32_t col = ld_agent(&touched[i]);
+        float p, t;
+        if (q_finalize(a, g, col, ld_agent(&acc[col]), p, t) > 0.0f) atomicAdd(&s_ncell, 1u);
+    }
+    pdl_sync();
+    if (threadIdx.x == 0) {
+        s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
+        a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
+    }
+    pdl_sync();
+    const float threshold = 1.0f / (2.0f * (float) a.k);
+    const uint32_t my_k = a.kseq_q[g];
+    for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // write, and leave the entries clean
+        const uint32_t col = ld_agent(&touched[i]);
+        const unsigned long long v = ld_agent(&acc[col]);
+        const uint32_t key = ld_agent(&first[col]);
+        float p, t;
+        const float score = finalize_cell(v, my_k, col < a.N ? a.kseq_b[col] : a.kseq_q[col - a.N], threshold, p, t);
+        if (score > 0.0f) {
+            const uint64_t o = s_cbase + atomicAdd(&s_emit, 1u);
+            a.st_score[o] = score; a.st_perc[o] = p; a.st_tr[o] = t; a.st_col[o] = col; a.st_first[o] = key;
+        }
+        acc[col] = 0ull; first[col] = 0xffffffffu;
+    }
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    pdl_sync();
+}
+
+// The rows k_q_join handed on, min(rows, QH_WG) workgroups with a table each.  Launched only when a row did overflow; the tables
+// are allocated then, and cleared again whenever the column count they were laid out for is not this query's.
+__global__ __launch_bounds__(QJ_T) void k_q_join_hbm(QJoinArgs a) {
     const uint32_t n_cols = a.N + a.n;
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(a.hbm + (size_t) blockIdx.x * n_cols * 16);
     uint32_t *first = reinterpret_cast<uint32_t *>(acc + n_cols);
-    uint32_t *touched = first + n_cols;
     const uint32_t n_over = (uint32_t) *a.n_overflow;
-    for (uint32_t w = blockIdx.x; w < n_over; w += gridDim.x) {
-        const uint32_t g = a.overflow_rows[w];
-        if (threadIdx.x == 0) { s_stop = 0; s_ntouch = 0; s_ncell = 0; s_emit = 0; }
-        pdl_sync();
-        q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
-            const uint32_t old = atomicMin(&first[col], key);
-            if (old == 0xffffffffu) touched[atomicAdd(&s_ntouch, 1u)] = col;
-            atomicAdd(&acc[col], packed);
-            return true;
-        });
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pdl_sync();
-        const uint32_t nt = s_ntouch;
-        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // count (the maxima are taken here, once per cell)
-            const uint32_t col = ld_agent(&touched[i]);
-            float p, t;
-            if (q_finalize(a, g, col, ld_agent(&acc[col]), p, t) > 0.0f) atomicAdd(&s_ncell, 1u);
-        }
-        pdl_sync();
-        if (threadIdx.x == 0) {
-            s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
-            a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
-        }
-        pdl_sync();
-        const float threshold = 1.0f / (2.0f * (float) a.k);
-        const uint32_t my_k = a.kseq_q[g];
-        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // write, and leave the entries clean
-            const uint32_t col = ld_agent(&touched[i]);
-            const unsigned long long v = ld_agent(&acc[col]);
-            const uint32_t key = ld_agent(&first[col]);
-            float p, t;
-            const float score = finalize_cell(v, my_k, col < a.N ? a.kseq_b[col] : a.kseq_q[col - a.N], threshold, p, t);
-            if (score > 0.0f) {
-                const uint64_t o = s_cbase + atomicAdd(&s_emit, 1u);
-                a.st_score[o] = score; a.st_perc[o] = p; a.st_tr[o] = t; a.st_col[o] = col; a.st_first[o] = key;
-            }
-            acc[col] = 0ull; first[col] = 0xffffffffu;
-        }
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pdl_sync();
-    }
+    for (uint32_t w = blockIdx.x; w < n_over; w += gridDim.x) q_row_hbm(a, a.overflow_rows[w], acc, first, first + n_cols);
 }
 
 // the HBM tables of `slots` workgroups laid out for n_cols columns, in the state k_q_join_hbm leaves them: acc 0, first all ones
@@ -466,11 +498,107 @@ __global__ __launch_bounds__(256) void k_q_rowids(uint32_t *ids, uint32_t base, 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
+// What pdl_run_query and the batch's qb_run_chunk (pdl_query_batch.h) both do behind the match.
+
+// device time = the stretches of device work between the host's reads, each between an event pair of `ev` (three at most)
+struct QSpans {
+    hipEvent_t *ev; hipStream_t st; int n = 0;
+    QSpans(hipEvent_t (&e)[6], hipStream_t s) : ev(e), st(s) { for (int i = 0; i < 6; i++) if (!ev[i]) PDL_HIP(hipEventCreate(&ev[i])); }
+    void begin() { PDL_HIP(hipEventRecord(ev[2 * n], st)); }
+    void end() { PDL_HIP(hipEventRecord(ev[2 * n + 1], st)); n++; }
+    float total_ms() const {           // (after the stream has been synchronized)
+        float total = 0.f;
+        for (int i = 0; i < n; i++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) total += ms; }
+        return total;
+    }
+};
+
+// the join's arguments as far as the base and the staging (five arrays of `cap` cells at `stf`) set them; the caller adds its own
+// buffers, the query genes' count and the counters
+static QJoinArgs q_join_args(pdl_ctx *c, float *stf, uint64_t cap) {
+    QJoinArgs a{};
+    a.post = c->post.as<uint2>(); a.kseq_b = c->kseq_len.as<uint32_t>(); a.genome_b = c->d_gen;
+    a.N = c->N; a.G1 = c->G + 1; a.k = c->rp.k;
+    a.st_score = stf; a.st_perc = stf + cap; a.st_tr = stf + 2 * cap;
+    a.st_col = reinterpret_cast<uint32_t *>(stf + 3 * cap); a.st_first = reinterpret_cast<uint32_t *>(stf + 4 * cap);
+    return a;
+}
+
+// The HBM tier, when some row has more lookups than the LDS table holds keys: the host looks whether a row left the table
+// (*d_n_over); if so, tables (c->qb.hbm, shared by the single query and the batch) for W = min(rows, QH_WG) workgroups laid out for
+// n_cols columns — clean tables of exactly that layout are taken as they are, any other are cleared, and the bookkeeping says what
+// a later query will find (not clean from before the allocation until the clear is queued, so a throwing allocation leaves no
+// stale claim) — then launch(tables, W).
+template <class LaunchF>
+static void q_join_hbm_tier(pdl_ctx *c, QSpans &spans, const unsigned long long *d_n_over, uint32_t n_cols, LaunchF launch) {
+    auto &q = c->qb;
+    uint64_t n_over = 0;
+    spans.end();
+    {
+        PinRead rd(c);
+        const uint64_t *pc = rd.add<uint64_t>(d_n_over, 1);
+        rd.sync();
+        n_over = pc[0];
+    }
+    spans.begin();
+    if (!n_over) return;
+    const uint32_t W = (uint32_t) std::min<uint64_t>(n_over, QH_WG);
+    if (!q.hbm_clean || q.hbm_cols != n_cols || q.hbm_slots < W) {
+        q.hbm_clean = false;
+        q.hbm.alloc((size_t) W * n_cols * 16);
+        hipLaunchKernelGGL(k_q_hbm_clear, dim3((uint32_t) std::min<uint64_t>(((uint64_t) W * n_cols + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                           q.hbm.as<uint8_t>(), n_cols, W);
+        q.hbm_cols = n_cols; q.hbm_slots = W; q.hbm_clean = true;
+    }
+    launch(q.hbm.as<uint8_t>(), W);
+    PDL_HIP(hipGetLastError());
+}
+
+// Q-order: the rows' final offsets (into fin_off; their total goes to *emitted) and the join's two ordering kernels, from the
+// staging of `a` into `cells` (five arrays of `cap`); rowid: the rows' gene ids; max_cols: the widest union's columns
+static void q_order_rows(pdl_ctx *c, const QJoinArgs &a, uint32_t *fin_off, uint32_t *rowid, float *cells, uint32_t n_rows, uint64_t cap,
+                         uint64_t max_cols, unsigned long long *emitted, unsigned long long *wide_rows) {
+    scan_and_apply(c, n_rows, RowCntFlag{a.row_cnt, nullptr}, FinOffApply{fin_off}, reinterpret_cast<uint64_t *>(emitted));
+    OrderArgs o{};
+    o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = fin_off; o.task_rows = rowid;
+    o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
+    o.c_score = cells; o.c_perc = cells + cap; o.c_tr = cells + 2 * cap;
+    o.c_row = reinterpret_cast<int32_t *>(cells + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cells + 4 * cap);
+    o.n_rows = n_rows; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = max_cols < (1u << 22) ? 1u : 0u;
+    o.wide_rows = reinterpret_cast<uint32_t *>(wide_rows);
+    hipLaunchKernelGGL(k_order_rows_wave, dim3((n_rows + 3) / 4), dim3(256), 0, c->stream, o);
+    hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n_rows, (uint32_t) pdl_cus(c) * 8)), dim3(ORDER_THREADS), 0, c->stream, o);
+}
+
+// The block as library.cpp:542-603 marshals it, for Z cells of n query genes: q_block_alloc sets the counts and allocates the
+// ten arrays (a throw leaves what is allocated to pdl_free_scores); q_block_ids fills what the host knows once r.column is in.
+static void q_block_alloc(pdl_ctx *c, pdl_scores &r, uint64_t Z, uint32_t n) {
+    const uint32_t G1 = c->G + 1, NC = c->N + n;
+    auto xm = [](size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) throw std::bad_alloc(); return p; };
+    if (Z > 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu cells exceed the block's 32-bit scoresCount", (unsigned long long) Z);
+    r.scoresCount = (uint32_t) Z; r.rows = n; r.genomes = G1; r.sequences = NC;
+    r.scores = (float *) xm(Z * 4); r.percs = (float *) xm(Z * 4); r.tr_percs = (float *) xm(Z * 4);
+    r.row = (int32_t *) xm(Z * 4); r.column = (int32_t *) xm(Z * 4);
+    r.first_seq_genome = (int32_t *) xm(Z * 4); r.second_seq_genome = (int32_t *) xm(Z * 4);
+    r.max_genome_score = (float *) xm((size_t) n * G1 * 4); r.max_genome_score_col = (float *) xm((size_t) NC * 4);
+    r.scoresMaxMappings = (int32_t *) xm((size_t) NC * 4);
+}
+static void q_block_ids(pdl_ctx *c, pdl_scores &r) {
+    const uint32_t N = c->N, G = c->G;
+    for (uint64_t i = 0; i < r.scoresCount; i++) {
+        r.first_seq_genome[i] = (int32_t) G;
+        const uint32_t col = (uint32_t) r.column[i];
+        r.second_seq_genome[i] = col < N ? (int32_t) c->h_genome_of[col] : (int32_t) G;
+    }
+    for (uint32_t i = 0; i < N; i++) r.scoresMaxMappings[i] = 0x7fffffff;
+    for (uint32_t g = 0; g < r.rows; g++) r.scoresMaxMappings[N + g] = (int32_t) g;
+}
+
 template <class KeyT>
 static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
     QView<KeyT> v;
-    v.bkeys = c->keys_b.as<KeyT>(); v.brecpos = c->recpos.as<uint32_t>(); v.bvals = c->vals_b.as<uint32_t>(); v.post = c->post.as<uint2>();
-    v.U = (uint32_t) c->U; v.M = c->M;
+    v.b.bkeys = c->keys_b.as<KeyT>(); v.b.brecpos = c->recpos.as<uint32_t>(); v.b.bvals = c->vals_b.as<uint32_t>(); v.b.post = c->post.as<uint2>();
+    v.b.U = (uint32_t) c->U; v.b.M = c->M;
     v.qkeys = static_cast<const KeyT *>(qkeys); v.qrecpos = c->qb.recpos.as<uint32_t>(); v.qpost = c->qb.post.as<uint2>();
     return v;
 }
@@ -498,12 +626,8 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     }
     h_off[n] = Rq; h_koff[n] = Mq;
     if (Mq >= 0x7ffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu query k-mers exceed the 31-bit record positions", (unsigned long long) Mq);
-    // device time = the stretches of device work between the host's reads, each between an event pair
-    for (int i = 0; i < 6; i++) if (!q.ev[i]) PDL_HIP(hipEventCreate(&q.ev[i]));
-    int span = 0;
-    auto span_begin = [&]() { PDL_HIP(hipEventRecord(q.ev[2 * span], st)); };
-    auto span_end = [&]() { PDL_HIP(hipEventRecord(q.ev[2 * span + 1], st)); span++; };
-    span_begin();
+    QSpans spans(q.ev, st);
+    spans.begin();
 
     // Q-alpha
     q.ctl.alloc(Q_CTL_WORDS * sizeof(uint64_t));
@@ -551,14 +675,14 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         q.rec_sorted_at = ix_out;
     }
     uint64_t h_ctl[Q_CTL_USED] = {};
-    span_end();
+    spans.end();
     {
         PinRead rd(c);
         const uint64_t *pc = rd.add<uint64_t>(ctl, Q_CTL_USED);
         rd.sync();
         memcpy(h_ctl, pc, sizeof(h_ctl));
     }
-    span_begin();
+    spans.begin();
     if (h_ctl[Q_CTL_BAD_BYTE]) pdl_fail_absent_byte(h_ctl[Q_CTL_BAD_BYTE], "query");
     const uint64_t Uq = h_ctl[Q_CTL_RECORDS], cost = h_ctl[Q_CTL_COST], matched = h_ctl[Q_CTL_MATCHED], bound = h_ctl[Q_CTL_BOUND],
                    may_overflow = h_ctl[Q_CTL_MAY_OVERFLOW];
@@ -574,58 +698,21 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         q.st.alloc(std::max<uint64_t>(bound, 1) * 20); q.cells.alloc(std::max<uint64_t>(bound, 1) * 20);
         hipLaunchKernelGGL(k_q_rowids, dim3((n + 255) / 256), dim3(256), 0, st, q.rowid.as<uint32_t>(), N, n);
         const uint64_t cap = std::max<uint64_t>(bound, 1);
-        QJoinArgs a{};
-        a.post = c->post.as<uint2>(); a.qpost = q.post.as<uint2>(); a.desc = q.desc.as<QDesc>();
-        a.rec_sorted = q.rec_sorted_at; a.row_off = q.row_off.as<uint32_t>();
-        a.kseq_b = c->kseq_len.as<uint32_t>(); a.kseq_q = q.kseq.as<uint32_t>(); a.genome_b = c->d_gen;
-        a.N = N; a.n = n; a.G1 = G1; a.k = k;
-        a.MS = q.MS.as<float>(); a.CM = q.CM.as<float>();
+        QJoinArgs a = q_join_args(c, q.st.as<float>(), cap);
+        a.qpost = q.post.as<uint2>(); a.desc = q.desc.as<QDesc>(); a.rec_sorted = q.rec_sorted_at; a.row_off = q.row_off.as<uint32_t>();
+        a.kseq_q = q.kseq.as<uint32_t>(); a.n = n; a.MS = q.MS.as<float>(); a.CM = q.CM.as<float>();
         a.row_base = q.row_base.as<uint32_t>(); a.row_cnt = q.row_cnt.as<uint32_t>();
-        float *stf = q.st.as<float>();
-        a.st_score = stf; a.st_perc = stf + cap; a.st_tr = stf + 2 * cap;
-        a.st_col = reinterpret_cast<uint32_t *>(stf + 3 * cap); a.st_first = reinterpret_cast<uint32_t *>(stf + 4 * cap);
         a.cell_cursor = ctl + Q_CTL_CELL_CURSOR; a.overflow_rows = q.overflow.as<uint32_t>(); a.n_overflow = ctl + Q_CTL_OVERFLOW_ROWS;
         hipLaunchKernelGGL(k_q_join, dim3(n), dim3(QJ_T), 0, st, a);
         PDL_HIP(hipGetLastError());
-        if (may_overflow) {      // some row has more lookups than the LDS table holds keys: did it leave the table?
-            uint64_t n_over = 0;
-            span_end();
-            {
-                PinRead rd(c);
-                const uint64_t *pc = rd.add<uint64_t>(ctl + Q_CTL_OVERFLOW_ROWS, 1);
-                rd.sync();
-                n_over = pc[0];
-            }
-            span_begin();
-            if (n_over) {
-                // tables for min(overflow rows, QH_WG) workgroups, laid out for THIS query's column count: tables cleaned for another
-                // count (another query) are cleared again — their layout is that of the other count
-                const uint32_t W = (uint32_t) std::min<uint64_t>(n_over, QH_WG);
-                if (!q.hbm_clean || q.hbm_cols != NC || q.hbm_slots < W) {
-                    q.hbm.alloc((size_t) W * NC * 16);
-                    hipLaunchKernelGGL(k_q_hbm_clear, dim3((uint32_t) std::min<uint64_t>(((uint64_t) W * NC + 255) / 256, 4096)), dim3(256), 0, st,
-                                       q.hbm.as<uint8_t>(), NC, W);
-                    q.hbm_cols = NC; q.hbm_slots = W; q.hbm_clean = true;
-                }
-                a.hbm = q.hbm.as<uint8_t>();
-                hipLaunchKernelGGL(k_q_join_hbm, dim3(W), dim3(QJ_T), 0, st, a);
-                PDL_HIP(hipGetLastError());
-            }
-        }
-        scan_and_apply(c, n, RowCntFlag{q.row_cnt.as<uint32_t>(), nullptr}, FinOffApply{q.fin_off.as<uint32_t>()}, reinterpret_cast<uint64_t *>(ctl + Q_CTL_EMITTED));
-        OrderArgs o{};
-        o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = q.fin_off.as<uint32_t>(); o.task_rows = q.rowid.as<uint32_t>();
-        o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
-        float *cf = q.cells.as<float>();
-        o.c_score = cf; o.c_perc = cf + cap; o.c_tr = cf + 2 * cap;
-        o.c_row = reinterpret_cast<int32_t *>(cf + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cf + 4 * cap);
-        o.n_rows = n; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = NC < (1u << 22) ? 1u : 0u;
-        o.wide_rows = reinterpret_cast<uint32_t *>(ctl + Q_CTL_WIDE_ROWS);
-        const uint32_t cus = (uint32_t) pdl_cus(c);
-        hipLaunchKernelGGL(k_order_rows_wave, dim3((n + 3) / 4), dim3(256), 0, st, o);
-        hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n, cus * 8)), dim3(ORDER_THREADS), 0, st, o);
+        // (tables laid out for THIS query's column count: those cleaned for another count are cleared again)
+        if (may_overflow) q_join_hbm_tier(c, spans, a.n_overflow, NC, [&](uint8_t *hbm, uint32_t W) {
+            a.hbm = hbm;
+            hipLaunchKernelGGL(k_q_join_hbm, dim3(W), dim3(QJ_T), 0, st, a);
+        });
+        q_order_rows(c, a, q.fin_off.as<uint32_t>(), q.rowid.as<uint32_t>(), q.cells.as<float>(), n, cap, NC, ctl + Q_CTL_EMITTED, ctl + Q_CTL_WIDE_ROWS);
         PDL_HIP(hipGetLastError());
-        span_end();
+        spans.end();
         uint64_t staged = 0;
         {
             PinRead rd(c);
@@ -635,19 +722,13 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         }
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
     } else {
-        span_end();
+        spans.end();
     }
 
-    // Q-copy: the block as library.cpp:542-603 marshals it
+    // Q-copy: straight into the block's arrays
     pdl_scores r{};
-    r.scoresCount = (uint32_t) Z; r.rows = n; r.genomes = G1; r.sequences = NC;
-    auto xm = [](size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) throw std::bad_alloc(); return p; };
     try {
-        r.scores = (float *) xm(Z * 4); r.percs = (float *) xm(Z * 4); r.tr_percs = (float *) xm(Z * 4);
-        r.row = (int32_t *) xm(Z * 4); r.column = (int32_t *) xm(Z * 4);
-        r.first_seq_genome = (int32_t *) xm(Z * 4); r.second_seq_genome = (int32_t *) xm(Z * 4);
-        r.max_genome_score = (float *) xm((size_t) n * G1 * 4); r.max_genome_score_col = (float *) xm((size_t) NC * 4);
-        r.scoresMaxMappings = (int32_t *) xm((size_t) NC * 4);
+        q_block_alloc(c, r, Z, n);
         if (Z) {
             const uint64_t cap = std::max<uint64_t>(bound, 1);
             const float *cf = q.cells.as<float>();
@@ -658,20 +739,11 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         PDL_HIP(hipMemcpyAsync(r.max_genome_score_col, q.CM.p, (size_t) NC * 4, hipMemcpyDeviceToHost, st));
         PDL_HIP(hipStreamSynchronize(st));
     } catch (...) { pdl_free_scores(&r); throw; }
-    for (uint64_t i = 0; i < Z; i++) {
-        r.first_seq_genome[i] = (int32_t) G;
-        const uint32_t col = (uint32_t) r.column[i];
-        r.second_seq_genome[i] = col < N ? (int32_t) c->h_genome_of[col] : (int32_t) G;
-    }
-    for (uint32_t i = 0; i < N; i++) r.scoresMaxMappings[i] = 0x7fffffff;
-    for (uint32_t g = 0; g < n; g++) r.scoresMaxMappings[N + g] = (int32_t) g;
+    q_block_ids(c, r);
     *out = r;
     if (info) {
         memset(info, 0, sizeof(*info));
         info->residues = Rq; info->kmer_occurrences = Mq; info->records = Uq; info->matched_records = matched; info->genome_cost = cost;
-        for (int i = 0; i < span; i++) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, q.ev[2 * i], q.ev[2 * i + 1]) == hipSuccess) info->device_ms += ms;
-        }
+        info->device_ms = spans.total_ms();
     }
 }

@@ -1,6 +1,7 @@
 // pdl_query_batch.h — K-query for a batch: q new genomes scored against the dictionary that is already in HBM, each on its own
-// (pdl_query_batch, include/pandelos_amd.h), included from pdl_join.hip behind pdl_query.h, whose group description (QDesc),
-// row walk, finalize and HBM table layout it reuses.  The single query's kernels and host path are not touched.
+// (pdl_query_batch, include/pandelos_amd.h), included from pdl_join.hip behind pdl_query.h.  The fold (q_fold_base,
+// q_fold_union), the group description (q_describe), the row program (q_row_lds, q_row_hbm) and the host's tail (join arguments,
+// HBM tier, order, block) are the single query's: the kernels here give them a query's segment and a row's own arguments.
 //
 // Contract: block j is what pdl_query_scores returns for genome j alone — computeScores(G) of base + genome j.  The queries
 // never see each other; the base context is only read.
@@ -92,14 +93,9 @@ __global__ __launch_bounds__(256) void k_qb_gather(const KeyT *keys, const uint3
 }
 
 template <class KeyT> struct QBView {
-    QView<KeyT> b;                  // the base half (bkeys, brecpos, bvals, post, U, M); its query half is not used
+    QBase<KeyT> b;
     const KeyT *srank; const uint2 *spost;
     const uint32_t *seg_off, *qid_sorted;
-    __device__ unsigned long long qrank(uint32_t j) const { return (unsigned long long) srank[j]; }
-    template <bool UPPER> __device__ uint32_t qbound(uint32_t lo, uint32_t hi, unsigned long long v) const {
-        while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); const unsigned long long r = qrank(m); if (UPPER ? r <= v : r < v) lo = m + 1; else hi = m; }
-        return lo;
-    }
 };
 
 // One thread per query: the base's fold (the same for all, computed by each) and the union's with this query's largest rank.
@@ -107,44 +103,17 @@ template <class KeyT>
 __global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyT> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
-    QFold f{};
-    f.p = Q_NONE; f.qL = Q_NONE;
-    const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1], Uq = s1 - s0;
-    qb_ctl(ctl, q)[QB_CTL_RECORDS] = Uq;
-    if (Uq == 0) { out[q] = f; return; }                          // no k-mer: no record reads the fold
-    const uint32_t U = v.b.U;
-    f.bmax = (unsigned long long) v.b.bkeys[v.b.M - 1];
-    bool lonely = U == 1;
-    bool has_r2 = false;
-    if (U == 1) f.p = 0;
-    else {
-        const unsigned long long rl = v.b.brank(U - 1), rl2 = v.b.brank(U - 2);
-        f.folded = (rl != f.bmax || rl2 != f.bmax) ? 1u : 0u;
-        if (f.folded) {
-            lonely = has_r2 = true;
-            f.r2 = rl != f.bmax ? rl : rl2;
-            f.gs = v.b.template bbound<false>(0, U, f.r2);
-            const uint32_t gl = v.b.bvals[v.b.M - 1];
-            uint32_t lo = f.gs, hi = U;
-            while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (v.b.post[m].x < gl) lo = m + 1; else hi = m; }
-            if (v.b.brank(lo) != f.bmax) lo++;
-            f.p = lo;
-        }
+    const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1];
+    qb_ctl(ctl, q)[QB_CTL_RECORDS] = s1 - s0;
+    if (s0 == s1) {                                               // no k-mer: no record reads the fold
+        QFold f{};
+        f.p = Q_NONE; f.qL = Q_NONE;
+        out[q] = f;
+        return;
     }
-    const unsigned long long qmax = v.qrank(s1 - 1);
-    const bool alone = Uq == 1 || v.qrank(s1 - 2) != qmax;
-    if (qmax > f.bmax) {
-        f.skip_p = f.folded;
-        if (alone) {
-            f.qL = s1 - 1;
-            const unsigned long long q2 = Uq >= 2 ? v.qrank(s1 - 2) : 0ull;
-            f.tgt = (Uq >= 2 && q2 > f.bmax) ? q2 : f.bmax;
-        }
-    } else if (qmax == f.bmax) {
-        f.skip_p = f.folded;
-    } else if (lonely && (!has_r2 || qmax > f.r2)) {
-        f.skip_p = f.folded; f.has_extra = 1; f.extra_target = qmax;
-    }
+    bool lonely, has_r2;
+    QFold f = q_fold_base(v.b, lonely, has_r2);
+    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.srank[j]; }, s0, s1);
     out[q] = f;
 }
 
@@ -161,23 +130,7 @@ __global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *f
     if (j < Ut && j < bound) {
         q = v.qid_sorted[j];
         const QFold f = folds[q];
-        const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1];
-        const unsigned long long r = v.qrank(j);
-        const unsigned long long eff = j == f.qL ? f.tgt : r;
-        QDesc d;
-        d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
-        if (f.folded) {
-            if (eff < f.r2) { d.blo = v.b.template bbound<false>(0, f.gs, eff); d.bhi = v.b.template bbound<true>(d.blo, f.gs, eff); }
-            else if (eff == f.r2) { d.blo = f.gs; d.bhi = v.b.U; if (f.skip_p) d.bskip = f.p; }
-            else if (eff == f.bmax) { d.blo = f.p; d.bhi = f.p + 1; }
-        } else {
-            d.blo = v.b.template bbound<false>(0, v.b.U, eff); d.bhi = v.b.template bbound<true>(d.blo, v.b.U, eff);
-        }
-        if (f.has_extra && eff == f.extra_target) d.bextra = f.p;
-        const uint32_t qn = f.qL != Q_NONE ? s1 - 1 : s1;         // searches among query records stay inside the record's own segment
-        d.qlo = v.template qbound<false>(s0, qn, eff); d.qhi = v.template qbound<true>(d.qlo, qn, eff);
-        if (f.qL != Q_NONE && eff == f.tgt) d.qextra = f.qL;
-        d.key = 2u * (d.qlo - s0) + (d.qhi > d.qlo ? 1u : 0u);
+        const QDesc d = q_describe(f, v.b, [&](uint32_t i) { return (unsigned long long) v.srank[i]; }, j, v.seg_off[q], v.seg_off[q + 1]);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
         const uint32_t gene = lay.gene_begin[q] + v.spost[j].x;
@@ -236,129 +189,22 @@ __device__ __forceinline__ QJoinArgs qb_row_args(const QBJoinArgs &b, uint32_t g
 }
 
 __global__ __launch_bounds__(QJ_T) void k_qb_join(QBJoinArgs b) {
-    __shared__ uint32_t s_key[QJ_HT], s_first[QJ_HT];
-    __shared__ unsigned long long s_acc[QJ_HT];
-    __shared__ QDesc s_d[QJ_T];
-    __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
-    __shared__ uint32_t s_nkeys, s_stop, s_ncell;
-    __shared__ unsigned long long s_cbase;
     uint32_t g;
     const QJoinArgs a = qb_row_args(b, blockIdx.x, g);
-    if (a.row_off[g] == a.row_off[g + 1]) {               // (uniform) no k-mer, no cell
-        if (threadIdx.x == 0) { a.row_cnt[g] = 0; a.row_base[g] = 0; }
-        return;
-    }
-    for (uint32_t i = threadIdx.x; i < QJ_HT; i += QJ_T) { s_key[i] = EMPTY_KEY; s_first[i] = 0xffffffffu; s_acc[i] = 0; }
-    if (threadIdx.x == 0) { s_nkeys = 0; s_stop = 0; s_ncell = 0; }
-    pdl_sync();
-    q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
-        uint32_t h = (col * 2654435761u) >> (32 - QJ_HT_BITS);
-        for (;;) {
-            const uint32_t k = *(volatile uint32_t *) &s_key[h];
-            if (k == col) break;
-            if (k == EMPTY_KEY) {
-                if (*(volatile uint32_t *) &s_nkeys >= QJ_LIMIT) return false;
-                const uint32_t old = atomicCAS(&s_key[h], EMPTY_KEY, col);
-                if (old == EMPTY_KEY) { atomicAdd(&s_nkeys, 1u); break; }
-                if (old == col) break;
-            }
-            h = (h + 1) & (QJ_HT - 1);
-        }
-        atomicAdd(&s_acc[h], packed);
-        atomicMin(&s_first[h], key);
-        return true;
-    });
-    if (s_stop) {                                         // (uniform: read after the walk's last barrier) more columns than the table holds
-        if (threadIdx.x == 0) {
-            const unsigned long long i = atomicAdd(a.n_overflow, 1ull);
-            a.overflow_rows[i] = blockIdx.x;              // (the chunk gene: k_qb_join_hbm cuts its query's slices out again)
-            a.row_cnt[g] = 0; a.row_base[g] = 0;
-        }
-        return;
-    }
-    float sc[QJ_SLOTS], pc[QJ_SLOTS], tc[QJ_SLOTS];
-    uint32_t at[QJ_SLOTS];
-#pragma unroll
-    for (uint32_t s = 0; s < QJ_SLOTS; s++) {
-        const uint32_t i = s * QJ_T + threadIdx.x;
-        at[s] = Q_NONE; sc[s] = 0.f; pc[s] = 0.f; tc[s] = 0.f;
-        const uint32_t col = s_key[i];
-        if (col != EMPTY_KEY) {
-            sc[s] = q_finalize(a, g, col, s_acc[i], pc[s], tc[s]);
-            if (sc[s] > 0.0f) at[s] = atomicAdd(&s_ncell, 1u);
-        }
-    }
-    pdl_sync();
-    if (threadIdx.x == 0) {
-        s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
-        a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
-    }
-    pdl_sync();
-#pragma unroll
-    for (uint32_t s = 0; s < QJ_SLOTS; s++) {
-        if (at[s] == Q_NONE) continue;
-        const uint32_t i = s * QJ_T + threadIdx.x;
-        const uint64_t o = s_cbase + at[s];
-        a.st_score[o] = sc[s]; a.st_perc[o] = pc[s]; a.st_tr[o] = tc[s];
-        a.st_col[o] = s_key[i]; a.st_first[o] = s_first[i];
-    }
+    q_row_lds(a, g, blockIdx.x);                                  // (overflow id = the chunk gene: k_qb_join_hbm cuts its query's slices out again)
 }
 
-// The rows k_qb_join handed on, on the single query's dense tables in HBM (k_q_join_hbm: all zero / all-ones first between
-// rows).  The tables are laid out for hbm_cols >= every query's columns, so rows of different queries share a workgroup's tables.
+// The rows k_qb_join handed on.  The tables are laid out for hbm_cols >= every query's columns, so rows of different queries
+// share a workgroup's tables.
 __global__ __launch_bounds__(QJ_T) void k_qb_join_hbm(QBJoinArgs b) {
-    __shared__ QDesc s_d[QJ_T];
-    __shared__ uint32_t s_cnt[QJ_T], s_pre[QJ_T + 1 + QJ_T / PDL_WAVE];
-    __shared__ uint32_t s_stop, s_ntouch, s_ncell, s_emit;
-    __shared__ unsigned long long s_cbase;
     const uint32_t n_cols = b.hbm_cols;
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(b.a.hbm + (size_t) blockIdx.x * n_cols * 16);
     uint32_t *first = reinterpret_cast<uint32_t *>(acc + n_cols);
-    uint32_t *touched = first + n_cols;
     const uint32_t n_over = (uint32_t) *b.a.n_overflow;
     for (uint32_t w = blockIdx.x; w < n_over; w += gridDim.x) {
         uint32_t g;
         const QJoinArgs a = qb_row_args(b, b.a.overflow_rows[w], g);
-        if (threadIdx.x == 0) { s_stop = 0; s_ntouch = 0; s_ncell = 0; s_emit = 0; }
-        pdl_sync();
-        q_walk_row(a, g, s_d, s_cnt, s_pre, &s_stop, [&](uint32_t col, unsigned long long packed, uint32_t key) -> bool {
-            const uint32_t old = atomicMin(&first[col], key);
-            if (old == 0xffffffffu) touched[atomicAdd(&s_ntouch, 1u)] = col;
-            atomicAdd(&acc[col], packed);
-            return true;
-        });
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pdl_sync();
-        const uint32_t nt = s_ntouch;
-        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // count (the maxima are taken here, once per cell)
-            const uint32_t col = ld_agent(&touched[i]);
-            float p, t;
-            if (q_finalize(a, g, col, ld_agent(&acc[col]), p, t) > 0.0f) atomicAdd(&s_ncell, 1u);
-        }
-        pdl_sync();
-        if (threadIdx.x == 0) {
-            s_cbase = atomicAdd(a.cell_cursor, (unsigned long long) s_ncell);
-            a.row_base[g] = (uint32_t) s_cbase; a.row_cnt[g] = s_ncell;
-        }
-        pdl_sync();
-        const float threshold = 1.0f / (2.0f * (float) a.k);
-        const uint32_t my_k = a.kseq_q[g];
-        for (uint32_t i = threadIdx.x; i < nt; i += QJ_T) {       // write, and leave the entries clean
-            const uint32_t col = ld_agent(&touched[i]);
-            const unsigned long long v = ld_agent(&acc[col]);
-            const uint32_t key = ld_agent(&first[col]);
-            float p, t;
-            const float score = finalize_cell(v, my_k, col < a.N ? a.kseq_b[col] : a.kseq_q[col - a.N], threshold, p, t);
-            if (score > 0.0f) {
-                const uint64_t o = s_cbase + atomicAdd(&s_emit, 1u);
-                a.st_score[o] = score; a.st_perc[o] = p; a.st_tr[o] = t; a.st_col[o] = col; a.st_first[o] = key;
-            }
-            acc[col] = 0ull; first[col] = 0xffffffffu;
-        }
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pdl_sync();
+        q_row_hbm(a, g, acc, first, first + n_cols);
     }
 }
 
@@ -384,7 +230,6 @@ static QBView<KeyT> qb_view(pdl_ctx *c) {
     QBView<KeyT> v;
     v.b.bkeys = c->keys_b.as<KeyT>(); v.b.brecpos = c->recpos.as<uint32_t>(); v.b.bvals = c->vals_b.as<uint32_t>(); v.b.post = c->post.as<uint2>();
     v.b.U = (uint32_t) c->U; v.b.M = c->M;
-    v.b.qkeys = nullptr; v.b.qrecpos = nullptr; v.b.qpost = nullptr;
     v.srank = w.srank.as<KeyT>(); v.spost = w.spost.as<uint2>(); v.seg_off = w.seg_off.as<uint32_t>();
     return v;
 }
@@ -394,8 +239,7 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
                          uint32_t hbm_cols, pdl_scores *out, pdl_query_info *info, float *device_ms) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
-    auto &sq = c->qb;                                             // the HBM tables and their bookkeeping are the single query's
-    const uint32_t N = c->N, G = c->G, G1 = G + 1, k = c->rp.k;
+    const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
     const uint32_t nq = qe - qa, ga = qs[qa].g0, NT = qs[qe - 1].g0 + qs[qe - 1].n - ga;
     const uint64_t r0 = offsets[ga], Rq = offsets[ga + NT] - r0;
     std::vector<uint64_t> h_off(NT + 1), h_koff(NT + 1), h_rbeg(nq + 1);
@@ -416,11 +260,8 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         }
     }
     h_off[NT] = Rq; h_koff[NT] = Mq; h_gbeg[nq] = NT; h_rbeg[nq] = Rq;
-    for (int i = 0; i < 6; i++) if (!w.ev[i]) PDL_HIP(hipEventCreate(&w.ev[i]));
-    int span = 0;
-    auto span_begin = [&]() { PDL_HIP(hipEventRecord(w.ev[2 * span], st)); };
-    auto span_end = [&]() { PDL_HIP(hipEventRecord(w.ev[2 * span + 1], st)); span++; };
-    span_begin();
+    QSpans spans(w.ev, st);
+    spans.begin();
 
     // B-alpha (and the chunk on its way to the device)
     const size_t ctl_words = QBG_WORDS + (size_t) nq * QB_CTL_WORDS;
@@ -491,7 +332,7 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         rec_sorted = ix_out;
     }
     std::vector<uint64_t> h_ctl(ctl_words);
-    span_end();
+    spans.end();
     {
         PinRead rd(c);
         const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
@@ -505,7 +346,7 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
             snprintf(who, sizeof(who), "query %u:", qa + q);
             pdl_fail_absent_byte(hq(q, QB_CTL_BAD_BYTE), who);
         }
-    span_begin();
+    spans.begin();
     const uint64_t Ut = h_ctl[QBG_RECORDS];
     uint64_t bound = 0, may_overflow = 0;
     for (uint32_t q = 0; q < nq; q++) { bound += hq(q, QB_CTL_BOUND); may_overflow += hq(q, QB_CTL_MAY_OVERFLOW); }
@@ -524,59 +365,22 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         QBJoinArgs b{};
         QJoinArgs &a = b.a;
         b.lay = lay; b.hbm_cols = hbm_cols;
-        a.post = c->post.as<uint2>(); a.qpost = w.spost.as<uint2>(); a.desc = w.desc.as<QDesc>();
-        a.rec_sorted = rec_sorted; a.row_off = w.row_off.as<uint32_t>();
-        a.kseq_b = c->kseq_len.as<uint32_t>(); a.kseq_q = w.kseq.as<uint32_t>(); a.genome_b = c->d_gen;
-        a.N = N; a.n = 0; a.G1 = G1; a.k = k;
-        a.MS = w.MS.as<float>(); a.CM = w.CM.as<float>();
+        a = q_join_args(c, w.st.as<float>(), cap);          // (a.n stays 0: qb_row_args sets it per row)
+        a.qpost = w.spost.as<uint2>(); a.desc = w.desc.as<QDesc>(); a.rec_sorted = rec_sorted; a.row_off = w.row_off.as<uint32_t>();
+        a.kseq_q = w.kseq.as<uint32_t>(); a.MS = w.MS.as<float>(); a.CM = w.CM.as<float>();
         a.row_base = w.row_base.as<uint32_t>(); a.row_cnt = w.row_cnt.as<uint32_t>();
-        float *stf = w.st.as<float>();
-        a.st_score = stf; a.st_perc = stf + cap; a.st_tr = stf + 2 * cap;
-        a.st_col = reinterpret_cast<uint32_t *>(stf + 3 * cap); a.st_first = reinterpret_cast<uint32_t *>(stf + 4 * cap);
         a.cell_cursor = ctl + QBG_CELL_CURSOR; a.overflow_rows = w.overflow.as<uint32_t>(); a.n_overflow = ctl + QBG_OVERFLOW_ROWS;
         hipLaunchKernelGGL(k_qb_join, dim3(NT), dim3(QJ_T), 0, st, b);
         PDL_HIP(hipGetLastError());
-        if (may_overflow) {      // some row has more lookups than the LDS table holds keys: did it leave the table?
-            uint64_t n_over = 0;
-            span_end();
-            {
-                PinRead rd(c);
-                const uint64_t *pc = rd.add<uint64_t>(ctl + QBG_OVERFLOW_ROWS, 1);
-                rd.sync();
-                n_over = pc[0];
-            }
-            span_begin();
-            if (n_over) {
-                // the single query's tables (pdl_query.h), laid out for the batch's widest union: clean tables of exactly that
-                // layout are taken as they are, others are cleared — and the bookkeeping says what a later query will find
-                const uint32_t W = (uint32_t) std::min<uint64_t>(n_over, QH_WG);
-                if (!sq.hbm_clean || sq.hbm_cols != hbm_cols || sq.hbm_slots < W) {
-                    sq.hbm_clean = false;
-                    sq.hbm.alloc((size_t) W * hbm_cols * 16);
-                    hipLaunchKernelGGL(k_q_hbm_clear, dim3((uint32_t) std::min<uint64_t>(((uint64_t) W * hbm_cols + 255) / 256, 4096)), dim3(256), 0, st,
-                                       sq.hbm.as<uint8_t>(), hbm_cols, W);
-                    sq.hbm_cols = hbm_cols; sq.hbm_slots = W; sq.hbm_clean = true;
-                }
-                a.hbm = sq.hbm.as<uint8_t>();
-                hipLaunchKernelGGL(k_qb_join_hbm, dim3(W), dim3(QJ_T), 0, st, b);
-                PDL_HIP(hipGetLastError());
-            }
-        }
-        scan_and_apply(c, NT, RowCntFlag{w.row_cnt.as<uint32_t>(), nullptr}, FinOffApply{w.fin_off.as<uint32_t>()}, reinterpret_cast<uint64_t *>(ctl + QBG_EMITTED));
-        OrderArgs o{};
-        o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = w.fin_off.as<uint32_t>(); o.task_rows = w.rowid.as<uint32_t>();
-        o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
-        float *cf = w.cells.as<float>();
-        o.c_score = cf; o.c_perc = cf + cap; o.c_tr = cf + 2 * cap;
-        o.c_row = reinterpret_cast<int32_t *>(cf + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cf + 4 * cap);
-        o.n_rows = NT; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = (uint64_t) N + n_max < (1u << 22) ? 1u : 0u;
-        o.wide_rows = reinterpret_cast<uint32_t *>(ctl + QBG_WIDE_ROWS);
-        const uint32_t cus = (uint32_t) pdl_cus(c);
-        hipLaunchKernelGGL(k_order_rows_wave, dim3((NT + 3) / 4), dim3(256), 0, st, o);
-        hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(NT, cus * 8)), dim3(ORDER_THREADS), 0, st, o);
+        // (tables laid out for the batch's widest union, which every query's columns fit)
+        if (may_overflow) q_join_hbm_tier(c, spans, a.n_overflow, hbm_cols, [&](uint8_t *hbm, uint32_t W) {
+            a.hbm = hbm;
+            hipLaunchKernelGGL(k_qb_join_hbm, dim3(W), dim3(QJ_T), 0, st, b);
+        });
+        q_order_rows(c, a, w.fin_off.as<uint32_t>(), w.rowid.as<uint32_t>(), w.cells.as<float>(), NT, cap, (uint64_t) N + n_max, ctl + QBG_EMITTED, ctl + QBG_WIDE_ROWS);
         hipLaunchKernelGGL(k_qb_counts, dim3((nq + 63) / 64), dim3(64), 0, st, (const uint32_t *) w.fin_off.as<uint32_t>(), lay, ctl);
         PDL_HIP(hipGetLastError());
-        span_end();
+        spans.end();
         {
             PinRead rd(c);                                       // the per-query counts (and the cursors beside them): one read
             const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
@@ -587,7 +391,7 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         Z = h_ctl[QBG_EMITTED];
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query batch join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
     } else {
-        span_end();
+        spans.end();
     }
 
     // B-copy: the chunk's cells and maxima come over in one piece each (7 copies per chunk, not per query) into pinned host
@@ -607,13 +411,8 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_ms), w.MS.p, ms_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_cm), w.CM.p, cm_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipStreamSynchronize(st));
-    float ms_total = 0.f;
-    for (int i = 0; i < span; i++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, w.ev[2 * i], w.ev[2 * i + 1]) == hipSuccess) ms_total += ms;
-    }
+    const float ms_total = spans.total_ms();
     *device_ms += ms_total;
-    auto xm = [](size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) throw std::bad_alloc(); return p; };
     uint64_t z0 = 0;
     for (uint32_t q = 0; q < nq; q++) {
         const QBQuery &Q = qs[qa + q];
@@ -621,23 +420,12 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         const uint32_t n = Q.n, NC = N + n;
         if (z0 + Zq > Z) PDL_FAIL(PDL_ERR_DEVICE, "query batch: the queries' cells (%llu) pass the emitted total %llu", (unsigned long long) (z0 + Zq), (unsigned long long) Z);
         pdl_scores &r = out[qa + q];                             // (filled in place: a throw leaves what is allocated to the caller's pdl_free_scores)
-        r.scoresCount = (uint32_t) Zq; r.rows = n; r.genomes = G1; r.sequences = NC;
-        r.scores = (float *) xm(Zq * 4); r.percs = (float *) xm(Zq * 4); r.tr_percs = (float *) xm(Zq * 4);
-        r.row = (int32_t *) xm(Zq * 4); r.column = (int32_t *) xm(Zq * 4);
-        r.first_seq_genome = (int32_t *) xm(Zq * 4); r.second_seq_genome = (int32_t *) xm(Zq * 4);
-        r.max_genome_score = (float *) xm((size_t) n * G1 * 4); r.max_genome_score_col = (float *) xm((size_t) NC * 4);
-        r.scoresMaxMappings = (int32_t *) xm((size_t) NC * 4);
+        q_block_alloc(c, r, Zq, n);
         void *dst[5] = {r.scores, r.percs, r.tr_percs, r.row, r.column};
         for (int i = 0; i < 5; i++) if (Zq) memcpy(dst[i], h_cells + (size_t) i * Z + z0, Zq * 4);
         memcpy(r.max_genome_score, h_ms + (size_t) h_gbeg[q] * G1, (size_t) n * G1 * 4);
         memcpy(r.max_genome_score_col, h_cm + (size_t) q * N + h_gbeg[q], (size_t) NC * 4);
-        for (uint64_t i = 0; i < Zq; i++) {
-            r.first_seq_genome[i] = (int32_t) G;
-            const uint32_t col = (uint32_t) r.column[i];
-            r.second_seq_genome[i] = col < N ? (int32_t) c->h_genome_of[col] : (int32_t) G;
-        }
-        for (uint32_t i = 0; i < N; i++) r.scoresMaxMappings[i] = 0x7fffffff;
-        for (uint32_t g = 0; g < n; g++) r.scoresMaxMappings[N + g] = (int32_t) g;
+        q_block_ids(c, r);
         z0 += Zq;
         if (info) {
             pdl_query_info &fi = info[qa + q];
