@@ -7,8 +7,8 @@
 //   K-rank    k_rank / k_rank_hash   per-gene k-mer ranks                    library.cpp:75-86,134-150
 //   K-sort    pdl_sort_pairs      stable LSD radix sort by rank              library.cpp:172-187,270-278
 //   K-rle     RecHead/RecScatter scan (records built in the apply)   dedup -> (rank,gene,count)   library.cpp:280-287
-//   K-groups  k_fold_last_record, k_group_waves (group extents from head bits, per tile)  library.cpp:297-335
-//   K-ranges  k_group_waves (range tuples), sort by gene, k_gather_ranges (+ per-gene cost), k_seq_offsets   library.cpp:312-327
+//   K-groups  k_fold_last_record, then per tile from the head bits: costs / count / write (pdl_groups.h)   library.cpp:297-335
+//   K-ranges  k_group_write or k_range_scatter (ranges), sort by gene, k_gather_ranges (+ per-gene cost), k_seq_offsets   library.cpp:312-327
 //   K-cost    k_genome_cost       per-genome and total lookups               library.cpp:337-350,535-538
 //
 // HBM layout after this stage (what the join reads):
@@ -21,6 +21,7 @@
 #include "pdl_sort.h"
 #include "pdl_append.h"
 #include "pdl_remove.h"
+#include "pdl_groups.h"
 
 #include <algorithm>
 #include <cstring>
@@ -353,663 +354,6 @@ template <class KeyT> struct SelApply {
     __device__ void store(uint64_t, uint32_t f, uint32_t prefix, const Loaded &v) const { if (f) { keys_out[prefix] = v.key; vals_out[prefix] = v.val; } }
 };
 
-// ------------------------------------------------------------------------------------------------
-// K-groups + K-ranges, fused (library.cpp:289-335).  The dictionary arrives as postings {gene, count} in (rank, gene)
-// order with "opens a rank-group" in bit 31 of the count (set by K-rle; it is also the form the runs of a multi-GPU
-// build travel in).  A group is the records from one head to the next; nothing is materialised about groups: every
-// tile of 1024 records (one wave) rebuilds the extents it needs from the head bits (a 64-bit ballot per round, prev/next
-// head by bit scans), looks beyond its borders only for the groups that cross them, and emits — for the records that
-// get a posting range — the 16-byte tuple {first posting, postings, own count, group size} and the gene as sort key:
-//
-//   k_fold_last_record   the reference's scan closes the current group at the LAST record whatever its rank
-//                        (library.cpp:300-306): a last record that opens a group of its own is folded into the preceding
-//                        group, moved to its gene-order place there (:312-315) and the head bits are put right, so that
-//                        from here on the bits alone say what the reference's groups are
-//   k_group_waves<COUNT> ranges per tile (+ first/last head of every tile; + counters U', shared groups; + per-genome
-//                        lookups; + per-gene costs in complexity-only mode)
-//   (scan of the tile counts)
-//   k_group_waves<WRITE> tuples and keys at tile offset + position inside the tile (record order), the group size of a
-//                        group's last member added to its gene's cost (it has no range of its own), head bits removed
-//
-// Two passes over the postings replace the group scan (gid/goff), the shared-record compaction and the counter pass
-// of the first version, i.e. about six passes over record-sized arrays.  The WRITE pass removes the head bits of its
-// own tile only and asks the per-tile head positions of the COUNT pass about its neighbours, so no tile ever reads
-// a bit another one may already have removed.
-// ------------------------------------------------------------------------------------------------
-constexpr uint32_t HEAD_BIT = 0x80000000u;
-constexpr uint32_t GT_NONE = 0xffffffffu;
-constexpr uint32_t COST_LDS_GENOMES = 4096;
-
-// last head at or before pos (record 0 always is one); one wave, 64 records per step
-__device__ __forceinline__ uint32_t find_head_back(const uint2 *post, uint32_t pos, uint32_t lane) {
-    for (;;) {
-        const uint32_t base = pos + 1 >= PDL_WAVE ? pos + 1 - PDL_WAVE : 0;
-        const uint32_t idx = base + lane;
-        const bool f = idx <= pos && ((post[idx <= pos ? idx : pos].y >> 31) || idx == 0);
-        const unsigned long long m = __ballot(f);
-        if (m) return base + 63u - (uint32_t) __clzll((long long) m);
-        pos = base - 1;                                   // (base > 0 here: index 0 always answers)
-    }
-}
-// first head at or after pos, n when there is none
-__device__ __forceinline__ uint32_t find_head_fwd(const uint2 *post, uint32_t pos, uint32_t n, uint32_t lane) {
-    for (uint32_t base = pos; base < n; base += PDL_WAVE) {
-        const uint32_t idx = base + lane;
-        const bool f = idx < n && (post[idx < n ? idx : n - 1].y >> 31);
-        const unsigned long long m = __ballot(f);
-        if (m) return base + (uint32_t) __ffsll((long long) m) - 1u;
-    }
-    return n;
-}
-
-// One workgroup.  recpos (position of each record's first occurrence in the sorted stream, for pdl_get_dictionary) moves
-// along when present.
-__global__ __launch_bounds__(1024) void k_fold_last_record(uint2 *__restrict__ post, uint32_t *__restrict__ recpos, const uint64_t *d_u) {
-    __shared__ uint32_t s_gs, s_p;
-    const uint32_t u_count = (uint32_t) *d_u;
-    if (u_count < 2) return;
-    const uint32_t lastp = u_count - 1;
-    uint2 last = post[lastp];
-    if (!(last.y >> 31)) return;                         // (uniform) the last record belongs to its group anyway, in gene order
-    last.y &= ~HEAD_BIT;                                 // it never opens a group (library.cpp:300-306)
-    const uint32_t last_rp = recpos ? recpos[lastp] : 0u;
-    if (threadIdx.x < PDL_WAVE) {
-        const uint32_t gs = find_head_back(post, lastp - 1, threadIdx.x);       // the group it joins
-        if (threadIdx.x == 0) {
-            uint32_t lo = gs, hi = lastp;                // first index in [gs, lastp) whose gene is above the last record's
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (post[mid].x <= last.x) lo = mid + 1; else hi = mid;
-            }
-            s_gs = gs; s_p = lo;
-        }
-    }
-    pdl_sync();
-    const uint32_t p = s_p, gs = s_gs;
-    if (p == lastp) { if (threadIdx.x == 0) post[lastp] = last; return; }       // already in place (uniform)
-    for (uint32_t hi = lastp; hi > p; hi = hi > 1024 ? hi - 1024 : 0) {
-        const bool live = hi >= 1 + threadIdx.x && hi - 1 - threadIdx.x >= p;
-        const uint32_t i = hi - 1 - threadIdx.x;
-        uint2 v = make_uint2(0, 0);
-        uint32_t rp = 0;
-        if (live) { v = post[i]; if (recpos) rp = recpos[i]; }
-        pdl_sync();
-        if (live) { post[i + 1] = v; if (recpos) recpos[i + 1] = rp; }
-        pdl_sync();
-        if (hi <= 1024) break;
-    }
-    if (threadIdx.x == 0) {
-        if (p == gs) { last.y |= HEAD_BIT; post[gs + 1].y &= ~HEAD_BIT; }       // the moved record is the group's smallest gene: it is the head now
-        post[p] = last;
-        if (recpos) recpos[p] = last_rp;
-    }
-}
-
-struct GroupTileArgs {
-    uint2 *post;
-    uint64_t n_bound; const uint64_t *d_n;      // record count: on the device (at most n_bound) or n_bound itself
-    const uint8_t *in_shard;                    // MODE 0, 2: the genes that get range lists, one byte per gene ...
-    const uint2 *own_iv; uint32_t n_own_iv;     // ... or (n_own_iv > 0) as sorted, disjoint gene-id intervals [x, y): searched in LDS,
-                                                //     where a per-record byte gather would cost 64 addresses per instruction
-    uint32_t *tile_sums;                        // [tiles] COUNT: ranges of the tile; k_tile_prefix: of the tiles before it in its block of 64
-    uint32_t *chunk_sums;                       // [blocks of 64 tiles] ranges of a block; exclusive-scanned between the passes
-    uint32_t n_blocks;
-    uint32_t *th_first, *th_last;               // [tiles] first / last head of a tile (GT_NONE: none), COUNT -> WRITE
-    uint32_t *key2; uint4 *tuples;              // WRITE: sort key (gene) and the 16-byte range tuple, or ...
-    unsigned long long *pay8;                   // ... (non-null) the packed 8-byte range {first posting | (postings + (min(own count, 1023) << 22)) << 32},
-                                                //     carried through the gene sort as its payload: no gather afterwards
-    unsigned long long *head_bits;              // WRITE: [tiles * 16] the head bits it removes from the postings, kept for the lazy cost pass
-    uint32_t pos_base;                          // WRITE, packed ranges: added to every first posting (a run of a multi-GPU build: its place in the gathered dictionary)
-    unsigned long long *cost;                   // per-gene total_visited (library.cpp:327): last members (WRITE), all shared records (COUNT, RECORD_COSTS)
-    unsigned long long *counters;               // COUNT: [0] += records in groups >= 2, [1] += such groups, [3] += records whose k-mer repeats inside its gene (range modes);  WRITE: [2] += lookups of the
-                                                //        records that belong to this context (library.cpp:327 summed: "Total cost")
-    const uint32_t *genome_of; uint32_t n_genomes;
-    unsigned long long *g_full, *g_upper;       // COUNT, GENOMES: per genome, lookups as the reference counts them / above the diagonal
-};
-
-// One WAVE per tile of GW_TILE consecutive records, no LDS and no barrier on the data path: the head bits of a round of
-// 64 records are one ballot (a scalar register pair); previous / next head of a record come from bit scans of its
-// round's mask, from scalar scans over the rounds, and — for the groups that cross the tile's borders — from a look at
-// the records around the tile (COUNT) or at the per-tile head positions the COUNT pass left (WRITE).
-// The ranges of a tile go to (scanned total of the 64-tile blocks before) + (tiles before it in its block) + rank
-// inside the tile, i.e. in record order.
-// MODE 0: whole groups for the genes of a shard | 1: the postings above the record, every gene | 2: those, for the genes
-// of a shard | 3: no ranges (counters / costs only).  PASS 0 = COUNT, 1 = WRITE.
-constexpr int GW_ROUNDS = 16, GW_TILE = GW_ROUNDS * PDL_WAVE, GW_THREADS = 256, GW_WAVES = GW_THREADS / PDL_WAVE;
-constexpr uint32_t GW_MAX_IV = 2048;                     // gene-id intervals of a shard held in LDS (16 KiB); more: the byte table
-template <int PASS, int MODE, bool GENOMES, bool RECORD_COSTS>
-__global__ __launch_bounds__(GW_THREADS) void k_group_waves(GroupTileArgs a) {
-    __shared__ uint32_t s_red[2];
-    extern __shared__ unsigned long long s_dyn[];        // GENOMES with <= COST_LDS_GENOMES genomes: full[G] | upper[G];  shard modes: intervals
-    unsigned long long *s_full = s_dyn, *s_upper = s_dyn + a.n_genomes;
-    uint2 *s_iv = reinterpret_cast<uint2 *>(s_dyn);      // (GENOMES and the shard modes never come together)
-    const uint32_t n_iv = (MODE == 0 || MODE == 2) ? a.n_own_iv : 0u;
-    if constexpr (MODE == 0 || MODE == 2) { for (uint32_t i = threadIdx.x; i < n_iv; i += GW_THREADS) s_iv[i] = a.own_iv[i]; }
-    const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1);
-    const uint32_t gw = blockIdx.x * GW_WAVES + tid / PDL_WAVE;                  // this wave's index = its chunk of tiles
-    const uint32_t n = (uint32_t) scan_count(a.n_bound, a.d_n);
-    const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
-    const bool lds_table = GENOMES && a.n_genomes <= COST_LDS_GENOMES;
-    if constexpr (GENOMES) { if (lds_table) { for (uint32_t i = tid; i < 2 * a.n_genomes; i += GW_THREADS) s_dyn[i] = 0; } }
-    if (tid < 2) s_red[tid] = 0;
-    pdl_sync();
-    const unsigned long long lt_mask = (1ull << lane) - 1ull, le_mask = (2ull << lane) - 1ull;
-    uint32_t n_rec = 0, n_grp = 0;
-    unsigned long long own_lookups = 0;
-    // Tiles are dealt round-robin over the waves: the waves in flight read neighbouring tiles (a wave that owned a run of
-    // consecutive tiles kept every wave on its own far-apart addresses, and the pass at a quarter of the streaming rate).
-    for (uint32_t tile = gw; tile < tiles; tile += gridDim.x * GW_WAVES) {
-        const uint32_t t0 = tile * GW_TILE, t1 = min(t0 + (uint32_t) GW_TILE, n);
-        uint2 po[GW_ROUNDS];
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) {            // all loads first, branch-free
-            const uint32_t u = t0 + j * PDL_WAVE + lane;
-            po[j] = a.post[u < n ? u : n - 1];
-        }
-        // COUNT: the 64 records behind the tile say where the group that runs out of it ends.  WRITE: other waves may have
-        // removed their tiles' head bits already, so the COUNT pass's per-tile heads answer: the nearest tile before / after
-        // with a head (64 tiles per look, issued with the tile's own loads).
-        constexpr bool may_peek = PASS == 0;
-        const uint32_t pu = t1 + lane;
-        const uint32_t peek = (may_peek && pu < n) ? a.post[pu].y >> 31 : 0u;
-        uint32_t hb = GT_NONE, ha = GT_NONE;
-        if constexpr (PASS == 1) {
-            hb = lane < tile ? a.th_last[tile - 1 - lane] : GT_NONE;
-            ha = tile + 1 + lane < tiles ? a.th_first[tile + 1 + lane] : GT_NONE;
-        }
-        // (shard modes) "this gene gets ranges" for all sixteen records at once: behind the ballots below each lookup would
-        // wait for the one before it
-        uint32_t ins = 0xffffffffu;
-        if constexpr (MODE == 0 || MODE == 2) {
-            ins = 0;
-            if (n_iv) {                                  // (uniform) sixteen independent binary searches over the interval starts, in LDS
-                uint32_t lo_i[GW_ROUNDS], hi_i[GW_ROUNDS];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) { lo_i[j] = 0; hi_i[j] = n_iv; }          // last interval with start <= gene is lo_i - 1
-                for (uint32_t span = n_iv; span > 0; span >>= 1) {
-#pragma unroll
-                    for (int j = 0; j < GW_ROUNDS; j++) {
-                        const uint32_t mid = (lo_i[j] + hi_i[j]) >> 1;
-                        const bool go = lo_i[j] < hi_i[j] && s_iv[mid < n_iv ? mid : n_iv - 1].x <= po[j].x;
-                        if (lo_i[j] < hi_i[j]) { if (go) lo_i[j] = mid + 1; else hi_i[j] = mid; }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) ins |= (uint32_t) (lo_i[j] > 0 && po[j].x < s_iv[lo_i[j] > 0 ? lo_i[j] - 1 : 0].y) << j;
-            } else {
-                uint8_t inb[GW_ROUNDS];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) inb[j] = a.in_shard[po[j].x];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) ins |= (uint32_t) (inb[j] != 0) << j;
-            }
-        }
-        unsigned long long m[GW_ROUNDS];
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) m[j] = __ballot(t0 + j * PDL_WAVE + lane < n && (po[j].y >> 31));
-        // head of the group that runs into the tile
-        uint32_t before = t0;
-        if (!(m[0] & 1ull)) {                            // (uniform) the tile starts inside a group (t0 > 0: record 0 is a head)
-            if constexpr (PASS == 0) before = find_head_back(a.post, t0 - 1, lane);
-            else {
-                unsigned long long hm = __ballot(hb != GT_NONE);
-                if (hm) before = (uint32_t) __shfl((int) hb, __ffsll((long long) hm) - 1, PDL_WAVE);        // lane 0 = the tile just before
-                else {
-                    before = 0;
-                    for (uint32_t hi = tile >= PDL_WAVE ? tile - PDL_WAVE : 0; hi > 0;) {                    // further back, 64 tiles per step
-                        const uint32_t base = hi >= PDL_WAVE ? hi - PDL_WAVE : 0, idx = base + lane;
-                        const uint32_t v = idx < hi ? a.th_last[idx] : GT_NONE;
-                        hm = __ballot(v != GT_NONE);
-                        if (hm) { before = (uint32_t) __shfl((int) v, 63 - __clzll((long long) hm), PDL_WAVE); break; }
-                        hi = base;
-                    }
-                }
-            }
-        }
-        // end of the group that runs out of the tile
-        uint32_t after;
-        if constexpr (PASS == 0) {
-            const unsigned long long pm = __ballot(peek != 0);
-            if (pm) after = t1 + (uint32_t) __ffsll((long long) pm) - 1u;
-            else if (t1 + PDL_WAVE >= n) after = n;
-            else after = find_head_fwd(a.post, t1 + PDL_WAVE, n, lane);
-        } else {
-            unsigned long long hm = __ballot(ha != GT_NONE);
-            if (hm) after = (uint32_t) __shfl((int) ha, __ffsll((long long) hm) - 1, PDL_WAVE);
-            else {
-                after = n;
-                for (uint32_t lo = tile + 1 + PDL_WAVE; lo < tiles; lo += PDL_WAVE) {
-                    const uint32_t idx = lo + lane;
-                    const uint32_t v = idx < tiles ? a.th_first[idx] : GT_NONE;
-                    hm = __ballot(v != GT_NONE);
-                    if (hm) { after = (uint32_t) __shfl((int) v, __ffsll((long long) hm) - 1, PDL_WAVE); break; }
-                }
-            }
-        }
-        before = (uint32_t) __builtin_amdgcn_readfirstlane((int) before);        // (uniform by construction: keep them in scalar registers)
-        after = (uint32_t) __builtin_amdgcn_readfirstlane((int) after);
-        // first head in the rounds after round j (scalar scan from the back)
-        uint32_t nextr[GW_ROUNDS];
-        uint32_t nx = after, first_in_tile = GT_NONE;
-#pragma unroll
-        for (int j = GW_ROUNDS - 1; j >= 0; j--) {
-            nextr[j] = nx;
-            if (m[j]) { nx = t0 + j * PDL_WAVE + (uint32_t) __ffsll((long long) m[j]) - 1u; first_in_tile = nx; }
-        }
-        uint32_t pr = before, cnt_tile = 0;              // (uniform) last head before the current round; ranges so far in the tile
-        const uint32_t tile_prefix = PASS == 1 ? a.chunk_sums[tile / PDL_WAVE] + a.tile_sums[tile] : 0u;
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) {
-            const uint32_t u = t0 + j * PDL_WAVE + lane;
-            const unsigned long long at_or_below = m[j] & le_mask, above = m[j] & ~le_mask;
-            const uint32_t gs = at_or_below ? t0 + j * PDL_WAVE + 63u - (uint32_t) __clzll((long long) at_or_below) : pr;
-            const uint32_t ge = above ? t0 + j * PDL_WAVE + (uint32_t) __ffsll((long long) above) - 1u : nextr[j];
-            const bool live = u < n;
-            const bool shared = live && ge - gs >= 2;
-            bool r = shared;
-            if constexpr (MODE == 1 || MODE == 2) r = r && u + 1 < ge;           // the last member of a group has nothing above it
-            if constexpr (MODE == 0 || MODE == 2) r = r && ((ins >> j) & 1u);
-            if constexpr (MODE == 3) r = false;
-            const unsigned long long rb = __ballot(r);
-            if constexpr (PASS == 0) {
-                n_rec += shared; n_grp += shared && u == gs;
-                if constexpr (RECORD_COSTS) { if (shared) atomicAdd(&a.cost[po[j].x], (unsigned long long) (ge - gs)); }
-                if constexpr (GENOMES) {
-                    if (shared) {
-                        const uint32_t gen = a.genome_of[po[j].x];
-                        const unsigned long long full = ge - gs, up = ge - u - 1;
-                        if (lds_table) { atomicAdd(&s_full[gen], full); if (up) atomicAdd(&s_upper[gen], up); }
-                        else { atomicAdd(&a.g_full[gen], full); if (up) atomicAdd(&a.g_upper[gen], up); }
-                    }
-                }
-            } else if (live) {
-                const uint32_t cnt = po[j].y & ~HEAD_BIT;
-                if (po[j].y >> 31) a.post[u].y = cnt;                              // the bit has done its job
-                const bool mine = MODE == 1 || ((ins >> j) & 1u);
-                if (shared && mine) own_lookups += ge - gs;
-                if (r) {
-                    const uint32_t at = tile_prefix + cnt_tile + (uint32_t) __popcll(rb & lt_mask);
-                    const uint32_t start = MODE == 0 ? gs : u + 1;
-                    a.key2[at] = po[j].x;
-                    if (a.pay8) a.pay8[at] = (unsigned long long) (start + a.pos_base) | ((unsigned long long) ((ge - start) | (min(cnt, 1023u) << 22)) << 32);
-                    else a.tuples[at] = make_uint4(start, ge - start, cnt, ge - gs);     // {first posting, postings, own count, group size}
-                } else if (MODE == 1 || MODE == 2) {
-                    if (!a.pay8 && ge - gs >= 2 && u + 1 == ge && mine)                  // (packed ranges: per-gene costs are made on demand)
-                        atomicAdd(&a.cost[po[j].x], (unsigned long long) (ge - gs));
-                }
-            }
-            if (PASS == 1 && a.head_bits && lane == 0) a.head_bits[(size_t) tile * GW_ROUNDS + j] = m[j];
-            cnt_tile += (uint32_t) __popcll(rb);
-            if (m[j]) pr = t0 + j * PDL_WAVE + 63u - (uint32_t) __clzll((long long) m[j]);
-        }
-        if constexpr (PASS == 0) {
-            if (lane == 0) { a.tile_sums[tile] = cnt_tile; a.th_first[tile] = first_in_tile; a.th_last[tile] = first_in_tile != GT_NONE ? pr : GT_NONE; }
-        }
-    }
-    if constexpr (PASS == 0) {
-#pragma unroll
-        for (int d = PDL_WAVE / 2; d > 0; d >>= 1) { n_rec += __shfl_xor(n_rec, d, PDL_WAVE); n_grp += __shfl_xor(n_grp, d, PDL_WAVE); }
-        if (lane == 0) { atomicAdd(&s_red[0], n_rec); atomicAdd(&s_red[1], n_grp); }
-        pdl_sync();
-        if (tid < 2 && s_red[tid]) atomicAdd(&a.counters[tid], (unsigned long long) s_red[tid]);
-        if constexpr (GENOMES) {
-            if (lds_table) for (uint32_t i = tid; i < a.n_genomes; i += GW_THREADS) {
-                if (s_full[i]) atomicAdd(&a.g_full[i], s_full[i]);
-                if (s_upper[i]) atomicAdd(&a.g_upper[i], s_upper[i]);
-            }
-        }
-    } else {
-        __shared__ unsigned long long s_own;
-        if (tid == 0) s_own = 0;
-        pdl_sync();
-#pragma unroll
-        for (int d = PDL_WAVE / 2; d > 0; d >>= 1) own_lookups += __shfl_xor(own_lookups, d, PDL_WAVE);
-        if (lane == 0 && own_lookups) atomicAdd(&s_own, own_lookups);
-        pdl_sync();
-        if (tid == 0 && s_own) atomicAdd(&a.counters[2], s_own);
-    }
-}
-
-// Per-gene total_visited (library.cpp:327: every record of a group with >= 2 records adds the group size to its gene)
-// made on demand from the head bits the WRITE pass kept — only pdl_sequence_costs / pdl_genome_cost ask for it once the
-// ranges travel packed.  One thread per record; the extents come from word scans of the bit array.
-__global__ __launch_bounds__(256) void k_gene_costs_lazy(const uint2 *__restrict__ post, const unsigned long long *__restrict__ head_bits,
-                                                         uint32_t n, unsigned long long *__restrict__ cost) {
-    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= n) return;
-    // word layout: tile t, round j -> word t * 16 + j holds records t * 1024 + j * 64 .. +63  == record >> 6
-    const uint32_t w = u >> 6, b = u & 63u, words = (n + 63) >> 6;
-    uint32_t gs, ge;
-    {
-        unsigned long long m = head_bits[w] & ((2ull << b) - 1ull);
-        uint32_t ww = w;
-        while (!m && ww > 0) m = head_bits[--ww];
-        gs = m ? ww * 64u + 63u - (uint32_t) __clzll((long long) m) : 0u;
-    }
-    {
-        unsigned long long m = b == 63 ? 0ull : head_bits[w] & ~((2ull << b) - 1ull);
-        uint32_t ww = w;
-        while (!m && ww + 1 < words) m = head_bits[++ww];
-        ge = m ? ww * 64u + (uint32_t) __ffsll((long long) m) - 1u : n;
-        if (ge > n) ge = n;
-    }
-    if (ge - gs >= 2) atomicAdd(&cost[post[u].x], (unsigned long long) (ge - gs));
-}
-
-// COUNT for the range modes, per-thread code (the mask arithmetic of k_group_waves keeps a wave's uniform values in
-// vector registers and ran at a quarter of the streaming rate): a record gets a range iff its successor does not open a
-// group [and its gene belongs to the shard]; MODE 0: iff it is not alone in its group.  One wave per 1024-record tile.
-// Also leaves the first / last head of every tile for the WRITE pass, and the counters U' / shared groups.
-template <int MODE>
-__global__ __launch_bounds__(GW_THREADS) void k_range_count(GroupTileArgs a) {
-    extern __shared__ unsigned long long s_dyn[];
-    __shared__ uint32_t s_red[2];
-    uint2 *s_iv = reinterpret_cast<uint2 *>(s_dyn);
-    const uint32_t n_iv = (MODE == 0 || MODE == 2) ? a.n_own_iv : 0u;
-    if constexpr (MODE == 0 || MODE == 2) { for (uint32_t i = threadIdx.x; i < n_iv; i += GW_THREADS) s_iv[i] = a.own_iv[i]; }
-    if (threadIdx.x < 2) s_red[threadIdx.x] = 0;
-    pdl_sync();
-    const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1);
-    const uint32_t gw = blockIdx.x * GW_WAVES + tid / PDL_WAVE;
-    const uint32_t n = (uint32_t) scan_count(a.n_bound, a.d_n);
-    const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
-    uint32_t n_rec = 0, n_grp = 0, n_rep = 0;
-    for (uint32_t tile = gw; tile < tiles; tile += gridDim.x * GW_WAVES) {
-        const uint32_t t0 = tile * GW_TILE;
-        uint2 po[GW_ROUNDS];
-        uint32_t ynext[GW_ROUNDS];
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) {            // all loads first, branch-free
-            const uint32_t u = t0 + j * PDL_WAVE + lane;
-            po[j] = a.post[u < n ? u : n - 1];
-            ynext[j] = a.post[u + 1 < n ? u + 1 : n - 1].y;
-        }
-        uint32_t ins = 0xffffffffu;
-        if constexpr (MODE == 0 || MODE == 2) {
-            ins = 0;
-            if (n_iv) {                                  // (uniform) sixteen independent binary searches over the interval starts, in LDS
-                uint32_t lo_i[GW_ROUNDS], hi_i[GW_ROUNDS];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) { lo_i[j] = 0; hi_i[j] = n_iv; }
-                for (uint32_t span = n_iv; span > 0; span >>= 1) {
-#pragma unroll
-                    for (int j = 0; j < GW_ROUNDS; j++) {
-                        const uint32_t mid = (lo_i[j] + hi_i[j]) >> 1;
-                        const bool go = lo_i[j] < hi_i[j] && s_iv[mid < n_iv ? mid : n_iv - 1].x <= po[j].x;
-                        if (lo_i[j] < hi_i[j]) { if (go) lo_i[j] = mid + 1; else hi_i[j] = mid; }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) ins |= (uint32_t) (lo_i[j] > 0 && po[j].x < s_iv[lo_i[j] > 0 ? lo_i[j] - 1 : 0].y) << j;
-            } else {
-                uint8_t inb[GW_ROUNDS];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) inb[j] = a.in_shard[po[j].x];
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) ins |= (uint32_t) (inb[j] != 0) << j;
-            }
-        }
-        uint32_t cnt = 0, first_h = GT_NONE, last_h = 0, any_h = 0;
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) {
-            const uint32_t u = t0 + j * PDL_WAVE + lane;
-            const bool live = u < n;
-            const bool head = live && (po[j].y >> 31);
-            const bool next_head = u + 1 >= n || (ynext[j] >> 31);           // the successor opens a group, or is the end
-            const bool shared = live && !(head && next_head);
-            bool r = MODE == 0 ? shared : (live && !next_head);
-            if constexpr (MODE == 0 || MODE == 2) r = r && ((ins >> j) & 1u);
-            cnt += r;
-            n_rec += shared; n_grp += head && !next_head;
-            if (head) { first_h = min(first_h, u); last_h = max(last_h, u); any_h = 1; }
-        }
-        if ((tile & 7u) == 0) {                          // (uniform) records whose k-mer repeats inside its gene: a statistic, taken from every eighth tile
-#pragma unroll
-            for (int j = 0; j < GW_ROUNDS; j++) n_rep += 8u * (uint32_t) (t0 + j * PDL_WAVE + lane < n && (po[j].y & ~HEAD_BIT) >= 2u);
-        }
-#pragma unroll
-        for (int d = PDL_WAVE / 2; d > 0; d >>= 1) {
-            cnt += __shfl_xor(cnt, d, PDL_WAVE);
-            first_h = min(first_h, (uint32_t) __shfl_xor((int) first_h, d, PDL_WAVE));
-            last_h = max(last_h, (uint32_t) __shfl_xor((int) last_h, d, PDL_WAVE));
-            any_h |= (uint32_t) __shfl_xor((int) any_h, d, PDL_WAVE);
-        }
-        if (lane == 0) { a.tile_sums[tile] = cnt; a.th_first[tile] = first_h; a.th_last[tile] = any_h ? last_h : GT_NONE; }
-    }
-#pragma unroll
-    for (int d = PDL_WAVE / 2; d > 0; d >>= 1) { n_rec += __shfl_xor(n_rec, d, PDL_WAVE); n_grp += __shfl_xor(n_grp, d, PDL_WAVE); n_rep += __shfl_xor(n_rep, d, PDL_WAVE); }
-    if (lane == 0) { atomicAdd(&s_red[0], n_rec); atomicAdd(&s_red[1], n_grp); if (n_rep) atomicAdd(&a.counters[3], (unsigned long long) n_rep); }
-    pdl_sync();
-    if (tid < 2 && s_red[tid]) atomicAdd(&a.counters[tid], (unsigned long long) s_red[tid]);
-}
-
-// ---- the range tuples sorted by gene without being written in record order first ------------------------------------------
-// (upper ranges for every gene, packed: the single-GPU build.)  The first radix pass of the gene sort reads what the WRITE
-// pass has just written; here the kernel that BUILDS the tuples is that pass: a workgroup takes PDL_RADIX_TILE = 4 tiles of
-// records, k_range_count_hist has counted its tuples by the low byte of their gene (the pass's histogram; a record that gets
-// no range is simply not there), the scan of those counts says where every (block, byte) run starts, and k_range_scatter
-// makes the tuples as k_group_waves<WRITE> does and files them as k_rs_scatter does (ballot ranks, digit-sorted in LDS,
-// coalesced runs out).  Saves the tuples' trip through HBM (12 B written + 16 B read per range) and three launches.
-static_assert(GW_WAVES * GW_TILE == (int) PDL_RADIX_TILE && GW_THREADS == (int) PDL_RADIX_BINS, "a workgroup's four tiles are one tile of the radix pass");
-__global__ __launch_bounds__(GW_THREADS) void k_range_count_hist(GroupTileArgs a, uint32_t n_tiles4, uint32_t *__restrict__ counts) {
-    __shared__ uint32_t s_h[PDL_RADIX_BINS];
-    __shared__ uint32_t s_red[2];
-    const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
-    const uint32_t n = (uint32_t) scan_count(a.n_bound, a.d_n);
-    if (tid < 2) s_red[tid] = 0;
-    uint32_t n_rec = 0, n_grp = 0, n_rep = 0;
-    for (uint32_t blk = blockIdx.x; blk < n_tiles4; blk += gridDim.x) {       // (uniform loop: barriers inside)
-        s_h[tid] = 0;
-        pdl_sync();
-        const uint32_t tile = blk * GW_WAVES + wave, t0 = tile * GW_TILE;
-        if (t0 < n) {                                     // (wave-uniform)
-            uint2 po[GW_ROUNDS];
-            uint32_t ynext[GW_ROUNDS];
-#pragma unroll
-            for (int j = 0; j < GW_ROUNDS; j++) {        // all loads first, branch-free
-                const uint32_t u = t0 + j * PDL_WAVE + lane;
-                po[j] = a.post[u < n ? u : n - 1];
-                ynext[j] = a.post[u + 1 < n ? u + 1 : n - 1].y;
-            }
-            uint32_t cnt = 0, first_h = GT_NONE, last_h = 0, any_h = 0;
-#pragma unroll
-            for (int j = 0; j < GW_ROUNDS; j++) {
-                const uint32_t u = t0 + j * PDL_WAVE + lane;
-                const bool live = u < n;
-                const bool head = live && (po[j].y >> 31);
-                const bool next_head = u + 1 >= n || (ynext[j] >> 31);
-                const bool r = live && !next_head;
-                if (r) atomicAdd(&s_h[po[j].x & (PDL_RADIX_BINS - 1)], 1u);
-                cnt += r;
-                n_rec += live && !(head && next_head); n_grp += head && !next_head;
-                if (head) { first_h = min(first_h, u); last_h = max(last_h, u); any_h = 1; }
-            }
-#pragma unroll
-            for (int d = PDL_WAVE / 2; d > 0; d >>= 1) {
-                cnt += __shfl_xor(cnt, d, PDL_WAVE);
-                first_h = min(first_h, (uint32_t) __shfl_xor((int) first_h, d, PDL_WAVE));
-                last_h = max(last_h, (uint32_t) __shfl_xor((int) last_h, d, PDL_WAVE));
-                any_h |= (uint32_t) __shfl_xor((int) any_h, d, PDL_WAVE);
-            }
-            if (lane == 0) { a.tile_sums[tile] = cnt; a.th_first[tile] = first_h; a.th_last[tile] = any_h ? last_h : GT_NONE; }
-            if ((tile & 7u) == 0) {                      // (uniform) records whose k-mer repeats inside its gene: a statistic, taken from every eighth tile
-#pragma unroll
-                for (int j = 0; j < GW_ROUNDS; j++) n_rep += 8u * (uint32_t) (t0 + j * PDL_WAVE + lane < n && (po[j].y & ~HEAD_BIT) >= 2u);
-            }
-        }
-        pdl_sync();
-        counts[(size_t) tid * n_tiles4 + blk] = s_h[tid];
-    }
-#pragma unroll
-    for (int d = PDL_WAVE / 2; d > 0; d >>= 1) { n_rec += __shfl_xor(n_rec, d, PDL_WAVE); n_grp += __shfl_xor(n_grp, d, PDL_WAVE); n_rep += __shfl_xor(n_rep, d, PDL_WAVE); }
-    if (lane == 0) { atomicAdd(&s_red[0], n_rec); atomicAdd(&s_red[1], n_grp); if (n_rep) atomicAdd(&a.counters[3], (unsigned long long) n_rep); }
-    pdl_sync();
-    if (tid < 2 && s_red[tid]) atomicAdd(&a.counters[tid], (unsigned long long) s_red[tid]);
-}
-
-__global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, uint32_t n_tiles4, const uint32_t *__restrict__ offs,
-                                                              uint32_t *__restrict__ keys_out, unsigned long long *__restrict__ vals_out) {
-    const uint32_t n = (uint32_t) scan_count(a.n_bound, a.d_n);
-    if ((uint64_t) blockIdx.x * PDL_RADIX_TILE >= n) return;               // (uniform) block past the end
-    __shared__ uint32_t s_key[PDL_RADIX_TILE];
-    __shared__ unsigned long long s_val[PDL_RADIX_TILE];
-    __shared__ uint16_t s_cnt[GW_WAVES][PDL_RADIX_BINS];   // per wave: running count of each byte value, then its base inside the block (16-bit: three workgroups per CU)
-    __shared__ uint32_t s_tile_off[PDL_RADIX_BINS];
-    __shared__ uint32_t s_goff[PDL_RADIX_BINS];
-    __shared__ uint32_t s_wsum[17];
-    __shared__ unsigned long long s_own;
-    const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
-    const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
-    const uint32_t tile = blockIdx.x * GW_WAVES + wave, t0 = tile * GW_TILE, t1 = min(t0 + (uint32_t) GW_TILE, n);
-    const bool active = tile < tiles;                    // (wave-uniform; the last block may hold fewer than four tiles)
-    for (int w = 0; w < GW_WAVES; w++) s_cnt[w][tid] = 0;
-    s_goff[tid] = offs[(size_t) tid * n_tiles4 + blockIdx.x];
-    if (tid == 0) s_own = 0;
-    pdl_sync();
-
-    const unsigned long long lt_mask = (1ull << lane) - 1ull, le_mask = (2ull << lane) - 1ull;
-    uint2 po[GW_ROUNDS];
-    unsigned long long val[GW_ROUNDS];
-    uint16_t rank[GW_ROUNDS];
-    uint32_t rbits = 0;                                  // bit j: this lane's record of round j gets a range
-    unsigned long long own_lookups = 0;
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {                // all loads first, branch-free
-        const uint32_t u = t0 + j * PDL_WAVE + lane;
-        po[j] = a.post[u < n ? u : n - 1];
-    }
-    if (active) {
-        // the nearest tiles before / after with a head, 64 tiles per look (the COUNT pass's per-tile heads: other
-        // workgroups may have removed their head bits already)
-        const uint32_t hb = lane < tile ? a.th_last[tile - 1 - lane] : GT_NONE;
-        const uint32_t ha = tile + 1 + lane < tiles ? a.th_first[tile + 1 + lane] : GT_NONE;
-        unsigned long long m[GW_ROUNDS];
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) m[j] = __ballot(t0 + j * PDL_WAVE + lane < n && (po[j].y >> 31));
-        uint32_t before = t0;
-        if (!(m[0] & 1ull)) {                            // (uniform) the tile starts inside a group
-            unsigned long long hm = __ballot(hb != GT_NONE);
-            if (hm) before = (uint32_t) __shfl((int) hb, __ffsll((long long) hm) - 1, PDL_WAVE);
-            else {
-                before = 0;
-                for (uint32_t hi = tile >= PDL_WAVE ? tile - PDL_WAVE : 0; hi > 0;) {
-                    const uint32_t base = hi >= PDL_WAVE ? hi - PDL_WAVE : 0, idx = base + lane;
-                    const uint32_t v = idx < hi ? a.th_last[idx] : GT_NONE;
-                    hm = __ballot(v != GT_NONE);
-                    if (hm) { before = (uint32_t) __shfl((int) v, 63 - __clzll((long long) hm), PDL_WAVE); break; }
-                    hi = base;
-                }
-            }
-        }
-        uint32_t after;
-        {
-            unsigned long long hm = __ballot(ha != GT_NONE);
-            if (hm) after = (uint32_t) __shfl((int) ha, __ffsll((long long) hm) - 1, PDL_WAVE);
-            else {
-                after = n;
-                for (uint32_t lo = tile + 1 + PDL_WAVE; lo < tiles; lo += PDL_WAVE) {
-                    const uint32_t idx = lo + lane;
-                    const uint32_t v = idx < tiles ? a.th_first[idx] : GT_NONE;
-                    hm = __ballot(v != GT_NONE);
-                    if (hm) { after = (uint32_t) __shfl((int) v, __ffsll((long long) hm) - 1, PDL_WAVE); break; }
-                }
-            }
-        }
-        before = (uint32_t) __builtin_amdgcn_readfirstlane((int) before);
-        after = (uint32_t) __builtin_amdgcn_readfirstlane((int) after);
-        uint32_t nextr[GW_ROUNDS];
-        uint32_t nx = after;
-#pragma unroll
-        for (int j = GW_ROUNDS - 1; j >= 0; j--) {
-            nextr[j] = nx;
-            if (m[j]) nx = t0 + j * PDL_WAVE + (uint32_t) __ffsll((long long) m[j]) - 1u;
-        }
-        uint32_t pr = before;
-#pragma unroll
-        for (int j = 0; j < GW_ROUNDS; j++) {
-            const uint32_t u = t0 + j * PDL_WAVE + lane;
-            const unsigned long long at_or_below = m[j] & le_mask, above = m[j] & ~le_mask;
-            const uint32_t gs = at_or_below ? t0 + j * PDL_WAVE + 63u - (uint32_t) __clzll((long long) at_or_below) : pr;
-            const uint32_t ge = above ? t0 + j * PDL_WAVE + (uint32_t) __ffsll((long long) above) - 1u : nextr[j];
-            const bool live = u < t1;
-            const bool shared = live && ge - gs >= 2;
-            const bool r = shared && u + 1 < ge;         // the last member of a group has nothing above it
-            const uint32_t cnt = po[j].y & ~HEAD_BIT;
-            if (live && (po[j].y >> 31)) a.post[u].y = cnt;                    // the bit has done its job
-            if (shared) own_lookups += ge - gs;
-            val[j] = (unsigned long long) (u + 1) | ((unsigned long long) ((ge - u - 1) | (min(cnt, 1023u) << 22)) << 32);
-            rbits |= (uint32_t) r << j;
-            if (lane == 0) a.head_bits[(size_t) tile * GW_ROUNDS + j] = m[j];
-            if (m[j]) pr = t0 + j * PDL_WAVE + 63u - (uint32_t) __clzll((long long) m[j]);
-        }
-    }
-    // ---- the radix pass on the low byte of the gene (k_rs_scatter's ranking; an element is a record with a range) ----------
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        const bool valid = (rbits >> j) & 1u;
-        const uint32_t d = po[j].x & (PDL_RADIX_BINS - 1);
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const unsigned long long mb = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? mb : ~mb;
-        }
-        const uint32_t seen = s_cnt[wave][d];                       // earlier rounds (own wave only: no race)
-        rank[j] = (uint16_t) (seen + (uint32_t) __popcll(same & lt_mask));
-        if (valid && (same & lt_mask) == 0) s_cnt[wave][d] = (uint16_t) (seen + (uint32_t) __popcll(same));      // lowest lane of the set
-    }
-    pdl_sync();
-    uint32_t tot = 0;
-    uint32_t wcnt[GW_WAVES];
-#pragma unroll
-    for (int w = 0; w < GW_WAVES; w++) { wcnt[w] = s_cnt[w][tid]; tot += wcnt[w]; }
-    uint32_t tile_total;
-    const uint32_t ex = block_exclusive_scan_u32(tot, s_wsum, tile_total);
-    s_tile_off[tid] = ex;
-    uint32_t run = ex;
-#pragma unroll
-    for (int w = 0; w < GW_WAVES; w++) { s_cnt[w][tid] = (uint16_t) run; run += wcnt[w]; }
-    pdl_sync();
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        if ((rbits >> j) & 1u) {
-            const uint32_t lp = s_cnt[wave][po[j].x & (PDL_RADIX_BINS - 1)] + rank[j];
-            s_key[lp] = po[j].x;
-            s_val[lp] = val[j];
-        }
-    }
-#pragma unroll
-    for (int d = PDL_WAVE / 2; d > 0; d >>= 1) own_lookups += __shfl_xor(own_lookups, d, PDL_WAVE);
-    if (lane == 0 && own_lookups) atomicAdd(&s_own, own_lookups);
-    pdl_sync();
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        const uint32_t e = j * GW_THREADS + tid;                     // coalesced over the digit-sorted block
-        if (e < tile_total) {
-            const uint32_t k = s_key[e];
-            const uint32_t d = k & (PDL_RADIX_BINS - 1);
-            const uint64_t dst = (uint64_t) s_goff[d] + (e - s_tile_off[d]);
-            keys_out[dst] = k;
-            vals_out[dst] = s_val[e];
-        }
-    }
-    if (tid == 0 && s_own) atomicAdd(&a.counters[2], s_own);
-}
-
-// Between the passes: tile_sums[t] (ranges of tile t) becomes the count of the tiles before t inside its block of 64 tiles,
-// chunk_sums[b] the block's total (scanned next); one wave per block.
-__global__ __launch_bounds__(256) void k_tile_prefix(uint32_t *__restrict__ tile_sums, const uint64_t *d_n, uint64_t n_bound,
-                                                     uint32_t *__restrict__ chunk_sums, uint32_t n_blocks) {
-    const uint32_t b = blockIdx.x * 4 + threadIdx.x / PDL_WAVE, lane = threadIdx.x & (PDL_WAVE - 1);
-    if (b >= n_blocks) return;
-    const uint32_t tiles = (uint32_t) ((scan_count(n_bound, d_n) + GW_TILE - 1) / GW_TILE);
-    const uint32_t t = b * PDL_WAVE + lane;
-    const uint32_t v = t < tiles ? tile_sums[t] : 0u;
-    const uint32_t inc = wave_inclusive_scan_u32(v);
-    if (t < tiles) tile_sums[t] = inc - v;
-    if (lane == PDL_WAVE - 1) chunk_sums[b] = inc;
-}
-
 // in_shard[gene] = the gene's genome belongs to this rank (multi-GPU: from the genome deal, without a host round trip)
 __global__ __launch_bounds__(256) void k_genes_of_rank(const uint32_t *__restrict__ genome_of, const uint32_t *__restrict__ owner, uint32_t rank,
                                                        uint32_t n_seq, uint8_t *__restrict__ in_shard) {
@@ -1230,24 +574,37 @@ static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint
     stage_dedup<KeyT>(c, m);
 }
 
-// Launch helpers of k_group_waves.  group_tiles_plan sizes the grid and the scratch: tile_sums[tiles] | th_first[tiles] |
-// th_last[tiles] | chunk_sums[blocks of 64 tiles].  Returns the number of workgroups.
-static uint32_t group_tiles_plan(pdl_ctx *c, GroupTileArgs &a) {
-    const uint64_t tiles = (a.n_bound + GW_TILE - 1) / GW_TILE;
-    if (tiles > 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "dictionary of %llu records exceeds the grid limit", (unsigned long long) a.n_bound);
-    const int cus = pdl_cus(c);
-    a.n_blocks = (uint32_t) ((tiles + PDL_WAVE - 1) / PDL_WAVE);
-    const uint32_t grid = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((tiles + GW_WAVES - 1) / GW_WAVES, (uint64_t) cus * 8));
-    c->scan_tmp.alloc(((size_t) tiles * 3 + a.n_blocks + 1) * sizeof(uint32_t));
-    a.tile_sums = c->scan_tmp.as<uint32_t>(); a.th_first = a.tile_sums + tiles; a.th_last = a.th_first + tiles; a.chunk_sums = a.th_last + tiles;
-    return grid;
-}
-template <int PASS, int MODE, bool GENOMES, bool RECORD_COSTS>
-static void launch_group_tiles(pdl_ctx *c, const GroupTileArgs &a, uint32_t grid) {
-    size_t dyn = GENOMES && a.n_genomes <= COST_LDS_GENOMES ? 2 * (size_t) a.n_genomes * sizeof(uint64_t) : 0;
-    if (MODE == 0 || MODE == 2) dyn = (size_t) a.n_own_iv * sizeof(uint2);
-    hipLaunchKernelGGL((k_group_waves<PASS, MODE, GENOMES, RECORD_COSTS>), dim3(grid), dim3(GW_THREADS), dyn, c->stream, a);
-    PDL_HIP(hipGetLastError());
+// The shard of a range build into ga: the genes that get range lists, as sorted gene-id intervals when every genome's genes
+// are consecutive ids (the usual .faa) and there are at most GW_MAX_IV of them, and as the byte table.
+static void group_shard_args(pdl_ctx *c, GroupTileArgs &ga) {
+    hipStream_t st = c->stream;
+    std::vector<uint2> &iv = c->h_own_iv;
+    iv.clear();
+    bool contiguous = true;
+    for (uint32_t g : c->dict_shard) {               // (ascending genome ids; genomes in first-seen order: ascending gene ids too)
+        const uint32_t b0 = c->h_genome_row_off[g], e0 = c->h_genome_row_off[g + 1];
+        if (b0 == e0) continue;
+        const uint32_t first = c->h_genome_rows[b0], last = c->h_genome_rows[e0 - 1];
+        if (last - first + 1 != e0 - b0) { contiguous = false; break; }
+        if (!iv.empty() && iv.back().y == first) iv.back().y = last + 1; else iv.push_back(make_uint2(first, last + 1));
+    }
+    if (contiguous) std::sort(iv.begin(), iv.end(), [](const uint2 &p, const uint2 &q) { return p.x < q.x; });
+    for (size_t i = 1; contiguous && i < iv.size(); i++) if (iv[i].x < iv[i - 1].y) contiguous = false;      // (cannot happen: genes belong to one genome)
+    if (contiguous && !iv.empty() && iv.size() <= GW_MAX_IV) {
+        c->own_iv.alloc(iv.size() * sizeof(uint2));
+        PDL_HIP(hipMemcpyAsync(c->own_iv.p, iv.data(), iv.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        ga.own_iv = c->own_iv.as<uint2>(); ga.n_own_iv = (uint32_t) iv.size();
+    }
+    if (!c->dist) {                                  // (multi-GPU: the deal is on the device already, pdl_run_dist_finish)
+        std::vector<uint8_t> &h = c->h_seq_in_shard; // lives in the context: the copy below needs no synchronisation
+        h.assign((size_t) c->N, 0);
+        std::vector<uint8_t> gsel((size_t) c->G, 0);
+        for (uint32_t g : c->dict_shard) gsel[g] = 1;
+        for (uint32_t i = 0; i < c->N; i++) h[i] = gsel[c->h_genome_of[i]];
+        c->seq_in_shard.alloc(c->N);
+        PDL_HIP(hipMemcpyAsync(c->seq_in_shard.p, h.data(), c->N, hipMemcpyHostToDevice, st));
+    }
+    ga.in_shard = c->seq_in_shard.as<uint8_t>();
 }
 
 // K-groups + K-ranges + K-cost over the dictionary (postings with head bits; `bound` records at most, the count is at
@@ -1266,7 +623,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
     ga.genome_of = c->d_gen; ga.n_genomes = c->G;
     hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, st, post, c->post_ext ? (uint32_t *) nullptr : c->recpos.as<uint32_t>(), d_u);
     if (only_complexity) {                   // (cost[] was zeroed by K-len's apply, the counters with the control block)
-        launch_group_tiles<0, 3, false, true>(c, ga, grid);
+        launch_group_costs<false, true>(c, ga, grid);
     } else {
         ev_begin(c, EV_SORT2);
         // Ranges travel packed (8 bytes, carried through the gene sort as its payload: no gather afterwards) whenever a
@@ -1294,37 +651,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             else { c->vals_a.alloc(cap * sizeof(uint32_t)); k2a = c->vals_a.as<uint32_t>(); }
         };
         if (!exact) carve();
-        if (mode != 1) {                    // the shard as gene-id intervals, when every genome's genes are consecutive ids (the usual .faa)
-            std::vector<uint2> &iv = c->h_own_iv;
-            iv.clear();
-            bool contiguous = true;
-            for (uint32_t g : c->dict_shard) {           // (ascending genome ids; genomes in first-seen order: ascending gene ids too)
-                const uint32_t b0 = c->h_genome_row_off[g], e0 = c->h_genome_row_off[g + 1];
-                if (b0 == e0) continue;
-                const uint32_t first = c->h_genome_rows[b0], last = c->h_genome_rows[e0 - 1];
-                if (last - first + 1 != e0 - b0) { contiguous = false; break; }
-                if (!iv.empty() && iv.back().y == first) iv.back().y = last + 1; else iv.push_back(make_uint2(first, last + 1));
-            }
-            if (contiguous) std::sort(iv.begin(), iv.end(), [](const uint2 &p, const uint2 &q) { return p.x < q.x; });
-            for (size_t i = 1; contiguous && i < iv.size(); i++) if (iv[i].x < iv[i - 1].y) contiguous = false;      // (cannot happen: genes belong to one genome)
-            if (contiguous && !iv.empty() && iv.size() <= GW_MAX_IV) {
-                c->own_iv.alloc(iv.size() * sizeof(uint2));
-                PDL_HIP(hipMemcpyAsync(c->own_iv.p, iv.data(), iv.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-                ga.own_iv = c->own_iv.as<uint2>(); ga.n_own_iv = (uint32_t) iv.size();
-            }
-        }
-        if (mode != 1 && c->dist) {         // multi-GPU: the deal is on the device already (pdl_run_dist_finish)
-            ga.in_shard = c->seq_in_shard.as<uint8_t>();
-        } else if (mode != 1) {             // only the genes this context scores need range lists
-            std::vector<uint8_t> &h = c->h_seq_in_shard;   // lives in the context: the copy below needs no synchronisation
-            h.assign((size_t) c->N, 0);
-            std::vector<uint8_t> gsel((size_t) c->G, 0);
-            for (uint32_t g : c->dict_shard) gsel[g] = 1;
-            for (uint32_t i = 0; i < c->N; i++) h[i] = gsel[c->h_genome_of[i]];
-            c->seq_in_shard.alloc(c->N);
-            PDL_HIP(hipMemcpyAsync(c->seq_in_shard.p, h.data(), c->N, hipMemcpyHostToDevice, st));
-            ga.in_shard = c->seq_in_shard.as<uint8_t>();
-        }
+        if (mode != 1) group_shard_args(c, ga);      // only the genes this context scores need range lists
         // the head bits the WRITE pass takes out of the postings are kept: for the per-gene costs made on demand (packed ranges), and
         // to put them back when the ranges are built again for another shard of genomes (pdl_run_reshard)
         c->head_bits.alloc(((bound + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
@@ -1346,15 +673,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, k2b, pay_b);
             PDL_HIP(hipGetLastError());
         } else {
-        {
-            const size_t dyn = (size_t) ga.n_own_iv * sizeof(uint2);
-            if (mode == 1) hipLaunchKernelGGL(k_range_count<1>, dim3(grid), dim3(GW_THREADS), 0, st, ga);
-            else if (mode == 2) hipLaunchKernelGGL(k_range_count<2>, dim3(grid), dim3(GW_THREADS), dyn, st, ga);
-            else hipLaunchKernelGGL(k_range_count<0>, dim3(grid), dim3(GW_THREADS), dyn, st, ga);
-            PDL_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_tile_prefix, dim3((ga.n_blocks + 3) / 4), dim3(256), 0, st, ga.tile_sums, ga.d_n, ga.n_bound, ga.chunk_sums, ga.n_blocks);
-        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + PDL_CTL_RANGES, (uint64_t *) nullptr);
+        launch_range_count(c, ga, grid, mode);
         if (exact) {                         // the shard's range count, then buffers of that size
             if (!c->tasks_ready) pdl_prepare_tasks(c);       // host work + small uploads while the device counts
             PinRead rd(c);
@@ -1364,9 +683,7 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             carve();
         }
         ga.key2 = k2a; ga.tuples = tuples; ga.pay8 = packed ? pay_a : nullptr;
-        if (mode == 1) launch_group_tiles<1, 1, false, false>(c, ga, grid);
-        else if (mode == 2) launch_group_tiles<1, 2, false, false>(c, ga, grid);
-        else launch_group_tiles<1, 0, false, false>(c, ga, grid);
+        launch_range_write(c, ga, grid, mode);
         }
         c->upper_only = mode != 0;
         const uint32_t seq_bits = std::max<uint32_t>(1, bit_length64(c->N ? c->N - 1 : 0));
@@ -1429,12 +746,6 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
 // (scoring a large set a batch of genomes at a time: the postings — rank, sort, dedup, most of the build — are made once; a batch
 // costs the two passes over the postings that form its genes' range lists.)  The WRITE pass took the group-head bits out of the
 // postings; they are put back from the copy it kept, the counters of the range stage start at zero again.
-__global__ __launch_bounds__(256) void k_restore_heads(uint2 *__restrict__ post, const unsigned long long *__restrict__ head_bits, uint32_t n) {
-    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= n) return;
-    if ((head_bits[u >> 6] >> (u & 63u)) & 1ull) post[u].y |= HEAD_BIT;          // (word layout: record >> 6, see k_gene_costs_lazy)
-}
-
 void pdl_run_reshard(pdl_ctx *c) {
     hipStream_t st = c->stream;
     if (c->dist || c->post_ext) PDL_FAIL(PDL_ERR_STATE, "genome shard: a multi-GPU context deals the genomes itself");
@@ -1912,7 +1223,7 @@ static void dist_slice_pipeline(pdl_ctx *c) {
         ga.genome_of = c->d_gen; ga.n_genomes = c->G;
         ga.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);             // scratch here, cleared again by the finish
         ga.g_upper = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST) + c->G;
-        launch_group_tiles<0, 3, true, false>(c, ga, grid);
+        launch_group_costs<true, false>(c, ga, grid);
         ev_end(c, EV_DICT);
     } else {
         c->post.alloc(16);
@@ -1998,7 +1309,7 @@ void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {
         ga.g_upper = c->scratch2.as<unsigned long long>();
         ga.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);       // (scratch: the K-cost words are cleared below)
         // (the fold of the last record is not applied yet: as with the callers' weights, these numbers only balance)
-        launch_group_tiles<0, 3, true, false>(c, ga, grid);
+        launch_group_costs<true, false>(c, ga, grid);
         {
             PinRead rd(c);
             const uint64_t *pu = rd.add<uint64_t>(ga.g_upper, c->G);
@@ -2084,10 +1395,7 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
         ga.cost = c->cost.as<unsigned long long>();
         ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
         ga.genome_of = c->d_gen; ga.n_genomes = c->G;
-        hipLaunchKernelGGL(k_range_count<1>, dim3(grid), dim3(GW_THREADS), 0, st, ga);
-        hipLaunchKernelGGL(k_tile_prefix, dim3((ga.n_blocks + 3) / 4), dim3(256), 0, st, ga.tile_sums, ga.d_n, ga.n_bound, ga.chunk_sums, ga.n_blocks);
-        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, st, ga.chunk_sums, ga.n_blocks, d_scal + PDL_CTL_RANGES, (uint64_t *) nullptr);
-        PDL_HIP(hipGetLastError());
+        launch_range_count(c, ga, grid, 1);
         uint64_t n_t = 0;
         {
             PinRead rd(c);
@@ -2102,7 +1410,7 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
         c->head_bits.alloc(((n_run + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
         ga.head_bits = c->head_bits.as<unsigned long long>();
         ga.key2 = k2a; ga.tuples = nullptr; ga.pay8 = pay_a; ga.pos_base = (uint32_t) base;
-        launch_group_tiles<1, 1, false, false>(c, ga, grid);
+        launch_range_write(c, ga, grid, 1);
         if (n_t) {
             hipLaunchKernelGGL(k_owner_keys, dim3((uint32_t) std::min<uint64_t>((n_t + 255) / 256, (uint64_t) c->cus * 16)), dim3(256), 0, st, k2a, d_scal + PDL_CTL_RANGES, c->seq_owner.as<uint8_t>());
             pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_t, 32, false, nullptr, 24, true);      // -> (k2b, pay_b), by destination
