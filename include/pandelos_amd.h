@@ -351,6 +351,70 @@ PDL_API int pdl_families_of_edges(pdl_ctx *, const int32_t *src, const int32_t *
                                   const uint32_t *genome_of /* [n_sequences] */, uint32_t n_sequences, pdl_families *out);
 PDL_API void pdl_free_families(pdl_families *);
 
+/* ---- place: a new genome's genes in the gene families already built, without a commit -------------------------------------
+ * pdl_place_query: the base context holds N genes in G genomes; the query is n_query genes taken as genome G with ids
+ * N..N+n_query-1 in union numbering, exactly as pdl_query_scores does.
+ * Edges: src/dst/score are the addConnection calls of task G in the union run — Pangenes.java:98-176 applied to the block
+ * pdl_query_scores returns, filtered on the device where the block lies — in the host's insertion order: phase 1 cell by cell,
+ * (row, col) then (col, row), then phase 2; edges_phase1 of them are phase 1.  Bit for bit and in order what
+ * pangenes.bbh_edges(block) gives on the host and what pdl_compute_edges(G) gives on a context the same genes were appended to.
+ * Placement: the combined network is the base network as the context has it (pdl_compute_edges over all genomes) plus the
+ * query's edges.  Components, labels, node-ness and collisions follow pdl_families: edges are undirected, a repeated pair is one
+ * edge, a self edge makes its gene a node but is no edge, a label is the smallest gene id of the component, a component collides
+ * when it holds two genes of one genome that are not adjacent.  Only the part the query touches is returned:
+ *   family_of[n]     label of each query gene's combined component: a base gene id when the component holds base genes, a query
+ *                    id >= N for a family of query genes only, the gene's own id for a gene without an edge
+ *   is_node[n]       the query gene has an edge (self edges count)
+ *   groups           the combined components that hold at least one query node, in ascending label order; per group its label,
+ *                    its query members ascending (group_query_off / group_query, union ids) and the labels of the base
+ *                    components it fuses, ascending (group_base_off / group_base; a base gene that was no node in the base counts
+ *                    as a component of one).  No base component: a novel family; one: the genes join it; two or more: a bridge.
+ *   group_collides   the collision flag of the whole combined component = a fused base component already collides, OR two
+ *                    distinct fused base components hold genes of one genome (they cannot be adjacent: every new edge has a
+ *                    query end), OR the group's m >= 2 query genes are not a clique under the phase-2 edges
+ *   novel, joined, bridging, colliding: groups of each kind; unplaced: query genes without an edge
+ *   device_ms        as pdl_query_info.device_ms, over the query and the placement
+ * NOT the families of a union rebuild, in two ways, neither of which is attempted: (1) the base genomes' paralog thresholds
+ * (Pangenes.java:146-155) can only fall once genome G exists, so a union run may add intra-genome edges between base genes;
+ * (2) the union's last-record fold (library.cpp:297-306) can change single base-to-base cells.  pdl_append_genomes commits.
+ * The base context is only read: scores, edges, families, dictionary, costs and timings are equal before and after, placements
+ * are independent of each other; the context's families are computed on first use, as by pdl_compute_families.  Refusals are
+ * decided before anything is returned and leave `out` zeroed: every state pdl_query_scores refuses and every state
+ * pdl_compute_families refuses (a genome shard in force included) is PDL_ERR_STATE; the query's argument and domain refusals pass
+ * through with their codes and messages.  `info` (may be NULL): the query's own sizes, as pdl_query_scores fills it.
+ * pdl_placement_of_edges: the same kernels over a caller's query edge list in union ids, on a caller's base — `base` as
+ * pdl_compute_families / pdl_families_of_edges returned it for the N = base->sequences base genes, genome_of[N] their genomes (the
+ * query is one further genome).  The list is read as pdl_families_of_edges reads one: any order, repeats, both directions and
+ * self edges allowed, query-query pairs de-duplicated before they are counted.  src/dst/score of `out` stay NULL.  Of the context
+ * only the device, the stream and work buffers are used.  PDL_ERR_ARGUMENT, counted on the device BEFORE any id indexes
+ * anything: an id outside [0, N + n_query), an edge with both ends below N; also NULL pointers, n_query == 0 and a `base` whose
+ * fields contradict each other.  Free with pdl_free_placement. */
+typedef struct {
+    uint32_t sequences;        /* N of the base */
+    uint32_t n_query;          /* n */
+    uint32_t genomes;          /* G: the query's genome id */
+    uint32_t edges;            /* pdl_place_query: the query's edges ... */
+    uint32_t edges_phase1;     /* ... of which phase 1 (the first edges_phase1 entries) */
+    uint32_t groups;
+    uint32_t novel, joined, bridging, colliding, unplaced;
+    float device_ms;
+    int32_t *src, *dst;        /* [edges] union ids */
+    float *score;              /* [edges] */
+    uint32_t *family_of;       /* [n] */
+    uint8_t *is_node;          /* [n] */
+    uint32_t *group_label;     /* [groups] ascending */
+    uint32_t *group_query_off; /* [groups+1] into group_query */
+    uint32_t *group_query;     /* query genes (union ids), ascending inside a group */
+    uint32_t *group_base_off;  /* [groups+1] into group_base */
+    uint32_t *group_base;      /* labels of the fused base components, ascending inside a group */
+    uint8_t *group_collides;   /* [groups] */
+} pdl_placement;
+PDL_API int pdl_place_query(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n_query+1] */, uint32_t n_query,
+                            pdl_placement *out, pdl_query_info *info /* may be NULL */);
+PDL_API int pdl_placement_of_edges(pdl_ctx *, const pdl_families *base, const uint32_t *genome_of /* [base->sequences] */, uint32_t n_query,
+                                   const int32_t *src, const int32_t *dst, uint64_t n_edges, pdl_placement *out);
+PDL_API void pdl_free_placement(pdl_placement *);
+
 /* Number of emitted cells per genome after pdl_score_all ([G], 0 for genomes outside the shard) */
 PDL_API int pdl_scores_counts(pdl_ctx *, uint32_t *out_counts);
 

@@ -123,6 +123,17 @@ class PdlFamilies(C.Structure):
                 ("family_genes", C.POINTER(C.c_uint32)), ("collides", C.POINTER(C.c_uint8)), ("device_ms", C.c_float)]
 
 
+class PdlPlacement(C.Structure):
+    _fields_ = [("sequences", C.c_uint32), ("n_query", C.c_uint32), ("genomes", C.c_uint32), ("edges", C.c_uint32),
+                ("edges_phase1", C.c_uint32), ("groups", C.c_uint32), ("novel", C.c_uint32), ("joined", C.c_uint32),
+                ("bridging", C.c_uint32), ("colliding", C.c_uint32), ("unplaced", C.c_uint32), ("device_ms", C.c_float),
+                ("src", C.POINTER(C.c_int32)), ("dst", C.POINTER(C.c_int32)), ("score", C.POINTER(C.c_float)),
+                ("family_of", C.POINTER(C.c_uint32)), ("is_node", C.POINTER(C.c_uint8)), ("group_label", C.POINTER(C.c_uint32)),
+                ("group_query_off", C.POINTER(C.c_uint32)), ("group_query", C.POINTER(C.c_uint32)),
+                ("group_base_off", C.POINTER(C.c_uint32)), ("group_base", C.POINTER(C.c_uint32)),
+                ("group_collides", C.POINTER(C.c_uint8))]
+
+
 DIST_CELL_BYTES = 24      # pdl_dist_cell: 3 x f32 + 3 x u32
 
 
@@ -135,7 +146,8 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_dist_genome_owner", "pdl_dist_score_begin", "pdl_dist_score_finish", "pdl_copy_device",
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
-           "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families")
+           "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
+           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement")
 
 _lib = None
 
@@ -195,6 +207,10 @@ def load():
     lib.pdl_compute_families.argtypes = [vp, C.POINTER(PdlFamilies)]; lib.pdl_compute_families.restype = i32
     lib.pdl_families_of_edges.argtypes = [vp, vp, vp, u64, vp, u32, C.POINTER(PdlFamilies)]; lib.pdl_families_of_edges.restype = i32
     lib.pdl_free_families.argtypes = [C.POINTER(PdlFamilies)]; lib.pdl_free_families.restype = None
+    lib.pdl_place_query.argtypes = [vp, vp, vp, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo)]; lib.pdl_place_query.restype = i32
+    lib.pdl_placement_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, u64, C.POINTER(PdlPlacement)]
+    lib.pdl_placement_of_edges.restype = i32
+    lib.pdl_free_placement.argtypes = [C.POINTER(PdlPlacement)]; lib.pdl_free_placement.restype = None
     lib.pdl_compute_edges.argtypes = [vp, u32, C.POINTER(PdlEdges)]; lib.pdl_compute_edges.restype = i32
     lib.pdl_free_edges.argtypes = [C.POINTER(PdlEdges)]; lib.pdl_free_edges.restype = None
     lib.pdl_ingest_faa.argtypes = [vp, C.c_char_p, C.POINTER(PdlIngest)]; lib.pdl_ingest_faa.restype = i32

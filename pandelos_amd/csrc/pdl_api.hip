@@ -24,6 +24,11 @@ template <class T> static T *xalloc(size_t n) {
     if (!p) throw std::bad_alloc();
     return p;
 }
+template <class T> static T *dup_vec(const std::vector<T> &v) {
+    T *p = xalloc<T>(v.size());
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
 
 extern "C" {
 
@@ -82,6 +87,7 @@ void pdl_destroy(pdl_ctx *c) {
     for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->rm.ev) if (e) (void) hipEventDestroy(e);
     for (hipEvent_t e : c->fb.ev) if (e) (void) hipEventDestroy(e);
+    for (hipEvent_t e : c->pb.ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
@@ -164,7 +170,7 @@ int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int onl
     PDL_GUARD_BEGIN
     PDL_HIP(hipSetDevice(c->device));
     c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;      // the genome shard, if one was set, stays in force
-    c->qb.release(); c->qbb.release();
+    c->qb.release(); c->qbb.release(); c->pb.release();
     c->N = n; c->R = n_res;
     c->U = c->Ushared = c->NG = c->P = c->M = 0;
     if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
@@ -616,6 +622,129 @@ int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, ui
         return PDL_OK;
     } catch (const pdl_error &e) { c->err = e.msg; pdl_free_families(out); return e.code;
     } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_families(out); return PDL_ERR_DEVICE; }
+}
+
+// ---- K-place (pdl_place.h) ---------------------------------------------------------------------------------------------------
+void pdl_free_placement(pdl_placement *p) {
+    if (!p) return;
+    free(p->src); free(p->dst); free(p->score); free(p->family_of); free(p->is_node); free(p->group_label); free(p->group_query_off);
+    free(p->group_query); free(p->group_base_off); free(p->group_base); free(p->group_collides);
+    memset(p, 0, sizeof(*p));
+}
+
+static void fill_placement(const pdl_place_result &r, bool with_edges, pdl_placement *out) {
+    out->sequences = r.sequences; out->n_query = r.n_query; out->genomes = r.genomes;
+    out->edges = (uint32_t) r.src.size(); out->edges_phase1 = r.edges_phase1; out->groups = r.groups;
+    out->novel = r.novel; out->joined = r.joined; out->bridging = r.bridging; out->colliding = r.colliding; out->unplaced = r.unplaced;
+    out->device_ms = r.device_ms;
+    if (with_edges) { out->src = dup_vec(r.src); out->dst = dup_vec(r.dst); out->score = dup_vec(r.score); }
+    out->family_of = dup_vec(r.family_of); out->is_node = dup_vec(r.is_node); out->group_label = dup_vec(r.group_label);
+    out->group_query_off = dup_vec(r.group_query_off); out->group_query = dup_vec(r.group_query);
+    out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
+}
+
+int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_placement *out, pdl_query_info *info) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out) memset(out, 0, sizeof(*out));
+    if (info) memset(info, 0, sizeof(*info));
+    try {
+        // the refusals of pdl_query_scores and of pdl_compute_families first: nothing of the context has been touched when one returns
+        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query before pdl_preprocess");
+        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: the context was preprocessed with only_complexity");
+        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: not available on a multi-GPU context");
+        if (c->shard_set || !c->dict_shard.empty())
+            PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: a genome shard is in force, the context does not hold every genome's edges (gather them: pdl_placement_of_edges)");
+        if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
+            PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: the sorted k-mer stream was released (option low_memory)");
+        if (!out || !offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL pointer");
+        if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: no query gene");
+        for (uint32_t i = 0; i < n_query; i++)
+            if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: offsets decrease at gene %u", i);
+        if (!residues && offsets[n_query] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL residues");
+        int rc = c->scored ? PDL_OK : score_all_locked(c);
+        if (rc != PDL_OK) return rc;
+        PDL_HIP(hipSetDevice(c->device));
+        if (!c->edges_valid) pdl_run_bbh_all(c);
+        if (!c->fam_valid) pdl_run_families_of_context(c);
+        pdl_place_result r;
+        pdl_query_info qi{};
+        pdl_run_place_query(c, residues, offsets, n_query, r, &qi);
+        fill_placement(r, true, out);
+        if (info) *info = qi;
+        return PDL_OK;
+    } catch (const pdl_error &e) { c->err = e.msg; if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); return e.code;
+    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); return PDL_ERR_DEVICE; }
+}
+
+int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t *genome_of, uint32_t n_query, const int32_t *src, const int32_t *dst,
+                           uint64_t n_edges, pdl_placement *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    try {
+        if (!base || (n_edges && (!src || !dst))) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
+        const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
+        if (N && (!genome_of || !base->component_of || !base->is_node)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
+        if (!base->family_off || (nodes && !base->family_genes) || (F && !base->collides)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer in the base families");
+        if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: no query gene");
+        if (n_edges >= 0x7fffffffull || (uint64_t) N + n_query >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_placement_of_edges: 2^31 genes or edges and more");
+        // the base is indexed by its own fields on the device: they must be what K-fam writes (labels are smallest members, families
+        // in label order, members ascending, every node in exactly one family)
+        if (nodes > N || F > nodes || base->family_off[0] != 0 || base->family_off[F] != nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (counts)");
+        std::vector<uint32_t> of_label(N, 0);
+        std::vector<uint8_t> listed(N, 0);             // the gene is a member of exactly one family
+        for (uint32_t f = 0; f < F; f++) {
+            const uint32_t a = base->family_off[f], b = base->family_off[f + 1];
+            if (b <= a || b > nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (family_off at %u)", f);
+            const uint32_t label = base->family_genes[a];
+            if (f && label <= base->family_genes[base->family_off[f - 1]])
+                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (family %u is not behind family %u in label order)", f, f - 1);
+            for (uint32_t j = a; j < b; j++) {
+                const uint32_t g = base->family_genes[j];
+                if (g >= N || listed[g] || !base->is_node[g] || base->component_of[g] != label || (j > a && g <= base->family_genes[j - 1]))
+                    PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (member %u of family %u)", j - a, f);
+                listed[g] = 1;
+            }
+            of_label[label] = f;
+        }
+        uint32_t g_max = 0;
+        for (uint32_t i = 0; i < N; i++) {
+            g_max = std::max(g_max, genome_of[i]);
+            // a node is listed in a family (its component_of was checked there: a label below N); any other gene is its own component
+            if (base->is_node[i] ? !listed[i] : base->component_of[i] != i)
+                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (gene %u)", i);
+        }
+        if (g_max >= 0x7fffffffu) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: genome id %u (ids below 2^31 - 1)", g_max);
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_ctx::PlaceBufs &b = c->pb;
+        hipStream_t st = c->stream;
+        b.up_comp.alloc((size_t) N * 4); b.up_is_node.alloc(N); b.up_fam_of_label.alloc((size_t) N * 4); b.up_gen.alloc((size_t) N * 4);
+        b.up_fam_off.alloc(((size_t) F + 1) * 4); b.up_fam_genes.alloc((size_t) nodes * 4); b.up_collides.alloc(F);
+        if (N) {
+            PDL_HIP(hipMemcpyAsync(b.up_comp.p, base->component_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
+            PDL_HIP(hipMemcpyAsync(b.up_is_node.p, base->is_node, N, hipMemcpyHostToDevice, st));
+            PDL_HIP(hipMemcpyAsync(b.up_fam_of_label.p, of_label.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
+            PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
+        }
+        PDL_HIP(hipMemcpyAsync(b.up_fam_off.p, base->family_off, ((size_t) F + 1) * 4, hipMemcpyHostToDevice, st));
+        if (nodes) PDL_HIP(hipMemcpyAsync(b.up_fam_genes.p, base->family_genes, (size_t) nodes * 4, hipMemcpyHostToDevice, st));
+        if (F) PDL_HIP(hipMemcpyAsync(b.up_collides.p, base->collides, F, hipMemcpyHostToDevice, st));
+        if (n_edges) {
+            b.up_src.alloc(n_edges * 4); b.up_dst.alloc(n_edges * 4);
+            PDL_HIP(hipMemcpyAsync(b.up_src.p, src, n_edges * 4, hipMemcpyHostToDevice, st));
+            PDL_HIP(hipMemcpyAsync(b.up_dst.p, dst, n_edges * 4, hipMemcpyHostToDevice, st));
+        }
+        PlaceBase B;
+        B.comp = b.up_comp.as<uint32_t>(); B.is_node = b.up_is_node.as<uint8_t>(); B.collides = b.up_collides.as<uint8_t>();
+        B.fam_off = b.up_fam_off.as<uint32_t>(); B.fam_genes = b.up_fam_genes.as<uint32_t>(); B.fam_of_label = b.up_fam_of_label.as<uint32_t>();
+        B.genome_of = b.up_gen.as<uint32_t>(); B.N = N; B.G = N ? g_max + 1 : 0;
+        pdl_place_result r;
+        pdl_run_place_edges(c, B, n_query, b.up_src.as<int32_t>(), b.up_dst.as<int32_t>(), n_edges, r);
+        fill_placement(r, false, out);
+        return PDL_OK;
+    } catch (const pdl_error &e) { c->err = e.msg; pdl_free_placement(out); return e.code;
+    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_placement(out); return PDL_ERR_DEVICE; }
 }
 
 int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {

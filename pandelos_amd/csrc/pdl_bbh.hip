@@ -15,9 +15,18 @@
 #include "pdl_common.h"
 #include "pdl_scan.h"
 
+// Where a cell's row and column sit in the maxima tables.  BbhTasks: the genome tasks of a scored context.  pdl_place.h adds the
+// one task of a query block (BbhQueryBlock); the three kernels below are the filter for both.
+struct BbhTasks {
+    const uint32_t *taskpos_of, *task_lg, *genome_of;
+    __device__ uint32_t pos(uint32_t gene) const { return taskpos_of[gene]; }          // row of MS / thr
+    __device__ uint32_t task(uint32_t p) const { return task_lg[p]; }                  // row of CM / inter_max
+    __device__ uint32_t genome(uint32_t gene) const { return genome_of[gene]; }
+};
+template <class L>
 struct BbhArgs {
     const float *score; const int32_t *row, *col;
-    const uint32_t *taskpos_of, *task_lg, *genome_of;
+    L at;
     const float *MS, *CM;
     uint32_t N, G, Z;
     uint32_t *inter_max;       // [shard][G] float bits, zero-initialised
@@ -25,33 +34,45 @@ struct BbhArgs {
     uint8_t *kind;             // [Z] 0: no edge | 1: best hit in both directions | 2: kept intra-genome cell
 };
 
-__global__ __launch_bounds__(256) void k_bbh_mark(BbhArgs a) {
+template <class L>
+__global__ __launch_bounds__(256) void k_bbh_mark(BbhArgs<L> a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.Z) return;
     const uint32_t r = (uint32_t) a.row[i], c = (uint32_t) a.col[i];
-    const uint32_t p = a.taskpos_of[r], lg = a.task_lg[p];
-    const uint32_t g1 = a.genome_of[r], g2 = a.genome_of[c];
+    const uint32_t p = a.at.pos(r), lg = a.at.task(p);
+    const uint32_t g1 = a.at.genome(r), g2 = a.at.genome(c);
     const float s = a.score[i];
     const bool bbh = g1 != g2 && s == a.MS[(size_t) p * a.G + g2] && s == a.CM[(size_t) lg * a.N + c];
     a.kind[i] = bbh ? 1 : 0;
     if (bbh && s < 1.0f) atomicMax(&a.inter_max[(size_t) lg * a.G + g2], __float_as_uint(s));       // (positive floats order like their bits)
 }
-__global__ __launch_bounds__(256) void k_bbh_threshold(BbhArgs a) {
+template <class L>
+__global__ __launch_bounds__(256) void k_bbh_threshold(BbhArgs<L> a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.Z || a.kind[i] != 1) return;
     const uint32_t r = (uint32_t) a.row[i];
-    const uint32_t p = a.taskpos_of[r], lg = a.task_lg[p];
-    atomicMin(&a.thr[p], a.inter_max[(size_t) lg * a.G + a.genome_of[(uint32_t) a.col[i]]]);
+    const uint32_t p = a.at.pos(r), lg = a.at.task(p);
+    atomicMin(&a.thr[p], a.inter_max[(size_t) lg * a.G + a.at.genome((uint32_t) a.col[i])]);
 }
-__global__ __launch_bounds__(256) void k_bbh_intra(BbhArgs a) {
+template <class L>
+__global__ __launch_bounds__(256) void k_bbh_intra(BbhArgs<L> a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.Z || a.kind[i] == 1) return;
     const uint32_t r = (uint32_t) a.row[i], c = (uint32_t) a.col[i];
-    const uint32_t g = a.genome_of[r];
-    if (g != a.genome_of[c] || r >= c) return;
-    const uint32_t p = a.taskpos_of[r], pc = a.taskpos_of[c];
+    const uint32_t g = a.at.genome(r);
+    if (g != a.at.genome(c) || r >= c) return;
+    const uint32_t p = a.at.pos(r), pc = a.at.pos(c);
     const float s = a.score[i];
     if (s == a.MS[(size_t) p * a.G + g] && s == a.MS[(size_t) pc * a.G + g] && s >= __uint_as_float(a.thr[p])) a.kind[i] = 2;
+}
+// mark, threshold, intra over Z cells (0 < Z < 2^31)
+template <class L>
+static void bbh_filter(hipStream_t st, const BbhArgs<L> &a) {
+    const uint32_t zb = (a.Z + 255) / 256;
+    hipLaunchKernelGGL(k_bbh_mark<L>, dim3(zb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_bbh_threshold<L>, dim3(zb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_bbh_intra<L>, dim3(zb), dim3(256), 0, st, a);
+    PDL_HIP(hipGetLastError());
 }
 
 struct KindFlag {
@@ -94,16 +115,12 @@ void pdl_run_bbh_all(pdl_ctx *c) {
     uint32_t *d_at = pre2 + (Z + 1), *d_pick = d_at + (S + 1);
     PDL_HIP(hipMemsetAsync(inter_max, 0, (size_t) S * G * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_fill_u32, dim3((n_rows + 255) / 256), dim3(256), 0, st, thr, n_rows, 0x7f800000u);
-    BbhArgs a{};
+    BbhArgs<BbhTasks> a{};
     a.score = c->c_score.as<float>(); a.row = c->c_row.as<int32_t>(); a.col = c->c_col.as<int32_t>();
-    a.taskpos_of = c->taskpos_of.as<uint32_t>(); a.task_lg = c->task_lg.as<uint32_t>(); a.genome_of = c->d_gen;
+    a.at = BbhTasks{c->taskpos_of.as<uint32_t>(), c->task_lg.as<uint32_t>(), c->d_gen};
     a.MS = c->MS.as<float>(); a.CM = c->CM.as<float>(); a.N = c->N; a.G = G; a.Z = (uint32_t) Z;
     a.inter_max = inter_max; a.thr = thr; a.kind = c->bbh_kind.as<uint8_t>();
-    const uint32_t zb = (uint32_t) ((Z + 255) / 256);
-    hipLaunchKernelGGL(k_bbh_mark, dim3(zb), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_bbh_threshold, dim3(zb), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_bbh_intra, dim3(zb), dim3(256), 0, st, a);
-    PDL_HIP(hipGetLastError());
+    bbh_filter(st, a);
     // compaction: phase-1 cells (two edges each) and phase-2 cells (one each), both in cell order
     c->e_src.alloc((2 * Z + Z) * sizeof(int32_t)); c->e_dst.alloc((2 * Z + Z) * sizeof(int32_t)); c->e_score.alloc((2 * Z + Z) * sizeof(float));
     int32_t *src1 = c->e_src.as<int32_t>(), *dst1 = c->e_dst.as<int32_t>(); float *sc1 = c->e_score.as<float>();
@@ -166,4 +183,7 @@ void pdl_run_families_of_context(pdl_ctx *c) {
     const uint64_t n[2] = {n1, n2};
     pdl_run_families(c, src, dst, n, true, false, false, c->d_gen, c->N, bit_length64(c->G ? c->G - 1 : 0), c->fam);
     c->fam_valid = true;
+    c->fam_serial++;                   // (K-place's device copy of c->fam is of an earlier run)
 }
+
+#include "pdl_place.h"           // K-place: a query's edges and their placement on these families (pdl_place_query)

@@ -93,6 +93,24 @@ enum : size_t {
     PDL_RM_WORDS = 4 + 128,
 };
 
+// ---- layout of pdl_ctx::pb.ctl (u64 words): K-place (pdl_place.h).  A block of its own: a placement only reads the context, so
+// no word of `scalars` but the sort's SCAN_TOTAL may move.  Cleared at the start of every placement; each word has one life.
+// One reader each on the host (the PinReads of pdl_place.h).  On the device a count is read only where it bounds a later stage's
+// grid instead of a host read in between: INTRA and BASE_EDGES by their sorts, BASE_EDGES / BASE_PAIRS as the d_n of the scans behind
+// them, BASE_PAIRS and GROUPS by k_place_base_off, NODES by k_place_clique.
+enum : size_t {
+    PDL_PL_BAD_EDGES = 0,       // P-check (a caller's list): edges with an id outside [0, N + n) or with both ends below N; read before P-cc
+    PDL_PL_EDGES_1 = 1,         // K-bbh over the query block: phase-1 cells (two edges each) and phase-2 cells, totals of the two
+    PDL_PL_EDGES_2 = 2,         //   edge scans; read together before P-cc
+    PDL_PL_INTRA = 3,           // a caller's list: query-query edges before de-duplication (total of their compaction, the sort's count)
+    PDL_PL_NODES = 4,           // query genes that are a node (stored by the group scan's apply functor); NODES..MEMBERS leave in one read
+    PDL_PL_GROUPS = 5,          // groups: total of the group scan
+    PDL_PL_BASE_EDGES = 6,      // edges with a base end (total of their compaction, the sort's count)
+    PDL_PL_BASE_PAIRS = 7,      // distinct (group, base component) pairs: total of the run-head scan
+    PDL_PL_MEMBERS = 8,         // genes of the base components that groups of two or more of them fuse (total of the member scan)
+    PDL_PL_WORDS = 16,
+};
+
 // ---- layout of pdl_ctx::join_ctr (u32 words): cursors and counters of one scoring pass, cleared by score_join ---------------
 // A tier draws rows through its cursor and lists the rows it hands on; the count of that list is the next tier's work size.
 enum : uint32_t {
@@ -207,6 +225,29 @@ struct pdl_fam_result {
     std::vector<uint32_t> component_of, family_off, family_genes;
     std::vector<uint8_t> is_node, collides;
     float device_ms = 0.f;
+};
+
+// what one run of K-place (pdl_place.h) leaves on the host: pdl_placement without the C allocation
+struct pdl_place_result {
+    uint32_t sequences = 0, n_query = 0, genomes = 0, edges_phase1 = 0, groups = 0;
+    uint32_t novel = 0, joined = 0, bridging = 0, colliding = 0, unplaced = 0;
+    std::vector<int32_t> src, dst;
+    std::vector<float> score;
+    std::vector<uint32_t> family_of, group_label, group_query_off, group_query, group_base_off, group_base;
+    std::vector<uint8_t> is_node, group_collides;
+    float device_ms = 0.f;
+};
+// the base network's families as K-place reads them (device pointers): the context's own, uploaded once from c->fam, or a caller's
+struct PlaceBase {
+    const uint32_t *comp = nullptr, *fam_off = nullptr, *fam_genes = nullptr, *fam_of_label = nullptr, *genome_of = nullptr;
+    const uint8_t *is_node = nullptr, *collides = nullptr;
+    uint32_t N = 0, G = 0;      // G: the query's genome id (every base genome id is below it)
+};
+// what the device half of a single query (pdl_query.h, pdl_run_query_device) leaves: Z cells in c->qb.cells (five arrays of `cap`),
+// the maxima in c->qb.MS / c->qb.CM, `spans` stretches of device work between the event pairs of c->qb.ev
+struct pdl_query_run {
+    uint64_t Z = 0, cap = 1, residues = 0, kmers = 0, records = 0, matched = 0, cost = 0;
+    int spans = 0;
 };
 
 // ---- the context --------------------------------------------------------------------------------
@@ -419,6 +460,29 @@ struct pdl_ctx {
     } fb;
     bool fam_valid = false;
     pdl_fam_result fam;
+    uint64_t fam_serial = 0;          // counts the runs of K-fam over the context's own edges: what pb's copy of c->fam is checked against
+    // K-place (pdl_place.h): the context's own families on the device (uploaded once per K-fam run: fb's buffers are work buffers that
+    // pdl_families_of_edges overwrites), a caller's base, and the work buffers of one placement
+    struct PlaceBufs {
+        DevBuf base_comp, base_is_node, base_collides, base_fam_off, base_fam_genes, base_fam_of_label;     // the context's own
+        uint64_t base_serial = 0;                   // c->fam_serial the copy was made at (0: none)
+        DevBuf up_comp, up_is_node, up_collides, up_fam_off, up_fam_genes, up_fam_of_label, up_gen, up_src, up_dst;   // a caller's base and edges
+        DevBuf ctl;                                 // u64 [PDL_PL_WORDS]
+        DevBuf kind, tab, e_src, e_dst, e_score;    // K-bbh over the query block: as bbh_kind, bbh_tab, e_* of the context
+        DevBuf parent, is_node, same_deg, family_of, gcol, grp_of_label, gq_off, gb_off, group_base, mpre;
+        DevBuf mk_a, mk_b, mv_a, mv_b;              // (root, query gene) sort
+        DevBuf bk_a, bk_b, bv_a, bv_b, uniq;        // (group, base component) keys; then (group, genome) keys of the bridged members
+        DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: query-query (lo, hi) keys
+        hipEvent_t ev[6] = {};                      // start / end of up to three stretches of device work
+        void release() {
+            DevBuf *all[] = {&base_comp, &base_is_node, &base_collides, &base_fam_off, &base_fam_genes, &base_fam_of_label, &up_comp, &up_is_node,
+                             &up_collides, &up_fam_off, &up_fam_genes, &up_fam_of_label, &up_gen, &up_src, &up_dst, &ctl, &kind, &tab, &e_src, &e_dst,
+                             &e_score, &parent, &is_node, &same_deg, &family_of, &gcol, &grp_of_label, &gq_off, &gb_off, &group_base, &mpre, &mk_a,
+                             &mk_b, &mv_a, &mv_b, &bk_a, &bk_b, &bv_a, &bv_b, &uniq, &ek_a, &ek_b, &ev_a, &ev_b};
+            for (DevBuf *b : all) b->release();
+            base_serial = 0;
+        }
+    } pb;
     hipEvent_t app_ev[4] = {};        // pdl_append_genomes: start / end of its two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
@@ -578,6 +642,15 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
+// ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there), and the device
+// time of its stretches (after the stream has been waited for)
+pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n);
+float pdl_query_device_ms(pdl_ctx *c, int spans);
+// K-place (pdl_place.h, pdl_bbh.hip): the query's edges (K-bbh over the query block) and their placement on the context's families;
+// the placement of a caller's edge list (device pointers, union ids) on a base
+void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_place_result &out, pdl_query_info *info);
+void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, const int32_t *d_src, const int32_t *d_dst, uint64_t n_edges,
+                         pdl_place_result &out);
 // K-query for a batch (pdl_query_batch.h): q genomes, each scored on its own; gene_begin [n_queries + 1] cuts the n genes
 void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
                          pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo);
@@ -628,6 +701,19 @@ inline float ev_ms(pdl_ctx *c, int i) {
     if (hipEventElapsedTime(&ms, c->ev[i].a, c->ev[i].b) != hipSuccess) return 0.f;
     return ms;
 }
+
+// device time of a call = the stretches of device work between the host's reads, each between an event pair of `ev` (three at most)
+struct QSpans {
+    hipEvent_t *ev; hipStream_t st; int n = 0;
+    QSpans(hipEvent_t (&e)[6], hipStream_t s) : ev(e), st(s) { for (int i = 0; i < 6; i++) if (!ev[i]) PDL_HIP(hipEventCreate(&ev[i])); }
+    void begin() { PDL_HIP(hipEventRecord(ev[2 * n], st)); }
+    void end() { PDL_HIP(hipEventRecord(ev[2 * n + 1], st)); n++; }
+    float total_ms() const {           // (after the stream has been synchronized)
+        float total = 0.f;
+        for (int i = 0; i < n; i++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) total += ms; }
+        return total;
+    }
+};
 
 static inline uint32_t bit_length64(uint64_t v) {
     uint32_t b = 0;

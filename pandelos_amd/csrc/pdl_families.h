@@ -118,13 +118,13 @@ struct FamIntraApply {
         keys[pre] = (unsigned long long) (a < b ? a : b) << 32 | (a < b ? b : a);
     }
 };
-// ... sorted, and counted once per run of equal keys
-__global__ __launch_bounds__(256) void k_fam_intra_sorted(const unsigned long long *keys, const uint64_t *d_n, uint32_t *same_deg) {
+// ... sorted, and counted once per run of equal keys (same_deg[0] belongs to gene id0: K-place keeps the query genes' only)
+__global__ __launch_bounds__(256) void k_fam_intra_sorted(const unsigned long long *keys, const uint64_t *d_n, uint32_t *same_deg, uint32_t id0) {
     const uint64_t j = (uint64_t) blockIdx.x * 256 + threadIdx.x;
     if (j >= *d_n) return;
     const unsigned long long k = keys[j];
     if (j && keys[j - 1] == k) return;
-    atomicAdd(same_deg + (uint32_t) (k >> 32), 1u); atomicAdd(same_deg + (uint32_t) k, 1u);
+    atomicAdd(same_deg + ((uint32_t) (k >> 32) - id0), 1u); atomicAdd(same_deg + ((uint32_t) k - id0), 1u);
 }
 
 // key2[j] = label of the j-th gene in genome order (the keys of F-collide's second, stable sort)
@@ -240,7 +240,7 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
             scan_and_apply(c, E, FamIntraFlag{src[0], dst[0], d_gen}, FamIntraApply{src[0], dst[0], ek_in}, d_intra);
             uint64_t *k_in = reinterpret_cast<uint64_t *>(ek_in), *k_out = reinterpret_cast<uint64_t *>(ek_out);
             pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, ev_in, ev_out, E, 32 + bit_length64(N - 1), true, d_intra, 0, true);
-            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg);
+            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
         }
     } else if (n_edges[1]) {
         hipLaunchKernelGGL(k_fam_intra, fam_grid(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], d_gen, same_deg);

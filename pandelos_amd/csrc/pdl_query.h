@@ -500,19 +500,6 @@ __global__ __launch_bounds__(256) void k_q_rowids(uint32_t *ids, uint32_t base, 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // What pdl_run_query and the batch's qb_run_chunk (pdl_query_batch.h) both do behind the match.
 
-// device time = the stretches of device work between the host's reads, each between an event pair of `ev` (three at most)
-struct QSpans {
-    hipEvent_t *ev; hipStream_t st; int n = 0;
-    QSpans(hipEvent_t (&e)[6], hipStream_t s) : ev(e), st(s) { for (int i = 0; i < 6; i++) if (!ev[i]) PDL_HIP(hipEventCreate(&ev[i])); }
-    void begin() { PDL_HIP(hipEventRecord(ev[2 * n], st)); }
-    void end() { PDL_HIP(hipEventRecord(ev[2 * n + 1], st)); n++; }
-    float total_ms() const {           // (after the stream has been synchronized)
-        float total = 0.f;
-        for (int i = 0; i < n; i++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) total += ms; }
-        return total;
-    }
-};
-
 // the join's arguments as far as the base and the staging (five arrays of `cap` cells at `stf`) set them; the caller adds its own
 // buffers, the query genes' count and the counters
 static QJoinArgs q_join_args(pdl_ctx *c, float *stf, uint64_t cap) {
@@ -603,7 +590,9 @@ static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
     return v;
 }
 
-void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info) {
+// The device half of a query: every stage up to the ordered cells, which stay where they are (pdl_run_query copies them out,
+// K-place — pdl_place.h — filters them in HBM).
+pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
     hipStream_t st = c->stream;
     auto &q = c->qb;
     const uint32_t N = c->N, G = c->G, G1 = G + 1, k = c->rp.k;
@@ -724,13 +713,30 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     } else {
         spans.end();
     }
+    pdl_query_run run;
+    run.Z = Z; run.cap = std::max<uint64_t>(bound, 1); run.residues = Rq; run.kmers = Mq; run.records = Uq; run.matched = matched; run.cost = cost;
+    run.spans = spans.n;
+    return run;
+}
+float pdl_query_device_ms(pdl_ctx *c, int spans) {           // (after the stream has been synchronized)
+    QSpans s(c->qb.ev, c->stream);
+    s.n = spans;
+    return s.total_ms();
+}
+
+void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info) {
+    hipStream_t st = c->stream;
+    auto &q = c->qb;
+    const uint32_t G1 = c->G + 1, NC = c->N + n;
+    const pdl_query_run run = pdl_run_query_device(c, residues, offsets, n);
+    const uint64_t Z = run.Z;
 
     // Q-copy: straight into the block's arrays
     pdl_scores r{};
     try {
         q_block_alloc(c, r, Z, n);
         if (Z) {
-            const uint64_t cap = std::max<uint64_t>(bound, 1);
+            const uint64_t cap = run.cap;
             const float *cf = q.cells.as<float>();
             void *dst[5] = {r.scores, r.percs, r.tr_percs, r.row, r.column};
             for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(dst[i], cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
@@ -743,7 +749,8 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     *out = r;
     if (info) {
         memset(info, 0, sizeof(*info));
-        info->residues = Rq; info->kmer_occurrences = Mq; info->records = Uq; info->matched_records = matched; info->genome_cost = cost;
-        info->device_ms = spans.total_ms();
+        info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
+        info->genome_cost = run.cost;
+        info->device_ms = pdl_query_device_ms(c, run.spans);
     }
 }

@@ -319,6 +319,69 @@ class PangeneNative:
             self._lib.pdl_free_families(C.byref(f))
         return out
 
+    def place_query(self, residues, offsets) -> dict:
+        """One new genome placed into this context's gene families, without a commit (``pdl_place_query``): the query's edges
+        (``src``, ``dst``, ``score`` in the host's insertion order, ``edges_phase1`` of them phase 1) and, per query gene and per
+        group the query touches, the fields of ``pdl_placement`` as a dict (counts as ints, arrays as numpy).  The context is
+        only read.  ``last_place_info`` holds the counts, the device time and the query's own ``pdl_query_info`` (``query``)."""
+        res = np.ascontiguousarray(residues, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or len(off) < 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n_query + 1 entries")
+        p, info = _lib.PdlPlacement(), _lib.PdlQueryInfo()
+        self._check(self._lib.pdl_place_query(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data, len(off) - 1,
+                                              C.byref(p), C.byref(info)))
+        return self._take_placement(p, True, info.as_dict())
+
+    def place_idata(self, data: PangeneIData) -> dict:
+        """``place_query`` for the genes of a ``PangeneIData`` that holds exactly one genome."""
+        residues, offsets, genome_of = data.flatten()
+        n_genomes = len(np.unique(genome_of))
+        if n_genomes != 1:
+            raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
+        return self.place_query(residues, offsets)
+
+    def placement_of_edges(self, base: dict, genome_of, n_query: int, src, dst) -> dict:
+        """The same kernels over a caller's query edge list in union ids (``pdl_placement_of_edges``): ``base`` is the dict
+        ``generate_families`` / ``families_of_edges`` returned for the N base genes, ``genome_of`` their genomes; the query is
+        ``n_query`` genes N..N+n_query-1 of one further genome.  Needs no preprocess and leaves the context's own state alone."""
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        d = np.ascontiguousarray(dst, dtype=np.int32)
+        g = np.ascontiguousarray(genome_of, dtype=np.uint32)
+        if s.ndim != 1 or s.shape != d.shape or g.ndim != 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "src and dst must be two vectors of one length, genome_of a vector")
+        keep = {f: np.ascontiguousarray(base[f], dtype=t) for f, t in (("component_of", np.uint32), ("is_node", np.uint8), ("family_off", np.uint32),
+                                                                        ("family_genes", np.uint32), ("collides", np.uint8))}
+        if len(keep["component_of"]) != len(g) or len(keep["is_node"]) != len(g) or len(keep["family_off"]) != len(keep["collides"]) + 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "the base families do not describe len(genome_of) genes")
+        fam = _lib.PdlFamilies(sequences=len(g), nodes=len(keep["family_genes"]), families=len(keep["collides"]), colliding=int(keep["collides"].sum()))
+        for f, a in keep.items():
+            setattr(fam, f, a.ctypes.data_as(dict(_lib.PdlFamilies._fields_)[f]))
+        p = _lib.PdlPlacement()
+        self._check(self._lib.pdl_placement_of_edges(self._ctx, C.byref(fam), g.ctypes.data if g.size else None, int(n_query),
+                                                     s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, len(s), C.byref(p)))
+        return self._take_placement(p, False, None)
+
+    def _take_placement(self, p, with_edges, query_info) -> dict:
+        try:
+            n, groups, e = p.n_query, p.groups, p.edges
+            counts = {f: int(getattr(p, f)) for f in ("sequences", "n_query", "genomes", "edges_phase1", "groups", "novel", "joined", "bridging",
+                                                       "colliding", "unplaced")}
+            q_off = _np_copy(p.group_query_off, np.uint32, groups + 1)
+            b_off = _np_copy(p.group_base_off, np.uint32, groups + 1)
+            out = dict(counts)
+            out.update({"family_of": _np_copy(p.family_of, np.uint32, n), "is_node": _np_copy(p.is_node, np.uint8, n),
+                        "group_label": _np_copy(p.group_label, np.uint32, groups), "group_query_off": q_off,
+                        "group_query": _np_copy(p.group_query, np.uint32, int(q_off[-1])), "group_base_off": b_off,
+                        "group_base": _np_copy(p.group_base, np.uint32, int(b_off[-1])), "group_collides": _np_copy(p.group_collides, np.uint8, groups)})
+            if with_edges:
+                out.update({"src": _np_copy(p.src, np.int32, e).astype(np.int64), "dst": _np_copy(p.dst, np.int32, e).astype(np.int64),
+                            "score": _np_copy(p.score, np.float32, e)})
+            self.last_place_info = dict(counts, edges=int(e), device_ms=float(p.device_ms), query=query_info)
+        finally:
+            self._lib.pdl_free_placement(C.byref(p))
+        return out
+
     # -- beyond the reference surface (device-resident batch, sharding, introspection) ------------------
     def score_all(self) -> None:
         self._check(self._lib.pdl_score_all(self._ctx))
