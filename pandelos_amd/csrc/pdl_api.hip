@@ -9,15 +9,72 @@
 
 static thread_local std::string g_create_error = "";
 
-#define PDL_GUARD_BEGIN try {
-#define PDL_GUARD_END(ctx_)                                                       \
-    } catch (const pdl_error &e) {                                                \
-        if (ctx_) (ctx_)->err = e.msg; else g_create_error = e.msg;               \
-        return e.code;                                                            \
-    } catch (const std::bad_alloc &) {                                            \
-        if (ctx_) (ctx_)->err = "host allocation failed";                         \
-        return PDL_ERR_DEVICE;                                                    \
+// The one place where exceptions become return codes: runs an entry point's body (-> its return code); what the body throws is
+// translated and the message stored in the context (pdl_create's when there is none), after `undo` has freed and zeroed the
+// outputs a failure must not leave behind.  The caller holds the context's lock — or, with Lock::take, has let go of it and
+// the message is stored under it.
+enum class Lock { held, take };
+template <class Body, class Undo>
+static int guarded(pdl_ctx *c, Lock lock, Body &&body, Undo &&undo) {
+    int code = PDL_ERR_DEVICE;
+    std::string msg;
+    try { return body(); }
+    catch (const pdl_error &e) { code = e.code; msg = e.msg; }
+    catch (const std::bad_alloc &) { msg = "host allocation failed"; }
+    catch (const std::exception &e) { msg = e.what(); }
+    undo();
+    if (!c) g_create_error = msg;
+    else if (lock == Lock::take) { std::lock_guard<std::mutex> lk(c->mu); c->err = msg; }
+    else c->err = msg;
+    return code;
+}
+template <class Body> static int guarded(pdl_ctx *c, Body &&body) { return guarded(c, Lock::held, body, [] {}); }
+
+// ---- the refusals the incremental entry points share ---------------------------------------------------------------------------
+// What an entry point needs of the context's state; which one needs what:
+//
+//   entry point             built   ranges   single-GPU   no shard   stream held
+//   pdl_query_scores         yes     yes        yes          -           yes
+//   pdl_query_batch          yes     yes        yes          -           yes
+//   pdl_place_query          yes     yes        yes         yes          yes
+//   pdl_append_genomes       yes     yes        yes         yes          yes
+//   pdl_remove_genomes       yes     yes        yes         yes          yes
+//   pdl_compute_families     yes     yes        yes         yes           -
+//
+// (a query under a genome shard is scored against the whole dictionary; the families need the edges, not the stream)
+enum : unsigned {
+    NEEDS_BUILT = 1,         // pdl_preprocess has run
+    NEEDS_RANGES = 2,        // ... and not with only_complexity: the posting ranges exist
+    NEEDS_SINGLE_GPU = 4,    // not a multi-GPU context
+    NEEDS_NO_SHARD = 8,      // no genome shard in force: the context holds every genome's ranges and edges
+    NEEDS_STREAM = 16,       // the sorted k-mer stream is still held (low_memory releases it)
+    NEEDS_QUERY = NEEDS_BUILT | NEEDS_RANGES | NEEDS_SINGLE_GPU | NEEDS_STREAM,
+    NEEDS_WHOLE_SET = NEEDS_QUERY | NEEDS_NO_SHARD,
+};
+// Throws the PDL_ERR_STATE refusal of the first need the context does not meet; nothing of the context has been touched then.
+// `edge_form`: the entry point that does the same over gathered edges, where there is one to point to.
+static void require_state(const pdl_ctx *c, const char *who, unsigned needs, const char *edge_form = nullptr) {
+    if ((needs & NEEDS_BUILT) && !c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "%s before pdl_preprocess", who);
+    if ((needs & NEEDS_RANGES) && c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "%s: the context was preprocessed with only_complexity", who);
+    if ((needs & NEEDS_SINGLE_GPU) && c->dist) {
+        if (edge_form) PDL_FAIL(PDL_ERR_STATE, "%s: not available on a multi-GPU context (gather the edges: %s)", who, edge_form);
+        PDL_FAIL(PDL_ERR_STATE, "%s: not available on a multi-GPU context", who);
     }
+    if ((needs & NEEDS_NO_SHARD) && (c->shard_set || !c->dict_shard.empty())) {
+        if (edge_form) PDL_FAIL(PDL_ERR_STATE, "%s: a genome shard is in force, the context does not hold every genome's edges (gather them: %s)", who, edge_form);
+        PDL_FAIL(PDL_ERR_STATE, "%s: not available with a genome shard in force", who);
+    }
+    if ((needs & NEEDS_STREAM) && (!c->keys_b.p || !c->recpos.p || !c->vals_b.p))
+        PDL_FAIL(PDL_ERR_STATE, "%s: the sorted k-mer stream was released (option low_memory)", who);
+}
+// The argument checks on n new genes (residues, offsets [n + 1]): PDL_ERR_ARGUMENT
+static void check_genes(const char *who, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
+    if (!offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
+    if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: no gene", who);
+    for (uint32_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: offsets decrease at gene %u", who, i);
+    if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL residues", who);
+}
 
 template <class T> static T *xalloc(size_t n) {
     T *p = static_cast<T *>(malloc((n ? n : 1) * sizeof(T)));
@@ -81,13 +138,6 @@ void pdl_destroy(pdl_ctx *c) {
     (void) hipSetDevice(c->device);
     (void) hipStreamSynchronize(c->stream);
     for (auto &e : c->ev) { if (e.a) (void) hipEventDestroy(e.a); if (e.b) (void) hipEventDestroy(e.b); }
-    for (hipEvent_t e : c->qb.ev) if (e) (void) hipEventDestroy(e);
-    for (hipEvent_t e : c->qbb.ev) if (e) (void) hipEventDestroy(e);
-    if (c->qbb.stage) (void) hipHostFree(c->qbb.stage);
-    for (hipEvent_t e : c->app_ev) if (e) (void) hipEventDestroy(e);
-    for (hipEvent_t e : c->rm.ev) if (e) (void) hipEventDestroy(e);
-    for (hipEvent_t e : c->fb.ev) if (e) (void) hipEventDestroy(e);
-    for (hipEvent_t e : c->pb.ev) if (e) (void) hipEventDestroy(e);
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
@@ -100,7 +150,7 @@ void pdl_destroy(pdl_ctx *c) {
     if (c->ev_gen) (void) hipEventDestroy(c->ev_gen);
     for (int i = 0; i < 2; i++) { if (c->ing_pin[i]) (void) hipHostFree(c->ing_pin[i]); if (c->ing_ev[i]) (void) hipEventDestroy(c->ing_ev[i]); }
     if (c->ing_stream) (void) hipStreamDestroy(c->ing_stream);
-    delete c;
+    delete c;                // (the work buffers and the span timers of the entry points go with their members)
 }
 
 const char *pdl_last_error(const pdl_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -167,10 +217,10 @@ void pdl_replace_layout(pdl_ctx *c, std::vector<uint32_t> &&genome_of) {
 }
 
 int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     PDL_HIP(hipSetDevice(c->device));
     c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;      // the genome shard, if one was set, stays in force
-    c->qb.release(); c->qbb.release(); c->pb.release();
+    pdl_renew(c->qb); pdl_renew(c->qbb); pdl_renew(c->pb);
     c->N = n; c->R = n_res;
     c->U = c->Ushared = c->NG = c->P = c->M = 0;
     if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
@@ -181,7 +231,7 @@ int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int onl
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 static int preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
     return pdl_preprocess_common(c, n, n_res, k, only_complexity, out_cost);
@@ -211,7 +261,7 @@ int pdl_preprocess(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
                    uint32_t n, int k, int only_complexity, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    const int rc = guarded(c, [&]() -> int {
     if (!offsets || !genome_of || (!residues && n && offsets[n] > 0)) PDL_FAIL(PDL_ERR_ARGUMENT, "null input pointer");
     PDL_HIP(hipSetDevice(c->device));
     const uint64_t n_res = n ? offsets[n] - offsets[0] : 0;
@@ -223,7 +273,9 @@ int pdl_preprocess(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     c->d_res = c->in_res.as<uint8_t>(); c->d_off = c->in_off.as<uint64_t>(); c->d_gen = c->in_gen.as<uint32_t>();
     c->h_genome_of.assign(genome_of, genome_of + n);
     PDL_HIP(hipStreamSynchronize(c->stream));
-    PDL_GUARD_END(c)
+    return PDL_OK;
+    });
+    if (rc != PDL_OK) return rc;
     return preprocess_common(c, n, n ? offsets[n] : 0, k, only_complexity, out_cost);
 }
 
@@ -231,7 +283,7 @@ int pdl_preprocess_device(pdl_ctx *c, const uint8_t *d_residues, const uint64_t 
                           uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    int rc = guarded(c, [&]() -> int {
     if (!d_offsets || !d_genome_of || (!d_residues && n_res)) PDL_FAIL(PDL_ERR_ARGUMENT, "null input pointer");
     if (((uintptr_t) d_residues & 15) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "d_residues must be 16-byte aligned");
     PDL_HIP(hipSetDevice(c->device));
@@ -265,8 +317,10 @@ int pdl_preprocess_device(pdl_ctx *c, const uint8_t *d_residues, const uint64_t 
         PDL_HIP(hipEventRecord(c->ev_gen, c->copy_stream));
         c->layout_deferred = true;
     }
-    PDL_GUARD_END(c)
-    const int rc = preprocess_common(c, n, n_res, k, only_complexity, out_cost);
+    return PDL_OK;
+    });
+    if (rc != PDL_OK) return rc;
+    rc = preprocess_common(c, n, n_res, k, only_complexity, out_cost);
     c->layout_deferred = false;
     return rc;
 }
@@ -277,14 +331,14 @@ int pdl_genome_cost(const pdl_ctx *cc, uint32_t genome, uint64_t *out) {
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->preprocessed) return PDL_ERR_STATE;
     if (genome >= c->G) return PDL_ERR_ARGUMENT;
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->costs_ready) {                       // (packed ranges: the per-gene / per-genome lookups are made on first request)
         PDL_HIP(hipSetDevice(c->device));
         pdl_ensure_costs(c);
     }
     *out = c->h_genome_cost[genome];
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_sequence_costs(const pdl_ctx *cc, uint64_t *out_cost, uint32_t *out_kseq) {
@@ -292,7 +346,7 @@ int pdl_sequence_costs(const pdl_ctx *cc, uint64_t *out_cost, uint32_t *out_kseq
     if (!c || !out_cost) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->preprocessed) return PDL_ERR_STATE;
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (c->dist && c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "per-gene costs are not kept by a multi-GPU build whose range lists came from the senders (pdl_genome_cost works)");
     PDL_HIP(hipSetDevice(c->device));
     pdl_ensure_costs(c);
@@ -300,7 +354,7 @@ int pdl_sequence_costs(const pdl_ctx *cc, uint64_t *out_cost, uint32_t *out_kseq
     if (out_kseq) PDL_HIP(hipMemcpyAsync(out_kseq, c->kseq_len.p, (size_t) c->N * 4, hipMemcpyDeviceToHost, c->stream));
     PDL_HIP(hipStreamSynchronize(c->stream));
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_set_genome_shard(pdl_ctx *c, const uint32_t *genomes, uint32_t count) {
@@ -336,7 +390,7 @@ int pdl_set_genome_shard(pdl_ctx *c, const uint32_t *genomes, uint32_t count) {
 }
 
 static int score_all_locked(pdl_ctx *c) {
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_score_all before pdl_preprocess");
     if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "the dictionary was built in complexity-only mode (no posting ranges)");
     if (c->scored) return PDL_OK;
@@ -346,7 +400,7 @@ static int score_all_locked(pdl_ctx *c) {
     if (c->reshard_pending) { pdl_run_reshard(c); c->reshard_pending = false; }
     pdl_run_score_all(c);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_score_all(pdl_ctx *c) {
@@ -430,7 +484,7 @@ thread_local ThreadCopier t_copier;
 int pdl_compute_scores(pdl_ctx *c, uint32_t genome, pdl_scores *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    try {
+    return guarded(c, Lock::take, [&]() -> int {
     bool use_mirror = false;
     size_t b_cells = 0, b_ms = 0;
     {
@@ -507,8 +561,7 @@ int pdl_compute_scores(pdl_ctx *c, uint32_t genome, pdl_scores *out) {
     for (uint32_t i = 0; i < N; i++) out->scoresMaxMappings[i] = std::numeric_limits<int32_t>::max();
     for (uint32_t j = 0; j < rows; j++) out->scoresMaxMappings[c->h_genome_rows[c->h_genome_row_off[genome] + j]] = (int32_t) j;
     return PDL_OK;
-    } catch (const pdl_error &e) { { std::lock_guard<std::mutex> lk(c->mu); c->err = e.msg; } pdl_free_scores(out); return e.code;
-    } catch (const std::bad_alloc &) { { std::lock_guard<std::mutex> lk(c->mu); c->err = "host allocation failed"; } pdl_free_scores(out); return PDL_ERR_DEVICE; }
+    }, [&] { pdl_free_scores(out); });
 }
 
 void pdl_free_edges(pdl_edges *e) {
@@ -520,7 +573,7 @@ void pdl_free_edges(pdl_edges *e) {
 int pdl_compute_edges(pdl_ctx *c, uint32_t genome, pdl_edges *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    try {
+    return guarded(c, Lock::take, [&]() -> int {
     {
         std::lock_guard<std::mutex> lk(c->mu);      // the scoring pass / the filter run once; slicing needs no lock
         int rc = c->scored ? PDL_OK : score_all_locked(c);
@@ -548,8 +601,7 @@ int pdl_compute_edges(pdl_ctx *c, uint32_t genome, pdl_edges *out) {
         memcpy(out->src + k1, m2 + a2 * 4, k2 * 4); memcpy(out->dst + k1, m2 + n2 * 4 + a2 * 4, k2 * 4); memcpy(out->score + k1, m2 + n2 * 8 + a2 * 4, k2 * 4);
     }
     return PDL_OK;
-    } catch (const pdl_error &e) { { std::lock_guard<std::mutex> lk(c->mu); c->err = e.msg; } pdl_free_edges(out); return e.code;
-    } catch (const std::bad_alloc &) { { std::lock_guard<std::mutex> lk(c->mu); c->err = "host allocation failed"; } pdl_free_edges(out); return PDL_ERR_DEVICE; }
+    }, [&] { pdl_free_edges(out); });
 }
 
 // ---- K-fam (pdl_families.h) -------------------------------------------------------------------------------------------------
@@ -575,13 +627,8 @@ int pdl_compute_families(pdl_ctx *c, pdl_families *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
     std::lock_guard<std::mutex> lk(c->mu);
-    try {
-        // the refusals first: nothing of the context has been touched when one of them returns
-        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families before pdl_preprocess");
-        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: the context was preprocessed with only_complexity");
-        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: not available on a multi-GPU context (gather the edges: pdl_families_of_edges)");
-        if (c->shard_set || !c->dict_shard.empty())
-            PDL_FAIL(PDL_ERR_STATE, "pdl_compute_families: a genome shard is in force, the context does not hold every genome's edges (gather them: pdl_families_of_edges)");
+    return guarded(c, Lock::held, [&]() -> int {
+        require_state(c, "pdl_compute_families", NEEDS_WHOLE_SET & ~NEEDS_STREAM, "pdl_families_of_edges");
         int rc = c->scored ? PDL_OK : score_all_locked(c);
         if (rc != PDL_OK) return rc;
         PDL_HIP(hipSetDevice(c->device));
@@ -589,8 +636,7 @@ int pdl_compute_families(pdl_ctx *c, pdl_families *out) {
         if (!c->fam_valid) pdl_run_families_of_context(c);
         fill_families(c->fam, out);
         return PDL_OK;
-    } catch (const pdl_error &e) { c->err = e.msg; c->fam_valid = false; pdl_free_families(out); return e.code;
-    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_families(out); return PDL_ERR_DEVICE; }
+    }, [&] { c->fam_valid = false; pdl_free_families(out); });      // (the families are made again by the next call: it costs a run, never an answer)
 }
 
 int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, uint64_t n_edges, const uint32_t *genome_of, uint32_t n_sequences,
@@ -598,7 +644,7 @@ int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, ui
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
     std::lock_guard<std::mutex> lk(c->mu);
-    try {
+    return guarded(c, Lock::held, [&]() -> int {
         if ((n_edges && (!src || !dst)) || (n_sequences && !genome_of)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_families_of_edges: NULL pointer");
         if (n_edges >= 0x7fffffffull || n_sequences >= 0x7fffffffu) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_families_of_edges: 2^31 genes or edges and more");
         PDL_HIP(hipSetDevice(c->device));
@@ -620,8 +666,7 @@ int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, ui
         pdl_run_families(c, s2, d2, n2, false, true, true, b.up_gen.as<uint32_t>(), n_sequences, bit_length64(g_max), r);
         fill_families(r, out);
         return PDL_OK;
-    } catch (const pdl_error &e) { c->err = e.msg; pdl_free_families(out); return e.code;
-    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_families(out); return PDL_ERR_DEVICE; }
+    }, [&] { pdl_free_families(out); });
 }
 
 // ---- K-place (pdl_place.h) ---------------------------------------------------------------------------------------------------
@@ -648,20 +693,10 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     std::lock_guard<std::mutex> lk(c->mu);
     if (out) memset(out, 0, sizeof(*out));
     if (info) memset(info, 0, sizeof(*info));
-    try {
-        // the refusals of pdl_query_scores and of pdl_compute_families first: nothing of the context has been touched when one returns
-        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query before pdl_preprocess");
-        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: the context was preprocessed with only_complexity");
-        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: not available on a multi-GPU context");
-        if (c->shard_set || !c->dict_shard.empty())
-            PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: a genome shard is in force, the context does not hold every genome's edges (gather them: pdl_placement_of_edges)");
-        if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
-            PDL_FAIL(PDL_ERR_STATE, "pdl_place_query: the sorted k-mer stream was released (option low_memory)");
-        if (!out || !offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL pointer");
-        if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: no query gene");
-        for (uint32_t i = 0; i < n_query; i++)
-            if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: offsets decrease at gene %u", i);
-        if (!residues && offsets[n_query] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL residues");
+    return guarded(c, Lock::held, [&]() -> int {
+        require_state(c, "pdl_place_query", NEEDS_WHOLE_SET, "pdl_placement_of_edges");
+        if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL pointer");
+        check_genes("pdl_place_query", residues, offsets, n_query);
         int rc = c->scored ? PDL_OK : score_all_locked(c);
         if (rc != PDL_OK) return rc;
         PDL_HIP(hipSetDevice(c->device));
@@ -673,8 +708,7 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         fill_placement(r, true, out);
         if (info) *info = qi;
         return PDL_OK;
-    } catch (const pdl_error &e) { c->err = e.msg; if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); return e.code;
-    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); return PDL_ERR_DEVICE; }
+    }, [&] { if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); });
 }
 
 int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t *genome_of, uint32_t n_query, const int32_t *src, const int32_t *dst,
@@ -682,7 +716,7 @@ int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t 
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
     std::lock_guard<std::mutex> lk(c->mu);
-    try {
+    return guarded(c, Lock::held, [&]() -> int {
         if (!base || (n_edges && (!src || !dst))) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
         const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
         if (N && (!genome_of || !base->component_of || !base->is_node)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
@@ -743,8 +777,7 @@ int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t 
         pdl_run_place_edges(c, B, n_query, b.up_src.as<int32_t>(), b.up_dst.as<int32_t>(), n_edges, r);
         fill_placement(r, false, out);
         return PDL_OK;
-    } catch (const pdl_error &e) { c->err = e.msg; pdl_free_placement(out); return e.code;
-    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; pdl_free_placement(out); return PDL_ERR_DEVICE; }
+    }, [&] { pdl_free_placement(out); });
 }
 
 int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
@@ -782,7 +815,7 @@ int pdl_dist_preprocess_begin(pdl_ctx *c, const uint8_t *d_residues, const uint6
                               uint32_t n, uint64_t n_res, int k, uint32_t world, uint32_t rank, pdl_dist_slice *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!d_offsets || !d_genome_of || (!d_residues && n_res)) PDL_FAIL(PDL_ERR_ARGUMENT, "null input pointer");
     if (((uintptr_t) d_residues & 15) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "d_residues must be 16-byte aligned");
     if (world == 0 || rank >= world || world > 64) PDL_FAIL(PDL_ERR_ARGUMENT, "rank %u of %u (at most 64 ranks)", rank, world);
@@ -802,13 +835,13 @@ int pdl_dist_preprocess_begin(pdl_ctx *c, const uint8_t *d_residues, const uint6
     out->genome_weights = c->h_run_weights.data(); out->genomes = c->G;
     out->genome_costs = c->h_run_costs.data();
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_dist_preprocess_finish(pdl_ctx *c, void *d_postings_all, uint64_t total_records, const uint64_t *genome_weights, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish without pdl_dist_preprocess_begin");
     if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges built this run's range tuples (and took its group-head bits out): finish with pdl_dist_preprocess_finish_ranges");
     if (!d_postings_all || ((uintptr_t) d_postings_all & 7) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary must be an 8-byte aligned device array");
@@ -820,13 +853,13 @@ int pdl_dist_preprocess_finish(pdl_ctx *c, void *d_postings_all, uint64_t total_
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_dist_preprocess_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t *genome_weights, const uint64_t *genome_costs, pdl_dist_ranges *out) {
     if (!c || !out || !run_records || !genome_weights || !genome_costs) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges without pdl_dist_preprocess_begin");
     PDL_HIP(hipSetDevice(c->device));
     memset(out, 0, sizeof(*out));
@@ -835,14 +868,14 @@ int pdl_dist_preprocess_ranges(pdl_ctx *c, const uint64_t *run_records, const ui
     out->counts = c->h_tuple_counts.data(); out->total = c->dist_out_total;
     out->shared_records = c->dist_run_counters[0]; out->groups = c->dist_run_counters[1]; out->repeat_sample = c->dist_run_counters[2];
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_dist_preprocess_finish_ranges(pdl_ctx *c, void *d_postings_all, uint64_t total_records, uint32_t *d_keys, uint64_t *d_ranges, uint64_t n_tuples,
                                       const uint64_t *counter_sums, pdl_cost *out_cost) {
     if (!c || !counter_sums || ((!d_keys || !d_ranges) && n_tuples)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 1 || !c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish_ranges without a pdl_dist_preprocess_ranges that said \"available\"");
     if (!d_postings_all || ((uintptr_t) d_postings_all & 7) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary must be an 8-byte aligned device array");
     if (n_tuples && ((((uintptr_t) d_keys) & 3) != 0 || (((uintptr_t) d_ranges) & 7) != 0)) PDL_FAIL(PDL_ERR_ARGUMENT, "the received tuples must be aligned device arrays");
@@ -852,7 +885,7 @@ int pdl_dist_preprocess_finish_ranges(pdl_ctx *c, void *d_postings_all, uint64_t
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_dist_genome_owner(const pdl_ctx *c, uint32_t *out) {
@@ -865,7 +898,7 @@ int pdl_dist_genome_owner(const pdl_ctx *c, uint32_t *out) {
 int pdl_dist_score_begin(pdl_ctx *c, pdl_dist_outbox *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage < 2) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_score_begin before pdl_dist_preprocess_finish");
     PDL_HIP(hipSetDevice(c->device));
     c->scored = false; c->mirror_valid = false; c->edges_valid = false; c->dist_stage = 2;
@@ -875,36 +908,36 @@ int pdl_dist_score_begin(pdl_ctx *c, pdl_dist_outbox *out) {
     out->total = 0;
     for (uint64_t v : c->h_outbox_counts) out->total += v;
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_t n_inbox) {
     if (!c || (!d_inbox && n_inbox)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 3) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_score_finish without pdl_dist_score_begin");
     if (n_inbox >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 received cells");
     PDL_HIP(hipSetDevice(c->device));
     pdl_run_dist_score_finish(c, d_inbox, n_inbox);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_copy_device(pdl_ctx *c, void *d_dst, const void *d_src, uint64_t bytes) {
     if (!c || ((!d_dst || !d_src) && bytes)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     PDL_HIP(hipSetDevice(c->device));
     if (bytes) PDL_HIP(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, c->stream));
     PDL_HIP(hipStreamSynchronize(c->stream));
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_get_dictionary(pdl_ctx *c, uint64_t *ranks, uint32_t *seqs, uint32_t *counts) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    PDL_GUARD_BEGIN
+    return guarded(c, [&]() -> int {
     if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary before pdl_preprocess");
     if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary: a multi-GPU context keeps ranks only for its own interval");
     if (!c->keys_b.p || !c->recpos.p) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary: the sorted k-mer stream was released (option low_memory)");
@@ -924,7 +957,7 @@ int pdl_get_dictionary(pdl_ctx *c, uint64_t *ranks, uint32_t *seqs, uint32_t *co
         if (counts) counts[u] = post[u].y & 0x7fffffffu;       // (complexity-only mode leaves the group-head bit in place)
     }
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_scores *out, pdl_query_info *info) {
@@ -932,21 +965,14 @@ int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offset
     std::lock_guard<std::mutex> lk(c->mu);
     if (out) memset(out, 0, sizeof(*out));
     if (info) memset(info, 0, sizeof(*info));
-    PDL_GUARD_BEGIN
-    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores before pdl_preprocess");
-    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: the context was preprocessed with only_complexity");
-    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: not available on a multi-GPU context");
-    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
-        PDL_FAIL(PDL_ERR_STATE, "pdl_query_scores: the sorted k-mer stream was released (option low_memory)");
-    if (!out || !offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL pointer");
-    if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: no query gene");
-    for (uint32_t i = 0; i < n_query; i++)
-        if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: offsets decrease at gene %u", i);
-    if (!residues && offsets[n_query] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL residues");
+    return guarded(c, [&]() -> int {
+    require_state(c, "pdl_query_scores", NEEDS_QUERY);
+    if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL pointer");
+    check_genes("pdl_query_scores", residues, offsets, n_query);
     PDL_HIP(hipSetDevice(c->device));
     pdl_run_query(c, residues, offsets, n_query, out, info);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
@@ -956,12 +982,8 @@ int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     if (out && n_queries) memset(out, 0, sizeof(*out) * (size_t) n_queries);
     if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
     if (binfo) memset(binfo, 0, sizeof(*binfo));
-    try {
-        if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch before pdl_preprocess");
-        if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: the context was preprocessed with only_complexity");
-        if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: not available on a multi-GPU context");
-        if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
-            PDL_FAIL(PDL_ERR_STATE, "pdl_query_batch: the sorted k-mer stream was released (option low_memory)");
+    return guarded(c, Lock::held, [&]() -> int {
+        require_state(c, "pdl_query_batch", NEEDS_QUERY);
         if (n_queries == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query");
         if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query gene");
         if (!out || !offsets || !gene_begin) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: NULL pointer");
@@ -975,22 +997,15 @@ int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
             const uint64_t nc = (uint64_t) c->N + (gene_begin[q + 1] - gene_begin[q]);
             if (nc >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu genes in the union exceed the 31-bit gene ids", q, (unsigned long long) nc);
         }
-        for (uint32_t i = 0; i < n; i++)
-            if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: offsets decrease at gene %u", i);
-        if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: NULL residues");
+        check_genes("pdl_query_batch", residues, offsets, n);
         PDL_HIP(hipSetDevice(c->device));
         pdl_run_query_batch(c, residues, offsets, gene_begin, n, n_queries, out, info, binfo);
         return PDL_OK;
-    } catch (...) {
-        // a refusal returns no block: what earlier chunks produced goes back, `out` is zero again
+    }, [&] {     // a refusal returns no block: what earlier chunks produced goes back, `out` is zero again
         if (out) for (uint32_t q = 0; q < n_queries; q++) pdl_free_scores(&out[q]);
         if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
         if (binfo) memset(binfo, 0, sizeof(*binfo));
-        try { throw; }
-        catch (const pdl_error &e) { c->err = e.msg; return e.code; }
-        catch (const std::bad_alloc &) { c->err = "host allocation failed"; return PDL_ERR_DEVICE; }
-        catch (const std::exception &e) { c->err = e.what(); return PDL_ERR_DEVICE; }
-    }
+    });
 }
 
 int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_of, uint32_t n, pdl_cost *out_cost,
@@ -998,18 +1013,9 @@ int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offs
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     if (info) memset(info, 0, sizeof(*info));
-    PDL_GUARD_BEGIN
-    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes before pdl_preprocess");
-    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: the context was preprocessed with only_complexity");
-    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: not available on a multi-GPU context");
-    if (c->shard_set || !c->dict_shard.empty()) PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: not available with a genome shard in force");
-    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
-        PDL_FAIL(PDL_ERR_STATE, "pdl_append_genomes: the sorted k-mer stream was released (option low_memory)");
-    if (!offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: NULL pointer");
-    if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: no gene");
-    for (uint32_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: offsets decrease at gene %u", i);
-    if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_append_genomes: NULL residues");
+    return guarded(c, [&]() -> int {
+    require_state(c, "pdl_append_genomes", NEEDS_WHOLE_SET);
+    check_genes("pdl_append_genomes", residues, offsets, n);
     // union genome ids: G, G+1, ... in first-seen order (PangeneIData.java:56-62 continued)
     std::vector<uint32_t> ids(n, c->G);
     uint32_t g_new = 1;
@@ -1028,20 +1034,15 @@ int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offs
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_remove_genomes(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_cost *out_cost, pdl_remove_info *info) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     if (info) memset(info, 0, sizeof(*info));
-    PDL_GUARD_BEGIN
-    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes before pdl_preprocess");
-    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: the context was preprocessed with only_complexity");
-    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: not available on a multi-GPU context");
-    if (c->shard_set || !c->dict_shard.empty()) PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: not available with a genome shard in force");
-    if (!c->keys_b.p || !c->recpos.p || !c->vals_b.p)
-        PDL_FAIL(PDL_ERR_STATE, "pdl_remove_genomes: the sorted k-mer stream was released (option low_memory)");
+    return guarded(c, [&]() -> int {
+    require_state(c, "pdl_remove_genomes", NEEDS_WHOLE_SET);
     if (!genomes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: NULL pointer");
     if (count == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: no genome");
     std::vector<uint8_t> named((size_t) c->G, 0);
@@ -1057,7 +1058,7 @@ int pdl_remove_genomes(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_
     c->preprocessed = true;
     fill_cost(c, out_cost);
     return PDL_OK;
-    PDL_GUARD_END(c)
+    });
 }
 
 int pdl_get_rank_table(const pdl_ctx *c, uint8_t out[256], uint64_t *out_lm) {

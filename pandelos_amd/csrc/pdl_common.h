@@ -7,10 +7,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
 #include <cstdlib>
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -191,6 +193,7 @@ struct DevBuf {
         p = q;
         bytes = n;
     }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(bytes, o.bytes); }
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
@@ -219,6 +222,27 @@ struct EventPair {
     bool used = false;
 };
 
+// device time of a call = its stretches of device work between the host's reads, each between a pair of events (N at most).
+// The timer owns its events: made at the first start(), destroyed with the struct that holds it.
+template <int N> struct EventSpans {
+    hipEvent_t ev[2 * N] = {};
+    hipStream_t st = nullptr;
+    int n = 0;
+    void start(hipStream_t s) { st = s; n = 0; for (hipEvent_t &e : ev) if (!e) PDL_HIP(hipEventCreate(&e)); }
+    void begin() { PDL_HIP(hipEventRecord(ev[2 * n], st)); }
+    void end() { PDL_HIP(hipEventRecord(ev[2 * n + 1], st)); n++; }
+    float ms(int i) const { float v = 0.f; return i < n && hipEventElapsedTime(&v, ev[2 * i], ev[2 * i + 1]) == hipSuccess ? v : 0.f; }     // (after the stream has been synchronized)
+    float total_ms() const { float total = 0.f; for (int i = 0; i < n; i++) total += ms(i); return total; }
+    EventSpans() = default;
+    EventSpans(const EventSpans &) = delete;
+    EventSpans &operator=(const EventSpans &) = delete;
+    ~EventSpans() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
+};
+using QSpans = EventSpans<3>;
+// Everything a struct of work buffers holds goes back and its bookkeeping starts again: the members release themselves, so a
+// member added to the struct is released without being named anywhere else.
+template <class T> inline void pdl_renew(T &x) { x.~T(); new (&x) T(); }
+
 // what one run of K-fam (pdl_families.h) leaves on the host: pdl_families without the C allocation
 struct pdl_fam_result {
     uint32_t sequences = 0, nodes = 0, families = 0, colliding = 0;
@@ -244,10 +268,9 @@ struct PlaceBase {
     uint32_t N = 0, G = 0;      // G: the query's genome id (every base genome id is below it)
 };
 // what the device half of a single query (pdl_query.h, pdl_run_query_device) leaves: Z cells in c->qb.cells (five arrays of `cap`),
-// the maxima in c->qb.MS / c->qb.CM, `spans` stretches of device work between the event pairs of c->qb.ev
+// the maxima in c->qb.MS / c->qb.CM, the stretches of device work in c->qb.spans
 struct pdl_query_run {
     uint64_t Z = 0, cap = 1, residues = 0, kmers = 0, records = 0, matched = 0, cost = 0;
-    int spans = 0;
 };
 
 // ---- the context --------------------------------------------------------------------------------
@@ -424,28 +447,16 @@ struct pdl_ctx {
         bool hbm_clean = false;                      // hbm holds hbm_slots tables laid out for hbm_cols columns, in their clean state
         uint32_t hbm_cols = 0, hbm_slots = 0;
         const uint32_t *rec_sorted_at = nullptr;     // (inside rec_sorted: the half the gene sort left its output in)
-        hipEvent_t ev[6] = {};                       // start / end of up to three stretches of device work
-        void release() {
-            DevBuf *all[] = {&res, &off, &koff, &kseq, &keys_a, &keys_b, &vals_a, &vals_b, &recpos, &post, &desc, &gkey, &rec_sorted,
-                             &row_lookups, &row_off, &fold, &ctl, &MS, &CM, &row_base, &row_cnt, &fin_off, &rowid, &overflow, &st, &cells, &hbm};
-            for (DevBuf *b : all) b->release();
-            hbm_clean = false; hbm_cols = hbm_slots = 0; rec_sorted_at = nullptr;
-        }
+        QSpans spans;                                // up to three stretches of device work
     } qb;
     // pdl_query_batch (pdl_query_batch.h): the buffers of one chunk of queries, reused across chunks and calls, released with qb's
     // (the HBM tables of the join's last tier and their bookkeeping are qb's: a batch and a single query find each other's clean)
     struct QueryBatchBufs {
         DevBuf res, off, koff, kseq, gene_begin, res_begin, gene_query, keys_a, keys_b, vals_a, vals_b, recpos, post, qkey, perm, srank, spost,
                seg_off, folds, desc, gkey, rec_sorted, row_lookups, row_off, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells;
-        hipEvent_t ev[6] = {};                       // start / end of up to three stretches of device work per chunk
+        QSpans spans;                                // up to three stretches of device work per chunk
         uint8_t *stage = nullptr; size_t stage_bytes = 0;     // pinned host staging of a chunk's cells and maxima (the blocks are cut out of it)
-        void release() {
-            if (stage) { (void) hipHostFree(stage); stage = nullptr; stage_bytes = 0; }
-            DevBuf *all[] = {&res, &off, &koff, &kseq, &gene_begin, &res_begin, &gene_query, &keys_a, &keys_b, &vals_a, &vals_b, &recpos, &post, &qkey,
-                             &perm, &srank, &spost, &seg_off, &folds, &desc, &gkey, &rec_sorted, &row_lookups, &row_off, &ctl, &MS, &CM, &row_base,
-                             &row_cnt, &fin_off, &rowid, &overflow, &st, &cells};
-            for (DevBuf *b : all) b->release();
-        }
+        ~QueryBatchBufs() { if (stage) (void) hipHostFree(stage); }
     } qbb;
     uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
     // K-fam (pdl_families.h): work buffers of a run (grown as needed, shared by pdl_compute_families and pdl_families_of_edges) and
@@ -456,7 +467,7 @@ struct pdl_ctx {
         DevBuf ck_a, ck_b, cv_a, cv_b;              // F-collide: by genome, then by label
         DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: intra-genome (lo, hi) keys and the sort's unused values
         DevBuf up_src, up_dst, up_gen;              // a caller's edges and genome ids on the device
-        hipEvent_t ev[4] = {};                      // start / end of the id check and of the rest
+        EventSpans<2> spans;                        // the id check and the rest (one stretch when nothing is checked)
     } fb;
     bool fam_valid = false;
     pdl_fam_result fam;
@@ -473,17 +484,9 @@ struct pdl_ctx {
         DevBuf mk_a, mk_b, mv_a, mv_b;              // (root, query gene) sort
         DevBuf bk_a, bk_b, bv_a, bv_b, uniq;        // (group, base component) keys; then (group, genome) keys of the bridged members
         DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: query-query (lo, hi) keys
-        hipEvent_t ev[6] = {};                      // start / end of up to three stretches of device work
-        void release() {
-            DevBuf *all[] = {&base_comp, &base_is_node, &base_collides, &base_fam_off, &base_fam_genes, &base_fam_of_label, &up_comp, &up_is_node,
-                             &up_collides, &up_fam_off, &up_fam_genes, &up_fam_of_label, &up_gen, &up_src, &up_dst, &ctl, &kind, &tab, &e_src, &e_dst,
-                             &e_score, &parent, &is_node, &same_deg, &family_of, &gcol, &grp_of_label, &gq_off, &gb_off, &group_base, &mpre, &mk_a,
-                             &mk_b, &mv_a, &mv_b, &bk_a, &bk_b, &bv_a, &bv_b, &uniq, &ek_a, &ek_b, &ev_a, &ev_b};
-            for (DevBuf *b : all) b->release();
-            base_serial = 0;
-        }
+        QSpans spans;                               // up to three stretches of device work
     } pb;
-    hipEvent_t app_ev[4] = {};        // pdl_append_genomes: start / end of its two stretches of device work
+    EventSpans<2> app_spans;          // pdl_append_genomes: its two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
         DevBuf gmap;                  // u32 [G] new genome id, RM_GONE for a genome that leaves
@@ -492,7 +495,7 @@ struct pdl_ctx {
         DevBuf kseq, gen, glen;       // u32 [N'] compacted kseq_len / genome ids / gene_len: they swap places with the context's
         DevBuf tile;                  // u32 [tiles] k-mers that stay per tile of the stream, then their exclusive scan
         DevBuf ctl;                   // u64 [PDL_RM_WORDS]
-        hipEvent_t ev[4] = {};        // start / end of its two stretches of device work
+        EventSpans<2> spans;          // its two stretches of device work
     } rm;
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
 
@@ -642,10 +645,9 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
-// ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there), and the device
-// time of its stretches (after the stream has been waited for)
+// ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there); the device time
+// of its stretches is c->qb.spans.total_ms() once the stream has been waited for
 pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n);
-float pdl_query_device_ms(pdl_ctx *c, int spans);
 // K-place (pdl_place.h, pdl_bbh.hip): the query's edges (K-bbh over the query block) and their placement on the context's families;
 // the placement of a caller's edge list (device pointers, union ids) on a base
 void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_place_result &out, pdl_query_info *info);
@@ -702,16 +704,34 @@ inline float ev_ms(pdl_ctx *c, int i) {
     return ms;
 }
 
-// device time of a call = the stretches of device work between the host's reads, each between an event pair of `ev` (three at most)
-struct QSpans {
-    hipEvent_t *ev; hipStream_t st; int n = 0;
-    QSpans(hipEvent_t (&e)[6], hipStream_t s) : ev(e), st(s) { for (int i = 0; i < 6; i++) if (!ev[i]) PDL_HIP(hipEventCreate(&ev[i])); }
-    void begin() { PDL_HIP(hipEventRecord(ev[2 * n], st)); }
-    void end() { PDL_HIP(hipEventRecord(ev[2 * n + 1], st)); n++; }
-    float total_ms() const {           // (after the stream has been synchronized)
-        float total = 0.f;
-        for (int i = 0; i < n; i++) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) total += ms; }
-        return total;
+// Genes that are not the context's input (a query, an append), as the host lays them out for K-rank from the caller's offsets:
+// residues from 0, k-mer offsets, k-mer counts.  The limits on R and M are the caller's (a query's differ from an append's).
+struct NewGenes {
+    std::vector<uint64_t> off, koff;        // [n + 1] residue / k-mer offset of every gene
+    std::vector<uint32_t> kseq, len;        // [n] k-mers / residues of every gene (a gene of 2^32 residues and more: 0xffffffff; the callers' limits exclude it)
+    uint64_t r0 = 0, R = 0, M = 0;          // the caller's first residue; residues; k-mers
+    NewGenes(const uint64_t *offsets, uint32_t n, uint32_t k) : off(n + 1), koff(n + 1), kseq(n), len(n) {
+        r0 = offsets[0]; R = offsets[n] - r0;
+        for (uint32_t g = 0; g < n; g++) {
+            const uint64_t l = offsets[g + 1] - offsets[g];
+            len[g] = (uint32_t) std::min<uint64_t>(l, 0xffffffffull);
+            off[g] = offsets[g] - r0;
+            koff[g] = M;
+            kseq[g] = l >= k ? (uint32_t) std::min<uint64_t>(l - k + 1, 0xffffffffull) : 0u;
+            M += kseq[g];
+        }
+        off[n] = R; koff[n] = M;
+    }
+    // ... on their way into c->qb (res with 16 bytes of slack, off, koff, kseq), queued on the context's stream
+    void upload(pdl_ctx *c, const uint8_t *residues) const {
+        auto &q = c->qb;
+        hipStream_t st = c->stream;
+        const size_t n = kseq.size();
+        q.res.alloc(R + 16); q.off.alloc((n + 1) * 8); q.koff.alloc((n + 1) * 8); q.kseq.alloc(n * 4);
+        if (R) PDL_HIP(hipMemcpyAsync(q.res.p, residues + r0, R, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(q.off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(q.koff.p, koff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(q.kseq.p, kseq.data(), n * 4, hipMemcpyHostToDevice, st));
     }
 };
 

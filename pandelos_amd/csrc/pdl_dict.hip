@@ -569,8 +569,8 @@ static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint
     pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
     ev_end(c, EV_SORT1);
     // remember which physical buffers hold the sorted stream (pdl_get_dictionary reads them)
-    if ((void *) keys_out != c->keys_b.p) { std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes); }
-    if ((void *) vals_out != c->vals_b.p) { std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes); }
+    if ((void *) keys_out != c->keys_b.p) c->keys_a.swap(c->keys_b);
+    if ((void *) vals_out != c->vals_b.p) c->vals_a.swap(c->vals_b);
     stage_dedup<KeyT>(c, m);
 }
 
@@ -793,6 +793,13 @@ void pdl_ensure_costs(pdl_ctx *c) {
     c->costs_ready = true;
 }
 
+// option low_memory, behind a build (the stream has been waited for): what only the build needed goes back — the sorted k-mer
+// stream with it, so pdl_get_dictionary and the incremental entry points are not available then.  Packed ranges live in
+// `scratch`: it stays.
+static void release_build_buffers(pdl_ctx *c) {
+    c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
+}
+
 template <class KeyT>
 static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
     const uint64_t M = c->M;
@@ -808,11 +815,45 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
     // U (records) and the range count stay on the device until the end of the build: everything below is sized and
     // launched for the bound M and reads the counts there — no host round trip in the middle of the pipeline
     stage_ranges_and_costs(c, M, c->dict_shard.empty() ? 1 : 0, only_complexity);
-    if (c->opt_low_memory) {                 // what only the build needed goes back (the sorted k-mer stream with it: pdl_get_dictionary is not available then)
+    if (c->opt_low_memory) {
         PDL_HIP(hipStreamSynchronize(c->stream));
-        c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
-        if (c->ranges8 == nullptr) {}        // (packed ranges live in `scratch`: it stays)
+        release_build_buffers(c);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// What the incremental rebuilds (K-append, K-remove) share.  Both leave a sorted stream of the new set in (keys_b, vals_b) and
+// then run the build's own stages on it; the next entry point that changes the set does the same through these two.
+// ------------------------------------------------------------------------------------------------
+// "From here on the context changes": whatever was derived from the old set is stale, and a failure leaves the context
+// un-preprocessed.  (The families would go with the edges anyway: pdl_run_bbh_all drops them before anyone reads them.)
+static void context_changes(pdl_ctx *c) {
+    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
+    c->mirror_valid = false; c->edges_valid = false; c->fam_valid = false;
+}
+
+// The tail behind the sort, for a set of N1 genes in G1 genomes (the layout of the host is the new one already) whose k-mers
+// are M1 sorted entries: control block and costs cleared for the new sizes, then — behind `queue_stream`, which queues
+// whatever still has to bring the stream into (keys_b, vals_b) — K-rle, the task layout, K-groups / K-ranges / K-cost.  The
+// device work is the caller's last span; the stream has been waited for on return, and low_memory has taken its buffers.
+template <class QueueStream>
+static void rebuild_behind_sort(pdl_ctx *c, EventSpans<2> &spans, uint64_t M1, uint32_t N1, uint32_t G1, QueueStream &&queue_stream) {
+    hipStream_t st = c->stream;
+    const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
+    c->scalars.alloc(ctl_words * sizeof(uint64_t));
+    c->cost.alloc((size_t) N1 * sizeof(uint64_t));
+    spans.begin();
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, c->scalars.as<uint64_t>(), ctl_words);
+    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
+    PDL_HIP(hipGetLastError());
+    queue_stream();
+    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
+    ev_end(c, EV_DICT);
+    pdl_prepare_tasks(c);
+    stage_ranges_and_costs(c, M1, 1, false);
+    spans.end();
+    PDL_HIP(hipStreamSynchronize(st));
+    if (c->opt_low_memory) release_build_buffers(c);
 }
 
 // K-rank of genes that are not the context's input (a query, an append) with the context's rank parameters: gene values 0..n-1
@@ -879,46 +920,32 @@ static void append_sorted_stream(pdl_ctx *c, uint32_t n, uint64_t m, uint64_t n_
     pdl_merge_streams<KeyT>(c->stream, c->keys_b.as<KeyT>(), c->vals_b.as<uint32_t>(), (uint32_t) m_base, k_out, v_out, (uint32_t) m, n_base, mask,
                             c->scan_tmp.as<uint32_t>(), c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>());
     ev_end(c, EV_MERGE);
-    std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes);      // the sorted stream is what keys_b / vals_b name
-    std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes);
+    c->keys_a.swap(c->keys_b); c->vals_a.swap(c->vals_b);      // the sorted stream is what keys_b / vals_b name
 }
 
 void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_ids, uint32_t n, uint32_t n_new_genomes,
                     pdl_append_info *info) {
     hipStream_t st = c->stream;
     auto &q = c->qb;
-    const uint32_t N0 = c->N, G0 = c->G, k = c->rp.k;
+    const uint32_t N0 = c->N, G0 = c->G;
     const uint64_t M0 = c->M, U0 = c->U;
     if ((uint64_t) N0 + n >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu genes in the union exceed the 31-bit gene ids", (unsigned long long) N0 + n);
-    const uint64_t r0 = offsets[0], Rq = offsets[n] - r0;
+    const uint64_t Rq = offsets[n] - offsets[0];
     if (c->R + Rq >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the union need 64-bit stream positions");
-    std::vector<uint64_t> h_off(n + 1), h_koff(n + 1);
-    std::vector<uint32_t> h_kseq(n), h_glen(n);
-    uint64_t m = 0;
-    for (uint32_t g = 0; g < n; g++) {
-        const uint64_t len = offsets[g + 1] - offsets[g];
-        h_glen[g] = (uint32_t) len;
-        h_off[g] = offsets[g] - r0;
-        h_koff[g] = m;
-        h_kseq[g] = len >= k ? (uint32_t) (len - k + 1) : 0u;        // (len < 2^32: checked above)
-        m += h_kseq[g];
-    }
-    h_off[n] = Rq; h_koff[n] = m;
+    const NewGenes genes(offsets, n, c->rp.k);
+    const uint64_t m = genes.M;
     if (M0 + m >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu k-mers in the union need 64-bit stream positions", (unsigned long long) (M0 + m));
-    for (hipEvent_t &e : c->app_ev) if (!e) PDL_HIP(hipEventCreate(&e));
+    EventSpans<2> &spans = c->app_spans;
+    spans.start(st);
 
     // A-alpha (and the new genes on their way to the device): the context is only read
-    PDL_HIP(hipEventRecord(c->app_ev[0], st));
+    spans.begin();
     q.ctl.alloc(16 * sizeof(uint64_t));
     unsigned long long *d_bad = q.ctl.as<unsigned long long>();
     PDL_HIP(hipMemsetAsync(d_bad, 0, sizeof(uint64_t), st));
-    q.res.alloc(Rq + 16); q.off.alloc((n + 1) * 8ull); q.koff.alloc((n + 1) * 8ull); q.kseq.alloc(n * 4ull);
-    if (Rq) PDL_HIP(hipMemcpyAsync(q.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.off.p, h_off.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.koff.p, h_koff.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
+    genes.upload(c, residues);
     pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, d_bad);
-    PDL_HIP(hipEventRecord(c->app_ev[1], st));
+    spans.end();
     {
         PinRead rd(c);
         const uint64_t *pb = rd.add<uint64_t>(d_bad, 1);
@@ -926,16 +953,13 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         if (pb[0]) pdl_fail_absent_byte(pb[0], "appended");
     }
 
-    // from here on the context changes; a failure leaves it un-preprocessed
-    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
-    c->mirror_valid = false; c->edges_valid = false;
+    context_changes(c);
     const uint32_t N1 = N0 + n, G1 = G0 + n_new_genomes;
     const uint64_t M1 = M0 + m;
     const size_t kb = c->key64 ? 8 : 4;
     // A-len: the per-gene arrays grow (k-mer counts keep their contents), the genome ids move into the context's own buffer
     c->kseq_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
     c->gene_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
-    c->cost.alloc((size_t) N1 * sizeof(uint64_t));
     const bool ids_on_device = c->d_gen && (c->d_gen == c->in_gen.p || c->d_gen == c->ing_gen.p);     // (a caller's buffer may be gone: the host copy serves)
     const bool ids_owned = c->d_gen && c->d_gen == c->own_gen.p;
     if (ids_owned) c->own_gen.grow_keep((size_t) N1 * sizeof(uint32_t), st); else c->own_gen.alloc((size_t) N1 * sizeof(uint32_t));
@@ -943,46 +967,29 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     pdl_extend_layout(c, genome_ids, n);                  // N, G, h_genome_of, genome rows
     c->M = M1; c->R += Rq;
     c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
-    const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
-    c->scalars.alloc(ctl_words * sizeof(uint64_t));
     if (m) {
         c->keys_a.alloc(M1 * kb); c->vals_a.alloc(M1 * sizeof(uint32_t));
         q.keys_a.alloc(m * kb); q.keys_b.alloc(m * kb); q.vals_a.alloc(m * 4); q.vals_b.alloc(m * 4);
         c->scan_tmp.alloc(pdl_merge_split_words(M1) * sizeof(uint32_t));
     }
-
-    PDL_HIP(hipEventRecord(c->app_ev[2], st));
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);
-    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
-    PDL_HIP(hipGetLastError());
-    PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
-    PDL_HIP(hipMemcpyAsync(c->gene_len.as<uint32_t>() + N0, h_glen.data(), n * 4ull, hipMemcpyHostToDevice, st));
-    if (ids_owned) {
-        PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
-    } else if (ids_on_device) {
-        PDL_HIP(hipMemcpyAsync(c->own_gen.p, old_gen, (size_t) N0 * 4, hipMemcpyDeviceToDevice, st));
-        PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
-    } else {
-        PDL_HIP(hipMemcpyAsync(c->own_gen.p, c->h_genome_of.data(), (size_t) N1 * 4, hipMemcpyHostToDevice, st));
-    }
     c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
-    if (m) {
-        if (c->key64) append_sorted_stream<uint64_t>(c, n, m, Rq, N0, M0);
-        else append_sorted_stream<uint32_t>(c, n, m, Rq, N0, M0);
-    }
-    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
-    ev_end(c, EV_DICT);
-    pdl_prepare_tasks(c);
-    stage_ranges_and_costs(c, M1, 1, false);
-    PDL_HIP(hipEventRecord(c->app_ev[3], st));
-    PDL_HIP(hipStreamSynchronize(st));
-    if (c->opt_low_memory) {                  // as a build does: what only the build needed goes back
-        c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
-    }
-    float ms0 = 0.f, ms1 = 0.f;
-    (void) hipEventElapsedTime(&ms0, c->app_ev[0], c->app_ev[1]);
-    (void) hipEventElapsedTime(&ms1, c->app_ev[2], c->app_ev[3]);
+    rebuild_behind_sort(c, spans, M1, N1, G1, [&] {        // (behind the clearing, as ever: the new genes' tails of the per-gene arrays, A-dict, A-merge)
+        PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
+        PDL_HIP(hipMemcpyAsync(c->gene_len.as<uint32_t>() + N0, genes.len.data(), n * 4ull, hipMemcpyHostToDevice, st));
+        if (ids_owned) {
+            PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
+        } else if (ids_on_device) {
+            PDL_HIP(hipMemcpyAsync(c->own_gen.p, old_gen, (size_t) N0 * 4, hipMemcpyDeviceToDevice, st));
+            PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
+        } else {
+            PDL_HIP(hipMemcpyAsync(c->own_gen.p, c->h_genome_of.data(), (size_t) N1 * 4, hipMemcpyHostToDevice, st));
+        }
+        if (m) {
+            if (c->key64) append_sorted_stream<uint64_t>(c, n, m, Rq, N0, M0);
+            else append_sorted_stream<uint32_t>(c, n, m, Rq, N0, M0);
+        }
+    });
+    const float ms0 = spans.ms(0), ms1 = spans.ms(1);
     const float rank_ms = ev_ms(c, EV_RANK), sort_ms = ev_ms(c, EV_SORT1), merge_ms = ev_ms(c, EV_MERGE);
     pdl_timings t{};                          // the preprocess fields describe the append, the scoring fields start again
     t.rank_ms = rank_ms; t.sort_rank_ms = sort_ms + merge_ms; t.dict_ms = ev_ms(c, EV_DICT);
@@ -1036,10 +1043,10 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
     std::vector<uint32_t> gmap((size_t) G0, 0u);
     for (uint32_t i = 0; i < count; i++) gmap[genomes[i]] = RM_GONE;
     for (uint32_t g = 0, next = 0; g < G0; g++) if (gmap[g] != RM_GONE) gmap[g] = next++;
-    for (hipEvent_t &e : r.ev) if (!e) PDL_HIP(hipEventCreate(&e));
+    r.spans.start(st);
 
     // R-map, R-compact, R-alpha: the context is only read
-    PDL_HIP(hipEventRecord(r.ev[0], st));
+    r.spans.begin();
     r.ctl.alloc(PDL_RM_WORDS * sizeof(uint64_t));
     uint64_t *d_ctl = r.ctl.as<uint64_t>();
     hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, st, d_ctl, (size_t) PDL_RM_WORDS);
@@ -1061,7 +1068,7 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
                    d_ctl + PDL_RM_GENES);
     if (c->key64) remove_from_stream<uint64_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
     else remove_from_stream<uint32_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
-    PDL_HIP(hipEventRecord(r.ev[1], st));
+    r.spans.end();
     // the host's side of it while the device works: the genome ids of the genes that stay
     std::vector<uint32_t> genome_of;
     genome_of.reserve(N0);
@@ -1089,39 +1096,16 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
         }
     }
 
-    // from here on the context changes; a failure leaves it un-preprocessed
-    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
-    c->mirror_valid = false; c->edges_valid = false; c->fam_valid = false;
-    std::swap(c->keys_a.p, c->keys_b.p); std::swap(c->keys_a.bytes, c->keys_b.bytes);      // the sorted stream is what keys_b / vals_b name
-    std::swap(c->vals_a.p, c->vals_b.p); std::swap(c->vals_a.bytes, c->vals_b.bytes);
-    std::swap(c->kseq_len.p, r.kseq.p); std::swap(c->kseq_len.bytes, r.kseq.bytes);
-    std::swap(c->gene_len.p, r.glen.p); std::swap(c->gene_len.bytes, r.glen.bytes);
-    std::swap(c->own_gen.p, r.gen.p); std::swap(c->own_gen.bytes, r.gen.bytes);             // the context owns the ids from here on, as after an append
+    context_changes(c);
+    c->keys_a.swap(c->keys_b); c->vals_a.swap(c->vals_b);      // the sorted stream is what keys_b / vals_b name
+    c->kseq_len.swap(r.kseq); c->gene_len.swap(r.glen);
+    c->own_gen.swap(r.gen);                                     // the context owns the ids from here on, as after an append
     pdl_replace_layout(c, std::move(genome_of));          // N, G, h_genome_of, genome rows
     c->M = M1; c->R -= gone_residues;
     c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
-    const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
-    c->scalars.alloc(ctl_words * sizeof(uint64_t));
-    c->cost.alloc((size_t) N1 * sizeof(uint64_t));
-
-    PDL_HIP(hipEventRecord(r.ev[2], st));
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);
-    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
-    PDL_HIP(hipGetLastError());
     c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
-    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
-    ev_end(c, EV_DICT);
-    pdl_prepare_tasks(c);
-    stage_ranges_and_costs(c, M1, 1, false);
-    PDL_HIP(hipEventRecord(r.ev[3], st));
-    PDL_HIP(hipStreamSynchronize(st));
-    if (c->opt_low_memory) {                  // as a build does: what only the build needed goes back
-        c->keys_a.release(); c->keys_b.release(); c->vals_a.release(); c->vals_b.release(); c->recpos.release(); c->sort_tmp.release();
-    }
-    float ms0 = 0.f, ms1 = 0.f;
-    (void) hipEventElapsedTime(&ms0, r.ev[0], r.ev[1]);
-    (void) hipEventElapsedTime(&ms1, r.ev[2], r.ev[3]);
+    rebuild_behind_sort(c, r.spans, M1, N1, G1, [] {});          // (the compacted stream is in place)
+    const float ms0 = r.spans.ms(0), ms1 = r.spans.ms(1);
     pdl_timings t{};                          // the preprocess fields describe the removal, the scoring fields start again
     t.sort_rank_ms = ms0; t.dict_ms = ev_ms(c, EV_DICT);
     t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);

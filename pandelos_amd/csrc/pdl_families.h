@@ -198,7 +198,7 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     }
     if (N >= 0x7fffffffu || n_edges[0] >= 0x7fffffffull || n_edges[1] >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "K-fam: 2^31 genes or edges and more");
     pdl_ctx::FamBufs &b = c->fb;
-    for (hipEvent_t &e : b.ev) if (!e) PDL_HIP(hipEventCreate(&e));
+    b.spans.start(st);
     if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t));      // (a context that has built nothing yet: the sort's and K-fam's words are all it needs)
     uint64_t *ctl = c->scalars.as<uint64_t>();
     const size_t n4 = (size_t) N * sizeof(uint32_t);
@@ -208,19 +208,17 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     uint32_t *parent = b.parent.as<uint32_t>(), *comp = b.comp.as<uint32_t>(), *same_deg = b.same_deg.as<uint32_t>();
     uint8_t *is_node = b.is_node.as<uint8_t>(), *collides = b.collides.as<uint8_t>();
 
-    PDL_HIP(hipEventRecord(b.ev[0], st));
+    b.spans.begin();
     hipLaunchKernelGGL(k_fam_init, fam_grid(std::max<uint32_t>(N, PDL_CTL_FAM_LAST + 1)), dim3(256), 0, st, parent, same_deg, is_node, collides, N, ctl);
-    bool checked = false;
     if (check_ids && n_edges[0]) {
         hipLaunchKernelGGL(k_fam_check, fam_grid(n_edges[0]), dim3(256), 0, st, src[0], dst[0], (uint32_t) n_edges[0], N, ctl + PDL_CTL_FAM_BAD_IDS);
         PDL_HIP(hipGetLastError());
-        PDL_HIP(hipEventRecord(b.ev[1], st));
+        b.spans.end();
         PinRead rd(c);
         const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_CTL_FAM_BAD_IDS, 1);
         rd.sync();
         if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-fam: %llu edges name a gene id outside [0, %u)", (unsigned long long) *bad, N);
-        PDL_HIP(hipEventRecord(b.ev[2], st));
-        checked = true;
+        b.spans.begin();
     }
     // F-cc
     for (int l = 0; l < 2; l++)
@@ -262,7 +260,7 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     hipLaunchKernelGGL(k_fam_collide, fam_grid(N), dim3(256), 0, st, ck_out, cv_out, run_of, run_off, same_deg, fam_of_label, N, collides);
     hipLaunchKernelGGL(k_fam_count, fam_grid(N), dim3(256), 0, st, collides, N, ctl + PDL_CTL_FAM_FAMILIES, ctl + PDL_CTL_FAM_COLLIDING);
     PDL_HIP(hipGetLastError());
-    PDL_HIP(hipEventRecord(b.ev[3], st));
+    b.spans.end();
     // F-out: the counts in one read, then the arrays
     {
         PinRead rd(c);
@@ -283,8 +281,5 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
         PDL_HIP(hipMemcpyAsync(out.collides.data(), collides, out.families, hipMemcpyDeviceToHost, st));
     }
     PDL_HIP(hipStreamSynchronize(st));
-    float ms0 = 0.f, ms1 = 0.f;
-    if (checked) { (void) hipEventElapsedTime(&ms0, b.ev[0], b.ev[1]); (void) hipEventElapsedTime(&ms1, b.ev[2], b.ev[3]); }
-    else (void) hipEventElapsedTime(&ms1, b.ev[0], b.ev[3]);
-    out.device_ms = ms0 + ms1;
+    out.device_ms = b.spans.total_ms();
 }

@@ -352,7 +352,8 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     const uint64_t Z = run.Z;
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells in the query block");
     uint64_t *ctl = place_begin(c);
-    QSpans spans(b.ev, st);
+    QSpans &spans = b.spans;
+    spans.start(st);
     spans.begin();
     // P-bbh
     uint64_t n1 = 0, n2 = 0;
@@ -401,11 +402,11 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     }
     if (n1 + n2) PDL_HIP(hipStreamSynchronize(st));
     out.edges_phase1 = (uint32_t) n1;
-    out.device_ms += pdl_query_device_ms(c, run.spans);
+    out.device_ms += c->qb.spans.total_ms();
     if (info) {
         memset(info, 0, sizeof(*info));
         info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
-        info->genome_cost = run.cost; info->device_ms = pdl_query_device_ms(c, run.spans);
+        info->genome_cost = run.cost; info->device_ms = c->qb.spans.total_ms();
     }
 }
 
@@ -413,7 +414,8 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
 void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, const int32_t *d_src, const int32_t *d_dst, uint64_t n_edges, pdl_place_result &out) {
     out = pdl_place_result{};
     (void) place_begin(c);
-    QSpans spans(c->pb.ev, c->stream);
+    QSpans &spans = c->pb.spans;
+    spans.start(c->stream);
     spans.begin();
     const int32_t *src[2] = {d_src, nullptr}, *dst[2] = {d_dst, nullptr};
     const uint64_t ne[2] = {n_edges, 0};

@@ -595,38 +595,27 @@ static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
 pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
     hipStream_t st = c->stream;
     auto &q = c->qb;
-    const uint32_t N = c->N, G = c->G, G1 = G + 1, k = c->rp.k;
+    const uint32_t N = c->N, G = c->G, G1 = G + 1;
     const uint64_t NC64 = (uint64_t) N + n;
     if (NC64 >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu genes in the union exceed the 31-bit gene ids", (unsigned long long) NC64);
     const uint32_t NC = (uint32_t) NC64;
-    const uint64_t r0 = offsets[0], Rq = offsets[n] - r0;
+    const uint64_t Rq = offsets[n] - offsets[0];
     if (c->R + Rq >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the union need 64-bit stream positions");
     if (c->max_kseq >= (1ull << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a base gene of %llu k-mers: queries need genes below 2^20 k-mers", (unsigned long long) c->max_kseq);
-    std::vector<uint64_t> h_off(n + 1), h_koff(n + 1);
-    std::vector<uint32_t> h_kseq(n);
-    uint64_t Mq = 0;
-    for (uint32_t g = 0; g < n; g++) {
-        const uint64_t len = offsets[g + 1] - offsets[g];
-        h_off[g] = offsets[g] - r0;
-        h_koff[g] = Mq;
-        h_kseq[g] = len >= k ? (uint32_t) std::min<uint64_t>(len - k + 1, 0xffffffffull) : 0u;
-        if (h_kseq[g] >= (1u << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query gene %u has %u k-mers: queries need genes below 2^20 k-mers", g, h_kseq[g]);
-        Mq += h_kseq[g];
-    }
-    h_off[n] = Rq; h_koff[n] = Mq;
+    const NewGenes genes(offsets, n, c->rp.k);
+    for (uint32_t g = 0; g < n; g++)
+        if (genes.kseq[g] >= (1u << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query gene %u has %u k-mers: queries need genes below 2^20 k-mers", g, genes.kseq[g]);
+    const uint64_t Mq = genes.M;
     if (Mq >= 0x7ffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu query k-mers exceed the 31-bit record positions", (unsigned long long) Mq);
-    QSpans spans(q.ev, st);
+    QSpans &spans = q.spans;
+    spans.start(st);
     spans.begin();
 
     // Q-alpha
     q.ctl.alloc(Q_CTL_WORDS * sizeof(uint64_t));
     unsigned long long *ctl = q.ctl.as<unsigned long long>();
     PDL_HIP(hipMemsetAsync(ctl, 0, Q_CTL_WORDS * sizeof(uint64_t), st));
-    q.res.alloc(Rq); q.off.alloc((n + 1) * 8ull); q.koff.alloc((n + 1) * 8ull); q.kseq.alloc(n * 4ull);
-    if (Rq) PDL_HIP(hipMemcpyAsync(q.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.off.p, h_off.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.koff.p, h_koff.data(), (n + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(q.kseq.p, h_kseq.data(), n * 4ull, hipMemcpyHostToDevice, st));
+    genes.upload(c, residues);
     pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
 
     // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look below)
@@ -715,13 +704,7 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
     }
     pdl_query_run run;
     run.Z = Z; run.cap = std::max<uint64_t>(bound, 1); run.residues = Rq; run.kmers = Mq; run.records = Uq; run.matched = matched; run.cost = cost;
-    run.spans = spans.n;
     return run;
-}
-float pdl_query_device_ms(pdl_ctx *c, int spans) {           // (after the stream has been synchronized)
-    QSpans s(c->qb.ev, c->stream);
-    s.n = spans;
-    return s.total_ms();
 }
 
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info) {
@@ -751,6 +734,6 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
         memset(info, 0, sizeof(*info));
         info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
         info->genome_cost = run.cost;
-        info->device_ms = pdl_query_device_ms(c, run.spans);
+        info->device_ms = q.spans.total_ms();
     }
 }

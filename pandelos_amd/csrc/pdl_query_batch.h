@@ -260,7 +260,8 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         }
     }
     h_off[NT] = Rq; h_koff[NT] = Mq; h_gbeg[nq] = NT; h_rbeg[nq] = Rq;
-    QSpans spans(w.ev, st);
+    QSpans &spans = w.spans;
+    spans.start(st);
     spans.begin();
 
     // B-alpha (and the chunk on its way to the device)

@@ -25,6 +25,35 @@ def _np_copy(ptr, dtype, n):
     return np.frombuffer(buf, dtype=dtype, count=n).copy()
 
 
+def _gene_arrays(residues, offsets, what="n", where=""):
+    """(residues, offsets) as the contiguous uint8 / uint64 arrays the library reads; offsets hold ``what`` + 1 entries
+    (``where``: a prefix of the message, such as the query's place in a batch)."""
+    res = np.ascontiguousarray(residues, dtype=np.uint8)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"{where}offsets must hold {what} + 1 entries")
+    return res, off
+
+
+def _one_genome(data: PangeneIData, query=None):
+    """(residues, offsets) of a ``PangeneIData`` that holds exactly one genome (``query``: its place in a batch, for the message)."""
+    residues, offsets, genome_of = data.flatten()
+    n_genomes = len(np.unique(genome_of))
+    if n_genomes != 1:
+        raise ValueError(f"a query holds exactly one genome, {'this data' if query is None else f'query {query}'} holds {n_genomes}")
+    return residues, offsets
+
+
+def _edge_arrays(src, dst, genome_of):
+    """An edge list (gene ids ``src`` / ``dst``) and the genes' genome ids as the contiguous int32 / uint32 arrays the library reads."""
+    s = np.ascontiguousarray(src, dtype=np.int32)
+    d = np.ascontiguousarray(dst, dtype=np.int32)
+    g = np.ascontiguousarray(genome_of, dtype=np.uint32)
+    if s.ndim != 1 or s.shape != d.shape or g.ndim != 1:
+        raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "src and dst must be two vectors of one length, genome_of a vector")
+    return s, d, g
+
+
 class PangeneNative:
     def __init__(self, k: int, data: PangeneIData, only_complexity: bool = False, device: int = -1,
                  stream: Optional[int] = None, flags: int = 0):
@@ -142,10 +171,7 @@ class PangeneNative:
         """One new genome against this dictionary, without a rebuild (``pdl_query_scores``): the Scores block of genome
         G = ``cost.genomes`` in the union run, with these genes appended as ids N..N+n-1.  ``last_query_info`` then holds
         the call's sizes, "Genome G cost" (``genome_cost``) and device time as a dict."""
-        res = np.ascontiguousarray(residues, dtype=np.uint8)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if off.ndim != 1 or len(off) < 1:
-            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n_query + 1 entries")
+        res, off = _gene_arrays(residues, offsets, "n_query")
         s, info = _lib.PdlScores(), _lib.PdlQueryInfo()
         self._check(self._lib.pdl_query_scores(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data,
                                                len(off) - 1, C.byref(s), C.byref(info)))
@@ -154,11 +180,7 @@ class PangeneNative:
 
     def query_idata(self, data: PangeneIData) -> Scores:
         """``query_scores`` for the genes of a ``PangeneIData`` that holds exactly one genome."""
-        residues, offsets, genome_of = data.flatten()
-        n_genomes = len(np.unique(genome_of))
-        if n_genomes != 1:
-            raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
-        return self.query_scores(residues, offsets)
+        return self.query_scores(*_one_genome(data))
 
     @staticmethod
     def pack_queries(queries):
@@ -168,10 +190,7 @@ class PangeneNative:
         parts, offs, begin = [], [np.zeros(1, np.uint64)], [0]
         at = 0
         for j, (residues, offsets) in enumerate(queries):
-            res = np.ascontiguousarray(residues, dtype=np.uint8)
-            off = np.ascontiguousarray(offsets, dtype=np.uint64)
-            if off.ndim != 1 or len(off) < 1:
-                raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"query {j}: offsets must hold n + 1 entries")
+            res, off = _gene_arrays(residues, offsets, where=f"query {j}: ")
             if (np.diff(off.astype(np.int64)) < 0).any() or int(off[-1]) > len(res):
                 raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"query {j}: offsets decrease or pass the residues")
             lo, hi = int(off[0]), int(off[-1])
@@ -207,14 +226,7 @@ class PangeneNative:
 
     def query_batch_idata(self, datas) -> list:
         """``query_batch`` for a list of ``PangeneIData``, each holding exactly one genome."""
-        queries = []
-        for j, data in enumerate(datas):
-            residues, offsets, genome_of = data.flatten()
-            n_genomes = len(np.unique(genome_of))
-            if n_genomes != 1:
-                raise ValueError(f"a query holds exactly one genome, query {j} holds {n_genomes}")
-            queries.append((residues, offsets))
-        return self.query_batch(queries)
+        return self.query_batch([_one_genome(data, j) for j, data in enumerate(datas)])
 
     def append(self, residues, offsets, genome_of=None) -> None:
         """New genomes join this dictionary by a merge, without a rebuild (``pdl_append_genomes``): the genes become ids
@@ -222,10 +234,7 @@ class PangeneNative:
         in first-seen order).  Afterwards the context is the one ``preprocess`` on the union would leave; ``cost`` is the
         union's and ``last_append_info`` holds the call's sizes and device times as a dict.  A refusal leaves everything as
         it was."""
-        res = np.ascontiguousarray(residues, dtype=np.uint8)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if off.ndim != 1 or len(off) < 1:
-            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n + 1 entries")
+        res, off = _gene_arrays(residues, offsets)
         gen = None
         if genome_of is not None:
             gen = np.ascontiguousarray(genome_of, dtype=np.uint32)
@@ -297,11 +306,7 @@ class PangeneNative:
         """The same kernels over a caller's edge list (``pdl_families_of_edges``): gene ids ``src`` / ``dst``, one genome id per
         gene — a network gathered from genome batches or from several ranks.  Needs no preprocess and leaves the context's own
         state alone."""
-        s = np.ascontiguousarray(src, dtype=np.int32)
-        d = np.ascontiguousarray(dst, dtype=np.int32)
-        g = np.ascontiguousarray(genome_of, dtype=np.uint32)
-        if s.ndim != 1 or s.shape != d.shape or g.ndim != 1:
-            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "src and dst must be two vectors of one length, genome_of a vector")
+        s, d, g = _edge_arrays(src, dst, genome_of)
         f = _lib.PdlFamilies()
         self._check(self._lib.pdl_families_of_edges(self._ctx, s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, len(s),
                                                     g.ctypes.data if g.size else None, len(g), C.byref(f)))
@@ -324,10 +329,7 @@ class PangeneNative:
         (``src``, ``dst``, ``score`` in the host's insertion order, ``edges_phase1`` of them phase 1) and, per query gene and per
         group the query touches, the fields of ``pdl_placement`` as a dict (counts as ints, arrays as numpy).  The context is
         only read.  ``last_place_info`` holds the counts, the device time and the query's own ``pdl_query_info`` (``query``)."""
-        res = np.ascontiguousarray(residues, dtype=np.uint8)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if off.ndim != 1 or len(off) < 1:
-            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "offsets must hold n_query + 1 entries")
+        res, off = _gene_arrays(residues, offsets, "n_query")
         p, info = _lib.PdlPlacement(), _lib.PdlQueryInfo()
         self._check(self._lib.pdl_place_query(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data, len(off) - 1,
                                               C.byref(p), C.byref(info)))
@@ -335,21 +337,13 @@ class PangeneNative:
 
     def place_idata(self, data: PangeneIData) -> dict:
         """``place_query`` for the genes of a ``PangeneIData`` that holds exactly one genome."""
-        residues, offsets, genome_of = data.flatten()
-        n_genomes = len(np.unique(genome_of))
-        if n_genomes != 1:
-            raise ValueError(f"a query holds exactly one genome, this data holds {n_genomes}")
-        return self.place_query(residues, offsets)
+        return self.place_query(*_one_genome(data))
 
     def placement_of_edges(self, base: dict, genome_of, n_query: int, src, dst) -> dict:
         """The same kernels over a caller's query edge list in union ids (``pdl_placement_of_edges``): ``base`` is the dict
         ``generate_families`` / ``families_of_edges`` returned for the N base genes, ``genome_of`` their genomes; the query is
         ``n_query`` genes N..N+n_query-1 of one further genome.  Needs no preprocess and leaves the context's own state alone."""
-        s = np.ascontiguousarray(src, dtype=np.int32)
-        d = np.ascontiguousarray(dst, dtype=np.int32)
-        g = np.ascontiguousarray(genome_of, dtype=np.uint32)
-        if s.ndim != 1 or s.shape != d.shape or g.ndim != 1:
-            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "src and dst must be two vectors of one length, genome_of a vector")
+        s, d, g = _edge_arrays(src, dst, genome_of)
         keep = {f: np.ascontiguousarray(base[f], dtype=t) for f, t in (("component_of", np.uint32), ("is_node", np.uint8), ("family_off", np.uint32),
                                                                         ("family_genes", np.uint32), ("collides", np.uint8))}
         if len(keep["component_of"]) != len(g) or len(keep["is_node"]) != len(g) or len(keep["family_off"]) != len(keep["collides"]) + 1:
