@@ -152,3 +152,140 @@ def wrapped_rank_set(letters: int, seed: int, genomes: int = 4, per_genome: int 
     offsets = np.zeros(len(genes) + 1, np.uint64)
     np.cumsum([len(x) for x in genes], out=offsets[1:])
     return GeneSet(np.concatenate(genes).astype(np.uint8), offsets, np.asarray(gen, np.uint32), np.asarray(fam_of, np.int64))
+
+
+# ---- k-mers that occur 1023 times or more inside one gene ---------------------------------------------------------------------
+# The single-GPU build packs a row's range into 8 bytes with the row's own count of the k-mer in a 10-bit field (gt_pack_range in
+# pdl_groups.h: min(count, 1023)); a reader that finds 1023 there takes the true count from the record in front of the range.  The
+# sets below plant such k-mers: a stretch of `runs[i]` repeats of a unit of `period` letters has runs[i] occurrences of each of the
+# `period` k-mers that lie inside it.
+SATURATED_RUNS = (1022, 1023, 1024, 3000)                # below the field's maximum, the maximum, above it, far above it
+
+
+def _as_gene_set(genes, genome_of, family_of):
+    from pandelos_amd.synth import GeneSet
+    offsets = np.zeros(len(genes) + 1, np.uint64)
+    np.cumsum([len(x) for x in genes], out=offsets[1:])
+    return GeneSet(np.concatenate(genes).astype(np.uint8), offsets, np.asarray(genome_of, np.uint32), np.asarray(family_of, np.int64))
+
+
+def stretch(unit, repeats: int, k: int) -> np.ndarray:
+    """`unit` repeated until every k-mer inside the stretch occurs `repeats` times: repeats * len(unit) + k - 1 residues"""
+    unit = np.asarray(unit, np.uint8)
+    n = repeats * len(unit) + k - 1
+    return np.tile(unit, n // len(unit) + 1)[:n]
+
+
+def saturated_count_set(k: int, period: int = 1, fams: int = 20, genomes: int = 4, runs=SATURATED_RUNS, body: int = 220,
+                        sub: float = 0.05, seed: int = 1):
+    """`fams` families in `genomes` genomes (genes listed genome by genome, a genome's genes in family order).  Every gene is its
+    family's random body of `body` residues with `sub` substitutions per copy and, spliced into its middle, a stretch of
+    runs[(family + genome) % len(runs)] repeats of the family's unit of `period` letters (letters family, family + 1, ...: no two
+    families share a planted k-mer).  Runs stay at 3000: K-rle's cost is quadratic in the run length.
+    -> pandelos_amd.synth.GeneSet"""
+    assert 1 <= period < 20 and fams <= 20 and max(runs) <= 3000
+    rng = np.random.default_rng(seed)
+    bases = [LETTERS[rng.integers(0, 20, body)] for _ in range(fams)]
+    genes, gen, fam_of = [], [], []
+    for g in range(genomes):
+        for f in range(fams):
+            s = bases[f].copy()
+            m = rng.random(body) < sub
+            s[m] = LETTERS[rng.integers(0, 20, int(m.sum()))]
+            unit = LETTERS[[(f + j) % 20 for j in range(period)]]
+            genes.append(np.concatenate([s[:body // 2], stretch(unit, runs[(f + g) % len(runs)], k), s[body // 2:]]))
+            gen.append(g); fam_of.append(f)
+    return _as_gene_set(genes, gen, fam_of)
+
+
+def saturated_dense_set(k: int = 3, genes: int = 600, genomes: int = 5, runs=(1022, 1023, 1100, 2500), first: int = 1, flank: int = 40, seed: int = 5):
+    """One planted k-mer that EVERY gene holds (a stretch of the alphabet's last but one letter between two random flanks of
+    `flank` residues, runs[(i + first) % len(runs)] occurrences in gene i): its rank-group has `genes` members, so gene i's one
+    range of it holds genes - 1 - i postings.  The cycle starts at runs[first] = 1023, so that gene 0 — the group's head, the only
+    record of the set whose count word ever carried the head bit AND is read again — has a saturated count.  Genes listed genome by
+    genome.  -> pandelos_amd.synth.GeneSet"""
+    rng = np.random.default_rng(seed)
+    out = [np.concatenate([LETTERS[rng.integers(0, 20, flank)], stretch([ord("W")], runs[(i + first) % len(runs)], k), LETTERS[rng.integers(0, 20, flank)]])
+           for i in range(genes)]
+    per = -(-genes // genomes)
+    return _as_gene_set(out, [i // per for i in range(genes)], [0] * genes)
+
+
+def rank_groups(d):
+    """The oracle's dictionary `d` (records {rank, seq, count}) -> (records in (rank, gene) order, group id of each, first record of
+    each group, size of each group), with the groups as the reference's scan forms them: the globally last record never opens one
+    (library.cpp:297-306), it belongs to the group in front of it."""
+    o = np.lexsort((d["seq"], d["rank"]))
+    r = d[o]
+    new = np.r_[True, r["rank"][1:] != r["rank"][:-1]]
+    if len(r) > 1:
+        new[-1] = False
+    gid = np.cumsum(new) - 1
+    if len(r) > 1 and r["rank"][-1] != r["rank"][-2]:   # the folded record: its place inside the group is by gene
+        o2 = np.lexsort((r["seq"], gid))
+        r, gid = r[o2], gid[o2]
+    start = np.flatnonzero(np.r_[True, gid[1:] != gid[:-1]])
+    return r, gid, start, np.diff(np.r_[start, len(r)])
+
+
+def fold_saturated_set(variant: str, k: int = 3, fams: int = 6, genomes: int = 3, body: int = 120, run: int = 3000, seed: int = 3):
+    """The fold of the globally last record (library.cpp:300-306) meets a saturated count.  Bodies over the 19 letters below Y;
+    the k-mers that start with Y are the largest ranks, and there are two of them: Y..Y, `run` times at the END of gene X and
+    nowhere else (the globally last record, a singleton with a count of `run`), and the motif YA..AC in the middle of the genes of
+    X's family in the other genomes (the group in front of it, into which the record is folded).  X's family is family 2.
+      "head":   X is in genome 0: the folded record has the smallest gene id of the group and becomes its head
+      "middle": X is in genome 1: the folded record lands between the members
+      "same_gene_twice": as "middle", and X holds the motif too (the shape of the q1_fold_same_gene_twice fixture)
+    -> (pandelos_amd.synth.GeneSet, id of gene X)"""
+    rng = np.random.default_rng(seed)
+    low = LETTERS[:19]
+    motif = np.frombuffer(b"Y" + b"A" * (k - 2) + b"C", np.uint8)
+    bases = [low[rng.integers(0, 19, body)] for _ in range(fams)]
+    xg = 0 if variant == "head" else 1
+    genes, gen, fam_of, x = [], [], [], -1
+    for g in range(genomes):
+        for f in range(fams):
+            s = bases[f].copy()
+            m = rng.random(body) < 0.05
+            s[m] = low[rng.integers(0, 19, int(m.sum()))]
+            if f == 2:
+                with_motif = np.concatenate([s[:body // 2], motif, s[body // 2:]])
+                if g != xg:
+                    s = with_motif
+                else:
+                    x = len(genes)
+                    s = np.concatenate([with_motif if variant == "same_gene_twice" else s, [low[0]], stretch([ord("Y")], run, k)])
+            genes.append(s); gen.append(g); fam_of.append(f)
+    return _as_gene_set(genes, gen, fam_of), x
+
+
+class OracleCase:
+    """A gene set with everything the CPU oracle says about it; made once, never changed."""
+
+    def __init__(self, gs, k: int):
+        from oracle import binding as ob
+        ora = ob.Oracle(gs.residues, gs.offsets, gs.genome_of, k)
+        self.gs, self.k, self.genomes = gs, k, int(ora.genomes)
+        self.arrays = (gs.residues, gs.offsets, gs.genome_of)
+        self.want = [ora.scores(g) for g in range(ora.genomes)]
+        self.total_cost = int(ora.total_cost)
+        self.genome_cost = [int(ora.genome_cost(g)) for g in range(ora.genomes)]
+        self.dictionary, self.total_visited, self.kseq = ora.dictionary(), ora.total_visited(), ora.kseq_lengths()
+        ora.close()
+
+
+_CASES = {}
+
+
+def saturated_case(name: str) -> OracleCase:
+    """"sat:<k>:<period>" = saturated_count_set(k, period), "dense" = saturated_dense_set() at k = 3"""
+    if name not in _CASES:
+        kind, _, arg = name.partition(":")
+        if kind == "sat":
+            k, period = (int(x) for x in arg.split(":"))
+            _CASES[name] = OracleCase(saturated_count_set(k, period), k)
+        elif kind == "dense":
+            _CASES[name] = OracleCase(saturated_dense_set(), 3)
+        else:
+            raise KeyError(name)
+    return _CASES[name]
