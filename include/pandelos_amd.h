@@ -445,7 +445,11 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * between dispatches, a few microseconds of idle stream on a two-millisecond step), "low_memory" 0|1 (for genome batches on a large set: the buffers only the dictionary build needed are released after it —
  * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "query_batch_bytes" n > 0
  * (device bytes one chunk of pdl_query_batch may take before its join, default 2^30), "onepass_scan" 0|1 (prefix scans
- * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "aside_test_reload" 0|1 (test switch: the next scoring pass
+ * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "lean_radix" 0|1
+ * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
+ * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"
+ * off; 0: a histogram kernel and a three-launch scan for every pass.  Same results either way: for parity tests and A/B timing),
+ * "aside_test_reload" 0|1 (test switch: the next scoring pass
  * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs). */
 PDL_API int pdl_set_option(pdl_ctx *, const char *name, int64_t value);
 

@@ -799,6 +799,7 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     else if (n == "staging_cap") c->opt_staging_cap = value > 0 ? (uint64_t) value : 0;
     else if (n == "aside_test_reload") c->opt_aside_test_reload = value != 0;
     else if (n == "onepass_scan") c->opt_onepass_scan = value != 0;
+    else if (n == "lean_radix") c->opt_lean_radix = value != 0;
     else if (n == "low_memory") c->opt_low_memory = value != 0;
     else if (n == "query_batch_bytes") {
         if (value <= 0) { c->err = "query_batch_bytes: a positive byte count"; return PDL_ERR_ARGUMENT; }

@@ -338,6 +338,7 @@ struct pdl_ctx {
     bool opt_low_memory = false;          // batches of genomes on a large set: build buffers released after the dictionary, small HBM tables for tier 3
     bool reshard_pending = false;         // pdl_set_genome_shard named genomes the range lists on the device do not cover: they are built before the next scoring pass
     bool opt_onepass_scan = false;        // scans in one launch (decoupled look-back) instead of three: measured 3-10 % slower per scan on MI355X, kept as an option
+    bool opt_lean_radix = true;           // radix passes: offsets in one launch (k_rs_offsets), the rank sort's first histogram filed by K-rank; 0: a histogram and a three-launch scan per pass
     DevBuf scratch;       // transient buffers of the range build
     DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*, above)
 

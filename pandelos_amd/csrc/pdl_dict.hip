@@ -164,28 +164,60 @@ __device__ __forceinline__ uint64_t load_residues8(const uint8_t *__restrict__ r
 // Interval histogram of the multi-GPU build: the rank space is cut where the top DIST_BIN_BITS bits of a rank change.
 constexpr uint32_t DIST_BIN_BITS = 12, DIST_BINS = 1u << DIST_BIN_BITS;
 
+// upper_bound_u64 by a whole wave (all 64 lanes active, same arguments; every lane returns the same index): lane i probes one
+// of 64 evenly spaced entries, a ballot picks the segment — three dependent loads for up to 64^3 entries where one lane's
+// binary search makes eighteen.
+__device__ __forceinline__ uint32_t wave_upper_bound_u64(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v) {
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1);
+    // invariant: a[i] <= v for every i < lo, a[i] > v for every i >= hi
+    while (hi - lo > PDL_WAVE) {
+        const uint32_t step = (hi - lo + PDL_WAVE - 1) / PDL_WAVE;
+        const uint64_t at = (uint64_t) lo + (uint64_t) lane * step;
+        const bool le = at < hi && a[at] <= v;
+        const uint32_t c = (uint32_t) __popcll(__ballot(le));        // (a ascends: the lanes 0 .. c-1)
+        if (c == 0) return lo;
+        const uint64_t next = (uint64_t) lo + (uint64_t) c * step;   // first probe above v, if it was made
+        if (next < hi) hi = (uint32_t) next;
+        lo = lo + (c - 1) * step + 1;
+    }
+    const bool le = lo + lane < hi && a[lo + lane] <= v;
+    return lo + (uint32_t) __popcll(__ballot(le));
+}
+
 // MODE 0: keys[q] = rank, vals[q] = gene for every slot q of the k-mer stream (one workgroup per tile).
 // MODE 1: the same, and counts the ranks by their top bits into bins[DIST_BINS] (persistent workgroups over the tiles,
 //         LDS histogram, one global atomic per non-empty bin and workgroup): the k-mer count of every rank interval,
 //         from which pdl_dist_preprocess_begin derives the same cuts on every GPU.
+// MODE 2: as MODE 0, and files the first histogram of the rank sort: a workgroup covers one tile of the radix pass
+//         (PDL_RADIX_TILE slots, in trips of RANK_TILE; its genes are bracketed and staged once), counts the low byte of the
+//         ranks it writes and stores bins[byte * tiles + tile] — what k_rs_hist would count from the keys read back.
 template <class KeyT, int MODE>
 __global__ __launch_bounds__(RANK_THREADS) void k_rank(const uint8_t *__restrict__ res, const uint64_t *__restrict__ off,
                                                        const uint64_t *__restrict__ kmer_off, uint32_t n_seq, uint64_t m, uint64_t n_res,
                                                        RankParams rp, KeyT *__restrict__ keys, uint32_t *__restrict__ vals,
                                                        uint32_t bin_shift, uint32_t *__restrict__ bins) {
+    static_assert(RANK_THREADS == (int) PDL_RADIX_BINS && PDL_RADIX_TILE % RANK_TILE == 0, "MODE 2: one thread per byte value, whole trips per radix tile");
+    constexpr uint32_t TRIPS = MODE == 2 ? PDL_RADIX_TILE / RANK_TILE : 1;
+    constexpr uint64_t TILE = (uint64_t) RANK_TILE * TRIPS;
     __shared__ uint8_t s_rv[256];
     __shared__ uint32_t s_lo, s_hi;
     __shared__ uint64_t s_koff[RANK_SPAN + 1], s_off[RANK_SPAN];    // k-mer and residue offsets of the genes this tile touches
-    __shared__ uint32_t s_bins[MODE == 1 ? DIST_BINS : 1];
+    __shared__ uint32_t s_bins[MODE == 1 ? DIST_BINS : MODE == 2 ? PDL_RADIX_BINS : 1];
     for (int i = threadIdx.x; i < 256; i += RANK_THREADS) s_rv[i] = rp.rank_values[i];
     if constexpr (MODE == 1) for (uint32_t i = threadIdx.x; i < DIST_BINS; i += RANK_THREADS) s_bins[i] = 0;
-    const uint64_t tiles = (m + RANK_TILE - 1) / RANK_TILE;
-  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {      // MODE 0: grid = tiles, one trip
+    const uint64_t tiles = (m + TILE - 1) / TILE;
+  for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {      // MODE 0, 2: grid = tiles, one trip
     pdl_sync();                                            // (the staged boundaries of the previous tile are done with)
-    const uint64_t q0 = tile * RANK_TILE;
-    const uint64_t q_last = min(q0 + RANK_TILE, m) - 1;
-    if (threadIdx.x == 0) s_lo = upper_bound_u64(kmer_off, 0, n_seq + 1, q0) - 1;
-    if (threadIdx.x == 64) s_hi = upper_bound_u64(kmer_off, 0, n_seq + 1, q_last) - 1;
+    const uint64_t q0 = tile * TILE;
+    const uint64_t q_last = min(q0 + TILE, m) - 1;
+    if (threadIdx.x < PDL_WAVE) {                          // (two whole waves, one bracket each)
+        const uint32_t b = wave_upper_bound_u64(kmer_off, 0, n_seq + 1, q0) - 1;
+        if (threadIdx.x == 0) s_lo = b;
+    } else if (threadIdx.x < 2 * PDL_WAVE) {
+        const uint32_t b = wave_upper_bound_u64(kmer_off, 0, n_seq + 1, q_last) - 1;
+        if (threadIdx.x == PDL_WAVE) s_hi = b;
+    }
+    if constexpr (MODE == 2) s_bins[threadIdx.x] = 0;
     pdl_sync();
     const uint32_t lo = s_lo, hi = s_hi;
     const uint32_t span = hi - lo + 1;                          // genes under this tile (uniform)
@@ -195,6 +227,12 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank(const uint8_t *__restrict
         for (uint32_t i = threadIdx.x; i < span; i += RANK_THREADS) s_off[i] = off[lo + i];
     }
     pdl_sync();
+    // (staged, at most 64 genes) the start of gene lo + lane; the lanes past the last gene hold the end of the bracket, above every slot of the tile
+    const uint64_t my_koff = staged ? s_koff[min(threadIdx.x & (PDL_WAVE - 1), span)] : 0;
+#pragma unroll 1
+   for (uint32_t trip = 0; trip < TRIPS; trip++) {
+    const uint64_t qt0 = q0 + (uint64_t) trip * RANK_TILE;
+    if (qt0 >= m) break;                                        // (uniform; MODE 2: the stream's last tile)
     const uint32_t k = rp.k;
     const KeyT base = (KeyT) rp.base;                           // the polynomial fits KeyT (checked on the host): KeyT arithmetic
     // Phase 1: gene and residue position of the lane's four k-mers.  Phase 2: their residues, eight bytes per load, the
@@ -203,13 +241,16 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank(const uint8_t *__restrict
     uint64_t pos[RANK_ITEMS];
 #pragma unroll
     for (int j = 0; j < RANK_ITEMS; j++) {
-        const uint64_t qj = q0 + (uint64_t) j * RANK_THREADS + threadIdx.x;
+        const uint64_t qj = qt0 + (uint64_t) j * RANK_THREADS + threadIdx.x;
         const uint64_t q = qj < m ? qj : m - 1;
         if (staged) {                                           // (uniform) boundaries from LDS: no chain of global loads
             uint32_t a = 0;                                     // last i in [0, span) with s_koff[i] <= q
-            if (span <= 8) {                                    // (uniform, the usual case) count the gene starts at or below q:
-#pragma unroll                                                  //  independent broadcast reads instead of a dependent search
-                for (uint32_t i = 1; i < 8; i++) a += (uint32_t) (i < span && s_koff[i < span ? i : 0] <= q);
+            if (span <= PDL_WAVE) {                             // (uniform, the usual case) lane i holds the start of gene lo + i: two ballots
+                // bracket the genes under the wave's 64 consecutive slots, mostly one gene or two; the lane counts the starts between
+                const uint64_t qf = min(qt0 + (uint64_t) j * RANK_THREADS + (threadIdx.x & ~(PDL_WAVE - 1)), m - 1), ql = min(qf + PDL_WAVE - 1, m - 1);
+                const uint32_t a0 = (uint32_t) __popcll(__ballot(my_koff <= qf)) - 1, a1 = (uint32_t) __popcll(__ballot(my_koff <= ql)) - 1;
+                a = a0;
+                for (uint32_t i = a0 + 1; i <= a1; i++) a += (uint32_t) (s_koff[i] <= q);
             } else {
                 uint32_t b = span;
                 while (a < b) { const uint32_t mid = (a + b) >> 1; if (s_koff[mid + 1] <= q) a = mid + 1; else b = mid; }
@@ -244,11 +285,17 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank(const uint8_t *__restrict
     }
 #pragma unroll
     for (int j = 0; j < RANK_ITEMS; j++) {
-        const uint64_t q = q0 + (uint64_t) j * RANK_THREADS + threadIdx.x;
+        const uint64_t q = qt0 + (uint64_t) j * RANK_THREADS + threadIdx.x;
         if (q < m) {
             if constexpr (MODE == 1) atomicAdd(&s_bins[(uint32_t) (r[j] >> bin_shift)], 1u);
+            if constexpr (MODE == 2) atomicAdd(&s_bins[(uint32_t) r[j] & (PDL_RADIX_BINS - 1)], 1u);      // (the digit of k_rs_scatter's first pass)
             keys[q] = r[j]; vals[q] = sq[j];
         }
+    }
+   }
+    if constexpr (MODE == 2) {
+        pdl_sync();
+        bins[(size_t) threadIdx.x * tiles + tile] = s_bins[threadIdx.x];
     }
   }
     if constexpr (MODE == 1) {
@@ -524,9 +571,10 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     c->key64 = c->rp.rank_bits > 32;
 }
 
-// K-rank over the whole stream into (keys_a, vals_a); d_bins != nullptr: also the interval histogram (multi-GPU build)
+// K-rank over the whole stream into (keys_a, vals_a); d_bins != nullptr: also the interval histogram (multi-GPU build).
+// Returns true when it has filed the counts of the rank sort's first pass in c->sort_tmp (pdl_sort_pairs, first_counts_filed).
 template <class KeyT>
-static void stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shift = 0) {
+static bool stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shift = 0) {
     hipStream_t st = c->stream;
     const uint64_t M = c->M;
     c->keys_a.alloc(M * sizeof(KeyT)); c->keys_b.alloc(M * sizeof(KeyT));
@@ -542,10 +590,18 @@ static void stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shif
         const uint64_t tiles = (M + RANK_TILE - 1) / RANK_TILE;
         if (d_bins) hipLaunchKernelGGL((k_rank<KeyT, 1>), dim3((uint32_t) std::min<uint64_t>(tiles, 2048)), dim3(RANK_THREADS), 0, st, c->d_res, c->d_off,
                                        c->kmer_off.as<uint64_t>(), c->N, M, c->R, c->rp, c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>(), bin_shift, d_bins);
+        else if (pdl_radix_lean(c, M)) {
+            c->sort_tmp.alloc(pdl_radix_tmp_bytes(M));
+            hipLaunchKernelGGL((k_rank<KeyT, 2>), dim3((uint32_t) ((M + PDL_RADIX_TILE - 1) / PDL_RADIX_TILE)), dim3(RANK_THREADS), 0, st, c->d_res, c->d_off,
+                               c->kmer_off.as<uint64_t>(), c->N, M, c->R, c->rp, c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>(), 0u, c->sort_tmp.as<uint32_t>());
+            PDL_HIP(hipGetLastError());
+            return true;
+        }
         else hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, c->d_res, c->d_off,
                                 c->kmer_off.as<uint64_t>(), c->N, M, c->R, c->rp, c->keys_a.as<KeyT>(), c->vals_a.as<uint32_t>(), 0u, (uint32_t *) nullptr);
     }
     PDL_HIP(hipGetLastError());
+    return false;
 }
 
 // K-rle over the sorted stream (keys_b, vals_b)[0 .. m): records into c->post / recpos, their count into scalars[PDL_CTL_RECORDS].
@@ -564,9 +620,10 @@ static void stage_dedup(pdl_ctx *c, uint64_t m) {
 // K-sort + K-rle over the first m elements of (keys_in, vals_in): records into c->post / recpos.
 // scalars[PDL_CTL_RECORDS] receives the record count.
 template <class KeyT>
-static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint64_t m) {
+static void stage_sort_and_dedup(pdl_ctx *c, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint64_t m,
+                                 bool first_counts_filed = false) {      // by K-rank, for all m elements (stage_rank)
     ev_begin(c, EV_SORT1);
-    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits, first_counts_filed);
     ev_end(c, EV_SORT1);
     // remember which physical buffers hold the sorted stream (pdl_get_dictionary reads them)
     if ((void *) keys_out != c->keys_b.p) c->keys_a.swap(c->keys_b);
@@ -664,13 +721,13 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             const uint32_t n_tiles4 = (uint32_t) ((bound + PDL_RADIX_TILE - 1) / PDL_RADIX_TILE);
             const size_t table = (size_t) PDL_RADIX_BINS * n_tiles4, tiles = (bound + GW_TILE - 1) / GW_TILE;
             // (the scan below uses scan_tmp: the per-tile heads move next to the radix tables)
-            c->sort_tmp.alloc((2 * table + 3 * tiles + 1) * sizeof(uint32_t));
-            uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table;
-            ga.tile_sums = offs + table; ga.th_first = ga.tile_sums + tiles; ga.th_last = ga.th_first + tiles; ga.chunk_sums = nullptr;
+            c->sort_tmp.alloc((2 * table + PDL_RADIX_BINS + 3 * tiles + 1) * sizeof(uint32_t));
+            uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table, *digit_total = offs + table;
+            ga.tile_sums = digit_total + PDL_RADIX_BINS; ga.th_first = ga.tile_sums + tiles; ga.th_last = ga.th_first + tiles; ga.chunk_sums = nullptr;
             const uint32_t grid4 = std::max<uint32_t>(1, std::min<uint32_t>(n_tiles4, (uint32_t) c->cus * 8));
             hipLaunchKernelGGL(k_range_count_hist, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
-            pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + PDL_CTL_RANGES);
-            hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, k2b, pay_b);
+            const uint32_t *totals = pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + PDL_CTL_RANGES, digit_total);
+            hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, k2b, pay_b, totals, d_scal + PDL_CTL_RANGES);
             PDL_HIP(hipGetLastError());
         } else {
         launch_range_count(c, ga, grid, mode);
@@ -804,11 +861,11 @@ template <class KeyT>
 static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
     const uint64_t M = c->M;
     ev_begin(c, EV_RANK);
-    stage_rank<KeyT>(c);
+    const bool counts_filed = stage_rank<KeyT>(c);
     ev_end(c, EV_RANK);
     KeyT *keys_in = c->keys_a.as<KeyT>(), *keys_out = c->keys_b.as<KeyT>();
     uint32_t *vals_in = c->vals_a.as<uint32_t>(), *vals_out = c->vals_b.as<uint32_t>();
-    stage_sort_and_dedup<KeyT>(c, keys_in, keys_out, vals_in, vals_out, M);
+    stage_sort_and_dedup<KeyT>(c, keys_in, keys_out, vals_in, vals_out, M, counts_filed);
     ev_end(c, EV_DICT);
     if (c->layout_deferred) pdl_finish_layout(c);   // device input: the genome layout is host work too, and nothing before this point needed it
     if (!only_complexity) pdl_prepare_tasks(c);     // host work + small uploads while the device sorts

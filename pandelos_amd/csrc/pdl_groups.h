@@ -523,22 +523,27 @@ __global__ __launch_bounds__(GW_THREADS) void k_group_write(GroupTileArgs a) {
 }
 
 __global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, uint32_t n_tiles4, const uint32_t *__restrict__ offs,
-                                                              uint32_t *__restrict__ keys_out, unsigned long long *__restrict__ vals_out) {
+                                                              uint32_t *__restrict__ keys_out, unsigned long long *__restrict__ vals_out,
+                                                              const uint32_t *__restrict__ digit_total, uint64_t *d_total) {      // offsets one row per digit: see radix_tile_scan
     const uint32_t n = (uint32_t) scan_count(a.n_bound, a.d_n);
-    if ((uint64_t) blockIdx.x * PDL_RADIX_TILE >= n) return;               // (uniform) block past the end
+    if ((uint64_t) blockIdx.x * PDL_RADIX_TILE >= n) {                     // (uniform) block past the end
+        if (digit_total && blockIdx.x == 0 && threadIdx.x == 0) *d_total = 0;      // (no records: no ranges)
+        return;
+    }
     __shared__ uint32_t s_key[PDL_RADIX_TILE];
     __shared__ unsigned long long s_val[PDL_RADIX_TILE];
     __shared__ uint16_t s_cnt[GW_WAVES][PDL_RADIX_BINS];   // per wave: running count of each byte value, then its base inside the block (16-bit: three workgroups per CU)
     __shared__ uint32_t s_tile_off[PDL_RADIX_BINS];
     __shared__ uint32_t s_goff[PDL_RADIX_BINS];
-    __shared__ uint32_t s_wsum[17];
+    __shared__ unsigned long long s_wsum[17];
     __shared__ unsigned long long s_own;
     const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
     const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
     const uint32_t tile = blockIdx.x * GW_WAVES + wave, t0 = tile * GW_TILE;
     const bool active = tile < tiles;                    // (wave-uniform; the last block may hold fewer than four tiles)
     for (int w = 0; w < GW_WAVES; w++) s_cnt[w][tid] = 0;
-    s_goff[tid] = offs[(size_t) tid * n_tiles4 + blockIdx.x];
+    const uint32_t goff = offs[(size_t) tid * n_tiles4 + blockIdx.x];
+    const uint32_t dtot = digit_total ? digit_total[tid] : 0u;
     if (tid == 0) s_own = 0;
     pdl_sync();
 
@@ -593,9 +598,11 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, u
     uint32_t wcnt[GW_WAVES];
 #pragma unroll
     for (int w = 0; w < GW_WAVES; w++) { wcnt[w] = s_cnt[w][tid]; tot += wcnt[w]; }
-    uint32_t tile_total;
-    const uint32_t ex = block_exclusive_scan_u32(tot, s_wsum, tile_total);
+    uint32_t tile_total, digit_base, grand_total;
+    const uint32_t ex = radix_tile_scan(tot, dtot, s_wsum, tile_total, digit_base, grand_total);
     s_tile_off[tid] = ex;
+    s_goff[tid] = goff + digit_base;                     // (offsets from the three-launch scan: no digit totals, base 0)
+    if (digit_total && blockIdx.x == 0 && tid == 0) *d_total = grand_total;
     uint32_t run = ex;
 #pragma unroll
     for (int w = 0; w < GW_WAVES; w++) { s_cnt[w][tid] = (uint16_t) run; run += wcnt[w]; }

@@ -56,6 +56,38 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_u32(uint32_t v, uint32_
     return res;
 }
 
+// The tile-level scan of a radix scatter (256 threads, thread d = digit d), two exclusive prefixes in ONE block scan: of the
+// tile's digit counts (returned; their sum, at most PDL_RADIX_TILE = 4096, in tile_total) and of the pass's digit totals
+// (digit_base = elements of the whole pass with a smaller digit, grand_total = all of them, below 2^32).  The second is what
+// offsets made one row per digit (k_rs_offsets, pdl_sort.hip) still lack; packed above the 13 bits of the first it costs the
+// scatter no barrier of its own.
+__device__ __forceinline__ uint32_t radix_tile_scan(uint32_t tile_cnt, uint32_t digit_tot, unsigned long long *s_wave /* [17] */, uint32_t &tile_total,
+                                                    uint32_t &digit_base, uint32_t &grand_total) {
+    const int lane = threadIdx.x & (PDL_WAVE - 1);
+    const int wave = threadIdx.x / PDL_WAVE;
+    const int nw = blockDim.x / PDL_WAVE;
+    const unsigned long long v = (unsigned long long) digit_tot << 13 | tile_cnt;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < PDL_WAVE; d <<= 1) {
+        const unsigned long long o = __shfl_up(inc, d, PDL_WAVE);
+        if (lane >= d) inc += o;
+    }
+    if (lane == PDL_WAVE - 1) s_wave[wave] = inc;
+    pdl_sync();
+    if (threadIdx.x == 0) {
+        unsigned long long run = 0;
+        for (int w = 0; w < nw; w++) { const unsigned long long t = s_wave[w]; s_wave[w] = run; run += t; }
+        s_wave[16] = run;
+    }
+    pdl_sync();
+    const unsigned long long res = inc - v + s_wave[wave], all = s_wave[16];
+    pdl_sync();
+    tile_total = (uint32_t) all & 0x1fffu; grand_total = (uint32_t) (all >> 13);
+    digit_base = (uint32_t) (res >> 13);
+    return (uint32_t) res & 0x1fffu;
+}
+
 // n = the element count; when d_n is set the count lives on the device (*d_n, at most n) and the grid was sized for the
 // bound n: the host does not have to read a count back before it can launch the kernels that depend on it.
 __device__ __forceinline__ uint64_t scan_count(uint64_t n, const uint64_t *d_n) {
@@ -85,10 +117,31 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_tile_sums(FlagF flag, uin
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
 }
 
-// one workgroup of 1024 threads; tile_sums becomes its own exclusive scan
+// one workgroup of 1024 threads; tile_sums becomes its own exclusive scan.  Up to 1024 x TS_ITEMS sums (33 M elements): a thread
+// holds TS_ITEMS consecutive sums in registers and ONE block scan does it; more: trips of 1024 with a carry.
+constexpr int TS_ITEMS = 16;
+__device__ __forceinline__ void scan_write_totals(uint32_t total, uint64_t *d_total, uint64_t *d_total2) {
+    *d_total = total;
+    if (d_total2) {                          // second copy of the total, as two words: its address may be only 4-byte aligned
+        reinterpret_cast<uint32_t *>(d_total2)[0] = total;
+        reinterpret_cast<uint32_t *>(d_total2)[1] = 0u;
+    }
+}
 static __global__ __launch_bounds__(1024) void k_scan_tile_scan(uint32_t *tile_sums, uint32_t n_tiles, uint64_t *d_total, uint64_t *d_total2) {
     __shared__ uint32_t s_wave[17];
     __shared__ uint32_t s_carry;
+    if (n_tiles <= 1024u * TS_ITEMS) {       // (uniform)
+        const uint32_t i0 = threadIdx.x * TS_ITEMS;
+        uint32_t v[TS_ITEMS], sum = 0;
+#pragma unroll
+        for (int j = 0; j < TS_ITEMS; j++) { v[j] = i0 + j < n_tiles ? tile_sums[i0 + j] : 0u; sum += v[j]; }
+        uint32_t total;
+        uint32_t ex = block_exclusive_scan_u32(sum, s_wave, total);
+#pragma unroll
+        for (int j = 0; j < TS_ITEMS; j++) { if (i0 + j < n_tiles) tile_sums[i0 + j] = ex; ex += v[j]; }
+        if (threadIdx.x == 0) scan_write_totals(total, d_total, d_total2);
+        return;
+    }
     if (threadIdx.x == 0) s_carry = 0;
     pdl_sync();
     for (uint32_t base = 0; base < n_tiles; base += 1024) {
@@ -102,13 +155,7 @@ static __global__ __launch_bounds__(1024) void k_scan_tile_scan(uint32_t *tile_s
         if (threadIdx.x == 0) s_carry = carry + total;
         pdl_sync();
     }
-    if (threadIdx.x == 0) {
-        *d_total = s_carry;
-        if (d_total2) {                      // second copy of the total, as two words: its address may be only 4-byte aligned
-            reinterpret_cast<uint32_t *>(d_total2)[0] = s_carry;
-            reinterpret_cast<uint32_t *>(d_total2)[1] = 0u;
-        }
-    }
+    if (threadIdx.x == 0) scan_write_totals(s_carry, d_total, d_total2);
 }
 
 // INLINE_PREFIX (short scans, <= SCAN_INLINE_TILES tiles): tile_sums holds the raw sums and every workgroup adds up the

@@ -68,25 +68,56 @@ struct RsOffsApply {
     __device__ void operator()(uint64_t i, uint32_t, uint32_t prefix) const { offs[i] = prefix; }
 };
 
+// The offsets of a pass in ONE launch: workgroup d takes the row counts[d][0 .. n_tiles) — the whole bound, tiles past a
+// device-side count hold zeros — and leaves the row's exclusive prefix in offs[d][..] and its sum in digit_total[d].  The
+// scatter turns the 256 sums into the digit bases itself (radix_tile_scan).  A thread holds RO_ITEMS consecutive entries
+// in registers, so a row of n_tiles entries takes n_tiles / RO_TRIP trips of one block scan each.
+constexpr int RO_THREADS = 1024, RO_ITEMS = 4, RO_TRIP = RO_THREADS * RO_ITEMS;
+constexpr uint32_t RO_MAX_TILES = 65536;                 // longer rows (16 trips): the three-launch scan over the whole table
+__global__ __launch_bounds__(RO_THREADS) void k_rs_offsets(const uint32_t *__restrict__ counts, uint32_t *__restrict__ offs, uint32_t n_tiles,
+                                                           uint32_t *__restrict__ digit_total) {
+    __shared__ uint32_t s_wave[17];
+    const uint32_t *row = counts + (size_t) blockIdx.x * n_tiles;
+    uint32_t *out = offs + (size_t) blockIdx.x * n_tiles;
+    uint32_t carry = 0;                                  // (uniform) sum of the trips before
+    for (uint32_t base = 0; base < n_tiles; base += RO_TRIP) {
+        const uint32_t i0 = base + threadIdx.x * RO_ITEMS;
+        uint32_t v[RO_ITEMS], sum = 0;
+#pragma unroll
+        for (int j = 0; j < RO_ITEMS; j++) { v[j] = i0 + j < n_tiles ? row[i0 + j] : 0u; sum += v[j]; }
+        uint32_t total;
+        uint32_t ex = block_exclusive_scan_u32(sum, s_wave, total) + carry;
+#pragma unroll
+        for (int j = 0; j < RO_ITEMS; j++) { if (i0 + j < n_tiles) out[i0 + j] = ex; ex += v[j]; }
+        carry += total;
+    }
+    if (threadIdx.x == 0) digit_total[blockIdx.x] = carry;
+}
+
 template <class KeyT, class ValT>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const KeyT *__restrict__ keys_in, const ValT *vals_in,
                                                            KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out, uint64_t n_bound,
                                                            const uint64_t *d_n, uint32_t shift, uint32_t n_tiles, const uint32_t *__restrict__ offs,
-                                                           uint32_t nbits) {       // significant bits of this pass's digit (the last pass of a sort may have fewer than 8)
+                                                           uint32_t nbits,         // significant bits of this pass's digit (the last pass of a sort may have fewer than 8)
+                                                           const uint32_t *__restrict__ digit_total, uint64_t *d_total) {     // offsets from k_rs_offsets: see radix_tile_scan
     const uint64_t n = scan_count(n_bound, d_n);
-    if ((uint64_t) blockIdx.x * (RS_THREADS * RS_ROUNDS) >= n) return;       // (uniform) tile past the end
+    if ((uint64_t) blockIdx.x * (RS_THREADS * RS_ROUNDS) >= n) {             // (uniform) tile past the end
+        if (digit_total && blockIdx.x == 0 && threadIdx.x == 0) *d_total = 0;      // (a count of zero on the device: the total is zero)
+        return;
+    }
     __shared__ KeyT s_key[RS_TILE];
     __shared__ ValT s_val[RS_TILE];
     __shared__ uint32_t s_cnt[RS_WAVES][RS_BINS];     // per wave: running count of each digit, then its base inside the tile
     __shared__ uint32_t s_tile_off[RS_BINS];          // start of each digit's run inside the tile
     __shared__ uint32_t s_goff[RS_BINS];              // global start of this tile's run of each digit
-    __shared__ uint32_t s_wsum[17];
+    __shared__ unsigned long long s_wsum[17];
 
     const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
     const uint64_t tile_base = (uint64_t) blockIdx.x * RS_TILE;
     const uint64_t wave_base = tile_base + (uint64_t) wave * RS_WAVE_SPAN;
     for (int w = 0; w < RS_WAVES; w++) s_cnt[w][tid] = 0;
-    s_goff[tid] = offs[(size_t) tid * n_tiles + blockIdx.x];
+    const uint32_t goff = offs[(size_t) tid * n_tiles + blockIdx.x];
+    const uint32_t dtot = digit_total ? digit_total[tid] : 0u;
     pdl_sync();
 
     KeyT key[RS_ROUNDS];
@@ -133,9 +164,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const KeyT *__restric
     uint32_t wcnt[RS_WAVES];
 #pragma unroll
     for (int w = 0; w < RS_WAVES; w++) { wcnt[w] = s_cnt[w][tid]; tot += wcnt[w]; }
-    uint32_t tile_total;
-    const uint32_t ex = block_exclusive_scan_u32(tot, s_wsum, tile_total);
+    uint32_t tile_total, digit_base, grand_total;
+    const uint32_t ex = radix_tile_scan(tot, dtot, s_wsum, tile_total, digit_base, grand_total);
     s_tile_off[tid] = ex;
+    s_goff[tid] = goff + digit_base;                     // (offsets from the three-launch scan: no digit totals, base 0)
+    if (digit_total && blockIdx.x == 0 && tid == 0) *d_total = grand_total;
     uint32_t run = ex;
 #pragma unroll
     for (int w = 0; w < RS_WAVES; w++) { s_cnt[w][tid] = run; run += wcnt[w]; }
@@ -165,24 +198,26 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const KeyT *__restric
 
 template <class KeyT, class ValT>
 void pdl_sort_pairs(pdl_ctx *c, KeyT *&keys_in, KeyT *&keys_out, ValT *&vals_in, ValT *&vals_out,
-                    uint64_t n, uint32_t end_bit, bool iota_values, const uint64_t *d_n, uint32_t begin_bit, bool keys_below_end_bit) {
+                    uint64_t n, uint32_t end_bit, bool iota_values, const uint64_t *d_n, uint32_t begin_bit, bool keys_below_end_bit,
+                    bool first_counts_filed) {
     if (n == 0) return;
     if (end_bit == 0) end_bit = 1;
     if (end_bit > sizeof(KeyT) * 8) end_bit = sizeof(KeyT) * 8;
     if (n >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "sort of %llu pairs needs 64-bit positions", (unsigned long long) n);
     const uint32_t n_tiles = (uint32_t) ((n + RS_TILE - 1) / RS_TILE);
     const size_t table = (size_t) RS_BINS * n_tiles;
-    c->sort_tmp.alloc(2 * table * sizeof(uint32_t));
-    uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table;
+    c->sort_tmp.alloc(pdl_radix_tmp_bytes(n));
+    uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table, *digit_total = offs + table;
     uint64_t *d_total = c->scalars.as<uint64_t>() + PDL_CTL_SCAN_TOTAL;
     const uint32_t passes = (end_bit + 7) / 8;
     for (uint32_t p = begin_bit / 8; p < passes; p++) {
         const uint32_t shift = p * 8;
-        hipLaunchKernelGGL((k_rs_hist<KeyT>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in, n, d_n, shift, n_tiles, counts);
-        scan_and_apply(c, table, RsCountFlag{counts}, RsOffsApply{offs}, d_total);
+        if (!(first_counts_filed && p == begin_bit / 8))
+            hipLaunchKernelGGL((k_rs_hist<KeyT>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in, n, d_n, shift, n_tiles, counts);
+        const uint32_t *totals = pdl_radix_offsets(c, counts, offs, n_tiles, d_total, digit_total);
         hipLaunchKernelGGL((k_rs_scatter<KeyT, ValT>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in,
                            (p == begin_bit / 8 && iota_values) ? (const ValT *) nullptr : vals_in, keys_out, vals_out, n, d_n, shift, n_tiles, offs,
-                           keys_below_end_bit ? std::min<uint32_t>(8, end_bit - shift) : 8u);
+                           keys_below_end_bit ? std::min<uint32_t>(8, end_bit - shift) : 8u, totals, d_total);
         PDL_HIP(hipGetLastError());
         std::swap(keys_in, keys_out);
         std::swap(vals_in, vals_out);
@@ -193,11 +228,21 @@ void pdl_sort_pairs(pdl_ctx *c, KeyT *&keys_in, KeyT *&keys_out, ValT *&vals_in,
     std::swap(vals_in, vals_out);
 }
 
-void pdl_radix_offsets(pdl_ctx *c, const uint32_t *counts, uint32_t *offs, uint32_t n_tiles, uint64_t *d_total) {
-    static_assert(PDL_RADIX_TILE == RS_TILE && PDL_RADIX_BINS == RS_BINS, "the caller's kernels use the tile shape of the sort");
-    scan_and_apply(c, (size_t) RS_BINS * n_tiles, RsCountFlag{counts}, RsOffsApply{offs}, d_total);
+bool pdl_radix_lean(const pdl_ctx *c, uint64_t n) {
+    return c->opt_lean_radix && !c->opt_onepass_scan && (n + RS_TILE - 1) / RS_TILE <= RO_MAX_TILES;
 }
 
-template void pdl_sort_pairs<uint32_t, uint32_t>(pdl_ctx *, uint32_t *&, uint32_t *&, uint32_t *&, uint32_t *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool);
-template void pdl_sort_pairs<uint64_t, uint32_t>(pdl_ctx *, uint64_t *&, uint64_t *&, uint32_t *&, uint32_t *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool);
-template void pdl_sort_pairs<uint32_t, unsigned long long>(pdl_ctx *, uint32_t *&, uint32_t *&, unsigned long long *&, unsigned long long *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool);
+const uint32_t *pdl_radix_offsets(pdl_ctx *c, const uint32_t *counts, uint32_t *offs, uint32_t n_tiles, uint64_t *d_total, uint32_t *digit_total) {
+    static_assert(PDL_RADIX_TILE == RS_TILE && PDL_RADIX_BINS == RS_BINS, "the caller's kernels use the tile shape of the sort");
+    if (!pdl_radix_lean(c, (uint64_t) n_tiles * RS_TILE)) {
+        scan_and_apply(c, (size_t) RS_BINS * n_tiles, RsCountFlag{counts}, RsOffsApply{offs}, d_total);
+        return nullptr;
+    }
+    hipLaunchKernelGGL(k_rs_offsets, dim3(RS_BINS), dim3(RO_THREADS), 0, c->stream, counts, offs, n_tiles, digit_total);
+    PDL_HIP(hipGetLastError());
+    return digit_total;
+}
+
+template void pdl_sort_pairs<uint32_t, uint32_t>(pdl_ctx *, uint32_t *&, uint32_t *&, uint32_t *&, uint32_t *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool, bool);
+template void pdl_sort_pairs<uint64_t, uint32_t>(pdl_ctx *, uint64_t *&, uint64_t *&, uint32_t *&, uint32_t *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool, bool);
+template void pdl_sort_pairs<uint32_t, unsigned long long>(pdl_ctx *, uint32_t *&, uint32_t *&, unsigned long long *&, unsigned long long *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool, bool);
