@@ -415,6 +415,41 @@ PDL_API int pdl_placement_of_edges(pdl_ctx *, const pdl_families *base, const ui
                                    const int32_t *src, const int32_t *dst, uint64_t n_edges, pdl_placement *out);
 PDL_API void pdl_free_placement(pdl_placement *);
 
+/* ---- place, for a batch: q new genomes placed in one pass, each on its own --------------------------------------------------
+ * pdl_place_batch: the n genes are cut into queries exactly as pdl_query_batch cuts them (gene_begin [n_queries + 1], from 0 to
+ * n, strictly increasing).  out[j] equals, field for field and byte for byte, what pdl_place_query returns for the genes of query
+ * j alone on the same context; only device_ms differs (an even share of its chunk's).  All ids in out[j] are query j's own union
+ * ids: its genes are N..N+n_j-1 of genome G, a novel family's label is its smallest query id in that numbering.  The queries
+ * never see each other: two that touch the same base component each get that component and do not fuse.  The base context is
+ * only read; its families are computed on first use, as by pdl_compute_families.  info[j] is filled as pdl_query_batch fills it.
+ * The queries are scored a chunk at a time (option "query_batch_bytes", as pdl_query_batch) and the best-hit filter runs once
+ * over a chunk's cells where they lie; only edges and the placements' small arrays come to the host.
+ *
+ * Refusals are decided before anything is returned; they leave every out[j] zeroed and the context as it was: every state
+ * pdl_place_query refuses (PDL_ERR_STATE), every argument and domain refusal of pdl_query_batch with its code (the absent-byte
+ * message names the first such query).  A refusal found in a later chunk returns nothing of the earlier chunks.  Each out[j] is
+ * freed with pdl_free_placement.
+ *
+ * pdl_placement_batch_of_edges: the batch form of pdl_placement_of_edges — one caller's base and n_queries edge lists laid end
+ * to end, list j = [edge_begin[j], edge_begin[j+1]) in query j's own union ids [0, N + n_query[j]).  out[j] equals
+ * pdl_placement_of_edges on list j alone (src / dst / score NULL).  The ids of every list are checked on the device, in one
+ * launch, before any id indexes anything: a list that names an id outside its own [0, N + n_query[j]) — which may be valid for a
+ * larger query of the same batch — or holds an edge with both ends below N gives PDL_ERR_ARGUMENT, and the message names the first
+ * failing query.  NULL pointers, n_queries == 0, an n_query[j] == 0, a decreasing edge_begin or a base whose fields contradict
+ * each other: PDL_ERR_ARGUMENT. */
+typedef struct {
+    uint32_t queries, chunks;
+    float device_ms;           /* the chunks' device time: queries, best-hit filter and placements */
+} pdl_place_batch_info;
+PDL_API int pdl_place_batch(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n+1] */,
+                            const uint32_t *gene_begin /* [n_queries+1] */, uint32_t n, uint32_t n_queries,
+                            pdl_placement *out /* [n_queries], each freed with pdl_free_placement */,
+                            pdl_query_info *info /* [n_queries] or NULL */, pdl_place_batch_info *binfo /* may be NULL */);
+PDL_API int pdl_placement_batch_of_edges(pdl_ctx *, const pdl_families *base, const uint32_t *genome_of /* [base->sequences] */,
+                                         uint32_t n_queries, const uint32_t *n_query /* [n_queries] genes of each query */,
+                                         const uint64_t *edge_begin /* [n_queries+1] */, const int32_t *src, const int32_t *dst,
+                                         pdl_placement *out /* [n_queries] */);
+
 /* Number of emitted cells per genome after pdl_score_all ([G], 0 for genomes outside the shard) */
 PDL_API int pdl_scores_counts(pdl_ctx *, uint32_t *out_counts);
 
@@ -444,7 +479,7 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * fields of pdl_timings; 0: only the totals and the join's launch time are taken — each event pair is two marker packets
  * between dispatches, a few microseconds of idle stream on a two-millisecond step), "low_memory" 0|1 (for genome batches on a large set: the buffers only the dictionary build needed are released after it —
  * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "query_batch_bytes" n > 0
- * (device bytes one chunk of pdl_query_batch may take before its join, default 2^30), "onepass_scan" 0|1 (prefix scans
+ * (device bytes one chunk of pdl_query_batch / pdl_place_batch may take before its join, default 2^30), "onepass_scan" 0|1 (prefix scans
  * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "lean_radix" 0|1
  * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"

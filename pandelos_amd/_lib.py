@@ -101,6 +101,13 @@ class PdlQueryBatchInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PdlPlaceBatchInfo(C.Structure):
+    _fields_ = [("queries", C.c_uint32), ("chunks", C.c_uint32), ("device_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PdlAppendInfo(C.Structure):
     _fields_ = [("residues", C.c_uint64), ("kmer_occurrences", C.c_uint64), ("records", C.c_uint64),
                 ("rank_sort_ms", C.c_float), ("merge_ms", C.c_float), ("device_ms", C.c_float)]
@@ -147,7 +154,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
-           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement")
+           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges")
 
 _lib = None
 
@@ -210,6 +217,10 @@ def load():
     lib.pdl_place_query.argtypes = [vp, vp, vp, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo)]; lib.pdl_place_query.restype = i32
     lib.pdl_placement_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, u64, C.POINTER(PdlPlacement)]
     lib.pdl_placement_of_edges.restype = i32
+    lib.pdl_place_batch.argtypes = [vp, vp, vp, vp, u32, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo), C.POINTER(PdlPlaceBatchInfo)]
+    lib.pdl_place_batch.restype = i32
+    lib.pdl_placement_batch_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, vp, vp, C.POINTER(PdlPlacement)]
+    lib.pdl_placement_batch_of_edges.restype = i32
     lib.pdl_free_placement.argtypes = [C.POINTER(PdlPlacement)]; lib.pdl_free_placement.restype = None
     lib.pdl_compute_edges.argtypes = [vp, u32, C.POINTER(PdlEdges)]; lib.pdl_compute_edges.restype = i32
     lib.pdl_free_edges.argtypes = [C.POINTER(PdlEdges)]; lib.pdl_free_edges.restype = None

@@ -37,6 +37,7 @@ template <class Body> static int guarded(pdl_ctx *c, Body &&body) { return guard
 //   pdl_query_scores         yes     yes        yes          -           yes
 //   pdl_query_batch          yes     yes        yes          -           yes
 //   pdl_place_query          yes     yes        yes         yes          yes
+//   pdl_place_batch          yes     yes        yes         yes          yes
 //   pdl_append_genomes       yes     yes        yes         yes          yes
 //   pdl_remove_genomes       yes     yes        yes         yes          yes
 //   pdl_compute_families     yes     yes        yes         yes           -
@@ -74,6 +75,26 @@ static void check_genes(const char *who, const uint8_t *residues, const uint64_t
     for (uint32_t i = 0; i < n; i++)
         if (offsets[i + 1] < offsets[i]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: offsets decrease at gene %u", who, i);
     if (!residues && offsets[n] > offsets[0]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL residues", who);
+}
+
+// The argument checks on a batch of queries (gene_begin [n_queries + 1] cuts the n genes) and the 31-bit limit of every union:
+// PDL_ERR_ARGUMENT, PDL_ERR_UNSUPPORTED
+static void check_batch(const pdl_ctx *c, const char *who, const void *out, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin,
+                        uint32_t n, uint32_t n_queries) {
+    if (n_queries == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: no query", who);
+    if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: no query gene", who);
+    if (!out || !offsets || !gene_begin) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
+    // gene_begin first: the 31-bit id limit is decided from it alone, before a single offset is read
+    if (gene_begin[0] != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: gene_begin[0] = %u, not 0", who, gene_begin[0]);
+    for (uint32_t q = 0; q < n_queries; q++)
+        if (gene_begin[q + 1] <= gene_begin[q] || gene_begin[q + 1] > n)
+            PDL_FAIL(PDL_ERR_ARGUMENT, "%s: gene_begin is not strictly increasing within the %u genes at query %u (a query needs a gene)", who, n, q);
+    if (gene_begin[n_queries] != n) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: gene_begin ends at %u, not at the %u genes", who, gene_begin[n_queries], n);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        const uint64_t nc = (uint64_t) c->N + (gene_begin[q + 1] - gene_begin[q]);
+        if (nc >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu genes in the union exceed the 31-bit gene ids", q, (unsigned long long) nc);
+    }
+    check_genes(who, residues, offsets, n);
 }
 
 template <class T> static T *xalloc(size_t n) {
@@ -677,15 +698,27 @@ void pdl_free_placement(pdl_placement *p) {
     memset(p, 0, sizeof(*p));
 }
 
-static void fill_placement(const pdl_place_result &r, bool with_edges, pdl_placement *out) {
+// (a batch's edges are the C arrays themselves: they change hands)
+static void fill_placement(pdl_place_result &r, bool with_edges, pdl_placement *out) {
     out->sequences = r.sequences; out->n_query = r.n_query; out->genomes = r.genomes;
-    out->edges = (uint32_t) r.src.size(); out->edges_phase1 = r.edges_phase1; out->groups = r.groups;
+    out->edges = (uint32_t) (r.c_edges.set ? r.c_edges.n : r.src.size()); out->edges_phase1 = r.edges_phase1; out->groups = r.groups;
     out->novel = r.novel; out->joined = r.joined; out->bridging = r.bridging; out->colliding = r.colliding; out->unplaced = r.unplaced;
     out->device_ms = r.device_ms;
-    if (with_edges) { out->src = dup_vec(r.src); out->dst = dup_vec(r.dst); out->score = dup_vec(r.score); }
+    if (with_edges && r.c_edges.set) { out->src = r.c_edges.src; out->dst = r.c_edges.dst; out->score = r.c_edges.score; r.c_edges.release(); }
+    else if (with_edges) { out->src = dup_vec(r.src); out->dst = dup_vec(r.dst); out->score = dup_vec(r.score); }
     out->family_of = dup_vec(r.family_of); out->is_node = dup_vec(r.is_node); out->group_label = dup_vec(r.group_label);
     out->group_query_off = dup_vec(r.group_query_off); out->group_query = dup_vec(r.group_query);
     out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
+}
+
+// the context's families, computed on first use as by pdl_compute_families (-> a return code; the device is the context's then)
+static int families_ready_locked(pdl_ctx *c) {
+    const int rc = c->scored ? PDL_OK : score_all_locked(c);
+    if (rc != PDL_OK) return rc;
+    PDL_HIP(hipSetDevice(c->device));
+    if (!c->edges_valid) pdl_run_bbh_all(c);
+    if (!c->fam_valid) pdl_run_families_of_context(c);
+    return PDL_OK;
 }
 
 int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_placement *out, pdl_query_info *info) {
@@ -697,11 +730,8 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         require_state(c, "pdl_place_query", NEEDS_WHOLE_SET, "pdl_placement_of_edges");
         if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL pointer");
         check_genes("pdl_place_query", residues, offsets, n_query);
-        int rc = c->scored ? PDL_OK : score_all_locked(c);
+        int rc = families_ready_locked(c);
         if (rc != PDL_OK) return rc;
-        PDL_HIP(hipSetDevice(c->device));
-        if (!c->edges_valid) pdl_run_bbh_all(c);
-        if (!c->fam_valid) pdl_run_families_of_context(c);
         pdl_place_result r;
         pdl_query_info qi{};
         pdl_run_place_query(c, residues, offsets, n_query, r, &qi);
@@ -711,73 +741,145 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     }, [&] { if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); });
 }
 
+// A caller's base families behind their checks, on the device (c->pb.up_*) with n_edges edges of the caller's: what
+// pdl_placement_of_edges and its batch form share.  The base is indexed by its own fields on the device: they must be what K-fam
+// writes (labels are smallest members, families in label order, members ascending, every node in exactly one family).
+static void check_base_pointers(const char *who, const pdl_families *base, const uint32_t *genome_of, const int32_t *src, const int32_t *dst, uint64_t n_edges) {
+    if (!base || (n_edges && (!src || !dst))) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
+    const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
+    if (N && (!genome_of || !base->component_of || !base->is_node)) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
+    if (!base->family_off || (nodes && !base->family_genes) || (F && !base->collides)) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer in the base families", who);
+}
+// `of_label` is the caller's: the copy that reads it is waited for by the placement behind it.
+static PlaceBase upload_base(pdl_ctx *c, const char *who, const pdl_families *base, const uint32_t *genome_of, const int32_t *src, const int32_t *dst, uint64_t n_edges,
+                             std::vector<uint32_t> &of_label) {
+    const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
+    if (nodes > N || F > nodes || base->family_off[0] != 0 || base->family_off[F] != nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (counts)", who);
+    of_label.assign(N, 0);
+    std::vector<uint8_t> listed(N, 0);             // the gene is a member of exactly one family
+    for (uint32_t f = 0; f < F; f++) {
+        const uint32_t a = base->family_off[f], b = base->family_off[f + 1];
+        if (b <= a || b > nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (family_off at %u)", who, f);
+        const uint32_t label = base->family_genes[a];
+        if (f && label <= base->family_genes[base->family_off[f - 1]])
+            PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (family %u is not behind family %u in label order)", who, f, f - 1);
+        for (uint32_t j = a; j < b; j++) {
+            const uint32_t g = base->family_genes[j];
+            if (g >= N || listed[g] || !base->is_node[g] || base->component_of[g] != label || (j > a && g <= base->family_genes[j - 1]))
+                PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (member %u of family %u)", who, j - a, f);
+            listed[g] = 1;
+        }
+        of_label[label] = f;
+    }
+    uint32_t g_max = 0;
+    for (uint32_t i = 0; i < N; i++) {
+        g_max = std::max(g_max, genome_of[i]);
+        // a node is listed in a family (its component_of was checked there: a label below N); any other gene is its own component
+        if (base->is_node[i] ? !listed[i] : base->component_of[i] != i)
+            PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (gene %u)", who, i);
+    }
+    if (g_max >= 0x7fffffffu) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: genome id %u (ids below 2^31 - 1)", who, g_max);
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_ctx::PlaceBufs &b = c->pb;
+    hipStream_t st = c->stream;
+    b.up_comp.alloc((size_t) N * 4); b.up_is_node.alloc(N); b.up_fam_of_label.alloc((size_t) N * 4); b.up_gen.alloc((size_t) N * 4);
+    b.up_fam_off.alloc(((size_t) F + 1) * 4); b.up_fam_genes.alloc((size_t) nodes * 4); b.up_collides.alloc(F);
+    if (N) {
+        PDL_HIP(hipMemcpyAsync(b.up_comp.p, base->component_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(b.up_is_node.p, base->is_node, N, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(b.up_fam_of_label.p, of_label.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
+    }
+    PDL_HIP(hipMemcpyAsync(b.up_fam_off.p, base->family_off, ((size_t) F + 1) * 4, hipMemcpyHostToDevice, st));
+    if (nodes) PDL_HIP(hipMemcpyAsync(b.up_fam_genes.p, base->family_genes, (size_t) nodes * 4, hipMemcpyHostToDevice, st));
+    if (F) PDL_HIP(hipMemcpyAsync(b.up_collides.p, base->collides, F, hipMemcpyHostToDevice, st));
+    if (n_edges) {
+        b.up_src.alloc(n_edges * 4); b.up_dst.alloc(n_edges * 4);
+        PDL_HIP(hipMemcpyAsync(b.up_src.p, src, n_edges * 4, hipMemcpyHostToDevice, st));
+        PDL_HIP(hipMemcpyAsync(b.up_dst.p, dst, n_edges * 4, hipMemcpyHostToDevice, st));
+    }
+    PlaceBase B;
+    B.comp = b.up_comp.as<uint32_t>(); B.is_node = b.up_is_node.as<uint8_t>(); B.collides = b.up_collides.as<uint8_t>();
+    B.fam_off = b.up_fam_off.as<uint32_t>(); B.fam_genes = b.up_fam_genes.as<uint32_t>(); B.fam_of_label = b.up_fam_of_label.as<uint32_t>();
+    B.genome_of = b.up_gen.as<uint32_t>(); B.N = N; B.G = N ? g_max + 1 : 0;
+    return B;
+}
+
 int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t *genome_of, uint32_t n_query, const int32_t *src, const int32_t *dst,
                            uint64_t n_edges, pdl_placement *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, Lock::held, [&]() -> int {
-        if (!base || (n_edges && (!src || !dst))) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
-        const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
-        if (N && (!genome_of || !base->component_of || !base->is_node)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer");
-        if (!base->family_off || (nodes && !base->family_genes) || (F && !base->collides)) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: NULL pointer in the base families");
+        check_base_pointers("pdl_placement_of_edges", base, genome_of, src, dst, n_edges);
         if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: no query gene");
-        if (n_edges >= 0x7fffffffull || (uint64_t) N + n_query >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_placement_of_edges: 2^31 genes or edges and more");
-        // the base is indexed by its own fields on the device: they must be what K-fam writes (labels are smallest members, families
-        // in label order, members ascending, every node in exactly one family)
-        if (nodes > N || F > nodes || base->family_off[0] != 0 || base->family_off[F] != nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (counts)");
-        std::vector<uint32_t> of_label(N, 0);
-        std::vector<uint8_t> listed(N, 0);             // the gene is a member of exactly one family
-        for (uint32_t f = 0; f < F; f++) {
-            const uint32_t a = base->family_off[f], b = base->family_off[f + 1];
-            if (b <= a || b > nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (family_off at %u)", f);
-            const uint32_t label = base->family_genes[a];
-            if (f && label <= base->family_genes[base->family_off[f - 1]])
-                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (family %u is not behind family %u in label order)", f, f - 1);
-            for (uint32_t j = a; j < b; j++) {
-                const uint32_t g = base->family_genes[j];
-                if (g >= N || listed[g] || !base->is_node[g] || base->component_of[g] != label || (j > a && g <= base->family_genes[j - 1]))
-                    PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (member %u of family %u)", j - a, f);
-                listed[g] = 1;
-            }
-            of_label[label] = f;
-        }
-        uint32_t g_max = 0;
-        for (uint32_t i = 0; i < N; i++) {
-            g_max = std::max(g_max, genome_of[i]);
-            // a node is listed in a family (its component_of was checked there: a label below N); any other gene is its own component
-            if (base->is_node[i] ? !listed[i] : base->component_of[i] != i)
-                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: inconsistent base families (gene %u)", i);
-        }
-        if (g_max >= 0x7fffffffu) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: genome id %u (ids below 2^31 - 1)", g_max);
-        PDL_HIP(hipSetDevice(c->device));
+        if (n_edges >= 0x7fffffffull || (uint64_t) base->sequences + n_query >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_placement_of_edges: 2^31 genes or edges and more");
+        std::vector<uint32_t> of_label;
+        const PlaceBase B = upload_base(c, "pdl_placement_of_edges", base, genome_of, src, dst, n_edges, of_label);
         pdl_ctx::PlaceBufs &b = c->pb;
-        hipStream_t st = c->stream;
-        b.up_comp.alloc((size_t) N * 4); b.up_is_node.alloc(N); b.up_fam_of_label.alloc((size_t) N * 4); b.up_gen.alloc((size_t) N * 4);
-        b.up_fam_off.alloc(((size_t) F + 1) * 4); b.up_fam_genes.alloc((size_t) nodes * 4); b.up_collides.alloc(F);
-        if (N) {
-            PDL_HIP(hipMemcpyAsync(b.up_comp.p, base->component_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
-            PDL_HIP(hipMemcpyAsync(b.up_is_node.p, base->is_node, N, hipMemcpyHostToDevice, st));
-            PDL_HIP(hipMemcpyAsync(b.up_fam_of_label.p, of_label.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
-            PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
-        }
-        PDL_HIP(hipMemcpyAsync(b.up_fam_off.p, base->family_off, ((size_t) F + 1) * 4, hipMemcpyHostToDevice, st));
-        if (nodes) PDL_HIP(hipMemcpyAsync(b.up_fam_genes.p, base->family_genes, (size_t) nodes * 4, hipMemcpyHostToDevice, st));
-        if (F) PDL_HIP(hipMemcpyAsync(b.up_collides.p, base->collides, F, hipMemcpyHostToDevice, st));
-        if (n_edges) {
-            b.up_src.alloc(n_edges * 4); b.up_dst.alloc(n_edges * 4);
-            PDL_HIP(hipMemcpyAsync(b.up_src.p, src, n_edges * 4, hipMemcpyHostToDevice, st));
-            PDL_HIP(hipMemcpyAsync(b.up_dst.p, dst, n_edges * 4, hipMemcpyHostToDevice, st));
-        }
-        PlaceBase B;
-        B.comp = b.up_comp.as<uint32_t>(); B.is_node = b.up_is_node.as<uint8_t>(); B.collides = b.up_collides.as<uint8_t>();
-        B.fam_off = b.up_fam_off.as<uint32_t>(); B.fam_genes = b.up_fam_genes.as<uint32_t>(); B.fam_of_label = b.up_fam_of_label.as<uint32_t>();
-        B.genome_of = b.up_gen.as<uint32_t>(); B.N = N; B.G = N ? g_max + 1 : 0;
         pdl_place_result r;
         pdl_run_place_edges(c, B, n_query, b.up_src.as<int32_t>(), b.up_dst.as<int32_t>(), n_edges, r);
         fill_placement(r, false, out);
         return PDL_OK;
     }, [&] { pdl_free_placement(out); });
+}
+
+int pdl_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
+                    pdl_placement *out, pdl_query_info *info, pdl_place_batch_info *binfo) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out && n_queries) memset(out, 0, sizeof(*out) * (size_t) n_queries);
+    if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
+    if (binfo) memset(binfo, 0, sizeof(*binfo));
+    return guarded(c, Lock::held, [&]() -> int {
+        require_state(c, "pdl_place_batch", NEEDS_WHOLE_SET, "pdl_placement_batch_of_edges");
+        check_batch(c, "pdl_place_batch", out, residues, offsets, gene_begin, n, n_queries);
+        int rc = families_ready_locked(c);
+        if (rc != PDL_OK) return rc;
+        std::vector<pdl_place_result> r;
+        std::vector<pdl_query_info> qi(n_queries);
+        uint32_t chunks = 0;
+        float device_ms = 0.f;
+        pdl_run_place_batch(c, residues, offsets, gene_begin, n, n_queries, r, qi.data(), &chunks, &device_ms);
+        for (uint32_t q = 0; q < n_queries; q++) fill_placement(r[q], true, &out[q]);      // (only now: every chunk is through)
+        if (info) memcpy(info, qi.data(), sizeof(*info) * (size_t) n_queries);
+        if (binfo) { binfo->queries = n_queries; binfo->chunks = chunks; binfo->device_ms = device_ms; }
+        return PDL_OK;
+    }, [&] {
+        if (out) for (uint32_t q = 0; q < n_queries; q++) pdl_free_placement(&out[q]);
+        if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
+        if (binfo) memset(binfo, 0, sizeof(*binfo));
+    });
+}
+
+int pdl_placement_batch_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t *genome_of, uint32_t n_queries, const uint32_t *n_query,
+                                 const uint64_t *edge_begin, const int32_t *src, const int32_t *dst, pdl_placement *out) {
+    if (!c) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (out && n_queries) memset(out, 0, sizeof(*out) * (size_t) n_queries);
+    return guarded(c, Lock::held, [&]() -> int {
+        const char *who = "pdl_placement_batch_of_edges";
+        if (n_queries == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: no query", who);
+        if (!out || !base || !n_query || !edge_begin) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
+        for (uint32_t q = 0; q < n_queries; q++) {
+            if (n_query[q] == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: query %u: no query gene", who, q);
+            if (edge_begin[q + 1] < edge_begin[q]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: edge_begin decreases at query %u", who, q);
+        }
+        for (uint32_t q = 0; q < n_queries; q++)
+            if (edge_begin[q + 1] - edge_begin[q] >= 0x7fffffffull || (uint64_t) base->sequences + n_query[q] >= 0x7fffffffull)
+                PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s: query %u: 2^31 genes or edges and more", who, q);
+        // the lists as one upload: [edge_begin[0], edge_begin[n_queries]) of the caller's arrays, offsets from 0 from here on
+        const uint64_t e0 = edge_begin[0], E = edge_begin[n_queries] - e0;
+        check_base_pointers(who, base, genome_of, src, dst, E);
+        std::vector<uint64_t> rel((size_t) n_queries + 1);
+        for (uint32_t q = 0; q <= n_queries; q++) rel[q] = edge_begin[q] - e0;
+        std::vector<uint32_t> of_label;
+        const PlaceBase B = upload_base(c, who, base, genome_of, src ? src + e0 : nullptr, dst ? dst + e0 : nullptr, E, of_label);
+        std::vector<pdl_place_result> r;
+        pdl_run_place_batch_edges(c, B, n_queries, n_query, rel.data(), c->pb.up_src.as<int32_t>(), c->pb.up_dst.as<int32_t>(), r);
+        for (uint32_t q = 0; q < n_queries; q++) fill_placement(r[q], false, &out[q]);
+        return PDL_OK;
+    }, [&] { if (out) for (uint32_t q = 0; q < n_queries; q++) pdl_free_placement(&out[q]); });
 }
 
 int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
@@ -985,20 +1087,7 @@ int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     if (binfo) memset(binfo, 0, sizeof(*binfo));
     return guarded(c, Lock::held, [&]() -> int {
         require_state(c, "pdl_query_batch", NEEDS_QUERY);
-        if (n_queries == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query");
-        if (n == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: no query gene");
-        if (!out || !offsets || !gene_begin) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: NULL pointer");
-        // gene_begin first: the 31-bit id limit is decided from it alone, before a single offset is read
-        if (gene_begin[0] != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin[0] = %u, not 0", gene_begin[0]);
-        for (uint32_t q = 0; q < n_queries; q++)
-            if (gene_begin[q + 1] <= gene_begin[q] || gene_begin[q + 1] > n)
-                PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin is not strictly increasing within the %u genes at query %u (a query needs a gene)", n, q);
-        if (gene_begin[n_queries] != n) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_batch: gene_begin ends at %u, not at the %u genes", gene_begin[n_queries], n);
-        for (uint32_t q = 0; q < n_queries; q++) {
-            const uint64_t nc = (uint64_t) c->N + (gene_begin[q + 1] - gene_begin[q]);
-            if (nc >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu genes in the union exceed the 31-bit gene ids", q, (unsigned long long) nc);
-        }
-        check_genes("pdl_query_batch", residues, offsets, n);
+        check_batch(c, "pdl_query_batch", out, residues, offsets, gene_begin, n, n_queries);
         PDL_HIP(hipSetDevice(c->device));
         pdl_run_query_batch(c, residues, offsets, gene_begin, n, n_queries, out, info, binfo);
         return PDL_OK;

@@ -16,11 +16,15 @@
 #include "pdl_scan.h"
 
 // Where a cell's row and column sit in the maxima tables.  BbhTasks: the genome tasks of a scored context.  pdl_place.h adds the
-// one task of a query block (BbhQueryBlock); the three kernels below are the filter for both.
+// one task of a query block (BbhQueryBlock), pdl_place_batch.h the queries of a chunk (BbhQueryChunk), where a gene id alone does
+// not say whose it is: `part` is what the locator makes of the cell's index (nothing, for the first two).  The three kernels
+// below are the filter for all.
 struct BbhTasks {
     const uint32_t *taskpos_of, *task_lg, *genome_of;
-    __device__ uint32_t pos(uint32_t gene) const { return taskpos_of[gene]; }          // row of MS / thr
-    __device__ uint32_t task(uint32_t p) const { return task_lg[p]; }                  // row of CM / inter_max
+    __device__ uint32_t part(uint32_t) const { return 0u; }
+    __device__ uint32_t pos(uint32_t, uint32_t gene) const { return taskpos_of[gene]; }    // row of MS / thr
+    __device__ uint32_t task(uint32_t, uint32_t p) const { return task_lg[p]; }            // row of CM / inter_max
+    __device__ uint32_t cm_at(uint32_t) const { return 0u; }                               // where the task's CM row starts inside its N floats
     __device__ uint32_t genome(uint32_t gene) const { return genome_of[gene]; }
 };
 template <class L>
@@ -39,10 +43,10 @@ __global__ __launch_bounds__(256) void k_bbh_mark(BbhArgs<L> a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.Z) return;
     const uint32_t r = (uint32_t) a.row[i], c = (uint32_t) a.col[i];
-    const uint32_t p = a.at.pos(r), lg = a.at.task(p);
+    const uint32_t w = a.at.part(i), p = a.at.pos(w, r), lg = a.at.task(w, p);
     const uint32_t g1 = a.at.genome(r), g2 = a.at.genome(c);
     const float s = a.score[i];
-    const bool bbh = g1 != g2 && s == a.MS[(size_t) p * a.G + g2] && s == a.CM[(size_t) lg * a.N + c];
+    const bool bbh = g1 != g2 && s == a.MS[(size_t) p * a.G + g2] && s == a.CM[(size_t) lg * a.N + a.at.cm_at(w) + c];
     a.kind[i] = bbh ? 1 : 0;
     if (bbh && s < 1.0f) atomicMax(&a.inter_max[(size_t) lg * a.G + g2], __float_as_uint(s));       // (positive floats order like their bits)
 }
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void k_bbh_threshold(BbhArgs<L> a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.Z || a.kind[i] != 1) return;
     const uint32_t r = (uint32_t) a.row[i];
-    const uint32_t p = a.at.pos(r), lg = a.at.task(p);
+    const uint32_t w = a.at.part(i), p = a.at.pos(w, r), lg = a.at.task(w, p);
     atomicMin(&a.thr[p], a.inter_max[(size_t) lg * a.G + a.at.genome((uint32_t) a.col[i])]);
 }
 template <class L>
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void k_bbh_intra(BbhArgs<L> a) {
     const uint32_t r = (uint32_t) a.row[i], c = (uint32_t) a.col[i];
     const uint32_t g = a.at.genome(r);
     if (g != a.at.genome(c) || r >= c) return;
-    const uint32_t p = a.at.pos(r), pc = a.at.pos(c);
+    const uint32_t w = a.at.part(i), p = a.at.pos(w, r), pc = a.at.pos(w, c);
     const float s = a.score[i];
     if (s == a.MS[(size_t) p * a.G + g] && s == a.MS[(size_t) pc * a.G + g] && s >= __uint_as_float(a.thr[p])) a.kind[i] = 2;
 }
@@ -187,3 +191,4 @@ void pdl_run_families_of_context(pdl_ctx *c) {
 }
 
 #include "pdl_place.h"           // K-place: a query's edges and their placement on these families (pdl_place_query)
+#include "pdl_place_batch.h"     // ... for a batch of queries (pdl_place_batch)

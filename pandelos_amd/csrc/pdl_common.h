@@ -113,6 +113,18 @@ enum : size_t {
     PDL_PL_WORDS = 16,
 };
 
+// ---- layout of pdl_ctx::pb.bctl (u64 words): K-place for a batch (pdl_place_batch.h).  The words of a chunk of queries in front
+// of the placement stages; those stages count in the PDL_PL_* words above, once per chunk (NODES .. MEMBERS are the chunk's, the
+// queries' shares are cut out of the arrays on the host).  Cleared at the start of every chunk; each word has one life and one
+// reader on the host.
+enum : size_t {
+    PDL_PB_EDGES_1 = 0,         // K-bbh over the chunk's cells: phase-1 cells (two edges each) and phase-2 cells of all its queries,
+    PDL_PB_EDGES_2 = 1,         //   totals of the two edge scans; read together with the prefixes at every query's first cell
+    PDL_PB_BAD_QUERY = 2,       // PB-check (callers' lists): number of failing queries behind the first one that fails, as
+                                //   n_queries - (its index), 0 when none fails (an atomicMax finds the FIRST); read before any id is used
+    PDL_PB_WORDS = 4,
+};
+
 // ---- layout of pdl_ctx::join_ctr (u32 words): cursors and counters of one scoring pass, cleared by score_join ---------------
 // A tier draws rows through its cursor and lists the rows it hands on; the count of that list is the next tier's work size.
 enum : uint32_t {
@@ -260,6 +272,22 @@ struct pdl_place_result {
     std::vector<uint32_t> family_of, group_label, group_query_off, group_query, group_base_off, group_base;
     std::vector<uint8_t> is_node, group_collides;
     float device_ms = 0.f;
+    // A batch hands a query's edges over as the C arrays themselves (malloc, `n` entries each; pdl_api.hip's fill_placement takes
+    // them), cut out of the chunk's pinned staging in one pass: src / dst / score above stay empty then.
+    struct CEdges {
+        int32_t *src = nullptr, *dst = nullptr; float *score = nullptr; uint64_t n = 0; bool set = false;
+        CEdges() = default;
+        CEdges(const CEdges &) = delete;
+        CEdges &operator=(const CEdges &) = delete;
+        CEdges(CEdges &&o) noexcept { *this = std::move(o); }
+        CEdges &operator=(CEdges &&o) noexcept {
+            if (this != &o) { drop(); src = o.src; dst = o.dst; score = o.score; n = o.n; set = o.set; o.release(); }
+            return *this;
+        }
+        void release() { src = dst = nullptr; score = nullptr; n = 0; set = false; }      // (the arrays have a new owner)
+        void drop() { free(src); free(dst); free(score); release(); }
+        ~CEdges() { drop(); }
+    } c_edges;
 };
 // the base network's families as K-place reads them (device pointers): the context's own, uploaded once from c->fam, or a caller's
 struct PlaceBase {
@@ -271,6 +299,21 @@ struct PlaceBase {
 // the maxima in c->qb.MS / c->qb.CM, the stretches of device work in c->qb.spans
 struct pdl_query_run {
     uint64_t Z = 0, cap = 1, residues = 0, kmers = 0, records = 0, matched = 0, cost = 0;
+};
+// what the host knows of one query of a batch before the device is asked (pdl_query_batch.h)
+struct QBQuery {
+    uint32_t g0, n;                 // its genes in the caller's arrays
+    uint64_t Rq, Mq;                // residues, k-mers
+    uint64_t bytes;                 // device memory the stages before the join need for it (the chunking's weight)
+};
+// what the device half of a chunk of a query batch (pdl_query_batch.h, pdl_run_query_chunk_device) leaves: Z ordered cells in
+// c->qbb.cells (five arrays of `cap`), query after query; MS [genes][G + 1] by chunk gene and the queries' CM slices [N + n_q] at
+// q * N + gene_begin[q] in c->qbb.MS / c->qbb.CM; gene_begin also on the device (c->qbb.gene_begin)
+struct pdl_query_chunk {
+    uint32_t nq = 0, genes = 0;
+    uint64_t Z = 0, cap = 1;
+    std::vector<uint32_t> gene_begin;                            // [nq + 1] first chunk gene of every query
+    std::vector<uint64_t> cells, records, matched, cost;         // [nq]
 };
 
 // ---- the context --------------------------------------------------------------------------------
@@ -480,6 +523,8 @@ struct pdl_ctx {
         uint64_t base_serial = 0;                   // c->fam_serial the copy was made at (0: none)
         DevBuf up_comp, up_is_node, up_collides, up_fam_off, up_fam_genes, up_fam_of_label, up_gen, up_src, up_dst;   // a caller's base and edges
         DevBuf ctl;                                 // u64 [PDL_PL_WORDS]
+        DevBuf bctl, btab, blay, up_edge_begin, up_n_query;   // a batch: u64 [PDL_PB_WORDS]; cell offsets and picked prefixes; the queries' layout; the callers' lists'
+        QSpans bspans;                              // ... and the stretch of device work of a chunk's K-bbh
         DevBuf kind, tab, e_src, e_dst, e_score;    // K-bbh over the query block: as bbh_kind, bbh_tab, e_* of the context
         DevBuf parent, is_node, same_deg, family_of, gcol, grp_of_label, gq_off, gb_off, group_base, mpre;
         DevBuf mk_a, mk_b, mv_a, mv_b;              // (root, query gene) sort
@@ -657,6 +702,20 @@ void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, co
 // K-query for a batch (pdl_query_batch.h): q genomes, each scored on its own; gene_begin [n_queries + 1] cuts the n genes
 void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
                          pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo);
+// ... its plan (the domain refusals, every query's sizes and weight — column_bytes more per column of its union; -> the HBM tables'
+// columns), its chunking rule and the device
+// half of one chunk [qa, qe): everything up to the ordered cells, which stay in HBM (K-place for a batch filters them there)
+uint32_t pdl_query_batch_plan(pdl_ctx *c, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries, std::vector<QBQuery> &qs,
+                              uint64_t column_bytes);
+uint32_t pdl_query_batch_chunk_end(const pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa);
+pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
+                                           uint32_t hbm_cols);
+// K-place for a batch (pdl_place_batch.h, pdl_bbh.hip): out [n_queries]; info [n_queries] or NULL
+void pdl_run_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
+                         std::vector<pdl_place_result> &out, pdl_query_info *info, uint32_t *chunks, float *device_ms);
+// ... and of callers' lists on a caller's base: n_query [n_queries], edge_begin [n_queries + 1] from 0, the lists end to end on the device
+void pdl_run_place_batch_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_queries, const uint32_t *n_query, const uint64_t *edge_begin,
+                               const int32_t *d_src, const int32_t *d_dst, std::vector<pdl_place_result> &out);
 void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad);      // k_q_alpha over device bytes (pdl_query.h)
 [[noreturn]] void pdl_fail_absent_byte(uint64_t bad_word, const char *who);                             // ... and the refusal that names the byte
 // K-append (pdl_append.h, pdl_dict.hip): the n genes of residues/offsets become genes N.. of the context; genome_ids [n] are their

@@ -25,7 +25,8 @@
 //
 // Work: the query's edges plus the members of bridged components; of the work nothing but the parent copy is proportional to N.
 // Memory is: parent and grp_of_label (indexed by label, touched at the groups' labels only) hold N + n words each.
-// A batch can wrap the kernels: they take the id origin N and the edge lists as arguments and keep no state between launches.
+// The kernels take the id origin N and the edge lists as arguments and keep no state between launches: pdl_place_batch.h runs
+// them over every query's stretch of a chunk's edges.
 #pragma once
 
 #include "pdl_common.h"
@@ -35,8 +36,10 @@
 // the one task of a query block: MS [n][G + 1], CM [N + n], inter_max [G + 1], thr [n]
 struct BbhQueryBlock {
     const uint32_t *genome_b; uint32_t N, G;
-    __device__ uint32_t pos(uint32_t gene) const { return gene - N; }
-    __device__ uint32_t task(uint32_t) const { return 0u; }
+    __device__ uint32_t part(uint32_t) const { return 0u; }
+    __device__ uint32_t pos(uint32_t, uint32_t gene) const { return gene - N; }
+    __device__ uint32_t task(uint32_t, uint32_t) const { return 0u; }
+    __device__ uint32_t cm_at(uint32_t) const { return 0u; }
     __device__ uint32_t genome(uint32_t gene) const { return gene < N ? genome_b[gene] : G; }
 };
 
@@ -178,10 +181,12 @@ static uint64_t *place_begin(pdl_ctx *c) {
 }
 
 // One placement.  list[0] / list[1]: device edge lists in union ids (the query block's two phases, or a caller's list and nothing).
-// mirrored0: list 0 holds every pair in both directions.  caller: ids are checked first and query-query edges (looked for in list
-// 0) may repeat; otherwise they are list 1's, distinct.  `spans` has a stretch open on entry and none on return.
+// mirrored0: list 0 holds every pair in both directions.  caller: query-query edges (looked for in list 0) may repeat; otherwise
+// they are list 1's, distinct.  check_ids: a caller's ids are checked first (a batch has checked all its lists at once).
+// `spans` has a stretch open on entry and none on return.
+// place_run_batch (pdl_place_batch.h) is its twin over the queries of a chunk, stage for stage: a change to one belongs into the other.
 static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t *const src[2], const int32_t *const dst[2], const uint64_t n_edges[2],
-                      bool mirrored0, bool caller, QSpans &spans, pdl_place_result &out) {
+                      bool mirrored0, bool caller, bool check_ids, QSpans &spans, pdl_place_result &out) {
     hipStream_t st = c->stream;
     pdl_ctx::PlaceBufs &b = c->pb;
     const uint32_t N = B.N;
@@ -197,7 +202,7 @@ static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t 
     uint32_t *grp_of_label = b.grp_of_label.as<uint32_t>(), *gq_off = b.gq_off.as<uint32_t>(), *gb_off = b.gb_off.as<uint32_t>();
     uint8_t *is_node = b.is_node.as<uint8_t>(), *gcol = b.gcol.as<uint8_t>();
 
-    if (caller && n_edges[0]) {                       // P-check
+    if (check_ids && n_edges[0]) {                    // P-check
         hipLaunchKernelGGL(k_place_check, fam_grid(n_edges[0]), dim3(256), 0, st, src[0], dst[0], (uint32_t) n_edges[0], N, NC, ctl + PDL_PL_BAD_EDGES);
         PDL_HIP(hipGetLastError());
         spans.end();
@@ -387,7 +392,7 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     }
     const int32_t *src[2] = {src1, src2}, *dst[2] = {dst1, dst2};
     const uint64_t ne[2] = {n1, n2};
-    place_run(c, B, n, src, dst, ne, true, false, spans, out);
+    place_run(c, B, n, src, dst, ne, true, false, false, spans, out);
     // the edges themselves, in the host's insertion order: phase 1, then phase 2
     out.src.resize(n1 + n2); out.dst.resize(n1 + n2); out.score.resize(n1 + n2);
     if (n1) {
@@ -419,5 +424,5 @@ void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, co
     spans.begin();
     const int32_t *src[2] = {d_src, nullptr}, *dst[2] = {d_dst, nullptr};
     const uint64_t ne[2] = {n_edges, 0};
-    place_run(c, base, n_query, src, dst, ne, false, true, spans, out);
+    place_run(c, base, n_query, src, dst, ne, false, true, true, spans, out);
 }

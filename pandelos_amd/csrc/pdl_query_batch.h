@@ -22,6 +22,11 @@
 //                           N + (largest query of the batch) columns
 //   B-order  k_order_rows_wave / k_order_rows once over the chunk's rows; k_qb_counts: cells per query
 //
+//   B-copy   the chunk's cells and maxima to the host in one piece each, every query's block cut out there
+//
+// B-alpha .. B-order and the per-query counts are pdl_run_query_chunk_device: the cells stay in HBM.  pdl_query_batch follows
+// it with B-copy; K-place for a batch (pdl_place_batch.h) filters the cells where they lie instead.
+//
 // Positions of query records (QDesc.qlo/qhi/qextra, QFold.qL) are positions in the segmented arrays of the chunk; QDesc.key is
 // taken relative to the segment start, so it is the single query's key.
 #pragma once
@@ -218,12 +223,6 @@ __global__ __launch_bounds__(64) void k_qb_counts(const uint32_t *fin_off, QBLay
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-struct QBQuery {                    // what the host knows of one query before the device is asked
-    uint32_t g0, n;                 // its genes in the caller's arrays
-    uint64_t Rq, Mq;                // residues, k-mers
-    uint64_t bytes;                 // device memory the stages before the join need for it (the chunking's weight)
-};
-
 template <class KeyT>
 static QBView<KeyT> qb_view(pdl_ctx *c) {
     auto &w = c->qbb;
@@ -234,9 +233,10 @@ static QBView<KeyT> qb_view(pdl_ctx *c) {
     return v;
 }
 
-// One chunk: queries [qa, qe) of `qs`.  Appends its blocks to out[qa..qe) / info (a failure leaves the freeing to the caller).
-static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
-                         uint32_t hbm_cols, pdl_scores *out, pdl_query_info *info, float *device_ms) {
+// The device half of one chunk, queries [qa, qe) of `qs`: B-alpha ... B-order and the per-query counts.  The ordered cells (five
+// arrays of `cap`), MS and CM stay in c->qbb; the stretches of device work are c->qbb.spans (read once the stream has been waited for).
+pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
+                                           uint32_t hbm_cols) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
     const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
@@ -360,6 +360,10 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     PDL_HIP(hipMemsetAsync(w.CM.p, 0, cm_floats * 4, st));
     const uint64_t cap = std::max<uint64_t>(bound, 1);
     uint64_t Z = 0;
+    pdl_query_chunk ch;
+    ch.nq = nq; ch.genes = NT; ch.cap = cap;
+    ch.gene_begin = h_gbeg;
+    ch.cells.assign(nq, 0); ch.records.resize(nq); ch.matched.resize(nq); ch.cost.resize(nq);
     if (Ut) {
         w.row_base.alloc(NT * 4ull); w.row_cnt.alloc(NT * 4ull); w.fin_off.alloc((NT + 1) * 4ull); w.overflow.alloc(NT * 4ull);
         w.st.alloc(cap * 20); w.cells.alloc(cap * 20);
@@ -394,9 +398,24 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     } else {
         spans.end();
     }
+    ch.Z = Z;
+    for (uint32_t q = 0; q < nq; q++) {
+        ch.cells[q] = Ut ? hq(q, QB_CTL_EMITTED) : 0;
+        ch.records[q] = hq(q, QB_CTL_RECORDS); ch.matched[q] = hq(q, QB_CTL_MATCHED); ch.cost[q] = hq(q, QB_CTL_COST);
+    }
+    return ch;
+}
 
-    // B-copy: the chunk's cells and maxima come over in one piece each (7 copies per chunk, not per query) into pinned host
-    // memory — a DMA, no staging by the runtime — then every query's block is cut out on the host
+// B-copy: the chunk's cells and maxima come over in one piece each (7 copies per chunk, not per query) into pinned host
+// memory — a DMA, no staging by the runtime — then every query's block is cut out on the host.  Appends the blocks to
+// out[qa..) / info (a failure leaves the freeing to the caller).
+static void qb_copy_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa, const pdl_query_chunk &ch, pdl_scores *out, pdl_query_info *info,
+                          float *device_ms) {
+    hipStream_t st = c->stream;
+    auto &w = c->qbb;
+    const uint32_t N = c->N, G1 = c->G + 1, nq = ch.nq;
+    const uint64_t Z = ch.Z, cap = ch.cap;
+    const size_t ms_floats = (size_t) ch.genes * G1, cm_floats = (size_t) nq * N + ch.genes;
     const size_t stage_words = (size_t) Z * 5 + ms_floats + cm_floats;
     if (w.stage_bytes < stage_words * 4) {
         if (w.stage) { (void) hipHostFree(w.stage); w.stage = nullptr; w.stage_bytes = 0; }
@@ -412,39 +431,42 @@ static void qb_run_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_ms), w.MS.p, ms_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_cm), w.CM.p, cm_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipStreamSynchronize(st));
-    const float ms_total = spans.total_ms();
+    const float ms_total = w.spans.total_ms();
     *device_ms += ms_total;
     uint64_t z0 = 0;
     for (uint32_t q = 0; q < nq; q++) {
         const QBQuery &Q = qs[qa + q];
-        const uint64_t Zq = Ut ? hq(q, QB_CTL_EMITTED) : 0;
+        const uint64_t Zq = ch.cells[q];
         const uint32_t n = Q.n, NC = N + n;
         if (z0 + Zq > Z) PDL_FAIL(PDL_ERR_DEVICE, "query batch: the queries' cells (%llu) pass the emitted total %llu", (unsigned long long) (z0 + Zq), (unsigned long long) Z);
         pdl_scores &r = out[qa + q];                             // (filled in place: a throw leaves what is allocated to the caller's pdl_free_scores)
         q_block_alloc(c, r, Zq, n);
         void *dst[5] = {r.scores, r.percs, r.tr_percs, r.row, r.column};
         for (int i = 0; i < 5; i++) if (Zq) memcpy(dst[i], h_cells + (size_t) i * Z + z0, Zq * 4);
-        memcpy(r.max_genome_score, h_ms + (size_t) h_gbeg[q] * G1, (size_t) n * G1 * 4);
-        memcpy(r.max_genome_score_col, h_cm + (size_t) q * N + h_gbeg[q], (size_t) NC * 4);
+        memcpy(r.max_genome_score, h_ms + (size_t) ch.gene_begin[q] * G1, (size_t) n * G1 * 4);
+        memcpy(r.max_genome_score_col, h_cm + (size_t) q * N + ch.gene_begin[q], (size_t) NC * 4);
         q_block_ids(c, r);
         z0 += Zq;
         if (info) {
             pdl_query_info &fi = info[qa + q];
             memset(&fi, 0, sizeof(fi));
-            fi.residues = Q.Rq; fi.kmer_occurrences = Q.Mq; fi.records = hq(q, QB_CTL_RECORDS); fi.matched_records = hq(q, QB_CTL_MATCHED);
-            fi.genome_cost = hq(q, QB_CTL_COST);
+            fi.residues = Q.Rq; fi.kmer_occurrences = Q.Mq; fi.records = ch.records[q]; fi.matched_records = ch.matched[q];
+            fi.genome_cost = ch.cost[q];
             fi.device_ms = ms_total / (float) nq;
         }
     }
 }
 
-void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
-                         pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo) {
+// What the host knows of every query before the device is asked, behind the domain refusals of a batch; -> columns the HBM tables
+// of the join's last tier are laid out for.  column_bytes: what the caller's own stages hold per column of a query's union on top
+// (K-place for a batch: its copy of the base's labels and the group table)
+uint32_t pdl_query_batch_plan(pdl_ctx *c, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries, std::vector<QBQuery> &qs,
+                              uint64_t column_bytes) {
     const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
     if (c->R + (offsets[n] - offsets[0]) >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the base and the batch need 64-bit stream positions");
     if (c->max_kseq >= (1ull << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a base gene of %llu k-mers: queries need genes below 2^20 k-mers", (unsigned long long) c->max_kseq);
     const size_t kb = c->key64 ? 8 : 4;
-    std::vector<QBQuery> qs(n_queries);
+    qs.assign(n_queries, QBQuery{});
     uint32_t n_max = 0;
     for (uint32_t q = 0; q < n_queries; q++) {
         QBQuery &Q = qs[q];
@@ -459,18 +481,30 @@ void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         if (Q.Mq >= 0x7ffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu k-mers exceed the 31-bit record positions", q, (unsigned long long) Q.Mq);
         // what the stages hold per k-mer (two key and value halves, recpos, postings, the two index sorts, segment copies, group
         // descriptions) and per gene / column (maxima, row tables); staging and cells are sized once the match has counted them
-        Q.bytes = Q.Rq + Q.Mq * (3 * kb + 2 * 4 + 4 + 8 + 4 * 8 + 8 + sizeof(QDesc)) + ((uint64_t) N + Q.n) * 4 + (uint64_t) Q.n * (G1 * 4ull + 48);
+        Q.bytes = Q.Rq + Q.Mq * (3 * kb + 2 * 4 + 4 + 8 + 4 * 8 + 8 + sizeof(QDesc)) + ((uint64_t) N + Q.n) * (4 + column_bytes) + (uint64_t) Q.n * (G1 * 4ull + 48);
         n_max = std::max(n_max, Q.n);
     }
-    const uint32_t hbm_cols = N + n_max;
-    // chunks of consecutive queries within the byte budget (and the 31-bit record positions); one query always goes
+    return N + n_max;
+}
+// the chunk that starts at query qa: consecutive queries within the byte budget (and the 31-bit record positions); one query always goes
+uint32_t pdl_query_batch_chunk_end(const pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa) {
+    const uint32_t n_queries = (uint32_t) qs.size();
+    uint32_t qe = qa + 1;
+    uint64_t bytes = qs[qa].bytes, m = qs[qa].Mq;
+    while (qe < n_queries && bytes + qs[qe].bytes <= c->opt_query_batch_bytes && m + qs[qe].Mq < 0x7ffff000ull) { bytes += qs[qe].bytes; m += qs[qe].Mq; qe++; }
+    return qe;
+}
+
+void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,
+                         pdl_scores *out, pdl_query_info *info, pdl_query_batch_info *binfo) {
+    std::vector<QBQuery> qs;
+    const uint32_t hbm_cols = pdl_query_batch_plan(c, offsets, gene_begin, n, n_queries, qs, 0);
     float device_ms = 0.f;
     uint32_t chunks = 0;
     for (uint32_t qa = 0; qa < n_queries;) {
-        uint32_t qe = qa + 1;
-        uint64_t bytes = qs[qa].bytes, m = qs[qa].Mq;
-        while (qe < n_queries && bytes + qs[qe].bytes <= c->opt_query_batch_bytes && m + qs[qe].Mq < 0x7ffff000ull) { bytes += qs[qe].bytes; m += qs[qe].Mq; qe++; }
-        qb_run_chunk(c, residues, offsets, qs, qa, qe, hbm_cols, out, info, &device_ms);
+        const uint32_t qe = pdl_query_batch_chunk_end(c, qs, qa);
+        const pdl_query_chunk ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);
+        qb_copy_chunk(c, qs, qa, ch, out, info, &device_ms);
         chunks++;
         qa = qe;
     }

@@ -339,11 +339,77 @@ class PangeneNative:
         """``place_query`` for the genes of a ``PangeneIData`` that holds exactly one genome."""
         return self.place_query(*_one_genome(data))
 
-    def placement_of_edges(self, base: dict, genome_of, n_query: int, src, dst) -> dict:
-        """The same kernels over a caller's query edge list in union ids (``pdl_placement_of_edges``): ``base`` is the dict
-        ``generate_families`` / ``families_of_edges`` returned for the N base genes, ``genome_of`` their genomes; the query is
-        ``n_query`` genes N..N+n_query-1 of one further genome.  Needs no preprocess and leaves the context's own state alone."""
-        s, d, g = _edge_arrays(src, dst, genome_of)
+    def place_batch(self, queries) -> list:
+        """Many new genomes placed into this context's gene families in one pass, each on its own (``pdl_place_batch``):
+        ``queries`` is a list of ``(residues, offsets)``; -> one dict per query, the one ``place_query`` returns for that
+        genome alone (ids are that query's own union ids).  ``last_place_batch_info`` then holds ``queries`` (per query: the
+        counts, ``edges``, ``device_ms`` and its ``pdl_query_info`` as ``query``), ``chunks`` and ``device_ms``."""
+        queries = list(queries)
+        res, off, begin = self.pack_queries(queries)
+        q = len(queries)
+        pls = (_lib.PdlPlacement * max(q, 1))()
+        infos = (_lib.PdlQueryInfo * max(q, 1))()
+        binfo = _lib.PdlPlaceBatchInfo()
+        self._check(self._lib.pdl_place_batch(self._ctx, res.ctypes.data if res.size else None, off.ctypes.data, begin.ctypes.data,
+                                              len(off) - 1, q, pls, infos, C.byref(binfo)))
+        out, per_query = self._take_placements(pls, q, True, [infos[j].as_dict() for j in range(q)])
+        self.last_place_batch_info = {"queries": per_query, "chunks": binfo.chunks, "device_ms": binfo.device_ms}
+        return out
+
+    def place_batch_idata(self, datas) -> list:
+        """``place_batch`` for a list of ``PangeneIData``, each holding exactly one genome."""
+        return self.place_batch([_one_genome(data, j) for j, data in enumerate(datas)])
+
+    @staticmethod
+    def pack_edge_lists(edge_lists):
+        """``[(src, dst), ...]`` -> (src, dst, edge_begin [q + 1]) as ``pdl_placement_batch_of_edges`` takes them: the lists laid
+        end to end, ``edge_begin[j]`` the first edge of list j."""
+        ss, dd, begin = [], [], [0]
+        for j, (src, dst) in enumerate(edge_lists):
+            s = np.ascontiguousarray(src, dtype=np.int32)
+            d = np.ascontiguousarray(dst, dtype=np.int32)
+            if s.ndim != 1 or s.shape != d.shape:
+                raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, f"query {j}: src and dst must be two vectors of one length")
+            ss.append(s); dd.append(d); begin.append(begin[-1] + len(s))
+        cat = lambda parts: np.ascontiguousarray(np.concatenate(parts), dtype=np.int32) if parts else np.zeros(0, np.int32)
+        return cat(ss), cat(dd), np.asarray(begin, dtype=np.uint64)
+
+    def placement_batch_of_edges(self, base: dict, genome_of, n_query, edge_lists) -> list:
+        """The batch form of ``placement_of_edges`` (``pdl_placement_batch_of_edges``): one base, ``n_query[j]`` query genes
+        and the edge list ``edge_lists[j] = (src, dst)`` in query j's own union ids per query; every list is checked on the
+        device against its own id range.  -> one dict per query, as ``placement_of_edges`` on that list alone."""
+        s, d, begin = self.pack_edge_lists(edge_lists)
+        nq = np.ascontiguousarray(n_query, dtype=np.uint32).reshape(-1)
+        if len(nq) != len(begin) - 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "n_query must hold one count per edge list")
+        fam, g, keep = self._base_families(base, genome_of)
+        q = len(nq)
+        pls = (_lib.PdlPlacement * max(q, 1))()
+        self._check(self._lib.pdl_placement_batch_of_edges(self._ctx, C.byref(fam), g.ctypes.data if g.size else None, q,
+                                                           nq.ctypes.data if nq.size else None, begin.ctypes.data,
+                                                           s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, pls))
+        del keep
+        return self._take_placements(pls, q, False, [None] * q)[0]
+
+    def _take_placements(self, pls, q, with_edges, query_infos):
+        """The q placements of a batch as dicts (each is freed as it is taken; the rest after a failure) and their infos."""
+        out, infos = [], []
+        try:
+            for j in range(q):
+                out.append(self._take_placement(pls[j], with_edges, query_infos[j]))
+                infos.append(self.last_place_info)
+        finally:                                         # (a placement that was taken is zero: freeing it again does nothing)
+            for j in range(len(out), q):
+                self._lib.pdl_free_placement(C.byref(pls[j]))
+        return out, infos
+
+    @staticmethod
+    def _base_families(base: dict, genome_of):
+        """A families dict and the genes' genomes as the ``pdl_families`` a placement of a caller's edges reads (and the arrays
+        it points into, to be kept alive over the call)."""
+        g = np.ascontiguousarray(genome_of, dtype=np.uint32)
+        if g.ndim != 1:
+            raise _lib.PdlError(_lib.PDL_ERR_ARGUMENT, "genome_of must be a vector")
         keep = {f: np.ascontiguousarray(base[f], dtype=t) for f, t in (("component_of", np.uint32), ("is_node", np.uint8), ("family_off", np.uint32),
                                                                         ("family_genes", np.uint32), ("collides", np.uint8))}
         if len(keep["component_of"]) != len(g) or len(keep["is_node"]) != len(g) or len(keep["family_off"]) != len(keep["collides"]) + 1:
@@ -351,6 +417,14 @@ class PangeneNative:
         fam = _lib.PdlFamilies(sequences=len(g), nodes=len(keep["family_genes"]), families=len(keep["collides"]), colliding=int(keep["collides"].sum()))
         for f, a in keep.items():
             setattr(fam, f, a.ctypes.data_as(dict(_lib.PdlFamilies._fields_)[f]))
+        return fam, g, keep
+
+    def placement_of_edges(self, base: dict, genome_of, n_query: int, src, dst) -> dict:
+        """The same kernels over a caller's query edge list in union ids (``pdl_placement_of_edges``): ``base`` is the dict
+        ``generate_families`` / ``families_of_edges`` returned for the N base genes, ``genome_of`` their genomes; the query is
+        ``n_query`` genes N..N+n_query-1 of one further genome.  Needs no preprocess and leaves the context's own state alone."""
+        s, d, g = _edge_arrays(src, dst, genome_of)
+        fam, g, keep = self._base_families(base, g)
         p = _lib.PdlPlacement()
         self._check(self._lib.pdl_placement_of_edges(self._ctx, C.byref(fam), g.ctypes.data if g.size else None, int(n_query),
                                                      s.ctypes.data if s.size else None, d.ctypes.data if d.size else None, len(s), C.byref(p)))
