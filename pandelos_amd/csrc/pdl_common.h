@@ -96,12 +96,13 @@ enum : size_t {
 };
 
 // ---- layout of pdl_ctx::pb.ctl (u64 words): K-place (pdl_place.h).  A block of its own: a placement only reads the context, so
-// no word of `scalars` but the sort's SCAN_TOTAL may move.  Cleared at the start of every placement; each word has one life.
+// no word of `scalars` but the sort's SCAN_TOTAL may move.  Cleared at the start of every run of the placement stages (a single
+// query's, or a chunk's of a batch: the counts are then the chunk's); each word has one life.
 // One reader each on the host (the PinReads of pdl_place.h).  On the device a count is read only where it bounds a later stage's
 // grid instead of a host read in between: INTRA and BASE_EDGES by their sorts, BASE_EDGES / BASE_PAIRS as the d_n of the scans behind
 // them, BASE_PAIRS and GROUPS by k_place_base_off, NODES by k_place_clique.
 enum : size_t {
-    PDL_PL_BAD_EDGES = 0,       // P-check (a caller's list): edges with an id outside [0, N + n) or with both ends below N; read before P-cc
+    PDL_PL_BAD_EDGES = 0,       // P-check (a caller's list, pdl_run_place_edges): edges with an id outside [0, N + n) or with both ends below N; read before the run
     PDL_PL_EDGES_1 = 1,         // K-bbh over the query block: phase-1 cells (two edges each) and phase-2 cells, totals of the two
     PDL_PL_EDGES_2 = 2,         //   edge scans; read together before P-cc
     PDL_PL_INTRA = 3,           // a caller's list: query-query edges before de-duplication (total of their compaction, the sort's count)

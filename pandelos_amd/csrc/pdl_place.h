@@ -1,32 +1,39 @@
-// pdl_place.h — K-place: a new genome's genes placed into the gene families that are already built (pdl_place_query,
-// pdl_placement_of_edges; included from pdl_bbh.hip behind pdl_families.h).  The query's Scores block (K-query, pdl_query.h) is
-// filtered where it lies — K-bbh's three kernels over the one task of the block — and the edges are hung onto the base network's
-// components without clustering the base again: the union-find of K-fam starts from the base's labels.
+// pdl_place.h — K-place: new genomes' genes placed into the gene families that are already built (pdl_place_query,
+// pdl_placement_of_edges, and through pdl_place_batch.h their batch forms; included from pdl_bbh.hip behind pdl_families.h).
+// A query's Scores block (K-query, pdl_query.h) is filtered where it lies — K-bbh's three kernels — and the edges are hung onto
+// the base network's components without clustering the base again: the union-find of K-fam starts from the base's labels.
 //
-// Ids are union ids: base genes 0..N-1, query genes N..N+n-1 (genome G).  Every edge has a query end; a base-base edge is refused.
+// A query's ids are its union ids: base genes 0..N-1, its genes N..N+n-1 (genome G).  Every edge has a query end; a base-base edge
+// is refused.  One run (place_run) takes nq queries that never see each other.  It works on flat ids (query q's own id x is
+// flat(q, x)) and chunk genes (the queries' genes one behind the other); how an edge, a gene or a flat id finds its query is the
+// layout's business, a template parameter of the run and of the kernels that map ids.  PlaceOne is a single query: one query 0,
+// flat(0, x) = x, gene x - N, constants to the compiler and nothing on the device.  PlaceChunk (pdl_place_batch.h) is a chunk
+// of a batch.
 //
-//   P-bbh      k_bbh_mark/_threshold/_intra (pdl_bbh.hip) with BbhQueryBlock: row p = gene - N, one task, genome G for ids >= N;
-//              the two kinds compacted in cell order (KindFlag / EdgeApply): phase 1 ((row, col) then (col, row)), phase 2
-//   P-check    k_place_check    (a caller's list only) ids outside [0, N + n) and base-base edges counted; read BEFORE anything below
-//   P-cc       parent[0..N) = the base's component_of (one device copy: the only O(N) step), parent[N..N+n) = identity: parent[x] <= x
-//              holds from the start, so fam_union / fam_find (pdl_families.h) over the query's edges leave every tree's root its
-//              smallest member.  k_place_union marks the query genes that are a node; k_place_roots: family_of and the sort keys
-//   P-degree   same_deg of the query genes from the query-query edges: phase 2's distinct pairs, or a caller's list compacted to
-//              (lo, hi) keys, sorted and counted at the run heads (k_fam_intra_sorted)
-//   P-groups   pdl_sort_pairs (root, query gene), run heads + scan (FamHeadFlag / FamHeadApply): groups in label order, their
-//              query members ascending, the group index of every label
+//   P-bbh      place_bbh: k_bbh_mark/_threshold/_intra (pdl_bbh.hip) with the caller's policy (BbhQueryBlock: row p = gene - N, one
+//              task, genome G for ids >= N); the two kinds compacted in cell order (KindFlag / EdgeApply): phase 1 ((row, col)
+//              then (col, row)), phase 2.  The reads of the totals and the copy-out of the edges are the caller's
+//   P-check    k_place_check    (a caller's list only, by its entry point) ids outside [0, N + n) and base-base edges counted; read
+//              BEFORE anything below
+//   P-cc       k_place_init: every query's copy of the base's component_of moved to its flat ids (the only O(N) step), its genes
+//              identity: parent[x] <= x holds from the start, so fam_union / fam_find (pdl_families.h) over the edges leave every
+//              tree's root its smallest member.  k_place_union marks the query genes that are a node; k_place_roots: the flat
+//              root of every chunk gene and the sort keys
+//   P-degree   same_deg of the chunk genes from the query-query edges: phase 2's distinct pairs (k_place_intra), or a caller's list
+//              compacted to (lo, hi) keys of chunk genes, sorted and counted at the run heads (k_fam_intra_sorted)
+//   P-groups   pdl_sort_pairs (flat root, chunk gene), run heads + scan (FamHeadFlag / FamHeadApply): groups in (query, label)
+//              order — a query's groups are one stretch —, their members ascending, the group index of every flat label
 //   P-base     edges with a base end -> (group, base label) keys, compacted, sorted, run heads: every group's fused base components;
 //              a component that collides in the base flags its group (a lookup)
 //   P-bridge   groups of two or more base components: their members gathered (a gene that was no node is its own), keyed by
 //              (group, genome), sorted; a run with genes of two components flags the group — such genes cannot be adjacent, every
-//              new edge has a query end
+//              new edge has a query end.  A group belongs to one query, so both keys keep the queries apart
 //   P-clique   a group's m >= 2 query genes are clean exactly when each has same_deg == m - 1 (as F-collide)
-//   P-out      one PinRead of the counts (the member total sizes P-bridge), then the arrays
+//   P-out      one PinRead of the counts (the member total sizes P-bridge), then the arrays come over whole; every query's
+//              placement is cut out of them and translated to its own ids on the host
 //
-// Work: the query's edges plus the members of bridged components; of the work nothing but the parent copy is proportional to N.
-// Memory is: parent and grp_of_label (indexed by label, touched at the groups' labels only) hold N + n words each.
-// The kernels take the id origin N and the edge lists as arguments and keep no state between launches: pdl_place_batch.h runs
-// them over every query's stretch of a chunk's edges.
+// Work: the queries' edges plus the members of bridged components; of the work nothing but the parent init is proportional to N.
+// Memory is: parent and grp_of_label (indexed by flat label, touched at the groups' labels only) hold N + n words per query.
 #pragma once
 
 #include "pdl_common.h"
@@ -43,9 +50,49 @@ struct BbhQueryBlock {
     __device__ uint32_t genome(uint32_t gene) const { return gene < N ? genome_b[gene] : G; }
 };
 
-__global__ __launch_bounds__(256) void k_place_init(uint32_t *parent_q, uint32_t *same_deg, uint8_t *is_node, uint8_t *gcol, uint32_t N, uint32_t n) {
+// The queries of one run: n[q] genes each, the edges of query q at eb[l][q] .. eb[l][q + 1] of list l.  Query q's own id x is the
+// flat id shift[q] + x, shift[q] = q * N + gene_begin[q]: the queries' unions [N + n_q] one behind the other
+struct PlaceQueries {
+    uint32_t nq = 0;
+    std::vector<uint32_t> n, gene_begin, shift, eb[2];            // [nq], then [nq + 1] each
+    void lay_out(uint32_t N) {
+        gene_begin.assign(nq + 1, 0); shift.assign(nq + 1, 0);
+        for (uint32_t q = 0; q < nq; q++) gene_begin[q + 1] = gene_begin[q] + n[q];
+        for (uint32_t q = 0; q <= nq; q++) shift[q] = q * N + gene_begin[q];
+    }
+    static PlaceQueries one(uint32_t N, uint32_t n, uint64_t e0, uint64_t e1) {
+        PlaceQueries Q;
+        Q.nq = 1; Q.n = {n};
+        Q.lay_out(N);
+        Q.eb[0] = {0u, (uint32_t) e0}; Q.eb[1] = {0u, (uint32_t) e1};
+        return Q;
+    }
+};
+// flat ids a run over nq queries would take (a run needs them below 2^31)
+static inline uint64_t place_flat_ids(uint32_t N, uint64_t nq, uint64_t genes) { return nq * N + genes; }
+
+// The layout of a single query: its union ids are the flat ids.  (`lists`: the layouts over list 0 and list 1 of a run.)
+struct PlaceOne {
+    uint32_t N;
+    static constexpr const char *too_large = "K-place: 2^31 genes or edges and more";
+    static void lists(pdl_ctx *, const PlaceQueries &, uint32_t N, PlaceOne L[2]) { L[0] = L[1] = PlaceOne{N}; }
+    __device__ uint32_t query_of_edge(uint32_t) const { return 0u; }
+    __device__ uint32_t query_of_gene(uint32_t) const { return 0u; }
+    __device__ uint32_t query_of_flat(uint32_t) const { return 0u; }
+    __device__ uint32_t flat(uint32_t, uint32_t x) const { return x; }
+    __device__ uint32_t gene(uint32_t, uint32_t x) const { return x - N; }            // chunk gene of the own id x >= N
+};
+
+// parent of every flat id: a base gene's label moved to its query's flat ids, a query gene its own; the chunk genes' arrays cleared
+template <class Lay>
+__global__ __launch_bounds__(256) void k_place_init(Lay L, const uint32_t *comp, uint32_t F, uint32_t NT, uint32_t *parent, uint32_t *same_deg, uint8_t *is_node,
+                                                    uint8_t *gcol) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { parent_q[i] = N + i; same_deg[i] = 0; is_node[i] = 0; gcol[i] = 0; }
+    if (i < F) {
+        const uint32_t s = L.flat(L.query_of_flat(i), 0), x = i - s;
+        parent[i] = x < L.N ? s + comp[x] : i;
+    }
+    if (i < NT) { same_deg[i] = 0; is_node[i] = 0; gcol[i] = 0; }
 }
 __global__ __launch_bounds__(256) void k_place_check(const int32_t *src, const int32_t *dst, uint32_t n_edges, uint32_t N, uint32_t NC, uint64_t *d_bad) {
     const uint32_t e = blockIdx.x * 256 + threadIdx.x;
@@ -53,36 +100,54 @@ __global__ __launch_bounds__(256) void k_place_check(const int32_t *src, const i
     const uint32_t a = (uint32_t) src[e], b = (uint32_t) dst[e];                 // (a negative id is a large unsigned one)
     if (a >= NC || b >= NC || (a < N && b < N)) atomicAdd(reinterpret_cast<unsigned long long *>(d_bad), 1ull);
 }
-// as k_fam_union; only the query genes' node flags are kept (is_node[0] belongs to gene N)
-__global__ __launch_bounds__(256) void k_place_union(const int32_t *src, const int32_t *dst, uint32_t n_edges, uint32_t mirrored, uint32_t N, uint32_t *parent,
+// as k_fam_union, an edge's ends mapped through its query; only the query genes' node flags are kept, by chunk gene
+template <class Lay>
+__global__ __launch_bounds__(256) void k_place_union(const int32_t *src, const int32_t *dst, uint32_t n_edges, uint32_t mirrored, Lay L, uint32_t *parent,
                                                      uint8_t *is_node) {
     const uint32_t e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_edges) return;
     const uint32_t a = (uint32_t) src[e], b = (uint32_t) dst[e];
     if (mirrored && a > b) return;
-    if (a >= N) is_node[a - N] = 1;
-    if (b >= N) is_node[b - N] = 1;
-    if (a != b) fam_union(parent, a, b);
+    const uint32_t q = L.query_of_edge(e);
+    if (a >= L.N) is_node[L.gene(q, a)] = 1;
+    if (b >= L.N) is_node[L.gene(q, b)] = 1;
+    if (a != b) fam_union(parent, L.flat(q, a), L.flat(q, b));
 }
-// phase 2: distinct query-query pairs
-__global__ __launch_bounds__(256) void k_place_intra(const int32_t *src, const int32_t *dst, uint32_t n_edges, uint32_t N, uint32_t *same_deg) {
+// phase 2 (list 1): distinct query-query pairs
+template <class Lay>
+__global__ __launch_bounds__(256) void k_place_intra(const int32_t *src, const int32_t *dst, uint32_t n_edges, Lay L, uint32_t *same_deg) {
     const uint32_t e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_edges) return;
     const uint32_t a = (uint32_t) src[e], b = (uint32_t) dst[e];
-    if (a == b || a < N || b < N) return;
-    atomicAdd(same_deg + (a - N), 1u); atomicAdd(same_deg + (b - N), 1u);
+    if (a == b || a < L.N || b < L.N) return;
+    const uint32_t q = L.query_of_edge(e);
+    atomicAdd(same_deg + L.gene(q, a), 1u); atomicAdd(same_deg + L.gene(q, b), 1u);
 }
+// a caller's list: a query-query edge ...
 struct PlaceIntraFlag {
     const int32_t *src, *dst; uint32_t N;
     __device__ uint32_t operator()(uint64_t e) const { const uint32_t a = (uint32_t) src[e], b = (uint32_t) dst[e]; return (uint32_t) (a != b && a >= N && b >= N); }
 };
-// family_of[i] = the root of query gene N + i (its own id when it is no node); key[i] = the sort key of P-groups (`none` behind all)
-__global__ __launch_bounds__(256) void k_place_roots(uint32_t *parent, const uint8_t *is_node, uint32_t N, uint32_t n, uint32_t *family_of, uint32_t *key) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t r = is_node[i] ? fam_find(parent, N + i) : N + i;
-    family_of[i] = r;
-    key[i] = is_node[i] ? r : N + n;
+// ... as the (lo << 32 | hi) key of its two chunk genes
+template <class Lay>
+struct PlaceIntraApply {
+    const int32_t *src, *dst; Lay L; unsigned long long *keys;
+    __device__ void operator()(uint64_t e, uint32_t f, uint32_t pre) const {
+        if (!f) return;
+        const uint32_t q = L.query_of_edge((uint32_t) e);
+        const uint32_t a = L.gene(q, (uint32_t) src[e]), b = L.gene(q, (uint32_t) dst[e]);
+        keys[pre] = (unsigned long long) (a < b ? a : b) << 32 | (a < b ? b : a);
+    }
+};
+// family[g] = the flat root of chunk gene g (its own flat id when it is no node); key[g] = the sort key of P-groups (`F` behind all)
+template <class Lay>
+__global__ __launch_bounds__(256) void k_place_roots(uint32_t *parent, const uint8_t *is_node, Lay L, uint32_t F, uint32_t NT, uint32_t *family, uint32_t *key) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= NT) return;
+    const uint32_t q = L.query_of_gene(g), f = L.flat(q, L.N + (g - L.gene(q, L.N)));
+    const uint32_t r = is_node[g] ? fam_find(parent, f) : f;
+    family[g] = r;
+    key[g] = is_node[g] ? r : F;
 }
 
 // an edge with one base end (a mirrored list holds it twice: the half with src < dst is taken) ...
@@ -95,14 +160,15 @@ struct PlaceBaseFlag {
     }
 };
 // ... as the key (group << label_bits | base label)
+template <class Lay>
 struct PlaceBaseApply {
-    const int32_t *src, *dst; uint32_t N, label_bits;
-    const uint32_t *family_of, *grp_of_label, *base_comp; unsigned long long *keys;
+    const int32_t *src, *dst; Lay L; uint32_t label_bits;
+    const uint32_t *family, *grp_of_label, *base_comp; unsigned long long *keys;
     __device__ void operator()(uint64_t e, uint32_t f, uint32_t pre) const {
         if (!f) return;
         const uint32_t a = (uint32_t) src[e], b = (uint32_t) dst[e];
-        const uint32_t q = a < N ? b : a, g = a < N ? a : b;
-        keys[pre] = (unsigned long long) grp_of_label[family_of[q - N]] << label_bits | base_comp[g];
+        const uint32_t qg = a < L.N ? b : a, g = a < L.N ? a : b;
+        keys[pre] = (unsigned long long) grp_of_label[family[L.gene(L.query_of_edge((uint32_t) e), qg)]] << label_bits | base_comp[g];
     }
 };
 // run heads of the sorted keys: the distinct (group, base component) pairs; a component that collides in the base flags its group
@@ -180,69 +246,60 @@ static uint64_t *place_begin(pdl_ctx *c) {
     return c->pb.ctl.as<uint64_t>();
 }
 
-// One placement.  list[0] / list[1]: device edge lists in union ids (the query block's two phases, or a caller's list and nothing).
-// mirrored0: list 0 holds every pair in both directions.  caller: query-query edges (looked for in list 0) may repeat; otherwise
-// they are list 1's, distinct.  check_ids: a caller's ids are checked first (a batch has checked all its lists at once).
-// `spans` has a stretch open on entry and none on return.
-// place_run_batch (pdl_place_batch.h) is its twin over the queries of a chunk, stage for stage: a change to one belongs into the other.
-static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t *const src[2], const int32_t *const dst[2], const uint64_t n_edges[2],
-                      bool mirrored0, bool caller, bool check_ids, QSpans &spans, pdl_place_result &out) {
+// The placement stages once over the nq queries of Q.  list[0] / list[1]: device edge lists, every query's edges one stretch (Q.eb),
+// in the query's own union ids (the query blocks' two phases, or callers' lists and nothing).  mirrored0: list 0 holds every pair in
+// both directions.  caller: query-query edges (looked for in list 0) may repeat; otherwise they are list 1's, distinct.  A caller's
+// ids have been checked.  `spans` has a stretch open on entry and none on return.  -> out[0 .. nq): every field but the edges and
+// device_ms; returns the device time of its stretches.
+template <class Lay>
+static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, const int32_t *const src[2], const int32_t *const dst[2], bool mirrored0,
+                       bool caller, QSpans &spans, pdl_place_result *out) {
     hipStream_t st = c->stream;
     pdl_ctx::PlaceBufs &b = c->pb;
-    const uint32_t N = B.N;
-    if ((uint64_t) N + n >= 0x7fffffffull || n_edges[0] >= 0x7fffffffull || n_edges[1] >= 0x7fffffffull)
-        PDL_FAIL(PDL_ERR_UNSUPPORTED, "K-place: 2^31 genes or edges and more");
-    const uint32_t NC = N + n;
+    const uint32_t N = B.N, nq = Q.nq, NT = Q.gene_begin[nq];
+    const uint64_t n_edges[2] = {Q.eb[0][nq], Q.eb[1][nq]};
+    if (place_flat_ids(N, nq, NT) >= 0x7fffffffull || n_edges[0] >= 0x7fffffffull || n_edges[1] >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s", Lay::too_large);
+    const uint32_t F = Q.shift[nq];
     uint64_t *ctl = b.ctl.as<uint64_t>();
-    const size_t n4 = (size_t) n * 4;
-    b.parent.alloc((size_t) NC * 4); b.grp_of_label.alloc((size_t) NC * 4);
-    b.is_node.alloc(n); b.gcol.alloc(n); b.same_deg.alloc(n4); b.family_of.alloc(n4); b.gq_off.alloc(n4 + 4); b.gb_off.alloc(n4 + 4);
+    const size_t n4 = (size_t) NT * 4;
+    b.parent.alloc((size_t) F * 4); b.grp_of_label.alloc((size_t) F * 4);
+    b.is_node.alloc(NT); b.gcol.alloc(NT); b.same_deg.alloc(n4); b.family_of.alloc(n4); b.gq_off.alloc(n4 + 4); b.gb_off.alloc(n4 + 4);
     for (DevBuf *d : {&b.mk_a, &b.mk_b, &b.mv_a, &b.mv_b}) d->alloc(n4);
-    uint32_t *parent = b.parent.as<uint32_t>(), *same_deg = b.same_deg.as<uint32_t>(), *family_of = b.family_of.as<uint32_t>();
+    uint32_t *parent = b.parent.as<uint32_t>(), *same_deg = b.same_deg.as<uint32_t>(), *family = b.family_of.as<uint32_t>();
     uint32_t *grp_of_label = b.grp_of_label.as<uint32_t>(), *gq_off = b.gq_off.as<uint32_t>(), *gb_off = b.gb_off.as<uint32_t>();
     uint8_t *is_node = b.is_node.as<uint8_t>(), *gcol = b.gcol.as<uint8_t>();
-
-    if (check_ids && n_edges[0]) {                    // P-check
-        hipLaunchKernelGGL(k_place_check, fam_grid(n_edges[0]), dim3(256), 0, st, src[0], dst[0], (uint32_t) n_edges[0], N, NC, ctl + PDL_PL_BAD_EDGES);
-        PDL_HIP(hipGetLastError());
-        spans.end();
-        PinRead rd(c);
-        const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_PL_BAD_EDGES, 1);
-        rd.sync();
-        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-place: %llu edges name a gene id outside [0, %u) or join two base genes (ids below %u)", (unsigned long long) *bad, NC, N);
-        spans.begin();
-    }
+    Lay lay[2];                                       // (over list 0, over list 1)
+    Lay::lists(c, Q, N, lay);
+    const Lay &L = lay[0];
     // P-cc
-    if (N) PDL_HIP(hipMemcpyAsync(parent, B.comp, (size_t) N * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_place_init, fam_grid(n), dim3(256), 0, st, parent + N, same_deg, is_node, gcol, N, n);
+    hipLaunchKernelGGL(k_place_init<Lay>, fam_grid(F), dim3(256), 0, st, L, B.comp, F, NT, parent, same_deg, is_node, gcol);
     for (int l = 0; l < 2; l++)
-        if (n_edges[l]) hipLaunchKernelGGL(k_place_union, fam_grid(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), N, parent, is_node);
+        if (n_edges[l]) hipLaunchKernelGGL(k_place_union<Lay>, fam_grid(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), lay[l], parent, is_node);
     uint32_t *mk_in = b.mk_a.as<uint32_t>(), *mk_out = b.mk_b.as<uint32_t>(), *mv_in = b.mv_a.as<uint32_t>(), *mv_out = b.mv_b.as<uint32_t>();
-    hipLaunchKernelGGL(k_place_roots, fam_grid(n), dim3(256), 0, st, parent, is_node, N, n, family_of, mk_in);
+    hipLaunchKernelGGL(k_place_roots<Lay>, fam_grid(NT), dim3(256), 0, st, parent, (const uint8_t *) is_node, L, F, NT, family, mk_in);
     PDL_HIP(hipGetLastError());
     // P-degree
+    const uint64_t E0 = n_edges[0];
     if (caller) {
-        const uint64_t E = n_edges[0];
-        if (E) {
-            b.ek_a.alloc(E * 8); b.ek_b.alloc(E * 8); b.ev_a.alloc(E * 4); b.ev_b.alloc(E * 4);
+        if (E0) {
+            b.ek_a.alloc(E0 * 8); b.ek_b.alloc(E0 * 8); b.ev_a.alloc(E0 * 4); b.ev_b.alloc(E0 * 4);
             unsigned long long *ek_in = b.ek_a.as<unsigned long long>();
             uint32_t *ev_in = b.ev_a.as<uint32_t>(), *ev_out = b.ev_b.as<uint32_t>();
             uint64_t *d_intra = ctl + PDL_PL_INTRA;
-            scan_and_apply(c, E, PlaceIntraFlag{src[0], dst[0], N}, FamIntraApply{src[0], dst[0], ek_in}, d_intra);
+            scan_and_apply(c, E0, PlaceIntraFlag{src[0], dst[0], N}, PlaceIntraApply<Lay>{src[0], dst[0], L, ek_in}, d_intra);
             uint64_t *k_in = reinterpret_cast<uint64_t *>(ek_in), *k_out = b.ek_b.as<uint64_t>();
-            pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, ev_in, ev_out, E, 32 + bit_length64(NC - 1), true, d_intra, 0, true);
-            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, N);
+            pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, ev_in, ev_out, E0, 32 + bit_length64(NT - 1), true, d_intra, 0, true);
+            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E0), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
         }
     } else if (n_edges[1]) {
-        hipLaunchKernelGGL(k_place_intra, fam_grid(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], N, same_deg);
+        hipLaunchKernelGGL(k_place_intra<Lay>, fam_grid(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], lay[1], same_deg);
     }
     PDL_HIP(hipGetLastError());
-    // P-groups: (root, query gene), query genes ascending in
-    pdl_sort_pairs<uint32_t, uint32_t>(c, mk_in, mk_out, mv_in, mv_out, n, bit_length64(NC), true, nullptr, 0, true);
-    scan_and_apply(c, n, FamHeadFlag{mk_out, mv_out, nullptr, NC}, FamHeadApply{mk_out, nullptr, NC, n, gq_off, grp_of_label, ctl + PDL_PL_NODES}, ctl + PDL_PL_GROUPS);
+    // P-groups: (flat root, chunk gene), chunk genes ascending in
+    pdl_sort_pairs<uint32_t, uint32_t>(c, mk_in, mk_out, mv_in, mv_out, NT, bit_length64(F), true, nullptr, 0, true);
+    scan_and_apply(c, NT, FamHeadFlag{mk_out, mv_out, nullptr, F}, FamHeadApply{mk_out, nullptr, F, NT, gq_off, grp_of_label, ctl + PDL_PL_NODES}, ctl + PDL_PL_GROUPS);
     // P-base
-    const uint64_t E0 = n_edges[0];
-    const uint32_t label_bits = std::max<uint32_t>(1, bit_length64(N ? N - 1 : 0)), group_bits = std::max<uint32_t>(1, bit_length64(n));
+    const uint32_t label_bits = std::max<uint32_t>(1, bit_length64(N ? N - 1 : 0)), group_bits = std::max<uint32_t>(1, bit_length64(NT));
     const uint32_t genome_bits = std::max<uint32_t>(1, bit_length64(B.G));
     unsigned long long *uniq = nullptr;
     uint32_t *group_base = nullptr, *mpre = nullptr;
@@ -253,15 +310,15 @@ static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t 
         uint32_t *v_in = b.bv_a.as<uint32_t>(), *v_out = b.bv_b.as<uint32_t>();
         uint64_t *d_base = ctl + PDL_PL_BASE_EDGES, *d_pairs = ctl + PDL_PL_BASE_PAIRS;
         scan_and_apply(c, E0, PlaceBaseFlag{src[0], dst[0], (uint32_t) mirrored0, N},
-                       PlaceBaseApply{src[0], dst[0], N, label_bits, family_of, grp_of_label, B.comp, reinterpret_cast<unsigned long long *>(k_in)}, d_base);
+                       PlaceBaseApply<Lay>{src[0], dst[0], L, label_bits, family, grp_of_label, B.comp, reinterpret_cast<unsigned long long *>(k_in)}, d_base);
         pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, v_in, v_out, E0, label_bits + group_bits, true, d_base, 0, true);
         const unsigned long long *sorted = reinterpret_cast<const unsigned long long *>(k_out);
         scan_and_apply(c, E0, PlaceUniqFlag{sorted}, PlaceUniqApply{sorted, uniq, group_base, gcol, B, label_bits}, d_pairs, nullptr, d_base);
-        hipLaunchKernelGGL(k_place_base_off, fam_grid((uint64_t) n + 1), dim3(256), 0, st, uniq, d_pairs, ctl + PDL_PL_GROUPS, n, label_bits, gb_off);
+        hipLaunchKernelGGL(k_place_base_off, fam_grid((uint64_t) NT + 1), dim3(256), 0, st, uniq, d_pairs, ctl + PDL_PL_GROUPS, NT, label_bits, gb_off);
         scan_and_apply(c, E0, PlaceMemberFlag{uniq, gb_off, B, label_bits}, PlaceMemberApply{mpre}, ctl + PDL_PL_MEMBERS, nullptr, d_pairs);
     }
     // P-clique
-    hipLaunchKernelGGL(k_place_clique, fam_grid(n), dim3(256), 0, st, mk_out, mv_out, grp_of_label, gq_off, same_deg, ctl + PDL_PL_NODES, n, gcol);
+    hipLaunchKernelGGL(k_place_clique, fam_grid(NT), dim3(256), 0, st, mk_out, mv_out, grp_of_label, gq_off, same_deg, ctl + PDL_PL_NODES, NT, gcol);
     PDL_HIP(hipGetLastError());
     spans.end();
     // P-out: the counts in one read ...
@@ -270,11 +327,11 @@ static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t 
         PinRead rd(c);
         const uint64_t *w = rd.add<uint64_t>(ctl + PDL_PL_NODES, PDL_PL_MEMBERS - PDL_PL_NODES + 1);
         rd.sync();
-        nodes = w[0]; groups = w[PDL_PL_GROUPS - PDL_PL_NODES]; pairs = w[PDL_PL_BASE_PAIRS - PDL_PL_NODES]; members = w[PDL_PL_MEMBERS - PDL_PL_NODES];
+        nodes = w[PDL_PL_NODES - PDL_PL_NODES]; groups = w[PDL_PL_GROUPS - PDL_PL_NODES]; pairs = w[PDL_PL_BASE_PAIRS - PDL_PL_NODES]; members = w[PDL_PL_MEMBERS - PDL_PL_NODES];
     }
-    if (nodes > n || groups > nodes || pairs > E0 || (groups == 0 && pairs) || members >= 0x7fffffffull)
+    if (nodes > NT || groups > nodes || pairs > E0 || (groups == 0 && pairs) || members >= 0x7fffffffull)
         PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent counts (%llu nodes, %llu groups, %llu base pairs, %llu members of %u query genes, %llu edges)",
-                 (unsigned long long) nodes, (unsigned long long) groups, (unsigned long long) pairs, (unsigned long long) members, n, (unsigned long long) E0);
+                 (unsigned long long) nodes, (unsigned long long) groups, (unsigned long long) pairs, (unsigned long long) members, NT, (unsigned long long) E0);
     // ... P-bridge, sized by the member total ...
     if (members) {
         spans.begin();
@@ -288,33 +345,64 @@ static void place_run(pdl_ctx *c, const PlaceBase &B, uint32_t n, const int32_t 
         PDL_HIP(hipGetLastError());
         spans.end();
     }
-    // ... then the arrays
-    out.sequences = N; out.n_query = n; out.genomes = B.G; out.groups = (uint32_t) groups;
-    out.family_of.resize(n); out.is_node.resize(n);
-    out.group_query_off.assign(groups + 1, 0); out.group_base_off.assign(groups + 1, 0);
-    out.group_query.resize(nodes); out.group_base.resize(pairs); out.group_collides.resize(groups); out.group_label.resize(groups);
-    PDL_HIP(hipMemcpyAsync(out.family_of.data(), family_of, n4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.is_node.data(), is_node, n, hipMemcpyDeviceToHost, st));
+    // ... then the arrays, whole
+    std::vector<uint32_t> h_family(NT), h_gq_off(groups + 1, 0), h_gb_off(groups + 1, 0), h_gene(nodes), h_base(pairs);
+    std::vector<uint8_t> h_is_node(NT), h_gcol(groups);
+    PDL_HIP(hipMemcpyAsync(h_family.data(), family, n4, hipMemcpyDeviceToHost, st));
+    PDL_HIP(hipMemcpyAsync(h_is_node.data(), is_node, NT, hipMemcpyDeviceToHost, st));
     if (groups) {
-        PDL_HIP(hipMemcpyAsync(out.group_query_off.data(), gq_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.group_query.data(), mv_out, nodes * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.group_collides.data(), gcol, groups, hipMemcpyDeviceToHost, st));
-        if (E0) PDL_HIP(hipMemcpyAsync(out.group_base_off.data(), gb_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
-        if (pairs) PDL_HIP(hipMemcpyAsync(out.group_base.data(), group_base, pairs * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(h_gq_off.data(), gq_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(h_gene.data(), mv_out, nodes * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(h_gcol.data(), gcol, groups, hipMemcpyDeviceToHost, st));
+        if (E0) PDL_HIP(hipMemcpyAsync(h_gb_off.data(), gb_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
+        if (pairs) PDL_HIP(hipMemcpyAsync(h_base.data(), group_base, pairs * 4, hipMemcpyDeviceToHost, st));
     }
     PDL_HIP(hipStreamSynchronize(st));
-    if (groups && (out.group_query_off[0] != 0 || out.group_query_off[groups] != nodes || out.group_base_off[groups] != pairs))
-        PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent group offsets");
-    out.unplaced = n - (uint32_t) nodes;
-    for (uint64_t g = 0; g < groups; g++) {
-        const uint32_t q0 = out.group_query_off[g], nb = out.group_base_off[g + 1] - out.group_base_off[g];
-        if (q0 >= nodes || out.group_query[q0] >= n) PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent group members");
-        out.group_label[g] = out.family_of[out.group_query[q0]];
-        (nb == 0 ? out.novel : nb == 1 ? out.joined : out.bridging)++;
-        out.colliding += out.group_collides[g] ? 1u : 0u;
+    if (groups && (h_gq_off[0] != 0 || h_gq_off[groups] != nodes || h_gb_off[groups] != pairs)) PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent group offsets");
+    for (uint64_t g = 0; g < groups; g++)
+        if (h_gq_off[g + 1] <= h_gq_off[g] || h_gq_off[g + 1] > nodes || h_gb_off[g + 1] < h_gb_off[g] || h_gb_off[g + 1] > pairs || h_gene[h_gq_off[g]] >= NT)
+            PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent group members");
+    // every query's placement cut out: its groups are one stretch (a group is its first member's query's), ids back in its own union
+    uint64_t g = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        pdl_place_result &r = out[q];
+        const uint32_t n = Q.n[q], g0 = Q.gene_begin[q], s = Q.shift[q];
+        r.sequences = N; r.n_query = n; r.genomes = B.G;
+        r.family_of.resize(n); r.is_node.assign(h_is_node.begin() + g0, h_is_node.begin() + g0 + n);
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t f = h_family[g0 + i];
+            if (f < s || f > s + N + i) PDL_FAIL(PDL_ERR_DEVICE, "K-place: a family label outside its query's ids");
+            r.family_of[i] = f - s;
+        }
+        const uint64_t ga = g;
+        while (g < groups && h_gene[h_gq_off[g]] < g0 + n) {
+            if (h_gene[h_gq_off[g]] < g0) PDL_FAIL(PDL_ERR_DEVICE, "K-place: the groups are not in the queries' order");
+            g++;
+        }
+        const uint32_t ng = (uint32_t) (g - ga), m0 = ng ? h_gq_off[ga] : 0, p0 = ng ? h_gb_off[ga] : 0;
+        r.groups = ng;
+        r.group_query_off.assign(ng + 1, 0); r.group_base_off.assign(ng + 1, 0); r.group_label.resize(ng); r.group_collides.resize(ng);
+        for (uint32_t j = 0; j <= ng; j++) { r.group_query_off[j] = h_gq_off[ga + j] - m0; r.group_base_off[j] = h_gb_off[ga + j] - p0; }
+        if (!ng) { r.group_query_off[0] = 0; r.group_base_off[0] = 0; }
+        const uint32_t nodes_q = r.group_query_off[ng];
+        r.group_query.resize(nodes_q);
+        for (uint32_t j = 0; j < nodes_q; j++) {
+            const uint32_t cg = h_gene[m0 + j];
+            if (cg < g0 || cg >= g0 + n) PDL_FAIL(PDL_ERR_DEVICE, "K-place: a group with members of two queries");
+            r.group_query[j] = N + (cg - g0);
+        }
+        r.group_base.assign(h_base.begin() + p0, h_base.begin() + p0 + r.group_base_off[ng]);
+        r.unplaced = n - nodes_q;
+        for (uint32_t j = 0; j < ng; j++) {
+            const uint32_t nb = r.group_base_off[j + 1] - r.group_base_off[j];
+            r.group_label[j] = r.family_of[r.group_query[r.group_query_off[j]] - N];
+            r.group_collides[j] = h_gcol[ga + j];
+            (nb == 0 ? r.novel : nb == 1 ? r.joined : r.bridging)++;
+            r.colliding += r.group_collides[j] ? 1u : 0u;
+        }
     }
-    for (uint32_t &q : out.group_query) q += N;       // (the sort carried the query genes' positions)
-    out.device_ms = spans.total_ms();
+    if (g != groups) PDL_FAIL(PDL_ERR_DEVICE, "K-place: groups behind the last query");
+    return spans.total_ms();
 }
 
 // the context's own families on the device: uploaded once per run of K-fam (c->fam is its answer on the host)
@@ -346,68 +434,76 @@ static PlaceBase place_context_base(pdl_ctx *c) {
     return B;
 }
 
+// P-bbh over the Z > 0 ordered cells of `tasks` query blocks with `genes` rows in all (w: the buffers K-query left them in, the
+// cells' arrays `cap` apart; `at`: where a cell finds its block; cm_n: what a block's CM slice starts at a multiple of): K-bbh's
+// filter, then the two kinds compacted in cell order (phase 1 leaves two edges per cell); the totals of cells go to d_n1 / d_n2.
+// -> the edges of the two phases and, per cell, the cells of each kind before it (pre [Z + 1]), on the device
+struct PlaceEdges { int32_t *src[2], *dst[2]; float *sc[2]; uint32_t *pre[2]; };
+template <class At, class W>
+static PlaceEdges place_bbh(pdl_ctx *c, W &w, uint64_t cap, const At &at, uint32_t cm_n, uint32_t tasks, uint32_t genes, uint64_t Z, uint64_t *d_n1, uint64_t *d_n2) {
+    hipStream_t st = c->stream;
+    pdl_ctx::PlaceBufs &b = c->pb;
+    const uint32_t G1 = c->G + 1;
+    b.kind.alloc(Z + 16);
+    b.tab.alloc(((size_t) tasks * G1 + genes + 2 * (Z + 1)) * sizeof(uint32_t));
+    uint32_t *inter_max = b.tab.as<uint32_t>(), *thr = inter_max + (size_t) tasks * G1;
+    PlaceEdges e{};
+    e.pre[0] = thr + genes; e.pre[1] = e.pre[0] + (Z + 1);
+    PDL_HIP(hipMemsetAsync(inter_max, 0, (size_t) tasks * G1 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_fill_u32, dim3((genes + 255) / 256), dim3(256), 0, st, thr, genes, 0x7f800000u);
+    const float *cf = w.cells.template as<float>();
+    BbhArgs<At> a{};
+    a.score = cf; a.row = reinterpret_cast<const int32_t *>(cf + 3 * cap); a.col = reinterpret_cast<const int32_t *>(cf + 4 * cap);
+    a.at = at;
+    a.MS = w.MS.template as<float>(); a.CM = w.CM.template as<float>(); a.N = cm_n; a.G = G1; a.Z = (uint32_t) Z;
+    a.inter_max = inter_max; a.thr = thr; a.kind = b.kind.as<uint8_t>();
+    bbh_filter(st, a);
+    b.e_src.alloc(3 * Z * sizeof(int32_t)); b.e_dst.alloc(3 * Z * sizeof(int32_t)); b.e_score.alloc(3 * Z * sizeof(float));
+    e.src[0] = b.e_src.as<int32_t>(); e.dst[0] = b.e_dst.as<int32_t>(); e.sc[0] = b.e_score.as<float>();
+    e.src[1] = e.src[0] + 2 * Z; e.dst[1] = e.dst[0] + 2 * Z; e.sc[1] = e.sc[0] + 2 * Z;
+    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, e.src[0], e.dst[0], e.sc[0], e.pre[0], 2}, d_n1);
+    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, e.src[1], e.dst[1], e.sc[1], e.pre[1], 1}, d_n2);
+    return e;
+}
+
 // pdl_place_query behind its refusals: the families of the context are valid (c->fam)
 void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_place_result &out, pdl_query_info *info) {
     hipStream_t st = c->stream;
-    pdl_ctx::PlaceBufs &b = c->pb;
     out = pdl_place_result{};
     const PlaceBase B = place_context_base(c);
     const pdl_query_run run = pdl_run_query_device(c, residues, offsets, n);          // (its argument and domain refusals leave from here)
-    const uint32_t N = c->N, G1 = c->G + 1;
+    const uint32_t N = c->N;
     const uint64_t Z = run.Z;
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells in the query block");
     uint64_t *ctl = place_begin(c);
-    QSpans &spans = b.spans;
+    QSpans &spans = c->pb.spans;
     spans.start(st);
     spans.begin();
-    // P-bbh
-    uint64_t n1 = 0, n2 = 0;
-    int32_t *src1 = nullptr, *dst1 = nullptr, *src2 = nullptr, *dst2 = nullptr;
-    float *sc1 = nullptr, *sc2 = nullptr;
+    uint64_t ne[2] = {0, 0};
+    PlaceEdges e{};
     if (Z) {
-        b.kind.alloc(Z + 16);
-        b.tab.alloc(((size_t) G1 + n + 2 * (Z + 1)) * sizeof(uint32_t));
-        uint32_t *inter_max = b.tab.as<uint32_t>(), *thr = inter_max + G1, *pre1 = thr + n, *pre2 = pre1 + (Z + 1);
-        PDL_HIP(hipMemsetAsync(inter_max, 0, (size_t) G1 * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_fill_u32, dim3((n + 255) / 256), dim3(256), 0, st, thr, n, 0x7f800000u);
-        const float *cf = c->qb.cells.as<float>();
-        BbhArgs<BbhQueryBlock> a{};
-        a.score = cf; a.row = reinterpret_cast<const int32_t *>(cf + 3 * run.cap); a.col = reinterpret_cast<const int32_t *>(cf + 4 * run.cap);
-        a.at = BbhQueryBlock{c->d_gen, N, c->G};
-        a.MS = c->qb.MS.as<float>(); a.CM = c->qb.CM.as<float>(); a.N = N + n; a.G = G1; a.Z = (uint32_t) Z;
-        a.inter_max = inter_max; a.thr = thr; a.kind = b.kind.as<uint8_t>();
-        bbh_filter(st, a);
-        b.e_src.alloc(3 * Z * sizeof(int32_t)); b.e_dst.alloc(3 * Z * sizeof(int32_t)); b.e_score.alloc(3 * Z * sizeof(float));
-        src1 = b.e_src.as<int32_t>(); dst1 = b.e_dst.as<int32_t>(); sc1 = b.e_score.as<float>();
-        src2 = src1 + 2 * Z; dst2 = dst1 + 2 * Z; sc2 = sc1 + 2 * Z;
-        scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, src1, dst1, sc1, pre1, 2}, ctl + PDL_PL_EDGES_1);
-        scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, src2, dst2, sc2, pre2, 1}, ctl + PDL_PL_EDGES_2);
+        e = place_bbh(c, c->qb, run.cap, BbhQueryBlock{c->d_gen, N, c->G}, N + n, 1, n, Z, ctl + PDL_PL_EDGES_1, ctl + PDL_PL_EDGES_2);
         spans.end();
         PinRead rd(c);
         const uint64_t *pt = rd.add<uint64_t>(ctl + PDL_PL_EDGES_1, PDL_PL_EDGES_2 - PDL_PL_EDGES_1 + 1);
         rd.sync();
-        n1 = 2 * pt[0]; n2 = pt[PDL_PL_EDGES_2 - PDL_PL_EDGES_1];
-        if (n1 > 2 * Z || n2 > Z) PDL_FAIL(PDL_ERR_DEVICE, "K-place: %llu + %llu edges of %llu cells", (unsigned long long) n1, (unsigned long long) n2, (unsigned long long) Z);
+        ne[0] = 2 * pt[0]; ne[1] = pt[PDL_PL_EDGES_2 - PDL_PL_EDGES_1];
+        if (ne[0] > 2 * Z || ne[1] > Z) PDL_FAIL(PDL_ERR_DEVICE, "K-place: %llu + %llu edges of %llu cells", (unsigned long long) ne[0], (unsigned long long) ne[1], (unsigned long long) Z);
         spans.begin();
     }
-    const int32_t *src[2] = {src1, src2}, *dst[2] = {dst1, dst2};
-    const uint64_t ne[2] = {n1, n2};
-    place_run(c, B, n, src, dst, ne, true, false, false, spans, out);
+    out.device_ms = place_run<PlaceOne>(c, B, PlaceQueries::one(N, n, ne[0], ne[1]), e.src, e.dst, true, false, spans, &out) + c->qb.spans.total_ms();
     // the edges themselves, in the host's insertion order: phase 1, then phase 2
-    out.src.resize(n1 + n2); out.dst.resize(n1 + n2); out.score.resize(n1 + n2);
-    if (n1) {
-        PDL_HIP(hipMemcpyAsync(out.src.data(), src1, n1 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.dst.data(), dst1, n1 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.score.data(), sc1, n1 * 4, hipMemcpyDeviceToHost, st));
+    const uint64_t E = ne[0] + ne[1];
+    out.src.resize(E); out.dst.resize(E); out.score.resize(E);
+    for (int l = 0; l < 2; l++) {
+        if (!ne[l]) continue;
+        const uint64_t at = l ? ne[0] : 0;
+        PDL_HIP(hipMemcpyAsync(out.src.data() + at, e.src[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(out.dst.data() + at, e.dst[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(out.score.data() + at, e.sc[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
     }
-    if (n2) {
-        PDL_HIP(hipMemcpyAsync(out.src.data() + n1, src2, n2 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.dst.data() + n1, dst2, n2 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.score.data() + n1, sc2, n2 * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (n1 + n2) PDL_HIP(hipStreamSynchronize(st));
-    out.edges_phase1 = (uint32_t) n1;
-    out.device_ms += c->qb.spans.total_ms();
+    if (E) PDL_HIP(hipStreamSynchronize(st));
+    out.edges_phase1 = (uint32_t) ne[0];
     if (info) {
         memset(info, 0, sizeof(*info));
         info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
@@ -415,14 +511,25 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     }
 }
 
-// pdl_placement_of_edges behind its argument checks: the same kernels over a caller's list on a caller's base (device pointers)
+// pdl_placement_of_edges behind its argument checks: the same stages over a caller's list on a caller's base (device pointers)
 void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, const int32_t *d_src, const int32_t *d_dst, uint64_t n_edges, pdl_place_result &out) {
+    hipStream_t st = c->stream;
     out = pdl_place_result{};
-    (void) place_begin(c);
+    uint64_t *ctl = place_begin(c);
     QSpans &spans = c->pb.spans;
-    spans.start(c->stream);
+    spans.start(st);
     spans.begin();
+    if (n_edges) {                                    // P-check
+        const uint32_t N = base.N, NC = N + n_query;
+        hipLaunchKernelGGL(k_place_check, fam_grid(n_edges), dim3(256), 0, st, d_src, d_dst, (uint32_t) n_edges, N, NC, ctl + PDL_PL_BAD_EDGES);
+        PDL_HIP(hipGetLastError());
+        spans.end();
+        PinRead rd(c);
+        const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_PL_BAD_EDGES, 1);
+        rd.sync();
+        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-place: %llu edges name a gene id outside [0, %u) or join two base genes (ids below %u)", (unsigned long long) *bad, NC, N);
+        spans.begin();
+    }
     const int32_t *src[2] = {d_src, nullptr}, *dst[2] = {d_dst, nullptr};
-    const uint64_t ne[2] = {n_edges, 0};
-    place_run(c, base, n_query, src, dst, ne, false, true, true, spans, out);
+    out.device_ms = place_run<PlaceOne>(c, base, PlaceQueries::one(base.N, n_query, n_edges, 0), src, dst, false, true, spans, &out);
 }
