@@ -539,7 +539,15 @@ typedef struct {
  *   pdl_dist_preprocess_finish_ranges  adopts the dictionary, sorts the received tuples (source-rank major) by gene
  *
  * `available` = 0 (gene ids beyond 22 bits, more than 256 ranks, a last run of exactly one record — the same verdict on every rank:
- * it depends on the input and the record counts only): nothing was built, the caller goes on with pdl_dist_preprocess_finish. */
+ * it depends on the input and the record counts only): nothing was built, the caller goes on with pdl_dist_preprocess_finish.
+ *
+ * Refusals (none of them damages the build or the pass: the contexts go on from where they stood, or from the call named here).
+ * PDL_ERR_STATE: any of these calls out of the order above — also pdl_dist_preprocess_ranges a second time on a run whose tuples it
+ * has built, and pdl_dist_preprocess_finish after it.  PDL_ERR_ARGUMENT: world 0 or above 64, rank >= world, NULL or misaligned
+ * arrays, record counts that do not add up to the runs; and what a peer could not have sent, counted on the device before it is
+ * used — a tuple whose key is not (this rank << 24 | a gene of this rank's genomes) or whose range ends past the gathered
+ * dictionary, tuples for a rank that owns no gene (then: pdl_dist_preprocess_begin again); a cell whose row or column is no gene
+ * or whose column is not a row of this rank (then: pdl_dist_score_begin again), cells for a rank without rows. */
 typedef struct {
     int available;
     const uint32_t *d_keys;         /* device, tuples grouped by destination rank, record order inside: (owner << 24 | gene) */

@@ -946,7 +946,7 @@ int pdl_dist_preprocess_finish(pdl_ctx *c, void *d_postings_all, uint64_t total_
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish without pdl_dist_preprocess_begin");
-    if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges built this run's range tuples (and took its group-head bits out): finish with pdl_dist_preprocess_finish_ranges");
+    if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish after a pdl_dist_preprocess_ranges that built this run's range tuples (and took its group-head bits out): finish with pdl_dist_preprocess_finish_ranges");
     if (!d_postings_all || ((uintptr_t) d_postings_all & 7) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary must be an 8-byte aligned device array");
     if (total_records < c->U_slice) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary (%llu records) is smaller than this rank's run (%llu)",
                                              (unsigned long long) total_records, (unsigned long long) c->U_slice);
@@ -964,6 +964,8 @@ int pdl_dist_preprocess_ranges(pdl_ctx *c, const uint64_t *run_records, const ui
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
     if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges without pdl_dist_preprocess_begin");
+    // (a second pass would count ranges on a run without heads: wrong tuples and counters, and nothing to show for it)
+    if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges has built this run's range tuples already (and took its group-head bits out): go on with pdl_dist_preprocess_finish_ranges");
     PDL_HIP(hipSetDevice(c->device));
     memset(out, 0, sizeof(*out));
     out->available = pdl_run_dist_ranges(c, run_records, genome_weights, genome_costs) ? 1 : 0;
@@ -991,9 +993,11 @@ int pdl_dist_preprocess_finish_ranges(pdl_ctx *c, void *d_postings_all, uint64_t
     });
 }
 
-int pdl_dist_genome_owner(const pdl_ctx *c, uint32_t *out) {
+int pdl_dist_genome_owner(const pdl_ctx *cc, uint32_t *out) {
+    pdl_ctx *c = const_cast<pdl_ctx *>(cc);
     if (!c || !out) return PDL_ERR_ARGUMENT;
-    if (!c->dist || c->dist_stage < 2) return PDL_ERR_STATE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->dist || c->dist_stage < 2) { c->err = "pdl_dist_genome_owner before pdl_dist_preprocess_finish: the genomes have not been dealt"; return PDL_ERR_STATE; }
     memcpy(out, c->h_owner.data(), (size_t) c->G * 4);
     return PDL_OK;
 }

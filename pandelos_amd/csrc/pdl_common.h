@@ -43,7 +43,8 @@ __device__ __forceinline__ void pdl_sync() {
 // total (no clearing needed); the atomically added words are cleared by the stage that is about to add to them.
 enum : size_t {
     PDL_CTL_RECORDS = 0,        // U: total of the dedup scan (K-rle); a multi-GPU finish uploads the gathered dictionary's count here
-    PDL_CTL_FREE_1 = 1,         // no stage uses it; cleared / uploaded with its neighbours
+    PDL_CTL_FREE_1 = 1,         // no stage of a build uses it (cleared / uploaded with its neighbours); pdl_dist_preprocess_finish_ranges counts
+                                //   the bad range tuples a peer sent here (k_tuple_check), before it uploads anything
     PDL_CTL_RANGES = 2,         // ranges built (total of the tile counts); sender-built lists: the tuples a rank received
     PDL_CTL_BAD_OFFSETS = 3,    // K-len: extra total of its apply functor (offsets that do not ascend)
     PDL_CTL_KSEQ_SUM = 4,       // k_genome_cost: sum of the genes' k-mer counts ...

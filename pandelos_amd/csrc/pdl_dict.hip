@@ -421,6 +421,18 @@ __global__ __launch_bounds__(256) void k_owner_keys(uint32_t *__restrict__ key, 
         key[i] = g | ((uint32_t) seq_owner[g] << 24);
     }
 }
+// What a peer sent (pdl_dist_preprocess_finish_ranges), counted before any of it is sorted or used, as k_fam_check counts a caller's
+// edges: a key that is not (this rank << 24 | a gene of this rank's genomes) — the gene sort promises pdl_sort_pairs that every gene
+// lies below N — and a packed range (gt_pack_range) that reaches past the gathered dictionary.
+__global__ __launch_bounds__(256) void k_tuple_check(const uint32_t *__restrict__ key, const unsigned long long *__restrict__ range, uint32_t n,
+                                                     const uint8_t *__restrict__ seq_owner, uint32_t n_seq, uint32_t rank, uint32_t total, uint64_t *d_bad) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = key[i], g = k & 0xffffffu;
+    const unsigned long long r = range[i];
+    const unsigned long long end = (r & 0xffffffffull) + ((r >> 32) & 0x3fffffull);       // first posting + postings
+    if ((k >> 24) != rank || g >= n_seq || seq_owner[g] != rank || end > total) atomicAdd(reinterpret_cast<unsigned long long *>(d_bad), 1ull);
+}
 
 // Also adds up total_visited (library.cpp:327) = the group sizes over a gene's ranges: the list is gene-sorted, so a
 // wave holds one or two genes as a rule; one atomic per (wave, gene).
@@ -1484,6 +1496,21 @@ void pdl_run_dist_finish_ranges(pdl_ctx *c, uint64_t total, uint32_t *d_keys, un
     ev_begin(c, EV_DIST_FINISH);
     if (total != c->dist_total) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary holds %llu records, the runs add up to %llu", (unsigned long long) total, (unsigned long long) c->dist_total);
     if (n_in >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 range tuples for one rank");
+    // the tuples come from other processes: nothing of this context is touched before they have been looked at
+    if (n_in) {
+        uint64_t own_genes = 0;
+        for (uint32_t g : c->shard) own_genes += c->h_genome_row_off[g + 1] - c->h_genome_row_off[g];
+        if (own_genes == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_preprocess_finish_ranges: %llu range tuples received by a rank that owns no gene", (unsigned long long) n_in);
+        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_FREE_1, 0, sizeof(uint64_t), st));
+        hipLaunchKernelGGL(k_tuple_check, dim3((uint32_t) ((n_in + 255) / 256)), dim3(256), 0, st, d_keys, d_ranges, (uint32_t) n_in, c->seq_owner.as<uint8_t>(), c->N,
+                           c->rank, (uint32_t) total, d_scal + PDL_CTL_FREE_1);
+        PDL_HIP(hipGetLastError());
+        PinRead rd(c);
+        const uint64_t *bad = rd.add<uint64_t>(d_scal + PDL_CTL_FREE_1, 1);
+        rd.sync();
+        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_preprocess_finish_ranges: %llu of the %llu received range tuples do not name this rank and a gene of its genomes (%u genes), or reach past the %llu records of the dictionary; begin the build again (pdl_dist_preprocess_begin)",
+                           (unsigned long long) *bad, (unsigned long long) n_in, c->N, (unsigned long long) total);
+    }
     uint64_t *h_u = reinterpret_cast<uint64_t *>(c->pin);       // (pinned scratch; rewritten only by the next PinRead, which comes after a sync)
     if (!h_u) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
     h_u[PDL_CTL_RECORDS] = total; h_u[PDL_CTL_FREE_1] = 0; h_u[PDL_CTL_RANGES] = n_in;

@@ -1690,7 +1690,10 @@ struct JoinCounters {
     uint32_t rows_tier2, rows_tier3, reloads;
     unsigned long long cells;                // staging cells reserved (>= cells staged: chunk tails are unused)
 };
-static JoinCounters join_counters(const uint32_t *w) {
+static JoinCounters join_counters(const uint32_t *w, bool inbox_filed = false) {
+    // (a multi-GPU pass has looked at the join's own count before the cells travelled: what is counted behind an inbox, the peers sent)
+    if (w[PDL_JC_ERRORS] && inbox_filed)
+        PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_score_finish: %u received cells name a gene beyond the set or a column that is not a row of this rank; begin the pass again (pdl_dist_score_begin)", w[PDL_JC_ERRORS]);
     if (w[PDL_JC_ERRORS]) PDL_FAIL(PDL_ERR_DEVICE, "join: %u internal consistency violations", w[PDL_JC_ERRORS]);
     JoinCounters j{w[PDL_JC_ROWS_T2], w[PDL_JC_ROWS_T3], w[PDL_JC_RELOADS], 0};
     memcpy(&j.cells, w + PDL_JC_CELLS, sizeof(j.cells));
@@ -1757,7 +1760,7 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
         memcpy(&zsum, tail + PDL_JT_EMITTED, sizeof(zsum));
         c->tm.tier1_rows = pl.tier0 ? tail[PDL_JT_ROWS_T1] : (pl.tier1 ? n_rows : 0);
         c->glb_clean = true;
-        jc = join_counters(tail);
+        jc = join_counters(tail, n_inbox != 0);
     }
     c->tm.aside_reloads = jc.reloads;
     c->tm.overflow_rows = jc.rows_tier3;
@@ -1915,9 +1918,11 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
     const uint32_t n_rows = c->n_task_rows;
     c->tm.inbox_cells = n_inbox;
     if (n_rows == 0) {
-        if (n_inbox) PDL_FAIL(PDL_ERR_ARGUMENT, "%llu cells received by a rank without rows", (unsigned long long) n_inbox);
+        if (n_inbox) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_score_finish: %llu cells received by a rank without rows", (unsigned long long) n_inbox);
         ev_end(c, EV_DIST_SCORE_FINISH); c->scored = true; c->dist_stage = 4; return;
     }
+    // (from here on the call counts cells into the rows and folds them into the maxima: one that fails leaves the pass to be begun again)
+    c->dist_stage = 2;
     const ScorePlan pl = score_plan(c);
     const unsigned long long cap = c->st_cap;
     if (n_inbox > cap) score_alloc_cells(c, pl, cap, n_inbox);             // (rare: the first allocation leaves room for `cap` received cells)

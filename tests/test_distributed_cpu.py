@@ -71,7 +71,14 @@ def test_two_gloo_ranks_cover_all_genomes_once():
 # ---- the exchange logic of the multi-GPU driver, on CPU tensors ----------------------------------------------------
 class _FakeRank:
     """Stands in for PangeneNative in DistributedPangenes: runs and outboxes with recognisable contents (rank and index
-    encoded in every word), so that the driver's offsets, split sizes and copy directions can be checked without a GPU."""
+    encoded in every word), so that the driver's offsets, split sizes and copy directions can be checked without a GPU.
+
+    It keeps the library's stage word (pdl_common.h: 0 none | 1 run built | 2 dictionary adopted | 3 outbox listed | 4 scored, and
+    "the senders built the range tuples") and refuses what the library refuses with PDL_ERR_STATE — a call out of order, a second
+    dist_preprocess_ranges — by raising: a driver that makes one ends its rank, and the test with it."""
+
+    class OutOfOrder(RuntimeError):
+        pass
 
     def __init__(self, rank, world, genomes=5):
         import torch
@@ -93,22 +100,34 @@ class _FakeRank:
             for i in range(int(self.counts[d])):
                 cells.append([rank, d, i, 7, 8, 9])
         self.outbox = torch.tensor(cells, dtype=torch.int32).reshape(-1, 6)
-        self.seen = {}
+        self.seen = {"calls": []}
+        self.stage, self.sender = 0, False
+
+    def _called(self, what, allowed):
+        if not allowed:
+            raise self.OutOfOrder(f"{what} at stage {self.stage}{', tuples built' if self.sender else ''}: PDL_ERR_STATE in the library")
+        self.seen["calls"].append(what)
 
     def copy_device(self, dst, src, nbytes):
         import ctypes
         ctypes.memmove(dst, src, nbytes)
 
     def dist_preprocess_begin(self, k, *a, keepalive=None):
+        self._called("begin", True)
+        self.stage, self.sender = 1, False
         return self.run.data_ptr(), self.records, self.records
 
     def dist_preprocess_finish(self, ptr, total, genome_weights=None, keepalive=None):
+        self._called("finish", self.stage == 1 and not self.sender)
+        self.stage = 2
         self.seen["dictionary"] = keepalive.clone()
         self.seen["total"] = total
         self.seen["weights"] = np.asarray(genome_weights).copy()
         self.seen["flow"] = "owner"
 
     def dist_preprocess_ranges(self, run_records, genome_weights, genome_costs):
+        self._called("ranges", self.stage == 1 and not self.sender)
+        self.sender = True
         self.seen["run_records"] = [int(x) for x in run_records]
         self.seen["weights"] = np.asarray(genome_weights).copy()
         self.seen["costs"] = np.asarray(genome_costs).copy()
@@ -116,6 +135,8 @@ class _FakeRank:
         return self.tkeys.data_ptr(), self.tranges.data_ptr(), self.tcounts, self.tctr
 
     def dist_preprocess_finish_ranges(self, ptr, total, d_keys, d_ranges, n_tuples, counter_sums, keepalive=None):
+        self._called("finish_ranges", self.stage == 1 and self.sender)
+        self.stage = 2
         full, rk, rr = keepalive
         self._full = full                        # (the runs may still be on their way: this call must not read the dictionary)
         self.seen["total"] = total
@@ -123,13 +144,66 @@ class _FakeRank:
         self.seen["sums"] = [int(x) for x in counter_sums]
         self.seen["flow"] = "sender"
 
+    def dist_genome_owner(self):
+        self._called("genome_owner", self.stage >= 2)
+        return np.arange(self.genomes, dtype=np.uint32) % self.world
+
     def dist_score_begin(self, world):
+        self._called("score_begin", self.stage >= 2)
+        self.stage = 3
         if getattr(self, "_full", None) is not None:
             self.seen["dictionary"] = self._full.clone()
         return self.outbox.data_ptr(), self.counts
 
     def dist_score_finish(self, ptr, n, keepalive=None):
+        self._called("score_finish", self.stage == 3)
+        self.stage = 4
         self.seen["inbox"] = keepalive[:n].clone()
+
+
+def test_the_twin_refuses_what_the_library_refuses():
+    """Table a of tests/test_gpu_dist_protocol.py, on the stand-in: every entry point in every state that refuses it."""
+    import torch
+    t = torch.zeros(4, dtype=torch.int64)
+
+    def to(state):
+        f = _FakeRank(0, 2)
+        if state in ("begun", "ranged", "finished", "finished by ranges", "listed", "scored"):
+            f.dist_preprocess_begin(3)
+        if state in ("ranged", "finished by ranges"):
+            f.dist_preprocess_ranges([3, 7], f.run_weights, f.run_costs)
+        if state == "finished by ranges":
+            f.dist_preprocess_finish_ranges(0, 10, 0, 0, 0, [0, 0, 0], keepalive=(t, t, t))
+        if state in ("finished", "listed", "scored"):
+            f.dist_preprocess_finish(0, 10, f.run_weights, keepalive=t)
+        if state in ("listed", "scored"):
+            f.dist_score_begin(2)
+        if state == "scored":
+            f.dist_score_finish(0, 0, keepalive=t)
+        return f
+
+    calls = {
+        "finish": lambda f: f.dist_preprocess_finish(0, 10, f.run_weights, keepalive=t),
+        "ranges": lambda f: f.dist_preprocess_ranges([3, 7], f.run_weights, f.run_costs),
+        "finish_ranges": lambda f: f.dist_preprocess_finish_ranges(0, 10, 0, 0, 0, [0, 0, 0], keepalive=(t, t, t)),
+        "genome_owner": lambda f: f.dist_genome_owner(),
+        "score_begin": lambda f: f.dist_score_begin(2),
+        "score_finish": lambda f: f.dist_score_finish(0, 0, keepalive=t),
+    }
+    refused = {"finish": ("fresh", "ranged", "finished", "finished by ranges"), "ranges": ("fresh", "ranged", "finished", "finished by ranges"),
+               "finish_ranges": ("fresh", "begun", "finished", "finished by ranges"), "genome_owner": ("fresh", "begun", "ranged"),
+               "score_begin": ("fresh", "begun", "ranged"), "score_finish": ("fresh", "finished", "finished by ranges", "scored")}
+    served = {"finish": ("begun",), "ranges": ("begun",), "finish_ranges": ("ranged",), "genome_owner": ("finished", "finished by ranges", "scored"),
+              "score_begin": ("finished", "finished by ranges", "scored"), "score_finish": ("listed",)}
+    for what, call in calls.items():
+        for state in refused[what]:
+            f = to(state)
+            before = (f.stage, f.sender, list(f.seen["calls"]))
+            with pytest.raises(_FakeRank.OutOfOrder):
+                call(f)
+            assert (f.stage, f.sender, f.seen["calls"]) == before, (what, state)      # a refusal changes nothing
+        for state in served[what]:
+            call(to(state))
 
 
 def _exchange_worker(rank, world, port, out, flow="host"):
@@ -156,7 +230,7 @@ def _exchange_worker(rank, world, port, out, flow="host"):
         dp.preprocess(3, t, t, t, 1, 1)
         dp.score_all()
         out.put((rank, fake.seen["dictionary"].tolist(), fake.seen["total"], fake.seen["weights"].tolist(), fake.seen["inbox"].tolist(),
-                 {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in fake.seen.items() if k in ("flow", "tuples", "sums", "costs", "run_records")}))
+                 {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in fake.seen.items() if k in ("flow", "tuples", "sums", "costs", "run_records", "calls")}))
     finally:
         dist.destroy_process_group()
 
@@ -192,6 +266,8 @@ def test_driver_exchanges_runs_and_cells_in_rank_order(world, flow):
         d, total, w, inbox, more = got[r]
         assert d[:total] == dictionary and total == len(dictionary) and w == weights
         assert more["flow"] == ("sender" if sender else "owner")
+        # the order of the library calls, which the twin would have refused otherwise (tests/test_gpu_dist_protocol.py: the library's own refusals)
+        assert more["calls"] == ["begin"] + (["ranges", "finish_ranges"] if sender else ["finish"]) + ["score_begin", "score_finish"]
         if sender:        # the tuples every rank filed for r, source-rank major, keys and ranges alike; the counters and costs summed
             want_k = [(r << 24) | (s << 8) | i for s in range(world) for i in range(int(fakes[s].tcounts[r]))]
             want_r = [(s << 40) | (r << 20) | i for s in range(world) for i in range(int(fakes[s].tcounts[r]))]
