@@ -424,7 +424,9 @@ struct pdl_ctx {
     DevBuf gene_info;             // uint4 [N] {k-mers, genome, task position, shard-local genome}: one load per candidate column in finalize
     DevBuf join_defer;            // filter tiers of the join: per workgroup, the first sightings put aside
     DevBuf glb_table;     // HBM tables of the overflow pass
-    bool glb_clean = false;   // all-zero (k_join_hbm leaves them that way)
+    bool glb_clean = false;   // all-zero where the layout below has its tables (k_join_hbm leaves them that way; its lists it leaves as they were)
+    uint32_t glb_cols = 0, glb_slots = 0;    // the layout the tables were last cleared or run for: columns (N), workgroups,
+    bool glb_wide = false;                   // 32-bit counters — under another one the old lists lie where the new tables do
     DevBuf row_desc2;     // descriptors of the rows handed from tier 1 to tier 2
     DevBuf mirror_cnt, mirror_ref;   // mirror mode (see pdl_join.hip); mirror_ref: the mirrored cells (MCell), per row
     DevView taskpos_of;                      // u32 [N] task position of every gene (0xffffffff: not a row of this context)

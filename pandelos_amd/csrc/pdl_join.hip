@@ -1501,10 +1501,15 @@ static ScorePlan score_plan(pdl_ctx *c) {
     }
     const size_t hbm_bytes = (size_t) pl.grid3 * N * ((pl.wide ? 2 : 1) * sizeof(uint64_t) + 3 * sizeof(uint32_t));
     if (c->glb_table.bytes < hbm_bytes) { c->glb_table.alloc(hbm_bytes); c->glb_clean = false; }
-    if (!c->glb_clean) {      // k_join_hbm leaves its tables zeroed: one memset per allocation
+    // k_join_hbm leaves its tables zeroed, not its touched / emitted lists, and the workgroups' tables and lists are laid out by N,
+    // the workgroup count and the counter width: a context rebuilt on a set of another size finds the old lists where its tables
+    // are.  One memset per allocation AND per layout (as q_join_hbm_tier keeps it for the query's tables).
+    if (c->glb_cols != N || c->glb_slots != pl.grid3 || c->glb_wide != pl.wide) c->glb_clean = false;
+    if (!c->glb_clean) {
         PDL_HIP(hipMemsetAsync(c->glb_table.p, 0, hbm_bytes, c->stream));
         c->glb_clean = true;
     }
+    c->glb_cols = N; c->glb_slots = pl.grid3; c->glb_wide = pl.wide;
     // Every workgroup reserves staging in chunks of CELL_CHUNK cells: a partly used chunk per workgroup of every tier
     pl.slack = 2ull * (pl.grid0 + pl.grid0b + pl.grid1 + pl.grid2 + pl.grid3) * CELL_CHUNK;
     return pl;
