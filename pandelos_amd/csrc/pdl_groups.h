@@ -530,24 +530,18 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, u
         if (digit_total && blockIdx.x == 0 && threadIdx.x == 0) *d_total = 0;      // (no records: no ranges)
         return;
     }
-    __shared__ uint32_t s_key[PDL_RADIX_TILE];
-    __shared__ unsigned long long s_val[PDL_RADIX_TILE];
-    __shared__ uint16_t s_cnt[GW_WAVES][PDL_RADIX_BINS];   // per wave: running count of each byte value, then its base inside the block (16-bit: three workgroups per CU)
-    __shared__ uint32_t s_tile_off[PDL_RADIX_BINS];
-    __shared__ uint32_t s_goff[PDL_RADIX_BINS];
-    __shared__ unsigned long long s_wsum[17];
+    __shared__ RadixTileLds<uint32_t, unsigned long long, uint16_t> s;      // (16-bit counters: three workgroups per CU)
     __shared__ unsigned long long s_own;
     const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
     const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
     const uint32_t tile = blockIdx.x * GW_WAVES + wave, t0 = tile * GW_TILE;
     const bool active = tile < tiles;                    // (wave-uniform; the last block may hold fewer than four tiles)
-    for (int w = 0; w < GW_WAVES; w++) s_cnt[w][tid] = 0;
+    s.clear_counts();
     const uint32_t goff = offs[(size_t) tid * n_tiles4 + blockIdx.x];
     const uint32_t dtot = digit_total ? digit_total[tid] : 0u;
     if (tid == 0) s_own = 0;
     pdl_sync();
 
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint2 po[GW_ROUNDS];
     unsigned long long val[GW_ROUNDS];
     uint16_t rank[GW_ROUNDS];
@@ -578,58 +572,23 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, u
             rbits |= (uint32_t) r << j;
         }
     }
-    // ---- the radix pass on the low byte of the gene (k_rs_scatter's ranking; an element is a record with a range) ----------
+    // ---- the radix pass on the low byte of the gene (the tile body of pdl_sort.h; an element is a record with a range) ------
+    uint32_t key[GW_ROUNDS];
 #pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        const bool valid = (rbits >> j) & 1u;
-        const uint32_t d = po[j].x & (PDL_RADIX_BINS - 1);
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const unsigned long long mb = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? mb : ~mb;
-        }
-        const uint32_t seen = s_cnt[wave][d];                       // earlier rounds (own wave only: no race)
-        rank[j] = (uint16_t) (seen + (uint32_t) __popcll(same & lt_mask));
-        if (valid && (same & lt_mask) == 0) s_cnt[wave][d] = (uint16_t) (seen + (uint32_t) __popcll(same));      // lowest lane of the set
-    }
+    for (int j = 0; j < GW_ROUNDS; j++) key[j] = po[j].x;
+    const auto valid = [&](int j) { return (rbits >> j) & 1u; };
+    radix_rank_rounds<8>(s.cnt[wave], key, 0u, valid, rank);
     pdl_sync();
-    uint32_t tot = 0;
-    uint32_t wcnt[GW_WAVES];
-#pragma unroll
-    for (int w = 0; w < GW_WAVES; w++) { wcnt[w] = s_cnt[w][tid]; tot += wcnt[w]; }
-    uint32_t tile_total, digit_base, grand_total;
-    const uint32_t ex = radix_tile_scan(tot, dtot, s_wsum, tile_total, digit_base, grand_total);
-    s_tile_off[tid] = ex;
-    s_goff[tid] = goff + digit_base;                     // (offsets from the three-launch scan: no digit totals, base 0)
+    uint32_t grand_total;
+    const uint32_t tile_total = radix_tile_layout(s, goff, dtot, grand_total);       // (offsets from the three-launch scan: no digit totals, base 0)
     if (digit_total && blockIdx.x == 0 && tid == 0) *d_total = grand_total;
-    uint32_t run = ex;
-#pragma unroll
-    for (int w = 0; w < GW_WAVES; w++) { s_cnt[w][tid] = (uint16_t) run; run += wcnt[w]; }
     pdl_sync();
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        if ((rbits >> j) & 1u) {
-            const uint32_t lp = s_cnt[wave][po[j].x & (PDL_RADIX_BINS - 1)] + rank[j];
-            s_key[lp] = po[j].x;
-            s_val[lp] = val[j];
-        }
-    }
+    radix_tile_place(s, wave, key, val, 0u, valid, rank);
 #pragma unroll
     for (int d = PDL_WAVE / 2; d > 0; d >>= 1) own_lookups += __shfl_xor(own_lookups, d, PDL_WAVE);
     if (lane == 0 && own_lookups) atomicAdd(&s_own, own_lookups);
     pdl_sync();
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        const uint32_t e = j * GW_THREADS + tid;                     // coalesced over the digit-sorted block
-        if (e < tile_total) {
-            const uint32_t k = s_key[e];
-            const uint32_t d = k & (PDL_RADIX_BINS - 1);
-            const uint64_t dst = (uint64_t) s_goff[d] + (e - s_tile_off[d]);
-            keys_out[dst] = k;
-            vals_out[dst] = s_val[e];
-        }
-    }
+    radix_tile_write(s, 0u, tile_total, keys_out, vals_out);
     if (tid == 0 && s_own) atomicAdd(&a.counters[2], s_own);
 }
 

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "pdl_common.h"
+#include "pdl_scan.h"
 
 // Sorts n pairs by key bits [begin_bit, end_bit) (begin_bit a multiple of 8: the passes below it were made by
 // the caller, see pdl_radix_offsets).  Input in (*keys_in, *vals_in); on return the sorted
@@ -36,6 +37,116 @@ bool pdl_radix_lean(const pdl_ctx *c, uint64_t n);                 // a sort of 
 // bytes of c->sort_tmp a sort of n elements works in: counts | offs | digit_total
 inline size_t pdl_radix_tmp_bytes(uint64_t n) {
     return (2 * (size_t) PDL_RADIX_BINS * ((n + PDL_RADIX_TILE - 1) / PDL_RADIX_TILE) + PDL_RADIX_BINS) * sizeof(uint32_t);
+}
+
+// ---- the radix tile body -----------------------------------------------------------------------------------------------------
+// One tile of a scatter pass, shared by k_rs_scatter<KeyT, ValT> (pdl_sort.hip) and k_range_scatter (pdl_groups.h): a workgroup
+// of RT_THREADS = 256 threads takes RT_TILE = 4096 elements, a wave RT_ROUNDS = 16 rounds of 64 consecutive ones.  The kernel
+// loads (or makes) key[j], val[j] of its lane's sixteen elements and says which of them are there (ValidF: bool operator()(int j));
+// the digit of an element is (key >> shift) & 0xff.  Four parts, in this order, a barrier between each two:
+//   radix_rank_rounds   rank[j] = elements of the same digit before this one in its wave; leaves the wave's digit counts
+//   radix_tile_layout   the tile scan (radix_tile_scan): the waves' counts become their bases inside the digit-sorted tile,
+//                       delta[d] = (where the tile's run of digit d starts in the output) - (where it starts in the tile)
+//   radix_tile_place    key and value to their place in the digit-sorted tile in LDS
+//   radix_tile_write    the digit-sorted tile out as coalesced runs: element e goes to delta[its digit] + e
+// CntT: the waves' counters, uint32_t or uint16_t (a count is at most 1024, a base at most 4096).  Positions are 32-bit: a pass
+// has fewer than 2^32 elements (pdl_sort_pairs refuses more, k_range_scatter counts records in 32 bits).
+constexpr int RT_THREADS = PDL_RADIX_BINS, RT_WAVES = RT_THREADS / PDL_WAVE, RT_TILE = PDL_RADIX_TILE, RT_ROUNDS = RT_TILE / RT_THREADS, RT_BINS = PDL_RADIX_BINS;
+static_assert(RT_ROUNDS == 16 && RT_WAVES == 4, "tile shape of the radix passes");
+
+template <class KeyT, class ValT, class CntT>
+struct RadixTileLds {
+    unsigned long long wsum[17];            // radix_tile_scan
+    ValT val[RT_TILE];
+    KeyT key[RT_TILE];
+    uint32_t delta[RT_BINS];
+    CntT cnt[RT_WAVES][RT_BINS];
+
+    __device__ __forceinline__ void clear_counts() {
+        for (int w = 0; w < RT_WAVES; w++) cnt[w][threadIdx.x] = 0;
+    }
+};
+
+template <class KeyT>
+__device__ __forceinline__ uint32_t radix_digit(KeyT k, uint32_t shift) { return (uint32_t) (k >> shift) & (RT_BINS - 1); }
+
+// NBITS: the bits of the digit that tell elements apart (8; fewer where every key of the pass has zeros above them).  The
+// lanes of a round that hold another digit are collected bit by bit: y = bit b of the own digit spread over a word, m = the
+// lanes whose bit b is set, so m ^ y has a 1 for every lane whose bit differs (one sign-extending bit-field extract, one
+// compare, two exclusive-ors per bit, the ors folded in pairs; no branch).  The first lane of a digit files the wave's new count.
+template <int NBITS, class KeyT, class CntT, class ValidF>
+__device__ __forceinline__ void radix_rank_rounds(CntT *cnt /* the wave's row */, const KeyT (&key)[RT_ROUNDS], uint32_t shift, ValidF valid,
+                                                  uint16_t (&rank)[RT_ROUNDS]) {
+    static_assert(NBITS >= 1 && NBITS <= 8, "a digit has eight bits");
+#pragma unroll
+    for (int j = 0; j < RT_ROUNDS; j++) {
+        const uint32_t d = radix_digit(key[j], shift);
+        const uint32_t seen = cnt[d];                                // earlier rounds (own wave only: no race); read here, used behind the ballots
+        const bool v = valid(j);
+        const unsigned long long vm = __ballot(v);
+        uint32_t diff_lo = 0, diff_hi = 0;
+#pragma unroll
+        for (int b = 0; b < NBITS; b++) {
+            uint32_t y = (uint32_t) ((int32_t) (d << (31 - b)) >> 31);
+            asm("" : "+v"(y));                                       // (the compare reads y: else the compiler tests a shifted copy of d, one instruction more)
+            const unsigned long long m = __ballot(y != 0u);
+            diff_lo |= (uint32_t) m ^ y;
+            diff_hi |= (uint32_t) (m >> 32) ^ y;
+        }
+        const uint32_t same_lo = (uint32_t) vm & ~diff_lo, same_hi = (uint32_t) (vm >> 32) & ~diff_hi;      // valid lanes of the wave holding digit d in this round
+        const uint32_t below_me = __builtin_amdgcn_mbcnt_hi(same_hi, __builtin_amdgcn_mbcnt_lo(same_lo, 0u));
+        rank[j] = (uint16_t) (seen + below_me);
+        const uint32_t now = seen + (uint32_t) __popc(same_lo) + (uint32_t) __popc(same_hi);
+        if (v && below_me == 0) cnt[d] = (CntT) now;
+    }
+}
+
+// After the barrier behind the ranking.  goff: offs[digit = thread][tile]; dtot: digit_total[thread] (0 where the offsets are
+// final).  Returns the elements of the tile; grand_total: those of the pass (where dtot is given).
+template <class KeyT, class ValT, class CntT>
+__device__ __forceinline__ uint32_t radix_tile_layout(RadixTileLds<KeyT, ValT, CntT> &s, uint32_t goff, uint32_t dtot, uint32_t &grand_total) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t tot = 0;
+    uint32_t wcnt[RT_WAVES];
+#pragma unroll
+    for (int w = 0; w < RT_WAVES; w++) { wcnt[w] = s.cnt[w][tid]; tot += wcnt[w]; }
+    uint32_t tile_total, digit_base;
+    const uint32_t ex = radix_tile_scan(tot, dtot, s.wsum, tile_total, digit_base, grand_total);
+    s.delta[tid] = goff + digit_base - ex;               // (mod 2^32; delta + position in the tile is the place in the output)
+    uint32_t run = ex;                                   // digit runs in digit order, inside a run wave 0's elements first
+#pragma unroll
+    for (int w = 0; w < RT_WAVES; w++) { s.cnt[w][tid] = (CntT) run; run += wcnt[w]; }
+    return tile_total;
+}
+
+template <class KeyT, class ValT, class CntT, class ValidF>
+__device__ __forceinline__ void radix_tile_place(RadixTileLds<KeyT, ValT, CntT> &s, uint32_t wave, const KeyT (&key)[RT_ROUNDS], const ValT (&val)[RT_ROUNDS],
+                                                 uint32_t shift, ValidF valid, const uint16_t (&rank)[RT_ROUNDS]) {
+#pragma unroll
+    for (int j = 0; j < RT_ROUNDS; j++) {
+        if (valid(j)) {
+            const uint32_t at = s.cnt[wave][radix_digit(key[j], shift)] + rank[j];
+            s.key[at] = key[j];
+            s.val[at] = val[j];
+        }
+    }
+}
+
+// After the barrier behind the placement.
+template <class KeyT, class ValT, class CntT>
+__device__ __forceinline__ void radix_tile_write(const RadixTileLds<KeyT, ValT, CntT> &s, uint32_t shift, uint32_t tile_total, KeyT *__restrict__ keys_out,
+                                                 ValT *__restrict__ vals_out) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < RT_ROUNDS; j++) {
+        const uint32_t e = j * RT_THREADS + tid;                     // coalesced over the digit-sorted tile
+        if (e < tile_total) {
+            const KeyT k = s.key[e];
+            const uint32_t dst = s.delta[radix_digit(k, shift)] + e;
+            keys_out[dst] = k;
+            vals_out[dst] = s.val[e];
+        }
+    }
 }
 
 extern template void pdl_sort_pairs<uint32_t, uint32_t>(pdl_ctx *, uint32_t *&, uint32_t *&, uint32_t *&, uint32_t *&, uint64_t, uint32_t, bool, const uint64_t *, uint32_t, bool, bool);

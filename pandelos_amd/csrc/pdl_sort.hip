@@ -22,15 +22,11 @@
 #include "pdl_scan.h"
 
 constexpr int RS_THREADS = 256;
-constexpr int RS_WAVES = RS_THREADS / PDL_WAVE;
 constexpr int RS_ROUNDS = 16;
 constexpr int RS_TILE = RS_THREADS * RS_ROUNDS;           // 4096 elements
 constexpr int RS_WAVE_SPAN = PDL_WAVE * RS_ROUNDS;        // elements of one wave inside a tile
 constexpr int RS_BINS = 256;
 static_assert(RS_THREADS == RS_BINS, "one thread per digit in the tile-level scans");
-
-template <class KeyT>
-__device__ __forceinline__ uint32_t rs_digit(KeyT k, uint32_t shift) { return (uint32_t) (k >> shift) & 0xffu; }
 
 template <class KeyT>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const KeyT *__restrict__ keys, uint64_t n_bound, const uint64_t *d_n, uint32_t shift,
@@ -53,7 +49,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const KeyT *__restrict__
 #pragma unroll
     for (int j = 0; j < RS_ROUNDS; j++) {
         const uint64_t i = base + (uint64_t) j * RS_THREADS + threadIdx.x;
-        if (i < n) atomicAdd(&s_h[rs_digit(key[j], shift)], 1u);
+        if (i < n) atomicAdd(&s_h[radix_digit(key[j], shift)], 1u);
     }
     pdl_sync();
     counts[(size_t) threadIdx.x * n_tiles + blockIdx.x] = s_h[threadIdx.x];
@@ -94,28 +90,23 @@ __global__ __launch_bounds__(RO_THREADS) void k_rs_offsets(const uint32_t *__res
     if (threadIdx.x == 0) digit_total[blockIdx.x] = carry;
 }
 
-template <class KeyT, class ValT>
+// NBITS: significant bits of this pass's digit (the last pass of a sort may have fewer than 8), see radix_rank_rounds.
+template <class KeyT, class ValT, int NBITS>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const KeyT *__restrict__ keys_in, const ValT *vals_in,
                                                            KeyT *__restrict__ keys_out, ValT *__restrict__ vals_out, uint64_t n_bound,
                                                            const uint64_t *d_n, uint32_t shift, uint32_t n_tiles, const uint32_t *__restrict__ offs,
-                                                           uint32_t nbits,         // significant bits of this pass's digit (the last pass of a sort may have fewer than 8)
                                                            const uint32_t *__restrict__ digit_total, uint64_t *d_total) {     // offsets from k_rs_offsets: see radix_tile_scan
     const uint64_t n = scan_count(n_bound, d_n);
-    if ((uint64_t) blockIdx.x * (RS_THREADS * RS_ROUNDS) >= n) {             // (uniform) tile past the end
+    if ((uint64_t) blockIdx.x * RS_TILE >= n) {                              // (uniform) tile past the end
         if (digit_total && blockIdx.x == 0 && threadIdx.x == 0) *d_total = 0;      // (a count of zero on the device: the total is zero)
         return;
     }
-    __shared__ KeyT s_key[RS_TILE];
-    __shared__ ValT s_val[RS_TILE];
-    __shared__ uint32_t s_cnt[RS_WAVES][RS_BINS];     // per wave: running count of each digit, then its base inside the tile
-    __shared__ uint32_t s_tile_off[RS_BINS];          // start of each digit's run inside the tile
-    __shared__ uint32_t s_goff[RS_BINS];              // global start of this tile's run of each digit
-    __shared__ unsigned long long s_wsum[17];
+    __shared__ RadixTileLds<KeyT, ValT, uint32_t> s;
 
     const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
     const uint64_t tile_base = (uint64_t) blockIdx.x * RS_TILE;
     const uint64_t wave_base = tile_base + (uint64_t) wave * RS_WAVE_SPAN;
-    for (int w = 0; w < RS_WAVES; w++) s_cnt[w][tid] = 0;
+    s.clear_counts();
     const uint32_t goff = offs[(size_t) tid * n_tiles + blockIdx.x];
     const uint32_t dtot = digit_total ? digit_total[tid] : 0u;
     pdl_sync();
@@ -140,60 +131,18 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const KeyT *__restric
 #pragma unroll
         for (int j = 0; j < RS_ROUNDS; j++) val[j] = (ValT) (wave_base + (uint64_t) j * PDL_WAVE + lane);
     }
-#pragma unroll
-    for (int j = 0; j < RS_ROUNDS; j++) {
-        const uint64_t i = wave_base + (uint64_t) j * PDL_WAVE + lane;
-        const bool valid = i < n;
-        const uint32_t d = rs_digit(key[j], shift);
-        unsigned long long same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            if ((uint32_t) b >= nbits) break;                       // (uniform) the bits above are zero in every key
-            const unsigned long long m = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? m : ~m;
-        }
-        // `same` = valid lanes of this wave holding digit d in this round
-        const uint32_t before = s_cnt[wave][d];                     // earlier rounds (own wave only: no race)
-        const uint32_t below_me = __builtin_amdgcn_mbcnt_hi((uint32_t) (same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) same, 0u));     // lanes of the set below this one
-        rank[j] = (uint16_t) (before + below_me);
-        if (valid && below_me == 0) s_cnt[wave][d] = before + (uint32_t) __popcll(same);   // lowest lane of the set
-    }
+    const uint64_t left = n - wave_base;             // (wave_base < n or not: an element is there when its place in the wave's span lies below)
+    const uint32_t lane_left = wave_base < n ? (uint32_t) (left < RS_WAVE_SPAN ? left : RS_WAVE_SPAN) : 0u;
+    const auto valid = [&](int j) { return (uint32_t) j * PDL_WAVE + lane < lane_left; };
+    radix_rank_rounds<NBITS>(s.cnt[wave], key, shift, valid, rank);
     pdl_sync();
-    // tile-level layout: digit runs in digit order, inside a run wave 0's elements first
-    uint32_t tot = 0;
-    uint32_t wcnt[RS_WAVES];
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) { wcnt[w] = s_cnt[w][tid]; tot += wcnt[w]; }
-    uint32_t tile_total, digit_base, grand_total;
-    const uint32_t ex = radix_tile_scan(tot, dtot, s_wsum, tile_total, digit_base, grand_total);
-    s_tile_off[tid] = ex;
-    s_goff[tid] = goff + digit_base;                     // (offsets from the three-launch scan: no digit totals, base 0)
+    uint32_t grand_total;
+    const uint32_t tile_total = radix_tile_layout(s, goff, dtot, grand_total);       // (offsets from the three-launch scan: no digit totals, base 0)
     if (digit_total && blockIdx.x == 0 && tid == 0) *d_total = grand_total;
-    uint32_t run = ex;
-#pragma unroll
-    for (int w = 0; w < RS_WAVES; w++) { s_cnt[w][tid] = run; run += wcnt[w]; }
     pdl_sync();
-#pragma unroll
-    for (int j = 0; j < RS_ROUNDS; j++) {
-        const uint64_t i = wave_base + (uint64_t) j * PDL_WAVE + lane;
-        if (i < n) {
-            const uint32_t lp = s_cnt[wave][rs_digit(key[j], shift)] + rank[j];
-            s_key[lp] = key[j];
-            s_val[lp] = val[j];
-        }
-    }
+    radix_tile_place(s, wave, key, val, shift, valid, rank);
     pdl_sync();
-#pragma unroll
-    for (int j = 0; j < RS_ROUNDS; j++) {
-        const uint32_t e = j * RS_THREADS + tid;                      // coalesced over the digit-sorted tile
-        if (e < tile_total) {
-            const KeyT k = s_key[e];
-            const uint32_t d = rs_digit(k, shift);
-            const uint64_t dst = (uint64_t) s_goff[d] + (e - s_tile_off[d]);
-            keys_out[dst] = k;
-            vals_out[dst] = s_val[e];
-        }
-    }
+    radix_tile_write(s, shift, tile_total, keys_out, vals_out);
 }
 
 template <class KeyT, class ValT>
@@ -215,9 +164,21 @@ void pdl_sort_pairs(pdl_ctx *c, KeyT *&keys_in, KeyT *&keys_out, ValT *&vals_in,
         if (!(first_counts_filed && p == begin_bit / 8))
             hipLaunchKernelGGL((k_rs_hist<KeyT>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in, n, d_n, shift, n_tiles, counts);
         const uint32_t *totals = pdl_radix_offsets(c, counts, offs, n_tiles, d_total, digit_total);
-        hipLaunchKernelGGL((k_rs_scatter<KeyT, ValT>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in,
-                           (p == begin_bit / 8 && iota_values) ? (const ValT *) nullptr : vals_in, keys_out, vals_out, n, d_n, shift, n_tiles, offs,
-                           keys_below_end_bit ? std::min<uint32_t>(8, end_bit - shift) : 8u, totals, d_total);
+        const ValT *vals = (p == begin_bit / 8 && iota_values) ? (const ValT *) nullptr : vals_in;
+        const auto scatter = [&](auto nbits) {
+            hipLaunchKernelGGL((k_rs_scatter<KeyT, ValT, decltype(nbits)::value>), dim3(n_tiles), dim3(RS_THREADS), 0, c->stream, keys_in, vals, keys_out, vals_out,
+                               n, d_n, shift, n_tiles, offs, totals, d_total);
+        };
+        switch (keys_below_end_bit ? std::min<uint32_t>(8, end_bit - shift) : 8u) {       // the bits the pass has to match: a compile-time count
+            case 1: scatter(std::integral_constant<int, 1>()); break;
+            case 2: scatter(std::integral_constant<int, 2>()); break;
+            case 3: scatter(std::integral_constant<int, 3>()); break;
+            case 4: scatter(std::integral_constant<int, 4>()); break;
+            case 5: scatter(std::integral_constant<int, 5>()); break;
+            case 6: scatter(std::integral_constant<int, 6>()); break;
+            case 7: scatter(std::integral_constant<int, 7>()); break;
+            default: scatter(std::integral_constant<int, 8>()); break;
+        }
         PDL_HIP(hipGetLastError());
         std::swap(keys_in, keys_out);
         std::swap(vals_in, vals_out);
