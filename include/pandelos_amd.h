@@ -317,6 +317,34 @@ typedef struct {
 PDL_API int pdl_remove_genomes(pdl_ctx *, const uint32_t *genomes /* [count] distinct ids < G */, uint32_t count,
                                pdl_cost *out_cost /* may be NULL: the remaining set's */, pdl_remove_info *info /* may be NULL */);
 
+/* ---- append and remove across a change of the alphabet: option "alphabet_rekey" ------------------------------------------
+ * With the option at 0 (the default) both calls above refuse whatever changes the alphabet, as described.  With it at 1:
+ *   pdl_append_genomes accepts bytes the base lacks.  The union's rank table is made on the host from the base's letters and the
+ *     new genes' (all of them, genes shorter than k included, as a build counts them); the base's sorted stream is written again,
+ *     key by key, in the union's base with the union's digits (one streaming pass, no sort: adding letters moves digits
+ *     monotonically, so order and equality of keys are kept); the new genes are ranked with the union's table and merged in.
+ *   pdl_remove_genomes is exact in both directions, provided the context was BUILT with the option on: pdl_preprocess (all three
+ *     forms) then records, per genome, the letters of its genes shorter than k — the ones no key shows — in a table the context owns
+ *     and appends and removals keep up.  The remaining alphabet is the digits of the keys that stay plus those letters of the genomes
+ *     that stay.  Equal to the context's: the removal goes through (also where the default refuses conservatively).  Smaller: the
+ *     compacted stream is written again for the smaller alphabet.  Without the table (the option was set after the build) a removal
+ *     that misses a digit is refused as by default, and the message names the option; an append does not need the table.
+ * The key width follows the new table in both directions (ACGT at k = 16 has 32-bit keys, ACGTN 38-bit ones).
+ * Both need ranks that are the polynomial itself BEFORE and AFTER the call: no hash fallback, B^k < 2^64.  Otherwise
+ * PDL_ERR_UNSUPPORTED, and the message says which side is hashed or wrapped; like every refusal it comes before anything changes.
+ * After PDL_OK the context equals, bit for bit, what pdl_preprocess leaves on the union / the remaining set: the contract above.
+ * pdl_get_timings: the re-key pass counts into sort_rank_ms (with "stage_timers" 0 it is not timed apart and shows only in the totals).
+ * Queries and placements with a byte the base lacks keep refusing.
+ * pdl_get_rekey_info: what the last successful pdl_append_genomes / pdl_remove_genomes of the context did about the alphabet. */
+typedef struct {
+    uint32_t letters_before, letters_after;     /* B of the rank table before and after the call */
+    uint32_t key_bits_before, key_bits_after;   /* rank_bits: 32-bit keys up to 32, 64-bit keys above */
+    uint64_t keys_rewritten;                    /* elements of the sorted stream written again (0: no re-key) */
+    float rekey_ms;                             /* the re-key pass on the device (0 with option "stage_timers" 0) */
+    uint32_t rekeyed;                           /* 1: the call changed the rank table */
+} pdl_rekey_info;
+PDL_API int pdl_get_rekey_info(pdl_ctx *, pdl_rekey_info *out);
+
 /* ---- gene families: the network's components and their collisions, on the device, from the edges where they lie --------
  * What netclu_ng.py does with the .net before Girvan-Newman: the connected components of the gene network (:58-66) and, per
  * component, whether it holds a collision — two genes of one genome that are not adjacent (get_max_collision, :75-92).  A
@@ -485,7 +513,11 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"
  * off; 0: a histogram kernel and a three-launch scan for every pass.  Same results either way: for parity tests and A/B timing),
  * "aside_test_reload" 0|1 (test switch: the next scoring pass
- * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs). */
+ * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs),
+ * "alphabet_rekey" 0|1 (default 0: pdl_append_genomes / pdl_remove_genomes go through where the alphabet changes, by writing the
+ * sorted stream's keys again; set BEFORE pdl_preprocess it also makes the build record the letters of genes shorter than k, one
+ * small launch more, which an exact removal needs — see pdl_get_rekey_info; like "query_batch_bytes" it leaves the context's
+ * scores in place). */
 PDL_API int pdl_set_option(pdl_ctx *, const char *name, int64_t value);
 
 /* ---- multi-GPU: one context per GPU, the caller moves bytes between them (RCCL over xGMI) -----------------------

@@ -908,6 +908,11 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
         c->opt_query_batch_bytes = (uint64_t) value;
         return PDL_OK;        // (no bearing on a scoring pass: the context's scores stay)
     }
+    else if (n == "alphabet_rekey") {
+        if (value != 0 && value != 1) { c->err = "alphabet_rekey: 0 or 1"; return PDL_ERR_ARGUMENT; }
+        c->opt_alphabet_rekey = value != 0;
+        return PDL_OK;        // (nor has this one)
+    }
     else { c->err = "unknown option " + n; return PDL_ERR_ARGUMENT; }
     c->scored = false;        // the next scoring call runs with the new setting
     return PDL_OK;
@@ -1153,6 +1158,13 @@ int pdl_remove_genomes(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_
     fill_cost(c, out_cost);
     return PDL_OK;
     });
+}
+
+int pdl_get_rekey_info(pdl_ctx *c, pdl_rekey_info *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->last_rekey;
+    return PDL_OK;
 }
 
 int pdl_get_rank_table(const pdl_ctx *c, uint8_t out[256], uint64_t *out_lm) {

@@ -548,9 +548,20 @@ struct pdl_ctx {
         EventSpans<2> spans;          // its two stretches of device work
     } rm;
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
+    // K-rekey (pdl_rekey.h): option "alphabet_rekey" — an append or a removal that changes the alphabet writes the stream's keys again
+    bool opt_alphabet_rekey = false;
+    bool short_valid = false;                 // h_short_letters describes the set (built with the option on, kept up by appends and removals)
+    std::vector<uint32_t> h_short_letters;    // [G][8] 256 bits per genome: the letters of its genes shorter than k (they show in no key)
+    struct RekeyBufs {
+        DevBuf keys;                          // the re-keyed stream on its way into keys_b (then: the old keys, released behind the call)
+        DevBuf table, short_letters;          // K-rekey's table on the device; k_short_letters' output
+        std::vector<uint64_t> h_table;        // (kept alive for the asynchronous upload)
+        std::vector<uint32_t> h_table32;
+    } rk;
+    pdl_rekey_info last_rekey{};              // what the last append or removal did (pdl_get_rekey_info)
 
     pdl_timings tm{};
-    EventPair ev[16];
+    EventPair ev[17];
     uint8_t *pin = nullptr;       // pinned host scratch for the small device->host reads (true async DMA, no staging copy)
     uint8_t *pin_dev = nullptr;   // the same buffer as the device addresses it (hipHostGetDevicePointer)
     size_t pin_bytes = 0;
@@ -744,12 +755,12 @@ inline int pdl_cus(pdl_ctx *c) {
 
 // event helpers
 enum { EV_HIST, EV_RANK, EV_SORT1, EV_DICT, EV_SORT2, EV_RANGES, EV_JOIN, EV_JOIN_OVF, EV_ORDER, EV_PRE_TOTAL, EV_SCORE_TOTAL,
-       EV_DIST_BEGIN, EV_DIST_FINISH, EV_DIST_SCORE_FINISH, EV_DIST_RANGES, EV_MERGE, EV_COUNT };
-static_assert(EV_COUNT <= 16, "pdl_ctx::ev");
+       EV_DIST_BEGIN, EV_DIST_FINISH, EV_DIST_SCORE_FINISH, EV_DIST_RANGES, EV_MERGE, EV_REKEY, EV_COUNT };
+static_assert(EV_COUNT <= 17, "pdl_ctx::ev");
 
 // An event record is a marker packet between two dispatches (a few us of idle stream each); the per-stage pairs can be
 // switched off ("stage_timers" 0) when only the totals and the join's launch time are wanted (bench.py's timed loop).
-inline bool ev_is_stage(int i) { return i == EV_HIST || i == EV_RANK || i == EV_SORT1 || i == EV_DICT || i == EV_SORT2 || i == EV_RANGES || i == EV_ORDER || i == EV_JOIN_OVF || i == EV_MERGE; }
+inline bool ev_is_stage(int i) { return i == EV_HIST || i == EV_RANK || i == EV_SORT1 || i == EV_DICT || i == EV_SORT2 || i == EV_RANGES || i == EV_ORDER || i == EV_JOIN_OVF || i == EV_MERGE || i == EV_REKEY; }
 inline void ev_begin(pdl_ctx *c, int i) {
     c->ev[i].used = false;
     if (!c->opt_stage_timers && ev_is_stage(i)) return;

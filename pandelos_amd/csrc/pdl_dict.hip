@@ -10,6 +10,7 @@
 //   K-groups  k_fold_last_record, then per tile from the head bits: costs / count / write (pdl_groups.h)   library.cpp:297-335
 //   K-ranges  k_group_write or k_range_scatter (ranges), sort by gene, k_gather_ranges (+ per-gene cost), k_seq_offsets   library.cpp:312-327
 //   K-cost    k_genome_cost       per-genome and total lookups               library.cpp:337-350,535-538
+//   (option "alphabet_rekey": k_short_letters, pdl_rekey.h — the letters of genes shorter than k, per genome; no reference function)
 //
 // HBM layout after this stage (what the join reads):
 //   post   uint2[U]   {gene, count}       rank-group major, ascending gene inside a group
@@ -21,6 +22,7 @@
 #include "pdl_sort.h"
 #include "pdl_append.h"
 #include "pdl_remove.h"
+#include "pdl_rekey.h"
 #include "pdl_groups.h"
 
 #include <algorithm>
@@ -880,6 +882,14 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
     stage_sort_and_dedup<KeyT>(c, keys_in, keys_out, vals_in, vals_out, M, counts_filed);
     ev_end(c, EV_DICT);
     if (c->layout_deferred) pdl_finish_layout(c);   // device input: the genome layout is host work too, and nothing before this point needed it
+    if (c->opt_alphabet_rekey) {                    // (G is known from here on; the residues are still the caller's to read)
+        c->rk.short_letters.alloc((size_t) c->G * 32);
+        hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) c->G * 4 + 255) / 256, 1024)), dim3(256), 0, c->stream,
+                           c->rk.short_letters.as<uint64_t>(), (size_t) c->G * 4);
+        hipLaunchKernelGGL(k_short_letters, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->d_res, c->d_off, c->d_gen, c->N, c->G, c->rp.k, c->R,
+                           c->rk.short_letters.as<uint32_t>());
+        PDL_HIP(hipGetLastError());
+    }
     if (!only_complexity) pdl_prepare_tasks(c);     // host work + small uploads while the device sorts
     // U (records) and the range count stay on the device until the end of the build: everything below is sized and
     // launched for the bound M and reads the counts there — no host round trip in the middle of the pipeline
@@ -957,6 +967,36 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
     return query_dictionary<uint32_t>(c, res, off, kmer_off, n, m, n_res, (uint32_t *) keys_a, (uint32_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
 }
 
+// K-rekey (pdl_rekey.h) of the first m keys of keys_b, `from_key64` wide, for the rank table c->rp / c->key64 hold ALREADY; the
+// plan's table is in c->rk.h_table.  Queued on the stream: keys_b names the re-keyed stream afterwards and c->rk.keys the old one,
+// which the caller releases once the stream has been waited for.  The values stay where they are.
+static void rekey_in_place(pdl_ctx *c, uint64_t m, bool from_key64, const RkArgs &a) {
+    auto &rk = c->rk;
+    hipStream_t st = c->stream;
+    const size_t kb = c->key64 ? 8 : 4;
+    rk.keys.alloc(m * kb);
+    rk.table.alloc((size_t) a.entries * kb);
+    ev_begin(c, EV_REKEY);
+    if (c->key64) {
+        PDL_HIP(hipMemcpyAsync(rk.table.p, rk.h_table.data(), (size_t) a.entries * 8, hipMemcpyHostToDevice, st));
+        if (from_key64) pdl_rekey_stream<uint64_t, uint64_t>(st, c->keys_b.as<uint64_t>(), rk.keys.as<uint64_t>(), m, a, rk.table.as<uint64_t>());
+        else pdl_rekey_stream<uint32_t, uint64_t>(st, c->keys_b.as<uint32_t>(), rk.keys.as<uint64_t>(), m, a, rk.table.as<uint64_t>());
+    } else {
+        rk.h_table32.assign(rk.h_table.begin(), rk.h_table.end());      // (B'^k <= 2^32: every entry fits)
+        PDL_HIP(hipMemcpyAsync(rk.table.p, rk.h_table32.data(), (size_t) a.entries * 4, hipMemcpyHostToDevice, st));
+        if (from_key64) pdl_rekey_stream<uint64_t, uint32_t>(st, c->keys_b.as<uint64_t>(), rk.keys.as<uint32_t>(), m, a, rk.table.as<uint32_t>());
+        else pdl_rekey_stream<uint32_t, uint32_t>(st, c->keys_b.as<uint32_t>(), rk.keys.as<uint32_t>(), m, a, rk.table.as<uint32_t>());
+    }
+    ev_end(c, EV_REKEY);
+    c->keys_b.swap(rk.keys);
+}
+// the rank table changes: c->rp, the letters, the key width
+static void adopt_rank_table(pdl_ctx *c, const RankParams &rp, const uint8_t present[256]) {
+    c->rp = rp;
+    memcpy(c->alpha_present, present, 256);
+    c->key64 = rp.rank_bits > 32;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K-append (pdl_append_genomes): new genes join the dictionary that is there.
 //
@@ -967,6 +1007,9 @@ const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t 
 //   A-merge   pdl_merge_streams (pdl_append.h)   (keys_b, vals_b)[M] + the new stream -> the free half of the ping-pong; the
 //                                       new genes' ids get their N there
 //   tail      K-rle over the M + m stream, task layout, K-groups / K-ranges / K-cost: the build's own stages
+// Option "alphabet_rekey": A-alpha comes with K-hist over the new residues; a byte the base lacks makes the union's RankParams on the
+// host (rank_init_host, as a build), and in front of A-dict the base's stream is re-keyed for them (K-rekey, pdl_rekey.h), a pass of
+// its own into a work buffer that then changes places with keys_b.
 //
 // Nothing behind K-rank reads residues, and the stream the tail starts from equals the union's sort (see pdl_append.h), so
 // the context ends up as pdl_preprocess on the union leaves it.
@@ -1009,20 +1052,59 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
 
     // A-alpha (and the new genes on their way to the device): the context is only read
     spans.begin();
-    q.ctl.alloc(16 * sizeof(uint64_t));
+    const bool rekey_on = c->opt_alphabet_rekey;
+    constexpr size_t A_HIST = 16;             // q.ctl: [0] the smallest absent byte (k_q_alpha) | [16, 272) K-hist of the new residues (rekey_on)
+    q.ctl.alloc((A_HIST + 256) * sizeof(uint64_t));
     unsigned long long *d_bad = q.ctl.as<unsigned long long>();
-    PDL_HIP(hipMemsetAsync(d_bad, 0, sizeof(uint64_t), st));
+    PDL_HIP(hipMemsetAsync(d_bad, 0, (rekey_on ? A_HIST + 256 : 1) * sizeof(uint64_t), st));
     genes.upload(c, residues);
     pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, d_bad);
+    if (rekey_on && Rq) {
+        hipLaunchKernelGGL(k_hist, dim3((uint32_t) std::min<uint64_t>((Rq / 64 + HIST_THREADS - 1) / HIST_THREADS + 1, 2048)), dim3(HIST_THREADS), 0, st,
+                           q.res.as<uint8_t>(), Rq, d_bad + A_HIST);
+        PDL_HIP(hipGetLastError());
+    }
     spans.end();
+    bool rekey = false;
+    RankParams rp1{};
+    uint8_t present1[256];
+    RkArgs rka{};
     {
         PinRead rd(c);
-        const uint64_t *pb = rd.add<uint64_t>(d_bad, 1);
+        const uint64_t *pb = rd.add<uint64_t>(d_bad, rekey_on ? A_HIST + 256 : 1);
         rd.sync();
-        if (pb[0]) pdl_fail_absent_byte(pb[0], "appended");
+        if (pb[0] && !rekey_on) pdl_fail_absent_byte(pb[0], "appended");
+        if (pb[0]) {                          // the union's rank table, as a build makes it; every refusal before anything changes
+            uint64_t counters[256];
+            for (int b = 0; b < 256; b++) { present1[b] = c->alpha_present[b] || pb[A_HIST + b]; counters[b] = present1[b]; }
+            rank_init_host(rp1, counters, (int) c->rp.k);
+            if (!rk_exact(c->rp))
+                PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_append_genomes: appended byte 0x%02x is not in the base's alphabet, and the base's ranks (%u letters, "
+                         "k = %u: %s) cannot be decoded into letters and written again (option alphabet_rekey); rebuild from the union",
+                         256u - (uint32_t) pb[0], c->rp.base, c->rp.k, rk_why_not(c->rp));
+            if (!rk_exact(rp1))
+                PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_append_genomes: appended byte 0x%02x is not in the base's alphabet, and the union's ranks (%u letters, "
+                         "k = %u) would be %s: the base's keys cannot be written again for them (option alphabet_rekey); rebuild from the union",
+                         256u - (uint32_t) pb[0], rp1.base, rp1.k, rk_why_not(rp1));
+            rka = rk_plan(c->rp, c->alpha_present, rp1, present1, c->rk.h_table);
+            rekey = true;
+        }
     }
 
     context_changes(c);
+    pdl_rekey_info ri{};
+    ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
+    const bool key64_0 = c->key64;
+    if (rekey) {
+        adopt_rank_table(c, rp1, present1);
+        ri.letters_after = rp1.base; ri.key_bits_after = rp1.rank_bits; ri.keys_rewritten = M0; ri.rekeyed = 1;
+    }
+    if (c->short_valid) {                     // the letters of the new genomes' genes shorter than k (a handful of residues: on the host)
+        c->h_short_letters.resize((size_t) (G0 + n_new_genomes) * 8, 0u);
+        for (uint32_t i = 0; i < n; i++)
+            if (offsets[i + 1] - offsets[i] < c->rp.k)
+                for (uint64_t r = offsets[i]; r < offsets[i + 1]; r++) c->h_short_letters[(size_t) genome_ids[i] * 8 + (residues[r] >> 5)] |= 1u << (residues[r] & 31);
+    }
     const uint32_t N1 = N0 + n, G1 = G0 + n_new_genomes;
     const uint64_t M1 = M0 + m;
     const size_t kb = c->key64 ? 8 : 4;
@@ -1041,7 +1123,7 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         q.keys_a.alloc(m * kb); q.keys_b.alloc(m * kb); q.vals_a.alloc(m * 4); q.vals_b.alloc(m * 4);
         c->scan_tmp.alloc(pdl_merge_split_words(M1) * sizeof(uint32_t));
     }
-    c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
+    c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = c->ev[EV_REKEY].used = false;
     rebuild_behind_sort(c, spans, M1, N1, G1, [&] {        // (behind the clearing, as ever: the new genes' tails of the per-gene arrays, A-dict, A-merge)
         PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
         PDL_HIP(hipMemcpyAsync(c->gene_len.as<uint32_t>() + N0, genes.len.data(), n * 4ull, hipMemcpyHostToDevice, st));
@@ -1053,15 +1135,19 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         } else {
             PDL_HIP(hipMemcpyAsync(c->own_gen.p, c->h_genome_of.data(), (size_t) N1 * 4, hipMemcpyHostToDevice, st));
         }
+        if (rekey) rekey_in_place(c, M0, key64_0, rka);
         if (m) {
             if (c->key64) append_sorted_stream<uint64_t>(c, n, m, Rq, N0, M0);
             else append_sorted_stream<uint32_t>(c, n, m, Rq, N0, M0);
         }
     });
+    c->rk.keys.release();
     const float ms0 = spans.ms(0), ms1 = spans.ms(1);
     const float rank_ms = ev_ms(c, EV_RANK), sort_ms = ev_ms(c, EV_SORT1), merge_ms = ev_ms(c, EV_MERGE);
+    ri.rekey_ms = ev_ms(c, EV_REKEY);
+    c->last_rekey = ri;
     pdl_timings t{};                          // the preprocess fields describe the append, the scoring fields start again
-    t.rank_ms = rank_ms; t.sort_rank_ms = sort_ms + merge_ms; t.dict_ms = ev_ms(c, EV_DICT);
+    t.rank_ms = rank_ms; t.sort_rank_ms = sort_ms + merge_ms + ri.rekey_ms; t.dict_ms = ev_ms(c, EV_DICT);
     t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
     t.preprocess_total_ms = ms0 + ms1;
     c->tm = t;
@@ -1087,6 +1173,9 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
 // they cover all B letters the remaining set's table is the context's, and the stream the tail starts from is the one
 // pdl_preprocess would sort for the remaining set (see pdl_remove.h).  A letter that survives only in genes shorter than k
 // cannot be seen this way: that removal is refused although a rebuild would have agreed.
+// Option "alphabet_rekey", on a context built with it: c->h_short_letters holds exactly those letters, so the remaining alphabet is
+// known — the digits seen plus the short genes' letters of the genomes that stay.  The context's: the removal goes through.
+// Smaller: the tail starts with K-rekey (pdl_rekey.h) of the compacted stream for the remaining set's RankParams.
 // ------------------------------------------------------------------------------------------------
 template <class KeyT>
 static void remove_from_stream(pdl_ctx *c, uint64_t m, const uint32_t *new_id, uint64_t *d_ctl) {
@@ -1144,6 +1233,10 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
     for (uint32_t i = 0; i < N0; i++) if (gmap[c->h_genome_of[i]] != RM_GONE) genome_of.push_back(gmap[c->h_genome_of[i]]);
     const uint32_t N1 = (uint32_t) genome_of.size();
     uint64_t M1 = 0, gone_residues = 0;
+    bool digit_missing = false, rekey = false;
+    RankParams rp1{};
+    uint8_t present1[256];
+    RkArgs rka{};
     {
         PinRead rd(c);
         const uint64_t *pc = rd.add<uint64_t>(d_ctl, PDL_RM_WORDS);
@@ -1156,6 +1249,7 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
         const uint32_t *seen = reinterpret_cast<const uint32_t *>(pc + PDL_RM_SEEN);
         for (uint32_t d = 0; d < c->rp.base; d++) {
             if (seen[d]) continue;
+            if (c->opt_alphabet_rekey) { digit_missing = true; break; }
             int letter = 0;
             for (int b = 0; b < 256; b++) if (c->alpha_present[b] && c->rp.rank_values[b] == d) { letter = b; break; }
             PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: no k-mer of the remaining genes holds the letter 0x%02x%s%c%s: without it the remaining set has "
@@ -1163,20 +1257,59 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
                      letter, letter >= 0x20 && letter < 0x7f ? " ('" : "", letter >= 0x20 && letter < 0x7f ? (char) letter : ' ',
                      letter >= 0x20 && letter < 0x7f ? "')" : "", c->rp.k);
         }
+        if (digit_missing) {
+            if (!c->short_valid)
+                PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: no k-mer of the remaining genes holds every letter of the alphabet, and the letters of genes "
+                         "shorter than k=%u are not known: option alphabet_rekey was not set when the context was built (set it before pdl_preprocess); "
+                         "rebuild from the remaining genes", c->rp.k);
+            // the remaining alphabet, exactly: every residue lies in a k-mer or in a gene shorter than k
+            uint32_t bits[8] = {};
+            for (uint32_t g = 0; g < G0; g++)
+                if (gmap[g] != RM_GONE) for (int w = 0; w < 8; w++) bits[w] |= c->h_short_letters[(size_t) g * 8 + w];
+            bool same = true;
+            for (int b = 0; b < 256; b++) {
+                present1[b] = c->alpha_present[b] && (seen[c->rp.rank_values[b]] || (bits[b >> 5] >> (b & 31) & 1u));
+                same = same && present1[b] == c->alpha_present[b];
+            }
+            if (!same) {
+                uint64_t counters[256];
+                for (int b = 0; b < 256; b++) counters[b] = present1[b];
+                rank_init_host(rp1, counters, (int) c->rp.k);
+                if (!rk_exact(rp1))           // (cannot happen: fewer letters than an exact table has)
+                    PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: the remaining set's ranks (%u letters, k = %u) would be %s", rp1.base, rp1.k, rk_why_not(rp1));
+                rka = rk_plan(c->rp, c->alpha_present, rp1, present1, c->rk.h_table);
+                rekey = true;
+            }
+        }
     }
 
     context_changes(c);
+    pdl_rekey_info ri{};
+    ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
+    const bool key64_0 = c->key64;
+    if (rekey) {
+        adopt_rank_table(c, rp1, present1);
+        ri.letters_after = rp1.base; ri.key_bits_after = rp1.rank_bits; ri.keys_rewritten = M1; ri.rekeyed = 1;
+    }
+    if (c->short_valid) {                     // the table closes up like the genome ids
+        for (uint32_t g = 0; g < G0; g++)
+            if (gmap[g] != RM_GONE && gmap[g] != g) memcpy(&c->h_short_letters[(size_t) gmap[g] * 8], &c->h_short_letters[(size_t) g * 8], 32);
+        c->h_short_letters.resize((size_t) G1 * 8);
+    }
     c->keys_a.swap(c->keys_b); c->vals_a.swap(c->vals_b);      // the sorted stream is what keys_b / vals_b name
     c->kseq_len.swap(r.kseq); c->gene_len.swap(r.glen);
     c->own_gen.swap(r.gen);                                     // the context owns the ids from here on, as after an append
     pdl_replace_layout(c, std::move(genome_of));          // N, G, h_genome_of, genome rows
     c->M = M1; c->R -= gone_residues;
     c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
-    c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = false;
-    rebuild_behind_sort(c, r.spans, M1, N1, G1, [] {});          // (the compacted stream is in place)
+    c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = c->ev[EV_REKEY].used = false;
+    rebuild_behind_sort(c, r.spans, M1, N1, G1, [&] { if (rekey) rekey_in_place(c, M1, key64_0, rka); });      // (the compacted stream is in place)
+    c->rk.keys.release();
     const float ms0 = r.spans.ms(0), ms1 = r.spans.ms(1);
+    ri.rekey_ms = ev_ms(c, EV_REKEY);
+    c->last_rekey = ri;
     pdl_timings t{};                          // the preprocess fields describe the removal, the scoring fields start again
-    t.sort_rank_ms = ms0; t.dict_ms = ev_ms(c, EV_DICT);
+    t.sort_rank_ms = ms0 + ri.rekey_ms; t.dict_ms = ev_ms(c, EV_DICT);
     t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
     t.preprocess_total_ms = ms0 + ms1;
     c->tm = t;
@@ -1191,11 +1324,17 @@ void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity) {
     hipStream_t st = c->stream;
     ev_begin(c, EV_PRE_TOTAL);
     c->dist = false; c->dist_stage = 0; c->post_ext = nullptr; c->dist_sender = false;
+    c->short_valid = false;
     stage_alphabet_and_lengths(c, kvalue, only_complexity);
     if (c->key64) dictionary_pipeline<uint64_t>(c, only_complexity);
     else dictionary_pipeline<uint32_t>(c, only_complexity);
     ev_end(c, EV_PRE_TOTAL);
     PDL_HIP(hipStreamSynchronize(st));
+    if (c->opt_alphabet_rekey) {                    // the table is the context's own from here on, on the host: a few words a genome
+        c->h_short_letters.assign((size_t) c->G * 8, 0u);
+        PDL_HIP(hipMemcpy(c->h_short_letters.data(), c->rk.short_letters.p, (size_t) c->G * 32, hipMemcpyDeviceToHost));
+        c->short_valid = true;
+    }
     c->tm.hist_ms = ev_ms(c, EV_HIST);
     c->tm.rank_ms = ev_ms(c, EV_RANK);
     c->tm.sort_rank_ms = ev_ms(c, EV_SORT1);

@@ -1,0 +1,155 @@
+// pdl_rekey.h — K-rekey: the sorted k-mer stream of a context is written again for another alphabet (option "alphabet_rekey" of
+// pdl_append_genomes / pdl_remove_genomes, include/pandelos_amd.h), included from pdl_dict.hip.
+//
+// A polynomial rank with an exact B^k is its k-mer written in base B with the dense digits rank_values[letter] (library.cpp:
+// 75-86, 96-99).  When letters join or leave the alphabet, B becomes B' and every digit d becomes map[d], and map is strictly
+// increasing on the letters both alphabets hold: digit by digit the order of two k-mers stays what it was, so
+//     key' = sum map[d_i] * B'^i        (d_i: digit i of the key in base B, low digit first)
+// is monotone in the key and equal keys stay equal.  The stream (keys, vals) stays sorted by (rank, input position): one
+// streaming pass over the keys leaves what the sort of the new set's build would have left; the values are not touched.
+//
+//   decode   a key below 2^32 gives its digits by one multiplication each (RmDigits of pdl_remove.h: magic = ceil(2^64 / B),
+//            exact for every x < 2^32).  A 64-bit key is first cut into parts of h digits, h the most with B^h <= 2^32, by a
+//            multiply-high with floor(2^64 / B^h) and one correction (the estimate is the quotient or one below it); since
+//            B^(h+1) > 2^32 and B^k < 2^64, k <= 2h + 1: three parts at most, the third a single digit.
+//   map +    one table T[i][d] = map[d] * B'^i of k * B entries (at most 2040 where B^k < 2^64: 16 KB), made by the host, in LDS:
+//   encode   key' = sum T[i][d_i] — an LDS load and an add per digit instead of a byte load and a 64-bit multiplication.
+//
+// A thread takes four consecutive keys (16-byte loads and stores; the streams start at allocations), its four digit chains
+// side by side; the m % 4 keys of the tail go one to a thread of the first workgroup.
+#pragma once
+#include "pdl_common.h"
+#include "pdl_remove.h"
+
+constexpr int RK_THREADS = 256, RK_ITEMS = 4;
+
+struct RkArgs {
+    uint32_t k, base;           // of the keys that come in
+    uint32_t nparts, h;         // parts a key is cut into (1 for 32-bit keys), digits of every part but the last
+    uint64_t magic;             // RmDigits::magic of `base`
+    uint64_t part_div;          // B^h
+    uint64_t part_magic;        // floor(2^64 / B^h)
+    uint32_t entries;           // k * base
+};
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+// ranks are the polynomial itself: no hashing, and B^k fits 64 bits EXACTLY (key_bits == rank_bits does not say so, see pdl_run_remove)
+inline bool rk_exact(const RankParams &rp) {
+    bool exact = !rp.hash_fallback && rp.base != 0;
+    unsigned __int128 bk = 1;
+    for (uint32_t i = 0; i < rp.k && exact; i++) { bk *= rp.base; exact = (bk >> 64) == 0; }
+    return exact;
+}
+inline const char *rk_why_not(const RankParams &rp) { return rp.hash_fallback ? "hashed" : "wrapped past 2^64"; }
+
+// The plan of a re-key from (from, present_from) to (to, present_to), both exact, same k: the kernel's arguments and the table
+// (as 64-bit words; the launch narrows them for 32-bit output).  A letter only `from` holds has no image: its row entries stay
+// 0, and no key that is re-keyed holds it (a removal re-keys what stays).
+inline RkArgs rk_plan(const RankParams &from, const uint8_t present_from[256], const RankParams &to, const uint8_t present_to[256],
+                      std::vector<uint64_t> &table) {
+    RkArgs a{};
+    a.k = from.k; a.base = from.base;
+    a.magic = rm_digits(from.k, from.base).magic;
+    a.h = 0; a.part_div = 1;
+    while (a.h < a.k && a.part_div * from.base <= (1ull << 32)) { a.part_div *= from.base; a.h++; }      // (B <= 256: h >= 1)
+    a.nparts = (a.k + a.h - 1) / a.h;
+    a.part_magic = a.part_div > 1 ? ~0ull / a.part_div + (~0ull % a.part_div == a.part_div - 1 ? 1 : 0) : 0;
+    a.entries = a.k * a.base;
+    table.assign(a.entries, 0);
+    uint64_t pw = 1;
+    for (uint32_t i = 0; i < a.k; i++) {
+        for (int b = 0; b < 256; b++)
+            if (present_from[b] && present_to[b]) table[(size_t) i * a.base + from.rank_values[b]] = (uint64_t) to.rank_values[b] * pw;
+        pw *= to.base;          // (B'^k fits: the last product is not used beyond it)
+    }
+    return a;
+}
+
+#ifdef __HIPCC__
+// ---- device --------------------------------------------------------------------------------------------------------------------
+template <class KeyIn, class KeyOut>
+__device__ __forceinline__ void rk_items(const KeyIn (&x)[RK_ITEMS], KeyOut (&y)[RK_ITEMS], const RkArgs &a, const KeyOut *T) {
+    uint64_t rest[RK_ITEMS];
+#pragma unroll
+    for (int j = 0; j < RK_ITEMS; j++) { rest[j] = x[j]; y[j] = 0; }
+    uint32_t left = a.k, row = 0;
+    for (uint32_t p = 0; p < a.nparts; p++) {                       // (uniform: one part for 32-bit keys, three at most)
+        const uint32_t nd = left < a.h ? left : a.h;
+        uint32_t part[RK_ITEMS];
+#pragma unroll
+        for (int j = 0; j < RK_ITEMS; j++) {
+            if (sizeof(KeyIn) == 8 && p + 1 < a.nparts) {
+                uint64_t q = __umul64hi(rest[j], a.part_magic);     // the quotient or one below it
+                uint64_t r = rest[j] - q * a.part_div;
+                if (r >= a.part_div) { q++; r -= a.part_div; }
+                part[j] = (uint32_t) r; rest[j] = q;
+            } else part[j] = (uint32_t) rest[j];                    // (the last part is below B^h <= 2^32)
+        }
+        for (uint32_t i = 0; i < nd; i++, row += a.base) {
+#pragma unroll
+            for (int j = 0; j < RK_ITEMS; j++) {
+                const uint32_t q = (uint32_t) __umul64hi((uint64_t) part[j], a.magic);
+                const uint32_t d = part[j] - q * a.base;            // (< base: row + d < entries)
+                y[j] += T[row + d];
+                part[j] = q;
+            }
+        }
+        left -= nd;
+    }
+}
+
+template <class KeyIn, class KeyOut>
+__global__ __launch_bounds__(RK_THREADS) void k_rekey(const KeyIn *__restrict__ in, KeyOut *__restrict__ out, uint64_t m, RkArgs a,
+                                                      const KeyOut *__restrict__ table) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rk_lds[];
+    KeyOut *T = reinterpret_cast<KeyOut *>(rk_lds);
+    for (uint32_t i = threadIdx.x; i < a.entries; i += RK_THREADS) T[i] = table[i];
+    pdl_sync();
+    constexpr int WI = sizeof(KeyIn) * RK_ITEMS / 16, WO = sizeof(KeyOut) * RK_ITEMS / 16;
+    const uint4 *in16 = reinterpret_cast<const uint4 *>(in);
+    uint4 *out16 = reinterpret_cast<uint4 *>(out);
+    const uint64_t chunks = m / RK_ITEMS, stride = (uint64_t) gridDim.x * RK_THREADS;
+    KeyIn x[RK_ITEMS];
+    KeyOut y[RK_ITEMS];
+    for (uint64_t ch = (uint64_t) blockIdx.x * RK_THREADS + threadIdx.x; ch < chunks; ch += stride) {
+        uint4 w[WI];
+#pragma unroll
+        for (int i = 0; i < WI; i++) w[i] = in16[ch * WI + i];
+        __builtin_memcpy(x, w, sizeof(x));
+        rk_items<KeyIn, KeyOut>(x, y, a, T);
+        uint4 v[WO];
+        __builtin_memcpy(v, y, sizeof(y));
+#pragma unroll
+        for (int i = 0; i < WO; i++) out16[ch * WO + i] = v[i];
+    }
+    const uint64_t t = chunks * RK_ITEMS + threadIdx.x;            // the tail: a key a thread
+    if (blockIdx.x == 0 && t < m) {
+#pragma unroll
+        for (int j = 0; j < RK_ITEMS; j++) x[j] = in[t];
+        rk_items<KeyIn, KeyOut>(x, y, a, T);
+        out[t] = y[0];
+    }
+}
+
+// out[0 .. m) = in[0 .. m) re-keyed by (a, table); `in` and `out` are 16-byte aligned and distinct; `d_table` holds a.entries KeyOut words
+template <class KeyIn, class KeyOut>
+static void pdl_rekey_stream(hipStream_t st, const KeyIn *in, KeyOut *out, uint64_t m, const RkArgs &a, const KeyOut *d_table) {
+    if (!m) return;
+    const uint64_t blocks = (m / RK_ITEMS + RK_THREADS - 1) / RK_THREADS;
+    hipLaunchKernelGGL((k_rekey<KeyIn, KeyOut>), dim3((uint32_t) std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 4096)), dim3(RK_THREADS),
+                       (size_t) a.entries * sizeof(KeyOut), st, in, out, m, a, d_table);
+    PDL_HIP(hipGetLastError());
+}
+
+// ---- the letters of genes shorter than k, per genome (256 bits each): they show in no key, and a removal must know them -----------
+__global__ __launch_bounds__(256) void k_short_letters(const uint8_t *__restrict__ res, const uint64_t *__restrict__ off, const uint32_t *__restrict__ gen,
+                                                       uint32_t n, uint32_t n_genomes, uint32_t k, uint64_t n_res, uint32_t *__restrict__ letters) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = off[i], e = off[i + 1];
+    if (e <= b || e - b >= k || e > n_res) return;
+    const uint32_t g = gen[i];
+    if (g >= n_genomes) return;
+    for (uint64_t r = b; r < e; r++) atomicOr(&letters[(size_t) g * 8 + (res[r] >> 5)], 1u << (res[r] & 31));      // (fewer than k residues)
+}
+#endif

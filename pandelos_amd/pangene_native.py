@@ -246,6 +246,7 @@ class PangeneNative:
                                                  C.byref(cost), C.byref(info)))
         self.cost = cost
         self.last_append_info = info.as_dict()
+        self.last_rekey_info = self._rekey_info()
 
     def append_idata(self, data: PangeneIData) -> None:
         """``append`` for the genes of a ``PangeneIData`` (one genome or several): its genome ids 0, 1, ... become
@@ -264,6 +265,14 @@ class PangeneNative:
         self._check(self._lib.pdl_remove_genomes(self._ctx, ids.ctypes.data if ids.size else None, len(ids), C.byref(cost), C.byref(info)))
         self.cost = cost
         self.last_remove_info = info.as_dict()
+        self.last_rekey_info = self._rekey_info()
+
+    def _rekey_info(self) -> dict:
+        """What the last append or removal did about the alphabet (``pdl_get_rekey_info``; option ``alphabet_rekey``): letters and
+        key bits before and after, keys written again, the pass's device time, and whether the rank table changed at all."""
+        info = _lib.PdlRekeyInfo()
+        self._check(self._lib.pdl_get_rekey_info(self._ctx, C.byref(info)))
+        return info.as_dict()
 
     def _take_scores(self, s) -> Scores:
         try:

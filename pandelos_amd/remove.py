@@ -1,6 +1,6 @@
 """Take genomes out of a pan-genome without a rebuild — and, with ``-a``, put others in their place.
 
-    python -m pandelos_amd.remove -i base.faa -k K -r LABEL [-r LABEL ...] [-a new.faa ...] -o out.net
+    python -m pandelos_amd.remove -i base.faa -k K -r LABEL [-r LABEL ...] [-a new.faa ...] [--rekey] -o out.net
 
 The base set is ingested and its dictionary built; the genomes named by their ``.faa`` labels (the header's text before the
 first tab) then leave it by ``pdl_remove_genomes``: one stable compaction pass over the sorted k-mer stream in HBM, no residue
@@ -11,6 +11,9 @@ file that holds the remaining records (and the appended files behind them).
 A label that names no genome of the base, no ``-r`` at all, or every genome named is refused before the device is touched
 (exit 2).  When the library cannot prove from its keys that the remaining set has the base's alphabet (``PDL_ERR_UNSUPPORTED``:
 hashed ranks, or a letter of which no k-mer is left) the command says why and rebuilds from the remaining records of the file.
+With ``--rekey`` (option ``alphabet_rekey``, set before the build) the library knows the remaining alphabet exactly: a letter
+that only seemed lost no longer stops it, one that is lost makes it write the keys of its stream again for the smaller
+alphabet, and appended files may bring letters the set lacks.  The rebuild remains for what it still refuses (hashed ranks).
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ from typing import Sequence
 
 import numpy as np
 
-from .append import AppendError, check_append
+from .append import AppendError, check_append, print_rekey
 from .pangene_idata import PangeneIData
 from .pangenes import run
 
@@ -71,6 +74,7 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("-r", "--remove", action="append", default=[], help="label of a genome to remove (may be given several times)")
     ap.add_argument("-a", "--append", action="append", default=[], help="new genomes (.faa), appended after the removal in the order given")
     ap.add_argument("-o", "--output", required=True, help="network of the remaining set (.net)")
+    ap.add_argument("--rekey", action="store_true", help="follow a change of the alphabet by re-keying the sorted stream (option alphabet_rekey)")
     args = ap.parse_args(argv)
 
     # every label is checked before the device is touched
@@ -91,6 +95,8 @@ def main(argv: Sequence[str] | None = None) -> int:
     from .pangene_native import PangeneNative
     nat = PangeneNative.open()
     try:
+        if args.rekey:
+            nat.set_option("alphabet_rekey", 1)
         nat.ingest_faa(args.input)
         nat.preprocess_ingested(args.kvalue)
         try:
@@ -98,6 +104,7 @@ def main(argv: Sequence[str] | None = None) -> int:
             info = nat.last_remove_info
             print(f"{', '.join(args.remove)}: {info['sequences']} genes, {info['kmer_occurrences']} k-mers, {info['records']} records "
                   f"removed in {info['device_ms']:.3f} ms on the device")
+            print_rekey(nat.last_rekey_info)
         except _lib.PdlError as e:
             if e.code != _lib.PDL_ERR_UNSUPPORTED:
                 raise
@@ -108,6 +115,7 @@ def main(argv: Sequence[str] | None = None) -> int:
             info = nat.last_append_info
             print(f"{path}: {len(new.sequences)} genes, {len(new.genomeNames)} genome(s), {info['kmer_occurrences']} k-mers, "
                   f"{info['records']} records appended in {info['device_ms']:.3f} ms on the device")
+            print_rekey(nat.last_rekey_info)
         print("------------\nCOMPUTATIONAL COSTS: ")
         print(f"Total cost: {nat.cost.total_cost} lookups")
         print(f"Linear ratio: {nat.cost.linear_ratio:g}\n------------\n")
