@@ -230,6 +230,20 @@ struct RankParams {
     uint32_t key_bits;      // bits a rank can really occupy: rank_bits — or 64 where B^k wrapped past 2^64 UNNOTICED by rank_init's overflow test
                             // (library.cpp:104-111 looks one multiplication ahead with wrapped products: 22 letters, k = 15), the ranks being the polynomial mod 2^64
 };
+#define RABIN_MODULO 18446744073709551557ULL   /* 2^64 - 59, library.cpp:19 */
+// base^k < 2^64, in exact arithmetic (the reference's own test compares wrapped products and lets some wraps through: 20 letters
+// at k = 15 wrap unnoticed to a 64-bit rank_bits).  The one place that says so: rank_init_host's key_bits and rk_exact ask here.
+inline bool pow_fits_u64(uint32_t base, uint32_t k) {
+    unsigned __int128 p = 1;
+    for (uint32_t i = 0; i < k; i++) { p *= base; if (p >> 64) return false; }
+    return true;
+}
+
+// The width of the context's keys as a type: f(uint64_t{}) or f(uint32_t{}), for a generic lambda that names it decltype(tag).
+template <class F> inline decltype(auto) pdl_with_key(bool key64, F &&f) {
+    if (key64) return f(uint64_t{});
+    return f(uint32_t{});
+}
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
@@ -536,7 +550,7 @@ struct pdl_ctx {
         DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: query-query (lo, hi) keys
         QSpans spans;                               // up to three stretches of device work
     } pb;
-    EventSpans<2> app_spans;          // pdl_append_genomes: its two stretches of device work
+    EventSpans<2> set_spans;          // pdl_append_genomes, pdl_remove_genomes (they exclude each other): the call's two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
         DevBuf gmap;                  // u32 [G] new genome id, RM_GONE for a genome that leaves
@@ -545,7 +559,6 @@ struct pdl_ctx {
         DevBuf kseq, gen, glen;       // u32 [N'] compacted kseq_len / genome ids / gene_len: they swap places with the context's
         DevBuf tile;                  // u32 [tiles] k-mers that stay per tile of the stream, then their exclusive scan
         DevBuf ctl;                   // u64 [PDL_RM_WORDS]
-        EventSpans<2> spans;          // its two stretches of device work
     } rm;
     uint8_t alpha_present[256] = {};  // letters of the base (residue histogram > 0): what a query may contain
     // K-rekey (pdl_rekey.h): option "alphabet_rekey" — an append or a removal that changes the alphabet writes the stream's keys again

@@ -2,7 +2,7 @@
 // (ig/native/library.cpp:189-371), one kernel (or kernel group) per reference function:
 //
 //   K-hist    k_hist              alphabet (which letters occur)             library.cpp:216-228
-//   (host)    rank_init_host      rank table, B^(k-1), overflow -> hashing   library.cpp:88-132
+//   (host)    rank_init_host      rank table, B^(k-1), overflow -> hashing   library.cpp:88-132   (pdl_rekey.h, host section)
 //   K-len     k_kseq_len          kseq_lengths + k-mer stream offsets        library.cpp:250-262
 //   K-rank    k_rank / k_rank_hash   per-gene k-mer ranks                    library.cpp:75-86,134-150
 //   K-sort    pdl_sort_pairs      stable LSD radix sort by rank              library.cpp:172-187,270-278
@@ -17,6 +17,9 @@
 //   ranges uint4[U']  {first posting, postings, own count, group size}   gene major (U' = records in groups >= 2);
 //                     without a shard a gene's range holds only the postings after its own record (genes above it)
 //   seq_off u32[N+1]  range list of each gene;   kseq_len u32[N];   cost u64[N]
+//
+// K-append and K-remove share their host side: rk_change (the alphabet decision, pdl_rekey.h), commit_set_change,
+// genome_ids_on_device, rekey_in_place and the tail rebuild_behind_sort; the key width picks a template through pdl_with_key.
 #include "pdl_common.h"
 #include "pdl_scan.h"
 #include "pdl_sort.h"
@@ -27,8 +30,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-#define RABIN_MODULO 18446744073709551557ULL   /* 2^64 - 59, library.cpp:19 */
 
 
 __global__ __launch_bounds__(256) void k_zero_u64(uint64_t *p, size_t n) {
@@ -68,45 +69,6 @@ __global__ __launch_bounds__(HIST_THREADS) void k_hist(const uint8_t *__restrict
         for (uint64_t t = n16 * 16 + threadIdx.x; t < n; t += HIST_THREADS) s_seen[res[t]] = 1u;
     pdl_sync();
     if (s_seen[threadIdx.x]) hist[threadIdx.x] = 1ull;
-}
-
-// library.cpp:88-132, literally (64-bit wraparound included); adds rank_bits for the device sort.
-static void rank_init_host(RankParams &rp, const uint64_t counters[256], int kvalue) {
-    memset(&rp, 0, sizeof(rp));
-    rp.k = (uint32_t) kvalue;
-    int rank = 0;
-    for (int i = 0; i < 256; i++)
-        if (counters[i] > 0) rp.rank_values[i] = (uint8_t) rank++;
-    const uint8_t rank_base = (uint8_t) rank;
-    rp.base = rank_base;
-    uint64_t last_multiplier = 1;
-    bool has_overflow = false;
-    int tmp_kvalue = kvalue - 1;
-    while (tmp_kvalue--) {
-        uint64_t ovflw_test = last_multiplier;
-        last_multiplier *= rank_base;
-        if (has_overflow) {
-            last_multiplier %= RABIN_MODULO;
-        } else if ((ovflw_test > last_multiplier) || (ovflw_test * rank_base > last_multiplier * rank_base)) {
-            has_overflow = true;
-            last_multiplier = ((ovflw_test % RABIN_MODULO) * rank_base) % RABIN_MODULO;
-        }
-    }
-    rp.last_multiplier = last_multiplier;
-    rp.hash_fallback = has_overflow ? 1u : 0u;
-    rp.key_bits = 64;
-    if (has_overflow) {
-        rp.rank_bits = 64;
-    } else {
-        uint64_t rank_tmp = last_multiplier * rank_base;   // B^k, fits (the loop above looked one step ahead)
-        rp.rank_bits = rank_tmp ? bit_length64(rank_tmp - 1) : 1;
-        if (rp.rank_bits == 0) rp.rank_bits = 1;
-        // did B^k fit?  (exact arithmetic: the reference's test compares wrapped products and lets some wraps through)
-        unsigned __int128 exact = 1;
-        bool fits = true;
-        for (int i = 0; i < kvalue && fits; i++) { exact *= rank_base; fits = (exact >> 64) == 0; }
-        if (fits) rp.key_bits = rp.rank_bits;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -538,6 +500,13 @@ static void launch_genome_cost(pdl_ctx *c, size_t w_sum, size_t w_max) {
 // Host side of the stages.  The words of the control block (c->scalars) are declared in pdl_common.h (PDL_CTL_*).
 // ------------------------------------------------------------------------------------------------
 
+// the rank table changes: c->rp, the letters, the key width — written here only (a build, an append, a removal)
+static void adopt_rank_table(pdl_ctx *c, const RankParams &rp, const uint8_t present[256]) {
+    c->rp = rp;
+    memcpy(c->alpha_present, present, 256);
+    c->key64 = rp.rank_bits > 32;
+}
+
 // K-hist + K-len + the rank table; leaves M, the rank parameters and the key width in the context.
 static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complexity) {
     hipStream_t st = c->stream;
@@ -575,14 +544,16 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
         M = pc[PDL_CTL_KMERS]; bad = pc[PDL_CTL_BAD_OFFSETS];
     }
     if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "offsets must ascend from 0 to the residue count (%llu)", (unsigned long long) c->R);
-    rank_init_host(c->rp, counters, kvalue);
-    for (int i = 0; i < 256; i++) c->alpha_present[i] = counters[i] ? 1 : 0;
+    RankParams rp;
+    uint8_t present[256];
+    for (int i = 0; i < 256; i++) present[i] = counters[i] ? 1 : 0;
+    rank_init_host(rp, counters, kvalue);
+    adopt_rank_table(c, rp, present);
     c->M = M;
     c->only_complexity = only_complexity;
     if (M == 0) PDL_FAIL(PDL_ERR_EMPTY, "no gene is at least k=%d residues long: the dictionary is empty", kvalue);
     // the scan above sums in 32 bits: make sure it cannot have wrapped, and keep stream positions in u32
     if (c->R >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues (%llu) need 64-bit stream positions", (unsigned long long) c->R);
-    c->key64 = c->rp.rank_bits > 32;
 }
 
 // K-rank over the whole stream into (keys_a, vals_a); d_bins != nullptr: also the interval histogram (multi-GPU build).
@@ -901,8 +872,9 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// What the incremental rebuilds (K-append, K-remove) share.  Both leave a sorted stream of the new set in (keys_b, vals_b) and
-// then run the build's own stages on it; the next entry point that changes the set does the same through these two.
+// What the incremental rebuilds (K-append, K-remove) share.  Both read the context only until the host has decided about the
+// alphabet (rk_change, pdl_rekey.h), commit (commit_set_change), leave a sorted stream of the new set in (keys_b, vals_b) and then
+// run the build's own stages on it (rebuild_behind_sort); the next entry point that changes the set does the same through these.
 // ------------------------------------------------------------------------------------------------
 // "From here on the context changes": whatever was derived from the old set is stale, and a failure leaves the context
 // un-preprocessed.  (The families would go with the edges anyway: pdl_run_bbh_all drops them before anyone reads them.)
@@ -911,28 +883,64 @@ static void context_changes(pdl_ctx *c) {
     c->mirror_valid = false; c->edges_valid = false; c->fam_valid = false;
 }
 
+// The commit of a call that changes the set, behind its last refusal: the context changes, and where the letters do (ch.rekey) it
+// takes the new rank table.  Returns what the tail needs: the width of the keys that are there, and the call's pdl_rekey_info
+// but for its time; `keys_rewritten` is the stream K-rekey will go over.
+struct SetCommit { bool key64_before; pdl_rekey_info ri; };
+static SetCommit commit_set_change(pdl_ctx *c, const RkChange &ch, uint64_t keys_rewritten) {
+    context_changes(c);
+    SetCommit sc{c->key64, pdl_rekey_info{}};
+    pdl_rekey_info &ri = sc.ri;
+    ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
+    if (ch.rekey) {
+        adopt_rank_table(c, ch.rp, ch.present);
+        ri.letters_after = ch.rp.base; ri.key_bits_after = ch.rp.rank_bits; ri.keys_rewritten = keys_rewritten; ri.rekeyed = 1;
+    }
+    return sc;
+}
+
+// Where the genome ids are on the device: c->d_gen is the context's own buffer (Own: an append grows it in place), an ingest
+// buffer of the context's, or a caller's — which may be gone: the host copy (h_genome_of) serves then.
+enum class GenomeIds { Callers, Ingest, Own };
+static GenomeIds genome_ids_on_device(const pdl_ctx *c) {
+    if (!c->d_gen) return GenomeIds::Callers;
+    return c->d_gen == c->own_gen.p ? GenomeIds::Own : c->d_gen == c->in_gen.p || c->d_gen == c->ing_gen.p ? GenomeIds::Ingest : GenomeIds::Callers;
+}
+
 // The tail behind the sort, for a set of N1 genes in G1 genomes (the layout of the host is the new one already) whose k-mers
 // are M1 sorted entries: control block and costs cleared for the new sizes, then — behind `queue_stream`, which queues
-// whatever still has to bring the stream into (keys_b, vals_b) — K-rle, the task layout, K-groups / K-ranges / K-cost.  The
-// device work is the caller's last span; the stream has been waited for on return, and low_memory has taken its buffers.
+// whatever still has to bring the stream into (keys_b, vals_b), K-rekey (rekey_in_place) included — K-rle, the task layout,
+// K-groups / K-ranges / K-cost.  The device work is the second stretch of c->set_spans; the stream has been waited for on return,
+// low_memory has taken its buffers and K-rekey's old keys are gone.  Closes the call's books: c->last_rekey is `ri` with its time;
+// c->tm starts from zero (the scoring fields start again) with the tail's fields and the total, the caller adds rank_ms and
+// sort_rank_ms from the stage events, which are unused here unless queue_stream used them.
 template <class QueueStream>
-static void rebuild_behind_sort(pdl_ctx *c, EventSpans<2> &spans, uint64_t M1, uint32_t N1, uint32_t G1, QueueStream &&queue_stream) {
+static void rebuild_behind_sort(pdl_ctx *c, pdl_rekey_info ri, uint64_t M1, uint32_t N1, uint32_t G1, QueueStream &&queue_stream) {
     hipStream_t st = c->stream;
+    EventSpans<2> &spans = c->set_spans;
     const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) G1;
     c->scalars.alloc(ctl_words * sizeof(uint64_t));
     c->cost.alloc((size_t) N1 * sizeof(uint64_t));
+    c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = c->ev[EV_REKEY].used = false;
     spans.begin();
     hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, c->scalars.as<uint64_t>(), ctl_words);
     hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>(((size_t) N1 + 255) / 256, 1024)), dim3(256), 0, st, c->cost.as<uint64_t>(), (size_t) N1);
     PDL_HIP(hipGetLastError());
     queue_stream();
-    if (c->key64) stage_dedup<uint64_t>(c, M1); else stage_dedup<uint32_t>(c, M1);
+    pdl_with_key(c->key64, [&](auto key) { stage_dedup<decltype(key)>(c, M1); });
     ev_end(c, EV_DICT);
     pdl_prepare_tasks(c);
     stage_ranges_and_costs(c, M1, 1, false);
     spans.end();
     PDL_HIP(hipStreamSynchronize(st));
     if (c->opt_low_memory) release_build_buffers(c);
+    c->rk.keys.release();
+    ri.rekey_ms = ev_ms(c, EV_REKEY);
+    c->last_rekey = ri;
+    pdl_timings t{};
+    t.dict_ms = ev_ms(c, EV_DICT); t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
+    t.preprocess_total_ms = spans.ms(0) + spans.ms(1);
+    c->tm = t;
 }
 
 // K-rank of genes that are not the context's input (a query, an append) with the context's rank parameters: gene values 0..n-1
@@ -951,20 +959,17 @@ static void rank_new_genes(pdl_ctx *c, const uint8_t *res, const uint64_t *off, 
     PDL_HIP(hipGetLastError());
 }
 
-template <class KeyT>
-static const void *query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
-                                    uint64_t n_res, KeyT *keys_in, KeyT *keys_out, uint32_t *vals_in, uint32_t *vals_out, uint32_t *recpos,
-                                    uint2 *post, uint64_t *d_u) {
-    rank_new_genes<KeyT>(c, res, off, kmer_off, n, m, n_res, keys_in, vals_in);
-    pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_in, vals_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
-    scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_out}, RecScatter<KeyT>{keys_out, vals_out, m, recpos, post}, d_u);
-    return keys_out;
-}
 const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u) {
-    if (c->key64) return query_dictionary<uint64_t>(c, res, off, kmer_off, n, m, n_res, (uint64_t *) keys_a, (uint64_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
-    return query_dictionary<uint32_t>(c, res, off, kmer_off, n, m, n_res, (uint32_t *) keys_a, (uint32_t *) keys_b, vals_a, vals_b, recpos, post, d_u);
+    return pdl_with_key(c->key64, [&](auto key) -> const void * {
+        using KeyT = decltype(key);
+        KeyT *keys_in = static_cast<KeyT *>(keys_a), *keys_out = static_cast<KeyT *>(keys_b);
+        rank_new_genes<KeyT>(c, res, off, kmer_off, n, m, n_res, keys_in, vals_a);
+        pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_a, vals_b, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+        scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_b}, RecScatter<KeyT>{keys_out, vals_b, m, recpos, post}, d_u);
+        return keys_out;
+    });
 }
 
 // K-rekey (pdl_rekey.h) of the first m keys of keys_b, `from_key64` wide, for the rank table c->rp / c->key64 hold ALREADY; the
@@ -977,24 +982,21 @@ static void rekey_in_place(pdl_ctx *c, uint64_t m, bool from_key64, const RkArgs
     rk.keys.alloc(m * kb);
     rk.table.alloc((size_t) a.entries * kb);
     ev_begin(c, EV_REKEY);
-    if (c->key64) {
-        PDL_HIP(hipMemcpyAsync(rk.table.p, rk.h_table.data(), (size_t) a.entries * 8, hipMemcpyHostToDevice, st));
-        if (from_key64) pdl_rekey_stream<uint64_t, uint64_t>(st, c->keys_b.as<uint64_t>(), rk.keys.as<uint64_t>(), m, a, rk.table.as<uint64_t>());
-        else pdl_rekey_stream<uint32_t, uint64_t>(st, c->keys_b.as<uint32_t>(), rk.keys.as<uint64_t>(), m, a, rk.table.as<uint64_t>());
-    } else {
-        rk.h_table32.assign(rk.h_table.begin(), rk.h_table.end());      // (B'^k <= 2^32: every entry fits)
-        PDL_HIP(hipMemcpyAsync(rk.table.p, rk.h_table32.data(), (size_t) a.entries * 4, hipMemcpyHostToDevice, st));
-        if (from_key64) pdl_rekey_stream<uint64_t, uint32_t>(st, c->keys_b.as<uint64_t>(), rk.keys.as<uint32_t>(), m, a, rk.table.as<uint32_t>());
-        else pdl_rekey_stream<uint32_t, uint32_t>(st, c->keys_b.as<uint32_t>(), rk.keys.as<uint32_t>(), m, a, rk.table.as<uint32_t>());
-    }
+    pdl_with_key(c->key64, [&](auto key_out) {
+        using KeyOut = decltype(key_out);
+        const void *h_table = rk.h_table.data();
+        if (sizeof(KeyOut) == 4) {                                          // (B'^k <= 2^32: every entry fits)
+            rk.h_table32.assign(rk.h_table.begin(), rk.h_table.end());
+            h_table = rk.h_table32.data();
+        }
+        PDL_HIP(hipMemcpyAsync(rk.table.p, h_table, (size_t) a.entries * sizeof(KeyOut), hipMemcpyHostToDevice, st));
+        pdl_with_key(from_key64, [&](auto key_in) {
+            using KeyIn = decltype(key_in);
+            pdl_rekey_stream<KeyIn, KeyOut>(st, c->keys_b.as<KeyIn>(), rk.keys.as<KeyOut>(), m, a, rk.table.as<KeyOut>());
+        });
+    });
     ev_end(c, EV_REKEY);
     c->keys_b.swap(rk.keys);
-}
-// the rank table changes: c->rp, the letters, the key width
-static void adopt_rank_table(pdl_ctx *c, const RankParams &rp, const uint8_t present[256]) {
-    c->rp = rp;
-    memcpy(c->alpha_present, present, 256);
-    c->key64 = rp.rank_bits > 32;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1047,7 +1049,7 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     const NewGenes genes(offsets, n, c->rp.k);
     const uint64_t m = genes.M;
     if (M0 + m >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu k-mers in the union need 64-bit stream positions", (unsigned long long) (M0 + m));
-    EventSpans<2> &spans = c->app_spans;
+    EventSpans<2> &spans = c->set_spans;
     spans.start(st);
 
     // A-alpha (and the new genes on their way to the device): the context is only read
@@ -1065,55 +1067,36 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         PDL_HIP(hipGetLastError());
     }
     spans.end();
-    bool rekey = false;
-    RankParams rp1{};
-    uint8_t present1[256];
-    RkArgs rka{};
+    RkChange ch;
     {
         PinRead rd(c);
         const uint64_t *pb = rd.add<uint64_t>(d_bad, rekey_on ? A_HIST + 256 : 1);
         rd.sync();
         if (pb[0] && !rekey_on) pdl_fail_absent_byte(pb[0], "appended");
         if (pb[0]) {                          // the union's rank table, as a build makes it; every refusal before anything changes
-            uint64_t counters[256];
-            for (int b = 0; b < 256; b++) { present1[b] = c->alpha_present[b] || pb[A_HIST + b]; counters[b] = present1[b]; }
-            rank_init_host(rp1, counters, (int) c->rp.k);
+            uint8_t present_union[256];
+            for (int b = 0; b < 256; b++) present_union[b] = c->alpha_present[b] || pb[A_HIST + b];
             if (!rk_exact(c->rp))
                 PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_append_genomes: appended byte 0x%02x is not in the base's alphabet, and the base's ranks (%u letters, "
                          "k = %u: %s) cannot be decoded into letters and written again (option alphabet_rekey); rebuild from the union",
                          256u - (uint32_t) pb[0], c->rp.base, c->rp.k, rk_why_not(c->rp));
-            if (!rk_exact(rp1))
+            if (!rk_change(c->rp, c->alpha_present, present_union, c->rk.h_table, ch))
                 PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_append_genomes: appended byte 0x%02x is not in the base's alphabet, and the union's ranks (%u letters, "
                          "k = %u) would be %s: the base's keys cannot be written again for them (option alphabet_rekey); rebuild from the union",
-                         256u - (uint32_t) pb[0], rp1.base, rp1.k, rk_why_not(rp1));
-            rka = rk_plan(c->rp, c->alpha_present, rp1, present1, c->rk.h_table);
-            rekey = true;
+                         256u - (uint32_t) pb[0], ch.rp.base, ch.rp.k, rk_why_not(ch.rp));
         }
     }
 
-    context_changes(c);
-    pdl_rekey_info ri{};
-    ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
-    const bool key64_0 = c->key64;
-    if (rekey) {
-        adopt_rank_table(c, rp1, present1);
-        ri.letters_after = rp1.base; ri.key_bits_after = rp1.rank_bits; ri.keys_rewritten = M0; ri.rekeyed = 1;
-    }
-    if (c->short_valid) {                     // the letters of the new genomes' genes shorter than k (a handful of residues: on the host)
-        c->h_short_letters.resize((size_t) (G0 + n_new_genomes) * 8, 0u);
-        for (uint32_t i = 0; i < n; i++)
-            if (offsets[i + 1] - offsets[i] < c->rp.k)
-                for (uint64_t r = offsets[i]; r < offsets[i + 1]; r++) c->h_short_letters[(size_t) genome_ids[i] * 8 + (residues[r] >> 5)] |= 1u << (residues[r] & 31);
-    }
+    const SetCommit sc = commit_set_change(c, ch, M0);
     const uint32_t N1 = N0 + n, G1 = G0 + n_new_genomes;
+    if (c->short_valid) short_letters_append(c->h_short_letters, G1, residues, offsets, genome_ids, n, c->rp.k);
     const uint64_t M1 = M0 + m;
     const size_t kb = c->key64 ? 8 : 4;
     // A-len: the per-gene arrays grow (k-mer counts keep their contents), the genome ids move into the context's own buffer
     c->kseq_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
     c->gene_len.grow_keep((size_t) N1 * sizeof(uint32_t), st);
-    const bool ids_on_device = c->d_gen && (c->d_gen == c->in_gen.p || c->d_gen == c->ing_gen.p);     // (a caller's buffer may be gone: the host copy serves)
-    const bool ids_owned = c->d_gen && c->d_gen == c->own_gen.p;
-    if (ids_owned) c->own_gen.grow_keep((size_t) N1 * sizeof(uint32_t), st); else c->own_gen.alloc((size_t) N1 * sizeof(uint32_t));
+    const GenomeIds ids = genome_ids_on_device(c);
+    if (ids == GenomeIds::Own) c->own_gen.grow_keep((size_t) N1 * sizeof(uint32_t), st); else c->own_gen.alloc((size_t) N1 * sizeof(uint32_t));
     const uint32_t *old_gen = c->d_gen;
     pdl_extend_layout(c, genome_ids, n);                  // N, G, h_genome_of, genome rows
     c->M = M1; c->R += Rq;
@@ -1123,38 +1106,26 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         q.keys_a.alloc(m * kb); q.keys_b.alloc(m * kb); q.vals_a.alloc(m * 4); q.vals_b.alloc(m * 4);
         c->scan_tmp.alloc(pdl_merge_split_words(M1) * sizeof(uint32_t));
     }
-    c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = c->ev[EV_REKEY].used = false;
-    rebuild_behind_sort(c, spans, M1, N1, G1, [&] {        // (behind the clearing, as ever: the new genes' tails of the per-gene arrays, A-dict, A-merge)
+    rebuild_behind_sort(c, sc.ri, M1, N1, G1, [&] {        // (behind the clearing, as ever: the new genes' tails of the per-gene arrays, A-dict, A-merge)
         PDL_HIP(hipMemcpyAsync(c->kseq_len.as<uint32_t>() + N0, q.kseq.p, n * 4ull, hipMemcpyDeviceToDevice, st));
         PDL_HIP(hipMemcpyAsync(c->gene_len.as<uint32_t>() + N0, genes.len.data(), n * 4ull, hipMemcpyHostToDevice, st));
-        if (ids_owned) {
+        if (ids == GenomeIds::Own) {
             PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
-        } else if (ids_on_device) {
+        } else if (ids == GenomeIds::Ingest) {
             PDL_HIP(hipMemcpyAsync(c->own_gen.p, old_gen, (size_t) N0 * 4, hipMemcpyDeviceToDevice, st));
             PDL_HIP(hipMemcpyAsync(c->own_gen.as<uint32_t>() + N0, c->h_genome_of.data() + N0, n * 4ull, hipMemcpyHostToDevice, st));
         } else {
             PDL_HIP(hipMemcpyAsync(c->own_gen.p, c->h_genome_of.data(), (size_t) N1 * 4, hipMemcpyHostToDevice, st));
         }
-        if (rekey) rekey_in_place(c, M0, key64_0, rka);
-        if (m) {
-            if (c->key64) append_sorted_stream<uint64_t>(c, n, m, Rq, N0, M0);
-            else append_sorted_stream<uint32_t>(c, n, m, Rq, N0, M0);
-        }
+        if (ch.rekey) rekey_in_place(c, M0, sc.key64_before, ch.args);
+        if (m) pdl_with_key(c->key64, [&](auto key) { append_sorted_stream<decltype(key)>(c, n, m, Rq, N0, M0); });
     });
-    c->rk.keys.release();
-    const float ms0 = spans.ms(0), ms1 = spans.ms(1);
     const float rank_ms = ev_ms(c, EV_RANK), sort_ms = ev_ms(c, EV_SORT1), merge_ms = ev_ms(c, EV_MERGE);
-    ri.rekey_ms = ev_ms(c, EV_REKEY);
-    c->last_rekey = ri;
-    pdl_timings t{};                          // the preprocess fields describe the append, the scoring fields start again
-    t.rank_ms = rank_ms; t.sort_rank_ms = sort_ms + merge_ms + ri.rekey_ms; t.dict_ms = ev_ms(c, EV_DICT);
-    t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
-    t.preprocess_total_ms = ms0 + ms1;
-    c->tm = t;
+    c->tm.rank_ms = rank_ms; c->tm.sort_rank_ms = sort_ms + merge_ms + c->last_rekey.rekey_ms;
     if (info) {
         info->residues = Rq; info->kmer_occurrences = m;
         info->records = c->U - U0;            // (a record belongs to one gene: the base's records are all still there)
-        info->rank_sort_ms = rank_ms + sort_ms; info->merge_ms = merge_ms; info->device_ms = ms0 + ms1;
+        info->rank_sort_ms = rank_ms + sort_ms; info->merge_ms = merge_ms; info->device_ms = c->tm.preprocess_total_ms;
     }
 }
 
@@ -1177,41 +1148,30 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
 // known — the digits seen plus the short genes' letters of the genomes that stay.  The context's: the removal goes through.
 // Smaller: the tail starts with K-rekey (pdl_rekey.h) of the compacted stream for the remaining set's RankParams.
 // ------------------------------------------------------------------------------------------------
-template <class KeyT>
-static void remove_from_stream(pdl_ctx *c, uint64_t m, const uint32_t *new_id, uint64_t *d_ctl) {
-    pdl_compact_stream<KeyT>(c->stream, c->keys_b.as<KeyT>(), c->vals_b.as<uint32_t>(), new_id, m, c->rm.tile.as<uint32_t>(), c->keys_a.as<KeyT>(),
-                             c->vals_a.as<uint32_t>(), rm_digits(c->rp.k, c->rp.base), reinterpret_cast<uint32_t *>(d_ctl + PDL_RM_SEEN), d_ctl + PDL_RM_KMERS);
-}
-
 void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_remove_info *info) {
     hipStream_t st = c->stream;
     auto &r = c->rm;
     const uint32_t N0 = c->N, G0 = c->G, G1 = G0 - count;
     const uint64_t M0 = c->M, U0 = c->U;
-    // a key decodes into letters when it is the polynomial itself: no hashing, and B^k fits 64 bits EXACTLY (key_bits == rank_bits
-    // does not say so: 20 letters at k = 15 wrap unnoticed to a 64-bit rank_bits)
-    bool exact = !c->rp.hash_fallback && c->rp.base != 0;
-    unsigned __int128 bk = 1;
-    for (uint32_t i = 0; i < c->rp.k && exact; i++) { bk *= c->rp.base; exact = (bk >> 64) == 0; }
-    if (!exact)
+    if (!rk_exact(c->rp))                     // a key decodes into letters when it is the polynomial itself
         PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: the ranks of this set (%u letters, k = %u: %s) cannot be decoded into letters, so the remaining "
-                 "set cannot be shown to have the same alphabet; rebuild from the remaining genes", c->rp.base, c->rp.k,
-                 c->rp.hash_fallback ? "hashed" : "wrapped past 2^64");
+                 "set cannot be shown to have the same alphabet; rebuild from the remaining genes", c->rp.base, c->rp.k, rk_why_not(c->rp));
     // genome ids of the remaining set: the order they have, closed up
     std::vector<uint32_t> gmap((size_t) G0, 0u);
     for (uint32_t i = 0; i < count; i++) gmap[genomes[i]] = RM_GONE;
     for (uint32_t g = 0, next = 0; g < G0; g++) if (gmap[g] != RM_GONE) gmap[g] = next++;
-    r.spans.start(st);
+    EventSpans<2> &spans = c->set_spans;
+    spans.start(st);
 
     // R-map, R-compact, R-alpha: the context is only read
-    r.spans.begin();
+    spans.begin();
     r.ctl.alloc(PDL_RM_WORDS * sizeof(uint64_t));
     uint64_t *d_ctl = r.ctl.as<uint64_t>();
     hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, st, d_ctl, (size_t) PDL_RM_WORDS);
     r.gmap.alloc((size_t) G0 * 4);
     PDL_HIP(hipMemcpyAsync(r.gmap.p, gmap.data(), (size_t) G0 * 4, hipMemcpyHostToDevice, st));
     const uint32_t *d_gen = c->d_gen;
-    if (!(d_gen && (d_gen == c->in_gen.p || d_gen == c->ing_gen.p || d_gen == c->own_gen.p))) {      // (a caller's buffer may be gone: the host copy serves)
+    if (genome_ids_on_device(c) == GenomeIds::Callers) {
         r.gen_in.alloc((size_t) N0 * 4);
         PDL_HIP(hipMemcpyAsync(r.gen_in.p, c->h_genome_of.data(), (size_t) N0 * 4, hipMemcpyHostToDevice, st));
         d_gen = r.gen_in.as<uint32_t>();
@@ -1224,19 +1184,20 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
                    RmMapApply{d_gen, r.gmap.as<uint32_t>(), c->kseq_len.as<uint32_t>(), c->gene_len.as<uint32_t>(), r.new_id.as<uint32_t>(), r.gen.as<uint32_t>(),
                               r.kseq.as<uint32_t>(), r.glen.as<uint32_t>(), reinterpret_cast<unsigned long long *>(d_ctl + PDL_RM_GONE_RESIDUES)},
                    d_ctl + PDL_RM_GENES);
-    if (c->key64) remove_from_stream<uint64_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
-    else remove_from_stream<uint32_t>(c, M0, r.new_id.as<uint32_t>(), d_ctl);
-    r.spans.end();
+    pdl_with_key(c->key64, [&](auto key) {
+        using KeyT = decltype(key);
+        pdl_compact_stream<KeyT>(st, c->keys_b.as<KeyT>(), c->vals_b.as<uint32_t>(), r.new_id.as<uint32_t>(), M0, r.tile.as<uint32_t>(), c->keys_a.as<KeyT>(),
+                                 c->vals_a.as<uint32_t>(), rm_digits(c->rp.k, c->rp.base), reinterpret_cast<uint32_t *>(d_ctl + PDL_RM_SEEN), d_ctl + PDL_RM_KMERS);
+    });
+    spans.end();
     // the host's side of it while the device works: the genome ids of the genes that stay
     std::vector<uint32_t> genome_of;
     genome_of.reserve(N0);
     for (uint32_t i = 0; i < N0; i++) if (gmap[c->h_genome_of[i]] != RM_GONE) genome_of.push_back(gmap[c->h_genome_of[i]]);
     const uint32_t N1 = (uint32_t) genome_of.size();
     uint64_t M1 = 0, gone_residues = 0;
-    bool digit_missing = false, rekey = false;
-    RankParams rp1{};
-    uint8_t present1[256];
-    RkArgs rka{};
+    bool digit_missing = false;
+    RkChange ch;
     {
         PinRead rd(c);
         const uint64_t *pc = rd.add<uint64_t>(d_ctl, PDL_RM_WORDS);
@@ -1263,60 +1224,29 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
                          "shorter than k=%u are not known: option alphabet_rekey was not set when the context was built (set it before pdl_preprocess); "
                          "rebuild from the remaining genes", c->rp.k);
             // the remaining alphabet, exactly: every residue lies in a k-mer or in a gene shorter than k
-            uint32_t bits[8] = {};
-            for (uint32_t g = 0; g < G0; g++)
-                if (gmap[g] != RM_GONE) for (int w = 0; w < 8; w++) bits[w] |= c->h_short_letters[(size_t) g * 8 + w];
-            bool same = true;
-            for (int b = 0; b < 256; b++) {
-                present1[b] = c->alpha_present[b] && (seen[c->rp.rank_values[b]] || (bits[b >> 5] >> (b & 31) & 1u));
-                same = same && present1[b] == c->alpha_present[b];
-            }
-            if (!same) {
-                uint64_t counters[256];
-                for (int b = 0; b < 256; b++) counters[b] = present1[b];
-                rank_init_host(rp1, counters, (int) c->rp.k);
-                if (!rk_exact(rp1))           // (cannot happen: fewer letters than an exact table has)
-                    PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: the remaining set's ranks (%u letters, k = %u) would be %s", rp1.base, rp1.k, rk_why_not(rp1));
-                rka = rk_plan(c->rp, c->alpha_present, rp1, present1, c->rk.h_table);
-                rekey = true;
-            }
+            uint8_t in_short[256], present_left[256];
+            short_letters_staying(c->h_short_letters, gmap, in_short);
+            for (int b = 0; b < 256; b++) present_left[b] = c->alpha_present[b] && (seen[c->rp.rank_values[b]] || in_short[b]);
+            if (!rk_change(c->rp, c->alpha_present, present_left, c->rk.h_table, ch))      // (cannot happen: fewer letters than an exact table has)
+                PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_remove_genomes: the remaining set's ranks (%u letters, k = %u) would be %s", ch.rp.base, ch.rp.k, rk_why_not(ch.rp));
         }
     }
 
-    context_changes(c);
-    pdl_rekey_info ri{};
-    ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
-    const bool key64_0 = c->key64;
-    if (rekey) {
-        adopt_rank_table(c, rp1, present1);
-        ri.letters_after = rp1.base; ri.key_bits_after = rp1.rank_bits; ri.keys_rewritten = M1; ri.rekeyed = 1;
-    }
-    if (c->short_valid) {                     // the table closes up like the genome ids
-        for (uint32_t g = 0; g < G0; g++)
-            if (gmap[g] != RM_GONE && gmap[g] != g) memcpy(&c->h_short_letters[(size_t) gmap[g] * 8], &c->h_short_letters[(size_t) g * 8], 32);
-        c->h_short_letters.resize((size_t) G1 * 8);
-    }
+    const SetCommit sc = commit_set_change(c, ch, M1);
+    if (c->short_valid) short_letters_remove(c->h_short_letters, gmap, G1);
     c->keys_a.swap(c->keys_b); c->vals_a.swap(c->vals_b);      // the sorted stream is what keys_b / vals_b name
     c->kseq_len.swap(r.kseq); c->gene_len.swap(r.glen);
     c->own_gen.swap(r.gen);                                     // the context owns the ids from here on, as after an append
     pdl_replace_layout(c, std::move(genome_of));          // N, G, h_genome_of, genome rows
     c->M = M1; c->R -= gone_residues;
     c->d_gen = c->own_gen.as<uint32_t>(); c->d_res = nullptr; c->d_off = nullptr;          // (nothing behind K-rank reads residues or offsets)
-    c->ev[EV_HIST].used = c->ev[EV_RANK].used = c->ev[EV_SORT1].used = c->ev[EV_MERGE].used = c->ev[EV_REKEY].used = false;
-    rebuild_behind_sort(c, r.spans, M1, N1, G1, [&] { if (rekey) rekey_in_place(c, M1, key64_0, rka); });      // (the compacted stream is in place)
-    c->rk.keys.release();
-    const float ms0 = r.spans.ms(0), ms1 = r.spans.ms(1);
-    ri.rekey_ms = ev_ms(c, EV_REKEY);
-    c->last_rekey = ri;
-    pdl_timings t{};                          // the preprocess fields describe the removal, the scoring fields start again
-    t.sort_rank_ms = ms0 + ri.rekey_ms; t.dict_ms = ev_ms(c, EV_DICT);
-    t.sort_seq_ms = ev_ms(c, EV_SORT2); t.ranges_ms = ev_ms(c, EV_RANGES);
-    t.preprocess_total_ms = ms0 + ms1;
-    c->tm = t;
+    rebuild_behind_sort(c, sc.ri, M1, N1, G1, [&] { if (ch.rekey) rekey_in_place(c, M1, sc.key64_before, ch.args); });      // (the compacted stream is in place)
+    const float ms0 = spans.ms(0);
+    c->tm.sort_rank_ms = ms0 + c->last_rekey.rekey_ms;
     if (info) {
         info->sequences = N0 - N1; info->residues = gone_residues; info->kmer_occurrences = M0 - M1;
         info->records = U0 - c->U;            // (a record belongs to one gene: the records of the genes that stay are all still there)
-        info->compact_ms = ms0; info->device_ms = ms0 + ms1;
+        info->compact_ms = ms0; info->device_ms = c->tm.preprocess_total_ms;
     }
 }
 
@@ -1326,13 +1256,11 @@ void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity) {
     c->dist = false; c->dist_stage = 0; c->post_ext = nullptr; c->dist_sender = false;
     c->short_valid = false;
     stage_alphabet_and_lengths(c, kvalue, only_complexity);
-    if (c->key64) dictionary_pipeline<uint64_t>(c, only_complexity);
-    else dictionary_pipeline<uint32_t>(c, only_complexity);
+    pdl_with_key(c->key64, [&](auto key) { dictionary_pipeline<decltype(key)>(c, only_complexity); });
     ev_end(c, EV_PRE_TOTAL);
     PDL_HIP(hipStreamSynchronize(st));
     if (c->opt_alphabet_rekey) {                    // the table is the context's own from here on, on the host: a few words a genome
-        c->h_short_letters.assign((size_t) c->G * 8, 0u);
-        PDL_HIP(hipMemcpy(c->h_short_letters.data(), c->rk.short_letters.p, (size_t) c->G * 32, hipMemcpyDeviceToHost));
+        short_letters_fetch(c->h_short_letters, c->rk.short_letters.p, c->G);
         c->short_valid = true;
     }
     c->tm.hist_ms = ev_ms(c, EV_HIST);
@@ -1428,7 +1356,7 @@ void pdl_run_dist_begin(pdl_ctx *c, int kvalue) {
     ev_begin(c, EV_DIST_BEGIN);
     c->dist = true; c->dist_stage = 0; c->post_ext = nullptr;
     stage_alphabet_and_lengths(c, kvalue, false);
-    if (c->key64) dist_slice_pipeline<uint64_t>(c); else dist_slice_pipeline<uint32_t>(c);
+    pdl_with_key(c->key64, [&](auto key) { dist_slice_pipeline<decltype(key)>(c); });
     ev_end(c, EV_DIST_BEGIN);
     c->h_run_weights.assign(c->G, 0);
     c->h_run_costs.assign(c->G, 0);

@@ -632,15 +632,12 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
         PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
         QMatchOut mo{q.desc.as<QDesc>(), q.gkey.as<uint32_t>(), q.row_lookups.as<uint32_t>(), ctl};
         const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
-        if (c->key64) {
-            const QView<uint64_t> v = q_view<uint64_t>(c, qkeys);
-            hipLaunchKernelGGL(k_q_fold<uint64_t>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
-            hipLaunchKernelGGL(k_q_match<uint64_t>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
-        } else {
-            const QView<uint32_t> v = q_view<uint32_t>(c, qkeys);
-            hipLaunchKernelGGL(k_q_fold<uint32_t>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
-            hipLaunchKernelGGL(k_q_match<uint32_t>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
-        }
+        pdl_with_key(c->key64, [&](auto key_tag) {
+            using KeyT = decltype(key_tag);
+            const QView<KeyT> v = q_view<KeyT>(c, qkeys);
+            hipLaunchKernelGGL(k_q_fold<KeyT>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
+            hipLaunchKernelGGL(k_q_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
+        });
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the record indices by gene (the records are in (rank, gene) order)
         uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;

@@ -311,7 +311,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         PDL_HIP(hipGetLastError());
         pdl_sort_pairs<uint32_t, uint32_t>(c, qk_in, qk_out, pm_in, pm_out, Mq, std::max<uint32_t>(1, bit_length64(nq)), true, d_u, 0, true);
         QBMatchOut mo{w.desc.as<QDesc>(), w.gkey.as<uint32_t>(), w.row_lookups.as<uint32_t>(), ctl};
-        auto run = [&](auto key_tag) {
+        pdl_with_key(c->key64, [&](auto key_tag) {
             using KeyT = decltype(key_tag);
             QBView<KeyT> v = qb_view<KeyT>(c);
             v.qid_sorted = qk_out;
@@ -320,8 +320,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
                                w.srank.as<KeyT>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
             hipLaunchKernelGGL(k_qb_fold<KeyT>, dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
             hipLaunchKernelGGL(k_qb_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
-        };
-        if (c->key64) run(uint64_t{}); else run(uint32_t{});
+        });
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the segment positions by chunk gene
         uint32_t *gk_in = w.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;

@@ -17,9 +17,15 @@
 //
 // A thread takes four consecutive keys (16-byte loads and stores; the streams start at allocations), its four digit chains
 // side by side; the m % 4 keys of the tail go one to a thread of the first workgroup.
+//
+// The host section is what an append and a removal share before the context changes (tools/rekey_host_check.cpp runs it without a
+// device): rank_init_host (the build's too), rk_exact, rk_plan, rk_change — the one decision: the same letters, a re-key, or a
+// target that is not exact — and the short_letters_* functions that keep pdl_ctx::h_short_letters.
 #pragma once
 #include "pdl_common.h"
 #include "pdl_remove.h"
+
+#include <cstring>
 
 constexpr int RK_THREADS = 256, RK_ITEMS = 4;
 
@@ -33,13 +39,44 @@ struct RkArgs {
 };
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// ranks are the polynomial itself: no hashing, and B^k fits 64 bits EXACTLY (key_bits == rank_bits does not say so, see pdl_run_remove)
-inline bool rk_exact(const RankParams &rp) {
-    bool exact = !rp.hash_fallback && rp.base != 0;
-    unsigned __int128 bk = 1;
-    for (uint32_t i = 0; i < rp.k && exact; i++) { bk *= rp.base; exact = (bk >> 64) == 0; }
-    return exact;
+// The rank table of an alphabet: library.cpp:88-132, literally (64-bit wraparound included); adds rank_bits for the device sort and
+// key_bits.  The build (stage_alphabet_and_lengths, pdl_dict.hip) and rk_change below make every table of a context through it.
+inline void rank_init_host(RankParams &rp, const uint64_t counters[256], int kvalue) {
+    memset(&rp, 0, sizeof(rp));
+    rp.k = (uint32_t) kvalue;
+    int rank = 0;
+    for (int i = 0; i < 256; i++)
+        if (counters[i] > 0) rp.rank_values[i] = (uint8_t) rank++;
+    const uint8_t rank_base = (uint8_t) rank;
+    rp.base = rank_base;
+    uint64_t last_multiplier = 1;
+    bool has_overflow = false;
+    int tmp_kvalue = kvalue - 1;
+    while (tmp_kvalue--) {
+        uint64_t ovflw_test = last_multiplier;
+        last_multiplier *= rank_base;
+        if (has_overflow) {
+            last_multiplier %= RABIN_MODULO;
+        } else if ((ovflw_test > last_multiplier) || (ovflw_test * rank_base > last_multiplier * rank_base)) {
+            has_overflow = true;
+            last_multiplier = ((ovflw_test % RABIN_MODULO) * rank_base) % RABIN_MODULO;
+        }
+    }
+    rp.last_multiplier = last_multiplier;
+    rp.hash_fallback = has_overflow ? 1u : 0u;
+    rp.key_bits = 64;
+    if (has_overflow) {
+        rp.rank_bits = 64;
+    } else {
+        uint64_t rank_tmp = last_multiplier * rank_base;   // B^k, fits (the loop above looked one step ahead)
+        rp.rank_bits = rank_tmp ? bit_length64(rank_tmp - 1) : 1;
+        if (rp.rank_bits == 0) rp.rank_bits = 1;
+        if (pow_fits_u64(rank_base, (uint32_t) kvalue)) rp.key_bits = rp.rank_bits;      // did B^k fit?
+    }
 }
+
+// ranks are the polynomial itself, so a key decodes into letters: no hashing, and B^k fits 64 bits EXACTLY (pow_fits_u64)
+inline bool rk_exact(const RankParams &rp) { return !rp.hash_fallback && rp.base != 0 && pow_fits_u64(rp.base, rp.k); }
 inline const char *rk_why_not(const RankParams &rp) { return rp.hash_fallback ? "hashed" : "wrapped past 2^64"; }
 
 // The plan of a re-key from (from, present_from) to (to, present_to), both exact, same k: the kernel's arguments and the table
@@ -63,6 +100,53 @@ inline RkArgs rk_plan(const RankParams &from, const uint8_t present_from[256], c
         pw *= to.base;          // (B'^k fits: the last product is not used beyond it)
     }
     return a;
+}
+
+// What a call that changes the set decides about the alphabet before the context changes: the letters afterwards, their rank
+// table as a build makes it and, when the letters differ (rekey), the plan that writes the stream's keys again.
+struct RkChange { bool rekey = false; RankParams rp{}; uint8_t present[256] = {}; RkArgs args{}; };
+// (from, present_from), exact, becomes the alphabet present_to: equal letters leave ch.rekey false; else ch.rp is
+// rank_init_host of them and, when it is exact too, ch.args / table the plan.  false: the target is not exact (ch.rp says why,
+// rk_why_not) and nothing can be re-keyed — the refusal and its words are the caller's.
+inline bool rk_change(const RankParams &from, const uint8_t present_from[256], const uint8_t present_to[256], std::vector<uint64_t> &table,
+                      RkChange &ch) {
+    ch = RkChange{};
+    uint64_t counters[256];
+    bool same = true;
+    for (int b = 0; b < 256; b++) { counters[b] = ch.present[b] = present_to[b] ? 1 : 0; same = same && ch.present[b] == (present_from[b] ? 1 : 0); }
+    if (same) { ch.rp = from; return true; }
+    rank_init_host(ch.rp, counters, (int) from.k);
+    if (!rk_exact(ch.rp)) return false;
+    ch.args = rk_plan(from, present_from, ch.rp, ch.present, table);
+    return ch.rekey = true;
+}
+
+// ---- the letters of genes shorter than k, per genome (256 bits each, pdl_ctx::h_short_letters): they show in no key, and a removal
+// must know them.  Filled behind a build (k_short_letters below), then kept up on the host by every append and removal.
+// behind a build: the device's table becomes the context's own, a few words a genome (the stream has been waited for)
+inline void short_letters_fetch(std::vector<uint32_t> &h, const void *d_letters, uint32_t n_genomes) {
+    h.assign((size_t) n_genomes * 8, 0u);
+    PDL_HIP(hipMemcpy(h.data(), d_letters, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+}
+// an append: the letters of the new genomes' genes shorter than k (a handful of residues: on the host); n_genomes counts the new ones in
+inline void short_letters_append(std::vector<uint32_t> &h, uint32_t n_genomes, const uint8_t *residues, const uint64_t *offsets,
+                                 const uint32_t *genome_ids, uint32_t n, uint32_t k) {
+    h.resize((size_t) n_genomes * 8, 0u);
+    for (uint32_t i = 0; i < n; i++)
+        if (offsets[i + 1] - offsets[i] < k)
+            for (uint64_t r = offsets[i]; r < offsets[i + 1]; r++) h[(size_t) genome_ids[i] * 8 + (residues[r] >> 5)] |= 1u << (residues[r] & 31);
+}
+// a removal, before it decides: is[b] = a gene shorter than k of a genome that stays (gmap[g] != RM_GONE) holds the byte b
+inline void short_letters_staying(const std::vector<uint32_t> &h, const std::vector<uint32_t> &gmap, uint8_t is[256]) {
+    uint32_t bits[8] = {};
+    for (size_t g = 0; g < gmap.size(); g++) for (size_t w = 0; w < 8 && gmap[g] != RM_GONE; w++) bits[w] |= h[g * 8 + w];
+    for (int b = 0; b < 256; b++) is[b] = (uint8_t) (bits[b >> 5] >> (b & 31) & 1u);
+}
+// a removal, once it goes through: the table closes up like the genome ids (gmap ascends over the genomes that stay)
+inline void short_letters_remove(std::vector<uint32_t> &h, const std::vector<uint32_t> &gmap, uint32_t n_genomes_left) {
+    for (size_t g = 0; g < gmap.size(); g++)
+        if (gmap[g] != RM_GONE && gmap[g] != g) memcpy(&h[(size_t) gmap[g] * 8], &h[g * 8], 32);
+    h.resize((size_t) n_genomes_left * 8);
 }
 
 #ifdef __HIPCC__

@@ -78,7 +78,11 @@ def _append_vs_union(base, query, k, label, rekeyed=True, options=ON):
     _assert_oracle(nat, res, off, gen, k, label)
     _assert_dictionary_is_the_oracles(nat, res, off, gen, k, label)
     _check_info(nat, rekeyed, before, (len(np.unique(res)), uni.cost.rank_bits), m0, label)
-    assert nat.timings()["preprocess_total_ms"] == nat.last_append_info["device_ms"], label
+    tm, info, ri = nat.timings(), nat.last_append_info, nat.last_rekey_info
+    assert tm["preprocess_total_ms"] == info["device_ms"], label
+    # the re-key's time is part of the sort's share: rank + (sort + merge + re-key) = what the infos report; K-hist is the build's alone
+    assert abs(tm["sort_rank_ms"] + tm["rank_ms"] - info["rank_sort_ms"] - info["merge_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
+    assert tm["hist_ms"] == 0, (label, tm)
     uni.close()
     return nat
 
@@ -93,7 +97,11 @@ def _remove_vs_rebuild(res, off, gen, k, removed, label, rekeyed=True, options=O
     _assert_oracle(nat, *rest, k, label)
     _assert_dictionary_is_the_oracles(nat, *rest, k, label)
     _check_info(nat, rekeyed, before, (len(np.unique(rest[0])), reb.cost.rank_bits), reb.cost.kmer_occurrences, label)
-    assert nat.timings()["preprocess_total_ms"] == nat.last_remove_info["device_ms"], label
+    tm, info, ri = nat.timings(), nat.last_remove_info, nat.last_rekey_info
+    assert tm["preprocess_total_ms"] == info["device_ms"], label
+    # the compaction and the re-key are the removal's "sort"; nothing is ranked or counted
+    assert abs(tm["sort_rank_ms"] - info["compact_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
+    assert tm["hist_ms"] == 0 and tm["rank_ms"] == 0, (label, tm)
     reb.close()
     return nat
 

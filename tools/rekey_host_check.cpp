@@ -1,11 +1,14 @@
-// rekey_host_check.cpp — the host side of K-rekey (pdl_rekey.h: rk_exact, rk_plan — digit map, table, the two reciprocals) run
-// through every key it is easy to get wrong, as a program of its own so that it can be built with the host sanitizers:
+// rekey_host_check.cpp — the host side of K-rekey (pdl_rekey.h: rank_init_host, rk_exact, rk_change and its rk_plan — digit map,
+// table, the two reciprocals) run through every key it is easy to get wrong, as a program of its own so that it can be built with
+// the host sanitizers:
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tools/rekey_host_check.cpp -o rekey_host_check && ./rekey_host_check
 //
 // No device is touched: the kernel's arithmetic (rk_items) is repeated here in 128-bit host integers and checked against plain
-// division, for alphabets of 1 .. 256 letters at the largest exact k and a few below, growing and shrinking.
+// division, for alphabets of 1 .. 256 letters at the largest exact k and a few below, growing and shrinking.  The decision is the
+// library's own (rk_change, with the rank tables rank_init_host makes, as an append and a removal call it): a letter more or less
+// re-keys, the same letters do not, and the first k at which B^k leaves 64 bits is refused by it and by rk_exact alike.
 #include "../pandelos_amd/csrc/pdl_rekey.h"
 
 #include <cinttypes>
@@ -14,13 +17,28 @@
 
 static uint64_t mulhi(uint64_t a, uint64_t b) { return (uint64_t) (((unsigned __int128) a * b) >> 64); }
 
-// RankParams of the alphabet `present` as rank_init makes the fields the plan reads (dense digits in byte order, B, k)
+// RankParams of the alphabet `present` as a build makes them
 static RankParams params_of(const uint8_t present[256], uint32_t k) {
-    RankParams rp{};
-    uint32_t r = 0;
-    for (int b = 0; b < 256; b++) if (present[b]) rp.rank_values[b] = (uint8_t) r++;
-    rp.base = r; rp.k = k;
+    RankParams rp;
+    uint64_t counters[256];
+    for (int b = 0; b < 256; b++) counters[b] = present[b];
+    rank_init_host(rp, counters, (int) k);
     return rp;
+}
+static bool same_params(const RankParams &a, const RankParams &b) {
+    return !memcmp(a.rank_values, b.rank_values, 256) && a.last_multiplier == b.last_multiplier && a.base == b.base && a.k == b.k &&
+           a.rank_bits == b.rank_bits && a.hash_fallback == b.hash_fallback && a.key_bits == b.key_bits;
+}
+// `letters` letters at k: rk_exact and rk_change (from one letter fewer, when that is exact) both say "not exact"
+static bool refused(uint32_t letters, uint32_t k) {
+    uint8_t to[256] = {}, from[256] = {};
+    for (uint32_t i = 0; i < letters; i++) to[i] = 1;
+    memcpy(from, to, 256); from[letters - 1] = 0;
+    if (rk_exact(params_of(to, k))) return false;
+    const RankParams rf = params_of(from, k);
+    std::vector<uint64_t> table;
+    RkChange ch;
+    return !rk_exact(rf) || (!rk_change(rf, from, to, table, ch) && !ch.rekey && same_params(ch.rp, params_of(to, k)));
 }
 
 // rk_items for one key on the host; *ok goes false when a quotient or digit is not what plain division gives
@@ -61,6 +79,7 @@ int main() {
     std::mt19937_64 rng(12345);
     uint64_t checked = 0;
     int failures = 0;
+    if (!refused(20, 15) || !refused(24, 14) || !refused(2, 64)) { printf("20 letters at k = 15, 24 at k = 14 or 2 at k = 64: not refused\n"); failures++; }
     for (uint32_t B = 1; B <= 255 && !failures; B++) {
         // `small`: B letters spread over the bytes; `big`: the same and one more, below, between or above them
         uint8_t small[256] = {}, big[256] = {};
@@ -70,12 +89,32 @@ int main() {
         memcpy(big, small, 256); big[extra] = 1;
         uint32_t kmax = 0;
         { unsigned __int128 p = 1; while (kmax < 64 && ((p * (B + 1)) >> 64) == 0) { p *= (B + 1); kmax++; } }
+        {   // the first k at which `big` to the k-th leaves 64 bits: the decision and rk_exact refuse it alike
+            uint32_t nb = 0, kout = 1;
+            for (int b = 0; b < 256; b++) nb += big[b];
+            { unsigned __int128 p = nb; while ((p >> 64) == 0) { p *= nb; kout++; } }
+            const RankParams rs = params_of(small, kout), rb = params_of(big, kout);
+            std::vector<uint64_t> none;
+            RkChange ch;
+            if (rk_exact(rb) || (rk_exact(rs) && (rk_change(rs, small, big, none, ch) || ch.rekey || !same_params(ch.rp, rb)))) {
+                printf("B=%u k=%u: %u letters taken for exact\n", B, kout, nb); failures++; break;
+            }
+        }
         for (uint32_t k : {kmax, kmax > 1 ? kmax - 1 : 1u, (kmax + 1) / 2, 1u}) {
             if (k == 0) continue;
             const RankParams rs = params_of(small, k), rb = params_of(big, k);
             if (!rk_exact(rs) || !rk_exact(rb)) { printf("B=%u k=%u: not exact\n", B, k); failures++; break; }
-            std::vector<uint64_t> up, down;
-            const RkArgs au = rk_plan(rs, small, rb, big, up), ad = rk_plan(rb, big, rs, small, down);
+            std::vector<uint64_t> up, down, none;
+            RkChange cu, cd, ce;
+            // a letter more, a letter fewer: a re-key each way, for the table a build of the other set makes; the same letters: none
+            if (!rk_change(rs, small, big, up, cu) || !cu.rekey || !same_params(cu.rp, rb) || memcmp(cu.present, big, 256) ||
+                !rk_change(rb, big, small, down, cd) || !cd.rekey || !same_params(cd.rp, rs) || memcmp(cd.present, small, 256)) {
+                printf("B=%u k=%u: no re-key between %u and %u letters\n", B, k, B, B + 1); failures++; break;
+            }
+            if (!rk_change(rb, big, big, none, ce) || ce.rekey || !same_params(ce.rp, rb) || !none.empty()) {
+                printf("B=%u k=%u: a re-key for the same %u letters\n", B, k, B + 1); failures++; break;
+            }
+            const RkArgs &au = cu.args, &ad = cd.args;
             unsigned __int128 top_s = 1, top_b = 1;
             for (uint32_t i = 0; i < k; i++) { top_s *= B; top_b *= B + 1; }
             const bool s64 = top_s > ((unsigned __int128) 1 << 32), b64 = top_b > ((unsigned __int128) 1 << 32);
