@@ -449,8 +449,7 @@ struct pdl_ctx {
     DevBuf scratch2;      // small transient device scratch (interval histogram, per-genome lookups)
     DevBuf task_off;      // u32 [shard+1] task offsets | gathered cell offsets + the counters behind them (PDL_JT_*)
     int cus = 0;
-    uint32_t occ_tier1[5] = {0, 0, 0, 0, 0};
-    uint32_t occ_tier0[2] = {0, 0}, occ_tier0b[2] = {0, 0};      // [bitmap form, counter form]
+    uint32_t join_occ[16] = {};   // workgroups per CU of the join's kernels, by entry of pdl_join.hip's tier table (0: not asked yet)
 
     // K-bbh (pdl_bbh.hip): network edges of every genome task, on the host after the first pdl_compute_edges
     bool edges_valid = false;

@@ -88,7 +88,7 @@ struct JoinArgs {
 };
 
 // smallest integer n with (float) n / denom >= threshold (the quotient is monotone in n; n < 2^24 is exact in float)
-__device__ __forceinline__ uint32_t min_numerator(float threshold, float denom) {
+__host__ __device__ __forceinline__ uint32_t min_numerator(float threshold, float denom) {
     uint32_t n = (uint32_t) (threshold * denom);
     n = n > 2 ? n - 2 : 0;
     while ((float) (int) n / denom < threshold) n++;
@@ -1400,19 +1400,51 @@ void pdl_prepare_tasks(pdl_ctx *c) {
 __global__ void k_iota_u32(uint32_t *dst, uint32_t n) { uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) dst[i] = i; }
 
 // ------------------------------------------------------------------------------------------------
-// The scoring pass on the host: plan (sizes, tiers), join (three tiers queued back to back), then the
+// The scoring pass on the host: plan (sizes, tiers), join (the tiers queued back to back), then the
 // emission-order pass.  Single GPU: join + order, the host looks at the counters once, at the end; a staging area
 // that turns out too small repeats the pass once with the size asked for (rows that did not fit hold no cell, so
 // everything queued behind an overflowing join stays inside its buffers).  Multi-GPU: join + outbox listing
 // (pdl_dist_score_begin), the caller's all-to-all, inbox filing + order (pdl_dist_score_finish).
 // ------------------------------------------------------------------------------------------------
+
+// The tier table: every instance of the join kernels the host launches, by tier and form, with its workgroup size.  The
+// occupancy query and the launch both go through an entry; pdl_ctx::join_occ caches the occupancy by entry.
+//   0  k_join_part            short rows, several per workgroup cycle (0B: 512 threads, for the rows that alone exceed that cycle)
+//   1  k_join_lds<FILTER>     small table + "seen twice" bitmap, several rows resident per CU
+//   2  k_join_lds<13,1024>    128-KiB table holding every column a row touches, one row per CU
+//   3  k_join_hbm             direct-addressed tables in HBM
+enum JoinTier { TIER0, TIER0B, TIER1, TIER2, TIER3 };
+struct JoinKernel { JoinTier tier; int form; void (*fn)(JoinArgs); uint32_t threads; };
+static const JoinKernel JOIN_KERNELS[] = {
+    {TIER0, 0, k_join_part<PT_T, PT_WG_PER_CU, false>, PT_T}, {TIER0, 1, k_join_part<PT_T, PT_WG_PER_CU, true>, PT_T},       // form: the sift has counters
+    {TIER0B, 0, k_join_part<PT_T2, PT_WGS2, false>, PT_T2},   {TIER0B, 1, k_join_part<PT_T2, PT_WGS2, true>, PT_T2},
+    {TIER1, 9, k_join_lds<9, 128, true>, 128}, {TIER1, 10, k_join_lds<10, 256, true>, 256}, {TIER1, 11, k_join_lds<11, 256, true>, 256},      // form: "join_tier1"
+    {TIER1, 20, k_join_lds<10, 256, false>, 256}, {TIER1, 21, k_join_lds<11, 256, false>, 256},
+    {TIER2, 0, k_join_lds<13, 1024, false>, 1024}, {TIER2, 1, k_join_lds<9, 64, false>, 64},                                  // form: "join_tiny_tier2"
+    {TIER3, 0, k_join_hbm<false>, HBM_THREADS},    {TIER3, 1, k_join_hbm<true>, HBM_THREADS},                                 // form: 32-bit counters
+};
+static int join_kernel(JoinTier tier, int form) {
+    for (int i = 0; i < (int) (sizeof(JOIN_KERNELS) / sizeof(JoinKernel)); i++) if (JOIN_KERNELS[i].tier == tier && JOIN_KERNELS[i].form == form) return i;
+    PDL_FAIL(PDL_ERR_STATE, "join: no kernel for tier %d in form %d", (int) tier, form);
+}
+static uint32_t join_occupancy(pdl_ctx *c, int kernel) {
+    static_assert(sizeof(JOIN_KERNELS) / sizeof(JoinKernel) <= sizeof(pdl_ctx::join_occ) / sizeof(uint32_t), "pdl_ctx::join_occ holds every entry");
+    int nb = (int) c->join_occ[kernel];
+    if (nb == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *) JOIN_KERNELS[kernel].fn, (int) JOIN_KERNELS[kernel].threads, 0) != hipSuccess || nb < 1)) nb = 1;
+    return c->join_occ[kernel] = (uint32_t) nb;
+}
+
+// tier 3's tables in glb_table: the sums of every workgroup (u64 [N]; with 32-bit counters u32 [3][N] in twice the bytes), and
+// behind the sums of ALL workgroups their first / touched / emit lists (u32 [N] each)
+struct HbmLayout { size_t sums, lists; size_t per_wg() const { return sums + lists; } };      // bytes per workgroup
+static HbmLayout hbm_layout(uint32_t N, bool wide) { return {(size_t) N * (wide ? 2 : 1) * sizeof(uint64_t), (size_t) N * 3 * sizeof(uint32_t)}; }
+
 struct ScorePlan {
     bool wide, mirror;
     bool tier0;                    // the partition tier runs in front of tier 1 (short rows)
-    bool tier0_cnt;                // ... sifting with counters against the set's threshold (false: with bitmaps, "seen twice")
+    int tier1;                     // "join_tier1": the tier-1 table (0: no tier 1)
+    int k0, k0b, k1, k2, k3;       // the tiers' entries of the table (k0, k0b: with tier0; k1: with tier1)
     uint32_t grid0, grid0b;        // (the second form of the partition tier: 512 threads, the rows that alone exceed the first form's cycle)
-    int tier1, occ_slot;
-    bool tiny_tier2;
     uint32_t grid1, grid2, grid3;
     unsigned long long slack;
     bool wide_aside;               // put-aside entries carry row and launch in full (16 bytes): gene ids beyond 22 bits, or the repeat of a pass
@@ -1433,29 +1465,14 @@ static ScorePlan score_plan(pdl_ctx *c) {
     if (pl.mirror && !c->dist && (c->shard_set && S != G))
         PDL_FAIL(PDL_ERR_STATE, "the dictionary was built for all genomes (upper-triangle ranges); a genome shard must be set before pdl_preprocess");
     const int cus = pdl_cus(c);
-    // ---- tiers ---------------------------------------------------------------------------------------
-    //   1  k_join_lds<FILTER>     small table + "seen twice" bitmap, several rows resident per CU
-    //   2  k_join_lds<13,1024>    128-KiB table holding every column a row touches, one row per CU
-    //   3  k_join_hbm             direct-addressed tables in HBM
+    // ---- tiers (the table above) ------------------------------------------------------------------------
     // A tier hands the rows it cannot hold to the next one through a device-side list.  pdl_set_option "join_tier1"
     // picks the tier-1 table (0: skip tier 1; 20 / 21: 1024 / 2048-slot tables WITHOUT the filter, one pass);
     // "join_tiny_tier2" swaps tier 2 for a tiny table so that tests can reach tier 3 with small inputs.
     pl.tier1 = c->opt_tier1 >= 0 ? c->opt_tier1 : (G <= 320 ? 10 : 11);    // keys per row ~ homologs (about one per genome) + repeated/colliding noise
-    pl.tiny_tier2 = c->opt_tiny_tier2;
-    auto occupancy = [&](const void *fn, int threads) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, 0) != hipSuccess || nb < 1) nb = 1;
-        return (uint32_t) nb;
-    };
     const int tier1 = pl.tier1;
-    const void *fn1 = tier1 == 9 ? (const void *) k_join_lds<9, 128, true>
-                    : tier1 == 10 ? (const void *) k_join_lds<10, 256, true>
-                    : tier1 == 11 ? (const void *) k_join_lds<11, 256, true>
-                    : tier1 == 20 ? (const void *) k_join_lds<10, 256, false> : (const void *) k_join_lds<11, 256, false>;
-    const int t1_threads = tier1 == 9 ? 128 : 256;
-    pl.occ_slot = tier1 >= 20 ? tier1 - 20 + 3 : (tier1 ? tier1 - 9 : 0);
-    if (tier1 && c->occ_tier1[pl.occ_slot] == 0) c->occ_tier1[pl.occ_slot] = occupancy(fn1, t1_threads);
-    pl.grid1 = tier1 ? std::min<uint32_t>(n_rows, (uint32_t) cus * c->occ_tier1[pl.occ_slot]) : 0;
+    pl.k1 = tier1 ? join_kernel(TIER1, tier1) : -1; pl.k2 = join_kernel(TIER2, c->opt_tiny_tier2); pl.k3 = join_kernel(TIER3, pl.wide);
+    pl.grid1 = tier1 ? std::min<uint32_t>(n_rows, (uint32_t) cus * join_occupancy(c, pl.k1)) : 0;
     if (c->opt_grid_pct > 0 && pl.grid1) pl.grid1 = std::max<uint32_t>(1, (uint32_t) ((uint64_t) pl.grid1 * (uint32_t) c->opt_grid_pct / 100));     // (experiments: fewer rows in flight)
     // tier 0, the partition tier: packed ranges (gene ids below 2^22), no gene of <= 2k k-mers (single sightings are never
     // emitted), short rows on average (a cycle takes 4096 lookups: rows of several thousand would all be handed on).
@@ -1473,33 +1490,21 @@ static ScorePlan score_plan(pdl_ctx *c) {
             // the sift: counters against the set's threshold clamp(tc_min, 2, 255) (the kernel works it out the same way) where that is
             // high enough for 12 index bits to beat "seen twice" on 15 (PT_SIFT_T_MIN), bitmaps below it.  "sift_threshold" 0 is the test
             // switch: the counters at a threshold of 2, whatever the set's.
-            {
-                const float thr = 1.0f / (2.0f * (float) c->rp.k), denom = (float) (int) (uint32_t) std::max<uint64_t>(c->min_kseq, 1);
-                uint32_t t = (uint32_t) (thr * denom);
-                t = t > 2 ? t - 2 : 0;
-                while ((float) (int) t / denom < thr) t++;             // (min_numerator)
-                pl.tier0_cnt = c->opt_sift_threshold == 0 || t >= PT_SIFT_T_MIN;
-            }
-            const int f = pl.tier0_cnt ? 1 : 0;
-            if (c->occ_tier0[f] == 0) {
-                c->occ_tier0[f] = f ? occupancy((const void *) k_join_part<PT_T, PT_WG_PER_CU, true>, (int) PT_T) : occupancy((const void *) k_join_part<PT_T, PT_WG_PER_CU, false>, (int) PT_T);
-                c->occ_tier0b[f] = f ? occupancy((const void *) k_join_part<PT_T2, PT_WGS2, true>, (int) PT_T2) : occupancy((const void *) k_join_part<PT_T2, PT_WGS2, false>, (int) PT_T2);
-            }
-            pl.grid0 = std::min<uint32_t>((n_rows + PT_BATCH - 1) / PT_BATCH, (uint32_t) cus * c->occ_tier0[f]);
-            pl.grid0b = std::min<uint32_t>(n_rows, (uint32_t) cus * c->occ_tier0b[f]);
+            const uint32_t t = min_numerator(1.0f / (2.0f * (float) c->rp.k), (float) (int) (uint32_t) std::max<uint64_t>(c->min_kseq, 1));
+            const bool counters = c->opt_sift_threshold == 0 || t >= PT_SIFT_T_MIN;
+            pl.k0 = join_kernel(TIER0, counters); pl.k0b = join_kernel(TIER0B, counters);
+            pl.grid0 = std::min<uint32_t>((n_rows + PT_BATCH - 1) / PT_BATCH, (uint32_t) cus * join_occupancy(c, pl.k0));
+            pl.grid0b = std::min<uint32_t>(n_rows, (uint32_t) cus * join_occupancy(c, pl.k0b));
             if (c->opt_grid_pct > 0) pl.grid0 = std::max<uint32_t>(1, (uint32_t) ((uint64_t) pl.grid0 * (uint32_t) c->opt_grid_pct / 100));
         }
     }
-    pl.grid2 = std::min<uint32_t>(n_rows, (uint32_t) cus * (pl.tiny_tier2 ? 4 : 1));
-    // tier 3: a direct-addressed table per workgroup (20 bytes per gene; 36 with 32-bit counters): as many workgroups as ~8 GB
+    pl.grid2 = std::min<uint32_t>(n_rows, (uint32_t) cus * (c->opt_tiny_tier2 ? 4 : 1));
+    // tier 3: a direct-addressed table per workgroup (20 bytes per gene; 28 with 32-bit counters): as many workgroups as ~8 GB
     // of tables allow, at least 64 (configs[4]: 2 778 rows of the first genomes end up here, 0.6 ms each — 64 workgroups took
     // 26.7 ms over them)
-    {
-        const unsigned long long per_wg = (unsigned long long) std::max<uint32_t>(N, 1) * ((pl.wide ? 2 : 1) * sizeof(uint64_t) + 3 * sizeof(uint32_t));
-        const unsigned long long fit = ((c->opt_low_memory ? 1ull : 8ull) << 30) / per_wg;
-        pl.grid3 = (uint32_t) std::min<unsigned long long>((unsigned long long) cus, std::max<unsigned long long>(64, fit));
-    }
-    const size_t hbm_bytes = (size_t) pl.grid3 * N * ((pl.wide ? 2 : 1) * sizeof(uint64_t) + 3 * sizeof(uint32_t));
+    const unsigned long long fit = ((c->opt_low_memory ? 1ull : 8ull) << 30) / hbm_layout(std::max<uint32_t>(N, 1), pl.wide).per_wg();
+    pl.grid3 = (uint32_t) std::min<unsigned long long>((unsigned long long) cus, std::max<unsigned long long>(64, fit));
+    const size_t hbm_bytes = (size_t) pl.grid3 * hbm_layout(N, pl.wide).per_wg();
     if (c->glb_table.bytes < hbm_bytes) { c->glb_table.alloc(hbm_bytes); c->glb_clean = false; }
     // k_join_hbm leaves its tables zeroed, not its touched / emitted lists, and the workgroups' tables and lists are laid out by N,
     // the workgroup count and the counter width: a context rebuilt on a set of another size finds the old lists where its tables
@@ -1515,6 +1520,54 @@ static ScorePlan score_plan(pdl_ctx *c) {
     return pl;
 }
 
+// The hand-over from tier to tier.  A tier draws its work with a cursor word of join_ctr, `batch` items a draw: every row (row_desc;
+// the host knows how many) or what the tier in front listed in a link.  A link is a count word of join_ctr, one of the row lists of
+// overflow_rows (task positions) and one of the descriptor lists of row_desc2: a tier writes the descriptors of the rows it hands
+// on beside their positions, so the reader starts without a pass that makes them.  Tier 3 alone goes by the task positions.
+struct JoinLink { uint32_t count, cursor, rows; int desc; };      // PDL_JC_* of the count and of the reader's cursor | row list | descriptor list (-1: none)
+constexpr JoinLink LINK_T1_T2{PDL_JC_ROWS_T2, PDL_JC_CURSOR_T2, 0, 0}, LINK_T2_T3{PDL_JC_ROWS_T3, PDL_JC_CURSOR_T3, 1, -1},
+                   LINK_T0_T0B{PDL_JC_ROWS_T0B, PDL_JC_CURSOR_T0B, 2, 1}, LINK_T0B_T1{PDL_JC_ROWS_T1, PDL_JC_CURSOR_T1, 3, 2};
+constexpr uint32_t JOIN_ROW_LISTS = 4, JOIN_DESC_LISTS = 3;       // (n_task_rows entries each)
+struct TierIn { const uint4 *desc; const uint32_t *work; uint32_t n; const uint32_t *n_ptr; uint32_t *cursor; uint32_t batch; };      // descriptors or task positions | host or device count
+struct TierOut { uint32_t *count, *rows; uint4 *desc; };
+struct JoinLists {
+    uint32_t *ctr, *rows; uint4 *desc; const uint4 *all_desc; uint32_t n_rows, n_all;      // n_all: 0 when the whole set goes to tier 3 (the LDS tiers still launch, and leave at once)
+    TierOut out(const JoinLink &l) const { return {ctr + l.count, rows + (size_t) l.rows * n_rows, l.desc < 0 ? nullptr : desc + (size_t) l.desc * n_rows}; }
+    TierIn in(const JoinLink &l) const { const TierOut o = out(l); return {o.desc, o.desc ? nullptr : o.rows, 0, o.count, ctr + l.cursor, 1}; }      // (few, long rows: one a draw)
+    TierIn all(uint32_t cursor_word, uint32_t batch) const { return {all_desc, nullptr, n_all, nullptr, ctr + cursor_word, batch}; }
+    TierIn spread(uint32_t cursor_word, uint32_t grid) const { return all(cursor_word, std::max<uint32_t>(1, std::min<uint32_t>(8, n_rows / (std::max<uint32_t>(grid, 1) * 8)))); }      // (up to 8 a draw while every workgroup gets 8 draws)
+};
+
+// One tier: an entry of the table at `grid` workgroups, reading `in` and handing on through `out`.  `timed` counts in the diagnostic
+// build (-DPDL_JOIN_PHASES) only: the kernel's phase words are cleared in front of the launch and printed behind it (which waits for the
+// stream), n_timers as us per workgroup — thread 0's clock, waiting for every access it brackets: read the shares, not the sum — then counts.
+struct TierPhases { const char *tier; uint32_t n_timers, n_words; const char *label[12]; };
+static const TierPhases PHASES_T0{"tier 0", 6, 12, {"draw + pick", "stage", "prefixes", "walk", "sift + add", "finalize", "cycles", "cycles that overflowed",
+                                                     "survivors of wave 0 (x4 for all)", "probe steps of thread 0", "lookups", "rows"}},
+                        PHASES_T1{"tier 1", 10, 10, {"dispense", "stage", "barrier", "aside pass", "finalize", "walk: map", "postings", "bitmap", "table", "aside stores"}};
+static void launch_tier(pdl_ctx *c, JoinArgs a, int kernel, uint32_t grid, const TierIn &in, const TierOut &out, const TierPhases *timed = nullptr) {
+    a.desc = in.desc; a.work = in.work; a.n_work = in.n; a.n_work_ptr = in.n_ptr; a.work_cursor = in.cursor; a.work_batch = in.batch;
+    a.overflow_count = out.count; a.overflow_rows = out.rows; a.overflow_desc = out.desc;
+#ifdef PDL_JOIN_PHASES
+    static unsigned long long *d_phase = nullptr;
+    unsigned long long h[12];
+    if (timed && !d_phase) PDL_HIP(hipMalloc((void **) &d_phase, sizeof(h)));
+    if (timed) { PDL_HIP(hipMemsetAsync(d_phase, 0, sizeof(h), c->stream)); a.phase = d_phase; }
+#endif
+    hipLaunchKernelGGL(JOIN_KERNELS[kernel].fn, dim3(grid), dim3(JOIN_KERNELS[kernel].threads), 0, c->stream, a);
+#ifdef PDL_JOIN_PHASES
+    if (!timed) return;
+    PDL_HIP(hipMemcpyAsync(h, d_phase, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    PDL_HIP(hipStreamSynchronize(c->stream));
+    const double wgs = std::max<uint32_t>(grid, 1);
+    fprintf(stderr, "%s, phases per workgroup (us) and counts:", timed->tier);
+    for (uint32_t i = 0; i < timed->n_words; i++)
+        if (i < timed->n_timers) fprintf(stderr, "  %s %.1f", timed->label[i], h[i] * (10.0 / 1000.0) / wgs);      // (ticks of 10 ns)
+        else fprintf(stderr, "  %s %llu", timed->label[i], h[i]);
+    fprintf(stderr, "  | rows/wg %.1f\n", (double) c->n_task_rows / wgs);
+#endif
+}
+
 // buffers that depend on the row count only
 static void score_alloc_rows(pdl_ctx *c, const ScorePlan &pl) {
     const uint32_t N = c->N, G = c->G, n_rows = c->n_task_rows;
@@ -1524,8 +1577,8 @@ static void score_alloc_rows(pdl_ctx *c, const ScorePlan &pl) {
     c->row_base.alloc((size_t) n_rows * 4); c->row_cnt.alloc((size_t) n_rows * 4); c->fin_off.alloc(((size_t) n_rows + 2) * 4);      // (+1: the scan stores its 64-bit total at [n_rows])
     c->join_ctr.alloc(PDL_JC_WORDS * sizeof(uint32_t));
     c->row_desc.alloc((size_t) n_rows * sizeof(uint4));
-    c->row_desc2.alloc((size_t) n_rows * sizeof(uint4) * (pl.tier0 ? 3 : 1));      // descriptors of the rows a tier handed on (tier 1 -> 2 | tier 0 -> its second form | that -> 1)
-    c->overflow_rows.alloc((size_t) n_rows * 4 * 4);     // list A (tier 1 -> 2), list B (tier 2 -> 3), list S (tier 0 -> its second form), list S2 (that -> tier 1)
+    c->row_desc2.alloc((size_t) n_rows * sizeof(uint4) * (pl.tier0 ? JOIN_DESC_LISTS : 1));      // (the links of tier 0 come last)
+    c->overflow_rows.alloc((size_t) n_rows * 4 * JOIN_ROW_LISTS);
     if (pl.mirror) c->mirror_cnt.alloc((size_t) n_rows * 4 * 3 + 16);    // counts | offsets | cursors
     c->gene_info.alloc((size_t) N * sizeof(uint4));
     hipLaunchKernelGGL(k_row_desc, dim3((std::max(n_rows, N) + 255) / 256), dim3(256), 0, c->stream, c->task_rows.as<uint32_t>(), c->seq_off.as<uint32_t>(),
@@ -1546,32 +1599,49 @@ static void score_alloc_cells(pdl_ctx *c, const ScorePlan &pl, unsigned long lon
     c->st_cap = cap;
 }
 
+// The staged cells of a pass — where a row's cells start, how many it has, whose row it is, and the five staging arrays — as
+// JoinArgs, MirrorArgs, OrderArgs and OutboxArgs all name them: one fill for whichever of those is in hand.
+struct StagedCells { uint32_t *row_base, *row_cnt; const uint32_t *task_rows; float *st_score, *st_perc, *st_tr; uint32_t *st_col, *st_first; };
+static StagedCells staged_cells(pdl_ctx *c) {
+    return {c->row_base.as<uint32_t>(), c->row_cnt.as<uint32_t>(), c->task_rows.as<uint32_t>(), c->st_score.as<float>(), c->st_perc.as<float>(), c->st_tr.as<float>(), c->st_col.as<uint32_t>(), c->st_first.as<uint32_t>()};
+}
+template <class Args> static void set_staged_cells(Args &a, const StagedCells &s) {
+    a.row_base = s.row_base; a.row_cnt = s.row_cnt; a.task_rows = s.task_rows;
+    a.st_score = s.st_score; a.st_perc = s.st_perc; a.st_tr = s.st_tr; a.st_col = s.st_col; a.st_first = s.st_first;
+}
+
+// K-order's two kernels: rows of up to 256 cells inside one wave, then the rows that left for the workgroup kernel, if any
+static void launch_order(pdl_ctx *c, const OrderArgs &o) {
+    hipLaunchKernelGGL(k_order_rows_wave, dim3((o.n_rows + 3) / 4), dim3(256), 0, c->stream, o);
+    hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(o.n_rows, (uint32_t) pdl_cus(c) * 8)), dim3(ORDER_THREADS), 0, c->stream, o);
+}
+
 static JoinArgs join_args(pdl_ctx *c, const ScorePlan &pl) {
     JoinArgs a{};
     a.post = pdl_postings(c); a.ranges = c->ranges.as<uint4>(); a.ranges8 = c->ranges8; a.seq_off = c->seq_off.as<uint32_t>();
     a.kseq_len = c->kseq_len.as<uint32_t>(); a.genome_of = c->d_gen; a.gene_info = c->gene_info.as<uint4>();
-    a.task_rows = c->task_rows.as<uint32_t>(); a.task_lg = c->task_lg.as<uint32_t>();
+    a.task_lg = c->task_lg.as<uint32_t>();
     a.N = c->N; a.G = c->G; a.k = c->rp.k;
     a.min_kseq = (uint32_t) std::max<uint64_t>(c->min_kseq, 1); a.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u;
     a.MS = c->MS.as<float>(); a.CM = c->CM.as<float>();
-    a.row_base = c->row_base.as<uint32_t>(); a.row_cnt = c->row_cnt.as<uint32_t>();
-    a.st_score = c->st_score.as<float>(); a.st_perc = c->st_perc.as<float>(); a.st_tr = c->st_tr.as<float>();
-    a.st_col = c->st_col.as<uint32_t>(); a.st_first = c->st_first.as<uint32_t>(); a.st_cap = c->st_cap;
+    set_staged_cells(a, staged_cells(c)); a.st_cap = c->st_cap;
     a.mirror = pl.mirror ? 1u : 0u;
     a.sift_threshold = c->opt_sift_threshold ? 1u : 0u;
     if (pl.mirror) {
         a.taskpos_of = c->taskpos_of.as<uint32_t>(); a.local_genome = c->local_genome.as<uint32_t>();
         a.mirror_cnt = c->mirror_cnt.as<uint32_t>();
     }
+    uint32_t *ctr32 = c->join_ctr.as<uint32_t>();
+    a.error_count = ctr32 + PDL_JC_ERRORS; a.reload_count = ctr32 + PDL_JC_RELOADS;
+    a.cell_cursor = reinterpret_cast<unsigned long long *>(ctr32 + PDL_JC_CELLS);
     return a;
 }
 
-// clears the maxima, the counters and the mirror bookkeeping, then queues the three tiers
+// clears the maxima, the counters and the mirror bookkeeping, then queues the tiers
 static void score_join(pdl_ctx *c, const ScorePlan &pl) {
     hipStream_t st = c->stream;
     const uint32_t N = c->N, G = c->G, n_rows = c->n_task_rows;
     const uint32_t S = (uint32_t) c->shard.size();
-    const int tier1 = pl.tier1;
     {   // maxima, counters and (mirror mode) the per-row mirror counts/offsets/cursors start at zero: one launch
         auto n16 = [](size_t bytes) { return (unsigned long long) ((bytes + 15) / 16); };      // (buffers are sized in whole 16-byte words)
         ZeroRanges z{};
@@ -1582,107 +1652,47 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
         const unsigned long long most = std::max(z.n16[0], z.n16[1]);
         hipLaunchKernelGGL(k_zero_ranges, dim3((uint32_t) std::min<unsigned long long>((most + 255) / 256 + 1, (unsigned long long) c->cus * 16)), dim3(256), 0, st, z);
     }
-    JoinArgs a = join_args(c, pl);
-    uint32_t *ctr32 = c->join_ctr.as<uint32_t>();
-    uint32_t *list_a = c->overflow_rows.as<uint32_t>(), *list_b = list_a + n_rows, *list_s = list_b + n_rows, *list_s2 = list_s + n_rows;
-    a.error_count = ctr32 + PDL_JC_ERRORS; a.reload_count = ctr32 + PDL_JC_RELOADS;
-    a.cell_cursor = reinterpret_cast<unsigned long long *>(ctr32 + PDL_JC_CELLS);
+    const JoinArgs a = join_args(c, pl);
+    const JoinLists L{c->join_ctr.as<uint32_t>(), c->overflow_rows.as<uint32_t>(), c->row_desc2.as<uint4>(), c->row_desc.as<uint4>(), n_rows, pl.wide ? 0 : n_rows};
 
     ev_begin(c, EV_JOIN);
-    if (pl.wide) {          // every row straight to tier 3: list B = all task positions
-        hipLaunchKernelGGL(k_iota_u32, dim3((n_rows + 255) / 256), dim3(256), 0, st, list_b, n_rows);
-        PDL_HIP(hipMemcpyAsync(ctr32 + PDL_JC_ROWS_T3, &c->n_task_rows, 4, hipMemcpyHostToDevice, st));
+    if (pl.wide) {          // every row straight to tier 3: its link lists all task positions
+        hipLaunchKernelGGL(k_iota_u32, dim3((n_rows + 255) / 256), dim3(256), 0, st, L.out(LINK_T2_T3).rows, n_rows);
+        PDL_HIP(hipMemcpyAsync(L.out(LINK_T2_T3).count, &c->n_task_rows, 4, hipMemcpyHostToDevice, st));
     }
-    // tier 0 (the partition tier) over every row; what it does not take is listed for tier 1
-    a.work = nullptr; a.desc = c->row_desc.as<uint4>(); a.n_work = pl.wide ? 0 : n_rows; a.n_work_ptr = nullptr;
+    // clear -> [tier 0 -> tier 0b] -> [tier 1] -> tier 2 -> tier 3: the first tier there is draws from every row, the others
+    // from the link of the tier in front
     if (pl.tier0) {
-        a.work_cursor = ctr32 + PDL_JC_CURSOR_T0; a.overflow_count = ctr32 + PDL_JC_ROWS_T0B; a.overflow_rows = list_s; a.work_batch = PT_BATCH;
-        a.overflow_desc = c->row_desc2.as<uint4>() + n_rows;
-#ifdef PDL_JOIN_PHASES
-        static unsigned long long *d_phase0 = nullptr;
-        if (!d_phase0) PDL_HIP(hipMalloc((void **) &d_phase0, 12 * sizeof(unsigned long long)));
-        PDL_HIP(hipMemsetAsync(d_phase0, 0, 12 * sizeof(unsigned long long), st));
-        a.phase = d_phase0;
-#endif
-        if (pl.tier0_cnt) hipLaunchKernelGGL((k_join_part<PT_T, PT_WG_PER_CU, true>), dim3(pl.grid0), dim3(PT_T), 0, st, a);
-        else hipLaunchKernelGGL((k_join_part<PT_T, PT_WG_PER_CU, false>), dim3(pl.grid0), dim3(PT_T), 0, st, a);
-#ifdef PDL_JOIN_PHASES
-        {   // (the first form only; the timers are thread 0's clock between the barriers: shares of a workgroup's time, other workgroups of the CU run beside it)
-            unsigned long long h[12];
-            PDL_HIP(hipMemcpyAsync(h, d_phase0, sizeof(h), hipMemcpyDeviceToHost, st));
-            PDL_HIP(hipStreamSynchronize(st));
-            const double per = 10.0 / 1000.0 / std::max<uint32_t>(pl.grid0, 1);       // ticks of 10 ns -> us per workgroup
-            fprintf(stderr, "tier 0 phases per workgroup (us): draw + pick %.1f  stage %.1f  prefixes %.1f  walk %.1f  sift + add %.1f  finalize %.1f  | rows/wg %.1f\n",
-                    h[0] * per, h[1] * per, h[2] * per, h[3] * per, h[4] * per, h[5] * per, (double) n_rows / std::max<uint32_t>(pl.grid0, 1));
-            fprintf(stderr, "tier 0 counts: cycles %llu (%.2f rows, %.0f lookups each)  cycles that overflowed %llu  survivors of wave 0 %llu (x4 = %.1f %% of the lookups)  probe steps of thread 0: %llu\n",
-                    h[6], (double) h[11] / std::max<unsigned long long>(h[6], 1), (double) h[10] / std::max<unsigned long long>(h[6], 1), h[7], h[8], 400.0 * h[8] / std::max<unsigned long long>(h[10], 1), h[9]);
-            a.phase = nullptr;
-        }
-#endif
-        // ... its second form (512 threads: twice the lookups per cycle) over the rows that alone exceed the first form's cycle,
-        // one row per draw; what that cannot hold either is listed for tier 1 (a tier writes the descriptors of the rows it hands on)
-        a.desc = c->row_desc2.as<uint4>() + n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T0B;
-        a.work_cursor = ctr32 + PDL_JC_CURSOR_T0B; a.overflow_count = ctr32 + PDL_JC_ROWS_T1; a.overflow_rows = list_s2; a.work_batch = 1;
-        a.overflow_desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows;
-        if (pl.tier0_cnt) hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2, true>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
-        else hipLaunchKernelGGL((k_join_part<PT_T2, PT_WGS2, false>), dim3(pl.grid0b), dim3(PT_T2), 0, st, a);
-        a.desc = c->row_desc2.as<uint4>() + 2 * (size_t) n_rows; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T1;
+        // the partition tier, and its second form (512 threads: twice the lookups per cycle) over the rows that alone exceed
+        // the first form's cycle; what that cannot hold either is listed for tier 1
+        launch_tier(c, a, pl.k0, pl.grid0, L.all(PDL_JC_CURSOR_T0, PT_BATCH), L.out(LINK_T0_T0B), &PHASES_T0);
+        launch_tier(c, a, pl.k0b, pl.grid0b, L.in(LINK_T0_T0B), L.out(LINK_T0B_T1));
         c->tm.join_launches += 2;
     }
-    // tier 1
-    a.work_cursor = ctr32 + PDL_JC_CURSOR_T1; a.overflow_count = ctr32 + PDL_JC_ROWS_T2; a.overflow_rows = list_a; a.overflow_desc = tier1 ? c->row_desc2.as<uint4>() : nullptr;
-    a.work_batch = pl.tier0 ? 1 : std::max<uint32_t>(1, std::min<uint32_t>(8, n_rows / (std::max<uint32_t>(pl.grid1, 1) * 8)));      // (behind tier 0: few, long rows)
-    if (tier1 >= 9 && tier1 <= 11) {
-        // the filter tiers put a row's first sightings aside in a list per workgroup (16 bytes each; rewritten row after row, so
-        // only the part in use is ever hot): room for 4x the lookups of the average row (never more than one per gene), a
-        // row with more first sightings goes to tier 2
-        const unsigned long long avg = n_rows ? c->P / n_rows : 0;
-        a.defer_cap = (uint32_t) std::min<unsigned long long>(std::min<unsigned long long>(std::max<unsigned long long>(4 * avg, 8192), 1u << 18), (unsigned long long) N + 64);
-        a.defer_wide = (N >= (1u << 22) || pl.wide_aside) ? 1u : 0u;
-        c->join_defer.alloc((size_t) pl.grid1 * a.defer_cap * (a.defer_wide ? sizeof(uint4) : sizeof(uint2)));
-        a.defer = c->join_defer.p;
-        static std::atomic<uint32_t> launch_serial{0};        // (process-wide: a freed list may come back to another context as it was left)
-        a.defer_serial = ++launch_serial;
+    if (pl.tier1) {
+        JoinArgs a1 = a;
+        if (pl.tier1 >= 9 && pl.tier1 <= 11) {
+            // the filter tiers put a row's first sightings aside in a list per workgroup (16 bytes each; rewritten row after row, so
+            // only the part in use is ever hot): room for 4x the lookups of the average row (never more than one per gene), a
+            // row with more first sightings goes to tier 2
+            const unsigned long long avg = n_rows ? c->P / n_rows : 0;
+            a1.defer_cap = (uint32_t) std::min<unsigned long long>(std::min<unsigned long long>(std::max<unsigned long long>(4 * avg, 8192), 1u << 18), (unsigned long long) N + 64);
+            a1.defer_wide = (N >= (1u << 22) || pl.wide_aside) ? 1u : 0u;
+            c->join_defer.alloc((size_t) pl.grid1 * a1.defer_cap * (a1.defer_wide ? sizeof(uint4) : sizeof(uint2)));
+            a1.defer = c->join_defer.p;
+            static std::atomic<uint32_t> launch_serial{0};        // (process-wide: a freed list may come back to another context as it was left)
+            a1.defer_serial = ++launch_serial;
+        }
+        launch_tier(c, a1, pl.k1, pl.grid1, pl.tier0 ? L.in(LINK_T0B_T1) : L.spread(PDL_JC_CURSOR_T1, pl.grid1), L.out(LINK_T1_T2), &PHASES_T1);
     }
-#ifdef PDL_JOIN_PHASES
-    static unsigned long long *d_phase = nullptr;
-    if (!d_phase) PDL_HIP(hipMalloc((void **) &d_phase, 10 * sizeof(unsigned long long)));
-    PDL_HIP(hipMemsetAsync(d_phase, 0, 10 * sizeof(unsigned long long), st));
-    a.phase = d_phase;
-#endif
-    if (tier1 == 9) hipLaunchKernelGGL((k_join_lds<9, 128, true>), dim3(pl.grid1), dim3(128), 0, st, a);
-    else if (tier1 == 10) hipLaunchKernelGGL((k_join_lds<10, 256, true>), dim3(pl.grid1), dim3(256), 0, st, a);
-    else if (tier1 == 11) hipLaunchKernelGGL((k_join_lds<11, 256, true>), dim3(pl.grid1), dim3(256), 0, st, a);
-    else if (tier1 == 20) hipLaunchKernelGGL((k_join_lds<10, 256, false>), dim3(pl.grid1), dim3(256), 0, st, a);
-    else if (tier1 == 21) hipLaunchKernelGGL((k_join_lds<11, 256, false>), dim3(pl.grid1), dim3(256), 0, st, a);
-#ifdef PDL_JOIN_PHASES
-    {   // (the timers wait for every access they bracket, which serialises the walk: read the shares, not the sum)
-        unsigned long long h[10];
-        PDL_HIP(hipMemcpyAsync(h, d_phase, sizeof(h), hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipStreamSynchronize(st));
-        const double per = 10.0 / 1000.0 / std::max<uint32_t>(pl.grid1, 1);       // ticks of 10 ns -> us per workgroup
-        fprintf(stderr, "join phases per workgroup (us): dispense %.1f  stage %.1f  [walk: map %.1f  postings %.1f  bitmap %.1f  table %.1f  aside stores %.1f]  barrier %.1f  aside pass %.1f  finalize %.1f  | rows/wg %.1f\n",
-                h[0] * per, h[1] * per, h[5] * per, h[6] * per, h[7] * per, h[8] * per, h[9] * per, h[2] * per, h[3] * per, h[4] * per,
-                (double) n_rows / std::max<uint32_t>(pl.grid1, 1));
-        a.phase = nullptr;
-    }
-#endif
-    // tier 2 over list A (or over everything when tier 1 is off)
-    if (tier1) { a.desc = c->row_desc2.as<uint4>(); a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T2; }
-    a.work_cursor = ctr32 + PDL_JC_CURSOR_T2; a.overflow_count = ctr32 + PDL_JC_ROWS_T3; a.overflow_rows = list_b; a.overflow_desc = nullptr;      // (tier 3 goes by the task positions)
-    a.work_batch = tier1 ? 1 : std::max<uint32_t>(1, std::min<uint32_t>(8, n_rows / (pl.grid2 * 8)));
-    if (pl.wide && !tier1) a.n_work = 0;
-    if (pl.tiny_tier2) hipLaunchKernelGGL((k_join_lds<9, 64, false>), dim3(pl.grid2), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_join_lds<13, 1024, false>), dim3(pl.grid2), dim3(1024), 0, st, a);
+    launch_tier(c, a, pl.k2, pl.grid2, pl.tier1 ? L.in(LINK_T1_T2) : L.spread(PDL_JC_CURSOR_T2, pl.grid2), L.out(LINK_T2_T3));
     PDL_HIP(hipGetLastError());
-    // tier 3 over list B (inside the join's event pair; its own pair is one of the optional stage timers)
-    a.hbm_acc = c->glb_table.as<unsigned long long>();
-    a.hbm_u32 = reinterpret_cast<uint32_t *>(a.hbm_acc + (size_t) pl.grid3 * N * (pl.wide ? 2 : 1));
-    a.work = list_b; a.n_work = 0; a.n_work_ptr = ctr32 + PDL_JC_ROWS_T3; a.work_cursor = ctr32 + PDL_JC_CURSOR_T3; a.work_batch = 1;
+    // tier 3 (inside the join's event pair; its own pair is one of the optional stage timers)
+    JoinArgs a3 = a; a3.hbm_acc = c->glb_table.as<unsigned long long>();
+    a3.hbm_u32 = reinterpret_cast<uint32_t *>(c->glb_table.as<uint8_t>() + (size_t) pl.grid3 * hbm_layout(N, pl.wide).sums);
     ev_begin(c, EV_JOIN_OVF);
     c->glb_clean = false;
-    if (pl.wide) hipLaunchKernelGGL(k_join_hbm<true>, dim3(pl.grid3), dim3(HBM_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k_join_hbm<false>, dim3(pl.grid3), dim3(HBM_THREADS), 0, st, a);
+    launch_tier(c, a3, pl.k3, pl.grid3, L.in(LINK_T2_T3), TierOut{});
     PDL_HIP(hipGetLastError());
     ev_end(c, EV_JOIN_OVF);
     ev_end(c, EV_JOIN);
@@ -1723,25 +1733,19 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
         uint32_t *m_off = c->mirror_cnt.as<uint32_t>() + n_rows, *m_cur = m_off + n_rows;
         scan_and_apply(c, n_rows, MirrorCntFlag{d_mcnt}, FinOffApply{m_off}, d_scal + PDL_CTL_MIRRORED);
         MirrorArgs ma{};
-        ma.row_base = c->row_base.as<uint32_t>(); ma.row_cnt = c->row_cnt.as<uint32_t>(); ma.task_rows = c->task_rows.as<uint32_t>();
-        ma.st_score = c->st_score.as<float>(); ma.st_perc = c->st_perc.as<float>(); ma.st_tr = c->st_tr.as<float>();
-        ma.st_col = c->st_col.as<uint32_t>(); ma.st_first = c->st_first.as<uint32_t>();
+        set_staged_cells(ma, staged_cells(c));
         ma.taskpos_of = c->taskpos_of.as<uint32_t>(); ma.mirror_off = m_off; ma.mirror_cur = m_cur; ma.n_rows = n_rows;
         ma.mcell = c->mirror_ref.as<MCell>();
         hipLaunchKernelGGL(k_mirror_cells, dim3((n_rows + 3) / 4), dim3(256), 0, st, ma);
         if (n_inbox) hipLaunchKernelGGL(k_mirror_cells_inbox, dim3((n_inbox + 255) / 256), dim3(256), 0, st, ma, d_inbox, n_inbox, c->N);
         o.mirror_cnt = d_mcnt; o.mirror_off = m_off; o.mcell = c->mirror_ref.as<MCell>();
     }
-    o.row_base = c->row_base.as<uint32_t>(); o.row_cnt = c->row_cnt.as<uint32_t>(); o.fin_off = c->fin_off.as<uint32_t>();
-    o.task_rows = c->task_rows.as<uint32_t>();
-    o.st_score = c->st_score.as<float>(); o.st_perc = c->st_perc.as<float>(); o.st_tr = c->st_tr.as<float>();
-    o.st_col = c->st_col.as<uint32_t>(); o.st_first = c->st_first.as<uint32_t>();
+    set_staged_cells(o, staged_cells(c)); o.fin_off = c->fin_off.as<uint32_t>();
     o.c_score = c->c_score.as<float>(); o.c_perc = c->c_perc.as<float>(); o.c_tr = c->c_tr.as<float>();
     o.c_row = c->c_row.as<int32_t>(); o.c_col = c->c_col.as<int32_t>();
     o.n_rows = n_rows; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = c->N < (1u << 22) ? 1u : 0u;
     o.wide_rows = ctr32 + PDL_JC_WIDE_ROWS;  // (counter block, zero since the clearing launch)
-    hipLaunchKernelGGL(k_order_rows_wave, dim3((n_rows + 3) / 4), dim3(256), 0, st, o);
-    hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n_rows, (uint32_t) c->cus * 8)), dim3(ORDER_THREADS), 0, st, o);   // rows of more than 256 cells, if any
+    launch_order(c, o);
     PDL_HIP(hipGetLastError());
     ev_end(c, EV_ORDER);
 
@@ -1811,6 +1815,8 @@ static unsigned long long first_staging_cap(pdl_ctx *c, const ScorePlan &pl, uin
     return std::min<unsigned long long>(cap, std::max<unsigned long long>(lookups, 1ull)) + pl.slack;
 }
 
+static void join_timings(pdl_ctx *c) { c->tm.join_ms = ev_ms(c, EV_JOIN); c->tm.join_overflow_ms = ev_ms(c, EV_JOIN_OVF); }
+
 static void score_reset(pdl_ctx *c) {
     const uint32_t S = (uint32_t) c->shard.size();
     c->h_cell_off.assign(S + 1, 0);
@@ -1838,8 +1844,7 @@ void pdl_run_score_all(pdl_ctx *c) {
         if (judge_pass(c, pl, z, cap, attempt, overflows) == PassVerdict::accept) break;
         ev_begin(c, EV_SCORE_TOTAL);
     }
-    c->tm.join_ms = ev_ms(c, EV_JOIN);
-    c->tm.join_overflow_ms = ev_ms(c, EV_JOIN_OVF);
+    join_timings(c);
     c->tm.order_ms = ev_ms(c, EV_ORDER);
     c->tm.score_total_ms = ev_ms(c, EV_SCORE_TOTAL);
     c->scored = true;
@@ -1875,9 +1880,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
         score_alloc_cells(c, pl, cap, cap);
         score_join(c, pl);
         OutboxArgs oa{};
-        oa.row_base = c->row_base.as<uint32_t>(); oa.row_cnt = c->row_cnt.as<uint32_t>(); oa.task_rows = c->task_rows.as<uint32_t>();
-        oa.st_score = c->st_score.as<float>(); oa.st_perc = c->st_perc.as<float>(); oa.st_tr = c->st_tr.as<float>();
-        oa.st_col = c->st_col.as<uint32_t>(); oa.st_first = c->st_first.as<uint32_t>();
+        set_staged_cells(oa, staged_cells(c));
         oa.taskpos_of = c->taskpos_of.as<uint32_t>(); oa.genome_of = c->d_gen; oa.owner = c->owner_of_genome.as<uint32_t>();
         oa.n_rows = n_rows; oa.rows_per_block = rows_per_block; oa.world = W; oa.n_blocks = n_blocks;
         oa.tab = tab; oa.offs = offs;
@@ -1911,8 +1914,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
     }
     ev_end(c, EV_SCORE_TOTAL);
     PDL_HIP(hipStreamSynchronize(st));
-    c->tm.join_ms = ev_ms(c, EV_JOIN);
-    c->tm.join_overflow_ms = ev_ms(c, EV_JOIN_OVF);
+    join_timings(c);
     c->tm.dist_score_begin_ms = ev_ms(c, EV_SCORE_TOTAL);
     c->dist_stage = 3;
 }

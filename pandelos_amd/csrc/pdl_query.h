@@ -547,14 +547,12 @@ static void q_order_rows(pdl_ctx *c, const QJoinArgs &a, uint32_t *fin_off, uint
                          uint64_t max_cols, unsigned long long *emitted, unsigned long long *wide_rows) {
     scan_and_apply(c, n_rows, RowCntFlag{a.row_cnt, nullptr}, FinOffApply{fin_off}, reinterpret_cast<uint64_t *>(emitted));
     OrderArgs o{};
-    o.row_base = a.row_base; o.row_cnt = a.row_cnt; o.fin_off = fin_off; o.task_rows = rowid;
-    o.st_score = a.st_score; o.st_perc = a.st_perc; o.st_tr = a.st_tr; o.st_col = a.st_col; o.st_first = a.st_first;
+    set_staged_cells(o, StagedCells{a.row_base, a.row_cnt, rowid, a.st_score, a.st_perc, a.st_tr, a.st_col, a.st_first}); o.fin_off = fin_off;
     o.c_score = cells; o.c_perc = cells + cap; o.c_tr = cells + 2 * cap;
     o.c_row = reinterpret_cast<int32_t *>(cells + 3 * cap); o.c_col = reinterpret_cast<int32_t *>(cells + 4 * cap);
     o.n_rows = n_rows; o.canonical = (c->flags & PDL_FLAG_CANONICAL_ORDER) ? 1u : 0u; o.pack_ok = max_cols < (1u << 22) ? 1u : 0u;
     o.wide_rows = reinterpret_cast<uint32_t *>(wide_rows);
-    hipLaunchKernelGGL(k_order_rows_wave, dim3((n_rows + 3) / 4), dim3(256), 0, c->stream, o);
-    hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(n_rows, (uint32_t) pdl_cus(c) * 8)), dim3(ORDER_THREADS), 0, c->stream, o);
+    launch_order(c, o);
 }
 
 // The block as library.cpp:542-603 marshals it, for Z cells of n query genes: q_block_alloc sets the counts and allocates the
