@@ -649,60 +649,123 @@ static void group_shard_args(pdl_ctx *c, GroupTileArgs &ga) {
     ga.in_shard = c->seq_in_shard.as<uint8_t>();
 }
 
-// K-groups + K-ranges + K-cost over the dictionary (postings with head bits; `bound` records at most, the count is at
-// scalars[PDL_CTL_RECORDS]).  mode 0: whole groups for the shard's genes | 1: upper ranges, every gene | 2: upper ranges, the shard's genes.
-static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool only_complexity) {
-    hipStream_t st = c->stream;
-    c->costs_ready = true; c->ranges8 = nullptr;
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    const uint64_t *d_u = d_scal + PDL_CTL_RECORDS;
-    uint2 *post = pdl_postings(c);
-    GroupTileArgs ga{};
-    ga.post = post; ga.n_bound = bound; ga.d_n = d_u;
-    const uint32_t grid = group_tiles_plan(c, ga);
-    ga.cost = c->cost.as<unsigned long long>();
-    ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
-    ga.genome_of = c->d_gen; ga.n_genomes = c->G;
-    hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, st, post, c->post_ext ? (uint32_t *) nullptr : c->recpos.as<uint32_t>(), d_u);
-    if (only_complexity) {                   // (cost[] was zeroed by K-len's apply, the counters with the control block)
-        launch_group_costs<false, true>(c, ga, grid);
+// ---- the range stage: K-groups + K-ranges + K-cost -------------------------------------------------------------------------------
+// What the five paths that build range lists share ("The host side of the range stage"): the whole build and the append / remove tail
+// (stage_ranges_and_costs), the next genome batch (pdl_run_reshard), the multi-GPU owner (pdl_run_dist_finish) and sender (pdl_run_dist_ranges, _finish_ranges).
+// mode 0: whole groups for the shard's genes | 1: upper ranges, every gene | 2: upper ranges, the shard's genes.
+
+// What a path clears of the control block, by name: an inclusive span of PDL_CTL_* words, the per-genome words, cost[].
+static void clear_ctl(pdl_ctx *c, size_t first, size_t last) { PDL_HIP(hipMemsetAsync(c->scalars.as<uint64_t>() + first, 0, (last - first + 1) * sizeof(uint64_t), c->stream)); }
+static void clear_genome_words(pdl_ctx *c, bool upper_too = true) {      // [G] costs (+ [G] lookups above the diagonal)
+    PDL_HIP(hipMemsetAsync(c->scalars.as<uint64_t>() + PDL_CTL_GCOST, 0, (upper_too ? 2 : 1) * (size_t) c->G * sizeof(uint64_t), c->stream));
+}
+static void clear_kseq_stats(pdl_ctx *c) { clear_ctl(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_SUM); clear_ctl(c, PDL_CTL_KSEQ_MAX, PDL_CTL_KSEQ_NMIN); }   // k_genome_cost's sum | max, ~min
+static void clear_gene_costs(pdl_ctx *c) { PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), c->stream)); }
+
+// How a path's ranges travel and what their buffers are sized for.
+//   packed    8 bytes, carried through the gene sort as its payload (no gather afterwards): whenever a range sits right behind its
+//             own record (the upper modes) and a posting count fits 22 bits; else 16-byte tuples fetched through the sorted positions
+//   exact     the COUNT pass's total is read (one synchronisation) and the buffers are sized for it: a shard (modes 0, 2: 1/W or one
+//             batch of the genes) and a rank's run — a 512-genome set would otherwise allocate 20-28 bytes for each of its 0.9 G
+//             records per shard.  Else (the whole build on one GPU, mode 1) the host does not look: the range count stays on the
+//             device, buffers and kernels are sized for the bound (every record may get a range)
+//   fused     single-GPU build with packed ranges: the tuples are filed by the low byte of their gene by the kernel that makes
+//             them (the first pass of the gene sort without a trip through HBM in between)
+//   received  the gene sort's first pair is the caller's inbox (pdl_run_dist_finish_ranges): only the second is carved
+struct RangePlan { bool packed, exact, fused, received; };
+static RangePlan range_plan(const pdl_ctx *c, int mode, bool run_of_a_rank = false) {
+    const bool packed = mode != 0 && c->N < (1u << 22);
+    return RangePlan{packed, mode != 1 || run_of_a_rank, mode == 1 && packed && !run_of_a_rank, false};
+}
+constexpr RangePlan RANGES_RECEIVED{true, true, false, true};
+
+// c->scratch for `cap` ranges:
+//   packed    pay_a u64[cap] | pay_b u64[cap] | [k2a u32[cap]] | k2b u32[cap]
+//   tuples    tuples uint4[cap] | v2a u32[cap] | [k2a u32[cap]] | k2b u32[cap] | v2b u32[cap]
+//   received  pay_b u64[cap] | k2b u32[cap]          (the outbox in `scratch` has been delivered: its memory takes this pair)
+// k2a, the gene sort's first key buffer: in `scratch` when exact (the rank sort's buffers may be gone: "low_memory"), else vals_a (free after sort 1)
+struct RangeBufs { uint4 *tuples; unsigned long long *pay_a, *pay_b; uint32_t *k2a, *k2b, *v2a, *v2b; };
+static RangeBufs carve_ranges(pdl_ctx *c, const RangePlan &p, uint64_t cap, uint32_t *in_keys = nullptr, unsigned long long *in_ranges = nullptr) {
+    const size_t first = p.received ? 0 : p.packed ? sizeof(uint64_t) : sizeof(uint4) + sizeof(uint32_t);      // pay_a, or tuples and v2a
+    const size_t second = p.packed ? sizeof(uint64_t) + sizeof(uint32_t) : 2 * sizeof(uint32_t);              // pay_b and k2b, or k2b and v2b
+    const bool k2a_here = p.exact && !p.received;
+    c->scratch.alloc(cap * (first + second + (k2a_here ? sizeof(uint32_t) : 0)) + 64);
+    RangeBufs b{};
+    if (p.packed) {
+        b.pay_a = p.received ? in_ranges : c->scratch.as<unsigned long long>();
+        b.pay_b = p.received ? c->scratch.as<unsigned long long>() : b.pay_a + cap;
+        b.k2b = reinterpret_cast<uint32_t *>(b.pay_b + cap);
     } else {
-        ev_begin(c, EV_SORT2);
-        // Ranges travel packed (8 bytes, carried through the gene sort as its payload: no gather afterwards) whenever a
-        // range sits right behind its own record (the upper modes) and a posting count fits 22 bits; else as 16-byte
-        // tuples fetched through the sorted positions.
-        const bool packed = mode != 0 && c->N < (1u << 22);
-        // scratch: packed   pay_a u64[cap] | pay_b u64[cap] | k2b u32[cap]
-        //          tuples   tuples uint4[cap] | v2a u32[cap] | k2b u32[cap] | v2b u32[cap];   key2 lives in vals_a (free after sort 1) or behind them
-        // cap = the bound (every record may get a range) when the whole build stays on the device without a look from the host
-        // (mode 1); with a shard (modes 0, 2: 1/W or one batch of the genes) the COUNT pass's total is read first and the buffers
-        // are sized for it — a 512-genome set would otherwise allocate 20-28 bytes for each of its 0.9 G records per shard
-        const bool exact = mode != 1;
-        uint64_t cap = bound;
-        uint4 *tuples = nullptr;
-        unsigned long long *pay_a = nullptr, *pay_b = nullptr;
-        uint32_t *k2a = nullptr, *v2a = nullptr, *k2b = nullptr, *v2b = nullptr;
-        auto carve = [&]() {
-            c->scratch.alloc(cap * (packed ? 2 * sizeof(uint64_t) + sizeof(uint32_t) : sizeof(uint4) + 3 * sizeof(uint32_t)) + (exact ? cap * sizeof(uint32_t) : 0) + 64);
-            tuples = c->scratch.as<uint4>();
-            pay_a = c->scratch.as<unsigned long long>(); pay_b = pay_a + cap;
-            v2a = packed ? nullptr : reinterpret_cast<uint32_t *>(tuples + cap);
-            k2b = packed ? reinterpret_cast<uint32_t *>(pay_b + cap) : v2a + cap;
-            v2b = packed ? nullptr : k2b + cap;
-            if (exact) k2a = (packed ? k2b : v2b) + cap;                     // (the sort's first buffer may be gone: "low_memory")
-            else { c->vals_a.alloc(cap * sizeof(uint32_t)); k2a = c->vals_a.as<uint32_t>(); }
-        };
-        if (!exact) carve();
-        if (mode != 1) group_shard_args(c, ga);      // only the genes this context scores need range lists
-        // the head bits the WRITE pass takes out of the postings are kept: for the per-gene costs made on demand (packed ranges), and
-        // to put them back when the ranges are built again for another shard of genomes (pdl_run_reshard)
-        c->head_bits.alloc(((bound + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
-        ga.head_bits = c->head_bits.as<unsigned long long>();
-        const uint64_t *d_us = d_scal + PDL_CTL_RANGES;       // ranges built = the total of the tile counts
-        // single-GPU build with packed ranges: the tuples are filed by the low byte of their gene by the kernel that makes
-        // them (the first pass of the gene sort without a trip through HBM in between)
-        const bool fused = mode == 1 && packed;
-        if (fused) {
+        b.tuples = c->scratch.as<uint4>();
+        b.v2a = reinterpret_cast<uint32_t *>(b.tuples + cap); b.k2b = b.v2a + cap;
+    }
+    if (p.received) b.k2a = in_keys;
+    else if (k2a_here) { b.k2a = b.k2b; b.k2b += cap; }
+    else { c->vals_a.alloc(cap * sizeof(uint32_t)); b.k2a = c->vals_a.as<uint32_t>(); }
+    if (!p.packed) b.v2b = b.k2b + cap;
+    return b;
+}
+
+// Where a WRITE pass writes: the ranges into b (k_group_write; k_range_scatter is told its own), and the head bits it takes out
+// of the postings, which are kept: for the per-gene costs made on demand (packed ranges), and to put them back when the ranges
+// are built again for another shard of genomes (pdl_run_reshard).
+static void set_write_targets(pdl_ctx *c, GroupTileArgs &ga, const RangeBufs &b) {
+    c->head_bits.alloc(((ga.n_bound + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
+    ga.head_bits = c->head_bits.as<unsigned long long>();
+    ga.key2 = b.k2a; ga.tuples = b.tuples; ga.pay8 = b.pay_a;
+}
+
+// An exact plan's two passes: COUNT, the range count read (with `tasks_meanwhile`, the task layout is made while the device
+// counts: host work + small uploads), buffers for max(count, 1) ranges into b, WRITE.  Returns the count.
+static uint64_t count_then_write(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode, const RangePlan &plan, bool tasks_meanwhile, RangeBufs &b) {
+    launch_range_count(c, ga, grid, mode);
+    if (tasks_meanwhile && !c->tasks_ready) pdl_prepare_tasks(c);
+    PinRead rd(c);
+    const uint64_t *pn = rd.add<uint64_t>(c->scalars.as<uint64_t>() + PDL_CTL_RANGES, 1);
+    rd.sync();
+    const uint64_t n = pn[0];
+    b = carve_ranges(c, plan, std::max<uint64_t>(n, 1));
+    set_write_targets(c, ga, b);
+    launch_range_write(c, ga, grid, mode);
+    return n;
+}
+
+// K-seq-offsets: every gene's place among the ranges sorted by gene (the gene of a key: its bits under gene_mask)
+static void launch_seq_offsets(pdl_ctx *c, const uint32_t *keys_by_gene, uint32_t gene_mask) {
+    c->seq_off.alloc(((size_t) c->N + 1) * sizeof(uint32_t));
+    hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, c->stream, keys_by_gene, c->scalars.as<uint64_t>() + PDL_CTL_RANGES, c->N, c->seq_off.as<uint32_t>(), 0u, gene_mask);
+    PDL_HIP(hipGetLastError());
+}
+static uint32_t gene_id_bits(const pdl_ctx *c) { return std::max<uint32_t>(1, bit_length64(c->N ? c->N - 1 : 0)); }
+
+// Packed ranges, by gene: the sort of n_sort pairs (their count at d_sort_n, or n_sort itself; none: no sort) over the gene bits from first_bit on into
+// (k2b, pay_b), the genes' offsets, and the context's view: the join reads the ranges where the sort left them.  Ends EV_SORT2 (the caller's), spans EV_RANGES.
+static void sort_ranges_by_gene(pdl_ctx *c, RangeBufs b, uint64_t n_sort, const uint64_t *d_sort_n, uint32_t first_bit, uint32_t gene_mask) {
+    if (n_sort) pdl_sort_pairs<uint32_t, unsigned long long>(c, b.k2a, b.k2b, b.pay_a, b.pay_b, n_sort, gene_id_bits(c), false, d_sort_n, first_bit, true);
+    ev_end(c, EV_SORT2); ev_begin(c, EV_RANGES);
+    c->ranges8 = reinterpret_cast<const uint2 *>(b.pay_b); c->upper_only = true;
+    launch_seq_offsets(c, b.k2b, gene_mask);
+    ev_end(c, EV_RANGES);
+}
+
+// K-ranges of stage_ranges_and_costs: the range lists of `mode` from the postings of ga, gene major, by the plan.
+static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode) {
+    hipStream_t st = c->stream;
+    uint64_t *d_scal = c->scalars.as<uint64_t>();
+    const uint64_t bound = ga.n_bound, *d_us = d_scal + PDL_CTL_RANGES;       // d_us: ranges built = the total of the tile counts
+    const RangePlan plan = range_plan(c, mode);
+    ev_begin(c, EV_SORT2);
+    if (mode != 1) group_shard_args(c, ga);                // only the genes this context scores need range lists
+    RangeBufs b{};
+    uint64_t n_sort = bound;                               // what the kernels behind the passes are sized for: the bound, the count at d_sort_n ...
+    const uint64_t *d_sort_n = d_us;
+    uint32_t first_bit = 0;                                // (fused: the gene sort's first digit is done)
+    if (plan.exact) {                                      // ... or the count the host has read
+        n_sort = std::max<uint64_t>(count_then_write(c, ga, grid, mode, plan, true, b), 1); d_sort_n = nullptr;
+    } else {
+        b = carve_ranges(c, plan, bound);
+        set_write_targets(c, ga, b);
+        if (plan.fused) {
             const uint32_t n_tiles4 = (uint32_t) ((bound + PDL_RADIX_TILE - 1) / PDL_RADIX_TILE);
             const size_t table = (size_t) PDL_RADIX_BINS * n_tiles4, tiles = (bound + GW_TILE - 1) / GW_TILE;
             // (the scan below uses scan_tmp: the per-tile heads move next to the radix tables)
@@ -712,76 +775,66 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
             const uint32_t grid4 = std::max<uint32_t>(1, std::min<uint32_t>(n_tiles4, (uint32_t) c->cus * 8));
             hipLaunchKernelGGL(k_range_count_hist, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
             const uint32_t *totals = pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + PDL_CTL_RANGES, digit_total);
-            hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, k2b, pay_b, totals, d_scal + PDL_CTL_RANGES);
+            hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, b.k2b, b.pay_b, totals, d_scal + PDL_CTL_RANGES);
             PDL_HIP(hipGetLastError());
+            // pass 1 of the gene sort is done: (k2b, pay_b) hold its output, the remaining passes go on from there
+            std::swap(b.k2a, b.k2b); std::swap(b.pay_a, b.pay_b); first_bit = 8;
         } else {
-        launch_range_count(c, ga, grid, mode);
-        if (exact) {                         // the shard's range count, then buffers of that size
-            if (!c->tasks_ready) pdl_prepare_tasks(c);       // host work + small uploads while the device counts
-            PinRead rd(c);
-            const uint64_t *pn = rd.add<uint64_t>(d_us, 1);
-            rd.sync();
-            cap = std::max<uint64_t>(pn[0], 1);
-            carve();
+            launch_range_count(c, ga, grid, mode);
+            launch_range_write(c, ga, grid, mode);
         }
-        ga.key2 = k2a; ga.tuples = tuples; ga.pay8 = packed ? pay_a : nullptr;
-        launch_range_write(c, ga, grid, mode);
-        }
-        c->upper_only = mode != 0;
-        const uint32_t seq_bits = std::max<uint32_t>(1, bit_length64(c->N ? c->N - 1 : 0));
-        // One GPU: the range count stays on the device, the kernels behind it are sized for the bound.  Multi-GPU: a rank
-        // builds ranges for 1/world of the records, so it reads the count (one synchronisation) and sizes them exactly.
-        uint64_t n_sort = bound;
-        const uint64_t *d_sort_n = d_us;
-        if (exact) { n_sort = cap; d_sort_n = nullptr; }
-        c->seq_off.alloc(((size_t) c->N + 1) * sizeof(uint32_t));
-        if (packed) {
-            if (fused) {                     // pass 1 is done: (k2b, pay_b) hold its output, the remaining passes go on from there
-                std::swap(k2a, k2b); std::swap(pay_a, pay_b);
-                pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_sort, seq_bits, false, d_sort_n, 8, true);
-            } else
-            pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_sort, seq_bits, false, d_sort_n, 0, true);   // sorted pairs now in (k2b, pay_b)
-            ev_end(c, EV_SORT2);
-            ev_begin(c, EV_RANGES);
-            c->ranges8 = reinterpret_cast<const uint2 *>(pay_b);       // gene major: the join reads them where the sort left them
-            c->costs_ready = false;
-        } else {
-            pdl_sort_pairs<uint32_t>(c, k2a, k2b, v2a, v2b, n_sort, seq_bits, true, d_sort_n, 0, true);     // values = tuple positions; sorted pairs now in (k2b, v2b)
-            ev_end(c, EV_SORT2);
-            ev_begin(c, EV_RANGES);
-            c->ranges8 = nullptr;
-            c->ranges.alloc(std::max<uint64_t>(n_sort, 1) * sizeof(uint4));
-            const uint32_t gblocks = (uint32_t) std::max<uint64_t>((n_sort + 255) / 256, 1);
-            hipLaunchKernelGGL(k_gather_ranges, dim3(gblocks), dim3(256), 0, st, v2b, k2b, tuples, d_us, c->ranges.as<uint4>(), c->cost.as<unsigned long long>());
-        }
-        hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, st, k2b, d_us, c->N, c->seq_off.as<uint32_t>());
-        PDL_HIP(hipGetLastError());
+    }
+    if (plan.packed) {
+        sort_ranges_by_gene(c, b, n_sort, d_sort_n, first_bit, 0xffffffffu);
+    } else {                                               // values = tuple positions: sorted pairs in (k2b, v2b), the tuples fetched through them
+        pdl_sort_pairs<uint32_t>(c, b.k2a, b.k2b, b.v2a, b.v2b, n_sort, gene_id_bits(c), true, d_sort_n, 0, true);
+        ev_end(c, EV_SORT2); ev_begin(c, EV_RANGES);
+        c->ranges8 = nullptr; c->upper_only = mode != 0;
+        c->ranges.alloc(std::max<uint64_t>(n_sort, 1) * sizeof(uint4));
+        const uint32_t gblocks = (uint32_t) std::max<uint64_t>((n_sort + 255) / 256, 1);
+        hipLaunchKernelGGL(k_gather_ranges, dim3(gblocks), dim3(256), 0, st, b.v2b, b.k2b, b.tuples, d_us, c->ranges.as<uint4>(), c->cost.as<unsigned long long>());
+        launch_seq_offsets(c, b.k2b, 0xffffffffu);
         ev_end(c, EV_RANGES);
     }
+}
 
-    // K-cost
-    launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);
+// The closing read of a build: `words` of the control block from word 0 on and the look-back error word, which is checked.  Decodes
+// the k-mer statistics k_genome_cost added up: sum, max, and the min kept as a max of complements (still zero: no gene has a k-mer).
+static const uint64_t *closing_read(pdl_ctx *c, PinRead &rd, size_t words) {
+    const uint64_t *pt = rd.add<uint64_t>(c->scalars.as<uint64_t>(), words);
+    const uint32_t *lbe = lookback_error_word(c, rd);
+    rd.sync();
+    lookback_check(c, lbe);
+    c->sum_kseq = pt[PDL_CTL_KSEQ_SUM]; c->max_kseq = pt[PDL_CTL_KSEQ_MAX]; c->min_kseq = pt[PDL_CTL_KSEQ_NMIN] == 0 ? 1 : ~pt[PDL_CTL_KSEQ_NMIN];
+    return pt;
+}
 
-    uint64_t own_cost = 0;
-    {
-        PinRead rd(c);                       // one copy: the whole control block
-        const uint64_t *pt = rd.add<uint64_t>(d_scal, PDL_CTL_GCOST + (size_t) c->G);
-        const uint32_t *lbe = lookback_error_word(c, rd);
-        rd.sync();
-        lookback_check(c, lbe);
-        c->h_genome_cost.assign(pt + PDL_CTL_GCOST, pt + PDL_CTL_GCOST + c->G);     // (a shard, one rank of several: its own genomes only)
-        c->U = pt[PDL_CTL_RECORDS];
-        c->Ushared = pt[PDL_CTL_SHARED];
-        c->Urepeat = pt[PDL_CTL_REPEATS];
-        c->NG = pt[PDL_CTL_GROUPS];
-        c->sum_kseq = pt[PDL_CTL_KSEQ_SUM];
-        c->max_kseq = pt[PDL_CTL_KSEQ_MAX];
-        c->min_kseq = pt[PDL_CTL_KSEQ_NMIN] == 0 ? 1 : ~pt[PDL_CTL_KSEQ_NMIN];
-        own_cost = pt[PDL_CTL_OWN_COST];
-    }
-    c->P = 0;
+// Waits for the stream and closes the range stage's timings; returns the time of `total_event`, which spans the call.
+static float close_range_timings(pdl_ctx *c, int total_event) {
+    PDL_HIP(hipStreamSynchronize(c->stream));
+    c->tm.sort_seq_ms = ev_ms(c, EV_SORT2); c->tm.ranges_ms = ev_ms(c, EV_RANGES);
+    return ev_ms(c, total_event);
+}
+
+// K-groups + K-ranges + K-cost over the dictionary (postings with head bits; `bound` records at most, the count is at
+// scalars[PDL_CTL_RECORDS]): fold the last record; complexity-only costs, or the ranges of `mode`; genome costs; closing read.
+static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool only_complexity) {
+    uint64_t *d_scal = c->scalars.as<uint64_t>();
+    GroupPlan gp = group_tiles_plan(c, pdl_postings(c), bound, d_scal + PDL_CTL_RECORDS);
+    gp.a.cost = c->cost.as<unsigned long long>();
+    gp.a.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
+    hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, c->stream, gp.a.post, c->post_ext ? (uint32_t *) nullptr : c->recpos.as<uint32_t>(), gp.a.d_n);
+    if (only_complexity) { c->ranges8 = nullptr; launch_group_costs<false, true>(c, gp.a, gp.grid); }    // (cost[] was zeroed by K-len's apply, the counters with the control block)
+    else build_ranges(c, gp.a, gp.grid, mode);
+    // packed ranges: "Total cost" straight from the WRITE pass; per-gene / per-genome costs on demand (pdl_ensure_costs)
+    c->costs_ready = c->ranges8 == nullptr;
+    launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);       // K-cost
+    PinRead rd(c);                           // one copy: the whole control block
+    const uint64_t *pt = closing_read(c, rd, PDL_CTL_GCOST + (size_t) c->G);
+    c->h_genome_cost.assign(pt + PDL_CTL_GCOST, pt + PDL_CTL_GCOST + c->G);     // (a shard, one rank of several: its own genomes only)
+    c->U = pt[PDL_CTL_RECORDS]; c->Ushared = pt[PDL_CTL_SHARED]; c->Urepeat = pt[PDL_CTL_REPEATS]; c->NG = pt[PDL_CTL_GROUPS];
+    c->P = c->costs_ready ? 0 : pt[PDL_CTL_OWN_COST];
     if (c->costs_ready) for (uint64_t v : c->h_genome_cost) c->P += v;
-    else c->P = own_cost;                     // packed ranges: "Total cost" straight from the WRITE pass; per-gene / per-genome costs on demand
 }
 
 // ---- the ranges again, for another shard of genomes, on the dictionary that is there ---------------------------------------------
@@ -792,28 +845,23 @@ void pdl_run_reshard(pdl_ctx *c) {
     hipStream_t st = c->stream;
     if (c->dist || c->post_ext) PDL_FAIL(PDL_ERR_STATE, "genome shard: a multi-GPU context deals the genomes itself");
     if (c->dict_shard.empty() || c->upper_only) PDL_FAIL(PDL_ERR_STATE, "genome shard: the dictionary was built for all genomes; set the first shard before pdl_preprocess");
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
     const uint32_t n = (uint32_t) c->U;
     ev_begin(c, EV_PRE_TOTAL);
     hipLaunchKernelGGL(k_restore_heads, dim3((n + 255) / 256), dim3(256), 0, st, c->post.as<uint2>(), c->head_bits.as<unsigned long long>(), n);
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_RANGES, 0, sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_COUNTERS, 0, (PDL_CTL_LAST - PDL_CTL_COUNTERS + 1) * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), st));
+    clear_ctl(c, PDL_CTL_RANGES, PDL_CTL_RANGES);
+    clear_ctl(c, PDL_CTL_COUNTERS, PDL_CTL_LAST);
+    clear_genome_words(c);
+    clear_gene_costs(c);
     // (k_genome_cost adds the k-mer statistics of all genes up once more: they are taken from the first build)
     const uint64_t sum_kseq = c->sum_kseq, max_kseq = c->max_kseq, min_kseq = c->min_kseq;
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_SUM, 0, sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_MAX, 0, (PDL_CTL_KSEQ_NMIN - PDL_CTL_KSEQ_MAX + 1) * sizeof(uint64_t), st));
+    clear_kseq_stats(c);
     c->dict_shard = c->shard;
     c->tasks_ready = false;
     ev_begin(c, EV_DICT); ev_end(c, EV_DICT);
     stage_ranges_and_costs(c, c->U, 0, false);
     c->sum_kseq = sum_kseq; c->max_kseq = max_kseq; c->min_kseq = min_kseq;
     ev_end(c, EV_PRE_TOTAL);
-    PDL_HIP(hipStreamSynchronize(st));
-    c->tm.sort_seq_ms = ev_ms(c, EV_SORT2);
-    c->tm.ranges_ms = ev_ms(c, EV_RANGES);
-    c->tm.reshard_ms = ev_ms(c, EV_PRE_TOTAL);
+    c->tm.reshard_ms = close_range_timings(c, EV_PRE_TOTAL);
 }
 
 // cost[] (per gene) and h_genome_cost (per genome), when the build left them for later (packed ranges)
@@ -821,8 +869,8 @@ void pdl_ensure_costs(pdl_ctx *c) {
     if (c->costs_ready) return;
     hipStream_t st = c->stream;
     uint64_t *d_scal = c->scalars.as<uint64_t>();
-    PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, (size_t) c->G * sizeof(uint64_t), st));
+    clear_gene_costs(c);
+    clear_genome_words(c, false);
     const uint32_t n = (uint32_t) c->U;
     hipLaunchKernelGGL(k_gene_costs_lazy, dim3((n + 255) / 256), dim3(256), 0, st, pdl_postings(c), c->head_bits.as<unsigned long long>(), n,
                        c->cost.as<unsigned long long>());
@@ -1336,14 +1384,11 @@ static void dist_slice_pipeline(pdl_ctx *c) {
         // every genome's lookups inside this run (groups never straddle runs), as the reference counts them and above the
         // diagonal: summed over the ranks the former are "Genome g cost" (exact when the fold above was made), the latter the
         // weights of the genome deal
-        GroupTileArgs ga{};
-        ga.post = c->post.as<uint2>(); ga.n_bound = m_own; ga.d_n = d_scal + PDL_CTL_RECORDS;
-        const uint32_t grid = group_tiles_plan(c, ga);
-        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_SLICE_COUNTERS);      // (scratch words: the real counters come from the finish)
-        ga.genome_of = c->d_gen; ga.n_genomes = c->G;
-        ga.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);             // scratch here, cleared again by the finish
-        ga.g_upper = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST) + c->G;
-        launch_group_costs<true, false>(c, ga, grid);
+        GroupPlan gp = group_tiles_plan(c, c->post.as<uint2>(), m_own, d_scal + PDL_CTL_RECORDS);
+        gp.a.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_SLICE_COUNTERS);    // (scratch words: the real counters come from the finish)
+        gp.a.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);           // scratch here, cleared again by the finish
+        gp.a.g_upper = gp.a.g_full + c->G;
+        launch_group_costs<true, false>(c, gp.a, gp.grid);
         ev_end(c, EV_DICT);
     } else {
         c->post.alloc(16);
@@ -1397,67 +1442,76 @@ static void lpt_owner(const std::vector<uint64_t> &w, uint32_t world, std::vecto
     }
 }
 
-void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {
-    hipStream_t st = c->stream;
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    ev_begin(c, EV_DIST_FINISH);
-    if (total == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dictionary");
-    if (total >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a dictionary of %llu records needs 64-bit record indices", (unsigned long long) total);
-    // the record count of the whole dictionary goes where the kernels expect it (PDL_CTL_RECORDS); the other counters and the
-    // per-genome words restart
-    uint64_t *h_u = reinterpret_cast<uint64_t *>(c->pin);       // (pinned scratch; rewritten only by the next PinRead, which comes after a sync)
-    if (!h_u) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
-    h_u[0] = total;
-    PDL_HIP(hipMemcpyAsync(d_scal + PDL_CTL_RECORDS, h_u, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    // (BAD_OFFSETS .. KSEQ_NMIN belong to K-len and stay: bad-offsets flag, kseq sums, M)
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_FREE_1, 0, (PDL_CTL_RANGES - PDL_CTL_FREE_1 + 1) * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_MIRRORED, 0, (PDL_CTL_LAST - PDL_CTL_MIRRORED + 1) * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
-    // genomes -> ranks by longest-processing-time on each genome's lookups above the diagonal: the caller's sum of the
-    // runs' weights, or — without one — an exact pass over the gathered dictionary first
-    c->h_upper_cost.assign(c->G, 0);
-    if (weights) {
-        c->h_upper_cost.assign(weights, weights + c->G);
-    } else {
-        c->scratch2.alloc(std::max<size_t>(c->scratch2.bytes, ((size_t) c->G + 2) * sizeof(uint64_t)));
-        PDL_HIP(hipMemsetAsync(c->scratch2.p, 0, ((size_t) c->G + 2) * sizeof(uint64_t), st));
-        GroupTileArgs ga{};
-        ga.post = c->post_ext; ga.n_bound = total; ga.d_n = nullptr;
-        const uint32_t grid = group_tiles_plan(c, ga);
-        ga.counters = c->scratch2.as<unsigned long long>() + c->G;
-        ga.genome_of = c->d_gen; ga.n_genomes = c->G;
-        ga.g_upper = c->scratch2.as<unsigned long long>();
-        ga.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);       // (scratch: the K-cost words are cleared below)
-        // (the fold of the last record is not applied yet: as with the callers' weights, these numbers only balance)
-        launch_group_costs<true, false>(c, ga, grid);
-        {
-            PinRead rd(c);
-            const uint64_t *pu = rd.add<uint64_t>(ga.g_upper, c->G);
-            rd.sync();
-            c->h_upper_cost.assign(pu, pu + c->G);
-        }
-        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
-    }
+// genomes -> ranks by longest-processing-time on each genome's lookups above the diagonal (`weights`; nullptr: h_upper_cost
+// holds them already); the deal goes to the device
+static void dist_deal_genomes(pdl_ctx *c, const uint64_t *weights) {
+    if (weights) c->h_upper_cost.assign(weights, weights + c->G);
     lpt_owner(c->h_upper_cost, c->world, c->h_owner);
     c->shard.clear();
     for (uint32_t g = 0; g < c->G; g++) if (c->h_owner[g] == c->rank) c->shard.push_back(g);
     c->shard_set = true;
     c->dict_shard = c->shard;
-    c->tasks_ready = false;                 // (the task layout is prepared inside, behind the launches of the two passes)
+    c->tasks_ready = false;                 // (the task layout is prepared behind the launches of the two passes, or by the finish)
     c->owner_of_genome.alloc((size_t) c->G * 4);
-    PDL_HIP(hipMemcpyAsync(c->owner_of_genome.p, c->h_owner.data(), (size_t) c->G * 4, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(c->owner_of_genome.p, c->h_owner.data(), (size_t) c->G * 4, hipMemcpyHostToDevice, c->stream));
+}
+
+// what a gathered dictionary of `total` records is refused for
+static void check_dictionary_total(uint64_t total) {
+    if (total == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dictionary");
+    if (total >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a dictionary of %llu records needs 64-bit record indices", (unsigned long long) total);
+}
+
+// the pinned scratch a finish uploads control words from (rewritten only by the next PinRead, which comes after a sync)
+static uint64_t *pinned_words(pdl_ctx *c) {
+    if (!c->pin) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
+    return reinterpret_cast<uint64_t *>(c->pin);
+}
+
+// the tail of both finishes; ranges_ms: what the sender path spent between begin and finish
+static void dist_finish_tail(pdl_ctx *c, float ranges_ms) {
+    ev_end(c, EV_DIST_FINISH); ev_end(c, EV_PRE_TOTAL);
+    c->tm.dist_finish_ms = close_range_timings(c, EV_DIST_FINISH);
+    c->tm.preprocess_total_ms = c->tm.dist_begin_ms + ranges_ms + c->tm.dist_finish_ms;
+    c->dist_stage = 2;
+}
+
+void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {
+    hipStream_t st = c->stream;
+    uint64_t *d_scal = c->scalars.as<uint64_t>();
+    ev_begin(c, EV_DIST_FINISH);
+    check_dictionary_total(total);
+    // the record count of the whole dictionary goes where the kernels expect it (PDL_CTL_RECORDS); the other counters and the
+    // per-genome words restart
+    uint64_t *h_u = pinned_words(c); h_u[0] = total;
+    PDL_HIP(hipMemcpyAsync(d_scal + PDL_CTL_RECORDS, h_u, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // (BAD_OFFSETS .. KSEQ_NMIN belong to K-len and stay: bad-offsets flag, kseq sums, M)
+    clear_ctl(c, PDL_CTL_FREE_1, PDL_CTL_RANGES);
+    clear_ctl(c, PDL_CTL_MIRRORED, PDL_CTL_LAST);
+    clear_genome_words(c);
+    // the deal goes by the caller's sum of the runs' weights, or — without one — by an exact pass over the gathered dictionary first
+    c->h_upper_cost.assign(c->G, 0);
+    if (!weights) {
+        c->scratch2.alloc(std::max<size_t>(c->scratch2.bytes, ((size_t) c->G + 2) * sizeof(uint64_t)));
+        PDL_HIP(hipMemsetAsync(c->scratch2.p, 0, ((size_t) c->G + 2) * sizeof(uint64_t), st));
+        GroupPlan gp = group_tiles_plan(c, c->post_ext, total, nullptr);
+        gp.a.counters = c->scratch2.as<unsigned long long>() + c->G;
+        gp.a.g_upper = c->scratch2.as<unsigned long long>();
+        gp.a.g_full = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_GCOST);     // (scratch: the K-cost words are cleared below)
+        // (the fold of the last record is not applied yet: as with the callers' weights, these numbers only balance)
+        launch_group_costs<true, false>(c, gp.a, gp.grid);
+        PinRead rd(c);
+        const uint64_t *pu = rd.add<uint64_t>(gp.a.g_upper, c->G);
+        rd.sync();
+        c->h_upper_cost.assign(pu, pu + c->G);
+        clear_genome_words(c);
+    }
+    dist_deal_genomes(c, weights);
     c->seq_in_shard.alloc(c->N);
     hipLaunchKernelGGL(k_genes_of_rank, dim3((c->N + 255) / 256), dim3(256), 0, st, c->d_gen, c->owner_of_genome.as<uint32_t>(), c->rank, c->N,
                        c->seq_in_shard.as<uint8_t>());
     stage_ranges_and_costs(c, total, 2, false);
-    ev_end(c, EV_DIST_FINISH);
-    ev_end(c, EV_PRE_TOTAL);
-    PDL_HIP(hipStreamSynchronize(st));
-    c->tm.sort_seq_ms = ev_ms(c, EV_SORT2);
-    c->tm.ranges_ms = ev_ms(c, EV_RANGES);
-    c->tm.dist_finish_ms = ev_ms(c, EV_DIST_FINISH);
-    c->tm.preprocess_total_ms = c->tm.dist_begin_ms + c->tm.dist_finish_ms;
-    c->dist_stage = 2;
+    dist_finish_tail(c, 0.f);
 }
 
 // ---- sender-built range lists ----------------------------------------------------------------------------------------------------
@@ -1468,19 +1522,6 @@ void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {
 // (1/world of the records, no "is this gene mine" per record), files them by the rank that owns the gene (one stable radix
 // pass on the owner byte: record order survives, so a gene's ranges still arrive in (rank, gene) order when the sources are
 // concatenated in rank order), and the owners sort what they receive by gene.
-static void dist_deal_genomes(pdl_ctx *c, const uint64_t *weights) {
-    hipStream_t st = c->stream;
-    c->h_upper_cost.assign(weights, weights + c->G);
-    lpt_owner(c->h_upper_cost, c->world, c->h_owner);
-    c->shard.clear();
-    for (uint32_t g = 0; g < c->G; g++) if (c->h_owner[g] == c->rank) c->shard.push_back(g);
-    c->shard_set = true;
-    c->dict_shard = c->shard;
-    c->tasks_ready = false;
-    c->owner_of_genome.alloc((size_t) c->G * 4);
-    PDL_HIP(hipMemcpyAsync(c->owner_of_genome.p, c->h_owner.data(), (size_t) c->G * 4, hipMemcpyHostToDevice, st));
-}
-
 bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t *weights, const uint64_t *costs) {
     hipStream_t st = c->stream;
     uint64_t *d_scal = c->scalars.as<uint64_t>();
@@ -1489,8 +1530,7 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
     int tail = -1;
     for (uint32_t r = 0; r < W; r++) { if (r < me) base += run_records[r]; total += run_records[r]; if (run_records[r]) tail = (int) r; }
     if (run_records[me] != c->U_slice) PDL_FAIL(PDL_ERR_ARGUMENT, "run_records[%u] = %llu, this rank's run holds %llu records", me, (unsigned long long) run_records[me], (unsigned long long) c->U_slice);
-    if (total == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dictionary");
-    if (total >= 0xfffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a dictionary of %llu records needs 64-bit record indices", (unsigned long long) total);
+    check_dictionary_total(total);
     c->dist_total = total; c->run_base = base;
     c->h_tuple_counts.assign(W, 0);
     c->dist_out_keys = nullptr; c->dist_out_ranges = nullptr; c->dist_out_total = 0;
@@ -1507,37 +1547,21 @@ bool pdl_run_dist_ranges(pdl_ctx *c, const uint64_t *run_records, const uint64_t
     hipLaunchKernelGGL(k_gene_owner, dim3((c->N + 255) / 256), dim3(256), 0, st, c->d_gen, c->owner_of_genome.as<uint32_t>(), c->N, c->seq_owner.as<uint8_t>());
     const uint64_t n_run = c->U_slice;
     if (n_run) {
-        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_RANGES, 0, sizeof(uint64_t), st));
-        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_COUNTERS, 0, (PDL_CTL_REPEATS - PDL_CTL_COUNTERS + 1) * sizeof(uint64_t), st));
-        GroupTileArgs ga{};
-        ga.post = c->post.as<uint2>(); ga.n_bound = n_run; ga.d_n = d_scal + PDL_CTL_RECORDS;       // (the run's record count is still where K-rle left it)
-        const uint32_t grid = group_tiles_plan(c, ga);
-        ga.cost = c->cost.as<unsigned long long>();
-        ga.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
-        ga.genome_of = c->d_gen; ga.n_genomes = c->G;
-        launch_range_count(c, ga, grid, 1);
-        uint64_t n_t = 0;
-        {
-            PinRead rd(c);
-            const uint64_t *pn = rd.add<uint64_t>(d_scal + PDL_CTL_RANGES, 1);
-            rd.sync();
-            n_t = pn[0];
-        }
-        const uint64_t cap = std::max<uint64_t>(n_t, 1);
-        c->scratch.alloc(cap * (2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + 64);
-        unsigned long long *pay_a = c->scratch.as<unsigned long long>(), *pay_b = pay_a + cap;
-        uint32_t *k2a = reinterpret_cast<uint32_t *>(pay_b + cap), *k2b = k2a + cap;
-        c->head_bits.alloc(((n_run + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
-        ga.head_bits = c->head_bits.as<unsigned long long>();
-        ga.key2 = k2a; ga.tuples = nullptr; ga.pay8 = pay_a; ga.pos_base = (uint32_t) base;
-        launch_range_write(c, ga, grid, 1);
+        clear_ctl(c, PDL_CTL_RANGES, PDL_CTL_RANGES);
+        clear_ctl(c, PDL_CTL_COUNTERS, PDL_CTL_REPEATS);
+        GroupPlan gp = group_tiles_plan(c, c->post.as<uint2>(), n_run, d_scal + PDL_CTL_RECORDS);      // (the run's record count is still where K-rle left it)
+        gp.a.cost = c->cost.as<unsigned long long>();
+        gp.a.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
+        gp.a.pos_base = (uint32_t) base;
+        RangeBufs b{};
+        const uint64_t n_t = count_then_write(c, gp.a, gp.grid, 1, range_plan(c, 1, true), false, b);
         if (n_t) {
-            hipLaunchKernelGGL(k_owner_keys, dim3((uint32_t) std::min<uint64_t>((n_t + 255) / 256, (uint64_t) c->cus * 16)), dim3(256), 0, st, k2a, d_scal + PDL_CTL_RANGES, c->seq_owner.as<uint8_t>());
-            pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_t, 32, false, nullptr, 24, true);      // -> (k2b, pay_b), by destination
+            hipLaunchKernelGGL(k_owner_keys, dim3((uint32_t) std::min<uint64_t>((n_t + 255) / 256, (uint64_t) c->cus * 16)), dim3(256), 0, st, b.k2a, d_scal + PDL_CTL_RANGES, c->seq_owner.as<uint8_t>());
+            pdl_sort_pairs<uint32_t, unsigned long long>(c, b.k2a, b.k2b, b.pay_a, b.pay_b, n_t, 32, false, nullptr, 24, true);      // -> (k2b, pay_b), by destination
             c->tuple_off.alloc(((size_t) W + 1) * sizeof(uint32_t));
-            hipLaunchKernelGGL(k_seq_offsets, dim3((W + 1 + 255) / 256), dim3(256), 0, st, k2b, d_scal + PDL_CTL_RANGES, W, c->tuple_off.as<uint32_t>(), 24u, 0xffu);
+            hipLaunchKernelGGL(k_seq_offsets, dim3((W + 1 + 255) / 256), dim3(256), 0, st, b.k2b, d_scal + PDL_CTL_RANGES, W, c->tuple_off.as<uint32_t>(), 24u, 0xffu);
             PDL_HIP(hipGetLastError());
-            c->dist_out_keys = k2b; c->dist_out_ranges = pay_b; c->dist_out_total = n_t;
+            c->dist_out_keys = b.k2b; c->dist_out_ranges = b.pay_b; c->dist_out_total = n_t;
         }
         PinRead rd(c);
         const uint64_t *pc = rd.add<uint64_t>(d_scal + PDL_CTL_COUNTERS, PDL_CTL_REPEATS - PDL_CTL_COUNTERS + 1);
@@ -1568,7 +1592,7 @@ void pdl_run_dist_finish_ranges(pdl_ctx *c, uint64_t total, uint32_t *d_keys, un
         uint64_t own_genes = 0;
         for (uint32_t g : c->shard) own_genes += c->h_genome_row_off[g + 1] - c->h_genome_row_off[g];
         if (own_genes == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_preprocess_finish_ranges: %llu range tuples received by a rank that owns no gene", (unsigned long long) n_in);
-        PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_FREE_1, 0, sizeof(uint64_t), st));
+        clear_ctl(c, PDL_CTL_FREE_1, PDL_CTL_FREE_1);
         hipLaunchKernelGGL(k_tuple_check, dim3((uint32_t) ((n_in + 255) / 256)), dim3(256), 0, st, d_keys, d_ranges, (uint32_t) n_in, c->seq_owner.as<uint8_t>(), c->N,
                            c->rank, (uint32_t) total, d_scal + PDL_CTL_FREE_1);
         PDL_HIP(hipGetLastError());
@@ -1578,55 +1602,25 @@ void pdl_run_dist_finish_ranges(pdl_ctx *c, uint64_t total, uint32_t *d_keys, un
         if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_preprocess_finish_ranges: %llu of the %llu received range tuples do not name this rank and a gene of its genomes (%u genes), or reach past the %llu records of the dictionary; begin the build again (pdl_dist_preprocess_begin)",
                            (unsigned long long) *bad, (unsigned long long) n_in, c->N, (unsigned long long) total);
     }
-    uint64_t *h_u = reinterpret_cast<uint64_t *>(c->pin);       // (pinned scratch; rewritten only by the next PinRead, which comes after a sync)
-    if (!h_u) PDL_FAIL(PDL_ERR_DEVICE, "pinned scratch missing");
+    uint64_t *h_u = pinned_words(c);
     h_u[PDL_CTL_RECORDS] = total; h_u[PDL_CTL_FREE_1] = 0; h_u[PDL_CTL_RANGES] = n_in;
     PDL_HIP(hipMemcpyAsync(d_scal + PDL_CTL_RECORDS, h_u, (PDL_CTL_RANGES - PDL_CTL_RECORDS + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_SUM, 0, sizeof(uint64_t), st));          // (k_genome_cost adds the k-mer statistics up: sum, max, ~min)
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_KSEQ_MAX, 0, (PDL_CTL_KSEQ_NMIN - PDL_CTL_KSEQ_MAX + 1) * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_MIRRORED, 0, (PDL_CTL_LAST - PDL_CTL_MIRRORED + 1) * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(d_scal + PDL_CTL_GCOST, 0, 2 * (size_t) c->G * sizeof(uint64_t), st));
-    PDL_HIP(hipMemsetAsync(c->cost.p, 0, (size_t) c->N * sizeof(uint64_t), st));
+    clear_kseq_stats(c);
+    clear_ctl(c, PDL_CTL_MIRRORED, PDL_CTL_LAST);
+    clear_genome_words(c);
+    clear_gene_costs(c);
     ev_begin(c, EV_SORT2);
-    const uint32_t seq_bits = std::max<uint32_t>(1, bit_length64(c->N ? c->N - 1 : 0));
-    c->seq_off.alloc(((size_t) c->N + 1) * sizeof(uint32_t));
-    const uint64_t cap = std::max<uint64_t>(n_in, 1);
-    // (the outbox in `scratch` has been delivered: its memory takes the sort's second pair)
-    c->scratch.alloc(cap * (sizeof(uint64_t) + sizeof(uint32_t)) + 64);
-    unsigned long long *pay_a = d_ranges, *pay_b = c->scratch.as<unsigned long long>();
-    uint32_t *k2a = d_keys, *k2b = reinterpret_cast<uint32_t *>(pay_b + cap);
+    const RangeBufs b = carve_ranges(c, RANGES_RECEIVED, std::max<uint64_t>(n_in, 1), d_keys, d_ranges);
     c->dist_out_keys = nullptr; c->dist_out_ranges = nullptr; c->dist_out_total = 0;
-    if (n_in) pdl_sort_pairs<uint32_t, unsigned long long>(c, k2a, k2b, pay_a, pay_b, n_in, seq_bits, false, nullptr, 0, true);      // the gene bits only (gene ids have 22 bits at most: the owner byte lies above every digit)
-    else { k2b = k2a; pay_b = pay_a; }
-    ev_end(c, EV_SORT2);
-    ev_begin(c, EV_RANGES);
-    c->ranges8 = reinterpret_cast<const uint2 *>(n_in ? pay_b : c->scratch.as<unsigned long long>());
-    hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, st, n_in ? k2b : reinterpret_cast<uint32_t *>(c->scratch.p), d_scal + PDL_CTL_RANGES, c->N,
-                       c->seq_off.as<uint32_t>(), 0u, 0xffffffu);
-    PDL_HIP(hipGetLastError());
-    ev_end(c, EV_RANGES);
-    c->upper_only = true;
+    // the gene bits only (gene ids have 22 bits at most: the owner byte lies above every digit)
+    sort_ranges_by_gene(c, b, n_in, nullptr, 0, 0xffffffu);
     // the k-mer statistics of the genes (the per-gene costs are all zero here: what it adds up per genome is not used)
     launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);
     if (!c->tasks_ready) pdl_prepare_tasks(c);           // host work + small uploads while the device sorts
-    {
-        PinRead rd(c);
-        const uint64_t *pt = rd.add<uint64_t>(d_scal, PDL_CTL_KSEQ_NMIN + 1);
-        const uint32_t *lbe = lookback_error_word(c, rd);
-        rd.sync();
-        lookback_check(c, lbe);
-        c->sum_kseq = pt[PDL_CTL_KSEQ_SUM]; c->max_kseq = pt[PDL_CTL_KSEQ_MAX]; c->min_kseq = pt[PDL_CTL_KSEQ_NMIN] == 0 ? 1 : ~pt[PDL_CTL_KSEQ_NMIN];
-    }
+    { PinRead rd(c); closing_read(c, rd, PDL_CTL_KSEQ_NMIN + 1); }
     c->U = total; c->Ushared = sums[0]; c->NG = sums[1]; c->Urepeat = sums[2];
     c->P = 0;
     for (uint32_t g : c->shard) c->P += c->h_genome_cost[g];
     c->costs_ready = true;                   // per genome, from the runs' counts; per gene: not kept by this build (pdl_sequence_costs says so)
-    ev_end(c, EV_DIST_FINISH);
-    ev_end(c, EV_PRE_TOTAL);
-    PDL_HIP(hipStreamSynchronize(st));
-    c->tm.sort_seq_ms = ev_ms(c, EV_SORT2);
-    c->tm.ranges_ms = ev_ms(c, EV_RANGES);
-    c->tm.dist_finish_ms = ev_ms(c, EV_DIST_FINISH);
-    c->tm.preprocess_total_ms = c->tm.dist_begin_ms + c->tm.dist_ranges_ms + c->tm.dist_finish_ms;
-    c->dist_stage = 2;
+    dist_finish_tail(c, c->tm.dist_ranges_ms);
 }

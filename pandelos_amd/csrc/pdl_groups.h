@@ -607,17 +607,21 @@ __global__ __launch_bounds__(256) void k_tile_prefix(uint32_t *__restrict__ tile
 }
 
 // ---- launch helpers --------------------------------------------------------------------------------------------------------
-// group_tiles_plan sizes the grid and the scratch of the count / write pair: tile_sums[tiles] | th_first[tiles] |
-// th_last[tiles] | chunk_sums[blocks of 64 tiles].  Returns the number of workgroups.
-static uint32_t group_tiles_plan(pdl_ctx *c, GroupTileArgs &a) {
-    const uint64_t tiles = (a.n_bound + GW_TILE - 1) / GW_TILE;
-    if (tiles > 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "dictionary of %llu records exceeds the grid limit", (unsigned long long) a.n_bound);
-    const int cus = pdl_cus(c);
+// The planned arguments of a pass over `bound` postings at most (their count at d_n, or — nullptr — the bound itself) and its grid: the
+// scratch of the count / write pair (tile_sums[tiles] | th_first[tiles] | th_last[tiles] | chunk_sums[blocks of 64 tiles]) and the genome
+// of every gene.  What the callers differ by they set themselves: counters, cost, g_full / g_upper, pos_base, the shard.
+struct GroupPlan { GroupTileArgs a; uint32_t grid; };
+static GroupPlan group_tiles_plan(pdl_ctx *c, uint2 *post, uint64_t bound, const uint64_t *d_n) {
+    const uint64_t tiles = (bound + GW_TILE - 1) / GW_TILE;
+    if (tiles > 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "dictionary of %llu records exceeds the grid limit", (unsigned long long) bound);
+    GroupPlan p{}; GroupTileArgs &a = p.a;
+    a.post = post; a.n_bound = bound; a.d_n = d_n;
     a.n_blocks = (uint32_t) ((tiles + PDL_WAVE - 1) / PDL_WAVE);
-    const uint32_t grid = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((tiles + GW_WAVES - 1) / GW_WAVES, (uint64_t) cus * 8));
+    p.grid = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((tiles + GW_WAVES - 1) / GW_WAVES, (uint64_t) pdl_cus(c) * 8));
     c->scan_tmp.alloc(((size_t) tiles * 3 + a.n_blocks + 1) * sizeof(uint32_t));
     a.tile_sums = c->scan_tmp.as<uint32_t>(); a.th_first = a.tile_sums + tiles; a.th_last = a.th_first + tiles; a.chunk_sums = a.th_last + tiles;
-    return grid;
+    a.genome_of = c->d_gen; a.n_genomes = c->G;
+    return p;
 }
 template <bool GENOMES, bool RECORD_COSTS>
 static void launch_group_costs(pdl_ctx *c, const GroupTileArgs &a, uint32_t grid) {
