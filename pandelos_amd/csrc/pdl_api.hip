@@ -9,65 +9,9 @@
 
 static thread_local std::string g_create_error = "";
 
-// The one place where exceptions become return codes: runs an entry point's body (-> its return code); what the body throws is
-// translated and the message stored in the context (pdl_create's when there is none), after `undo` has freed and zeroed the
-// outputs a failure must not leave behind.  The caller holds the context's lock — or, with Lock::take, has let go of it and
-// the message is stored under it.
-enum class Lock { held, take };
-template <class Body, class Undo>
-static int guarded(pdl_ctx *c, Lock lock, Body &&body, Undo &&undo) {
-    int code = PDL_ERR_DEVICE;
-    std::string msg;
-    try { return body(); }
-    catch (const pdl_error &e) { code = e.code; msg = e.msg; }
-    catch (const std::bad_alloc &) { msg = "host allocation failed"; }
-    catch (const std::exception &e) { msg = e.what(); }
-    undo();
-    if (!c) g_create_error = msg;
-    else if (lock == Lock::take) { std::lock_guard<std::mutex> lk(c->mu); c->err = msg; }
-    else c->err = msg;
-    return code;
-}
-template <class Body> static int guarded(pdl_ctx *c, Body &&body) { return guarded(c, Lock::held, body, [] {}); }
+// Every entry point below has one shape: the NULL handles, the lock, then one `guarded` body (pdl_common.h) that opens with
+// require_state(c, E_...) — the table of which entry point needs which state, and the reset pdl_stale, are pdl_state.h's.
 
-// ---- the refusals the incremental entry points share ---------------------------------------------------------------------------
-// What an entry point needs of the context's state; which one needs what:
-//
-//   entry point             built   ranges   single-GPU   no shard   stream held
-//   pdl_query_scores         yes     yes        yes          -           yes
-//   pdl_query_batch          yes     yes        yes          -           yes
-//   pdl_place_query          yes     yes        yes         yes          yes
-//   pdl_place_batch          yes     yes        yes         yes          yes
-//   pdl_append_genomes       yes     yes        yes         yes          yes
-//   pdl_remove_genomes       yes     yes        yes         yes          yes
-//   pdl_compute_families     yes     yes        yes         yes           -
-//
-// (a query under a genome shard is scored against the whole dictionary; the families need the edges, not the stream)
-enum : unsigned {
-    NEEDS_BUILT = 1,         // pdl_preprocess has run
-    NEEDS_RANGES = 2,        // ... and not with only_complexity: the posting ranges exist
-    NEEDS_SINGLE_GPU = 4,    // not a multi-GPU context
-    NEEDS_NO_SHARD = 8,      // no genome shard in force: the context holds every genome's ranges and edges
-    NEEDS_STREAM = 16,       // the sorted k-mer stream is still held (low_memory releases it)
-    NEEDS_QUERY = NEEDS_BUILT | NEEDS_RANGES | NEEDS_SINGLE_GPU | NEEDS_STREAM,
-    NEEDS_WHOLE_SET = NEEDS_QUERY | NEEDS_NO_SHARD,
-};
-// Throws the PDL_ERR_STATE refusal of the first need the context does not meet; nothing of the context has been touched then.
-// `edge_form`: the entry point that does the same over gathered edges, where there is one to point to.
-static void require_state(const pdl_ctx *c, const char *who, unsigned needs, const char *edge_form = nullptr) {
-    if ((needs & NEEDS_BUILT) && !c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "%s before pdl_preprocess", who);
-    if ((needs & NEEDS_RANGES) && c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "%s: the context was preprocessed with only_complexity", who);
-    if ((needs & NEEDS_SINGLE_GPU) && c->dist) {
-        if (edge_form) PDL_FAIL(PDL_ERR_STATE, "%s: not available on a multi-GPU context (gather the edges: %s)", who, edge_form);
-        PDL_FAIL(PDL_ERR_STATE, "%s: not available on a multi-GPU context", who);
-    }
-    if ((needs & NEEDS_NO_SHARD) && (c->shard_set || !c->dict_shard.empty())) {
-        if (edge_form) PDL_FAIL(PDL_ERR_STATE, "%s: a genome shard is in force, the context does not hold every genome's edges (gather them: %s)", who, edge_form);
-        PDL_FAIL(PDL_ERR_STATE, "%s: not available with a genome shard in force", who);
-    }
-    if ((needs & NEEDS_STREAM) && (!c->keys_b.p || !c->recpos.p || !c->vals_b.p))
-        PDL_FAIL(PDL_ERR_STATE, "%s: the sorted k-mer stream was released (option low_memory)", who);
-}
 // The argument checks on n new genes (residues, offsets [n + 1]): PDL_ERR_ARGUMENT
 static void check_genes(const char *who, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
     if (!offsets) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
@@ -125,7 +69,7 @@ uint32_t pdl_pin_checksum(const uint32_t *payload, const uint32_t *dst_word, con
 
 pdl_ctx *pdl_create(const pdl_config *cfg) {
     pdl_ctx *c = nullptr;
-    try {
+    guarded(nullptr, Lock::held, [&]() -> int {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         if (e != hipSuccess || ndev == 0)
@@ -146,12 +90,9 @@ pdl_ctx *pdl_create(const pdl_config *cfg) {
             if (hipHostGetDevicePointer(&dp, c->pin, 0) == hipSuccess && dp) c->pin_dev = static_cast<uint8_t *>(dp);
             else (void) hipGetLastError();
         } else { c->pin = nullptr; (void) hipGetLastError(); }
-        return c;
-    } catch (const pdl_error &e) {
-        g_create_error = e.msg;
-        delete c;
-        return nullptr;
-    }
+        return PDL_OK;
+    }, [&] { delete c; c = nullptr; });
+    return c;
 }
 
 void pdl_destroy(pdl_ctx *c) {
@@ -213,12 +154,16 @@ static void layout_and_shard(pdl_ctx *c) {
 }
 
 }  // extern "C"   (C++ helpers of the other translation units)
+// the two ends of device-resident offsets against n_res (a wrong n_res would make the ranking kernels read past the residues;
+// ascending order is checked by K-len)
+static void check_span(const uint64_t ends[2], uint64_t n_res) {
+    if (ends[0] != 0 || ends[1] != n_res)
+        PDL_FAIL(PDL_ERR_ARGUMENT, "offsets[0] = %llu, offsets[n] = %llu do not span the %llu residues", (unsigned long long) ends[0],
+                 (unsigned long long) ends[1], (unsigned long long) n_res);
+}
 void pdl_input_arrived(pdl_ctx *c) {
     PDL_HIP(hipEventSynchronize(c->ev_gen));
-    const uint64_t *ends = reinterpret_cast<const uint64_t *>(c->gen_pin + ((c->N + 1) & ~1u));
-    if (ends[0] != 0 || ends[1] != c->R)
-        PDL_FAIL(PDL_ERR_ARGUMENT, "offsets[0] = %llu, offsets[n] = %llu do not span the %llu residues", (unsigned long long) ends[0],
-                 (unsigned long long) ends[1], (unsigned long long) c->R);
+    check_span(reinterpret_cast<const uint64_t *>(c->gen_pin + ((c->N + 1) & ~1u)), c->R);
 }
 void pdl_finish_layout(pdl_ctx *c) {
     c->h_genome_of.assign(c->gen_pin, c->gen_pin + c->N);
@@ -237,31 +182,27 @@ void pdl_replace_layout(pdl_ctx *c, std::vector<uint32_t> &&genome_of) {
     layout_and_shard(c);
 }
 
-int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
-    return guarded(c, [&]() -> int {
-    PDL_HIP(hipSetDevice(c->device));
-    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;      // the genome shard, if one was set, stays in force
-    pdl_renew(c->qb); pdl_renew(c->qbb); pdl_renew(c->pb);
+// What every build checks of its sizes, behind pdl_stale(Stale::set): a build refused here leaves a context that refuses every
+// reader.  (The genome shard, if one was set, stays in force.)
+static void begin_build(pdl_ctx *c, uint32_t n, uint64_t n_res, int k) {
     c->N = n; c->R = n_res;
-    c->U = c->Ushared = c->NG = c->P = c->M = 0;
     if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
     if (n == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dataset");
-    if (c->dist) { c->shard.clear(); c->shard_set = false; c->dist = false; c->dist_stage = 0; }    // (a multi-GPU build's own deal does not carry over)
+}
+// The common part of the single-GPU builds, behind the adopted input (d_res, d_off, d_gen; h_genome_of or the deferred layout)
+void pdl_build(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_stale(c, Stale::set);
+    begin_build(c, n, n_res, k);
     if (!c->layout_deferred) layout_and_shard(c);        // (device input: done behind the first kernels, pdl_finish_layout)
     pdl_run_preprocess(c, k, only_complexity != 0);
     c->preprocessed = true;
     fill_cost(c, out_cost);
-    return PDL_OK;
-    });
-}
-static int preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
-    return pdl_preprocess_common(c, n, n_res, k, only_complexity, out_cost);
 }
 
 extern "C" {
 
-// device-resident input: genome ids come to the host (task layout), and the two ends of the offsets are checked against
-// n_res (a wrong n_res would make the ranking kernels read past the residues; ascending order is checked by K-len)
+// device-resident input: genome ids come to the host (task layout), and the two ends of the offsets are checked against n_res
 static void adopt_device_input(pdl_ctx *c, const uint8_t *d_residues, const uint64_t *d_offsets, const uint32_t *d_genome_of,
                                uint32_t n, uint64_t n_res) {
     c->d_res = d_residues; c->d_off = d_offsets; c->d_gen = d_genome_of;
@@ -273,16 +214,14 @@ static void adopt_device_input(pdl_ctx *c, const uint8_t *d_residues, const uint
         PDL_HIP(hipMemcpyAsync(&ends[1], d_offsets + n, 8, hipMemcpyDeviceToHost, c->stream));
     }
     PDL_HIP(hipStreamSynchronize(c->stream));
-    if (ends[0] != 0 || ends[1] != n_res)
-        PDL_FAIL(PDL_ERR_ARGUMENT, "offsets[0] = %llu, offsets[n] = %llu do not span the %llu residues", (unsigned long long) ends[0],
-                 (unsigned long long) ends[1], (unsigned long long) n_res);
+    check_span(ends, n_res);
 }
 
 int pdl_preprocess(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *genome_of,
                    uint32_t n, int k, int only_complexity, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    const int rc = guarded(c, [&]() -> int {
+    return guarded(c, [&]() -> int {
     if (!offsets || !genome_of || (!residues && n && offsets[n] > 0)) PDL_FAIL(PDL_ERR_ARGUMENT, "null input pointer");
     PDL_HIP(hipSetDevice(c->device));
     const uint64_t n_res = n ? offsets[n] - offsets[0] : 0;
@@ -294,17 +233,16 @@ int pdl_preprocess(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     c->d_res = c->in_res.as<uint8_t>(); c->d_off = c->in_off.as<uint64_t>(); c->d_gen = c->in_gen.as<uint32_t>();
     c->h_genome_of.assign(genome_of, genome_of + n);
     PDL_HIP(hipStreamSynchronize(c->stream));
+    pdl_build(c, n, n_res, k, only_complexity, out_cost);
     return PDL_OK;
     });
-    if (rc != PDL_OK) return rc;
-    return preprocess_common(c, n, n ? offsets[n] : 0, k, only_complexity, out_cost);
 }
 
 int pdl_preprocess_device(pdl_ctx *c, const uint8_t *d_residues, const uint64_t *d_offsets, const uint32_t *d_genome_of,
                           uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = guarded(c, [&]() -> int {
+    const int rc = guarded(c, [&]() -> int {
     if (!d_offsets || !d_genome_of || (!d_residues && n_res)) PDL_FAIL(PDL_ERR_ARGUMENT, "null input pointer");
     if (((uintptr_t) d_residues & 15) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "d_residues must be 16-byte aligned");
     PDL_HIP(hipSetDevice(c->device));
@@ -338,11 +276,10 @@ int pdl_preprocess_device(pdl_ctx *c, const uint8_t *d_residues, const uint64_t 
         PDL_HIP(hipEventRecord(c->ev_gen, c->copy_stream));
         c->layout_deferred = true;
     }
+    pdl_build(c, n, n_res, k, only_complexity, out_cost);
     return PDL_OK;
     });
-    if (rc != PDL_OK) return rc;
-    rc = preprocess_common(c, n, n_res, k, only_complexity, out_cost);
-    c->layout_deferred = false;
+    c->layout_deferred = false;         // (whatever the call's end)
     return rc;
 }
 
@@ -350,9 +287,9 @@ int pdl_genome_cost(const pdl_ctx *cc, uint32_t genome, uint64_t *out) {
     pdl_ctx *c = const_cast<pdl_ctx *>(cc);
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->preprocessed) return PDL_ERR_STATE;
-    if (genome >= c->G) return PDL_ERR_ARGUMENT;
     return guarded(c, [&]() -> int {
+    require_state(c, E_GENOME_COST);
+    if (genome >= c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_genome_cost: genome %u out of range (%u genomes)", genome, c->G);
     if (!c->costs_ready) {                       // (packed ranges: the per-gene / per-genome lookups are made on first request)
         PDL_HIP(hipSetDevice(c->device));
         pdl_ensure_costs(c);
@@ -366,9 +303,8 @@ int pdl_sequence_costs(const pdl_ctx *cc, uint64_t *out_cost, uint32_t *out_kseq
     pdl_ctx *c = const_cast<pdl_ctx *>(cc);
     if (!c || !out_cost) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->preprocessed) return PDL_ERR_STATE;
     return guarded(c, [&]() -> int {
-    if (c->dist && c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "per-gene costs are not kept by a multi-GPU build whose range lists came from the senders (pdl_genome_cost works)");
+    require_state(c, E_SEQUENCE_COSTS);
     PDL_HIP(hipSetDevice(c->device));
     pdl_ensure_costs(c);
     PDL_HIP(hipMemcpyAsync(out_cost, c->cost.p, (size_t) c->N * 8, hipMemcpyDeviceToHost, c->stream));
@@ -381,65 +317,66 @@ int pdl_sequence_costs(const pdl_ctx *cc, uint64_t *out_cost, uint32_t *out_kseq
 int pdl_set_genome_shard(pdl_ctx *c, const uint32_t *genomes, uint32_t count) {
     if (!c || (!genomes && count)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->dist && c->dist_stage) { c->err = "genome shard: a multi-GPU build deals the genomes itself (pdl_dist_genome_owner)"; return PDL_ERR_STATE; }
+    return guarded(c, [&]() -> int {
+    require_state(c, E_SET_GENOME_SHARD);
     std::vector<uint32_t> s(genomes, genomes + count);
     std::sort(s.begin(), s.end());
-    for (size_t i = 0; i < s.size(); i++) {
-        if ((c->preprocessed && s[i] >= c->G) || (i && s[i] == s[i - 1])) { c->err = "genome shard: id out of range or repeated"; return PDL_ERR_ARGUMENT; }
-    }
-    if (c->preprocessed && c->upper_only && count != 0 && s.size() != c->G) {
-        // without a shard the ranges hold only the genes above each row and every cell is produced once for both
-        // rows; scoring a subset needs the full ranges of a shard-aware build
-        c->err = "genome shard: set it before pdl_preprocess (the dictionary on the device was built for all genomes)";
-        return PDL_ERR_STATE;
-    }
+    for (size_t i = 0; i < s.size(); i++)
+        if ((c->preprocessed && s[i] >= c->G) || (i && s[i] == s[i - 1])) PDL_FAIL(PDL_ERR_ARGUMENT, "genome shard: id out of range or repeated");
+    // without a shard the ranges hold only the genes above each row and every cell is produced once for both
+    // rows; scoring a subset needs the full ranges of a shard-aware build
+    if (c->preprocessed && c->upper_only && count != 0 && s.size() != c->G)
+        PDL_FAIL(PDL_ERR_STATE, "genome shard: set it before pdl_preprocess (the dictionary on the device was built for all genomes)");
     bool rebuild = false;
     if (c->preprocessed && !c->dict_shard.empty()) {
         // the dictionary on the device only has range lists for the genes of dict_shard: another shard gets its own before the next
         // scoring pass (the postings stay: two passes over them, pdl_run_reshard) — how a large set is scored a batch of genomes at a time
-        if (count == 0) { c->err = "genome shard: the dictionary was built for a shard; run pdl_preprocess again to widen it to all genomes"; return PDL_ERR_STATE; }
+        if (count == 0) PDL_FAIL(PDL_ERR_STATE, "genome shard: the dictionary was built for a shard; run pdl_preprocess again to widen it to all genomes");
         for (uint32_t g : s)
             if (!std::binary_search(c->dict_shard.begin(), c->dict_shard.end(), g)) rebuild = true;
-        if (rebuild && (c->only_complexity || !c->head_bits.p)) { c->err = "genome shard: not a subset of the shard the dictionary was built for; run pdl_preprocess again"; return PDL_ERR_STATE; }
+        if (rebuild && (c->only_complexity || !c->head_bits.p)) PDL_FAIL(PDL_ERR_STATE, "genome shard: not a subset of the shard the dictionary was built for; run pdl_preprocess again");
     }
     c->reshard_pending = c->reshard_pending || rebuild;
     c->shard = std::move(s);
     c->shard_set = count != 0;
-    c->scored = false;
-    c->tasks_ready = false;
-    return PDL_OK;
-}
-
-static int score_all_locked(pdl_ctx *c) {
-    return guarded(c, [&]() -> int {
-    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_score_all before pdl_preprocess");
-    if (c->only_complexity) PDL_FAIL(PDL_ERR_STATE, "the dictionary was built in complexity-only mode (no posting ranges)");
-    if (c->scored) return PDL_OK;
-    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "multi-GPU context: score with pdl_dist_score_begin / pdl_dist_score_finish");
-    PDL_HIP(hipSetDevice(c->device));
-    c->mirror_valid = false; c->edges_valid = false;
-    if (c->reshard_pending) { pdl_run_reshard(c); c->reshard_pending = false; }
-    pdl_run_score_all(c);
+    pdl_stale(c, Stale::scores_and_tasks);
     return PDL_OK;
     });
+}
+
+// The scoring pass, unless the context is scored (the caller holds the lock and a guard)
+static void score_all_locked(pdl_ctx *c) {
+    if (c->scored) return;
+    require_state(c, E_SCORE);
+    PDL_HIP(hipSetDevice(c->device));
+    pdl_stale(c, Stale::scores);
+    if (c->reshard_pending) { pdl_run_reshard(c); c->reshard_pending = false; }
+    pdl_run_score_all(c);
+}
+// ... and `genome` is one of this context's
+static void scored_and_mine(pdl_ctx *c, uint32_t genome) {
+    score_all_locked(c);
+    if (genome >= c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u out of range (%u genomes)", genome, c->G);
+    if (c->h_local_genome[genome] < 0) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u is not in this context's shard", genome);
 }
 
 int pdl_score_all(pdl_ctx *c) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    return score_all_locked(c);
+    return guarded(c, [&]() -> int { score_all_locked(c); return PDL_OK; });
 }
 
 int pdl_scores_counts(pdl_ctx *c, uint32_t *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = score_all_locked(c);
-    if (rc != PDL_OK) return rc;
+    return guarded(c, [&]() -> int {
+    score_all_locked(c);
     for (uint32_t g = 0; g < c->G; g++) {
         int32_t lg = c->h_local_genome[g];
         out[g] = lg < 0 ? 0u : (uint32_t) (c->h_cell_off[lg + 1] - c->h_cell_off[lg]);
     }
     return PDL_OK;
+    });
 }
 
 void pdl_free_scores(pdl_scores *s) {
@@ -512,10 +449,7 @@ int pdl_compute_scores(pdl_ctx *c, uint32_t genome, pdl_scores *out) {
         // The lock covers the scoring pass (first call) and the one-time fill of the host mirror; slicing a genome's block
         // out of either the mirror or the device arrays runs without it, so the pool's threads do not serialise.
         std::lock_guard<std::mutex> lk(c->mu);
-        int rc = c->scored ? PDL_OK : score_all_locked(c);
-        if (rc != PDL_OK) return rc;
-        if (genome >= c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u out of range (%u genomes)", genome, c->G);
-        if (c->h_local_genome[genome] < 0) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u is not in this context's shard", genome);
+        scored_and_mine(c, genome);
         // Results up to PDL_MIRROR_LIMIT come to the host once, into pinned memory, with one copy per array; the per-genome
         // calls (the reference's thread pool makes G of them, Pangenes.java:54-66) then only slice that mirror.
         const uint64_t Zall = c->h_cell_off.back();
@@ -597,10 +531,7 @@ int pdl_compute_edges(pdl_ctx *c, uint32_t genome, pdl_edges *out) {
     return guarded(c, Lock::take, [&]() -> int {
     {
         std::lock_guard<std::mutex> lk(c->mu);      // the scoring pass / the filter run once; slicing needs no lock
-        int rc = c->scored ? PDL_OK : score_all_locked(c);
-        if (rc != PDL_OK) return rc;
-        if (genome >= c->G) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u out of range (%u genomes)", genome, c->G);
-        if (c->h_local_genome[genome] < 0) PDL_FAIL(PDL_ERR_ARGUMENT, "genome %u is not in this context's shard", genome);
+        scored_and_mine(c, genome);
         if (!c->edges_valid) {
             PDL_HIP(hipSetDevice(c->device));
             pdl_run_bbh_all(c);
@@ -644,17 +575,21 @@ static void fill_families(const pdl_fam_result &r, pdl_families *out) {
     if (!r.collides.empty()) memcpy(out->collides, r.collides.data(), r.collides.size());
 }
 
+// the context's families, computed on first use: scored, then the edges, then the families (the device is the context's then)
+static void families_ready_locked(pdl_ctx *c) {
+    score_all_locked(c);
+    PDL_HIP(hipSetDevice(c->device));
+    if (!c->edges_valid) pdl_run_bbh_all(c);
+    if (!c->fam_valid) pdl_run_families_of_context(c);
+}
+
 int pdl_compute_families(pdl_ctx *c, pdl_families *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     memset(out, 0, sizeof(*out));
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, Lock::held, [&]() -> int {
-        require_state(c, "pdl_compute_families", NEEDS_WHOLE_SET & ~NEEDS_STREAM, "pdl_families_of_edges");
-        int rc = c->scored ? PDL_OK : score_all_locked(c);
-        if (rc != PDL_OK) return rc;
-        PDL_HIP(hipSetDevice(c->device));
-        if (!c->edges_valid) pdl_run_bbh_all(c);
-        if (!c->fam_valid) pdl_run_families_of_context(c);
+        require_state(c, E_COMPUTE_FAMILIES);
+        families_ready_locked(c);
         fill_families(c->fam, out);
         return PDL_OK;
     }, [&] { c->fam_valid = false; pdl_free_families(out); });      // (the families are made again by the next call: it costs a run, never an answer)
@@ -711,27 +646,16 @@ static void fill_placement(pdl_place_result &r, bool with_edges, pdl_placement *
     out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
 }
 
-// the context's families, computed on first use as by pdl_compute_families (-> a return code; the device is the context's then)
-static int families_ready_locked(pdl_ctx *c) {
-    const int rc = c->scored ? PDL_OK : score_all_locked(c);
-    if (rc != PDL_OK) return rc;
-    PDL_HIP(hipSetDevice(c->device));
-    if (!c->edges_valid) pdl_run_bbh_all(c);
-    if (!c->fam_valid) pdl_run_families_of_context(c);
-    return PDL_OK;
-}
-
 int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_placement *out, pdl_query_info *info) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     if (out) memset(out, 0, sizeof(*out));
     if (info) memset(info, 0, sizeof(*info));
     return guarded(c, Lock::held, [&]() -> int {
-        require_state(c, "pdl_place_query", NEEDS_WHOLE_SET, "pdl_placement_of_edges");
+        require_state(c, E_PLACE_QUERY);
         if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_place_query: NULL pointer");
         check_genes("pdl_place_query", residues, offsets, n_query);
-        int rc = families_ready_locked(c);
-        if (rc != PDL_OK) return rc;
+        families_ready_locked(c);
         pdl_place_result r;
         pdl_query_info qi{};
         pdl_run_place_query(c, residues, offsets, n_query, r, &qi);
@@ -832,10 +756,9 @@ int pdl_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
     if (binfo) memset(binfo, 0, sizeof(*binfo));
     return guarded(c, Lock::held, [&]() -> int {
-        require_state(c, "pdl_place_batch", NEEDS_WHOLE_SET, "pdl_placement_batch_of_edges");
+        require_state(c, E_PLACE_BATCH);
         check_batch(c, "pdl_place_batch", out, residues, offsets, gene_begin, n, n_queries);
-        int rc = families_ready_locked(c);
-        if (rc != PDL_OK) return rc;
+        families_ready_locked(c);
         std::vector<pdl_place_result> r;
         std::vector<pdl_query_info> qi(n_queries);
         uint32_t chunks = 0;
@@ -885,13 +808,14 @@ int pdl_placement_batch_of_edges(pdl_ctx *c, const pdl_families *base, const uin
 int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, [&]() -> int {
     const std::string n(name);
     if (n == "join_tier1") {
-        if (!(value == -1 || value == 0 || (value >= 9 && value <= 11) || value == 20 || value == 21)) { c->err = "join_tier1: -1, 0, 9, 10, 11, 20 or 21"; return PDL_ERR_ARGUMENT; }
+        if (!(value == -1 || value == 0 || (value >= 9 && value <= 11) || value == 20 || value == 21)) PDL_FAIL(PDL_ERR_ARGUMENT, "join_tier1: -1, 0, 9, 10, 11, 20 or 21");
         c->opt_tier1 = (int) value;
     } else if (n == "join_tier0") c->opt_tier0 = value < 0 ? -1 : (value != 0);
     else if (n == "sift_threshold") {
-        if (value != 0 && value != 1) { c->err = "sift_threshold: 0 or 1"; return PDL_ERR_ARGUMENT; }
+        if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "sift_threshold: 0 or 1");
         c->opt_sift_threshold = (int) value;
     }
     else if (n == "join_tiny_tier2") c->opt_tiny_tier2 = value != 0;
@@ -904,18 +828,19 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     else if (n == "lean_radix") c->opt_lean_radix = value != 0;
     else if (n == "low_memory") c->opt_low_memory = value != 0;
     else if (n == "query_batch_bytes") {
-        if (value <= 0) { c->err = "query_batch_bytes: a positive byte count"; return PDL_ERR_ARGUMENT; }
+        if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "query_batch_bytes: a positive byte count");
         c->opt_query_batch_bytes = (uint64_t) value;
         return PDL_OK;        // (no bearing on a scoring pass: the context's scores stay)
     }
     else if (n == "alphabet_rekey") {
-        if (value != 0 && value != 1) { c->err = "alphabet_rekey: 0 or 1"; return PDL_ERR_ARGUMENT; }
+        if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "alphabet_rekey: 0 or 1");
         c->opt_alphabet_rekey = value != 0;
         return PDL_OK;        // (nor has this one)
     }
-    else { c->err = "unknown option " + n; return PDL_ERR_ARGUMENT; }
-    c->scored = false;        // the next scoring call runs with the new setting
+    else throw pdl_error{PDL_ERR_ARGUMENT, "unknown option " + n};
+    pdl_stale(c, Stale::scores);        // the next scoring call runs with the new setting
     return PDL_OK;
+    });
 }
 
 // ---- multi-GPU (see include/pandelos_amd.h) -------------------------------------------------------------------------
@@ -928,13 +853,9 @@ int pdl_dist_preprocess_begin(pdl_ctx *c, const uint8_t *d_residues, const uint6
     if (((uintptr_t) d_residues & 15) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "d_residues must be 16-byte aligned");
     if (world == 0 || rank >= world || world > 64) PDL_FAIL(PDL_ERR_ARGUMENT, "rank %u of %u (at most 64 ranks)", rank, world);
     PDL_HIP(hipSetDevice(c->device));
-    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->mirror_valid = false;
-    c->dist = false; c->dist_stage = 0;
+    pdl_stale(c, Stale::set);
     adopt_device_input(c, d_residues, d_offsets, d_genome_of, n, n_res);
-    c->N = n; c->R = n_res;
-    c->U = c->Ushared = c->NG = c->P = c->M = 0;
-    if (k <= 0) PDL_FAIL(PDL_ERR_KVALUE, "K value must be greater than 0.");
-    if (n == 0) PDL_FAIL(PDL_ERR_EMPTY, "empty dataset");
+    begin_build(c, n, n_res, k);
     build_genome_layout(c);
     c->world = world; c->rank = rank;
     c->shard.clear(); c->shard_set = false; c->dict_shard.clear();
@@ -950,8 +871,7 @@ int pdl_dist_preprocess_finish(pdl_ctx *c, void *d_postings_all, uint64_t total_
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish without pdl_dist_preprocess_begin");
-    if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish after a pdl_dist_preprocess_ranges that built this run's range tuples (and took its group-head bits out): finish with pdl_dist_preprocess_finish_ranges");
+    require_state(c, E_DIST_FINISH);
     if (!d_postings_all || ((uintptr_t) d_postings_all & 7) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary must be an 8-byte aligned device array");
     if (total_records < c->U_slice) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary (%llu records) is smaller than this rank's run (%llu)",
                                              (unsigned long long) total_records, (unsigned long long) c->U_slice);
@@ -968,9 +888,7 @@ int pdl_dist_preprocess_ranges(pdl_ctx *c, const uint64_t *run_records, const ui
     if (!c || !out || !run_records || !genome_weights || !genome_costs) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->dist || c->dist_stage != 1) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges without pdl_dist_preprocess_begin");
-    // (a second pass would count ranges on a run without heads: wrong tuples and counters, and nothing to show for it)
-    if (c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_ranges has built this run's range tuples already (and took its group-head bits out): go on with pdl_dist_preprocess_finish_ranges");
+    require_state(c, E_DIST_RANGES);
     PDL_HIP(hipSetDevice(c->device));
     memset(out, 0, sizeof(*out));
     out->available = pdl_run_dist_ranges(c, run_records, genome_weights, genome_costs) ? 1 : 0;
@@ -986,7 +904,7 @@ int pdl_dist_preprocess_finish_ranges(pdl_ctx *c, void *d_postings_all, uint64_t
     if (!c || !counter_sums || ((!d_keys || !d_ranges) && n_tuples)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->dist || c->dist_stage != 1 || !c->dist_sender) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_preprocess_finish_ranges without a pdl_dist_preprocess_ranges that said \"available\"");
+    require_state(c, E_DIST_FINISH_RANGES);
     if (!d_postings_all || ((uintptr_t) d_postings_all & 7) != 0) PDL_FAIL(PDL_ERR_ARGUMENT, "the gathered dictionary must be an 8-byte aligned device array");
     if (n_tuples && ((((uintptr_t) d_keys) & 3) != 0 || (((uintptr_t) d_ranges) & 7) != 0)) PDL_FAIL(PDL_ERR_ARGUMENT, "the received tuples must be aligned device arrays");
     PDL_HIP(hipSetDevice(c->device));
@@ -1002,18 +920,21 @@ int pdl_dist_genome_owner(const pdl_ctx *cc, uint32_t *out) {
     pdl_ctx *c = const_cast<pdl_ctx *>(cc);
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->dist || c->dist_stage < 2) { c->err = "pdl_dist_genome_owner before pdl_dist_preprocess_finish: the genomes have not been dealt"; return PDL_ERR_STATE; }
+    return guarded(c, [&]() -> int {
+    require_state(c, E_DIST_GENOME_OWNER);
     memcpy(out, c->h_owner.data(), (size_t) c->G * 4);
     return PDL_OK;
+    });
 }
 
 int pdl_dist_score_begin(pdl_ctx *c, pdl_dist_outbox *out) {
     if (!c || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->dist || c->dist_stage < 2) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_score_begin before pdl_dist_preprocess_finish");
+    require_state(c, E_DIST_SCORE_BEGIN);
     PDL_HIP(hipSetDevice(c->device));
-    c->scored = false; c->mirror_valid = false; c->edges_valid = false; c->dist_stage = 2;
+    pdl_stale(c, Stale::scores);
+    c->dist_stage = DistStage::adopted;
     pdl_run_dist_score_begin(c);
     out->d_cells = c->outbox.as<pdl_dist_cell>();
     out->counts = c->h_outbox_counts.data();
@@ -1027,7 +948,7 @@ int pdl_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_t n_i
     if (!c || (!d_inbox && n_inbox)) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->dist || c->dist_stage != 3) PDL_FAIL(PDL_ERR_STATE, "pdl_dist_score_finish without pdl_dist_score_begin");
+    require_state(c, E_DIST_SCORE_FINISH);
     if (n_inbox >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 received cells");
     PDL_HIP(hipSetDevice(c->device));
     pdl_run_dist_score_finish(c, d_inbox, n_inbox);
@@ -1050,9 +971,7 @@ int pdl_get_dictionary(pdl_ctx *c, uint64_t *ranks, uint32_t *seqs, uint32_t *co
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
-    if (!c->preprocessed) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary before pdl_preprocess");
-    if (c->dist) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary: a multi-GPU context keeps ranks only for its own interval");
-    if (!c->keys_b.p || !c->recpos.p) PDL_FAIL(PDL_ERR_STATE, "pdl_get_dictionary: the sorted k-mer stream was released (option low_memory)");
+    require_state(c, E_GET_DICTIONARY);
     PDL_HIP(hipSetDevice(c->device));
     const uint64_t U = c->U, M = c->M;
     std::vector<uint32_t> recpos(U);
@@ -1078,7 +997,7 @@ int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offset
     if (out) memset(out, 0, sizeof(*out));
     if (info) memset(info, 0, sizeof(*info));
     return guarded(c, [&]() -> int {
-    require_state(c, "pdl_query_scores", NEEDS_QUERY);
+    require_state(c, E_QUERY_SCORES);
     if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL pointer");
     check_genes("pdl_query_scores", residues, offsets, n_query);
     PDL_HIP(hipSetDevice(c->device));
@@ -1095,7 +1014,7 @@ int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     if (info && n_queries) memset(info, 0, sizeof(*info) * (size_t) n_queries);
     if (binfo) memset(binfo, 0, sizeof(*binfo));
     return guarded(c, Lock::held, [&]() -> int {
-        require_state(c, "pdl_query_batch", NEEDS_QUERY);
+        require_state(c, E_QUERY_BATCH);
         check_batch(c, "pdl_query_batch", out, residues, offsets, gene_begin, n, n_queries);
         PDL_HIP(hipSetDevice(c->device));
         pdl_run_query_batch(c, residues, offsets, gene_begin, n, n_queries, out, info, binfo);
@@ -1113,7 +1032,7 @@ int pdl_append_genomes(pdl_ctx *c, const uint8_t *residues, const uint64_t *offs
     std::lock_guard<std::mutex> lk(c->mu);
     if (info) memset(info, 0, sizeof(*info));
     return guarded(c, [&]() -> int {
-    require_state(c, "pdl_append_genomes", NEEDS_WHOLE_SET);
+    require_state(c, E_APPEND_GENOMES);
     check_genes("pdl_append_genomes", residues, offsets, n);
     // union genome ids: G, G+1, ... in first-seen order (PangeneIData.java:56-62 continued)
     std::vector<uint32_t> ids(n, c->G);
@@ -1141,7 +1060,7 @@ int pdl_remove_genomes(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_
     std::lock_guard<std::mutex> lk(c->mu);
     if (info) memset(info, 0, sizeof(*info));
     return guarded(c, [&]() -> int {
-    require_state(c, "pdl_remove_genomes", NEEDS_WHOLE_SET);
+    require_state(c, E_REMOVE_GENOMES);
     if (!genomes) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: NULL pointer");
     if (count == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_remove_genomes: no genome");
     std::vector<uint8_t> named((size_t) c->G, 0);
@@ -1167,12 +1086,16 @@ int pdl_get_rekey_info(pdl_ctx *c, pdl_rekey_info *out) {
     return PDL_OK;
 }
 
-int pdl_get_rank_table(const pdl_ctx *c, uint8_t out[256], uint64_t *out_lm) {
+int pdl_get_rank_table(const pdl_ctx *cc, uint8_t out[256], uint64_t *out_lm) {
+    pdl_ctx *c = const_cast<pdl_ctx *>(cc);
     if (!c || !out) return PDL_ERR_ARGUMENT;
-    if (!c->preprocessed) return PDL_ERR_STATE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, [&]() -> int {
+    require_state(c, E_GET_RANK_TABLE);
     memcpy(out, c->rp.rank_values, 256);
     if (out_lm) *out_lm = c->rp.last_multiplier;
     return PDL_OK;
+    });
 }
 
 int pdl_get_timings(pdl_ctx *c, pdl_timings *out) {

@@ -332,6 +332,10 @@ struct pdl_query_chunk {
     std::vector<uint64_t> cells, records, matched, cost;         // [nq]
 };
 
+// The stages of a multi-GPU build and pass, in the order the pdl_dist_* calls walk them (DESIGN.md section 16 has who sets and
+// who requires each); `none`: no multi-GPU build has gone as far as its slice.
+enum class DistStage : int { none, slice_built, adopted, joined, scored };
+
 // ---- the context --------------------------------------------------------------------------------
 struct pdl_ctx {
     int device = 0;
@@ -474,7 +478,7 @@ struct pdl_ctx {
     // multi-GPU (pdl_dist_*): this context is rank `rank` of `world`; the postings live in caller-owned memory
     bool dist = false;
     uint32_t world = 1, rank = 0;
-    int dist_stage = 0;           // 0 none | 1 slice built | 2 dictionary adopted | 3 join done, outbox listed | 4 scored
+    DistStage dist_stage = DistStage::none;   // none | slice built | dictionary adopted | join done, outbox listed | scored
     uint2 *post_ext = nullptr;    // the all-gathered dictionary (caller's buffer), used instead of `post`
     uint64_t U_slice = 0, M_slice = 0;
     std::vector<uint32_t> h_owner;            // [G] rank of every genome
@@ -584,6 +588,30 @@ struct pdl_ctx {
     size_t mirror_bytes = 0;
     bool mirror_valid = false;
 };
+
+#include "pdl_state.h"        // the reset and the gate over the state words above
+
+// The one place where exceptions become return codes: runs an entry point's body (-> its return code); what the body throws is
+// translated and the message stored in the context (pdl_create's, through pdl_set_create_error, when there is none), after `undo`
+// has freed and zeroed the outputs a failure must not leave behind.  The caller holds the context's lock — or, with Lock::take,
+// has let go of it and the message is stored under it.
+void pdl_set_create_error(const std::string &msg);
+enum class Lock { held, take };
+template <class Body, class Undo>
+inline int guarded(pdl_ctx *c, Lock lock, Body &&body, Undo &&undo) {
+    int code = PDL_ERR_DEVICE;
+    std::string msg;
+    try { return body(); }
+    catch (const pdl_error &e) { code = e.code; msg = e.msg; }
+    catch (const std::bad_alloc &) { msg = "host allocation failed"; }
+    catch (const std::exception &e) { msg = e.what(); }
+    undo();
+    if (!c) pdl_set_create_error(msg);
+    else if (lock == Lock::take) { std::lock_guard<std::mutex> lk(c->mu); c->err = msg; }
+    else c->err = msg;
+    return code;
+}
+template <class Body> inline int guarded(pdl_ctx *c, Body &&body) { return guarded(c, Lock::held, body, [] {}); }
 
 // Small device->host reads through the pinned scratch: queue with add(), one sync(), then read the returned pointers.
 // Small device -> host reads (counters, control blocks) WITHOUT a DMA copy and without hipStreamSynchronize: on this

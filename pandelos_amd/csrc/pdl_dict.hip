@@ -924,19 +924,12 @@ static void dictionary_pipeline(pdl_ctx *c, bool only_complexity) {
 // alphabet (rk_change, pdl_rekey.h), commit (commit_set_change), leave a sorted stream of the new set in (keys_b, vals_b) and then
 // run the build's own stages on it (rebuild_behind_sort); the next entry point that changes the set does the same through these.
 // ------------------------------------------------------------------------------------------------
-// "From here on the context changes": whatever was derived from the old set is stale, and a failure leaves the context
-// un-preprocessed.  (The families would go with the edges anyway: pdl_run_bbh_all drops them before anyone reads them.)
-static void context_changes(pdl_ctx *c) {
-    c->preprocessed = false; c->scored = false; c->tasks_ready = false; c->reshard_pending = false;
-    c->mirror_valid = false; c->edges_valid = false; c->fam_valid = false;
-}
-
 // The commit of a call that changes the set, behind its last refusal: the context changes, and where the letters do (ch.rekey) it
 // takes the new rank table.  Returns what the tail needs: the width of the keys that are there, and the call's pdl_rekey_info
 // but for its time; `keys_rewritten` is the stream K-rekey will go over.
 struct SetCommit { bool key64_before; pdl_rekey_info ri; };
 static SetCommit commit_set_change(pdl_ctx *c, const RkChange &ch, uint64_t keys_rewritten) {
-    context_changes(c);
+    pdl_stale(c, Stale::build);         // "from here on the context changes": what was derived from the old set is stale, and a failure leaves the context un-preprocessed
     SetCommit sc{c->key64, pdl_rekey_info{}};
     pdl_rekey_info &ri = sc.ri;
     ri.letters_before = ri.letters_after = c->rp.base; ri.key_bits_before = ri.key_bits_after = c->rp.rank_bits;
@@ -1301,7 +1294,6 @@ void pdl_run_remove(pdl_ctx *c, const uint32_t *genomes, uint32_t count, pdl_rem
 void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity) {
     hipStream_t st = c->stream;
     ev_begin(c, EV_PRE_TOTAL);
-    c->dist = false; c->dist_stage = 0; c->post_ext = nullptr; c->dist_sender = false;
     c->short_valid = false;
     stage_alphabet_and_lengths(c, kvalue, only_complexity);
     pdl_with_key(c->key64, [&](auto key) { dictionary_pipeline<decltype(key)>(c, only_complexity); });
@@ -1399,7 +1391,7 @@ void pdl_run_dist_begin(pdl_ctx *c, int kvalue) {
     hipStream_t st = c->stream;
     ev_begin(c, EV_PRE_TOTAL);
     ev_begin(c, EV_DIST_BEGIN);
-    c->dist = true; c->dist_stage = 0; c->post_ext = nullptr;
+    c->dist = true; c->dist_stage = DistStage::none; c->post_ext = nullptr;
     stage_alphabet_and_lengths(c, kvalue, false);
     pdl_with_key(c->key64, [&](auto key) { dist_slice_pipeline<decltype(key)>(c); });
     ev_end(c, EV_DIST_BEGIN);
@@ -1423,7 +1415,7 @@ void pdl_run_dist_begin(pdl_ctx *c, int kvalue) {
     c->tm.sort_rank_ms = c->M_slice ? ev_ms(c, EV_SORT1) : 0.f;
     c->tm.dict_ms = c->M_slice ? ev_ms(c, EV_DICT) : 0.f;
     c->tm.dist_begin_ms = ev_ms(c, EV_DIST_BEGIN);
-    c->dist_stage = 1;
+    c->dist_stage = DistStage::slice_built;
 }
 
 // longest-processing-time assignment, deterministic (ties: lower genome id first, then lower rank)
@@ -1473,7 +1465,7 @@ static void dist_finish_tail(pdl_ctx *c, float ranges_ms) {
     ev_end(c, EV_DIST_FINISH); ev_end(c, EV_PRE_TOTAL);
     c->tm.dist_finish_ms = close_range_timings(c, EV_DIST_FINISH);
     c->tm.preprocess_total_ms = c->tm.dist_begin_ms + ranges_ms + c->tm.dist_finish_ms;
-    c->dist_stage = 2;
+    c->dist_stage = DistStage::adopted;
 }
 
 void pdl_run_dist_finish(pdl_ctx *c, uint64_t total, const uint64_t *weights) {

@@ -26,8 +26,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-void pdl_set_create_error(const std::string &msg);                                                     // pdl_api.hip
-int pdl_preprocess_common(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost);
+void pdl_build(pdl_ctx *c, uint32_t n, uint64_t n_res, int k, int only_complexity, pdl_cost *out_cost);   // pdl_api.hip
 
 namespace {
 
@@ -347,7 +346,7 @@ extern "C" {
 int pdl_scan_faa(const char *path, pdl_ingest *out, uint8_t *residues, uint64_t cap_residues, uint64_t *offsets, uint32_t *genome_of,
                  uint32_t cap_sequences) {
     if (!path || !out) return PDL_ERR_ARGUMENT;
-    try {
+    return guarded(nullptr, [&]() -> int {          // (no context: the text goes where pdl_create's does)
         const auto t0 = std::chrono::steady_clock::now();
         MappedFile f(path);
         FaaTables t;
@@ -358,14 +357,13 @@ int pdl_scan_faa(const char *path, pdl_ingest *out, uint8_t *residues, uint64_t 
         if (genome_of && !t.gen.empty()) memcpy(genome_of, t.gen.data(), t.gen.size() * 4);
         fill_ingest(out, t, t.gen.size(), t.names.size(), f.n, ms_since(t0));
         return PDL_OK;
-    } catch (const pdl_error &e) { pdl_set_create_error(e.msg); return e.code;
-    } catch (const std::bad_alloc &) { pdl_set_create_error("host allocation failed"); return PDL_ERR_DEVICE; }
+    });
 }
 
 int pdl_ingest_faa(pdl_ctx *c, const char *path, pdl_ingest *out) {
     if (!c || !path || !out) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    try {
+    return guarded(c, [&]() -> int {
         const auto t0 = std::chrono::steady_clock::now();
         PDL_HIP(hipSetDevice(c->device));
         c->ingested = false;
@@ -381,7 +379,7 @@ int pdl_ingest_faa(pdl_ctx *c, const char *path, pdl_ingest *out) {
         }
         // a dictionary built from the previous ingest still reads these buffers: wait for whatever the context has queued
         PDL_HIP(hipStreamSynchronize(c->stream));
-        c->preprocessed = false; c->scored = false; c->tasks_ready = false;
+        pdl_stale(c, Stale::build);
         c->ing_res.alloc(f.n + 16);
         FaaTables t;
         uint8_t *stage = c->ing_pin[0], *d_dst = c->ing_res.as<uint8_t>();
@@ -405,8 +403,7 @@ int pdl_ingest_faa(pdl_ctx *c, const char *path, pdl_ingest *out) {
         c->ing_R = out->residues;
         c->ingested = true;
         return PDL_OK;
-    } catch (const pdl_error &e) { c->err = e.msg; return e.code;
-    } catch (const std::bad_alloc &) { c->err = "host allocation failed"; return PDL_ERR_DEVICE; }
+    });
 }
 
 const char *pdl_ingest_genome_name(const pdl_ctx *c, uint32_t genome) {
@@ -417,12 +414,15 @@ const char *pdl_ingest_genome_name(const pdl_ctx *c, uint32_t genome) {
 int pdl_preprocess_ingested(pdl_ctx *c, int k, int only_complexity, pdl_cost *out_cost) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->ingested) { c->err = "pdl_preprocess_ingested before pdl_ingest_faa"; return PDL_ERR_STATE; }
+    return guarded(c, [&]() -> int {
+    require_state(c, E_PREPROCESS_INGESTED);
     const uint32_t n = (uint32_t) c->ing_h_gen.size();
     c->d_res = c->ing_res.as<uint8_t>(); c->d_off = c->ing_off.as<uint64_t>(); c->d_gen = c->ing_gen.as<uint32_t>();
     c->h_genome_of = c->ing_h_gen;                 // the genome layout is built from the host copy: nothing comes back from the device
     c->layout_deferred = false;
-    return pdl_preprocess_common(c, n, c->ing_R, k, only_complexity, out_cost);
+    pdl_build(c, n, c->ing_R, k, only_complexity, out_cost);
+    return PDL_OK;
+    });
 }
 
 }  // extern "C"

@@ -1863,7 +1863,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
     uint64_t upper = 0;
     for (uint32_t g : c->shard) upper += c->h_upper_cost[g];
     c->tm.walked_lookups = upper;
-    if (n_rows == 0) { ev_end(c, EV_SCORE_TOTAL); PDL_HIP(hipStreamSynchronize(st)); c->dist_stage = 3; return; }
+    if (n_rows == 0) { ev_end(c, EV_SCORE_TOTAL); PDL_HIP(hipStreamSynchronize(st)); c->dist_stage = DistStage::joined; return; }
     ScorePlan pl = score_plan(c);
     if (!pl.mirror) PDL_FAIL(PDL_ERR_STATE, "multi-GPU scoring needs the upper-triangle range lists of pdl_dist_preprocess_finish");
     score_alloc_rows(c, pl);
@@ -1916,7 +1916,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
     PDL_HIP(hipStreamSynchronize(st));
     join_timings(c);
     c->tm.dist_score_begin_ms = ev_ms(c, EV_SCORE_TOTAL);
-    c->dist_stage = 3;
+    c->dist_stage = DistStage::joined;
 }
 
 void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_t n_inbox) {
@@ -1926,10 +1926,10 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
     c->tm.inbox_cells = n_inbox;
     if (n_rows == 0) {
         if (n_inbox) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_dist_score_finish: %llu cells received by a rank without rows", (unsigned long long) n_inbox);
-        ev_end(c, EV_DIST_SCORE_FINISH); c->scored = true; c->dist_stage = 4; return;
+        ev_end(c, EV_DIST_SCORE_FINISH); c->scored = true; c->dist_stage = DistStage::scored; return;
     }
     // (from here on the call counts cells into the rows and folds them into the maxima: one that fails leaves the pass to be begun again)
-    c->dist_stage = 2;
+    c->dist_stage = DistStage::adopted;
     const ScorePlan pl = score_plan(c);
     const unsigned long long cap = c->st_cap;
     if (n_inbox > cap) score_alloc_cells(c, pl, cap, n_inbox);             // (rare: the first allocation leaves room for `cap` received cells)
@@ -1949,7 +1949,7 @@ void pdl_run_dist_score_finish(pdl_ctx *c, const pdl_dist_cell *d_inbox, uint64_
     c->tm.dist_score_finish_ms = ev_ms(c, EV_DIST_SCORE_FINISH);
     c->tm.score_total_ms = c->tm.dist_score_begin_ms + c->tm.dist_score_finish_ms;
     c->scored = true;
-    c->dist_stage = 4;
+    c->dist_stage = DistStage::scored;
 }
 
 #include "pdl_query.h"           // K-query: one new genome against this dictionary (pdl_query_scores)

@@ -1,7 +1,7 @@
 """Which incremental entry point refuses which state of the context, and the argument checks on new genes that four of them
 share — through the C ABI, with stale bytes in every output first.
 
-The table (pdl_api.hip keeps it at the gate the six entry points call):
+The table (pdl_state.h keeps it, with the other entry points' rows, at the gate the six entry points call):
 
     entry point            built  ranges  single-GPU  no shard  stream held
     pdl_query_scores        yes    yes      yes         -          yes
