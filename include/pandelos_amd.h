@@ -208,8 +208,9 @@ PDL_API void pdl_free_edges(pdl_edges *);
  * buffers are reused and released at the next preprocess or destroy.  Free `out` with pdl_free_scores.
  * PDL_ERR_STATE: no preprocess, only_complexity, a multi-GPU context, or low_memory released the sorted k-mer stream.
  * PDL_ERR_ARGUMENT: n_query == 0, NULL pointers, decreasing offsets.  PDL_ERR_UNSUPPORTED: a query byte the base's alphabet
- * lacks (the union would have another rank table, library.cpp:96-119; the message names the byte), genes of 2^20 k-mers or
- * more, or union sizes past the base build's limits (2^32 residues, 31-bit gene ids). */
+ * lacks (the union would have another rank table, library.cpp:96-119; the message names the byte) unless option "query_rekey"
+ * is on (see there: the query is then ranked in the union's alphabet), genes of 2^20 k-mers or more, or union sizes past the
+ * base build's limits (2^32 residues, 31-bit gene ids). */
 typedef struct {
     uint64_t residues, kmer_occurrences;   /* of the query */
     uint64_t records;          /* unique (rank, query gene) records */
@@ -234,7 +235,8 @@ PDL_API int pdl_query_scores(pdl_ctx *, const uint8_t *residues, const uint64_t 
  * Every refusal is decided before a block is returned: `out` is left zeroed and the context as it was.
  * PDL_ERR_STATE: as pdl_query_scores.  PDL_ERR_ARGUMENT: n_queries == 0, n == 0, NULL pointers, decreasing offsets, a gene_begin
  * that does not start at 0, does not end at n or is not strictly increasing (a query without genes).  PDL_ERR_UNSUPPORTED: a
- * byte the base's alphabet lacks (the message names the first such query and its smallest absent byte), a gene of 2^20 k-mers
+ * byte the base's alphabet lacks (the message names the first such query and its smallest absent byte; with option "query_rekey"
+ * only a query whose own union has no exact ranks is refused so), a gene of 2^20 k-mers
  * or more, a batch whose residues pass 2^32 with the base's, or N + n_j past the 31-bit gene ids (decided from gene_begin alone,
  * before offsets is read). */
 typedef struct {
@@ -334,7 +336,7 @@ PDL_API int pdl_remove_genomes(pdl_ctx *, const uint32_t *genomes /* [count] dis
  * PDL_ERR_UNSUPPORTED, and the message says which side is hashed or wrapped; like every refusal it comes before anything changes.
  * After PDL_OK the context equals, bit for bit, what pdl_preprocess leaves on the union / the remaining set: the contract above.
  * pdl_get_timings: the re-key pass counts into sort_rank_ms (with "stage_timers" 0 it is not timed apart and shows only in the totals).
- * Queries and placements with a byte the base lacks keep refusing.
+ * Queries and placements with a byte the base lacks keep refusing under this option; option "query_rekey" below is theirs.
  * pdl_get_rekey_info: what the last successful pdl_append_genomes / pdl_remove_genomes of the context did about the alphabet. */
 typedef struct {
     uint32_t letters_before, letters_after;     /* B of the rank table before and after the call */
@@ -344,6 +346,38 @@ typedef struct {
     uint32_t rekeyed;                           /* 1: the call changed the rank table */
 } pdl_rekey_info;
 PDL_API int pdl_get_rekey_info(pdl_ctx *, pdl_rekey_info *out);
+
+/* ---- query and place a genome that brings letters the base lacks: option "query_rekey" --------------------------------------
+ * With the option at 0 (the default) pdl_query_scores, pdl_query_batch, pdl_place_query and pdl_place_batch refuse a query byte
+ * the base's alphabet lacks, as described with each.  With it at 1 they accept such bytes:
+ *   The union's rank table is made on the host from the base's letters and ALL the query's (genes shorter than k included, as a
+ *     build counts them).  The query is ranked with it; its records are then written back, digit by digit, into the base's
+ *     alphabet to search the base's keys, which are not touched: the digit map between an alphabet and a superset of it is
+ *     strictly increasing, so order and equality of k-mers are the same on both sides, and a k-mer with a new letter equals no
+ *     base k-mer.  The key width follows the union (ACGT at k = 16 has 32-bit keys, with N the query's are 38-bit ones).
+ *   pdl_query_scores: the block, pdl_query_info.genome_cost, records and matched_records are what the reference returns for task
+ *     G of the union run, bit for bit and in emission order.
+ *   pdl_query_batch: block j is what pdl_query_scores returns for query j alone, whatever letters the other queries bring and
+ *     however the batch is chunked.  A chunk is ranked once, with the letters of all its queries — a block is the same in whichever
+ *     exact superset alphabet it was ranked — and is cut in front of the query that would make that alphabet inexact.
+ *   pdl_place_query, pdl_place_batch: the query's edges and every placement field follow from that block as before.
+ * The base context is only read: scores, edges, families, dictionary, costs, timings, the rank table and pdl_get_rekey_info are the
+ * same before and after, and a later query without a new letter behaves exactly as with the option off.
+ * Both sides need ranks that are the polynomial itself: PDL_ERR_UNSUPPORTED when the base's ranks are hashed or wrapped past 2^64,
+ * or those of the union of the base and THIS query alone would be; the message names the byte, says which side, and names the
+ * option.  In a batch the verdict is each query's own, and the message names the first refused query.  Every other refusal of the
+ * four keeps its code and words, and like them these come before a block is returned and leave the context as it was.
+ * pdl_get_query_rekey_info: what the last successful call of the four did about letters (all of a batch's chunks together). */
+typedef struct {
+    uint32_t queries_rekeyed;                   /* queries that brought a letter the base lacks */
+    uint32_t letters_base;                      /* B of the base's rank table */
+    uint32_t letters_max;                       /* the most letters a query's own union had (letters_base: no query brought one) */
+    uint32_t key_bits_base;                     /* rank_bits of the base: 32-bit keys up to 32, 64-bit keys above */
+    uint32_t key_bits_max;                      /* the widest rank_bits a query or a chunk was ranked with */
+    uint64_t records_rebased;                   /* query records written back into the base's alphabet */
+    float rebase_ms;                            /* that pass on the device (0 with option "stage_timers" 0) */
+} pdl_query_rekey_info;
+PDL_API int pdl_get_query_rekey_info(pdl_ctx *, pdl_query_rekey_info *out);
 
 /* ---- gene families: the network's components and their collisions, on the device, from the edges where they lie --------
  * What netclu_ng.py does with the .net before Girvan-Newman: the connected components of the gene network (:58-66) and, per
@@ -455,7 +489,8 @@ PDL_API void pdl_free_placement(pdl_placement *);
  *
  * Refusals are decided before anything is returned; they leave every out[j] zeroed and the context as it was: every state
  * pdl_place_query refuses (PDL_ERR_STATE), every argument and domain refusal of pdl_query_batch with its code (the absent-byte
- * message names the first such query).  A refusal found in a later chunk returns nothing of the earlier chunks.  Each out[j] is
+ * message names the first such query; option "query_rekey" accepts such bytes as for pdl_query_batch).  A refusal found in a later
+ * chunk returns nothing of the earlier chunks.  Each out[j] is
  * freed with pdl_free_placement.
  *
  * pdl_placement_batch_of_edges: the batch form of pdl_placement_of_edges — one caller's base and n_queries edge lists laid end
@@ -517,7 +552,9 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * "alphabet_rekey" 0|1 (default 0: pdl_append_genomes / pdl_remove_genomes go through where the alphabet changes, by writing the
  * sorted stream's keys again; set BEFORE pdl_preprocess it also makes the build record the letters of genes shorter than k, one
  * small launch more, which an exact removal needs — see pdl_get_rekey_info; like "query_batch_bytes" it leaves the context's
- * scores in place). */
+ * scores in place), "query_rekey" 0|1 (default 0: pdl_query_scores, pdl_query_batch, pdl_place_query and pdl_place_batch accept
+ * query bytes the base's alphabet lacks by ranking the query in the union's alphabet — see pdl_get_query_rekey_info; it too leaves
+ * the context's scores in place and, like every option, outlives a rebuild). */
 PDL_API int pdl_set_option(pdl_ctx *, const char *name, int64_t value);
 
 /* ---- multi-GPU: one context per GPU, the caller moves bytes between them (RCCL over xGMI) -----------------------

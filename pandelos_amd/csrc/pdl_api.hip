@@ -646,6 +646,15 @@ static void fill_placement(pdl_place_result &r, bool with_edges, pdl_placement *
     out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
 }
 
+// pdl_get_query_rekey_info's books over one call of the four that score a query: opened behind the call's refusals of state and
+// argument, closed — the report becomes the context's — only when the call went through.
+static void query_rekey_open(pdl_ctx *c) {
+    c->qrk_call = pdl_query_rekey_info{};
+    c->qrk_call.letters_base = c->qrk_call.letters_max = c->rp.base;
+    c->qrk_call.key_bits_base = c->qrk_call.key_bits_max = c->rp.rank_bits;
+}
+static void query_rekey_close(pdl_ctx *c) { c->last_query_rekey = c->qrk_call; }
+
 int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_placement *out, pdl_query_info *info) {
     if (!c) return PDL_ERR_ARGUMENT;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -658,7 +667,9 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         families_ready_locked(c);
         pdl_place_result r;
         pdl_query_info qi{};
+        query_rekey_open(c);
         pdl_run_place_query(c, residues, offsets, n_query, r, &qi);
+        query_rekey_close(c);
         fill_placement(r, true, out);
         if (info) *info = qi;
         return PDL_OK;
@@ -763,7 +774,9 @@ int pdl_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         std::vector<pdl_query_info> qi(n_queries);
         uint32_t chunks = 0;
         float device_ms = 0.f;
+        query_rekey_open(c);
         pdl_run_place_batch(c, residues, offsets, gene_begin, n, n_queries, r, qi.data(), &chunks, &device_ms);
+        query_rekey_close(c);
         for (uint32_t q = 0; q < n_queries; q++) fill_placement(r[q], true, &out[q]);      // (only now: every chunk is through)
         if (info) memcpy(info, qi.data(), sizeof(*info) * (size_t) n_queries);
         if (binfo) { binfo->queries = n_queries; binfo->chunks = chunks; binfo->device_ms = device_ms; }
@@ -831,6 +844,11 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
         if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "query_batch_bytes: a positive byte count");
         c->opt_query_batch_bytes = (uint64_t) value;
         return PDL_OK;        // (no bearing on a scoring pass: the context's scores stay)
+    }
+    else if (n == "query_rekey") {
+        if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "query_rekey: 0 or 1");
+        c->opt_query_rekey = value != 0;
+        return PDL_OK;        // (nor has this one)
     }
     else if (n == "alphabet_rekey") {
         if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "alphabet_rekey: 0 or 1");
@@ -1001,7 +1019,9 @@ int pdl_query_scores(pdl_ctx *c, const uint8_t *residues, const uint64_t *offset
     if (!out) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_query_scores: NULL pointer");
     check_genes("pdl_query_scores", residues, offsets, n_query);
     PDL_HIP(hipSetDevice(c->device));
+    query_rekey_open(c);
     pdl_run_query(c, residues, offsets, n_query, out, info);
+    query_rekey_close(c);
     return PDL_OK;
     });
 }
@@ -1017,7 +1037,9 @@ int pdl_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
         require_state(c, E_QUERY_BATCH);
         check_batch(c, "pdl_query_batch", out, residues, offsets, gene_begin, n, n_queries);
         PDL_HIP(hipSetDevice(c->device));
+        query_rekey_open(c);
         pdl_run_query_batch(c, residues, offsets, gene_begin, n, n_queries, out, info, binfo);
+        query_rekey_close(c);
         return PDL_OK;
     }, [&] {     // a refusal returns no block: what earlier chunks produced goes back, `out` is zero again
         if (out) for (uint32_t q = 0; q < n_queries; q++) pdl_free_scores(&out[q]);
@@ -1084,6 +1106,15 @@ int pdl_get_rekey_info(pdl_ctx *c, pdl_rekey_info *out) {
     std::lock_guard<std::mutex> lk(c->mu);
     *out = c->last_rekey;
     return PDL_OK;
+}
+
+int pdl_get_query_rekey_info(pdl_ctx *c, pdl_query_rekey_info *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, [&]() -> int {
+    *out = c->last_query_rekey;
+    return PDL_OK;
+    });
 }
 
 int pdl_get_rank_table(const pdl_ctx *cc, uint8_t out[256], uint64_t *out_lm) {

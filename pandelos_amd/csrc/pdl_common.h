@@ -231,6 +231,15 @@ struct RankParams {
                             // (library.cpp:104-111 looks one multiplication ahead with wrapped products: 22 letters, k = 15), the ranks being the polynomial mod 2^64
 };
 #define RABIN_MODULO 18446744073709551557ULL   /* 2^64 - 59, library.cpp:19 */
+// what a kernel needs to take a key of an exact alphabet apart into its digits (pdl_rekey.h: rk_plan makes it, rk_items / rk_one read it)
+struct RkArgs {
+    uint32_t k, base;           // of the keys that come in
+    uint32_t nparts, h;         // parts a key is cut into (1 for 32-bit keys), digits of every part but the last
+    uint64_t magic;             // RmDigits::magic of `base`
+    uint64_t part_div;          // B^h
+    uint64_t part_magic;        // floor(2^64 / B^h)
+    uint32_t entries;           // k * base
+};
 // base^k < 2^64, in exact arithmetic (the reference's own test compares wrapped products and lets some wraps through: 20 letters
 // at k = 15 wrap unnoticed to a 64-bit rank_bits).  The one place that says so: rank_init_host's key_bits and rk_exact ask here.
 inline bool pow_fits_u64(uint32_t base, uint32_t k) {
@@ -266,7 +275,7 @@ template <int N> struct EventSpans {
     EventSpans &operator=(const EventSpans &) = delete;
     ~EventSpans() { for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e); }
 };
-using QSpans = EventSpans<3>;
+using QSpans = EventSpans<4>;      // (a query that is asked for its letters has one host read more)
 // Everything a struct of work buffers holds goes back and its bookkeeping starts again: the members release themselves, so a
 // member added to the struct is released without being named anywhere else.
 template <class T> inline void pdl_renew(T &x) { x.~T(); new (&x) T(); }
@@ -512,7 +521,21 @@ struct pdl_ctx {
         bool hbm_clean = false;                      // hbm holds hbm_slots tables laid out for hbm_cols columns, in their clean state
         uint32_t hbm_cols = 0, hbm_slots = 0;
         const uint32_t *rec_sorted_at = nullptr;     // (inside rec_sorted: the half the gene sort left its output in)
-        QSpans spans;                                // up to three stretches of device work
+        QSpans spans;                                // up to three stretches of device work (four with option "query_rekey")
+        // option "query_rekey" (a single query's and a chunk's alike): the union's rank table and the two plans between the base's
+        // alphabet and the union's, as the host decided them (pdl_query_rekey_plan, pdl_dict.hip), and Q-rebase's output
+        struct Rekey {
+            RankParams rp{};                         // the union's
+            bool key64 = false;
+            RkArgs up{}, down{};                     // base -> union (the fold's two ranks), union -> base (Q-rebase)
+            std::vector<uint64_t> h_up, h_down;      // their tables (kept alive for the asynchronous uploads)
+            std::vector<uint32_t> h_down32;
+            uint32_t absent[8] = {};                 // digits of the union's alphabet that are letters the base lacks
+            DevBuf up_table, down_table;
+            DevBuf up3;                              // u64 [3]: the base's bmax and its last two records' ranks, in the union's alphabet
+            DevBuf bkey, none;                       // per query record: its key in the base's alphabet | 1: it holds a letter the base lacks
+            EventSpans<1> span;                      // Q-rebase alone (option "stage_timers")
+        } rk;
     } qb;
     // pdl_query_batch (pdl_query_batch.h): the buffers of one chunk of queries, reused across chunks and calls, released with qb's
     // (the HBM tables of the join's last tier and their bookkeeping are qb's: a batch and a single query find each other's clean)
@@ -524,6 +547,8 @@ struct pdl_ctx {
         ~QueryBatchBufs() { if (stage) (void) hipHostFree(stage); }
     } qbb;
     uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
+    bool opt_query_rekey = false;                   // queries and placements accept letters the base lacks (pdl_query.h, Q-rebase)
+    pdl_query_rekey_info qrk_call{}, last_query_rekey{};    // what the call under way / the last successful one of the four did about letters
     // K-fam (pdl_families.h): work buffers of a run (grown as needed, shared by pdl_compute_families and pdl_families_of_edges) and
     // the context's own families, kept on the host until the edges change (pdl_run_bbh_all drops them)
     struct FamBufs {
@@ -745,6 +770,18 @@ void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on
 const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
                                  uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
                                  uint64_t *d_u);
+// ... with another alphabet's rank table and key width than the context's (option "query_rekey": the union's)
+const void *pdl_query_dictionary(pdl_ctx *c, const RankParams &rp, bool key64, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off,
+                                 uint32_t n, uint64_t m, uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b,
+                                 uint32_t *recpos, uint2 *post, uint64_t *d_u);
+// Option "query_rekey" (pdl_rekey.h, pdl_dict.hip).  The alphabet decision for the letters (256 bits) queries bring on top of the
+// base's: false when the union's ranks would not be exact (*why: rk_why_not), else the union's table and the plans are in
+// c->qb.rk when `adopt` is set, their tables on their way to the device.  pdl_query_rebase queues, for the plan in c->qb.rk, the
+// fold's three base ranks in the union's alphabet (up3) and Q-rebase over the query records: record j's key is qkeys[recpos[j]]
+// (recpos NULL: qkeys[j]), j below *d_records and below `bound`.
+bool pdl_query_rekey_base_exact(const pdl_ctx *c, const char **why);
+bool pdl_query_rekey_plan(pdl_ctx *c, const uint32_t letters[8], bool adopt, const char **why);
+void pdl_query_rebase(pdl_ctx *c, const void *qkeys, const uint32_t *recpos, const unsigned long long *d_records, uint64_t bound);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
 // ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there); the device time
 // of its stretches is c->qb.spans.total_ms() once the stream has been waited for

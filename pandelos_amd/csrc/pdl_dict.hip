@@ -984,33 +984,93 @@ static void rebuild_behind_sort(pdl_ctx *c, pdl_rekey_info ri, uint64_t M1, uint
     c->tm = t;
 }
 
-// K-rank of genes that are not the context's input (a query, an append) with the context's rank parameters: gene values 0..n-1
+// K-rank of genes that are not the context's input (a query, an append) with the rank parameters `rp` — the context's, or the
+// union's of a query that brings letters: gene values 0..n-1
 template <class KeyT>
-static void rank_new_genes(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m, uint64_t n_res,
-                           KeyT *keys, uint32_t *vals) {
+static void rank_new_genes(pdl_ctx *c, const RankParams &rp, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
+                           uint64_t n_res, KeyT *keys, uint32_t *vals) {
     hipStream_t st = c->stream;
-    if (c->rp.hash_fallback) {
+    if (rp.hash_fallback) {
         if constexpr (sizeof(KeyT) == 8)
-            hipLaunchKernelGGL(k_rank_hash<0>, dim3((n + 255) / 256), dim3(256), 0, st, res, off, kmer_off, n, c->rp, keys, vals, (uint32_t *) nullptr);
+            hipLaunchKernelGGL(k_rank_hash<0>, dim3((n + 255) / 256), dim3(256), 0, st, res, off, kmer_off, n, rp, keys, vals, (uint32_t *) nullptr);
     } else {
         const uint64_t tiles = (m + RANK_TILE - 1) / RANK_TILE;
-        hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, res, off, kmer_off, n, m, n_res, c->rp,
+        hipLaunchKernelGGL((k_rank<KeyT, 0>), dim3((uint32_t) tiles), dim3(RANK_THREADS), 0, st, res, off, kmer_off, n, m, n_res, rp,
                            keys, vals, 0u, (uint32_t *) nullptr);
     }
     PDL_HIP(hipGetLastError());
 }
 
-const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
-                                 uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
-                                 uint64_t *d_u) {
-    return pdl_with_key(c->key64, [&](auto key) -> const void * {
+const void *pdl_query_dictionary(pdl_ctx *c, const RankParams &rp, bool key64, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off,
+                                 uint32_t n, uint64_t m, uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b,
+                                 uint32_t *recpos, uint2 *post, uint64_t *d_u) {
+    return pdl_with_key(key64, [&](auto key) -> const void * {
         using KeyT = decltype(key);
         KeyT *keys_in = static_cast<KeyT *>(keys_a), *keys_out = static_cast<KeyT *>(keys_b);
-        rank_new_genes<KeyT>(c, res, off, kmer_off, n, m, n_res, keys_in, vals_a);
-        pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_a, vals_b, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);
+        rank_new_genes<KeyT>(c, rp, res, off, kmer_off, n, m, n_res, keys_in, vals_a);
+        pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_a, vals_b, m, rp.rank_bits, false, nullptr, 0, rp.key_bits == rp.rank_bits);
         scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_b}, RecScatter<KeyT>{keys_out, vals_b, m, recpos, post}, d_u);
         return keys_out;
     });
+}
+const void *pdl_query_dictionary(pdl_ctx *c, const uint8_t *res, const uint64_t *off, const uint64_t *kmer_off, uint32_t n, uint64_t m,
+                                 uint64_t n_res, void *keys_a, void *keys_b, uint32_t *vals_a, uint32_t *vals_b, uint32_t *recpos, uint2 *post,
+                                 uint64_t *d_u) {
+    return pdl_query_dictionary(c, c->rp, c->key64, res, off, kmer_off, n, m, n_res, keys_a, keys_b, vals_a, vals_b, recpos, post, d_u);
+}
+
+// ---- option "query_rekey": the host's alphabet decision for a query or a chunk of queries, and what it queues (pdl_rekey.h) ------
+bool pdl_query_rekey_base_exact(const pdl_ctx *c, const char **why) {
+    if (rk_exact(c->rp)) return true;
+    *why = rk_why_not(c->rp);
+    return false;
+}
+bool pdl_query_rekey_plan(pdl_ctx *c, const uint32_t letters[8], bool adopt, const char **why) {
+    RkQuery q;
+    if (!rk_query(c->rp, c->alpha_present, letters, q)) { *why = rk_why_not(q.up.rp); return false; }
+    if (!adopt) return true;
+    auto &rk = c->qb.rk;
+    hipStream_t st = c->stream;
+    rk.rp = q.up.rp; rk.key64 = q.up.rp.rank_bits > 32;
+    rk.up = q.up.args; rk.down = q.down;
+    memcpy(rk.absent, q.absent, sizeof(rk.absent));
+    rk.h_up.swap(q.up_table); rk.h_down.swap(q.down_table);
+    rk.up_table.alloc(rk.h_up.size() * 8);
+    PDL_HIP(hipMemcpyAsync(rk.up_table.p, rk.h_up.data(), rk.h_up.size() * 8, hipMemcpyHostToDevice, st));
+    const void *h_down = rk.h_down.data();
+    const size_t kb = c->key64 ? 8 : 4;
+    if (!c->key64) {                                                        // (B^k <= 2^32: every entry fits)
+        rk.h_down32.assign(rk.h_down.begin(), rk.h_down.end());
+        h_down = rk.h_down32.data();
+    }
+    rk.down_table.alloc(rk.h_down.size() * kb);
+    PDL_HIP(hipMemcpyAsync(rk.down_table.p, h_down, rk.h_down.size() * kb, hipMemcpyHostToDevice, st));
+    return true;
+}
+void pdl_query_rebase(pdl_ctx *c, const void *qkeys, const uint32_t *recpos, const unsigned long long *d_records, uint64_t bound) {
+    auto &rk = c->qb.rk;
+    hipStream_t st = c->stream;
+    const size_t kb = c->key64 ? 8 : 4;
+    rk.up3.alloc(3 * 8); rk.bkey.alloc(std::max<uint64_t>(bound, 1) * kb); rk.none.alloc(std::max<uint64_t>(bound, 1));
+    RkAbsent ab;
+    memcpy(ab.bits, rk.absent, sizeof(ab.bits));
+    const bool timed = c->opt_stage_timers;
+    rk.span.start(st);
+    pdl_with_key(c->key64, [&](auto key_b) {
+        using KeyB = decltype(key_b);
+        hipLaunchKernelGGL(k_q_up3<KeyB>, dim3(1), dim3(64), 0, st, (const KeyB *) c->keys_b.as<KeyB>(), (const uint32_t *) c->recpos.as<uint32_t>(),
+                           (uint32_t) c->U, c->M, rk.up, (const uint64_t *) rk.up_table.as<uint64_t>(), rk.up3.as<unsigned long long>());
+        if (!bound) return;
+        if (timed) rk.span.begin();
+        pdl_with_key(rk.key64, [&](auto key_q) {
+            using KeyQ = decltype(key_q);
+            hipLaunchKernelGGL((k_q_rebase<KeyQ, KeyB>), dim3((uint32_t) ((bound + RK_THREADS - 1) / RK_THREADS)), dim3(RK_THREADS),
+                               (size_t) rk.down.entries * sizeof(KeyB), st, static_cast<const KeyQ *>(qkeys), recpos, d_records, bound, rk.down,
+                               (const KeyB *) rk.down_table.as<KeyB>(), ab, rk.bkey.as<KeyB>(), rk.none.as<uint8_t>());
+        });
+        if (timed) rk.span.end();
+    });
+    PDL_HIP(hipGetLastError());
 }
 
 // K-rekey (pdl_rekey.h) of the first m keys of keys_b, `from_key64` wide, for the rank table c->rp / c->key64 hold ALREADY; the
@@ -1063,7 +1123,7 @@ static void append_sorted_stream(pdl_ctx *c, uint32_t n, uint64_t m, uint64_t n_
     KeyT *k_in = q.keys_a.as<KeyT>(), *k_out = q.keys_b.as<KeyT>();
     uint32_t *v_in = q.vals_a.as<uint32_t>(), *v_out = q.vals_b.as<uint32_t>();
     ev_begin(c, EV_RANK);
-    rank_new_genes<KeyT>(c, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, m, n_res, k_in, v_in);
+    rank_new_genes<KeyT>(c, c->rp, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, m, n_res, k_in, v_in);
     ev_end(c, EV_RANK);
     ev_begin(c, EV_SORT1);
     pdl_sort_pairs<KeyT>(c, k_in, k_out, v_in, v_out, m, c->rp.rank_bits, false, nullptr, 0, c->rp.key_bits == c->rp.rank_bits);

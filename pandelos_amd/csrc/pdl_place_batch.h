@@ -216,7 +216,7 @@ void pdl_run_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         const pdl_query_chunk ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);       // (its argument and domain refusals leave from here)
         place_chunk(c, B, qs, qa, ch, out, info, device_ms);
         (*chunks)++;
-        qa = qe;
+        qa += ch.nq;                                                 // (option "query_rekey" may have cut the chunk short of qe)
     }
 }
 

@@ -15,6 +15,16 @@
 //            k_q_join_hbm       the same row program on direct-addressed tables in HBM
 //   Q-order  k_order_rows_wave / k_order_rows   the reference's emission order (chunk, first group, column)
 //
+// Option "query_rekey" (default off: the stages above, launched as ever).  On, Q-alpha is k_q_letters — the absent bytes themselves,
+// 256 bits, read by the host before Q-dict — and a query that brings one takes these stages instead:
+//   Q-dict   with the UNION's RankParams and key width (rk_query, pdl_rekey.h: base letters + all the query's)
+//   Q-rebase k_q_up3, k_q_rebase (pdl_rekey.h)   the fold's three base ranks written up into the union's alphabet; every query
+//                               record's key written back into the base's, with a flag where it holds a new letter
+//   Q-fold   k_q_fold_rk        Q-match  k_q_match_rk   the same fold and description over union ranks; only the searches in
+//                               the base's keys take the record's rebased key (q_base_key), and none for a flagged record
+// Q-rows, Q-join and Q-order read no key: they are the same launches.  The digit map between an alphabet and a superset of it
+// is strictly increasing, so order and equality of k-mers are the same on both sides.
+//
 // Match.  The base postings are rank-group major: the rank of post[u] is keys_b[recpos[u]] (what pdl_get_dictionary reads).
 // They are in rank order except for ONE record: when the base's last record (rank bmax) was alone in its rank,
 // k_fold_last_record moved it into the group before it (rank r2), at its gene-order place.  Every rank of [gs, U) is r2
@@ -48,7 +58,8 @@ __device__ __forceinline__ uint32_t q_size(const QDesc &d) {
 }
 
 struct QFold {
-    unsigned long long bmax, r2, tgt, extra_target;
+    unsigned long long bmax, r2, tgt, extra_target;     // ranks in the alphabet the query is ranked in (the base's, or the union's: Q-rebase below)
+    unsigned long long bmax_b;                          // bmax as the base's keys hold it
     uint32_t folded;        // the base folded its last record p into the group of rank r2 = [gs, U)
     uint32_t gs, p;
     uint32_t skip_p;        // in the union p is not part of [gs, U)
@@ -68,7 +79,8 @@ enum : uint32_t {
     Q_CTL_EMITTED = 7,          // emitted cells (total of the row-count scan)
     Q_CTL_WIDE_ROWS = 8,        // order: rows of more than 256 cells
     Q_CTL_MAY_OVERFLOW = 9,     // rows that may overflow (more lookups than the LDS table holds keys)
-    Q_CTL_USED = 10,
+    Q_CTL_USED = 10,            // (the words above: what the look behind the match reads)
+    Q_CTL_LETTERS = 10,         // option "query_rekey": 256 bits, the query bytes that are not in the base's alphabet (4 words)
     Q_CTL_WORDS = 16,
 };
 
@@ -81,6 +93,15 @@ __global__ __launch_bounds__(256) void k_q_alpha(QAlphaArgs a) {
         if (!((a.present[b >> 5] >> (b & 31)) & 1u)) worst = max(worst, 256u - b);
     }
     if (worst) atomicMax(a.bad, (unsigned long long) worst);
+}
+// Option "query_rekey": the absent bytes themselves, 256 bits at `letters` (32-bit words).  The common path stays the table test; an
+// absent byte — rare — sets its bit.
+struct QLettersArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; uint32_t *letters; };
+__global__ __launch_bounds__(256) void k_q_letters(QLettersArgs a) {
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
+        const uint32_t b = a.res[i];
+        if (!((a.present[b >> 5] >> (b & 31)) & 1u)) atomicOr(&a.letters[b >> 5], 1u << (b & 31));
+    }
 }
 // Host side of the letter check, shared with the append (pdl_dict.hip): queue k_q_alpha over n device bytes; the word it leaves
 // at d_bad is turned into the refusal by pdl_fail_absent_byte (`who`: "query" / "appended").
@@ -118,15 +139,27 @@ template <class KeyT> struct QView {
     QBase<KeyT> b;
     const KeyT *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
 };
+// Option "query_rekey", a query that brings letters the base lacks: it is ranked in the union's alphabet — keys of another type,
+// KeyQ, where the union needs more bits — and searches the base's keys, which stay as they are.  What Q-rebase (pdl_rekey.h) left:
+// per query record its key in the base's alphabet, or the flag that it has none (it holds a new letter: it equals no base rank);
+// up3: the three ranks the fold reads from the base's keys, in the union's alphabet.  Every comparison of the fold and of
+// q_describe is one between union ranks then; only the base searches take the record's key in the base's alphabet (q_base_key).
+template <class KeyB> struct QRebased { const KeyB *bkey; const uint8_t *none; const unsigned long long *up3; };
+template <class KeyB, class KeyQ> struct QViewRk {
+    QBase<KeyB> b;
+    const KeyQ *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
+    QRebased<KeyB> r;
+};
 
 // The base half of the fold (see the head of this file): bmax, and when the base folded its last record: r2, gs, p.
 // lonely: the base's last record is alone in its rank; has_r2: there is a group below it that it was folded into.
+// up3 (null: the query is ranked in the base's alphabet): bmax and the ranks of the base's last two records in the union's.
 template <class KeyT>
-__device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely, bool &has_r2) {
+__device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely, bool &has_r2, const unsigned long long *up3 = nullptr) {
     QFold f{};
     f.p = Q_NONE; f.qL = Q_NONE;
     const uint32_t U = b.U;
-    f.bmax = (unsigned long long) b.bkeys[b.M - 1];
+    f.bmax = f.bmax_b = (unsigned long long) b.bkeys[b.M - 1];
     lonely = U == 1;                      // (U == 1: nothing to fold it into)
     has_r2 = false;
     if (U == 1) f.p = 0;
@@ -135,8 +168,10 @@ __device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely,
         f.folded = (rl != f.bmax || rl2 != f.bmax) ? 1u : 0u;
         if (f.folded) {
             lonely = has_r2 = true;
-            f.r2 = rl != f.bmax ? rl : rl2;
+            const bool r2_last = rl != f.bmax;
+            f.r2 = r2_last ? rl : rl2;
             f.gs = b.template bbound<false>(0, U, f.r2);          // (p ranks above r2: the predicate rank < r2 stays monotone)
+            if (up3) f.r2 = r2_last ? up3[1] : up3[2];            // (behind the last search that takes it as a base key)
             const uint32_t gl = b.bvals[b.M - 1];                 // gene of the folded record; [gs, U) ascends by gene, p included
             uint32_t lo = f.gs, hi = U;
             while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (b.post[m].x < gl) lo = m + 1; else hi = m; }
@@ -144,6 +179,7 @@ __device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely,
             f.p = lo;
         }
     }
+    if (up3) f.bmax = up3[0];
     return f;
 }
 
@@ -178,20 +214,45 @@ __global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *ou
     q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.qkeys[v.qrecpos[j]]; }, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
     *out = f;
 }
+// ... of a query ranked in the union's alphabet: the base's ranks come re-keyed (v.r.up3)
+template <class KeyB, class KeyQ>
+__global__ void k_q_fold_rk(QViewRk<KeyB, KeyQ> v, const unsigned long long *ctl, QFold *out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    bool lonely, has_r2;
+    QFold f = q_fold_base(v.b, lonely, has_r2, v.r.up3);
+    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.qkeys[v.qrecpos[j]]; }, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
+    *out = f;
+}
 
 // The union group of query record j, one of the records [s0, s1) of its query (positions of qrank's index space).  The key is
 // taken relative to s0: the same for a query on its own and as a segment of a batch.
-template <class KeyT, class RankF>
-__device__ __forceinline__ QDesc q_describe(const QFold &f, const QBase<KeyT> &b, RankF qrank, uint32_t j, uint32_t s0, uint32_t s1) {
+// The rank record j's base searches look for, in the base's alphabet; none: there is no such rank (the record holds a letter the
+// base lacks).  bkey(i, none): record i's own.  A record the union folds (j == f.qL) looks for f.tgt, which is the base's bmax — its
+// key in the base's alphabet is kept beside it — or the rank of the query's last record but one, s1 - 2 (q_fold_union).
+template <class BKeyF>
+__device__ __forceinline__ unsigned long long q_base_key(const QFold &f, BKeyF bkey, uint32_t j, uint32_t s1, bool &none) {
+    none = false;
+    if (j != f.qL) return bkey(j, none);
+    return f.tgt == f.bmax ? f.bmax_b : bkey(s1 - 2, none);
+}
+// a query ranked in the base's alphabet: a record's rank is its base key
+template <class RankF> __device__ __forceinline__ auto q_same_alphabet(RankF qrank) {
+    return [qrank](uint32_t i, bool &) { return qrank(i); };
+}
+
+template <class KeyT, class RankF, class BKeyF>
+__device__ __forceinline__ QDesc q_describe(const QFold &f, const QBase<KeyT> &b, RankF qrank, BKeyF bkey, uint32_t j, uint32_t s0, uint32_t s1) {
     const unsigned long long eff = j == f.qL ? f.tgt : qrank(j);
+    bool none;
+    const unsigned long long beff = q_base_key(f, bkey, j, s1, none);
     QDesc d;
     d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
     if (f.folded) {
-        if (eff < f.r2) { d.blo = b.template bbound<false>(0, f.gs, eff); d.bhi = b.template bbound<true>(d.blo, f.gs, eff); }
+        if (eff < f.r2) { if (!none) { d.blo = b.template bbound<false>(0, f.gs, beff); d.bhi = b.template bbound<true>(d.blo, f.gs, beff); } }
         else if (eff == f.r2) { d.blo = f.gs; d.bhi = b.U; if (f.skip_p) d.bskip = f.p; }
         else if (eff == f.bmax) { d.blo = f.p; d.bhi = f.p + 1; }
-    } else {
-        d.blo = b.template bbound<false>(0, b.U, eff); d.bhi = b.template bbound<true>(d.blo, b.U, eff);
+    } else if (!none) {
+        d.blo = b.template bbound<false>(0, b.U, beff); d.bhi = b.template bbound<true>(d.blo, b.U, beff);
     }
     if (f.has_extra && eff == f.extra_target) d.bextra = f.p;
     const uint32_t qn = f.qL != Q_NONE ? s1 - 1 : s1;             // the searches among query records stay inside [s0, s1)
@@ -205,17 +266,19 @@ struct QMatchOut {
     QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
     unsigned long long *ctl;
 };
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf, QMatchOut o, uint64_t bound) {
+// k_q_match's body: qrank(i) / bkey(i, none) = record i's rank / its key in the base's alphabet (q_base_key)
+template <class KeyB, class RankF, class BKeyF>
+__device__ __forceinline__ void q_match_records(const QBase<KeyB> &b, const uint2 *qpost, RankF qrank, BKeyF bkey, const QFold *pf, const QMatchOut &o,
+                                                uint64_t bound) {
     const QFold f = *pf;
     const uint32_t Uq = (uint32_t) o.ctl[Q_CTL_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     if (j < Uq && j < bound) {
-        const QDesc d = q_describe(f, v.b, [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; }, j, 0u, Uq);
+        const QDesc d = q_describe(f, b, qrank, bkey, j, 0u, Uq);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
-        const uint32_t gene = v.qpost[j].x;
+        const uint32_t gene = qpost[j].x;
         o.gene_key[j] = gene;
         if (sz >= 2) { cost = sz; atomicAdd(&o.row_lookups[gene], sz); }
         matched = (j != f.qL && d.bhi > d.blo) ? 1ull : 0ull;
@@ -226,6 +289,16 @@ __global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf,
         if (cost) atomicAdd(&o.ctl[Q_CTL_COST], cost);
         if (matched) atomicAdd(&o.ctl[Q_CTL_MATCHED], matched);
     }
+}
+template <class KeyT>
+__global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf, QMatchOut o, uint64_t bound) {
+    const auto qrank = [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; };
+    q_match_records(v.b, v.qpost, qrank, q_same_alphabet(qrank), pf, o, bound);
+}
+template <class KeyB, class KeyQ>
+__global__ __launch_bounds__(256) void k_q_match_rk(QViewRk<KeyB, KeyQ> v, const QFold *pf, QMatchOut o, uint64_t bound) {
+    q_match_records(v.b, v.qpost, [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; },
+                    [&](uint32_t i, bool &none) { none = v.r.none[i] != 0; return (unsigned long long) v.r.bkey[i]; }, pf, o, bound);
 }
 
 // row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns); rows whose
@@ -579,6 +652,46 @@ static void q_block_ids(pdl_ctx *c, pdl_scores &r) {
     for (uint32_t g = 0; g < r.rows; g++) r.scoresMaxMappings[N + g] = (int32_t) g;
 }
 
+// Option "query_rekey": the verdict about the letters ONE query brings (256 bits, not empty) on its own — `who`: "query" /
+// "query 3:" — and, with `adopt`, the plan for exactly these letters in c->qb.rk.  Both alphabets must give exact ranks.
+static void q_rekey_verdict(pdl_ctx *c, const uint32_t letters[8], const char *who, bool adopt) {
+    uint32_t b = 0;
+    while (b < 255 && !((letters[b >> 5] >> (b & 31)) & 1u)) b++;
+    const char shown = (b >= 32 && b < 127) ? (char) b : '?';
+    const char *why = "";
+    if (!pdl_query_rekey_base_exact(c, &why))
+        PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s byte 0x%02x ('%c') is not in the base's alphabet, and the base's ranks are %s: option query_rekey needs exact ranks "
+                 "on the base's side and on the union's", who, b, shown, why);
+    if (!pdl_query_rekey_plan(c, letters, adopt, &why))
+        PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s byte 0x%02x ('%c') is not in the base's alphabet, and the union's ranks would be %s: option query_rekey needs exact "
+                 "ranks on the base's side and on the union's", who, b, shown, why);
+    uint32_t brought = 0;
+    for (int w = 0; w < 8; w++) brought += (uint32_t) __builtin_popcount(letters[w]);
+    pdl_query_rekey_info &ri = c->qrk_call;
+    ri.queries_rekeyed++;
+    ri.letters_max = std::max(ri.letters_max, c->rp.base + brought);
+}
+// ... and what a pass that ran with the plan of c->qb.rk adds to the call's report (the stream is waited for when the pass is timed)
+static void q_rekey_report(pdl_ctx *c, uint64_t records, bool rebased) {
+    pdl_query_rekey_info &ri = c->qrk_call;
+    ri.key_bits_max = std::max(ri.key_bits_max, c->qb.rk.rp.rank_bits);
+    ri.records_rebased += records;
+    if (rebased && c->opt_stage_timers) {
+        PDL_HIP(hipStreamSynchronize(c->stream));
+        ri.rebase_ms += c->qb.rk.span.total_ms();
+    }
+}
+static bool q_any_letter(const uint32_t letters[8]) {
+    uint32_t any = 0;
+    for (int w = 0; w < 8; w++) any |= letters[w];
+    return any != 0;
+}
+
+template <class KeyB>
+static QRebased<KeyB> q_rebased(pdl_ctx *c) {
+    auto &rk = c->qb.rk;
+    return QRebased<KeyB>{rk.bkey.as<KeyB>(), rk.none.as<uint8_t>(), rk.up3.as<unsigned long long>()};
+}
 template <class KeyT>
 static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
     QView<KeyT> v;
@@ -614,28 +727,65 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
     unsigned long long *ctl = q.ctl.as<unsigned long long>();
     PDL_HIP(hipMemsetAsync(ctl, 0, Q_CTL_WORDS * sizeof(uint64_t), st));
     genes.upload(c, residues);
-    pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
+    // option "query_rekey": the letters themselves come to the host before the dictionary is made; a query that brings one is
+    // ranked with the union's table (base letters + ALL its letters, genes shorter than k included, as a build counts them)
+    bool rekey = false;
+    if (c->opt_query_rekey && Rq) {
+        QLettersArgs la{};
+        la.res = q.res.as<uint8_t>(); la.n = Rq; la.letters = reinterpret_cast<uint32_t *>(ctl + Q_CTL_LETTERS);
+        for (int b = 0; b < 256; b++) if (c->alpha_present[b]) la.present[b >> 5] |= 1u << (b & 31);
+        hipLaunchKernelGGL(k_q_letters, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, la);
+        PDL_HIP(hipGetLastError());
+        uint32_t letters[8];
+        spans.end();
+        {
+            PinRead rd(c);
+            const uint32_t *pl = rd.add<uint32_t>(ctl + Q_CTL_LETTERS, 8);
+            rd.sync();
+            memcpy(letters, pl, sizeof(letters));
+        }
+        spans.begin();
+        if (q_any_letter(letters)) { q_rekey_verdict(c, letters, "query", true); rekey = true; }
+    }
+    if (!rekey) pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
+    const bool qkey64 = rekey ? q.rk.key64 : c->key64;
 
     // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look below)
     const void *qkeys = nullptr;
     if (Mq) {
-        const size_t kb = c->key64 ? 8 : 4;
+        const size_t kb = qkey64 ? 8 : 4;
         q.keys_a.alloc(Mq * kb); q.keys_b.alloc(Mq * kb); q.vals_a.alloc(Mq * 4); q.vals_b.alloc(Mq * 4);
         q.recpos.alloc((Mq + 1) * 4); q.post.alloc(Mq * 8);
-        qkeys = pdl_query_dictionary(c, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, Mq, Rq, q.keys_a.p, q.keys_b.p,
-                                     q.vals_a.as<uint32_t>(), q.vals_b.as<uint32_t>(), q.recpos.as<uint32_t>(), q.post.as<uint2>(),
+        qkeys = pdl_query_dictionary(c, rekey ? q.rk.rp : c->rp, qkey64, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, Mq, Rq,
+                                     q.keys_a.p, q.keys_b.p, q.vals_a.as<uint32_t>(), q.vals_b.as<uint32_t>(), q.recpos.as<uint32_t>(), q.post.as<uint2>(),
                                      reinterpret_cast<uint64_t *>(ctl + Q_CTL_RECORDS));
         q.fold.alloc(sizeof(QFold)); q.desc.alloc(Mq * sizeof(QDesc)); q.gkey.alloc(Mq * 8); q.rec_sorted.alloc(Mq * 8);
         q.row_lookups.alloc(n * 4ull); q.row_off.alloc((n + 1) * 4ull);
         PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
         QMatchOut mo{q.desc.as<QDesc>(), q.gkey.as<uint32_t>(), q.row_lookups.as<uint32_t>(), ctl};
         const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
-        pdl_with_key(c->key64, [&](auto key_tag) {
+        if (!rekey) pdl_with_key(c->key64, [&](auto key_tag) {
             using KeyT = decltype(key_tag);
             const QView<KeyT> v = q_view<KeyT>(c, qkeys);
             hipLaunchKernelGGL(k_q_fold<KeyT>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
             hipLaunchKernelGGL(k_q_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
         });
+        else {
+            // Q-rebase, then fold and match in two alphabets: the base's key type for its keys, the union's for the query's
+            pdl_query_rebase(c, qkeys, q.recpos.as<uint32_t>(), ctl + Q_CTL_RECORDS, Mq);
+            pdl_with_key(c->key64, [&](auto base_tag) {
+                using KeyB = decltype(base_tag);
+                pdl_with_key(qkey64, [&](auto query_tag) {
+                    using KeyQ = decltype(query_tag);
+                    const QView<KeyB> vb = q_view<KeyB>(c, nullptr);
+                    QViewRk<KeyB, KeyQ> v;
+                    v.b = vb.b; v.qkeys = static_cast<const KeyQ *>(qkeys); v.qrecpos = vb.qrecpos; v.qpost = vb.qpost;
+                    v.r = q_rebased<KeyB>(c);
+                    hipLaunchKernelGGL((k_q_fold_rk<KeyB, KeyQ>), dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
+                    hipLaunchKernelGGL((k_q_match_rk<KeyB, KeyQ>), grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
+                });
+            });
+        }
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the record indices by gene (the records are in (rank, gene) order)
         uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
@@ -697,6 +847,7 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
     } else {
         spans.end();
     }
+    if (rekey) q_rekey_report(c, Uq, Mq != 0);
     pdl_query_run run;
     run.Z = Z; run.cap = std::max<uint64_t>(bound, 1); run.residues = Rq; run.kmers = Mq; run.records = Uq; run.matched = matched; run.cost = cost;
     return run;

@@ -27,6 +27,11 @@
 // B-alpha .. B-order and the per-query counts are pdl_run_query_chunk_device: the cells stay in HBM.  pdl_query_batch follows
 // it with B-copy; K-place for a batch (pdl_place_batch.h) filters the cells where they lie instead.
 //
+// Option "query_rekey": B-alpha is qb_rekey_chunk — every query's absent bytes (k_qb_letters), the host's verdict per query and the
+// chunk's joint alphabet, the chunk cut where that would not be exact; a chunk whose queries bring a letter is ranked once with
+// the joint table, B-seg copies those keys, Q-rebase (pdl_rekey.h) runs over the segment positions and k_qb_fold_rk / k_qb_match_rk
+// take its output as the single query's do.  A chunk without a new letter takes the stages above untouched.
+//
 // Positions of query records (QDesc.qlo/qhi/qextra, QFold.qL) are positions in the segmented arrays of the chunk; QDesc.key is
 // taken relative to the segment start, so it is the single query's key.
 #pragma once
@@ -50,7 +55,8 @@ enum : uint32_t {
     QB_CTL_BOUND = 4,           // staging bound
     QB_CTL_MAY_OVERFLOW = 5,    // rows that may overflow (more lookups than the LDS table holds keys)
     QB_CTL_EMITTED = 6,         // emitted cells
-    QB_CTL_WORDS = 8,
+    QB_CTL_LETTERS = 8,         // option "query_rekey": 256 bits, the query's bytes that are not in the base's alphabet (4 words)
+    QB_CTL_WORDS = 12,
 };
 __device__ __forceinline__ unsigned long long *qb_ctl(unsigned long long *ctl, uint32_t q) { return ctl + QBG_WORDS + (size_t) q * QB_CTL_WORDS; }
 
@@ -70,6 +76,17 @@ __global__ __launch_bounds__(256) void k_qb_alpha(QBAlphaArgs a) {
         uint32_t lo = 0, hi = a.lay.nq;                       // last query q with res_begin[q] <= i (absent bytes are rare: searched only then)
         while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.lay.res_begin[m] <= i) lo = m; else hi = m; }
         atomicMax(qb_ctl(a.ctl, lo) + QB_CTL_BAD_BYTE, (unsigned long long) (256u - b));
+    }
+}
+
+// Option "query_rekey": every query's absent bytes themselves, 256 bits at its QB_CTL_LETTERS (as k_q_letters; the search as above)
+__global__ __launch_bounds__(256) void k_qb_letters(QBAlphaArgs a) {
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
+        const uint32_t b = a.res[i];
+        if ((a.present[b >> 5] >> (b & 31)) & 1u) continue;
+        uint32_t lo = 0, hi = a.lay.nq;
+        while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.lay.res_begin[m] <= i) lo = m; else hi = m; }
+        atomicOr(reinterpret_cast<uint32_t *>(qb_ctl(a.ctl, lo) + QB_CTL_LETTERS) + (b >> 5), 1u << (b & 31));
     }
 }
 
@@ -103,12 +120,24 @@ template <class KeyT> struct QBView {
     const uint32_t *seg_off, *qid_sorted;
 };
 
+// Option "query_rekey", a chunk whose queries bring letters the base lacks: the chunk is ranked once, in the base's letters plus
+// those of ALL its queries (a block is the same in whichever exact superset alphabet it was ranked); srank holds those keys, of
+// type KeyQ, and r what Q-rebase left for every segment position (pdl_query.h, QRebased).
+template <class KeyB, class KeyQ> struct QBViewRk {
+    QBase<KeyB> b;
+    const KeyQ *srank; const uint2 *spost;
+    const uint32_t *seg_off, *qid_sorted;
+    QRebased<KeyB> r;
+};
+
 // One thread per query: the base's fold (the same for all, computed by each) and the union's with this query's largest rank.
-template <class KeyT>
-__global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyT> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
+// up3: as q_fold_base takes it.
+template <class KeyB, class KeyQ>
+__device__ __forceinline__ void qb_fold_query(const QBase<KeyB> &b, const KeyQ *srank, const uint32_t *seg_off, const unsigned long long *up3, uint32_t nq,
+                                              unsigned long long *ctl, QFold *out) {
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
-    const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1];
+    const uint32_t s0 = seg_off[q], s1 = seg_off[q + 1];
     qb_ctl(ctl, q)[QB_CTL_RECORDS] = s1 - s0;
     if (s0 == s1) {                                               // no k-mer: no record reads the fold
         QFold f{};
@@ -117,17 +146,27 @@ __global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyT> v, uint32_t nq, uns
         return;
     }
     bool lonely, has_r2;
-    QFold f = q_fold_base(v.b, lonely, has_r2);
-    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.srank[j]; }, s0, s1);
+    QFold f = q_fold_base(b, lonely, has_r2, up3);
+    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) srank[j]; }, s0, s1);
     out[q] = f;
+}
+template <class KeyT>
+__global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyT> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
+    qb_fold_query(v.b, v.srank, v.seg_off, nullptr, nq, ctl, out);
+}
+template <class KeyB, class KeyQ>
+__global__ __launch_bounds__(64) void k_qb_fold_rk(QBViewRk<KeyB, KeyQ> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
+    qb_fold_query(v.b, v.srank, v.seg_off, v.r.up3, nq, ctl, out);
 }
 
 struct QBMatchOut {
     QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
     unsigned long long *ctl;
 };
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
+// k_qb_match's body over a view `v` (QBView, QBViewRk): qrank(i) / bkey(i, none) as q_match_records takes them
+template <class View, class RankF, class BKeyF>
+__device__ __forceinline__ void qb_match_records(const View &v, RankF qrank, BKeyF bkey, const QFold *folds, const QBLayout &lay, const QBMatchOut &o,
+                                                 uint64_t bound) {
     const uint32_t Ut = (uint32_t) o.ctl[QBG_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
@@ -135,7 +174,7 @@ __global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *f
     if (j < Ut && j < bound) {
         q = v.qid_sorted[j];
         const QFold f = folds[q];
-        const QDesc d = q_describe(f, v.b, [&](uint32_t i) { return (unsigned long long) v.srank[i]; }, j, v.seg_off[q], v.seg_off[q + 1]);
+        const QDesc d = q_describe(f, v.b, qrank, bkey, j, v.seg_off[q], v.seg_off[q + 1]);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
         const uint32_t gene = lay.gene_begin[q] + v.spost[j].x;
@@ -154,6 +193,16 @@ __global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *f
     if (q == Q_NONE) return;
     if (cost) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_COST, cost);
     if (matched) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_MATCHED, matched);
+}
+template <class KeyT>
+__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
+    const auto qrank = [&](uint32_t i) { return (unsigned long long) v.srank[i]; };
+    qb_match_records(v, qrank, q_same_alphabet(qrank), folds, lay, o, bound);
+}
+template <class KeyB, class KeyQ>
+__global__ __launch_bounds__(256) void k_qb_match_rk(QBViewRk<KeyB, KeyQ> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
+    qb_match_records(v, [&](uint32_t i) { return (unsigned long long) v.srank[i]; },
+                     [&](uint32_t i, bool &none) { none = v.r.none[i] != 0; return (unsigned long long) v.r.bkey[i]; }, folds, lay, o, bound);
 }
 
 // row_off[g] = first position of chunk gene g in the gene-sorted records; per query: staging bound = sum of
@@ -233,12 +282,76 @@ static QBView<KeyT> qb_view(pdl_ctx *c) {
     return v;
 }
 
-// The device half of one chunk, queries [qa, qe) of `qs`: B-alpha ... B-order and the per-query counts.  The ordered cells (five
+// Option "query_rekey", in front of a chunk [qa, qe): every query's letters come to the host (k_qb_letters over the chunk's bytes),
+// and the host decides.  Each query's own verdict uses its own union only (q_rekey_verdict: a refusal names the first such query).
+// The chunk is ranked with the base's letters plus those of all its queries if that alphabet is exact; where a query tips it
+// over, the chunk is cut in front of it (a chunk of one is a query's own union: exact, or refused).  -> the chunk's end; rekey:
+// its queries bring a letter and the plan for their joint letters is in c->qb.rk.  The stretch of device work is w.spans' first.
+static uint32_t qb_rekey_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
+                               bool &rekey) {
+    hipStream_t st = c->stream;
+    auto &w = c->qbb;
+    const uint32_t nq = qe - qa, ga = qs[qa].g0;
+    const uint64_t r0 = offsets[ga], Rq = offsets[qs[qe - 1].g0 + qs[qe - 1].n] - r0;
+    rekey = false;
+    w.spans.start(st);
+    if (!Rq) return qe;
+    std::vector<uint64_t> h_rbeg(nq + 1);
+    for (uint32_t q = 0; q < nq; q++) h_rbeg[q] = offsets[qs[qa + q].g0] - r0;
+    h_rbeg[nq] = Rq;
+    const size_t ctl_words = QBG_WORDS + (size_t) nq * QB_CTL_WORDS;
+    w.spans.begin();
+    w.ctl.alloc(ctl_words * sizeof(uint64_t));
+    unsigned long long *ctl = w.ctl.as<unsigned long long>();
+    PDL_HIP(hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint64_t), st));
+    w.res.alloc(Rq); w.res_begin.alloc((nq + 1) * 8ull);
+    PDL_HIP(hipMemcpyAsync(w.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.res_begin.p, h_rbeg.data(), (nq + 1) * 8ull, hipMemcpyHostToDevice, st));
+    QBAlphaArgs aa{};
+    aa.res = w.res.as<uint8_t>(); aa.n = Rq; aa.ctl = ctl;
+    aa.lay = QBLayout{nullptr, w.res_begin.as<uint64_t>(), nullptr, nq, 0};
+    for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
+    hipLaunchKernelGGL(k_qb_letters, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
+    PDL_HIP(hipGetLastError());
+    std::vector<uint64_t> h_ctl(ctl_words);
+    w.spans.end();
+    {
+        PinRead rd(c);
+        const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
+        rd.sync();
+        memcpy(h_ctl.data(), pc, ctl_words * sizeof(uint64_t));
+    }
+    uint32_t joint[8] = {};
+    const char *why = "";
+    const bool base_exact = pdl_query_rekey_base_exact(c, &why);
+    for (uint32_t q = 0; q < nq; q++) {
+        uint32_t own[8], with[8];
+        memcpy(own, &h_ctl[QBG_WORDS + (size_t) q * QB_CTL_WORDS + QB_CTL_LETTERS], sizeof(own));
+        if (!q_any_letter(own)) continue;
+        bool grows = false;
+        for (int i = 0; i < 8; i++) { with[i] = joint[i] | own[i]; grows = grows || with[i] != joint[i]; }
+        if (q > 0 && grows && base_exact && !pdl_query_rekey_plan(c, with, false, &why)) { qe = qa + q; break; }
+        char who[48];
+        snprintf(who, sizeof(who), "query %u:", qa + q);
+        q_rekey_verdict(c, own, who, false);
+        memcpy(joint, with, sizeof(joint));
+    }
+    if (q_any_letter(joint)) {
+        if (!pdl_query_rekey_plan(c, joint, true, &why)) PDL_FAIL(PDL_ERR_DEVICE, "query batch: the chunk's joint alphabet is not exact (%s)", why);
+        rekey = true;
+    }
+    return qe;
+}
+
+// The device half of one chunk, queries [qa, qe) of `qs` — with option "query_rekey" a prefix of them (qb_rekey_chunk), the
+// chunk's nq says how many: B-alpha ... B-order and the per-query counts.  The ordered cells (five
 // arrays of `cap`), MS and CM stay in c->qbb; the stretches of device work are c->qbb.spans (read once the stream has been waited for).
 pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
                                            uint32_t hbm_cols) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
+    bool rekey = false;
+    if (c->opt_query_rekey) qe = qb_rekey_chunk(c, residues, offsets, qs, qa, qe, rekey);
     const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
     const uint32_t nq = qe - qa, ga = qs[qa].g0, NT = qs[qe - 1].g0 + qs[qe - 1].n - ga;
     const uint64_t r0 = offsets[ga], Rq = offsets[ga + NT] - r0;
@@ -261,7 +374,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
     }
     h_off[NT] = Rq; h_koff[NT] = Mq; h_gbeg[nq] = NT; h_rbeg[nq] = Rq;
     QSpans &spans = w.spans;
-    spans.start(st);
+    if (!c->opt_query_rekey) spans.start(st);
     spans.begin();
 
     // B-alpha (and the chunk on its way to the device)
@@ -279,7 +392,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
     PDL_HIP(hipMemcpyAsync(w.res_begin.p, h_rbeg.data(), (nq + 1) * 8ull, hipMemcpyHostToDevice, st));
     PDL_HIP(hipMemcpyAsync(w.gene_query.p, h_gq.data(), NT * 4ull, hipMemcpyHostToDevice, st));
     const QBLayout lay{w.gene_begin.as<uint32_t>(), w.res_begin.as<uint64_t>(), w.gene_query.as<uint32_t>(), nq, NT};
-    if (Rq) {
+    if (Rq && !rekey) {                                              // (a chunk that is re-keyed has had its verdicts)
         QBAlphaArgs aa{};
         aa.res = w.res.as<uint8_t>(); aa.n = Rq; aa.lay = lay; aa.ctl = ctl;
         for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
@@ -291,13 +404,14 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
     w.rowid.alloc(NT * 4ull);
     const uint32_t *rec_sorted = nullptr;
     if (Mq) {
-        const size_t kb = c->key64 ? 8 : 4;
+        const bool qkey64 = rekey ? c->qb.rk.key64 : c->key64;
+        const size_t kb = qkey64 ? 8 : 4;
         w.keys_a.alloc(Mq * kb); w.keys_b.alloc(Mq * kb); w.vals_a.alloc(Mq * 4); w.vals_b.alloc(Mq * 4);
         w.recpos.alloc((Mq + 1) * 4); w.post.alloc(Mq * 8);
         const uint64_t *d_u = reinterpret_cast<const uint64_t *>(ctl + QBG_RECORDS);
-        const void *qkeys = pdl_query_dictionary(c, w.res.as<uint8_t>(), w.off.as<uint64_t>(), w.koff.as<uint64_t>(), NT, Mq, Rq, w.keys_a.p, w.keys_b.p,
-                                                 w.vals_a.as<uint32_t>(), w.vals_b.as<uint32_t>(), w.recpos.as<uint32_t>(), w.post.as<uint2>(),
-                                                 reinterpret_cast<uint64_t *>(ctl + QBG_RECORDS));
+        const void *qkeys = pdl_query_dictionary(c, rekey ? c->qb.rk.rp : c->rp, qkey64, w.res.as<uint8_t>(), w.off.as<uint64_t>(), w.koff.as<uint64_t>(), NT, Mq, Rq,
+                                                 w.keys_a.p, w.keys_b.p, w.vals_a.as<uint32_t>(), w.vals_b.as<uint32_t>(), w.recpos.as<uint32_t>(),
+                                                 w.post.as<uint2>(), reinterpret_cast<uint64_t *>(ctl + QBG_RECORDS));
         w.qkey.alloc(Mq * 8); w.perm.alloc(Mq * 8); w.srank.alloc(Mq * kb); w.spost.alloc(Mq * 8); w.seg_off.alloc((nq + 1) * 4ull);
         w.folds.alloc(nq * sizeof(QFold)); w.desc.alloc(Mq * sizeof(QDesc)); w.gkey.alloc(Mq * 8); w.rec_sorted.alloc(Mq * 8);
         w.row_lookups.alloc(NT * 4ull); w.row_off.alloc((NT + 1) * 4ull);
@@ -311,7 +425,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         PDL_HIP(hipGetLastError());
         pdl_sort_pairs<uint32_t, uint32_t>(c, qk_in, qk_out, pm_in, pm_out, Mq, std::max<uint32_t>(1, bit_length64(nq)), true, d_u, 0, true);
         QBMatchOut mo{w.desc.as<QDesc>(), w.gkey.as<uint32_t>(), w.row_lookups.as<uint32_t>(), ctl};
-        pdl_with_key(c->key64, [&](auto key_tag) {
+        if (!rekey) pdl_with_key(c->key64, [&](auto key_tag) {
             using KeyT = decltype(key_tag);
             QBView<KeyT> v = qb_view<KeyT>(c);
             v.qid_sorted = qk_out;
@@ -320,6 +434,24 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
                                w.srank.as<KeyT>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
             hipLaunchKernelGGL(k_qb_fold<KeyT>, dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
             hipLaunchKernelGGL(k_qb_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
+        });
+        else pdl_with_key(c->key64, [&](auto base_tag) {
+            // the segments in the chunk's joint alphabet, Q-rebase over the segment positions, fold and match in two alphabets
+            using KeyB = decltype(base_tag);
+            pdl_with_key(qkey64, [&](auto query_tag) {
+                using KeyQ = decltype(query_tag);
+                const QBView<KeyB> vb = qb_view<KeyB>(c);
+                QBViewRk<KeyB, KeyQ> v;
+                v.b = vb.b; v.srank = w.srank.as<KeyQ>(); v.spost = vb.spost; v.seg_off = vb.seg_off; v.qid_sorted = qk_out;
+                hipLaunchKernelGGL(k_qb_gather<KeyQ>, grid_m, dim3(256), 0, st, static_cast<const KeyQ *>(qkeys), (const uint32_t *) w.recpos.as<uint32_t>(),
+                                   (const uint2 *) w.post.as<uint2>(), (const uint32_t *) pm_out, (const uint32_t *) qk_out, (const unsigned long long *) ctl, lay,
+                                   w.srank.as<KeyQ>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
+                PDL_HIP(hipGetLastError());
+                pdl_query_rebase(c, w.srank.p, nullptr, ctl + QBG_RECORDS, Mq);
+                v.r = q_rebased<KeyB>(c);
+                hipLaunchKernelGGL((k_qb_fold_rk<KeyB, KeyQ>), dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
+                hipLaunchKernelGGL((k_qb_match_rk<KeyB, KeyQ>), grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
+            });
         });
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the segment positions by chunk gene
@@ -398,6 +530,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         spans.end();
     }
     ch.Z = Z;
+    if (rekey) q_rekey_report(c, Ut, Mq != 0);
     for (uint32_t q = 0; q < nq; q++) {
         ch.cells[q] = Ut ? hq(q, QB_CTL_EMITTED) : 0;
         ch.records[q] = hq(q, QB_CTL_RECORDS); ch.matched[q] = hq(q, QB_CTL_MATCHED); ch.cost[q] = hq(q, QB_CTL_COST);
@@ -464,7 +597,8 @@ uint32_t pdl_query_batch_plan(pdl_ctx *c, const uint64_t *offsets, const uint32_
     const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
     if (c->R + (offsets[n] - offsets[0]) >= 0xfffffff0ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^32 residues in the base and the batch need 64-bit stream positions");
     if (c->max_kseq >= (1ull << 20)) PDL_FAIL(PDL_ERR_UNSUPPORTED, "a base gene of %llu k-mers: queries need genes below 2^20 k-mers", (unsigned long long) c->max_kseq);
-    const size_t kb = c->key64 ? 8 : 4;
+    // (option "query_rekey": a chunk may be ranked with 64-bit keys over a 32-bit base, and Q-rebase leaves a base key and a flag per record)
+    const size_t kb = (c->key64 || c->opt_query_rekey) ? 8 : 4, rebased = c->opt_query_rekey ? (c->key64 ? 8 : 4) + 1 : 0;
     qs.assign(n_queries, QBQuery{});
     uint32_t n_max = 0;
     for (uint32_t q = 0; q < n_queries; q++) {
@@ -480,7 +614,7 @@ uint32_t pdl_query_batch_plan(pdl_ctx *c, const uint64_t *offsets, const uint32_
         if (Q.Mq >= 0x7ffff000ull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "query %u: %llu k-mers exceed the 31-bit record positions", q, (unsigned long long) Q.Mq);
         // what the stages hold per k-mer (two key and value halves, recpos, postings, the two index sorts, segment copies, group
         // descriptions) and per gene / column (maxima, row tables); staging and cells are sized once the match has counted them
-        Q.bytes = Q.Rq + Q.Mq * (3 * kb + 2 * 4 + 4 + 8 + 4 * 8 + 8 + sizeof(QDesc)) + ((uint64_t) N + Q.n) * (4 + column_bytes) + (uint64_t) Q.n * (G1 * 4ull + 48);
+        Q.bytes = Q.Rq + Q.Mq * (3 * kb + rebased + 2 * 4 + 4 + 8 + 4 * 8 + 8 + sizeof(QDesc)) + ((uint64_t) N + Q.n) * (4 + column_bytes) + (uint64_t) Q.n * (G1 * 4ull + 48);
         n_max = std::max(n_max, Q.n);
     }
     return N + n_max;
@@ -505,7 +639,7 @@ void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         const pdl_query_chunk ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);
         qb_copy_chunk(c, qs, qa, ch, out, info, &device_ms);
         chunks++;
-        qa = qe;
+        qa += ch.nq;                                              // (option "query_rekey" may have cut the chunk short of qe)
     }
     if (binfo) { binfo->queries = n_queries; binfo->chunks = chunks; binfo->device_ms = device_ms; }
 }

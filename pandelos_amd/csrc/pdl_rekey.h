@@ -18,6 +18,9 @@
 // A thread takes four consecutive keys (16-byte loads and stores; the streams start at allocations), its four digit chains
 // side by side; the m % 4 keys of the tail go one to a thread of the first workgroup.
 //
+// Q-rebase (option "query_rekey" of the query entry points, pdl_query.h) uses the same plan the other way round for single keys: a
+// query ranked in a superset alphabet has its records' keys written back into the base's (rk_one, k_q_rebase), see there.
+//
 // The host section is what an append and a removal share before the context changes (tools/rekey_host_check.cpp runs it without a
 // device): rank_init_host (the build's too), rk_exact, rk_plan, rk_change — the one decision: the same letters, a re-key, or a
 // target that is not exact — and the short_letters_* functions that keep pdl_ctx::h_short_letters.
@@ -27,16 +30,7 @@
 
 #include <cstring>
 
-constexpr int RK_THREADS = 256, RK_ITEMS = 4;
-
-struct RkArgs {
-    uint32_t k, base;           // of the keys that come in
-    uint32_t nparts, h;         // parts a key is cut into (1 for 32-bit keys), digits of every part but the last
-    uint64_t magic;             // RmDigits::magic of `base`
-    uint64_t part_div;          // B^h
-    uint64_t part_magic;        // floor(2^64 / B^h)
-    uint32_t entries;           // k * base
-};
+constexpr int RK_THREADS = 256, RK_ITEMS = 4;     // (RkArgs, the kernels' arguments: pdl_common.h)
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // The rank table of an alphabet: library.cpp:88-132, literally (64-bit wraparound included); adds rank_bits for the device sort and
@@ -119,6 +113,24 @@ inline bool rk_change(const RankParams &from, const uint8_t present_from[256], c
     if (!rk_exact(ch.rp)) return false;
     ch.args = rk_plan(from, present_from, ch.rp, ch.present, table);
     return ch.rekey = true;
+}
+
+// What queries that bring `letters` (256 bits, bytes the base lacks among them or not) decide about the alphabet they are ranked
+// in (option "query_rekey"): the base's letters plus theirs.  (base, present_base) is exact.  false: that union is not exact
+// (q.up.rp says why).  Else q.up is the change base -> union (q.up.rekey false: no new letter at all) with its forward table,
+// q.down / q.down_table the plan union -> base that Q-rebase reads — a new letter's entries are 0 there — and q.absent the
+// union's digits that are new letters.
+struct RkQuery { RkChange up; std::vector<uint64_t> up_table, down_table; RkArgs down{}; uint32_t absent[8] = {}; };
+inline bool rk_query(const RankParams &base, const uint8_t present_base[256], const uint32_t letters[8], RkQuery &q) {
+    uint8_t present_to[256];
+    for (int b = 0; b < 256; b++) present_to[b] = (present_base[b] || ((letters[b >> 5] >> (b & 31)) & 1u)) ? 1 : 0;
+    memset(q.absent, 0, sizeof(q.absent));
+    if (!rk_change(base, present_base, present_to, q.up_table, q.up)) return false;
+    if (!q.up.rekey) return true;
+    q.down = rk_plan(q.up.rp, q.up.present, base, present_base, q.down_table);
+    for (int b = 0; b < 256; b++)
+        if (present_to[b] && !present_base[b]) { const uint32_t d = q.up.rp.rank_values[b]; q.absent[d >> 5] |= 1u << (d & 31); }
+    return true;
 }
 
 // ---- the letters of genes shorter than k, per genome (256 bits each, pdl_ctx::h_short_letters): they show in no key, and a removal
@@ -223,6 +235,81 @@ static void pdl_rekey_stream(hipStream_t st, const KeyIn *in, KeyOut *out, uint6
     hipLaunchKernelGGL((k_rekey<KeyIn, KeyOut>), dim3((uint32_t) std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 4096)), dim3(RK_THREADS),
                        (size_t) a.entries * sizeof(KeyOut), st, in, out, m, a, d_table);
     PDL_HIP(hipGetLastError());
+}
+
+// ---- Q-rebase (option "query_rekey", pdl_query.h) ------------------------------------------------------------------------------
+// A query that brings letters the base lacks is ranked in the union's alphabet (B' letters); its records search the base's keys,
+// which stay in the base's (B letters).  The digit map base -> union is strictly increasing, so its inverse on the digits that
+// have one keeps order and equality: a query key written back digit by digit, key_b = sum inv[d_i] * B^i, compares with a base
+// key exactly as the two k-mers compare in the union — and a key with a digit that has no inverse (a new letter) equals no
+// base key at all.  That is said by a flag beside the key, not by a key value.
+//
+// One key taken apart as rk_items takes four: parts of h digits, a multiplication per digit, a table load and an add.
+// T[row + d] with row = i * base and d < base (a remainder), i < k: below entries = k * base whatever the key is.
+// `absent`: 256 bits over the digits, or null; hit = some digit of the key has its bit set.
+template <class KeyOut>
+__device__ __forceinline__ KeyOut rk_one(uint64_t x, const RkArgs &a, const KeyOut *T, const uint32_t *absent, bool &hit) {
+    uint64_t rest = x;
+    KeyOut y = 0;
+    uint32_t left = a.k, row = 0, seen = 0;
+    for (uint32_t p = 0; p < a.nparts; p++) {                       // (uniform: three parts at most)
+        const uint32_t nd = left < a.h ? left : a.h;
+        uint32_t part;
+        if (p + 1 < a.nparts) {
+            uint64_t q = __umul64hi(rest, a.part_magic);            // the quotient or one below it
+            uint64_t r = rest - q * a.part_div;
+            if (r >= a.part_div) { q++; r -= a.part_div; }
+            part = (uint32_t) r; rest = q;
+        } else part = (uint32_t) rest;                              // (the last part is below B^h <= 2^32)
+        for (uint32_t i = 0; i < nd; i++, row += a.base) {
+            const uint32_t q = (uint32_t) __umul64hi((uint64_t) part, a.magic);
+            const uint32_t d = part - q * a.base;                   // (< base: row + d < entries, d < 256)
+            y += T[row + d];
+            if (absent) seen |= (absent[d >> 5] >> (d & 31)) & 1u;
+            part = q;
+        }
+        left -= nd;
+    }
+    hit = seen != 0;
+    return y;
+}
+
+// The three ranks the fold reads from the base's keys (q_fold_base, pdl_query.h: bmax and the ranks of the last two records),
+// in the union's alphabet: up3[0 .. 3).  One thread, the forward table (rk_plan base -> union, 64-bit words) in global memory.
+// U >= 1 and M >= 1: the context is built.
+template <class KeyB>
+__global__ void k_q_up3(const KeyB *__restrict__ bkeys, const uint32_t *__restrict__ brecpos, uint32_t U, uint64_t M, RkArgs a,
+                        const uint64_t *__restrict__ table, unsigned long long *__restrict__ up3) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    bool hit;
+    up3[0] = rk_one<uint64_t>(bkeys[M - 1], a, table, nullptr, hit);
+    up3[1] = rk_one<uint64_t>(bkeys[brecpos[U - 1]], a, table, nullptr, hit);
+    up3[2] = U >= 2 ? rk_one<uint64_t>(bkeys[brecpos[U - 2]], a, table, nullptr, hit) : 0ull;
+}
+
+// Q-rebase: query record j (j below the record count on the device and below the host's bound, as k_q_match) has the union key
+// qkeys[recpos[j]] (recpos null: qkeys[j]); bkey[j] = that key in the base's alphabet, none[j] = 1 when it holds a new letter.
+// `a` / `table`: rk_plan union -> base (a new letter's entries are 0), the table in LDS; absent: the union's digits that are
+// new letters.  One thread a record: a query holds 1 / (G + 1) of the records.
+struct RkAbsent { uint32_t bits[8]; };
+template <class KeyQ, class KeyB>
+__global__ __launch_bounds__(RK_THREADS) void k_q_rebase(const KeyQ *__restrict__ qkeys, const uint32_t *__restrict__ recpos,
+                                                         const unsigned long long *__restrict__ d_records, uint64_t bound, RkArgs a,
+                                                         const KeyB *__restrict__ table, RkAbsent ab, KeyB *__restrict__ bkey,
+                                                         uint8_t *__restrict__ none) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rb_lds[];
+    __shared__ uint32_t s_absent[8];
+    KeyB *T = reinterpret_cast<KeyB *>(rb_lds);
+    for (uint32_t i = threadIdx.x; i < a.entries; i += RK_THREADS) T[i] = table[i];
+    if (threadIdx.x < 8) s_absent[threadIdx.x] = ab.bits[threadIdx.x];
+    pdl_sync();
+    const uint64_t records = *d_records, n = records < bound ? records : bound;
+    const uint64_t j = (uint64_t) blockIdx.x * RK_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t x = (uint64_t) (recpos ? qkeys[recpos[j]] : qkeys[j]);
+    bool hit;
+    bkey[j] = rk_one<KeyB>(x, a, T, s_absent, hit);
+    none[j] = hit ? 1 : 0;
 }
 
 // ---- the letters of genes shorter than k, per genome (256 bits each): they show in no key, and a removal must know them -----------

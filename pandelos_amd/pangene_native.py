@@ -274,6 +274,15 @@ class PangeneNative:
         self._check(self._lib.pdl_get_rekey_info(self._ctx, C.byref(info)))
         return info.as_dict()
 
+    @property
+    def last_query_rekey_info(self) -> dict:
+        """What the last successful ``query_scores`` / ``query_batch`` / ``place_query`` / ``place_batch`` did about letters the base
+        lacks (``pdl_get_query_rekey_info``; option ``query_rekey``): queries that brought one, letters and key bits of the base and
+        the most a query's union had, records written back into the base's alphabet and that pass's device time."""
+        info = _lib.PdlQueryRekeyInfo()
+        self._check(self._lib.pdl_get_query_rekey_info(self._ctx, C.byref(info)))
+        return info.as_dict()
+
     def _take_scores(self, s) -> Scores:
         try:
             z, rows, g, n = s.scoresCount, s.rows, s.genomes, s.sequences

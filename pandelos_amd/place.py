@@ -1,6 +1,6 @@
 """Place one newly sequenced genome into a pan-genome's gene families without committing it.
 
-    python -m pandelos_amd.place -i base.faa -k K -q new.faa -o new.tsv [--net new.net]
+    python -m pandelos_amd.place -i base.faa -k K -q new.faa -o new.tsv [--net new.net] [--rekey]
 
 The base set is ingested, its dictionary built and its families clustered once on the device; the query file (one genome, read
 like ``PangeneIData.readFromFile``) is scored against the dictionary, its block is filtered to the edges its own task adds to the
@@ -139,6 +139,7 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("-q", "--query", required=True, help="the new genome (.faa, one genome)")
     ap.add_argument("-o", "--output", required=True, help="one line per query gene: its family (.tsv)")
     ap.add_argument("--net", default=None, help="edges of the new genome's task (.net), as python -m pandelos_amd.query writes them")
+    ap.add_argument("--rekey", action="store_true", help="accept letters the base lacks: rank the query in the union's alphabet (option query_rekey)")
     args = ap.parse_args(argv)
 
     base = PangeneIData.read_from_file(args.input)          # (names, and the label check)
@@ -153,6 +154,8 @@ def main(argv: Sequence[str] | None = None) -> int:
     try:
         ing = nat.ingest_faa(args.input)
         nat.preprocess_ingested(args.kvalue)
+        if args.rekey:
+            nat.set_option("query_rekey", 1)
         pl = nat.place_idata(query)
         info = nat.last_place_info
     finally:

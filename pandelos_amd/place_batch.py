@@ -1,6 +1,6 @@
 """Place many newly sequenced genomes into a pan-genome's gene families in one pass, each on its own, without a commit.
 
-    python -m pandelos_amd.place_batch -i base.faa -k K -q new.faa [-q more.faa ...] --out-dir DIR [--net]
+    python -m pandelos_amd.place_batch -i base.faa -k K -q new.faa [-q more.faa ...] --out-dir DIR [--net] [--rekey]
 
 The base set is ingested, its dictionary built and its families clustered once on the device; every genome of the query files,
 in first-seen order, is an independent query of ``pdl_place_batch``: its placement is the one ``python -m pandelos_amd.place``
@@ -35,6 +35,7 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("-q", "--query", required=True, action="append", help="new genomes (.faa, one or more genomes); may be given several times")
     ap.add_argument("--out-dir", required=True, help="directory of the <label>.tsv (and <label>.net) files")
     ap.add_argument("--net", action="store_true", help="also write the edges of each genome's task (<label>.net)")
+    ap.add_argument("--rekey", action="store_true", help="accept letters the base lacks: rank the query in the union's alphabet (option query_rekey)")
     args = ap.parse_args(argv)
 
     base = PangeneIData.read_from_file(args.input)
@@ -48,6 +49,8 @@ def main(argv: Sequence[str] | None = None) -> int:
     try:
         ing = nat.ingest_faa(args.input)
         nat.preprocess_ingested(args.kvalue)
+        if args.rekey:
+            nat.set_option("query_rekey", 1)
         pls = nat.place_batch_idata([d for _, d in queries])
         info = nat.last_place_batch_info
     finally:

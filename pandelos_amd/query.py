@@ -1,6 +1,6 @@
 """Score one newly sequenced genome against a pan-genome's dictionary without a rebuild.
 
-    python -m pandelos_amd.query -i base.faa -k K -q new.faa -o new.net [--cells new.tsv]
+    python -m pandelos_amd.query -i base.faa -k K -q new.faa -o new.net [--cells new.tsv] [--rekey]
 
 The base set is ingested and its dictionary built once (``pdl_ingest_faa`` + ``pdl_preprocess_ingested``); the query file
 (one genome, read like ``PangeneIData.readFromFile``) is scored against it with ``pdl_query_scores``: the Scores block the
@@ -12,6 +12,9 @@ new genome are not part of it: their per-genome and per-column maxima change onl
 
 ``--cells`` writes every emitted cell as ``query_gene  target_gene  target_genome  score  perc  tr_perc`` (tab-separated,
 gene and genome names from the headers).
+
+A residue the base set lacks (one ``X``, ``U``, ``B``, ``Z`` or ``*``) is refused, since the union would rank k-mers differently;
+``--rekey`` (option ``query_rekey``) ranks the query in the union's alphabet instead and returns the union run's block.
 
 A query file that holds more than one genome (or none), or a genome whose label already names a base genome, is refused:
 in the union the genes of such a label would join that genome.
@@ -62,6 +65,7 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("-q", "--query", required=True, help="the new genome (.faa, one genome)")
     ap.add_argument("-o", "--output", required=True, help="edges of the new genome's task (.net)")
     ap.add_argument("--cells", default=None, help="every emitted cell of the new genome, with names (.tsv)")
+    ap.add_argument("--rekey", action="store_true", help="accept letters the base lacks: rank the query in the union's alphabet (option query_rekey)")
     args = ap.parse_args(argv)
 
     base = PangeneIData.read_from_file(args.input)          # (names for --cells and the label check)
@@ -76,6 +80,8 @@ def main(argv: Sequence[str] | None = None) -> int:
     try:
         ing = nat.ingest_faa(args.input)
         nat.preprocess_ingested(args.kvalue)
+        if args.rekey:
+            nat.set_option("query_rekey", 1)
         block = nat.query_idata(query)
         info = nat.last_query_info
     finally:

@@ -1,6 +1,6 @@
 """Score many newly sequenced genomes against a pan-genome's dictionary in one pass, each on its own.
 
-    python -m pandelos_amd.query_batch -i base.faa -k K -q new.faa [-q more.faa ...] --out-dir DIR [--cells]
+    python -m pandelos_amd.query_batch -i base.faa -k K -q new.faa [-q more.faa ...] --out-dir DIR [--cells] [--rekey]
 
 The base set is ingested and its dictionary built once; every genome of the query files, in first-seen order, is an
 independent query of ``pdl_query_batch``: its block is the one ``python -m pandelos_amd.query`` gets for that genome alone
@@ -69,6 +69,7 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("-q", "--query", required=True, action="append", help="new genomes (.faa, one or more genomes); may be given several times")
     ap.add_argument("--out-dir", required=True, help="directory of the <label>.net (and <label>.tsv) files")
     ap.add_argument("--cells", action="store_true", help="also write every emitted cell of each genome, with names (<label>.tsv)")
+    ap.add_argument("--rekey", action="store_true", help="accept letters the base lacks: rank the query in the union's alphabet (option query_rekey)")
     args = ap.parse_args(argv)
 
     base = PangeneIData.read_from_file(args.input)
@@ -82,6 +83,8 @@ def main(argv: Sequence[str] | None = None) -> int:
     try:
         ing = nat.ingest_faa(args.input)
         nat.preprocess_ingested(args.kvalue)
+        if args.rekey:
+            nat.set_option("query_rekey", 1)
         blocks = nat.query_batch_idata([d for _, d in queries])
         info = nat.last_query_batch_info
     finally:

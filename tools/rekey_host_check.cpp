@@ -8,7 +8,8 @@
 // No device is touched: the kernel's arithmetic (rk_items) is repeated here in 128-bit host integers and checked against plain
 // division, for alphabets of 1 .. 256 letters at the largest exact k and a few below, growing and shrinking.  The decision is the
 // library's own (rk_change, with the rank tables rank_init_host makes, as an append and a removal call it): a letter more or less
-// re-keys, the same letters do not, and the first k at which B^k leaves 64 bits is refused by it and by rk_exact alike.
+// re-keys, the same letters do not, and the first k at which B^k leaves 64 bits is refused by it and by rk_exact alike.  rk_query, the
+// decision of a query that brings a letter (option "query_rekey"), gives the same union, the same two plans and the new letter's digit.
 #include "../pandelos_amd/csrc/pdl_rekey.h"
 
 #include <cinttypes>
@@ -66,6 +67,11 @@ static uint64_t rekey_one(uint64_t x, const RkArgs &a, const std::vector<uint64_
         left -= nd;
     }
     return y;
+}
+
+static bool same_args(const RkArgs &a, const RkArgs &b) {
+    return a.k == b.k && a.base == b.base && a.nparts == b.nparts && a.h == b.h && a.magic == b.magic && a.part_div == b.part_div &&
+           a.part_magic == b.part_magic && a.entries == b.entries;
 }
 
 // the same k-mer (digits low first, as letters' indices in `letters`) as a key of an alphabet
@@ -134,6 +140,31 @@ int main() {
                     break;
                 }
             }
+            // what a query that brings `extra` decides (rk_query, option "query_rekey"): the same union and the same two plans, and
+            // the one digit of the union that is the new letter in `absent`; no letter at all is no re-key
+            uint32_t bits[8] = {}, no_bits[8] = {};
+            bits[extra >> 5] |= 1u << (extra & 31);
+            RkQuery rq, rn;
+            const uint32_t dx = rb.rank_values[extra];
+            bool one_bit = true;
+            if (rk_query(rs, small, bits, rq))
+                for (uint32_t d = 0; d < 256; d++) one_bit = one_bit && (((rq.absent[d >> 5] >> (d & 31)) & 1u) == (d == dx ? 1u : 0u));
+            if (!rq.up.rekey || !same_params(rq.up.rp, rb) || rq.up_table != up || rq.down_table != down || !same_args(rq.down, ad) || !same_args(rq.up.args, au) ||
+                !one_bit || !rk_query(rs, small, no_bits, rn) || rn.up.rekey) {
+                printf("B=%u k=%u: the query's decision differs from the append's and the removal's\n", B, k); failures++; break;
+            }
+            checked++;
+        }
+    }
+    {   // 18 letters at k = 15: one more is exact, two more are not — and the query's decision says so
+        uint8_t a18[256] = {};
+        for (int i = 0; i < 18; i++) a18[65 + i] = 1;
+        uint32_t one[8] = {}, two[8] = {};
+        one[3] = 1u << 0; two[3] = 3u;                                  // bytes 96, 97
+        RkQuery q1, q2;
+        const RankParams r18 = params_of(a18, 15);
+        if (!rk_exact(r18) || !rk_query(r18, a18, one, q1) || q1.up.rp.base != 19 || rk_query(r18, a18, two, q2) || q2.up.rp.base != 20 || rk_exact(q2.up.rp)) {
+            printf("18 letters at k = 15: 19 not taken or 20 taken for exact\n"); failures++;
         }
     }
     printf("%" PRIu64 " keys re-keyed up and down, %d failures\n", checked, failures);
