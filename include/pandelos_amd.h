@@ -547,6 +547,9 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"
  * off; 0: a histogram kernel and a three-launch scan for every pass.  Same results either way: for parity tests and A/B timing),
+ * "order_offsets" 0|1|2 (default 2: the cell offsets of a scoring pass with upper-triangle range lists come from one launch of
+ * several workgroups; 1: of one workgroup; 0: from two prefix scans, four launches.  Same results: for parity tests and A/B timing),
+ * "order_offsets_rows" n (that launch serves at most n task rows, default and maximum 131 072; tests lower it),
  * "aside_test_reload" 0|1 (test switch: the next scoring pass
  * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs),
  * "alphabet_rekey" 0|1 (default 0: pdl_append_genomes / pdl_remove_genomes go through where the alphabet changes, by writing the
@@ -603,8 +606,8 @@ typedef struct {
  *   -- caller: all-gather [records | genome_weights | genome_costs] --
  *   pdl_dist_preprocess_ranges         deals the genomes (as _finish would), builds + files the tuples of this run
  *   -- caller: all-gather [counts[world] | shared_records | groups | repeat_sample]; all-to-all the tuples (keys: 4 bytes, ranges:
- *      8 bytes, same split sizes); the runs into one device array as before (AFTER this call: it takes the group-head bits out of
- *      the run) --
+ *      8 bytes, same split sizes); the runs into one device array as before (this call only reads the run: the group-head bits
+ *      travel with it, every reader of a count masks bit 31; libraries before that took them out here, so the flow gathers AFTER) --
  *   pdl_dist_preprocess_finish_ranges  adopts the dictionary, sorts the received tuples (source-rank major) by gene
  *
  * `available` = 0 (gene ids beyond 22 bits, more than 256 ranks, a last run of exactly one record — the same verdict on every rank:

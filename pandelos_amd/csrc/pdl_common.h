@@ -21,6 +21,10 @@
 
 #define PDL_WAVE 64
 
+// A posting is {gene, count}; bit 31 of the count word says "opens a rank-group" (K-rle sets it, nothing takes it out): whoever
+// reads a count masks it.
+constexpr uint32_t PDL_COUNT_MASK = 0x7fffffffu;
+
 // The workgroup barrier of every kernel here: all LDS operations of the wave have COMPLETED before it arrives.
 // hipcc (ROCm 7.2, gfx950) leaves the `s_waitcnt lgkmcnt(0)` out in front of an `s_barrier` when the wave needs no LDS result
 // any more — e.g. behind a run of no-return LDS atomics or stores — relying on the LDS pipe serving the CU's waves in order.
@@ -397,7 +401,7 @@ struct pdl_ctx {
     DevBuf keys_a, keys_b, vals_a, vals_b, sort_tmp;
     bool key64 = false;
     DevBuf recpos;        // u32 [U+1] position of each record's first occurrence in the sorted stream
-    DevBuf post;          // uint2 [U] {seq, count}  — the dictionary postings, rank-group major (bit 31 of count: opens a rank-group, until K-ranges removes it)
+    DevBuf post;          // uint2 [U] {seq, count}  — the dictionary postings, rank-group major (bit 31 of count: opens a rank-group; it stays, readers mask it)
     DevBuf ranges;        // uint4 [U'] {group start, group length, own count, 0}, gene major
     const uint2 *ranges8 = nullptr;   // packed 8-byte ranges (inside `scratch`, the gene sort's output) when the dataset allows: see GroupTileArgs::pay8
     DevBuf head_bits;     // u64 [U / 64] "opens a rank-group" per record, kept by K-ranges for the per-gene costs made on demand
@@ -410,7 +414,9 @@ struct pdl_ctx {
     bool opt_low_memory = false;          // batches of genomes on a large set: build buffers released after the dictionary, small HBM tables for tier 3
     bool reshard_pending = false;         // pdl_set_genome_shard named genomes the range lists on the device do not cover: they are built before the next scoring pass
     bool opt_onepass_scan = false;        // scans in one launch (decoupled look-back) instead of three: measured 3-10 % slower per scan on MI355X, kept as an option
-    bool opt_lean_radix = true;           // radix passes: offsets in one launch (k_rs_offsets), the rank sort's first histogram filed by K-rank; 0: a histogram and a three-launch scan per pass
+    int opt_order_offsets = 2;            // K-order's two offset scans: 2 = one launch of several workgroups (k_order_offsets), 1 = of one workgroup, 0 = the four launches of two scans
+    uint32_t opt_order_offsets_rows = 1u << 17;   // ... for at most so many task rows (at most OO_MAX_ROWS; tests lower it)
+    bool opt_lean_radix = true;          // radix passes: offsets in one launch (k_rs_offsets), the rank sort's first histogram filed by K-rank; 0: a histogram and a three-launch scan per pass
     DevBuf scratch;       // transient buffers of the range build
     DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*, above)
 

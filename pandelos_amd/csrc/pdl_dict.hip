@@ -706,9 +706,8 @@ static RangeBufs carve_ranges(pdl_ctx *c, const RangePlan &p, uint64_t cap, uint
     return b;
 }
 
-// Where a WRITE pass writes: the ranges into b (k_group_write; k_range_scatter is told its own), and the head bits it takes out
-// of the postings, which are kept: for the per-gene costs made on demand (packed ranges), and to put them back when the ranges
-// are built again for another shard of genomes (pdl_run_reshard).
+// Where a WRITE pass writes: the ranges into b (k_group_write; k_range_scatter is told its own), and its copy of the postings'
+// head bits, one bit per record: for the per-gene costs made on demand (packed ranges).
 static void set_write_targets(pdl_ctx *c, GroupTileArgs &ga, const RangeBufs &b) {
     c->head_bits.alloc(((ga.n_bound + GW_TILE - 1) / GW_TILE) * GW_ROUNDS * sizeof(uint64_t));
     ga.head_bits = c->head_bits.as<unsigned long long>();
@@ -839,15 +838,12 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
 
 // ---- the ranges again, for another shard of genomes, on the dictionary that is there ---------------------------------------------
 // (scoring a large set a batch of genomes at a time: the postings — rank, sort, dedup, most of the build — are made once; a batch
-// costs the two passes over the postings that form its genes' range lists.)  The WRITE pass took the group-head bits out of the
-// postings; they are put back from the copy it kept, the counters of the range stage start at zero again.
+// costs the two passes over the postings that form its genes' range lists.)  The postings are as the first build left them,
+// group-head bits included (a WRITE pass only reads them); the counters of the range stage start at zero again.
 void pdl_run_reshard(pdl_ctx *c) {
-    hipStream_t st = c->stream;
     if (c->dist || c->post_ext) PDL_FAIL(PDL_ERR_STATE, "genome shard: a multi-GPU context deals the genomes itself");
     if (c->dict_shard.empty() || c->upper_only) PDL_FAIL(PDL_ERR_STATE, "genome shard: the dictionary was built for all genomes; set the first shard before pdl_preprocess");
-    const uint32_t n = (uint32_t) c->U;
     ev_begin(c, EV_PRE_TOTAL);
-    hipLaunchKernelGGL(k_restore_heads, dim3((n + 255) / 256), dim3(256), 0, st, c->post.as<uint2>(), c->head_bits.as<unsigned long long>(), n);
     clear_ctl(c, PDL_CTL_RANGES, PDL_CTL_RANGES);
     clear_ctl(c, PDL_CTL_COUNTERS, PDL_CTL_LAST);
     clear_genome_words(c);

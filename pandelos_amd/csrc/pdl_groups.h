@@ -14,11 +14,12 @@
 //   count  per-thread code: ranges per tile, first / last head of every tile, counters.  k_range_count<MODE>, or
 //          k_range_count_hist: + a workgroup's ranges counted by the low byte of their gene (the gene sort's first histogram)
 //   (scan of the counts: k_tile_prefix + k_scan_tile_scan, or the radix offsets)
-//   write  extents as in the costs kernel, but a write pass removes the head bits of its own tile, so the groups that cross
-//          the borders are found in the per-tile heads the count pass left (gt_tile_borders): no tile reads a bit another may
-//          have removed.  k_group_write<MODE> files {gene, range} in record order; k_range_scatter (single-GPU build: upper
+//   write  extents as in the costs kernel; the groups that cross the borders are found in the per-tile heads the count pass
+//          left (gt_tile_borders: two coalesced reads issued with the tile's own loads).  The postings are only read: the head
+//          bits stay in them (the next genome batch counts and writes from them again; the joins mask bit 31 of a count).
+//          k_group_write<MODE> files {gene, range} in record order; k_range_scatter (single-GPU build: upper
 //          ranges, packed) ranks them by the low byte of the gene and files them as the gene sort's first pass would
-//   k_gene_costs_lazy, k_restore_heads   read the head bits a write pass kept (GroupTileArgs::head_bits)
+//   k_gene_costs_lazy   reads the copy of the head bits a write pass filed, one bit per record (GroupTileArgs::head_bits)
 //
 // MODE 0: whole groups for the genes of a shard | 1: the postings above the record, every gene | 2: those, for the genes of
 // a shard.  The gt_* bodies are shared by the kernels named in their comments: arrays by reference, no LDS of their own.
@@ -111,7 +112,7 @@ struct GroupTileArgs {
     uint32_t *key2; uint4 *tuples;              // write: sort key (gene) and the 16-byte range tuple, or ...
     unsigned long long *pay8;                   // ... (non-null) the packed 8-byte range (gt_pack_range), carried through the gene sort
                                                 //     as its payload: no gather afterwards
-    unsigned long long *head_bits;              // write: [tiles * 16] the head bits it removes from the postings, kept for the lazy cost pass
+    unsigned long long *head_bits;              // write: [tiles * 16] the head bits of the postings, one per record, filed for the lazy cost pass
     uint32_t pos_base;                          // write, packed ranges: added to every first posting (a run of a multi-GPU build: its place in the gathered dictionary)
     unsigned long long *cost;                   // per-gene total_visited (library.cpp:327): last members (write), all shared records (costs, RECORD_COSTS)
     unsigned long long *counters;               // costs, count: [0] += records in groups >= 2, [1] += such groups, [3] += records whose k-mer repeats inside its gene (count);
@@ -232,8 +233,8 @@ __device__ __forceinline__ void gt_head_masks(const uint2 (&po)[GW_ROUNDS], uint
     for (int j = 0; j < GW_ROUNDS; j++) m[j] = __ballot(t0 + j * PDL_WAVE + lane < n && (po[j].y >> 31));
 }
 
-// Write side, the groups that cross the tile's borders: other waves may have removed their tiles' head bits already, so
-// the count pass's per-tile heads answer — the nearest tile before / after with a head, 64 tiles per look.
+// Write side, the groups that cross the tile's borders: the count pass's per-tile heads answer — the nearest tile before /
+// after with a head, 64 tiles per look (two coalesced reads, where a look at the records around the tile is a dependent walk).
 // gt_load_borders issues the first look (with the tile's own loads); gt_tile_borders gives `before` (head of the group
 // that runs into the tile) and `after` (end of the group that runs out of it), wave-uniform.  (write, k_range_scatter)
 __device__ __forceinline__ void gt_load_borders(const GroupTileArgs &a, uint32_t tile, uint32_t tiles, uint32_t lane, uint32_t &hb, uint32_t &ha) {
@@ -292,13 +293,12 @@ __device__ __forceinline__ void gt_round_extent(unsigned long long mj, uint32_t 
     if (mj) pr = r0 + 63u - (uint32_t) __clzll((long long) mj);
 }
 
-// Write side of a round: the head bit leaves the posting (it has done its job) and stays in head_bits for the lazy cost
-// pass and a reshard.  Returns the record's own count.  (write, k_range_scatter)
-__device__ __forceinline__ uint32_t gt_take_head(const GroupTileArgs &a, uint32_t tile, int j, uint32_t u, bool live, uint32_t y, unsigned long long mj, uint32_t lane) {
-    const uint32_t cnt = y & ~HEAD_BIT;
-    if (live && (y >> 31)) a.post[u].y = cnt;
+// Write side of a round: the round's head bits are filed in head_bits for the lazy cost pass; the postings are only read
+// (the bit stays where K-rle put it: clearing it made the pass write back every line of the postings it had just read, and
+// whoever reads a count masks it).  Returns the record's own count.  (write, k_range_scatter)
+__device__ __forceinline__ uint32_t gt_take_head(const GroupTileArgs &a, uint32_t tile, int j, uint32_t y, unsigned long long mj, uint32_t lane) {
     if (a.head_bits && lane == 0) a.head_bits[(size_t) tile * GW_ROUNDS + j] = mj;
-    return cnt;
+    return y & PDL_COUNT_MASK;
 }
 
 // the packed 8-byte range: first posting | (postings + (min(own count, 1023) << 22)) << 32
@@ -398,12 +398,6 @@ __global__ __launch_bounds__(256) void k_gene_costs_lazy(const uint2 *__restrict
     }
     if (ge - gs >= 2) atomicAdd(&cost[post[u].x], (unsigned long long) (ge - gs));
 }
-// the head bits back into the postings (the ranges are built again, for another shard of genomes)
-__global__ __launch_bounds__(256) void k_restore_heads(uint2 *__restrict__ post, const unsigned long long *__restrict__ head_bits, uint32_t n) {
-    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= n) return;
-    if ((head_bits[u >> 6] >> (u & 63u)) & 1ull) post[u].y |= HEAD_BIT;          // (word layout: record >> 6, see k_gene_costs_lazy)
-}
 
 // ---- count ---------------------------------------------------------------------------------------------------------------------
 // Per-thread code (the mask arithmetic of the costs / write kernels keeps a wave's uniform values in vector registers and
@@ -499,7 +493,7 @@ __global__ __launch_bounds__(GW_THREADS) void k_group_write(GroupTileArgs a) {
             bool r = shared && mine;
             if constexpr (MODE == 1 || MODE == 2) r = r && u + 1 < ge;           // the last member of a group has nothing above it
             const unsigned long long rb = __ballot(r);
-            const uint32_t cnt = gt_take_head(a, tile, j, u, live, po[j].y, m[j], lane);
+            const uint32_t cnt = gt_take_head(a, tile, j, po[j].y, m[j], lane);
             if (live) {
                 if (shared && mine) own_lookups += ge - gs;
                 if (r) {
@@ -566,7 +560,7 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_scatter(GroupTileArgs a, u
             const bool live = u < n;
             const bool shared = live && ge - gs >= 2;
             const bool r = shared && u + 1 < ge;         // the last member of a group has nothing above it
-            const uint32_t cnt = gt_take_head(a, tile, j, u, live, po[j].y, m[j], lane);
+            const uint32_t cnt = gt_take_head(a, tile, j, po[j].y, m[j], lane);
             if (shared) own_lookups += ge - gs;
             val[j] = gt_pack_range(u + 1, ge - u - 1, cnt, 0u);
             rbits |= (uint32_t) r << j;

@@ -380,7 +380,7 @@ __global__ __launch_bounds__(T_, (FILTER && HT_BITS_ <= 10) ? 5 : (FILTER && T_ 
         if (packed) {                                        // (uniform) {first posting, postings | min(own, 1023) << 22}: the group is named by its end
             gsv = gm.x + (gm.y & 0x3fffffu);
             gm.y >>= 22;
-            if (__builtin_expect(gm.y == 1023u && live, 0)) gm.y = a.post[gm.x - 1].y;       // (rare) the k-mer occurs >= 1023 times in this gene; (a dead lane holds no range)
+            if (__builtin_expect(gm.y == 1023u && live, 0)) gm.y = a.post[gm.x - 1].y & PDL_COUNT_MASK;       // (rare) the k-mer occurs >= 1023 times in this gene; (a dead lane holds no range)
         } else gsv = s_gsv[r];
     };
     auto walk = [&](uint32_t total, auto &&fn4) {
@@ -459,6 +459,8 @@ __global__ __launch_bounds__(T_, (FILTER && HT_BITS_ <= 10) ? 5 : (FILTER && T_ 
             PH_WAIT(); PH_MARK(5);
 #pragma unroll
             for (uint32_t u = 0; u < NCH; u++) po[u] = a.post[live[u] ? adr[u] : 0u];     // dead lanes (last chunk) read posting 0: no exec juggling
+#pragma unroll
+            for (uint32_t u = 0; u < NCH; u++) po[u].y &= PDL_COUNT_MASK;                 // (a group's head keeps its bit: MODE 0 gathers it)
             PH_WAIT(); PH_MARK(6);
 #ifdef PDL_JOIN_CHECK
             if (*(volatile uint32_t *) &s_rowseq != my_seq) atomicAdd(a.error_count, 1000000u);
@@ -800,7 +802,7 @@ __global__ __launch_bounds__(HBM_THREADS) void k_join_hbm(JoinArgs a) {
             if (a.ranges8) {
                 const uint2 r8 = a.ranges8[e];
                 uint32_t own = r8.y >> 22;
-                if (own == 1023u) own = a.post[r8.x - 1].y;
+                if (own == 1023u) own = a.post[r8.x - 1].y & PDL_COUNT_MASK;
                 rg = make_uint4(r8.x, r8.y & 0x3fffffu, own, 0u);
                 group_key = rg.x + rg.y;
             } else {
@@ -809,7 +811,8 @@ __global__ __launch_bounds__(HBM_THREADS) void k_join_hbm(JoinArgs a) {
             }
             const uint32_t finv = 0xffffffffu - group_key;
             for (uint32_t q = lane; q < rg.y; q += PDL_WAVE) {
-                const uint2 po = a.post[rg.x + q];
+                uint2 po = a.post[rg.x + q];
+                po.y &= PDL_COUNT_MASK;
                 const uint32_t c = po.x;
                 if (ld_agent(&t_first[c]) < finv) {
                     const uint32_t old = atomicMax(&t_first[c], finv);
@@ -1319,6 +1322,109 @@ struct FinOffApply {
     uint32_t *fin_off;
     __device__ void operator()(uint64_t p, uint32_t, uint32_t prefix) const { fin_off[p] = prefix; }
 };
+// K-order's offsets in ONE launch (mirror mode, up to OO_MAX_ROWS rows): fin_off[p] = cells (own + mirrored) of the rows before
+// p, m_off[p] = their mirrored cells, and the two totals — what scan_and_apply(RowCntFlag) + scan_and_apply(MirrorCntFlag) make
+// in four dependent launches that are nearly all launch cost at these sizes.  Both prefixes ride in one u64 (cells << 32 |
+// mirrored: each total stays below 2^32, nothing carries across).  A workgroup owns `span` rows (a multiple of OO_TILE; one
+// workgroup: all of them): it adds up the raw counts in front of its part itself (L2-resident, at most 2 x 4 x OO_MAX_ROWS bytes),
+// then scans its part OO_TILE rows at a time, four consecutive rows per thread.  Nobody waits for another workgroup.
+constexpr uint32_t OO_THREADS = 1024, OO_ITEMS = 4, OO_TILE = OO_THREADS * OO_ITEMS;
+// The bound: the last workgroup reads all counts in front of it, 1 MiB at 2^17 rows — about 7 us from L2 for one CU, half of
+// the three launches the kernel saves; beyond it the scans' parallel tiles are the better tool.
+constexpr uint32_t OO_MAX_ROWS = 1u << 17;
+__device__ __forceinline__ unsigned long long oo_pack(uint32_t cells, uint32_t mirrored) { return ((unsigned long long) cells << 32) + mirrored; }
+// exclusive prefix of v over the workgroup's OO_THREADS threads, the workgroup's sum in `total`; `extra` is added up over the
+// workgroup behind the same barriers (extra_total)
+__device__ __forceinline__ unsigned long long oo_block_scan(unsigned long long v, unsigned long long extra, unsigned long long *s_wave /* [17] */,
+                                                            unsigned long long *s_extra /* [16] */, unsigned long long &total, unsigned long long &extra_total) {
+    constexpr uint32_t NW = OO_THREADS / PDL_WAVE;
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1), wave = threadIdx.x / PDL_WAVE;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < PDL_WAVE; d <<= 1) {
+        const unsigned long long o = __shfl_up(inc, d, PDL_WAVE);
+        if (lane >= (uint32_t) d) inc += o;
+    }
+#pragma unroll
+    for (int d = PDL_WAVE / 2; d > 0; d >>= 1) extra += __shfl_xor(extra, d, PDL_WAVE);
+    if (lane == PDL_WAVE - 1) { s_wave[wave] = inc; s_extra[wave] = extra; }
+    pdl_sync();
+    if (threadIdx.x < PDL_WAVE) {                            // (the first wave, whole: the 16 wave sums)
+        const unsigned long long w = lane < NW ? s_wave[lane] : 0ull;
+        unsigned long long winc = w, e = lane < NW ? s_extra[lane] : 0ull;
+#pragma unroll
+        for (int d = 1; d < (int) NW; d <<= 1) {
+            const unsigned long long o = __shfl_up(winc, d, PDL_WAVE);
+            if (lane >= (uint32_t) d) winc += o;
+        }
+#pragma unroll
+        for (int d = (int) NW / 2; d > 0; d >>= 1) e += __shfl_xor(e, d, PDL_WAVE);
+        if (lane < NW) s_wave[lane] = winc - w;
+        if (lane == NW - 1) s_wave[16] = winc;
+        if (lane == 0) s_extra[0] = e;
+    }
+    pdl_sync();
+    const unsigned long long res = inc - v + s_wave[wave];
+    total = s_wave[16]; extra_total = s_extra[0];
+    pdl_sync();
+    return res;
+}
+__global__ __launch_bounds__(OO_THREADS) void k_order_offsets(const uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ mirror_cnt, uint32_t n_rows,
+                                                              uint32_t span, uint32_t *__restrict__ fin_off, uint32_t *__restrict__ m_off,
+                                                              uint64_t *d_emitted, uint64_t *d_mirrored) {
+    __shared__ unsigned long long s_wave[17], s_extra[16];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t r0 = min(blockIdx.x * span, n_rows), r1 = min(r0 + span, n_rows);
+    unsigned long long carry = 0;                            // cells | mirrored cells of the rows before the current trip
+    for (uint32_t base = r0; base < r1; base += OO_TILE) {   // (uniform: barriers inside)
+        const uint32_t i0 = base + tid * OO_ITEMS;
+        const bool whole = i0 + OO_ITEMS <= r1;              // (16-byte loads: both arrays start an allocation, i0 is a multiple of four)
+        uint32_t f[OO_ITEMS], m[OO_ITEMS];
+        if (whole) {
+            const uint4 rc = *reinterpret_cast<const uint4 *>(row_cnt + i0), mc = *reinterpret_cast<const uint4 *>(mirror_cnt + i0);
+            m[0] = mc.x; m[1] = mc.y; m[2] = mc.z; m[3] = mc.w;
+            f[0] = rc.x + mc.x; f[1] = rc.y + mc.y; f[2] = rc.z + mc.z; f[3] = rc.w + mc.w;
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < OO_ITEMS; j++) {
+                const bool live = i0 + j < r1;
+                m[j] = live ? mirror_cnt[i0 + j] : 0u;
+                f[j] = live ? row_cnt[i0 + j] + m[j] : 0u;
+            }
+        }
+        // first trip: the rows in front of the part, 16 bytes a load and sixteen loads in flight per thread (one load at a time,
+        // each waited for, took 19 us for 45 000 rows: latency, not bytes); 32-bit sums: the totals stay below 2^32
+        uint32_t pc = 0, pm = 0;
+        if (base == r0) {
+            const uint32_t n4 = r0 / 4;                      // (r0 is a multiple of four: span is one of OO_TILE)
+            const uint4 *rc4 = reinterpret_cast<const uint4 *>(row_cnt), *mc4 = reinterpret_cast<const uint4 *>(mirror_cnt);
+#pragma unroll 8
+            for (uint32_t i = tid; i < n4; i += OO_THREADS) {
+                const uint4 a = rc4[i], b = mc4[i];
+                pc += a.x + a.y + a.z + a.w; pm += b.x + b.y + b.z + b.w;
+            }
+        }
+        unsigned long long sum = 0, total, front;
+#pragma unroll
+        for (uint32_t j = 0; j < OO_ITEMS; j++) sum += oo_pack(f[j], m[j]);
+        unsigned long long ex = oo_block_scan(sum, oo_pack(pc + pm, pm), s_wave, s_extra, total, front);
+        carry += front;
+        ex += carry;
+#pragma unroll
+        for (uint32_t j = 0; j < OO_ITEMS; j++) {
+            if (i0 + j < r1) { fin_off[i0 + j] = (uint32_t) (ex >> 32); m_off[i0 + j] = (uint32_t) ex; }
+            ex += oo_pack(f[j], m[j]);
+        }
+        carry += total;
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) {           // the last part ends the rows: its carry is the totals
+        const uint32_t cells = (uint32_t) (carry >> 32);
+        *d_emitted = cells;
+        fin_off[n_rows] = cells; fin_off[n_rows + 1] = 0u;   // (the total closes fin_off; written as a u64 in two words, as the scan does)
+        *d_mirrored = (uint32_t) carry;
+    }
+}
+
 // dst[0..n) = src[idx[..]]; then the join counters and the emitted-cell total (u64 as two words) are appended (PDL_JT_*), so
 // the host fetches everything it wants to know after a scoring pass with ONE copy
 __global__ void k_gather_u32(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t *dst, const uint32_t *ctr, const uint32_t *z64) {
@@ -1725,13 +1831,21 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
     uint32_t *ctr32 = c->join_ctr.as<uint32_t>();
     ev_begin(c, EV_ORDER);
     const uint32_t *d_mcnt = pl.mirror ? c->mirror_cnt.as<uint32_t>() : nullptr;
-    // the scan's total (all emitted cells, < 2^32) also closes fin_off: the low word of the u64 lands in fin_off[n_rows]
-    scan_and_apply(c, n_rows, RowCntFlag{c->row_cnt.as<uint32_t>(), d_mcnt}, FinOffApply{c->fin_off.as<uint32_t>()}, d_scal + PDL_CTL_EMITTED,
-                   reinterpret_cast<uint64_t *>(c->fin_off.as<uint32_t>() + n_rows));
+    // mirror mode, a row count within the bound: both offset arrays and both totals from k_order_offsets; else the scans
+    const bool one_launch = pl.mirror && c->opt_order_offsets != 0 && n_rows > 0 && n_rows <= std::min(c->opt_order_offsets_rows, OO_MAX_ROWS);
+    if (one_launch) {
+        const uint32_t span = c->opt_order_offsets == 1 ? (n_rows + OO_TILE - 1) / OO_TILE * OO_TILE : OO_TILE;        // one workgroup, or one per OO_TILE rows
+        hipLaunchKernelGGL(k_order_offsets, dim3((n_rows + span - 1) / span), dim3(OO_THREADS), 0, st, c->row_cnt.as<uint32_t>(), d_mcnt, n_rows, span,
+                           c->fin_off.as<uint32_t>(), c->mirror_cnt.as<uint32_t>() + n_rows, d_scal + PDL_CTL_EMITTED, d_scal + PDL_CTL_MIRRORED);
+    } else {
+        // the scan's total (all emitted cells, < 2^32) also closes fin_off: the low word of the u64 lands in fin_off[n_rows]
+        scan_and_apply(c, n_rows, RowCntFlag{c->row_cnt.as<uint32_t>(), d_mcnt}, FinOffApply{c->fin_off.as<uint32_t>()}, d_scal + PDL_CTL_EMITTED,
+                       reinterpret_cast<uint64_t *>(c->fin_off.as<uint32_t>() + n_rows));
+    }
     OrderArgs o{};
     if (pl.mirror) {
         uint32_t *m_off = c->mirror_cnt.as<uint32_t>() + n_rows, *m_cur = m_off + n_rows;
-        scan_and_apply(c, n_rows, MirrorCntFlag{d_mcnt}, FinOffApply{m_off}, d_scal + PDL_CTL_MIRRORED);
+        if (!one_launch) scan_and_apply(c, n_rows, MirrorCntFlag{d_mcnt}, FinOffApply{m_off}, d_scal + PDL_CTL_MIRRORED);
         MirrorArgs ma{};
         set_staged_cells(ma, staged_cells(c));
         ma.taskpos_of = c->taskpos_of.as<uint32_t>(); ma.mirror_off = m_off; ma.mirror_cur = m_cur; ma.n_rows = n_rows;

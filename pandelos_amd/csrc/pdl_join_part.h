@@ -418,10 +418,10 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                             // a count >= 2 on either side (rare; an own count of 1023 stands for "1023 or more"): the lookup keeps its column in
                             // whatever else is seen of it (it adds the threshold); it is entered as an ordinary sighting, and what its counts add
                             // beyond (1, 1, 1) is listed.  No room in the list: the cycle is void, and the counter is left alone (it cannot overflow)
-                            if (live[u] && (po[u].y >= 2u || ((ownhv >> u) & 1u))) {
+                            if (live[u] && ((po[u].y & PDL_COUNT_MASK) >= 2u || ((ownhv >> u) & 1u))) {
                                 const uint32_t i = atomicAdd(&s_nheavy, 1u);
                                 add = i < PT_HEAVY_CAP ? sift_t : 0u;
-                                if (i < PT_HEAVY_CAP) s_heavy[i] = make_uint2(key[it * PT_NCH + u], po[u].y);
+                                if (i < PT_HEAVY_CAP) s_heavy[i] = make_uint2(key[it * PT_NCH + u], po[u].y & PDL_COUNT_MASK);
                             }
                             if (live[u]) atomicAdd(&s_cnt[ci >> 1], add << ((ci & 1u) << 4));
                         }
@@ -434,10 +434,10 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                         wd[u] = h >> PT_BM_SHIFT; bit[u] = 1u << ((h >> (PT_BM_SHIFT - 5)) & 31u);        // (the column alone: a column two rows of the cycle meet once each survives the sift and is told apart later)
                         seen[u] = live[u] ? atomicOr(&s_bm1[wd[u]], bit[u]) : 0u;
                         // a count >= 2 on either side: the lookup survives the sift by itself (both bits set); entered and listed as above
-                        if (live[u] && (po[u].y >= 2u || ((ownhv >> u) & 1u))) {
+                        if (live[u] && ((po[u].y & PDL_COUNT_MASK) >= 2u || ((ownhv >> u) & 1u))) {
                             seen[u] = bit[u];
                             const uint32_t i = atomicAdd(&s_nheavy, 1u);
-                            if (i < PT_HEAVY_CAP) s_heavy[i] = make_uint2(key[it * PT_NCH + u], po[u].y);
+                            if (i < PT_HEAVY_CAP) s_heavy[i] = make_uint2(key[it * PT_NCH + u], po[u].y & PDL_COUNT_MASK);
                         }
                     }
 #pragma unroll
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(TT, WGS) void k_join_part(JoinArgs a) {
                 if ((hv.x >> 10) == hk && slot_of(hv.x & 1023u) == sl) {
                     const uint2 g = s_gm[hv.x & 1023u];
                     uint32_t own = g.y >> 22;
-                    if (own == 1023u) own = a.post[g.x - 1].y;
+                    if (own == 1023u) own = a.post[g.x - 1].y & PDL_COUNT_MASK;       // (the record in front of a range can be its group's head)
                     s_min += min(hv.y, own) - 1u; s_own += own - 1u; s_cc += hv.y - 1u;
                 }
             }

@@ -317,7 +317,7 @@ class DistributedPangenes:
         weights, costs = allv[:, 1:1 + G].sum(axis=0), allv[:, 1 + G:1 + 2 * G].sum(axis=0)
         total = int(offs[-1])
         self.exchange_s["dictionary"] = time.perf_counter() - t0
-        # the range tuples of my run, filed by owner (takes the group-head bits out of the run: the runs travel afterwards)
+        # the range tuples of my run, filed by owner (it only reads the run: the group-head bits travel with it)
         made = nat.dist_preprocess_ranges(run_records, weights, costs) if self.use_sender else None
         self.sender_ranges = made is not None
         t0 = time.perf_counter()
@@ -440,7 +440,7 @@ class LocalRanks:
         self.run_records = [rec for _, rec, _ in runs]
         weights = np.sum([n.run_weights for n in self.ranks], axis=0) if self.exchange_weights else None
         made = None
-        if self.sender_ranges:               # every rank: the tuples of its run, by owner (before the runs are "gathered": it takes their head bits out)
+        if self.sender_ranges:               # every rank: the tuples of its run, by owner (before the runs are "gathered", as ever; the call only reads them)
             costs = np.sum([n.run_costs for n in self.ranks], axis=0)
             made = [n.dist_preprocess_ranges(self.run_records, weights, costs) for n in self.ranks]
             assert all(m is None for m in made) or all(m is not None for m in made), "ranks disagree on who builds the range lists"
@@ -569,7 +569,7 @@ class RanksInTurn:
         self.used_sender_ranges = sender
         full0 = torch.cat(saved) if total else torch.zeros(1, dtype=torch.int64, device=dev)
         del saved
-        full = full0 if sender else torch.empty_like(full0)     # the owners' finish works in place (head bits, the fold of the last record): a fresh copy per rank
+        full = full0 if sender else torch.empty_like(full0)     # the owners' finish works in place (the fold of the last record): a fresh copy per rank
         if sender:
             tmat, sums = np.stack(tcounts), np.sum(ctrs, axis=0)
             self.tuple_counts = tmat
