@@ -257,6 +257,13 @@ template <class F> inline decltype(auto) pdl_with_key(bool key64, F &&f) {
     if (key64) return f(uint64_t{});
     return f(uint32_t{});
 }
+// ... and of a base's keys beside those of a superset alphabet's (option "query_rekey"): f(KeyB{}, KeyQ{}).  B'^k >= B^k, so
+// 64-bit base keys never meet 32-bit union keys: that pair is not instantiated, and seeing it is an error of the plan.
+template <class F> inline void pdl_with_keys_up(bool base64, bool union64, F &&f) {
+    if (base64 && !union64) PDL_FAIL(PDL_ERR_DEVICE, "query_rekey: the base's keys are 64 bits wide and the union's 32 — a superset alphabet cannot need fewer");
+    if (!union64) f(uint32_t{}, uint32_t{});
+    else pdl_with_key(base64, [&](auto key_b) { f(key_b, uint64_t{}); });
+}
 
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
@@ -814,7 +821,7 @@ void pdl_run_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
 // ... and of callers' lists on a caller's base: n_query [n_queries], edge_begin [n_queries + 1] from 0, the lists end to end on the device
 void pdl_run_place_batch_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_queries, const uint32_t *n_query, const uint64_t *edge_begin,
                                const int32_t *d_src, const int32_t *d_dst, std::vector<pdl_place_result> &out);
-void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad);      // k_q_alpha over device bytes (pdl_query.h)
+void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad);      // k_q_absent over device bytes (pdl_query.h)
 [[noreturn]] void pdl_fail_absent_byte(uint64_t bad_word, const char *who);                             // ... and the refusal that names the byte
 // K-append (pdl_append.h, pdl_dict.hip): the n genes of residues/offsets become genes N.. of the context; genome_ids [n] are their
 // union genome ids (checked by the caller), n_new_genomes of them new.  pdl_extend_layout (pdl_api.hip): the host's genome layout.

@@ -1052,18 +1052,16 @@ void pdl_query_rebase(pdl_ctx *c, const void *qkeys, const uint32_t *recpos, con
     memcpy(ab.bits, rk.absent, sizeof(ab.bits));
     const bool timed = c->opt_stage_timers;
     rk.span.start(st);
-    pdl_with_key(c->key64, [&](auto key_b) {
+    pdl_with_keys_up(c->key64, rk.key64, [&](auto key_b, auto key_q) {
         using KeyB = decltype(key_b);
+        using KeyQ = decltype(key_q);
         hipLaunchKernelGGL(k_q_up3<KeyB>, dim3(1), dim3(64), 0, st, (const KeyB *) c->keys_b.as<KeyB>(), (const uint32_t *) c->recpos.as<uint32_t>(),
                            (uint32_t) c->U, c->M, rk.up, (const uint64_t *) rk.up_table.as<uint64_t>(), rk.up3.as<unsigned long long>());
         if (!bound) return;
         if (timed) rk.span.begin();
-        pdl_with_key(rk.key64, [&](auto key_q) {
-            using KeyQ = decltype(key_q);
-            hipLaunchKernelGGL((k_q_rebase<KeyQ, KeyB>), dim3((uint32_t) ((bound + RK_THREADS - 1) / RK_THREADS)), dim3(RK_THREADS),
-                               (size_t) rk.down.entries * sizeof(KeyB), st, static_cast<const KeyQ *>(qkeys), recpos, d_records, bound, rk.down,
-                               (const KeyB *) rk.down_table.as<KeyB>(), ab, rk.bkey.as<KeyB>(), rk.none.as<uint8_t>());
-        });
+        hipLaunchKernelGGL((k_q_rebase<KeyQ, KeyB>), dim3((uint32_t) ((bound + RK_THREADS - 1) / RK_THREADS)), dim3(RK_THREADS),
+                           (size_t) rk.down.entries * sizeof(KeyB), st, static_cast<const KeyQ *>(qkeys), recpos, d_records, bound, rk.down,
+                           (const KeyB *) rk.down_table.as<KeyB>(), ab, rk.bkey.as<KeyB>(), rk.none.as<uint8_t>());
         if (timed) rk.span.end();
     });
     PDL_HIP(hipGetLastError());
@@ -1099,7 +1097,7 @@ static void rekey_in_place(pdl_ctx *c, uint64_t m, bool from_key64, const RkArgs
 // ------------------------------------------------------------------------------------------------
 // K-append (pdl_append_genomes): new genes join the dictionary that is there.
 //
-//   A-alpha   k_q_alpha (pdl_query.h)   the new bytes against the base's letters — the only refusal that needs the device, so
+//   A-alpha   k_q_absent (pdl_query.h)  the new bytes against the base's letters — the only refusal that needs the device, so
 //                                       it comes first: until the host has read its word the context is untouched
 //   A-len     (host)                    kseq_len / k-mer offsets of the new genes; kseq_len, cost, genome ids grown to N + n
 //   A-dict    k_rank / k_rank_hash + pdl_sort_pairs on the m new k-mers with the base's RankParams (gene values 0..n-1)
@@ -1152,7 +1150,7 @@ void pdl_run_append(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     // A-alpha (and the new genes on their way to the device): the context is only read
     spans.begin();
     const bool rekey_on = c->opt_alphabet_rekey;
-    constexpr size_t A_HIST = 16;             // q.ctl: [0] the smallest absent byte (k_q_alpha) | [16, 272) K-hist of the new residues (rekey_on)
+    constexpr size_t A_HIST = 16;             // q.ctl: [0] the smallest absent byte (k_q_absent) | [16, 272) K-hist of the new residues (rekey_on)
     q.ctl.alloc((A_HIST + 256) * sizeof(uint64_t));
     unsigned long long *d_bad = q.ctl.as<unsigned long long>();
     PDL_HIP(hipMemsetAsync(d_bad, 0, (rekey_on ? A_HIST + 256 : 1) * sizeof(uint64_t), st));

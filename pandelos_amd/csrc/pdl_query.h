@@ -4,24 +4,28 @@
 // Contract: the block computeScores(G) (library.cpp:409-527) returns for the UNION run — base genes 0..N-1, then the n query
 // genes as genome G with ids N..N+n-1, same k.  The base context is only read.
 //
-//   Q-alpha  k_q_alpha          query bytes against the base's letter-presence table (an absent letter changes the union's
+//   Q-alpha  k_q_absent         query bytes against the base's letter-presence table (an absent letter changes the union's
 //                               rank table, library.cpp:96-119): the smallest offending byte
 //   Q-dict   pdl_query_dictionary (pdl_dict.hip)   K-rank with the base's RankParams, K-sort, K-rle: query records
 //                               (rank, gene, count) in (rank, gene) order
 //   Q-fold   k_q_fold           one thread: the base's last-record fold (k_fold_last_record) and the union's (Q1 below)
 //   Q-match  k_q_match          per query record: its union group as base slice(s) + query slice(s), binary searches
+//                               (both over one view, QView<KeyB, KeyQ, RK>: the base's key type, the query's, and whether the query
+//                               is re-keyed — below; a plain query is <KeyT, KeyT, false>, chosen on the host by q_with_keys)
 //   Q-rows   gene sort of the records (pdl_sort_pairs) + k_q_row_off: each query gene's records, in rank order
 //   Q-join   k_q_join           one workgroup per query gene, LDS hash keyed by column; rows whose columns do not fit go to
 //            k_q_join_hbm       the same row program on direct-addressed tables in HBM
 //   Q-order  k_order_rows_wave / k_order_rows   the reference's emission order (chunk, first group, column)
 //
-// Option "query_rekey" (default off: the stages above, launched as ever).  On, Q-alpha is k_q_letters — the absent bytes themselves,
-// 256 bits, read by the host before Q-dict — and a query that brings one takes these stages instead:
+// Option "query_rekey" (default off: the stages above, launched as ever).  On, Q-alpha is k_q_absent<LETTERS> — the absent bytes
+// themselves, 256 bits, read by the host before Q-dict — and a query that brings one takes the same stages with RK set:
 //   Q-dict   with the UNION's RankParams and key width (rk_query, pdl_rekey.h: base letters + all the query's)
 //   Q-rebase k_q_up3, k_q_rebase (pdl_rekey.h)   the fold's three base ranks written up into the union's alphabet; every query
 //                               record's key written back into the base's, with a flag where it holds a new letter
-//   Q-fold   k_q_fold_rk        Q-match  k_q_match_rk   the same fold and description over union ranks; only the searches in
-//                               the base's keys take the record's rebased key (q_base_key), and none for a flagged record
+//   Q-fold, Q-match  <KeyB, KeyQ, true>: the same fold and description over union ranks; the view's up3() and bkey(i, none) hand
+//                               them what Q-rebase left — only the searches in the base's keys take the record's rebased key
+//                               (q_base_key), and none for a flagged record.  (KeyB, KeyQ) is (u32, u32), (u32, u64) or (u64, u64):
+//                               a superset alphabet never needs fewer bits (pdl_with_keys_up, pdl_common.h)
 // Q-rows, Q-join and Q-order read no key: they are the same launches.  The digit map between an alphabet and a superset of it
 // is strictly increasing, so order and equality of k-mers are the same on both sides.
 //
@@ -84,34 +88,49 @@ enum : uint32_t {
     Q_CTL_WORDS = 16,
 };
 
-// *bad = max(256 - byte) over the absent bytes (0: none), i.e. 256 - the smallest absent byte
-struct QAlphaArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; unsigned long long *bad; };
-__global__ __launch_bounds__(256) void k_q_alpha(QAlphaArgs a) {
+// Q-alpha: the bytes of `res` that the base's alphabet lacks — rare, so everything but the table test sits behind it.
+//   LETTERS   false: the word at `words` is raised to 256 - byte, i.e. it ends as 256 - the smallest absent byte (0: none)
+//             true:  the byte's bit is set in the 256 bits (32-bit words) at `words` (option "query_rekey")
+//   BATCH     the words are those of the query the byte belongs to: `stride` words further per query, the query found by a
+//             search of res_begin [nq + 1] (pdl_query_batch.h); false: one query, one atomic a thread
+struct QAbsentArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; const uint64_t *res_begin; uint32_t nq, stride; unsigned long long *words; };
+template <bool LETTERS, bool BATCH>
+__global__ __launch_bounds__(256) void k_q_absent(QAbsentArgs a) {
     uint32_t worst = 0;
     for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
         const uint32_t b = a.res[i];
-        if (!((a.present[b >> 5] >> (b & 31)) & 1u)) worst = max(worst, 256u - b);
+        if ((a.present[b >> 5] >> (b & 31)) & 1u) continue;
+        unsigned long long *w = a.words;
+        if constexpr (BATCH) {
+            uint32_t lo = 0, hi = a.nq;                           // last query q with res_begin[q] <= i
+            while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.res_begin[m] <= i) lo = m; else hi = m; }
+            w += (size_t) lo * a.stride;
+        }
+        if constexpr (LETTERS) atomicOr(reinterpret_cast<uint32_t *>(w) + (b >> 5), 1u << (b & 31));
+        else if constexpr (BATCH) atomicMax(w, (unsigned long long) (256u - b));
+        else worst = max(worst, 256u - b);
     }
-    if (worst) atomicMax(a.bad, (unsigned long long) worst);
+    if constexpr (!LETTERS && !BATCH) if (worst) atomicMax(a.words, (unsigned long long) worst);
 }
-// Option "query_rekey": the absent bytes themselves, 256 bits at `letters` (32-bit words).  The common path stays the table test; an
-// absent byte — rare — sets its bit.
-struct QLettersArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; uint32_t *letters; };
-__global__ __launch_bounds__(256) void k_q_letters(QLettersArgs a) {
-    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
-        const uint32_t b = a.res[i];
-        if (!((a.present[b >> 5] >> (b & 31)) & 1u)) atomicOr(&a.letters[b >> 5], 1u << (b & 31));
-    }
+// the base's letters as the scan tests them: 256 bits
+static void q_present_bits(const pdl_ctx *c, uint32_t present[8]) {
+    for (int w = 0; w < 8; w++) present[w] = 0;
+    for (int b = 0; b < 256; b++) if (c->alpha_present[b]) present[b >> 5] |= 1u << (b & 31);
 }
-// Host side of the letter check, shared with the append (pdl_dict.hip): queue k_q_alpha over n device bytes; the word it leaves
-// at d_bad is turned into the refusal by pdl_fail_absent_byte (`who`: "query" / "appended").
-void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad) {
+// ... and its launch over n device bytes (none: nothing is queued)
+template <bool LETTERS, bool BATCH>
+static void q_scan_absent(pdl_ctx *c, const uint8_t *d_res, uint64_t n, const uint64_t *d_res_begin, uint32_t nq, uint32_t stride, unsigned long long *d_words) {
     if (!n) return;
-    QAlphaArgs aa{};
-    aa.res = d_res; aa.n = n; aa.bad = d_bad;
-    for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
-    hipLaunchKernelGGL(k_q_alpha, dim3((uint32_t) std::min<uint64_t>((n + 255) / 256, 1024)), dim3(256), 0, c->stream, aa);
+    QAbsentArgs a{};
+    a.res = d_res; a.n = n; a.res_begin = d_res_begin; a.nq = nq; a.stride = stride; a.words = d_words;
+    q_present_bits(c, a.present);
+    hipLaunchKernelGGL((k_q_absent<LETTERS, BATCH>), dim3((uint32_t) std::min<uint64_t>((n + 255) / 256, 1024)), dim3(256), 0, c->stream, a);
     PDL_HIP(hipGetLastError());
+}
+// The letter check shared with the append (pdl_dict.hip): the word the scan leaves at d_bad is turned into the refusal by
+// pdl_fail_absent_byte (`who`: "query" / "appended").
+void pdl_check_alphabet(pdl_ctx *c, const uint8_t *d_res, uint64_t n, unsigned long long *d_bad) {
+    q_scan_absent<false, false>(c, d_res, n, nullptr, 1, 0, d_bad);
 }
 void pdl_fail_absent_byte(uint64_t bad_word, const char *who) {
     const uint32_t b = 256u - (uint32_t) bad_word;
@@ -126,8 +145,8 @@ __device__ __forceinline__ uint32_t q_bound(RankF rank, uint32_t lo, uint32_t hi
     return lo;
 }
 
-// The base's postings as the searches see them.  The query records come with a rank accessor of the caller's — position ->
-// rank over the caller's index space: k_q_fold / k_q_match read keys[recpos[j]], the batch (pdl_query_batch.h) its segment copy.
+// The base's postings as the searches see them.  The query records come with the accessors of a view (below) over its own index
+// space: QView reads keys[recpos[j]], the batch's QBView (pdl_query_batch.h) its segment copy.
 template <class KeyT> struct QBase {
     const KeyT *bkeys; const uint32_t *brecpos; const uint32_t *bvals; const uint2 *post; uint32_t U; uint64_t M;
     __device__ unsigned long long brank(uint32_t u) const { return (unsigned long long) bkeys[brecpos[u]]; }
@@ -135,20 +154,29 @@ template <class KeyT> struct QBase {
         return q_bound<UPPER>([&](uint32_t u) { return brank(u); }, lo, hi, v);
     }
 };
-template <class KeyT> struct QView {
-    QBase<KeyT> b;
-    const KeyT *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
-};
 // Option "query_rekey", a query that brings letters the base lacks: it is ranked in the union's alphabet — keys of another type,
 // KeyQ, where the union needs more bits — and searches the base's keys, which stay as they are.  What Q-rebase (pdl_rekey.h) left:
 // per query record its key in the base's alphabet, or the flag that it has none (it holds a new letter: it equals no base rank);
 // up3: the three ranks the fold reads from the base's keys, in the union's alphabet.  Every comparison of the fold and of
 // q_describe is one between union ranks then; only the base searches take the record's key in the base's alphabet (q_base_key).
 template <class KeyB> struct QRebased { const KeyB *bkey; const uint8_t *none; const unsigned long long *up3; };
-template <class KeyB, class KeyQ> struct QViewRk {
+// ... as a view holds it: `r` when the query is re-keyed (RK), nothing at all — an empty base — when it is not
+template <class KeyB, bool RK> struct QRebasedIf { QRebased<KeyB> r; };
+template <class KeyB> struct QRebasedIf<KeyB, false> {};
+// What a view (QView here, QBView of pdl_query_batch.h) gives the fold and the description besides `b`, over its own index space
+// of query records — here the records themselves, keys[recpos[i]]:
+//   qrank(i)        record i's rank in the alphabet the query is ranked in
+//   bkey(i, none)   its key in the base's alphabet (none: it has no such key); !RK: qrank(i), always one
+//   up3()           QRebased::up3; !RK: null
+template <class KeyB, class KeyQ, bool RK> struct QView : QRebasedIf<KeyB, RK> {
     QBase<KeyB> b;
     const KeyQ *qkeys; const uint32_t *qrecpos; const uint2 *qpost;
-    QRebased<KeyB> r;
+    __device__ unsigned long long qrank(uint32_t i) const { return (unsigned long long) qkeys[qrecpos[i]]; }
+    __device__ unsigned long long bkey(uint32_t i, bool &none) const {
+        if constexpr (RK) { none = this->r.none[i] != 0; return (unsigned long long) this->r.bkey[i]; }
+        else { none = false; return qrank(i); }
+    }
+    __device__ const unsigned long long *up3() const { if constexpr (RK) return this->r.up3; else return nullptr; }
 };
 
 // The base half of the fold (see the head of this file): bmax, and when the base folded its last record: r2, gs, p.
@@ -183,18 +211,18 @@ __device__ __forceinline__ QFold q_fold_base(const QBase<KeyT> &b, bool &lonely,
     return f;
 }
 
-// The union half: Q1's cases (a)-(d) for the query whose records are the positions [s0, s1) (not empty) of qrank's index
+// The union half: Q1's cases (a)-(d) for the query whose records are the positions [s0, s1) (not empty) of the view's index
 // space; f.qL is a position of that space.
-template <class RankF>
-__device__ __forceinline__ void q_fold_union(QFold &f, bool lonely, bool has_r2, RankF qrank, uint32_t s0, uint32_t s1) {
+template <class View>
+__device__ __forceinline__ void q_fold_union(QFold &f, bool lonely, bool has_r2, const View &v, uint32_t s0, uint32_t s1) {
     const uint32_t Uq = s1 - s0;
-    const unsigned long long qmax = qrank(s1 - 1);
-    const bool alone = Uq == 1 || qrank(s1 - 2) != qmax;
+    const unsigned long long qmax = v.qrank(s1 - 1);
+    const bool alone = Uq == 1 || v.qrank(s1 - 2) != qmax;
     if (qmax > f.bmax) {
         f.skip_p = f.folded;
         if (alone) {
             f.qL = s1 - 1;
-            const unsigned long long q2 = Uq >= 2 ? qrank(s1 - 2) : 0ull;
+            const unsigned long long q2 = Uq >= 2 ? v.qrank(s1 - 2) : 0ull;
             f.tgt = (Uq >= 2 && q2 > f.bmax) ? q2 : f.bmax;
         }
     } else if (qmax == f.bmax) {
@@ -206,45 +234,35 @@ __device__ __forceinline__ void q_fold_union(QFold &f, bool lonely, bool has_r2,
 
 // One thread: the folds of the base and of the union.  Launched only for a query with a k-mer (Mq >= 1), which therefore has a
 // record: q_fold_union's [0, records) is not empty.
-template <class KeyT>
-__global__ void k_q_fold(QView<KeyT> v, const unsigned long long *ctl, QFold *out) {
+template <class KeyB, class KeyQ, bool RK>
+__global__ void k_q_fold(QView<KeyB, KeyQ, RK> v, const unsigned long long *ctl, QFold *out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     bool lonely, has_r2;
-    QFold f = q_fold_base(v.b, lonely, has_r2);
-    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.qkeys[v.qrecpos[j]]; }, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
-    *out = f;
-}
-// ... of a query ranked in the union's alphabet: the base's ranks come re-keyed (v.r.up3)
-template <class KeyB, class KeyQ>
-__global__ void k_q_fold_rk(QViewRk<KeyB, KeyQ> v, const unsigned long long *ctl, QFold *out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    bool lonely, has_r2;
-    QFold f = q_fold_base(v.b, lonely, has_r2, v.r.up3);
-    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) v.qkeys[v.qrecpos[j]]; }, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
+    QFold f = q_fold_base(v.b, lonely, has_r2, v.up3());
+    q_fold_union(f, lonely, has_r2, v, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
     *out = f;
 }
 
-// The union group of query record j, one of the records [s0, s1) of its query (positions of qrank's index space).  The key is
+// The union group of query record j, one of the records [s0, s1) of its query (positions of the view's index space).  The key is
 // taken relative to s0: the same for a query on its own and as a segment of a batch.
 // The rank record j's base searches look for, in the base's alphabet; none: there is no such rank (the record holds a letter the
-// base lacks).  bkey(i, none): record i's own.  A record the union folds (j == f.qL) looks for f.tgt, which is the base's bmax — its
-// key in the base's alphabet is kept beside it — or the rank of the query's last record but one, s1 - 2 (q_fold_union).
-template <class BKeyF>
-__device__ __forceinline__ unsigned long long q_base_key(const QFold &f, BKeyF bkey, uint32_t j, uint32_t s1, bool &none) {
+// base lacks).  A record the union folds (j == f.qL) looks for f.tgt, which is the base's bmax — its key in the base's alphabet is
+// kept beside it — or the rank of the query's last record but one, s1 - 2 (q_fold_union).
+template <class View>
+__device__ __forceinline__ unsigned long long q_base_key(const QFold &f, const View &v, uint32_t j, uint32_t s1, bool &none) {
+    const unsigned long long bmax_b = f.bmax_b;       // (read up here, as a value: a choice between the ADDRESS of f's copy and of a key puts f in scratch)
     none = false;
-    if (j != f.qL) return bkey(j, none);
-    return f.tgt == f.bmax ? f.bmax_b : bkey(s1 - 2, none);
-}
-// a query ranked in the base's alphabet: a record's rank is its base key
-template <class RankF> __device__ __forceinline__ auto q_same_alphabet(RankF qrank) {
-    return [qrank](uint32_t i, bool &) { return qrank(i); };
+    if (j != f.qL) return v.bkey(j, none);
+    return f.tgt == f.bmax ? bmax_b : v.bkey(s1 - 2, none);
 }
 
-template <class KeyT, class RankF, class BKeyF>
-__device__ __forceinline__ QDesc q_describe(const QFold &f, const QBase<KeyT> &b, RankF qrank, BKeyF bkey, uint32_t j, uint32_t s0, uint32_t s1) {
+template <class View>
+__device__ __forceinline__ QDesc q_describe(const QFold &f, const View &v, uint32_t j, uint32_t s0, uint32_t s1) {
+    const auto &b = v.b;
+    const auto qrank = [&](uint32_t i) { return v.qrank(i); };
     const unsigned long long eff = j == f.qL ? f.tgt : qrank(j);
     bool none;
-    const unsigned long long beff = q_base_key(f, bkey, j, s1, none);
+    const unsigned long long beff = q_base_key(f, v, j, s1, none);
     QDesc d;
     d.blo = d.bhi = 0; d.bskip = d.bextra = d.qextra = Q_NONE;
     if (f.folded) {
@@ -266,19 +284,18 @@ struct QMatchOut {
     QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
     unsigned long long *ctl;
 };
-// k_q_match's body: qrank(i) / bkey(i, none) = record i's rank / its key in the base's alphabet (q_base_key)
-template <class KeyB, class RankF, class BKeyF>
-__device__ __forceinline__ void q_match_records(const QBase<KeyB> &b, const uint2 *qpost, RankF qrank, BKeyF bkey, const QFold *pf, const QMatchOut &o,
-                                                uint64_t bound) {
+// One thread per query record: its union group, the gene it sorts by, the row's lookups; cost and matched count of the query
+template <class KeyB, class KeyQ, bool RK>
+__global__ __launch_bounds__(256) void k_q_match(QView<KeyB, KeyQ, RK> v, const QFold *pf, QMatchOut o, uint64_t bound) {
     const QFold f = *pf;
     const uint32_t Uq = (uint32_t) o.ctl[Q_CTL_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     if (j < Uq && j < bound) {
-        const QDesc d = q_describe(f, b, qrank, bkey, j, 0u, Uq);
+        const QDesc d = q_describe(f, v, j, 0u, Uq);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
-        const uint32_t gene = qpost[j].x;
+        const uint32_t gene = v.qpost[j].x;
         o.gene_key[j] = gene;
         if (sz >= 2) { cost = sz; atomicAdd(&o.row_lookups[gene], sz); }
         matched = (j != f.qL && d.bhi > d.blo) ? 1ull : 0ull;
@@ -289,16 +306,6 @@ __device__ __forceinline__ void q_match_records(const QBase<KeyB> &b, const uint
         if (cost) atomicAdd(&o.ctl[Q_CTL_COST], cost);
         if (matched) atomicAdd(&o.ctl[Q_CTL_MATCHED], matched);
     }
-}
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_q_match(QView<KeyT> v, const QFold *pf, QMatchOut o, uint64_t bound) {
-    const auto qrank = [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; };
-    q_match_records(v.b, v.qpost, qrank, q_same_alphabet(qrank), pf, o, bound);
-}
-template <class KeyB, class KeyQ>
-__global__ __launch_bounds__(256) void k_q_match_rk(QViewRk<KeyB, KeyQ> v, const QFold *pf, QMatchOut o, uint64_t bound) {
-    q_match_records(v.b, v.qpost, [&](uint32_t i) { return (unsigned long long) v.qkeys[v.qrecpos[i]]; },
-                    [&](uint32_t i, bool &none) { none = v.r.none[i] != 0; return (unsigned long long) v.r.bkey[i]; }, pf, o, bound);
 }
 
 // row_off[g] = first position of gene g in the gene-sorted records; staging bound = sum of min(lookups, columns); rows whose
@@ -584,6 +591,20 @@ static QJoinArgs q_join_args(pdl_ctx *c, float *stf, uint64_t cap) {
     return a;
 }
 
+// One look of the host at n words on the device: the stretch of device work ends, the words come over (PinRead), and — unless
+// this was the call's last look — the next stretch begins.
+template <class T>
+static void q_read_words(pdl_ctx *c, QSpans &spans, const void *d_src, size_t n, T *dst, bool more_work = true) {
+    spans.end();
+    {
+        PinRead rd(c);
+        const T *p = rd.add<T>(d_src, n);
+        rd.sync();
+        memcpy(dst, p, n * sizeof(T));
+    }
+    if (more_work) spans.begin();
+}
+
 // The HBM tier, when some row has more lookups than the LDS table holds keys: the host looks whether a row left the table
 // (*d_n_over); if so, tables (c->qb.hbm, shared by the single query and the batch) for W = min(rows, QH_WG) workgroups laid out for
 // n_cols columns — clean tables of exactly that layout are taken as they are, any other are cleared, and the bookkeeping says what
@@ -593,14 +614,7 @@ template <class LaunchF>
 static void q_join_hbm_tier(pdl_ctx *c, QSpans &spans, const unsigned long long *d_n_over, uint32_t n_cols, LaunchF launch) {
     auto &q = c->qb;
     uint64_t n_over = 0;
-    spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(d_n_over, 1);
-        rd.sync();
-        n_over = pc[0];
-    }
-    spans.begin();
+    q_read_words(c, spans, d_n_over, 1, &n_over);
     if (!n_over) return;
     const uint32_t W = (uint32_t) std::min<uint64_t>(n_over, QH_WG);
     if (!q.hbm_clean || q.hbm_cols != n_cols || q.hbm_slots < W) {
@@ -687,17 +701,29 @@ static bool q_any_letter(const uint32_t letters[8]) {
     return any != 0;
 }
 
+// The key types of a query's two sides and whether it is re-keyed, as types: f(KeyB{}, KeyQ{}, std::bool_constant<RK>{}) — the
+// base's keys, the keys the query is ranked with (the plan of c->qb.rk when `rekey`, else the base's own) and RK = rekey.
+template <class F>
+static void q_with_keys(pdl_ctx *c, bool rekey, F &&f) {
+    if (!rekey) pdl_with_key(c->key64, [&](auto key) { f(key, key, std::false_type{}); });
+    else pdl_with_keys_up(c->key64, c->qb.rk.key64, [&](auto key_b, auto key_q) { f(key_b, key_q, std::true_type{}); });
+}
+template <class KeyB>
+static QBase<KeyB> q_base(pdl_ctx *c) {
+    return QBase<KeyB>{c->keys_b.as<KeyB>(), c->recpos.as<uint32_t>(), c->vals_b.as<uint32_t>(), c->post.as<uint2>(), (uint32_t) c->U, c->M};
+}
+// (RK: what pdl_query_rebase has left in c->qb.rk)
 template <class KeyB>
 static QRebased<KeyB> q_rebased(pdl_ctx *c) {
     auto &rk = c->qb.rk;
     return QRebased<KeyB>{rk.bkey.as<KeyB>(), rk.none.as<uint8_t>(), rk.up3.as<unsigned long long>()};
 }
-template <class KeyT>
-static QView<KeyT> q_view(pdl_ctx *c, const void *qkeys) {
-    QView<KeyT> v;
-    v.b.bkeys = c->keys_b.as<KeyT>(); v.b.brecpos = c->recpos.as<uint32_t>(); v.b.bvals = c->vals_b.as<uint32_t>(); v.b.post = c->post.as<uint2>();
-    v.b.U = (uint32_t) c->U; v.b.M = c->M;
-    v.qkeys = static_cast<const KeyT *>(qkeys); v.qrecpos = c->qb.recpos.as<uint32_t>(); v.qpost = c->qb.post.as<uint2>();
+template <class KeyB, class KeyQ, bool RK>
+static QView<KeyB, KeyQ, RK> q_view(pdl_ctx *c, const void *qkeys) {
+    QView<KeyB, KeyQ, RK> v;
+    v.b = q_base<KeyB>(c);
+    v.qkeys = static_cast<const KeyQ *>(qkeys); v.qrecpos = c->qb.recpos.as<uint32_t>(); v.qpost = c->qb.post.as<uint2>();
+    if constexpr (RK) v.r = q_rebased<KeyB>(c);
     return v;
 }
 
@@ -731,20 +757,9 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
     // ranked with the union's table (base letters + ALL its letters, genes shorter than k included, as a build counts them)
     bool rekey = false;
     if (c->opt_query_rekey && Rq) {
-        QLettersArgs la{};
-        la.res = q.res.as<uint8_t>(); la.n = Rq; la.letters = reinterpret_cast<uint32_t *>(ctl + Q_CTL_LETTERS);
-        for (int b = 0; b < 256; b++) if (c->alpha_present[b]) la.present[b >> 5] |= 1u << (b & 31);
-        hipLaunchKernelGGL(k_q_letters, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, la);
-        PDL_HIP(hipGetLastError());
+        q_scan_absent<true, false>(c, q.res.as<uint8_t>(), Rq, nullptr, 1, 0, ctl + Q_CTL_LETTERS);
         uint32_t letters[8];
-        spans.end();
-        {
-            PinRead rd(c);
-            const uint32_t *pl = rd.add<uint32_t>(ctl + Q_CTL_LETTERS, 8);
-            rd.sync();
-            memcpy(letters, pl, sizeof(letters));
-        }
-        spans.begin();
+        q_read_words(c, spans, ctl + Q_CTL_LETTERS, 8, letters);
         if (q_any_letter(letters)) { q_rekey_verdict(c, letters, "query", true); rekey = true; }
     }
     if (!rekey) pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
@@ -764,28 +779,16 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
         PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
         QMatchOut mo{q.desc.as<QDesc>(), q.gkey.as<uint32_t>(), q.row_lookups.as<uint32_t>(), ctl};
         const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
-        if (!rekey) pdl_with_key(c->key64, [&](auto key_tag) {
-            using KeyT = decltype(key_tag);
-            const QView<KeyT> v = q_view<KeyT>(c, qkeys);
-            hipLaunchKernelGGL(k_q_fold<KeyT>, dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
-            hipLaunchKernelGGL(k_q_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
+        // (re-keyed: Q-rebase first, then fold and match in two alphabets — the base's key type for its keys, the union's for the query's)
+        q_with_keys(c, rekey, [&](auto key_b, auto key_q, auto rk) {
+            using KeyB = decltype(key_b);
+            using KeyQ = decltype(key_q);
+            constexpr bool RK = decltype(rk)::value;
+            if constexpr (RK) pdl_query_rebase(c, qkeys, q.recpos.as<uint32_t>(), ctl + Q_CTL_RECORDS, Mq);
+            const QView<KeyB, KeyQ, RK> v = q_view<KeyB, KeyQ, RK>(c, qkeys);
+            hipLaunchKernelGGL((k_q_fold<KeyB, KeyQ, RK>), dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
+            hipLaunchKernelGGL((k_q_match<KeyB, KeyQ, RK>), grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
         });
-        else {
-            // Q-rebase, then fold and match in two alphabets: the base's key type for its keys, the union's for the query's
-            pdl_query_rebase(c, qkeys, q.recpos.as<uint32_t>(), ctl + Q_CTL_RECORDS, Mq);
-            pdl_with_key(c->key64, [&](auto base_tag) {
-                using KeyB = decltype(base_tag);
-                pdl_with_key(qkey64, [&](auto query_tag) {
-                    using KeyQ = decltype(query_tag);
-                    const QView<KeyB> vb = q_view<KeyB>(c, nullptr);
-                    QViewRk<KeyB, KeyQ> v;
-                    v.b = vb.b; v.qkeys = static_cast<const KeyQ *>(qkeys); v.qrecpos = vb.qrecpos; v.qpost = vb.qpost;
-                    v.r = q_rebased<KeyB>(c);
-                    hipLaunchKernelGGL((k_q_fold_rk<KeyB, KeyQ>), dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
-                    hipLaunchKernelGGL((k_q_match_rk<KeyB, KeyQ>), grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
-                });
-            });
-        }
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the record indices by gene (the records are in (rank, gene) order)
         uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
@@ -798,14 +801,7 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
         q.rec_sorted_at = ix_out;
     }
     uint64_t h_ctl[Q_CTL_USED] = {};
-    spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(ctl, Q_CTL_USED);
-        rd.sync();
-        memcpy(h_ctl, pc, sizeof(h_ctl));
-    }
-    spans.begin();
+    q_read_words(c, spans, ctl, Q_CTL_USED, h_ctl);
     if (h_ctl[Q_CTL_BAD_BYTE]) pdl_fail_absent_byte(h_ctl[Q_CTL_BAD_BYTE], "query");
     const uint64_t Uq = h_ctl[Q_CTL_RECORDS], cost = h_ctl[Q_CTL_COST], matched = h_ctl[Q_CTL_MATCHED], bound = h_ctl[Q_CTL_BOUND],
                    may_overflow = h_ctl[Q_CTL_MAY_OVERFLOW];
@@ -835,14 +831,10 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
         });
         q_order_rows(c, a, q.fin_off.as<uint32_t>(), q.rowid.as<uint32_t>(), q.cells.as<float>(), n, cap, NC, ctl + Q_CTL_EMITTED, ctl + Q_CTL_WIDE_ROWS);
         PDL_HIP(hipGetLastError());
-        spans.end();
-        uint64_t staged = 0;
-        {
-            PinRead rd(c);
-            const uint64_t *pc = rd.add<uint64_t>(ctl + Q_CTL_OVERFLOW_ROWS, Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1);
-            rd.sync();
-            staged = pc[Q_CTL_CELL_CURSOR - Q_CTL_OVERFLOW_ROWS]; Z = pc[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS];
-        }
+        uint64_t tail[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1];
+        q_read_words(c, spans, ctl + Q_CTL_OVERFLOW_ROWS, Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1, tail, false);
+        const uint64_t staged = tail[Q_CTL_CELL_CURSOR - Q_CTL_OVERFLOW_ROWS];
+        Z = tail[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS];
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
     } else {
         spans.end();

@@ -9,7 +9,8 @@
 // One genome cannot fill the chip (the match is one round of latency, the join has fewer workgroups than the chip
 // holds, the launches and host reads are a third of the time), so the stages run ONCE over all genes of a chunk of queries:
 //
-//   B-alpha  k_qb_alpha     every query byte against the base's letters; per query the smallest absent byte
+//   B-stage  qb_stage_chunk the chunk's layout, its control words cleared, residues and the six layout arrays on their way up
+//   B-alpha  k_q_absent<.., BATCH> (pdl_query.h)   every query byte against the base's letters; per query the smallest absent byte
 //   B-dict   pdl_query_dictionary over all genes of the chunk (gene value = position in the chunk): records in (rank, gene) order
 //   B-seg    k_qb_seg_key + pdl_sort_pairs (stable, key = query) + k_qb_gather: every query's records as ONE segment in
 //            (rank, gene) order — rank and {gene local to the query, count} copied out, so a probe is one load
@@ -27,10 +28,13 @@
 // B-alpha .. B-order and the per-query counts are pdl_run_query_chunk_device: the cells stay in HBM.  pdl_query_batch follows
 // it with B-copy; K-place for a batch (pdl_place_batch.h) filters the cells where they lie instead.
 //
-// Option "query_rekey": B-alpha is qb_rekey_chunk — every query's absent bytes (k_qb_letters), the host's verdict per query and the
-// chunk's joint alphabet, the chunk cut where that would not be exact; a chunk whose queries bring a letter is ranked once with
-// the joint table, B-seg copies those keys, Q-rebase (pdl_rekey.h) runs over the segment positions and k_qb_fold_rk / k_qb_match_rk
-// take its output as the single query's do.  A chunk without a new letter takes the stages above untouched.
+// Fold and match run over one view, QBView<KeyB, KeyQ, RK> (QView's accessors over segment positions), chosen by q_with_keys.
+//
+// Option "query_rekey": behind B-stage comes qb_rekey_chunk — every query's absent bytes (k_q_absent<LETTERS, BATCH>), the host's
+// verdict per query and the chunk's joint alphabet, the chunk cut where that would not be exact: what is staged serves the prefix
+// as it is, only the counts are taken again.  A chunk whose queries bring a letter is ranked once with the joint table, B-seg
+// copies those keys, Q-rebase (pdl_rekey.h) runs over the segment positions and k_qb_fold / k_qb_match <KeyB, KeyQ, true> take its
+// output as the single query's do.  A chunk without a new letter takes the stages above untouched.
 //
 // Positions of query records (QDesc.qlo/qhi/qextra, QFold.qL) are positions in the segmented arrays of the chunk; QDesc.key is
 // taken relative to the segment start, so it is the single query's key.
@@ -68,28 +72,6 @@ struct QBLayout {
     uint32_t nq, genes;
 };
 
-struct QBAlphaArgs { const uint8_t *res; uint64_t n; uint32_t present[8]; QBLayout lay; unsigned long long *ctl; };
-__global__ __launch_bounds__(256) void k_qb_alpha(QBAlphaArgs a) {
-    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
-        const uint32_t b = a.res[i];
-        if ((a.present[b >> 5] >> (b & 31)) & 1u) continue;
-        uint32_t lo = 0, hi = a.lay.nq;                       // last query q with res_begin[q] <= i (absent bytes are rare: searched only then)
-        while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.lay.res_begin[m] <= i) lo = m; else hi = m; }
-        atomicMax(qb_ctl(a.ctl, lo) + QB_CTL_BAD_BYTE, (unsigned long long) (256u - b));
-    }
-}
-
-// Option "query_rekey": every query's absent bytes themselves, 256 bits at its QB_CTL_LETTERS (as k_q_letters; the search as above)
-__global__ __launch_bounds__(256) void k_qb_letters(QBAlphaArgs a) {
-    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t) gridDim.x * 256) {
-        const uint32_t b = a.res[i];
-        if ((a.present[b >> 5] >> (b & 31)) & 1u) continue;
-        uint32_t lo = 0, hi = a.lay.nq;
-        while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a.lay.res_begin[m] <= i) lo = m; else hi = m; }
-        atomicOr(reinterpret_cast<uint32_t *>(qb_ctl(a.ctl, lo) + QB_CTL_LETTERS) + (b >> 5), 1u << (b & 31));
-    }
-}
-
 // key of the segment sort: the query of every record of the chunk's dictionary
 __global__ __launch_bounds__(256) void k_qb_seg_key(const uint2 *post, const unsigned long long *ctl, QBLayout lay, uint32_t *key) {
     const uint32_t u = blockIdx.x * 256 + threadIdx.x;
@@ -114,30 +96,28 @@ __global__ __launch_bounds__(256) void k_qb_gather(const KeyT *keys, const uint3
     if (j == U - 1) for (uint32_t s = q + 1; s <= lay.nq; s++) seg_off[s] = U;
 }
 
-template <class KeyT> struct QBView {
-    QBase<KeyT> b;
-    const KeyT *srank; const uint2 *spost;
-    const uint32_t *seg_off, *qid_sorted;
-};
-
-// Option "query_rekey", a chunk whose queries bring letters the base lacks: the chunk is ranked once, in the base's letters plus
-// those of ALL its queries (a block is the same in whichever exact superset alphabet it was ranked); srank holds those keys, of
-// type KeyQ, and r what Q-rebase left for every segment position (pdl_query.h, QRebased).
-template <class KeyB, class KeyQ> struct QBViewRk {
+// The chunk's records as fold and match see them (QView's accessors, pdl_query.h, over segment positions).  Option "query_rekey", a
+// chunk whose queries bring letters the base lacks (RK): the chunk is ranked once, in the base's letters plus those of ALL its
+// queries (a block is the same in whichever exact superset alphabet it was ranked); srank holds those keys, of type KeyQ, and r
+// what Q-rebase left for every segment position.
+template <class KeyB, class KeyQ, bool RK> struct QBView : QRebasedIf<KeyB, RK> {
     QBase<KeyB> b;
     const KeyQ *srank; const uint2 *spost;
     const uint32_t *seg_off, *qid_sorted;
-    QRebased<KeyB> r;
+    __device__ unsigned long long qrank(uint32_t i) const { return (unsigned long long) srank[i]; }
+    __device__ unsigned long long bkey(uint32_t i, bool &none) const {
+        if constexpr (RK) { none = this->r.none[i] != 0; return (unsigned long long) this->r.bkey[i]; }
+        else { none = false; return qrank(i); }
+    }
+    __device__ const unsigned long long *up3() const { if constexpr (RK) return this->r.up3; else return nullptr; }
 };
 
 // One thread per query: the base's fold (the same for all, computed by each) and the union's with this query's largest rank.
-// up3: as q_fold_base takes it.
-template <class KeyB, class KeyQ>
-__device__ __forceinline__ void qb_fold_query(const QBase<KeyB> &b, const KeyQ *srank, const uint32_t *seg_off, const unsigned long long *up3, uint32_t nq,
-                                              unsigned long long *ctl, QFold *out) {
+template <class KeyB, class KeyQ, bool RK>
+__global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyB, KeyQ, RK> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
-    const uint32_t s0 = seg_off[q], s1 = seg_off[q + 1];
+    const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1];
     qb_ctl(ctl, q)[QB_CTL_RECORDS] = s1 - s0;
     if (s0 == s1) {                                               // no k-mer: no record reads the fold
         QFold f{};
@@ -146,27 +126,18 @@ __device__ __forceinline__ void qb_fold_query(const QBase<KeyB> &b, const KeyQ *
         return;
     }
     bool lonely, has_r2;
-    QFold f = q_fold_base(b, lonely, has_r2, up3);
-    q_fold_union(f, lonely, has_r2, [&](uint32_t j) { return (unsigned long long) srank[j]; }, s0, s1);
+    QFold f = q_fold_base(v.b, lonely, has_r2, v.up3());
+    q_fold_union(f, lonely, has_r2, v, s0, s1);
     out[q] = f;
-}
-template <class KeyT>
-__global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyT> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
-    qb_fold_query(v.b, v.srank, v.seg_off, nullptr, nq, ctl, out);
-}
-template <class KeyB, class KeyQ>
-__global__ __launch_bounds__(64) void k_qb_fold_rk(QBViewRk<KeyB, KeyQ> v, uint32_t nq, unsigned long long *ctl, QFold *out) {
-    qb_fold_query(v.b, v.srank, v.seg_off, v.r.up3, nq, ctl, out);
 }
 
 struct QBMatchOut {
     QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
     unsigned long long *ctl;
 };
-// k_qb_match's body over a view `v` (QBView, QBViewRk): qrank(i) / bkey(i, none) as q_match_records takes them
-template <class View, class RankF, class BKeyF>
-__device__ __forceinline__ void qb_match_records(const View &v, RankF qrank, BKeyF bkey, const QFold *folds, const QBLayout &lay, const QBMatchOut &o,
-                                                 uint64_t bound) {
+// One thread per record of the chunk: k_q_match inside the record's own segment; cost and matched count per query
+template <class KeyB, class KeyQ, bool RK>
+__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyB, KeyQ, RK> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
     const uint32_t Ut = (uint32_t) o.ctl[QBG_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
@@ -174,7 +145,7 @@ __device__ __forceinline__ void qb_match_records(const View &v, RankF qrank, BKe
     if (j < Ut && j < bound) {
         q = v.qid_sorted[j];
         const QFold f = folds[q];
-        const QDesc d = q_describe(f, v.b, qrank, bkey, j, v.seg_off[q], v.seg_off[q + 1]);
+        const QDesc d = q_describe(f, v, j, v.seg_off[q], v.seg_off[q + 1]);
         const uint32_t sz = q_size(d);
         o.desc[j] = d;
         const uint32_t gene = lay.gene_begin[q] + v.spost[j].x;
@@ -193,16 +164,6 @@ __device__ __forceinline__ void qb_match_records(const View &v, RankF qrank, BKe
     if (q == Q_NONE) return;
     if (cost) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_COST, cost);
     if (matched) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_MATCHED, matched);
-}
-template <class KeyT>
-__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyT> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
-    const auto qrank = [&](uint32_t i) { return (unsigned long long) v.srank[i]; };
-    qb_match_records(v, qrank, q_same_alphabet(qrank), folds, lay, o, bound);
-}
-template <class KeyB, class KeyQ>
-__global__ __launch_bounds__(256) void k_qb_match_rk(QBViewRk<KeyB, KeyQ> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
-    qb_match_records(v, [&](uint32_t i) { return (unsigned long long) v.srank[i]; },
-                     [&](uint32_t i, bool &none) { none = v.r.none[i] != 0; return (unsigned long long) v.r.bkey[i]; }, folds, lay, o, bound);
 }
 
 // row_off[g] = first position of chunk gene g in the gene-sorted records; per query: staging bound = sum of
@@ -272,65 +233,96 @@ __global__ __launch_bounds__(64) void k_qb_counts(const uint32_t *fin_off, QBLay
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-template <class KeyT>
-static QBView<KeyT> qb_view(pdl_ctx *c) {
+template <class KeyB, class KeyQ, bool RK>
+static QBView<KeyB, KeyQ, RK> qb_view(pdl_ctx *c, const uint32_t *qid_sorted) {
     auto &w = c->qbb;
-    QBView<KeyT> v;
-    v.b.bkeys = c->keys_b.as<KeyT>(); v.b.brecpos = c->recpos.as<uint32_t>(); v.b.bvals = c->vals_b.as<uint32_t>(); v.b.post = c->post.as<uint2>();
-    v.b.U = (uint32_t) c->U; v.b.M = c->M;
-    v.srank = w.srank.as<KeyT>(); v.spost = w.spost.as<uint2>(); v.seg_off = w.seg_off.as<uint32_t>();
+    QBView<KeyB, KeyQ, RK> v;
+    v.b = q_base<KeyB>(c);
+    v.srank = w.srank.as<KeyQ>(); v.spost = w.spost.as<uint2>(); v.seg_off = w.seg_off.as<uint32_t>(); v.qid_sorted = qid_sorted;
+    if constexpr (RK) v.r = q_rebased<KeyB>(c);
     return v;
 }
 
-// Option "query_rekey", in front of a chunk [qa, qe): every query's letters come to the host (k_qb_letters over the chunk's bytes),
-// and the host decides.  Each query's own verdict uses its own union only (q_rekey_verdict: a refusal names the first such query).
-// The chunk is ranked with the base's letters plus those of all its queries if that alphabet is exact; where a query tips it
-// over, the chunk is cut in front of it (a chunk of one is a query's own union: exact, or refused).  -> the chunk's end; rekey:
-// its queries bring a letter and the plan for their joint letters is in c->qb.rk.  The stretch of device work is w.spans' first.
-static uint32_t qb_rekey_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
-                               bool &rekey) {
+// A chunk as the host lays it out and qb_stage_chunk leaves it in c->qbb: the counts, and the host's copies of the seven arrays
+// (off, koff, kseq by chunk gene; gene_query; gene_begin, res_begin by query) for as long as their uploads may read them.
+struct QBStage {
+    uint32_t nq = 0, NT = 0, n_max = 0;             // queries, genes, genes of the largest query
+    uint64_t Rq = 0, Mq = 0;                        // residues, k-mers
+    std::vector<uint64_t> off, koff, rbeg;
+    std::vector<uint32_t> kseq, gq, gbeg;
+    size_t ctl_words() const { return QBG_WORDS + (size_t) nq * QB_CTL_WORDS; }
+    // The counts of the first n queries [qa, qa + n).  Every staged array is valid as a prefix — off[NT'] = Rq', koff[NT'] = Mq',
+    // gene_begin[n] = NT', res_begin[n] = Rq', the control words lie query by query — so a chunk that is cut stages nothing again.
+    void take(const std::vector<QBQuery> &qs, uint32_t qa, uint32_t n) {
+        nq = n; NT = gbeg[n]; Rq = rbeg[n]; Mq = koff[NT];
+        n_max = 0;
+        for (uint32_t q = 0; q < n; q++) n_max = std::max(n_max, qs[qa + q].n);
+    }
+};
+// The queries [qa, qe) on their way to the device: the layout, the chunk's control words cleared, the seven uploads.  Opens the
+// chunk's first stretch of device work (w.spans) behind the host's layout.
+static QBStage qb_stage_chunk(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
-    const uint32_t nq = qe - qa, ga = qs[qa].g0;
-    const uint64_t r0 = offsets[ga], Rq = offsets[qs[qe - 1].g0 + qs[qe - 1].n] - r0;
-    rekey = false;
-    w.spans.start(st);
-    if (!Rq) return qe;
-    std::vector<uint64_t> h_rbeg(nq + 1);
-    for (uint32_t q = 0; q < nq; q++) h_rbeg[q] = offsets[qs[qa + q].g0] - r0;
-    h_rbeg[nq] = Rq;
-    const size_t ctl_words = QBG_WORDS + (size_t) nq * QB_CTL_WORDS;
-    w.spans.begin();
-    w.ctl.alloc(ctl_words * sizeof(uint64_t));
-    unsigned long long *ctl = w.ctl.as<unsigned long long>();
-    PDL_HIP(hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint64_t), st));
-    w.res.alloc(Rq); w.res_begin.alloc((nq + 1) * 8ull);
-    PDL_HIP(hipMemcpyAsync(w.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.res_begin.p, h_rbeg.data(), (nq + 1) * 8ull, hipMemcpyHostToDevice, st));
-    QBAlphaArgs aa{};
-    aa.res = w.res.as<uint8_t>(); aa.n = Rq; aa.ctl = ctl;
-    aa.lay = QBLayout{nullptr, w.res_begin.as<uint64_t>(), nullptr, nq, 0};
-    for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
-    hipLaunchKernelGGL(k_qb_letters, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
-    PDL_HIP(hipGetLastError());
-    std::vector<uint64_t> h_ctl(ctl_words);
-    w.spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
-        rd.sync();
-        memcpy(h_ctl.data(), pc, ctl_words * sizeof(uint64_t));
+    const uint32_t k = c->rp.k, nq = qe - qa, ga = qs[qa].g0, NT = qs[qe - 1].g0 + qs[qe - 1].n - ga;
+    const uint64_t r0 = offsets[ga], Rq = offsets[ga + NT] - r0;
+    QBStage s;
+    s.off.resize(NT + 1); s.koff.resize(NT + 1); s.rbeg.resize(nq + 1); s.kseq.resize(NT); s.gq.resize(NT); s.gbeg.resize(nq + 1);
+    uint64_t Mq = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        const QBQuery &Q = qs[qa + q];
+        s.gbeg[q] = Q.g0 - ga; s.rbeg[q] = offsets[Q.g0] - r0;
+        for (uint32_t i = 0; i < Q.n; i++) {
+            const uint32_t g = Q.g0 - ga + i;
+            const uint64_t len = offsets[ga + g + 1] - offsets[ga + g];
+            s.off[g] = offsets[ga + g] - r0; s.koff[g] = Mq;
+            s.kseq[g] = len >= k ? (uint32_t) (len - k + 1) : 0u;      // (below 2^20: checked by the caller)
+            s.gq[g] = q;
+            Mq += s.kseq[g];
+        }
     }
+    s.off[NT] = Rq; s.koff[NT] = Mq; s.gbeg[nq] = NT; s.rbeg[nq] = Rq;
+    s.take(qs, qa, nq);
+    w.spans.start(st);
+    w.spans.begin();
+    w.ctl.alloc(s.ctl_words() * sizeof(uint64_t));
+    PDL_HIP(hipMemsetAsync(w.ctl.p, 0, s.ctl_words() * sizeof(uint64_t), st));
+    w.res.alloc(Rq); w.off.alloc((NT + 1) * 8ull); w.koff.alloc((NT + 1) * 8ull); w.kseq.alloc(NT * 4ull);
+    w.gene_begin.alloc((nq + 1) * 4ull); w.res_begin.alloc((nq + 1) * 8ull); w.gene_query.alloc(NT * 4ull);
+    if (Rq) PDL_HIP(hipMemcpyAsync(w.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.off.p, s.off.data(), (NT + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.koff.p, s.koff.data(), (NT + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.kseq.p, s.kseq.data(), NT * 4ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.gene_begin.p, s.gbeg.data(), (nq + 1) * 4ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.res_begin.p, s.rbeg.data(), (nq + 1) * 8ull, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemcpyAsync(w.gene_query.p, s.gq.data(), NT * 4ull, hipMemcpyHostToDevice, st));
+    return s;
+}
+
+// Option "query_rekey", behind the staging of a chunk [qa, qa + s.nq): every query's letters come to the host (the absent-byte scan
+// over the chunk's bytes), and the host decides.  Each query's own verdict uses its own union only (q_rekey_verdict: a refusal names
+// the first such query).  The chunk is ranked with the base's letters plus those of all its queries if that alphabet is exact;
+// where a query tips it over, the chunk is cut in front of it (a chunk of one is a query's own union: exact, or refused): `s`
+// then holds the counts of that prefix of what is staged.  rekey: the chunk's queries bring a letter and the plan for their joint
+// letters is in c->qb.rk.  The scan closes the chunk's first stretch of device work; the next one is opened behind the verdicts.
+static void qb_rekey_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa, QBStage &s, bool &rekey) {
+    auto &w = c->qbb;
+    rekey = false;
+    if (!s.Rq) return;
+    unsigned long long *ctl = w.ctl.as<unsigned long long>();
+    q_scan_absent<true, true>(c, w.res.as<uint8_t>(), s.Rq, w.res_begin.as<uint64_t>(), s.nq, QB_CTL_WORDS, ctl + QBG_WORDS + QB_CTL_LETTERS);
+    std::vector<uint64_t> h_ctl(s.ctl_words());
+    q_read_words(c, w.spans, ctl, h_ctl.size(), h_ctl.data(), false);
     uint32_t joint[8] = {};
     const char *why = "";
     const bool base_exact = pdl_query_rekey_base_exact(c, &why);
-    for (uint32_t q = 0; q < nq; q++) {
+    for (uint32_t q = 0; q < s.nq; q++) {
         uint32_t own[8], with[8];
         memcpy(own, &h_ctl[QBG_WORDS + (size_t) q * QB_CTL_WORDS + QB_CTL_LETTERS], sizeof(own));
         if (!q_any_letter(own)) continue;
         bool grows = false;
         for (int i = 0; i < 8; i++) { with[i] = joint[i] | own[i]; grows = grows || with[i] != joint[i]; }
-        if (q > 0 && grows && base_exact && !pdl_query_rekey_plan(c, with, false, &why)) { qe = qa + q; break; }
+        if (q > 0 && grows && base_exact && !pdl_query_rekey_plan(c, with, false, &why)) { s.take(qs, qa, q); break; }
         char who[48];
         snprintf(who, sizeof(who), "query %u:", qa + q);
         q_rekey_verdict(c, own, who, false);
@@ -340,7 +332,7 @@ static uint32_t qb_rekey_chunk(pdl_ctx *c, const uint8_t *residues, const uint64
         if (!pdl_query_rekey_plan(c, joint, true, &why)) PDL_FAIL(PDL_ERR_DEVICE, "query batch: the chunk's joint alphabet is not exact (%s)", why);
         rekey = true;
     }
-    return qe;
+    w.spans.begin();
 }
 
 // The device half of one chunk, queries [qa, qe) of `qs` — with option "query_rekey" a prefix of them (qb_rekey_chunk), the
@@ -350,55 +342,19 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
                                            uint32_t hbm_cols) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
-    bool rekey = false;
-    if (c->opt_query_rekey) qe = qb_rekey_chunk(c, residues, offsets, qs, qa, qe, rekey);
-    const uint32_t N = c->N, G1 = c->G + 1, k = c->rp.k;
-    const uint32_t nq = qe - qa, ga = qs[qa].g0, NT = qs[qe - 1].g0 + qs[qe - 1].n - ga;
-    const uint64_t r0 = offsets[ga], Rq = offsets[ga + NT] - r0;
-    std::vector<uint64_t> h_off(NT + 1), h_koff(NT + 1), h_rbeg(nq + 1);
-    std::vector<uint32_t> h_kseq(NT), h_gq(NT), h_gbeg(nq + 1);
-    uint64_t Mq = 0;
-    uint32_t n_max = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        const QBQuery &Q = qs[qa + q];
-        h_gbeg[q] = Q.g0 - ga; h_rbeg[q] = offsets[Q.g0] - r0;
-        n_max = std::max(n_max, Q.n);
-        for (uint32_t i = 0; i < Q.n; i++) {
-            const uint32_t g = Q.g0 - ga + i;
-            const uint64_t len = offsets[ga + g + 1] - offsets[ga + g];
-            h_off[g] = offsets[ga + g] - r0; h_koff[g] = Mq;
-            h_kseq[g] = len >= k ? (uint32_t) (len - k + 1) : 0u;      // (below 2^20: checked by the caller)
-            h_gq[g] = q;
-            Mq += h_kseq[g];
-        }
-    }
-    h_off[NT] = Rq; h_koff[NT] = Mq; h_gbeg[nq] = NT; h_rbeg[nq] = Rq;
     QSpans &spans = w.spans;
-    if (!c->opt_query_rekey) spans.start(st);
-    spans.begin();
 
     // B-alpha (and the chunk on its way to the device)
-    const size_t ctl_words = QBG_WORDS + (size_t) nq * QB_CTL_WORDS;
-    w.ctl.alloc(ctl_words * sizeof(uint64_t));
+    QBStage s = qb_stage_chunk(c, residues, offsets, qs, qa, qe);
+    bool rekey = false;
+    if (c->opt_query_rekey) qb_rekey_chunk(c, qs, qa, s, rekey);
+    const uint32_t N = c->N, G1 = c->G + 1, nq = s.nq, NT = s.NT, n_max = s.n_max;
+    const uint64_t Rq = s.Rq, Mq = s.Mq;
+    const size_t ctl_words = s.ctl_words();
     unsigned long long *ctl = w.ctl.as<unsigned long long>();
-    PDL_HIP(hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint64_t), st));
-    w.res.alloc(Rq); w.off.alloc((NT + 1) * 8ull); w.koff.alloc((NT + 1) * 8ull); w.kseq.alloc(NT * 4ull);
-    w.gene_begin.alloc((nq + 1) * 4ull); w.res_begin.alloc((nq + 1) * 8ull); w.gene_query.alloc(NT * 4ull);
-    if (Rq) PDL_HIP(hipMemcpyAsync(w.res.p, residues + r0, Rq, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.off.p, h_off.data(), (NT + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.koff.p, h_koff.data(), (NT + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.kseq.p, h_kseq.data(), NT * 4ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.gene_begin.p, h_gbeg.data(), (nq + 1) * 4ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.res_begin.p, h_rbeg.data(), (nq + 1) * 8ull, hipMemcpyHostToDevice, st));
-    PDL_HIP(hipMemcpyAsync(w.gene_query.p, h_gq.data(), NT * 4ull, hipMemcpyHostToDevice, st));
     const QBLayout lay{w.gene_begin.as<uint32_t>(), w.res_begin.as<uint64_t>(), w.gene_query.as<uint32_t>(), nq, NT};
-    if (Rq && !rekey) {                                              // (a chunk that is re-keyed has had its verdicts)
-        QBAlphaArgs aa{};
-        aa.res = w.res.as<uint8_t>(); aa.n = Rq; aa.lay = lay; aa.ctl = ctl;
-        for (int b = 0; b < 256; b++) if (c->alpha_present[b]) aa.present[b >> 5] |= 1u << (b & 31);
-        hipLaunchKernelGGL(k_qb_alpha, dim3((uint32_t) std::min<uint64_t>((Rq + 255) / 256, 1024)), dim3(256), 0, st, aa);
-        PDL_HIP(hipGetLastError());
-    }
+    // (a chunk that is re-keyed has had its verdicts)
+    if (!rekey) q_scan_absent<false, true>(c, w.res.as<uint8_t>(), Rq, lay.res_begin, nq, QB_CTL_WORDS, ctl + QBG_WORDS + QB_CTL_BAD_BYTE);
 
     // B-dict, B-seg, B-fold, B-match, B-rows (sized by the bound Mq; the record count stays on the device until the look below)
     w.rowid.alloc(NT * 4ull);
@@ -425,33 +381,19 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         PDL_HIP(hipGetLastError());
         pdl_sort_pairs<uint32_t, uint32_t>(c, qk_in, qk_out, pm_in, pm_out, Mq, std::max<uint32_t>(1, bit_length64(nq)), true, d_u, 0, true);
         QBMatchOut mo{w.desc.as<QDesc>(), w.gkey.as<uint32_t>(), w.row_lookups.as<uint32_t>(), ctl};
-        if (!rekey) pdl_with_key(c->key64, [&](auto key_tag) {
-            using KeyT = decltype(key_tag);
-            QBView<KeyT> v = qb_view<KeyT>(c);
-            v.qid_sorted = qk_out;
-            hipLaunchKernelGGL(k_qb_gather<KeyT>, grid_m, dim3(256), 0, st, static_cast<const KeyT *>(qkeys), (const uint32_t *) w.recpos.as<uint32_t>(),
+        // the segments in the alphabet the chunk is ranked in; re-keyed: Q-rebase over the segment positions, fold and match in two alphabets
+        q_with_keys(c, rekey, [&](auto key_b, auto key_q, auto rk) {
+            using KeyB = decltype(key_b);
+            using KeyQ = decltype(key_q);
+            constexpr bool RK = decltype(rk)::value;
+            hipLaunchKernelGGL(k_qb_gather<KeyQ>, grid_m, dim3(256), 0, st, static_cast<const KeyQ *>(qkeys), (const uint32_t *) w.recpos.as<uint32_t>(),
                                (const uint2 *) w.post.as<uint2>(), (const uint32_t *) pm_out, (const uint32_t *) qk_out, (const unsigned long long *) ctl, lay,
-                               w.srank.as<KeyT>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
-            hipLaunchKernelGGL(k_qb_fold<KeyT>, dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
-            hipLaunchKernelGGL(k_qb_match<KeyT>, grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
-        });
-        else pdl_with_key(c->key64, [&](auto base_tag) {
-            // the segments in the chunk's joint alphabet, Q-rebase over the segment positions, fold and match in two alphabets
-            using KeyB = decltype(base_tag);
-            pdl_with_key(qkey64, [&](auto query_tag) {
-                using KeyQ = decltype(query_tag);
-                const QBView<KeyB> vb = qb_view<KeyB>(c);
-                QBViewRk<KeyB, KeyQ> v;
-                v.b = vb.b; v.srank = w.srank.as<KeyQ>(); v.spost = vb.spost; v.seg_off = vb.seg_off; v.qid_sorted = qk_out;
-                hipLaunchKernelGGL(k_qb_gather<KeyQ>, grid_m, dim3(256), 0, st, static_cast<const KeyQ *>(qkeys), (const uint32_t *) w.recpos.as<uint32_t>(),
-                                   (const uint2 *) w.post.as<uint2>(), (const uint32_t *) pm_out, (const uint32_t *) qk_out, (const unsigned long long *) ctl, lay,
-                                   w.srank.as<KeyQ>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
-                PDL_HIP(hipGetLastError());
-                pdl_query_rebase(c, w.srank.p, nullptr, ctl + QBG_RECORDS, Mq);
-                v.r = q_rebased<KeyB>(c);
-                hipLaunchKernelGGL((k_qb_fold_rk<KeyB, KeyQ>), dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
-                hipLaunchKernelGGL((k_qb_match_rk<KeyB, KeyQ>), grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
-            });
+                               w.srank.as<KeyQ>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
+            PDL_HIP(hipGetLastError());
+            if constexpr (RK) pdl_query_rebase(c, w.srank.p, nullptr, ctl + QBG_RECORDS, Mq);
+            const QBView<KeyB, KeyQ, RK> v = qb_view<KeyB, KeyQ, RK>(c, qk_out);
+            hipLaunchKernelGGL((k_qb_fold<KeyB, KeyQ, RK>), dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
+            hipLaunchKernelGGL((k_qb_match<KeyB, KeyQ, RK>), grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
         });
         PDL_HIP(hipGetLastError());
         // each gene's records in rank order: a stable sort of the segment positions by chunk gene
@@ -464,13 +406,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         rec_sorted = ix_out;
     }
     std::vector<uint64_t> h_ctl(ctl_words);
-    spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
-        rd.sync();
-        memcpy(h_ctl.data(), pc, ctl_words * sizeof(uint64_t));
-    }
+    q_read_words(c, spans, ctl, ctl_words, h_ctl.data());
     auto hq = [&](uint32_t q, uint32_t word) -> uint64_t { return h_ctl[QBG_WORDS + (size_t) q * QB_CTL_WORDS + word]; };
     for (uint32_t q = 0; q < nq; q++)
         if (hq(q, QB_CTL_BAD_BYTE)) {
@@ -478,7 +414,6 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
             snprintf(who, sizeof(who), "query %u:", qa + q);
             pdl_fail_absent_byte(hq(q, QB_CTL_BAD_BYTE), who);
         }
-    spans.begin();
     const uint64_t Ut = h_ctl[QBG_RECORDS];
     uint64_t bound = 0, may_overflow = 0;
     for (uint32_t q = 0; q < nq; q++) { bound += hq(q, QB_CTL_BOUND); may_overflow += hq(q, QB_CTL_MAY_OVERFLOW); }
@@ -493,7 +428,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
     uint64_t Z = 0;
     pdl_query_chunk ch;
     ch.nq = nq; ch.genes = NT; ch.cap = cap;
-    ch.gene_begin = h_gbeg;
+    ch.gene_begin.assign(s.gbeg.begin(), s.gbeg.begin() + nq + 1);
     ch.cells.assign(nq, 0); ch.records.resize(nq); ch.matched.resize(nq); ch.cost.resize(nq);
     if (Ut) {
         w.row_base.alloc(NT * 4ull); w.row_cnt.alloc(NT * 4ull); w.fin_off.alloc((NT + 1) * 4ull); w.overflow.alloc(NT * 4ull);
@@ -516,13 +451,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         q_order_rows(c, a, w.fin_off.as<uint32_t>(), w.rowid.as<uint32_t>(), w.cells.as<float>(), NT, cap, (uint64_t) N + n_max, ctl + QBG_EMITTED, ctl + QBG_WIDE_ROWS);
         hipLaunchKernelGGL(k_qb_counts, dim3((nq + 63) / 64), dim3(64), 0, st, (const uint32_t *) w.fin_off.as<uint32_t>(), lay, ctl);
         PDL_HIP(hipGetLastError());
-        spans.end();
-        {
-            PinRead rd(c);                                       // the per-query counts (and the cursors beside them): one read
-            const uint64_t *pc = rd.add<uint64_t>(ctl, ctl_words);
-            rd.sync();
-            memcpy(h_ctl.data(), pc, ctl_words * sizeof(uint64_t));
-        }
+        q_read_words(c, spans, ctl, ctl_words, h_ctl.data(), false);       // the per-query counts (and the cursors beside them): one read
         const uint64_t staged = h_ctl[QBG_CELL_CURSOR];
         Z = h_ctl[QBG_EMITTED];
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query batch join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);

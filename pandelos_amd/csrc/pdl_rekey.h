@@ -19,7 +19,8 @@
 // side by side; the m % 4 keys of the tail go one to a thread of the first workgroup.
 //
 // Q-rebase (option "query_rekey" of the query entry points, pdl_query.h) uses the same plan the other way round for single keys: a
-// query ranked in a superset alphabet has its records' keys written back into the base's (rk_one, k_q_rebase), see there.
+// query ranked in a superset alphabet has its records' keys written back into the base's (rk_one, k_q_rebase), see there; what it
+// leaves (QRebased) is the `r` of the views QView / QBView<KeyB, KeyQ, true> that k_q_fold, k_q_match, k_qb_fold and k_qb_match read.
 //
 // The host section is what an append and a removal share before the context changes (tools/rekey_host_check.cpp runs it without a
 // device): rank_init_host (the build's too), rk_exact, rk_plan, rk_change — the one decision: the same letters, a re-key, or a

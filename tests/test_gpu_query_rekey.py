@@ -235,6 +235,50 @@ def test_a_chunk_whose_joint_alphabet_is_inexact_is_cut_and_still_answers():
     nat.close()
 
 
+def _cpu_chunks(base_res, queries, k):
+    """the cut rule of a chunk on the CPU (rk_query's: base letters + the chunk's joint new letters must keep B^k below 2^64; a
+    query that would tip that over starts the next chunk): -> the lists of query indices"""
+    have = set(base_res.tolist())
+    chunks, joint = [], set()
+    for j, (res, _) in enumerate(queries):
+        own = set(res.tolist()) - have
+        if chunks and (own <= joint or (len(have) + len(joint | own)) ** k < 1 << 64):
+            chunks[-1].append(j)
+            joint |= own
+        else:
+            chunks.append([j])
+            joint = set(own)
+    return chunks
+
+
+def test_a_chunk_cut_at_every_tipping_query_is_staged_once_and_read_as_prefixes():
+    k = 15
+    base, w, y, _ = _a18_case(k)
+    plain = _genes(base[0][:int(base[1][1])].tobytes())
+    short = _genes(b"AY", b"")                                       # no k-mer; its Y counts all the same
+    qs = [w, y, short, w, plain, y]
+    assert _cpu_chunks(base[0], qs, k) == [[0], [1, 2], [3, 4], [5]]
+    nat = _native(k, *base, options=REKEY)
+    singles, costs = [], []
+    for q in qs:
+        singles.append(nat.query_scores(*q).as_dict())
+        costs.append(nat.last_query_info["genome_cost"])
+    places = [nat.place_query(*q) for q in qs]
+    blocks = nat.query_batch(qs)                                     # (default query_batch_bytes: only the alphabet cuts)
+    info = nat.last_query_batch_info
+    assert info["chunks"] == 4
+    for j, b in enumerate(blocks):
+        H.assert_scores_equal(b.as_dict(), singles[j], f"query {j}")
+        assert info["queries"][j]["genome_cost"] == costs[j], j
+    assert blocks[2].as_dict()["scoresCount"] == 0
+    for j, pl in enumerate(nat.place_batch(qs)):
+        assert_placement(pl, places[j], f"placement {j}")
+    nat.set_option("query_rekey", 0)
+    c, msg = _code(lambda: nat.query_batch(qs))
+    assert c == _lib.PDL_ERR_UNSUPPORTED and "the union would rank k-mers differently" in msg and "query 0:" in msg, msg
+    nat.close()
+
+
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------------
 def _raw_query(nat, q):
     """pdl_query_scores through ctypes with a stale `out`: -> (code, message); a refusal must leave `out` zeroed"""

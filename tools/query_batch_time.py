@@ -13,8 +13,12 @@ alternate --repeat times; median, min, max and the 10th / 90th percentiles of ea
 are compared byte for byte with the sequential ones.  For the ratio DESIGN.md §9 uses, the union rebuild (pdl_preprocess +
 pdl_score_all of base + the first held-out genome, this library) is timed --union-repeat times.
 
+With --rekey-copies N (default 0: off) the batch is instead N copies of tools/query_rekey_time.py's genome — the last genome of
+CONFIG with ONE residue replaced by a letter the set lacks — against the other genomes, option "query_rekey" on in both contexts:
+a re-keyed chunk.  No union rebuild is timed then.
+
 usage: python tools/query_batch_time.py [--config mycoplasma64_standin:8 mycoplasma64_standin:32 synthetic_128x4000x300:8]
-                                        [--baseline-lib PATH] [--out FILE]
+                                        [--rekey-copies N] [--baseline-lib PATH] [--out FILE]
 """
 from __future__ import annotations
 
@@ -85,18 +89,38 @@ def split_last_genomes(gs, q):
     return (rb, ob_, gb), queries, union
 
 
-def measure(config: str, q: int, repeat: int, warmup: int, union_repeat: int, baseline_lib) -> dict:
+def letter_bearing_copies(gs, k, copies):
+    """(base arrays, `copies` times the last genome with a letter the set lacks in the middle of its first gene that has a k-mer)"""
+    from tools.query_time import split_last_genome
+    base, query, _ = split_last_genome(gs)
+    present = np.zeros(256, bool)
+    present[gs.residues] = True
+    letter = next(b for b in b"XUBZOJ*" if not present[b])
+    qx = query[0].copy()
+    lens = np.diff(query[1].astype(np.int64))
+    gene = int(np.argmax(lens >= k))
+    qx[int(query[1][gene]) + int(lens[gene]) // 2] = letter
+    return base, [(qx, query[1])] * copies
+
+
+def measure(config: str, q: int, repeat: int, warmup: int, union_repeat: int, baseline_lib, rekey_copies: int = 0) -> dict:
     from pandelos_amd import _lib
     from pandelos_amd.calculate_k import calculate_k
     from pandelos_amd.pangene_native import PangeneNative
     from pandelos_amd.synth import CONFIGS, make_gene_set
     gs = make_gene_set(**CONFIGS[config])
     k = calculate_k(gs.residues)
-    base, queries, union = split_last_genomes(gs, q)
+    if rekey_copies:
+        q, union_repeat = rekey_copies, -1
+        base, queries = letter_bearing_copies(gs, k, q)
+    else:
+        base, queries, union = split_last_genomes(gs, q)
     nb = PangeneNative.open()
     ns = open_with_library(baseline_lib) if baseline_lib else PangeneNative.open()
     for nat in (nb, ns):
         nat.set_option("stage_timers", 0)
+        if rekey_copies:
+            nat.set_option("query_rekey", 1)
         nat.preprocess(k, *base)
     res, off, begin = PangeneNative.pack_queries(queries)
     n = len(off) - 1
@@ -155,7 +179,7 @@ def measure(config: str, q: int, repeat: int, warmup: int, union_repeat: int, ba
         u_dev.append(tm["preprocess_total_ms"] + tm["score_total_ms"])
     u_dev = u_dev[1:]
     out = {
-        "config": config, "shape": CONFIGS[config], "k": k, "queries": q, "chunks": chunks,
+        "config": config, "shape": CONFIGS[config], "k": k, "queries": q, "chunks": chunks, "rekeyed_copies_of_one_genome": bool(rekey_copies),
         "baseline": "parent commit's library" if baseline_lib else "this library",
         "base": {"sequences": int(nb.cost.sequences), "genomes": int(nb.cost.genomes), "records": int(nb.cost.dictionary_records)},
         "batch": {"genes": n, "residues": int(off[-1]), "cells": cells},
@@ -185,13 +209,14 @@ def main():
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--union-repeat", type=int, default=5)
+    ap.add_argument("--rekey-copies", type=int, default=0, help="N > 0: the batch is N copies of the last genome with a letter the set lacks, query_rekey on")
     ap.add_argument("--baseline-lib", default=None, help="libpandelos_amd.so of the parent commit (default: this library's pdl_query_scores)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     res = []
     for spec in args.config:
         config, _, q = spec.partition(":")
-        r = measure(config, int(q or 8), args.repeat, args.warmup, args.union_repeat, args.baseline_lib)
+        r = measure(config, int(q or 8), args.repeat, args.warmup, args.union_repeat, args.baseline_lib, args.rekey_copies)
         res.append(r)
         print(json.dumps({kk: r.get(kk) for kk in ("config", "queries", "chunks", "baseline", "blocks_equal_the_sequential_ones", "device_speedup_median",
                                                    "wall_speedup_median", "batch_faster_ranges_apart", "per_query_device_ms",
