@@ -550,6 +550,13 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * "order_offsets" 0|1|2 (default 2: the cell offsets of a scoring pass with upper-triangle range lists come from one launch of
  * several workgroups; 1: of one workgroup; 0: from two prefix scans, four launches.  Same results: for parity tests and A/B timing),
  * "order_offsets_rows" n (that launch serves at most n task rows, default and maximum 131 072; tests lower it),
+ * "order_subwave" 0|1|16|32 (default 1 = 16: a wave of the kernel that puts the cells in emission order takes 64 / W rows, each in a
+ * segment of W lanes, and the mirrored cells are handed on W lanes per source row; 0: a wave per row), "order_wide_merged" 0|1
+ * (default 1: the rows of more than 256 cells are sorted by workgroups of that same launch; 0: by a launch of their own),
+ * "fused_glue" 0|1|n (default 1: the descriptors and the clearing that open the first scoring pass are one launch, and so are the
+ * genes' range offsets and the per-genome costs that close a build; 0: one launch each; n > 1: as 1, and the k-mer counts of the
+ * genes with the clearing of the control block in one launch for up to min(n, 65 536) genes, measured slower.  Same results for all three: for parity
+ * tests and A/B timing),
  * "aside_test_reload" 0|1 (test switch: the next scoring pass
  * behaves as if an entry of a put-aside list had needed a second look, so the repeat with fully tagged entries runs),
  * "alphabet_rekey" 0|1 (default 0: pdl_append_genomes / pdl_remove_genomes go through where the alphabet changes, by writing the

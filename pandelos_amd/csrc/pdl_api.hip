@@ -847,6 +847,18 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
         if (value < 0) PDL_FAIL(PDL_ERR_ARGUMENT, "order_offsets_rows: a row count");
         c->opt_order_offsets_rows = (uint32_t) std::min<int64_t>(value, 0xffffffffll);
     }
+    else if (n == "order_subwave") {
+        if (!(value == 0 || value == 1 || value == 16 || value == 32)) PDL_FAIL(PDL_ERR_ARGUMENT, "order_subwave: 0 (a wave per row), 1 (the default width), 16 or 32 (lanes per row)");
+        c->opt_order_subwave = (int) value;
+    }
+    else if (n == "order_wide_merged") {
+        if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "order_wide_merged: 0 or 1");
+        c->opt_order_wide_merged = value != 0;
+    }
+    else if (n == "fused_glue") {
+        if (value < 0) PDL_FAIL(PDL_ERR_ARGUMENT, "fused_glue: 0, 1, or n > 1 (as 1, and K-len in one launch for up to n genes)");
+        c->opt_fused_glue = (int) std::min<int64_t>(value, 0x7fffffff);
+    }
     else if (n == "low_memory") c->opt_low_memory = value != 0;
     else if (n == "query_batch_bytes") {
         if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "query_batch_bytes: a positive byte count");

@@ -423,6 +423,9 @@ struct pdl_ctx {
     bool opt_onepass_scan = false;        // scans in one launch (decoupled look-back) instead of three: measured 3-10 % slower per scan on MI355X, kept as an option
     int opt_order_offsets = 2;            // K-order's two offset scans: 2 = one launch of several workgroups (k_order_offsets), 1 = of one workgroup, 0 = the four launches of two scans
     uint32_t opt_order_offsets_rows = 1u << 17;   // ... for at most so many task rows (at most OO_MAX_ROWS; tests lower it)
+    int opt_order_subwave = 1;            // K-order: several short rows per wave, each in a segment of lanes: 1 = the default width, 16 | 32 = that many lanes, 0 = a wave per row
+    bool opt_order_wide_merged = true;    // ... with the wide rows' workgroups behind them in the same launch; 0: k_order_rows in a launch of its own
+    int opt_fused_glue = 1;               // small launches that share one: row descriptors + clearing (scoring), K-cost + K-seq-offsets (build); n > 1: also K-len with the control block's clearing, for up to min(n, KL_MAX_GENES) genes (measured: does not pay); 0: each its own
     bool opt_lean_radix = true;          // radix passes: offsets in one launch (k_rs_offsets), the rank sort's first histogram filed by K-rank; 0: a histogram and a three-launch scan per pass
     DevBuf scratch;       // transient buffers of the range build
     DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*, above)

@@ -96,6 +96,103 @@ struct KseqApply {
     }
 };
 
+// K-len in ONE launch (option "fused_glue" n > 1, up to KL_MAX_GENES genes), after k_order_offsets: a workgroup owns KL_TILE genes, adds up
+// the k-mer counts of the genes in front of them itself (the offsets are L2-resident: 8 bytes a gene) and scans its own, four
+// consecutive genes per thread.  Nobody waits for another workgroup.  It writes what KseqFlag / KseqApply write, and clears the
+// control block first (the k_zero_u64 in front of the scan): every workgroup a slice of it, except the two words this launch
+// writes itself — the last workgroup, which has seen every offset, stores the total (PDL_CTL_KMERS, kmer_off[N]) and whether the
+// offsets fail to ascend to the residue count (PDL_CTL_BAD_OFFSETS), plainly, so neither word needs to be zero beforehand.
+constexpr uint32_t KL_THREADS = 1024, KL_ITEMS = 4, KL_TILE = KL_THREADS * KL_ITEMS;
+// Measured: 14.1 / 19.4 / 30.0 / 53.0 us at 2^15 / 2^16 / 2^17 / 2^18 genes against 13.3 - 15.6 us for the clearing
+// launch and the scan's kernels together — never below them, so "fused_glue" 1 leaves K-len its scan and only a value n > 1 asks
+// for this kernel, for up to min(n, KL_MAX_GENES) genes.  The bound: up to 2^16 genes the one launch still ends sooner than the
+// three it replaces (19.4 us against 21.8 from the first's start to the last's end); the last workgroup's read of everything in
+// front of it doubles with the gene count, the scan's tiles do not.
+constexpr uint32_t KL_MAX_GENES = 1u << 16;
+struct KlenArgs {
+    const uint64_t *off; uint64_t n_res; uint32_t k, n;
+    uint32_t *kseq_len, *gene_len; uint64_t *kmer_off; unsigned long long *cost;
+    uint64_t *ctl; uint64_t ctl_words;
+};
+__device__ __forceinline__ uint32_t kseq_of(uint64_t b, uint64_t e, uint32_t k) {
+    const uint64_t len = e >= b ? e - b : 0;
+    return len >= k ? (uint32_t) (len - k + 1) : 0u;
+}
+__global__ __launch_bounds__(KL_THREADS) void k_kseq_lengths(KlenArgs a) {
+    constexpr uint32_t NW = KL_THREADS / PDL_WAVE;
+    __shared__ unsigned long long s_sum[NW], s_front[NW];
+    __shared__ uint32_t s_bad[NW];
+    const uint32_t tid = threadIdx.x, lane = tid & (PDL_WAVE - 1), wave = tid / PDL_WAVE;
+    for (uint64_t i = (uint64_t) blockIdx.x * KL_THREADS + tid; i < a.ctl_words; i += (uint64_t) gridDim.x * KL_THREADS)
+        if (i != PDL_CTL_KMERS && i != PDL_CTL_BAD_OFFSETS) a.ctl[i] = 0;
+    const uint32_t r0 = min(blockIdx.x * KL_TILE, a.n), r1 = min(r0 + KL_TILE, a.n);
+    // five offsets of four consecutive genes (from a multiple of four on: `off` is 16-byte aligned, the host has seen to that) in
+    // three independent loads; the genes' k-mers summed, and whether an offset is out of order
+    auto four = [&](uint32_t i, uint32_t *f4, uint32_t *gl4) -> uint32_t {
+        const ulonglong2 lo = *reinterpret_cast<const ulonglong2 *>(a.off + i), hi = *reinterpret_cast<const ulonglong2 *>(a.off + i + 2);
+        const uint64_t o[5] = {lo.x, lo.y, hi.x, hi.y, a.off[i + 4]};
+        uint32_t wrong = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) {
+            f4[j] = kseq_of(o[j], o[j + 1], a.k); gl4[j] = (uint32_t) (o[j + 1] - o[j]);
+            wrong |= (o[j + 1] < o[j] || o[j + 1] > a.n_res) ? 1u : 0u;
+        }
+        return wrong;
+    };
+    // the genes in front (r0 is a multiple of KL_TILE): their k-mers, and (of use to the last workgroup only) whether their
+    // offsets are in order.  Eight trips' loads in flight: one at a time, each waited for, is all latency (57 us for 2^17 genes).
+    unsigned long long front = 0;
+    uint32_t bad = 0;
+#pragma unroll 8
+    for (uint32_t i = tid * KL_ITEMS; i < r0; i += KL_TILE) {
+        uint32_t f4[4], gl4[4];
+        bad |= four(i, f4, gl4);
+        front += (unsigned long long) f4[0] + f4[1] + f4[2] + f4[3];
+    }
+    // this workgroup's genes
+    const uint32_t i0 = r0 + tid * KL_ITEMS;
+    uint32_t f[KL_ITEMS], gl[KL_ITEMS];
+    unsigned long long sum = 0;
+    if (i0 + KL_ITEMS <= r1) bad |= four(i0, f, gl);
+    else {
+#pragma unroll
+        for (uint32_t j = 0; j < KL_ITEMS; j++) {
+            f[j] = 0; gl[j] = 0;
+            if (i0 + j < r1) {
+                const uint64_t b = a.off[i0 + j], e = a.off[i0 + j + 1];
+                f[j] = kseq_of(b, e, a.k); gl[j] = (uint32_t) (e - b);
+                bad |= (e < b || e > a.n_res) ? 1u : 0u;
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < KL_ITEMS; j++) sum += f[j];
+    unsigned long long inc = sum;
+#pragma unroll
+    for (int d = 1; d < PDL_WAVE; d <<= 1) {
+        const unsigned long long o = __shfl_up(inc, d, PDL_WAVE);
+        if (lane >= (uint32_t) d) inc += o;
+    }
+#pragma unroll
+    for (int d = PDL_WAVE / 2; d > 0; d >>= 1) { front += __shfl_xor(front, d, PDL_WAVE); bad |= (uint32_t) __shfl_xor((int) bad, d, PDL_WAVE); }
+    if (lane == PDL_WAVE - 1) s_sum[wave] = inc;
+    if (lane == 0) { s_front[wave] = front; s_bad[wave] = bad; }
+    pdl_sync();
+    unsigned long long ex = inc - sum, total = 0;          // exclusive inside the wave, + the waves before, + the genes in front
+    uint32_t bad_all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < NW; w++) {
+        const unsigned long long v = s_sum[w], fr = s_front[w];
+        ex += fr + (w < wave ? v : 0ull); total += fr + v; bad_all |= s_bad[w];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < KL_ITEMS; j++) {
+        if (i0 + j < r1) { a.kseq_len[i0 + j] = f[j]; a.gene_len[i0 + j] = gl[j]; a.kmer_off[i0 + j] = ex; a.cost[i0 + j] = 0; }
+        ex += f[j];
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) { a.ctl[PDL_CTL_KMERS] = total; a.kmer_off[a.n] = total; a.ctl[PDL_CTL_BAD_OFFSETS] = bad_all ? 1ull : 0ull; }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K-rank (exact): one thread per k-mer of the stream.  Because B^k < 2^64 here, the reference's
 // rolling update (library.cpp:75-79) equals the direct base-B polynomial of the k residues, so
@@ -430,10 +527,9 @@ __global__ __launch_bounds__(256) void k_gather_ranges(const uint32_t *__restric
 }
 // seq_off[s] = first range of gene s in the gene-sorted list (lower bound), seq_off[N] = number of ranges
 // (the sorted field of a key is (key >> shift) & mask: the tuples of a multi-GPU build carry the owner rank above the gene)
-__global__ __launch_bounds__(256) void k_seq_offsets(const uint32_t *__restrict__ key_sorted, const uint64_t *d_n, uint32_t n_seq,
-                                                     uint32_t *__restrict__ seq_off, uint32_t shift = 0, uint32_t mask = 0xffffffffu) {
+__device__ __forceinline__ void seq_offset_of(uint32_t s, const uint32_t *__restrict__ key_sorted, const uint64_t *d_n, uint32_t n_seq,
+                                              uint32_t *__restrict__ seq_off, uint32_t shift, uint32_t mask) {
     const uint32_t n = (uint32_t) *d_n;
-    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
     if (s > n_seq) return;
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
@@ -442,21 +538,30 @@ __global__ __launch_bounds__(256) void k_seq_offsets(const uint32_t *__restrict_
     }
     seq_off[s] = lo;
 }
+__global__ __launch_bounds__(256) void k_seq_offsets(const uint32_t *__restrict__ key_sorted, const uint64_t *d_n, uint32_t n_seq,
+                                                     uint32_t *__restrict__ seq_off, uint32_t shift = 0, uint32_t mask = 0xffffffffu) {
+    seq_offset_of(blockIdx.x * 256 + threadIdx.x, key_sorted, d_n, n_seq, seq_off, shift, mask);
+}
 
 // K-cost: per-genome cost (library.cpp:535-538); the total is their sum (library.cpp:337-349).
 // Genes of a genome are usually adjacent, so a wave first tries to add up as one.  The three dataset-wide values
 // (sum / max / min of kseq_lengths) are kept per lane over a grid-stride loop and leave the workgroup as ONE atomic each:
 // same-address device atomics serialise at ~10-50 ns apiece, a wave's worth per 64 genes took longer than the sums.
-__global__ __launch_bounds__(256) void k_genome_cost(const unsigned long long *__restrict__ cost, const uint32_t *__restrict__ kseq_len,
-                                                     const uint32_t *__restrict__ genome_of, uint32_t n_seq,
-                                                     unsigned long long *__restrict__ genome_cost, unsigned long long *__restrict__ sum_kseq,
-                                                     unsigned long long *__restrict__ max_kseq, unsigned long long *__restrict__ min_kseq) {
+struct GenomeCostArgs {
+    const unsigned long long *cost; const uint32_t *kseq_len, *genome_of; uint32_t n_seq;
+    unsigned long long *genome_cost, *sum_kseq, *max_kseq, *min_kseq;
+};
+__device__ __forceinline__ void genome_cost_by(const GenomeCostArgs &a, uint32_t block, uint32_t n_blocks) {
+    const unsigned long long *__restrict__ cost = a.cost;
+    const uint32_t *__restrict__ kseq_len = a.kseq_len, *__restrict__ genome_of = a.genome_of;
+    const uint32_t n_seq = a.n_seq;
+    unsigned long long *__restrict__ genome_cost = a.genome_cost, *__restrict__ sum_kseq = a.sum_kseq, *__restrict__ max_kseq = a.max_kseq, *__restrict__ min_kseq = a.min_kseq;
     __shared__ unsigned long long s_sum, s_max, s_min;
     if (threadIdx.x == 0) { s_sum = 0; s_max = 0; s_min = ~0ull; }
     pdl_sync();
     const uint32_t lane = threadIdx.x & (PDL_WAVE - 1);
     unsigned long long ksum = 0, kmax = 0, kmin = ~0ull;
-    for (uint32_t s0 = blockIdx.x * 256; s0 < n_seq; s0 += gridDim.x * 256) {
+    for (uint32_t s0 = block * 256; s0 < n_seq; s0 += n_blocks * 256) {
         const uint32_t s = s0 + threadIdx.x;
         const bool live = s < n_seq;
         unsigned long long c = live ? cost[s] : 0ull;
@@ -485,14 +590,25 @@ __global__ __launch_bounds__(256) void k_genome_cost(const unsigned long long *_
     pdl_sync();
     if (threadIdx.x == 0 && s_sum) { atomicAdd(sum_kseq, s_sum); atomicMax(max_kseq, s_max); atomicMax(min_kseq, ~s_min); }   // min kept as a max of complements: zero-initialised like the rest
 }
+__global__ __launch_bounds__(256) void k_genome_cost(GenomeCostArgs a) { genome_cost_by(a, blockIdx.x, gridDim.x); }
+// Option "fused_glue": the two kernels that close a build in ONE launch — the first `off_blocks` workgroups place the genes among
+// the sorted ranges, the ones behind them add up the costs.  Neither half reads what the other writes.
+__global__ __launch_bounds__(256) void k_close_build(const uint32_t *__restrict__ key_sorted, const uint64_t *d_n, uint32_t *__restrict__ seq_off, uint32_t gene_mask,
+                                                     GenomeCostArgs a, uint32_t off_blocks) {
+    if (blockIdx.x < off_blocks) seq_offset_of(blockIdx.x * 256 + threadIdx.x, key_sorted, d_n, a.n_seq, seq_off, 0u, gene_mask);
+    else genome_cost_by(a, blockIdx.x - off_blocks, gridDim.x - off_blocks);
+}
 
 // K-cost: cost[] summed per genome into scalars[PDL_CTL_GCOST ..]; the k-mer statistics of the genes it adds up on the way
 // go to scalars[w_sum] (sum), scalars[w_max] (max) and the word behind that (~min)
-static void launch_genome_cost(pdl_ctx *c, size_t w_sum, size_t w_max) {
+static GenomeCostArgs genome_cost_args(pdl_ctx *c, size_t w_sum, size_t w_max) {
     static_assert(PDL_CTL_KSEQ_NMIN == PDL_CTL_KSEQ_MAX + 1 && PDL_CTL_LAZY_KSEQ_MAX + 1 <= PDL_CTL_LAST, "~min sits behind max");
     unsigned long long *d_scal = c->scalars.as<unsigned long long>();
-    hipLaunchKernelGGL(k_genome_cost, dim3(std::min<uint32_t>((c->N + 255) / 256, 128)), dim3(256), 0, c->stream, c->cost.as<unsigned long long>(),
-                       c->kseq_len.as<uint32_t>(), c->d_gen, c->N, d_scal + PDL_CTL_GCOST, d_scal + w_sum, d_scal + w_max, d_scal + w_max + 1);
+    return {c->cost.as<unsigned long long>(), c->kseq_len.as<uint32_t>(), c->d_gen, c->N, d_scal + PDL_CTL_GCOST, d_scal + w_sum, d_scal + w_max, d_scal + w_max + 1};
+}
+static uint32_t genome_cost_blocks(const pdl_ctx *c) { return std::min<uint32_t>((c->N + 255) / 256, 128); }
+static void launch_genome_cost(pdl_ctx *c, size_t w_sum, size_t w_max) {
+    hipLaunchKernelGGL(k_genome_cost, dim3(genome_cost_blocks(c)), dim3(256), 0, c->stream, genome_cost_args(c, w_sum, w_max));
     PDL_HIP(hipGetLastError());
 }
 
@@ -516,7 +632,11 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     const size_t ctl_words = PDL_CTL_GCOST + 2 * (size_t) (c->layout_deferred ? c->N : c->G);
     c->scalars.alloc(ctl_words * sizeof(uint64_t));
     uint64_t *d_scal = c->scalars.as<uint64_t>();
-    hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);     // (a kernel: a fill is a blit with ~10 us of barrier packets around it)
+    // K-len in one launch, which clears the control block itself (option "fused_glue" n > 1: up to min(n, KL_MAX_GENES) genes), or the
+    // clearing launch here and the three-launch scan below
+    const bool klen_one_launch = c->opt_fused_glue > 1 && c->N > 0 && ((uintptr_t) c->d_off & 15) == 0 && c->N <= std::min<uint32_t>((uint32_t) c->opt_fused_glue, KL_MAX_GENES);
+    if (!klen_one_launch)
+        hipLaunchKernelGGL(k_zero_u64, dim3((uint32_t) std::min<size_t>((ctl_words + 255) / 256, 1024)), dim3(256), 0, st, d_scal, ctl_words);     // (a kernel: a fill is a blit with ~10 us of barrier packets around it)
 
     ev_begin(c, EV_HIST);
     // K-len (independent of the histogram, reads the offsets only); its apply step also clears cost[], its total also lands in kmer_off[N]
@@ -524,7 +644,12 @@ static void stage_alphabet_and_lengths(pdl_ctx *c, int kvalue, bool only_complex
     c->gene_len.alloc((size_t) c->N * sizeof(uint32_t));
     c->kmer_off.alloc(((size_t) c->N + 1) * sizeof(uint64_t));
     c->cost.alloc((size_t) c->N * sizeof(uint64_t));
-    scan_and_apply(c, c->N, KseqFlag{c->d_off, (uint32_t) kvalue},
+    if (klen_one_launch)
+        hipLaunchKernelGGL(k_kseq_lengths, dim3((c->N + KL_TILE - 1) / KL_TILE), dim3(KL_THREADS), 0, st,
+                           KlenArgs{c->d_off, c->R, (uint32_t) kvalue, c->N, c->kseq_len.as<uint32_t>(), c->gene_len.as<uint32_t>(), c->kmer_off.as<uint64_t>(),
+                                    c->cost.as<unsigned long long>(), d_scal, (uint64_t) ctl_words});
+    else
+        scan_and_apply(c, c->N, KseqFlag{c->d_off, (uint32_t) kvalue},
                    KseqApply{c->kseq_len.as<uint32_t>(), c->gene_len.as<uint32_t>(), c->kmer_off.as<uint64_t>(), c->cost.as<unsigned long long>(), c->d_off, c->R,
                              reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_BAD_OFFSETS)}, d_scal + PDL_CTL_KMERS, c->kmer_off.as<uint64_t>() + c->N);
     if (c->layout_deferred) pdl_input_arrived(c);        // offsets[0] = 0 and offsets[N] = R checked before anything indexes residues
@@ -730,25 +855,32 @@ static uint64_t count_then_write(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, i
 }
 
 // K-seq-offsets: every gene's place among the ranges sorted by gene (the gene of a key: its bits under gene_mask)
-static void launch_seq_offsets(pdl_ctx *c, const uint32_t *keys_by_gene, uint32_t gene_mask) {
+// with_cost (a build's own range stage under option "fused_glue"): K-cost, which would be the next launch, rides in this one
+static void launch_seq_offsets(pdl_ctx *c, const uint32_t *keys_by_gene, uint32_t gene_mask, bool with_cost = false) {
     c->seq_off.alloc(((size_t) c->N + 1) * sizeof(uint32_t));
-    hipLaunchKernelGGL(k_seq_offsets, dim3((c->N + 1 + 255) / 256), dim3(256), 0, c->stream, keys_by_gene, c->scalars.as<uint64_t>() + PDL_CTL_RANGES, c->N, c->seq_off.as<uint32_t>(), 0u, gene_mask);
+    const uint32_t off_blocks = (c->N + 1 + 255) / 256;
+    const uint64_t *d_n = c->scalars.as<uint64_t>() + PDL_CTL_RANGES;
+    if (with_cost)
+        hipLaunchKernelGGL(k_close_build, dim3(off_blocks + genome_cost_blocks(c)), dim3(256), 0, c->stream, keys_by_gene, d_n, c->seq_off.as<uint32_t>(), gene_mask,
+                           genome_cost_args(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX), off_blocks);
+    else hipLaunchKernelGGL(k_seq_offsets, dim3(off_blocks), dim3(256), 0, c->stream, keys_by_gene, d_n, c->N, c->seq_off.as<uint32_t>(), 0u, gene_mask);
     PDL_HIP(hipGetLastError());
 }
 static uint32_t gene_id_bits(const pdl_ctx *c) { return std::max<uint32_t>(1, bit_length64(c->N ? c->N - 1 : 0)); }
 
 // Packed ranges, by gene: the sort of n_sort pairs (their count at d_sort_n, or n_sort itself; none: no sort) over the gene bits from first_bit on into
 // (k2b, pay_b), the genes' offsets, and the context's view: the join reads the ranges where the sort left them.  Ends EV_SORT2 (the caller's), spans EV_RANGES.
-static void sort_ranges_by_gene(pdl_ctx *c, RangeBufs b, uint64_t n_sort, const uint64_t *d_sort_n, uint32_t first_bit, uint32_t gene_mask) {
+static void sort_ranges_by_gene(pdl_ctx *c, RangeBufs b, uint64_t n_sort, const uint64_t *d_sort_n, uint32_t first_bit, uint32_t gene_mask, bool with_cost = false) {
     if (n_sort) pdl_sort_pairs<uint32_t, unsigned long long>(c, b.k2a, b.k2b, b.pay_a, b.pay_b, n_sort, gene_id_bits(c), false, d_sort_n, first_bit, true);
     ev_end(c, EV_SORT2); ev_begin(c, EV_RANGES);
     c->ranges8 = reinterpret_cast<const uint2 *>(b.pay_b); c->upper_only = true;
-    launch_seq_offsets(c, b.k2b, gene_mask);
+    launch_seq_offsets(c, b.k2b, gene_mask, with_cost);
     ev_end(c, EV_RANGES);
 }
 
-// K-ranges of stage_ranges_and_costs: the range lists of `mode` from the postings of ga, gene major, by the plan.
-static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode) {
+// K-ranges of stage_ranges_and_costs: the range lists of `mode` from the postings of ga, gene major, by the plan.  with_cost: K-cost
+// rides in the last launch (launch_seq_offsets).
+static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode, bool with_cost) {
     hipStream_t st = c->stream;
     uint64_t *d_scal = c->scalars.as<uint64_t>();
     const uint64_t bound = ga.n_bound, *d_us = d_scal + PDL_CTL_RANGES;       // d_us: ranges built = the total of the tile counts
@@ -784,7 +916,7 @@ static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode)
         }
     }
     if (plan.packed) {
-        sort_ranges_by_gene(c, b, n_sort, d_sort_n, first_bit, 0xffffffffu);
+        sort_ranges_by_gene(c, b, n_sort, d_sort_n, first_bit, 0xffffffffu, with_cost);
     } else {                                               // values = tuple positions: sorted pairs in (k2b, v2b), the tuples fetched through them
         pdl_sort_pairs<uint32_t>(c, b.k2a, b.k2b, b.v2a, b.v2b, n_sort, gene_id_bits(c), true, d_sort_n, 0, true);
         ev_end(c, EV_SORT2); ev_begin(c, EV_RANGES);
@@ -792,7 +924,7 @@ static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode)
         c->ranges.alloc(std::max<uint64_t>(n_sort, 1) * sizeof(uint4));
         const uint32_t gblocks = (uint32_t) std::max<uint64_t>((n_sort + 255) / 256, 1);
         hipLaunchKernelGGL(k_gather_ranges, dim3(gblocks), dim3(256), 0, st, b.v2b, b.k2b, b.tuples, d_us, c->ranges.as<uint4>(), c->cost.as<unsigned long long>());
-        launch_seq_offsets(c, b.k2b, 0xffffffffu);
+        launch_seq_offsets(c, b.k2b, 0xffffffffu, with_cost);
         ev_end(c, EV_RANGES);
     }
 }
@@ -823,11 +955,12 @@ static void stage_ranges_and_costs(pdl_ctx *c, uint64_t bound, int mode, bool on
     gp.a.cost = c->cost.as<unsigned long long>();
     gp.a.counters = reinterpret_cast<unsigned long long *>(d_scal + PDL_CTL_COUNTERS);
     hipLaunchKernelGGL(k_fold_last_record, dim3(1), dim3(1024), 0, c->stream, gp.a.post, c->post_ext ? (uint32_t *) nullptr : c->recpos.as<uint32_t>(), gp.a.d_n);
+    const bool cost_rides = c->opt_fused_glue && !only_complexity && c->N > 0;     // K-cost in K-seq-offsets' launch
     if (only_complexity) { c->ranges8 = nullptr; launch_group_costs<false, true>(c, gp.a, gp.grid); }    // (cost[] was zeroed by K-len's apply, the counters with the control block)
-    else build_ranges(c, gp.a, gp.grid, mode);
+    else build_ranges(c, gp.a, gp.grid, mode, cost_rides);
     // packed ranges: "Total cost" straight from the WRITE pass; per-gene / per-genome costs on demand (pdl_ensure_costs)
     c->costs_ready = c->ranges8 == nullptr;
-    launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);       // K-cost
+    if (!cost_rides) launch_genome_cost(c, PDL_CTL_KSEQ_SUM, PDL_CTL_KSEQ_MAX);       // K-cost
     PinRead rd(c);                           // one copy: the whole control block
     const uint64_t *pt = closing_read(c, rd, PDL_CTL_GCOST + (size_t) c->G);
     c->h_genome_cost.assign(pt + PDL_CTL_GCOST, pt + PDL_CTL_GCOST + c->G);     // (a shard, one rank of several: its own genomes only)

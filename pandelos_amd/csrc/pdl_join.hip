@@ -7,7 +7,7 @@
 //                            and per-(row, genome) / per-column maxima.  Tier 1 = small table behind a
 //                            "seen twice" bitmap filter (several rows per CU), tier 2 = 8192-slot table
 //   K-join-hbm  k_join_hbm   tier 3: same row program with direct-addressed tables in HBM
-//   K-order     k_mirror_cells, k_order_rows  every row's cells in the reference's emission order
+//   K-order     k_mirror_cells_sub, k_order_rows_sub  every row's cells in the reference's emission order
 //                            (first-touch order, library.cpp:456-482,493 — SURVEY.md §8a row 9a)
 //
 // Row program (all tiers).  A row gene r owns a list of posting ranges, one per record of r that sits in a
@@ -910,6 +910,9 @@ constexpr int ORDER_TILE = 2048;
 constexpr uint32_t ORDER_CPL = 4;                              // cells per lane in the wave-per-row kernel
 constexpr uint32_t ORDER_WAVE_CELLS = ORDER_CPL * PDL_WAVE;    // rows up to this many cells are ranked inside one wave
 
+constexpr uint32_t ORDER_SUB_W = 16;                           // option "order_subwave" 1: lanes per short row
+static uint32_t order_sub_w(const pdl_ctx *c) { return c->opt_order_subwave == 1 ? ORDER_SUB_W : (uint32_t) c->opt_order_subwave; }      // 0 | 16 | 32
+
 struct MCell { uint32_t col, first; float score, perc, tr; uint32_t pad; };       // a mirrored cell as its row reads it (24 bytes)
 struct OrderArgs {
     const uint32_t *row_base, *row_cnt, *fin_off, *task_rows;
@@ -957,14 +960,10 @@ __device__ __forceinline__ void cell_values(const OrderArgs &a, const OrderCell 
     else { score = a.st_score[oc.slot]; perc = a.st_perc[oc.slot]; tr = a.st_tr[oc.slot]; }
 }
 
-__global__ __launch_bounds__(ORDER_THREADS) void k_order_rows(OrderArgs a) {
+// a row of more than ORDER_WAVE_CELLS cells (`own` of them its own), by the whole workgroup
+__device__ __forceinline__ void order_wide_row(const OrderArgs &a, uint32_t p, uint32_t own, uint32_t cnt) {
     __shared__ unsigned long long s_hi[ORDER_TILE];
     __shared__ uint32_t s_col[ORDER_TILE];
-    if (*a.wide_rows == 0) return;               // no row is wider than the wave kernel's limit (the usual case)
-  for (uint32_t p = blockIdx.x; p < a.n_rows; p += gridDim.x) {       // persistent workgroups: rows dealt round-robin
-    const uint32_t own = a.row_cnt[p];
-    const uint32_t cnt = own + (a.mirror_cnt ? a.mirror_cnt[p] : 0u);
-    if (cnt <= ORDER_WAVE_CELLS) continue;       // k_order_rows_wave's rows (uniform)
     pdl_sync();                             // the LDS tiles of the previous row are done with
     const uint32_t out0 = a.fin_off[p];
     const uint32_t row = a.task_rows[p];
@@ -1009,7 +1008,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_order_rows(OrderArgs a) {
             a.c_row[o] = (int32_t) row;
             a.c_col[o] = (int32_t) col;
         }
-        continue;
+        return;
     }
     if (cnt <= ORDER_TILE) {
         // bitonic sort of the row's keys in LDS (keys are unique: the column is part of them); position q of the sorted
@@ -1065,7 +1064,7 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_order_rows(OrderArgs a) {
             a.c_row[o] = (int32_t) row;
             a.c_col[o] = (int32_t) s_col[q];
         }
-        continue;
+        return;
     }
     for (uint32_t i0 = 0; i0 < cnt; i0 += ORDER_THREADS) {
         const uint32_t i = i0 + threadIdx.x;
@@ -1108,9 +1107,35 @@ __global__ __launch_bounds__(ORDER_THREADS) void k_order_rows(OrderArgs a) {
             a.c_col[o] = (int32_t) col;
         }
     }
-  }
 }
-
+__global__ __launch_bounds__(ORDER_THREADS) void k_order_rows(OrderArgs a) {
+    if (*a.wide_rows == 0) return;               // no row is wider than the wave kernel's limit (the usual case)
+    for (uint32_t p = blockIdx.x; p < a.n_rows; p += gridDim.x) {       // persistent workgroups: rows dealt round-robin
+        const uint32_t own = a.row_cnt[p];
+        const uint32_t cnt = own + (a.mirror_cnt ? a.mirror_cnt[p] : 0u);
+        if (cnt > ORDER_WAVE_CELLS) order_wide_row(a, p, own, cnt);       // (the others: k_order_rows_wave's rows; uniform)
+    }
+}
+// The same without the counter, for workgroups that share a launch with the short rows' ones: workgroup `block` of `n_blocks` has
+// the rows k_order_rows would deal it (block, block + n_blocks, ...) and looks at 256 of their counts at a time, one per thread
+// (a workgroup that walked its rows one dependent load after the other took 20 us to find nothing on 47 891 rows), and lists the
+// wide ones in LDS.
+__device__ __forceinline__ void order_wide_rows_dealt(const OrderArgs &a, uint32_t block, uint32_t n_blocks) {
+    __shared__ uint32_t s_found[ORDER_THREADS], s_n;
+    for (uint32_t base = block; base < a.n_rows; base += ORDER_THREADS * n_blocks) {       // (uniform: barriers inside; n_rows < 2^31 task rows)
+        const uint64_t p = (uint64_t) base + (uint64_t) threadIdx.x * n_blocks;
+        if (threadIdx.x == 0) s_n = 0;
+        pdl_sync();
+        if (p < a.n_rows && a.row_cnt[p] + (a.mirror_cnt ? a.mirror_cnt[p] : 0u) > ORDER_WAVE_CELLS) s_found[atomicAdd(&s_n, 1u)] = (uint32_t) p;
+        pdl_sync();
+        const uint32_t n = s_n;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t q = s_found[i], own = a.row_cnt[q];
+            order_wide_row(a, q, own, own + (a.mirror_cnt ? a.mirror_cnt[q] : 0u));
+        }
+        pdl_sync();                              // everybody has read s_n and the list
+    }
+}
 // Rows of at most 256 cells (nearly all rows of most datasets): one wave per row, up to four cells per lane, the keys
 // compared through lane reads — no LDS, no barrier, four rows per workgroup.
 __global__ __launch_bounds__(256) void k_order_rows_wave(OrderArgs a) {
@@ -1186,6 +1211,100 @@ __global__ __launch_bounds__(256) void k_order_rows_wave(OrderArgs a) {
     }
 }
 
+// Option "order_subwave": a wave ranks 64 / W rows at a time, each in a segment of W lanes (a row of the 64-genome set has ~11
+// cells: a whole wave for it keeps a sixth of the lanes busy, and every wave waits through the same chain of dependent loads).
+// The rank is the same count over the same keys, read through lane reads of width W; the keys are unique, so where a cell sits
+// among the lanes does not matter.  `cnt` is 0 for a segment that sits this call out; `max_cnt` is the largest cnt of the wave
+// (uniform): every segment walks that many keys, and what lies behind a row's own cells are padding keys that sort last.
+template <uint32_t W>
+__device__ __forceinline__ void order_rank_rows(const OrderArgs &a, uint32_t p, uint32_t own, uint32_t cnt, uint32_t sl, uint32_t max_cnt) {
+    uint32_t col[ORDER_CPL], first[ORDER_CPL], rank[ORDER_CPL];
+    OrderCell me[ORDER_CPL];
+#pragma unroll
+    for (uint32_t s = 0; s < ORDER_CPL; s++) {
+        col[s] = 0xffffffffu; first[s] = 0; rank[s] = 0; me[s] = OrderCell{0, false};
+        const uint32_t i = s * W + sl;
+        if (i < cnt) {
+            me[s] = order_cell(a, p, own, i);
+            const uint2 km = cell_key(a, me[s]);
+            col[s] = km.x; first[s] = km.y;
+        }
+    }
+    if (a.pack_ok) {                                     // (uniform)
+        unsigned long long key[ORDER_CPL];
+#pragma unroll
+        for (uint32_t s = 0; s < ORDER_CPL; s++) key[s] = s * W + sl < cnt ? order_key_packed(col[s], first[s], a.canonical) : ~0ull;
+#pragma unroll
+        for (uint32_t sj = 0; sj < ORDER_CPL; sj++) {
+            if (sj * W >= max_cnt) break;
+            const uint32_t nj = min(W, max_cnt - sj * W);
+            for (uint32_t j = 0; j < nj; j++) {
+                const unsigned long long kj = ((unsigned long long) (uint32_t) __shfl((int) (uint32_t) (key[sj] >> 32), (int) j, (int) W) << 32) |
+                                              (uint32_t) __shfl((int) (uint32_t) key[sj], (int) j, (int) W);
+#pragma unroll
+                for (uint32_t s = 0; s < ORDER_CPL; s++) rank[s] += kj < key[s] ? 1u : 0u;
+            }
+        }
+    } else {
+        unsigned long long hi[ORDER_CPL];                // (a padding cell: every word all ones, behind every key there is)
+#pragma unroll
+        for (uint32_t s = 0; s < ORDER_CPL; s++) hi[s] = s * W + sl < cnt ? order_key_hi(col[s], first[s], a.canonical) : ~0ull;
+#pragma unroll
+        for (uint32_t sj = 0; sj < ORDER_CPL; sj++) {
+            if (sj * W >= max_cnt) break;
+            const uint32_t nj = min(W, max_cnt - sj * W);
+            for (uint32_t j = 0; j < nj; j++) {
+                const unsigned long long hj = ((unsigned long long) (uint32_t) __shfl((int) (uint32_t) (hi[sj] >> 32), (int) j, (int) W) << 32) |
+                                              (uint32_t) __shfl((int) (uint32_t) hi[sj], (int) j, (int) W);
+                const uint32_t cj = (uint32_t) __shfl((int) col[sj], (int) j, (int) W);
+#pragma unroll
+                for (uint32_t s = 0; s < ORDER_CPL; s++) rank[s] += (hj < hi[s] || (hj == hi[s] && cj < col[s])) ? 1u : 0u;
+            }
+        }
+    }
+    if (cnt == 0) return;
+    const uint32_t out0 = a.fin_off[p];
+    const int32_t row = (int32_t) a.task_rows[p];
+#pragma unroll
+    for (uint32_t s = 0; s < ORDER_CPL; s++) {
+        if (s * W + sl < cnt) {
+            const uint32_t o = out0 + rank[s];
+            float v_score, v_perc, v_tr;
+            cell_values(a, me[s], v_score, v_perc, v_tr);
+            a.c_score[o] = v_score; a.c_perc[o] = v_perc; a.c_tr[o] = v_tr;
+            a.c_row[o] = row;
+            a.c_col[o] = (int32_t) col[s];
+        }
+    }
+}
+// The first `short_blocks` workgroups: four waves of 64 / W rows each.  A row of up to W x ORDER_CPL cells is ranked in its
+// segment; one of more, up to ORDER_WAVE_CELLS, by the whole wave afterwards (uniform: the count comes from a lane read).
+// WIDE: the workgroups behind them do k_order_rows' work in the same launch.  They find their rows themselves (a row count
+// above ORDER_WAVE_CELLS) and read nothing this launch writes; a set without such a row costs them one pass over the counts.
+template <uint32_t W, bool WIDE>
+__global__ __launch_bounds__(ORDER_THREADS) void k_order_rows_sub(OrderArgs a, uint32_t short_blocks) {
+    static_assert(W == 16 || W == 32, "segments of 16 or 32 lanes");
+    if (WIDE && blockIdx.x >= short_blocks) { order_wide_rows_dealt(a, blockIdx.x - short_blocks, gridDim.x - short_blocks); return; }
+    constexpr uint32_t R = PDL_WAVE / W, SEG_CELLS = W * ORDER_CPL;
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1);
+    const uint32_t p0 = (blockIdx.x * (ORDER_THREADS / PDL_WAVE) + threadIdx.x / PDL_WAVE) * R;       // the wave's first row
+    if (p0 >= a.n_rows) return;                          // (wave-uniform)
+    const uint32_t p = p0 + lane / W;
+    uint32_t own = 0, cnt = 0;
+    if (p < a.n_rows) { own = a.row_cnt[p]; cnt = own + (a.mirror_cnt ? a.mirror_cnt[p] : 0u); }
+    if (cnt > ORDER_WAVE_CELLS && (lane & (W - 1)) == 0) *a.wide_rows = 1;       // (plain store of the same value from whoever sees one)
+    const uint32_t fit = cnt <= SEG_CELLS ? cnt : 0u;
+    uint32_t max_cnt = fit;
+#pragma unroll
+    for (uint32_t d = W; d < PDL_WAVE; d <<= 1) max_cnt = max(max_cnt, (uint32_t) __shfl_xor((int) max_cnt, (int) d, PDL_WAVE));
+    if (max_cnt) order_rank_rows<W>(a, p, own, fit, lane & (W - 1), max_cnt);
+#pragma unroll
+    for (uint32_t s = 0; s < R; s++) {
+        const uint32_t cs = (uint32_t) __builtin_amdgcn_readlane((int) cnt, (int) (s * W)), os = (uint32_t) __builtin_amdgcn_readlane((int) own, (int) (s * W));
+        if (cs > SEG_CELLS && cs <= ORDER_WAVE_CELLS) order_rank_rows<PDL_WAVE>(a, p0 + s, os, cs, lane, cs);
+    }
+}
+
 // mirror mode: hand every staged cell (r, c) to row c — as row c reads it: column r, perc and tr_perc swapped — by copying
 // it into c's stretch of mcell.  One wave per source row (coalesced reads of its staged cells); the slot inside c's
 // stretch is drawn with an atomic (the order inside a stretch is irrelevant: K-order ranks the cells by key).
@@ -1198,17 +1317,30 @@ struct MirrorArgs {
     uint32_t n_rows;
     MCell *mcell;
 };
-__global__ __launch_bounds__(256) void k_mirror_cells(MirrorArgs a) {
-    const uint32_t p = blockIdx.x * (256 / PDL_WAVE) + threadIdx.x / PDL_WAVE;
-    if (p >= a.n_rows) return;
+// source row p, by the W lanes of which this is lane `sl`
+template <uint32_t W>
+__device__ __forceinline__ void mirror_row(const MirrorArgs &a, uint32_t p, uint32_t sl) {
     const uint32_t base = a.row_base[p], cnt = a.row_cnt[p], r = a.task_rows[p];
-    for (uint32_t i = threadIdx.x & (PDL_WAVE - 1); i < cnt; i += PDL_WAVE) {
+    for (uint32_t i = sl; i < cnt; i += W) {
         const uint32_t s = base + i;
         const uint32_t pc = a.taskpos_of[a.st_col[s]];
         if (pc == 0xffffffffu) continue;                 // another GPU's row: the cell travels there (k_outbox)
         const uint32_t dst = a.mirror_off[pc] + atomicAdd(&a.mirror_cur[pc], 1u);
         a.mcell[dst] = MCell{r, a.st_first[s], a.st_score[s], a.st_tr[s], a.st_perc[s], 0u};
     }
+}
+__global__ __launch_bounds__(256) void k_mirror_cells(MirrorArgs a) {
+    const uint32_t p = blockIdx.x * (256 / PDL_WAVE) + threadIdx.x / PDL_WAVE;
+    if (p >= a.n_rows) return;
+    mirror_row<PDL_WAVE>(a, p, threadIdx.x & (PDL_WAVE - 1));
+}
+// option "order_subwave": W lanes per source row (a row stages two or three cells of its own on a set of short rows), 256 / W
+// rows per workgroup
+template <uint32_t W>
+__global__ __launch_bounds__(256) void k_mirror_cells_sub(MirrorArgs a) {
+    const uint32_t p = blockIdx.x * (256 / W) + threadIdx.x / W;
+    if (p >= a.n_rows) return;
+    mirror_row<W>(a, p, threadIdx.x & (W - 1));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1294,21 +1426,22 @@ __global__ __launch_bounds__(256) void k_mirror_cells_inbox(MirrorArgs a, const 
 
 // work-item descriptors of the LDS join, in processing order (currently task order)
 // ... and what the join wants to know about a gene when it meets it as a column, gathered into one 16-byte record
-__global__ __launch_bounds__(256) void k_row_desc(const uint32_t *__restrict__ task_rows, const uint32_t *__restrict__ seq_off,
-                                                  uint32_t n_rows, uint4 *__restrict__ desc,
-                                                  const uint32_t *__restrict__ kseq_len, const uint32_t *__restrict__ genome_of,
-                                                  const uint32_t *__restrict__ taskpos_of, const uint32_t *__restrict__ local_genome,
-                                                  uint32_t n_genes, uint4 *__restrict__ gene_info) {
-    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    if (p < n_genes) {
-        const uint32_t g = genome_of[p];
-        gene_info[p] = make_uint4(kseq_len[p], g, taskpos_of[p], local_genome[g]);
+struct RowDescArgs {
+    const uint32_t *task_rows, *seq_off, *kseq_len, *genome_of, *taskpos_of, *local_genome;
+    uint32_t n_rows, n_genes;
+    uint4 *desc, *gene_info;
+};
+__device__ __forceinline__ void row_desc_at(const RowDescArgs &d, uint32_t p) {
+    if (p < d.n_genes) {
+        const uint32_t g = d.genome_of[p];
+        d.gene_info[p] = make_uint4(d.kseq_len[p], g, d.taskpos_of[p], d.local_genome[g]);
     }
-    if (p >= n_rows) return;
-    const uint32_t r = task_rows[p];
-    const uint32_t e0 = seq_off[r];
-    desc[p] = make_uint4(p, r, e0, seq_off[r + 1] - e0);
+    if (p >= d.n_rows) return;
+    const uint32_t r = d.task_rows[p];
+    const uint32_t e0 = d.seq_off[r];
+    d.desc[p] = make_uint4(p, r, e0, d.seq_off[r + 1] - e0);
 }
+__global__ __launch_bounds__(256) void k_row_desc(RowDescArgs d) { row_desc_at(d, blockIdx.x * 256 + threadIdx.x); }
 
 struct RowCntFlag {
     const uint32_t *row_cnt; const uint32_t *mirror_cnt;     // cells of a row = its own + the mirrored ones
@@ -1438,11 +1571,18 @@ __global__ void k_gather_u32(const uint32_t *src, const uint32_t *idx, uint32_t 
 
 // Clears up to four arrays in one launch (16-byte words; every separate small fill is a dispatch of its own).
 struct ZeroRanges { uint4 *p[4]; unsigned long long n16[4]; };
-__global__ __launch_bounds__(256) void k_zero_ranges(ZeroRanges z) {
-    const unsigned long long stride = (unsigned long long) gridDim.x * 256;
+__device__ __forceinline__ void zero_ranges_by(const ZeroRanges &z, uint32_t block, uint32_t n_blocks) {
+    const unsigned long long stride = (unsigned long long) n_blocks * 256;
 #pragma unroll
     for (int r = 0; r < 4; r++)
-        for (unsigned long long i = (unsigned long long) blockIdx.x * 256 + threadIdx.x; i < z.n16[r]; i += stride) z.p[r][i] = make_uint4(0, 0, 0, 0);
+        for (unsigned long long i = (unsigned long long) block * 256 + threadIdx.x; i < z.n16[r]; i += stride) z.p[r][i] = make_uint4(0, 0, 0, 0);
+}
+__global__ __launch_bounds__(256) void k_zero_ranges(ZeroRanges z) { zero_ranges_by(z, blockIdx.x, gridDim.x); }
+// Option "fused_glue": what opens the first scoring pass over a task layout in ONE launch — the first `desc_blocks` workgroups
+// write the row and gene descriptors, the ones behind them clear.  Neither half reads or writes what the other touches.
+__global__ __launch_bounds__(256) void k_open_pass(RowDescArgs d, ZeroRanges z, uint32_t desc_blocks) {
+    if (blockIdx.x < desc_blocks) row_desc_at(d, blockIdx.x * 256 + threadIdx.x);
+    else zero_ranges_by(z, blockIdx.x - desc_blocks, gridDim.x - desc_blocks);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1674,6 +1814,12 @@ static void launch_tier(pdl_ctx *c, JoinArgs a, int kernel, uint32_t grid, const
 #endif
 }
 
+static RowDescArgs row_desc_args(pdl_ctx *c) {
+    return {c->task_rows.as<uint32_t>(), c->seq_off.as<uint32_t>(), c->kseq_len.as<uint32_t>(), c->d_gen, c->taskpos_of.as<uint32_t>(), c->local_genome.as<uint32_t>(),
+            c->n_task_rows, c->N, c->row_desc.as<uint4>(), c->gene_info.as<uint4>()};
+}
+static uint32_t row_desc_blocks(const pdl_ctx *c) { return (std::max(c->n_task_rows, c->N) + 255) / 256; }
+
 // buffers that depend on the row count only
 static void score_alloc_rows(pdl_ctx *c, const ScorePlan &pl) {
     const uint32_t N = c->N, G = c->G, n_rows = c->n_task_rows;
@@ -1687,9 +1833,8 @@ static void score_alloc_rows(pdl_ctx *c, const ScorePlan &pl) {
     c->overflow_rows.alloc((size_t) n_rows * 4 * JOIN_ROW_LISTS);
     if (pl.mirror) c->mirror_cnt.alloc((size_t) n_rows * 4 * 3 + 16);    // counts | offsets | cursors
     c->gene_info.alloc((size_t) N * sizeof(uint4));
-    hipLaunchKernelGGL(k_row_desc, dim3((std::max(n_rows, N) + 255) / 256), dim3(256), 0, c->stream, c->task_rows.as<uint32_t>(), c->seq_off.as<uint32_t>(),
-                       n_rows, c->row_desc.as<uint4>(), c->kseq_len.as<uint32_t>(), c->d_gen, c->taskpos_of.as<uint32_t>(), c->local_genome.as<uint32_t>(),
-                       N, c->gene_info.as<uint4>());
+    // the descriptors: with the clearing launch of the first pass (option "fused_glue"), or here
+    if (!c->opt_fused_glue) hipLaunchKernelGGL(k_row_desc, dim3(row_desc_blocks(c)), dim3(256), 0, c->stream, row_desc_args(c));
 }
 
 // staging for `cap` cells of this context's rows; final cells and mirrored copies also for `extra` cells received from other
@@ -1716,10 +1861,23 @@ template <class Args> static void set_staged_cells(Args &a, const StagedCells &s
     a.st_score = s.st_score; a.st_perc = s.st_perc; a.st_tr = s.st_tr; a.st_col = s.st_col; a.st_first = s.st_first;
 }
 
-// K-order's two kernels: rows of up to 256 cells inside one wave, then the rows that left for the workgroup kernel, if any
+// K-order's kernels: rows of up to 256 cells inside a wave or a segment of one, and the rows that are left for the workgroup
+// kernel, if any.  Option "order_subwave" (W lanes per short row; 1: ORDER_SUB_W) puts both into one launch unless
+// "order_wide_merged" is 0; "order_subwave" 0: a wave per short row, and k_order_rows behind it.
+template <uint32_t W>
+static void launch_order_sub(pdl_ctx *c, const OrderArgs &o, uint32_t wide_blocks) {
+    const uint32_t rows_per_block = ORDER_THREADS / W, short_blocks = (o.n_rows + rows_per_block - 1) / rows_per_block;
+    if (c->opt_order_wide_merged) { hipLaunchKernelGGL((k_order_rows_sub<W, true>), dim3(short_blocks + wide_blocks), dim3(ORDER_THREADS), 0, c->stream, o, short_blocks); return; }
+    hipLaunchKernelGGL((k_order_rows_sub<W, false>), dim3(short_blocks), dim3(ORDER_THREADS), 0, c->stream, o, short_blocks);
+    hipLaunchKernelGGL(k_order_rows, dim3(wide_blocks), dim3(ORDER_THREADS), 0, c->stream, o);
+}
 static void launch_order(pdl_ctx *c, const OrderArgs &o) {
+    const uint32_t wide_blocks = std::min<uint32_t>(o.n_rows, (uint32_t) pdl_cus(c) * 8);
+    const uint32_t w = order_sub_w(c);
+    if (w == 16) return launch_order_sub<16>(c, o, wide_blocks);
+    if (w == 32) return launch_order_sub<32>(c, o, wide_blocks);
     hipLaunchKernelGGL(k_order_rows_wave, dim3((o.n_rows + 3) / 4), dim3(256), 0, c->stream, o);
-    hipLaunchKernelGGL(k_order_rows, dim3(std::min<uint32_t>(o.n_rows, (uint32_t) pdl_cus(c) * 8)), dim3(ORDER_THREADS), 0, c->stream, o);
+    hipLaunchKernelGGL(k_order_rows, dim3(wide_blocks), dim3(ORDER_THREADS), 0, c->stream, o);
 }
 
 static JoinArgs join_args(pdl_ctx *c, const ScorePlan &pl) {
@@ -1743,8 +1901,9 @@ static JoinArgs join_args(pdl_ctx *c, const ScorePlan &pl) {
     return a;
 }
 
-// clears the maxima, the counters and the mirror bookkeeping, then queues the tiers
-static void score_join(pdl_ctx *c, const ScorePlan &pl) {
+// clears the maxima, the counters and the mirror bookkeeping (first_pass: the first pass since score_alloc_rows, whose
+// descriptors ride in that launch with option "fused_glue"), then queues the tiers
+static void score_join(pdl_ctx *c, const ScorePlan &pl, bool first_pass) {
     hipStream_t st = c->stream;
     const uint32_t N = c->N, G = c->G, n_rows = c->n_task_rows;
     const uint32_t S = (uint32_t) c->shard.size();
@@ -1756,7 +1915,11 @@ static void score_join(pdl_ctx *c, const ScorePlan &pl) {
         z.p[2] = c->join_ctr.as<uint4>(); z.n16[2] = n16(PDL_JC_WORDS * sizeof(uint32_t));
         z.p[3] = pl.mirror ? c->mirror_cnt.as<uint4>() : nullptr; z.n16[3] = pl.mirror ? n16((size_t) n_rows * 4 * 3) : 0;
         const unsigned long long most = std::max(z.n16[0], z.n16[1]);
-        hipLaunchKernelGGL(k_zero_ranges, dim3((uint32_t) std::min<unsigned long long>((most + 255) / 256 + 1, (unsigned long long) c->cus * 16)), dim3(256), 0, st, z);
+        const uint32_t zero_blocks = (uint32_t) std::min<unsigned long long>((most + 255) / 256 + 1, (unsigned long long) c->cus * 16);
+        if (first_pass && c->opt_fused_glue) {
+            const uint32_t desc_blocks = row_desc_blocks(c);
+            hipLaunchKernelGGL(k_open_pass, dim3(desc_blocks + zero_blocks), dim3(256), 0, st, row_desc_args(c), z, desc_blocks);
+        } else hipLaunchKernelGGL(k_zero_ranges, dim3(zero_blocks), dim3(256), 0, st, z);
     }
     const JoinArgs a = join_args(c, pl);
     const JoinLists L{c->join_ctr.as<uint32_t>(), c->overflow_rows.as<uint32_t>(), c->row_desc2.as<uint4>(), c->row_desc.as<uint4>(), n_rows, pl.wide ? 0 : n_rows};
@@ -1850,7 +2013,10 @@ static unsigned long long score_order(pdl_ctx *c, const ScorePlan &pl, const pdl
         set_staged_cells(ma, staged_cells(c));
         ma.taskpos_of = c->taskpos_of.as<uint32_t>(); ma.mirror_off = m_off; ma.mirror_cur = m_cur; ma.n_rows = n_rows;
         ma.mcell = c->mirror_ref.as<MCell>();
-        hipLaunchKernelGGL(k_mirror_cells, dim3((n_rows + 3) / 4), dim3(256), 0, st, ma);
+        const uint32_t w = order_sub_w(c);
+        if (w == 16) hipLaunchKernelGGL(k_mirror_cells_sub<16>, dim3((n_rows + 15) / 16), dim3(256), 0, st, ma);
+        else if (w == 32) hipLaunchKernelGGL(k_mirror_cells_sub<32>, dim3((n_rows + 7) / 8), dim3(256), 0, st, ma);
+        else hipLaunchKernelGGL(k_mirror_cells, dim3((n_rows + 3) / 4), dim3(256), 0, st, ma);
         if (n_inbox) hipLaunchKernelGGL(k_mirror_cells_inbox, dim3((n_inbox + 255) / 256), dim3(256), 0, st, ma, d_inbox, n_inbox, c->N);
         o.mirror_cnt = d_mcnt; o.mirror_off = m_off; o.mcell = c->mirror_ref.as<MCell>();
     }
@@ -1953,7 +2119,7 @@ void pdl_run_score_all(pdl_ctx *c) {
     unsigned long long cap = first_staging_cap(c, pl, c->P);
     for (int attempt = 0, overflows = 0;; attempt++) {
         score_alloc_cells(c, pl, cap, 0);
-        score_join(c, pl);
+        score_join(c, pl, attempt == 0);
         const unsigned long long z = score_order(c, pl, nullptr, 0, EV_SCORE_TOTAL);
         if (judge_pass(c, pl, z, cap, attempt, overflows) == PassVerdict::accept) break;
         ev_begin(c, EV_SCORE_TOTAL);
@@ -1992,7 +2158,7 @@ void pdl_run_dist_score_begin(pdl_ctx *c) {
     for (int attempt = 0, overflows = 0;; attempt++) {
         // room for as many received cells as staged ones right away (the exchange is symmetric on average); grown if short
         score_alloc_cells(c, pl, cap, cap);
-        score_join(c, pl);
+        score_join(c, pl, attempt == 0);
         OutboxArgs oa{};
         set_staged_cells(oa, staged_cells(c));
         oa.taskpos_of = c->taskpos_of.as<uint32_t>(); oa.genome_of = c->d_gen; oa.owner = c->owner_of_genome.as<uint32_t>();
