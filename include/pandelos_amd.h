@@ -674,6 +674,34 @@ PDL_API int pdl_copy_device(pdl_ctx *, void *d_dst, const void *d_src, uint64_t 
 PDL_API int pdl_pin_arrived(const uint32_t *pin, const uint32_t *dst_word, const uint32_t *words, uint32_t n, uint32_t flag_word, uint32_t epoch);
 PDL_API uint32_t pdl_pin_checksum(const uint32_t *payload, const uint32_t *dst_word, const uint32_t *words, uint32_t n);
 
+/* Test hooks of the generic device primitives (pandelos_amd/csrc/pdl_hooks.hip): each runs one primitive as the library calls
+ * it, on the caller's device buffers, on the context's stream, and waits for it.  The form taken follows the options
+ * onepass_scan and lean_radix.  For a context that holds no build: PDL_ERR_STATE on one that does (the scratch buffers the hooks
+ * grow are the build's); PDL_ERR_ARGUMENT for a NULL where a pointer is needed or a width that is not listed.
+ *
+ * pdl_test_scan: scan_and_apply over d_flags[0 .. min(*d_n, n_bound)) — d_prefix[i] = exclusive prefix, d_seen_flag[i] = the flag
+ * the apply step was handed; two_phase: an apply functor of the load/store form, which reads d_flags[i] again and sets bit 31 of
+ * d_seen_flag[i] where that differs.  *d_total (and *d_total2, which may be only 4-byte aligned) = the sum.  With onepass_scan
+ * the look-back error word is read and a set one fails the call with PDL_ERR_DEVICE.
+ * pdl_test_radix_offsets: pdl_radix_offsets over d_counts[256][n_tiles].  *out_lean = 1: d_offs holds each row's own exclusive
+ * prefix and d_digit_total[256] the rows' sums (*d_total is not written); 0: d_offs is the exclusive prefix over the whole
+ * table, *d_total its sum (d_digit_total is not written).
+ * pdl_test_sort_pairs: pdl_sort_pairs for (key_bytes, val_bytes) = (4, 4), (8, 4), (4, 8); begin_bit a multiple of 8.
+ * d_first_counts [256][tiles of 4096], on the device: filed at the head of the sort's scratch as the first pass's histogram.
+ * *out_result_in_b = 1 when the sorted pairs are in (d_keys_b, d_vals_b); *out_total = the control block's total of the last
+ * pass (all ones where no pass ran).
+ * pdl_test_merge: pdl_merge_streams for key_bytes 4 | 8: the stable merge of a and b on key & mask, a first on ties, b's
+ * values + b_val_add.  Sources need element alignment only, the outputs 16 bytes. */
+PDL_API int pdl_test_scan(pdl_ctx *, const uint32_t *d_flags, uint64_t n_bound, const uint64_t *d_n /* may be NULL */, uint32_t *d_prefix,
+                          uint32_t *d_seen_flag, int two_phase, uint64_t *d_total, uint64_t *d_total2 /* may be NULL */);
+PDL_API int pdl_test_radix_offsets(pdl_ctx *, const uint32_t *d_counts, uint32_t *d_offs, uint32_t n_tiles, uint64_t *d_total,
+                                   uint32_t *d_digit_total /* [256] */, int *out_lean);
+PDL_API int pdl_test_sort_pairs(pdl_ctx *, uint32_t key_bytes, uint32_t val_bytes, void *d_keys_a, void *d_keys_b, void *d_vals_a, void *d_vals_b,
+                                uint64_t n, uint32_t end_bit, int iota_values, const uint64_t *d_n /* may be NULL */, uint32_t begin_bit,
+                                int keys_below_end_bit, const uint32_t *d_first_counts /* may be NULL */, int *out_result_in_b, uint64_t *out_total);
+PDL_API int pdl_test_merge(pdl_ctx *, uint32_t key_bytes, const void *d_a_keys, const uint32_t *d_a_vals, uint32_t na, const void *d_b_keys,
+                           const uint32_t *d_b_vals, uint32_t nb, uint32_t b_val_add, uint64_t mask, void *d_out_keys, uint32_t *d_out_vals);
+
 /* Library/build identification, e.g. "pandelos_amd 0.2 (HIP, gfx950)" */
 PDL_API const char *pdl_version(void);
 

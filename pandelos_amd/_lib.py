@@ -170,7 +170,8 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
-           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges")
+           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
+           "pdl_test_scan", "pdl_test_radix_offsets", "pdl_test_sort_pairs", "pdl_test_merge")
 
 _lib = None
 
@@ -248,5 +249,10 @@ def load():
     lib.pdl_scan_faa.argtypes = [C.c_char_p, C.POINTER(PdlIngest), vp, u64, vp, vp, u32]; lib.pdl_scan_faa.restype = i32
     lib.pdl_pin_arrived.argtypes = [vp, vp, vp, u32, u32, u32]; lib.pdl_pin_arrived.restype = i32
     lib.pdl_pin_checksum.argtypes = [vp, vp, vp, u32]; lib.pdl_pin_checksum.restype = u32
+    lib.pdl_test_scan.argtypes = [vp, vp, u64, vp, vp, vp, i32, vp, vp]; lib.pdl_test_scan.restype = i32
+    lib.pdl_test_radix_offsets.argtypes = [vp, vp, vp, u32, vp, vp, C.POINTER(i32)]; lib.pdl_test_radix_offsets.restype = i32
+    lib.pdl_test_sort_pairs.argtypes = [vp, u32, u32, vp, vp, vp, vp, u64, u32, i32, vp, u32, i32, vp, C.POINTER(i32), C.POINTER(u64)]
+    lib.pdl_test_sort_pairs.restype = i32
+    lib.pdl_test_merge.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, u32, u64, vp, vp]; lib.pdl_test_merge.restype = i32
     _lib = lib
     return lib
