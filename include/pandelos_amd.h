@@ -413,6 +413,35 @@ PDL_API int pdl_families_of_edges(pdl_ctx *, const int32_t *src, const int32_t *
                                   const uint32_t *genome_of /* [n_sequences] */, uint32_t n_sequences, pdl_families *out);
 PDL_API void pdl_free_families(pdl_families *);
 
+/* ---- split: the first level of Girvan-Newman on a batch of ordered graphs, on the device -----------------------------------
+ * What netclu.girvan_newman_first_level does to a component that holds a collision (netclu_ng.py:97-111 through networkx): the
+ * edge of highest UNWEIGHTED shortest-path betweenness is removed, the betweenness of the whole graph is computed again, and so
+ * on until the removed edge's two ends are no longer connected (the component count has grown).  The orders that decide ties
+ * stay with the caller: graph j is the ordered adjacency g = rebuilt(rebuilt(view)), flattened — local node i is the i-th key of
+ * g, adj[adj_off[node] .. adj_off[node + 1]) its neighbours in dict order as LOCAL indices (node = node_off[j] + i; adj_off is
+ * one array over all graphs' nodes, from 0).  The answer is the removed edges in removal order, each as the edge list of the
+ * graph names it (u < v, local indices): removed_u / removed_v [removed_off[j] .. removed_off[j + 1]).  A graph without an edge
+ * gets no removal.  The sequence equals, exactly and in order, what the Python loop removes: all arithmetic in doubles, no fused
+ * multiply-add, every sum in the order Brandes' algorithm as networkx wrote it adds.
+ * PDL_ERR_ARGUMENT, before any index is used: NULL pointers, n_graphs == 0, offsets that do not start at 0 or decrease, a
+ * neighbour index outside its graph, a self loop, a neighbour named twice, an edge present in one direction only.
+ * PDL_ERR_UNSUPPORTED: 2^31 nodes or adjacency slots and more; a graph whose scratch does not fit option "split_scratch_bytes"
+ * (default 2^30; a batch is cut into chunks of graphs under it).  Needs no preprocess and changes nothing of the context: scores,
+ * edges, families and pdl_timings stay as they were.  Free with pdl_free_split. */
+typedef struct {
+    uint32_t graphs, chunks;  /* graphs of the call; launches it was cut into */
+    uint64_t nodes, edges;    /* over all graphs (an edge counts once) */
+    uint64_t removals;        /* removed_off[graphs] */
+    uint64_t rounds;          /* betweenness computations over all graphs (= removals: every round removes one edge) */
+    uint64_t *removed_off;    /* [graphs + 1] */
+    uint32_t *removed_u;      /* [removals] */
+    uint32_t *removed_v;      /* [removals] */
+    float device_ms;          /* the launches, between HIP event pairs; validation, uploads and the copies back are not in it */
+} pdl_split;
+PDL_API int pdl_split_first_level(pdl_ctx *, uint32_t n_graphs, const uint64_t *node_off /* [n_graphs + 1] */,
+                                  const uint64_t *adj_off /* [nodes + 1] */, const uint32_t *adj, pdl_split *out);
+PDL_API void pdl_free_split(pdl_split *);
+
 /* ---- place: a new genome's genes in the gene families already built, without a commit -------------------------------------
  * pdl_place_query: the base context holds N genes in G genomes; the query is n_query genes taken as genome G with ids
  * N..N+n_query-1 in union numbering, exactly as pdl_query_scores does.
@@ -542,7 +571,8 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * fields of pdl_timings; 0: only the totals and the join's launch time are taken — each event pair is two marker packets
  * between dispatches, a few microseconds of idle stream on a two-millisecond step), "low_memory" 0|1 (for genome batches on a large set: the buffers only the dictionary build needed are released after it —
  * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "query_batch_bytes" n > 0
- * (device bytes one chunk of pdl_query_batch / pdl_place_batch may take before its join, default 2^30), "onepass_scan" 0|1 (prefix scans
+ * (device bytes one chunk of pdl_query_batch / pdl_place_batch may take before its join, default 2^30), "split_scratch_bytes" n > 0 (device bytes of scratch one launch of
+ * pdl_split_first_level may take, default 2^30; it too leaves the context's scores in place), "onepass_scan" 0|1 (prefix scans
  * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "lean_radix" 0|1
  * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"

@@ -146,6 +146,12 @@ class PdlFamilies(C.Structure):
                 ("family_genes", C.POINTER(C.c_uint32)), ("collides", C.POINTER(C.c_uint8)), ("device_ms", C.c_float)]
 
 
+class PdlSplit(C.Structure):
+    _fields_ = [("graphs", C.c_uint32), ("chunks", C.c_uint32), ("nodes", C.c_uint64), ("edges", C.c_uint64), ("removals", C.c_uint64),
+                ("rounds", C.c_uint64), ("removed_off", C.POINTER(C.c_uint64)), ("removed_u", C.POINTER(C.c_uint32)),
+                ("removed_v", C.POINTER(C.c_uint32)), ("device_ms", C.c_float)]
+
+
 class PdlPlacement(C.Structure):
     _fields_ = [("sequences", C.c_uint32), ("n_query", C.c_uint32), ("genomes", C.c_uint32), ("edges", C.c_uint32),
                 ("edges_phase1", C.c_uint32), ("groups", C.c_uint32), ("novel", C.c_uint32), ("joined", C.c_uint32),
@@ -170,7 +176,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
-           "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
+           "pdl_split_first_level", "pdl_free_split", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
            "pdl_test_scan", "pdl_test_radix_offsets", "pdl_test_sort_pairs", "pdl_test_merge")
 
 _lib = None
@@ -233,6 +239,8 @@ def load():
     lib.pdl_compute_families.argtypes = [vp, C.POINTER(PdlFamilies)]; lib.pdl_compute_families.restype = i32
     lib.pdl_families_of_edges.argtypes = [vp, vp, vp, u64, vp, u32, C.POINTER(PdlFamilies)]; lib.pdl_families_of_edges.restype = i32
     lib.pdl_free_families.argtypes = [C.POINTER(PdlFamilies)]; lib.pdl_free_families.restype = None
+    lib.pdl_split_first_level.argtypes = [vp, u32, vp, vp, vp, C.POINTER(PdlSplit)]; lib.pdl_split_first_level.restype = i32
+    lib.pdl_free_split.argtypes = [C.POINTER(PdlSplit)]; lib.pdl_free_split.restype = None
     lib.pdl_place_query.argtypes = [vp, vp, vp, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo)]; lib.pdl_place_query.restype = i32
     lib.pdl_placement_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, u64, C.POINTER(PdlPlacement)]
     lib.pdl_placement_of_edges.restype = i32

@@ -625,6 +625,30 @@ int pdl_families_of_edges(pdl_ctx *c, const int32_t *src, const int32_t *dst, ui
     }, [&] { pdl_free_families(out); });
 }
 
+// ---- K-split (pdl_split.h) ---------------------------------------------------------------------------------------------------
+void pdl_free_split(pdl_split *s) {
+    if (!s) return;
+    free(s->removed_off); free(s->removed_u); free(s->removed_v);
+    memset(s, 0, sizeof(*s));
+}
+
+int pdl_split_first_level(pdl_ctx *c, uint32_t n_graphs, const uint64_t *node_off, const uint64_t *adj_off, const uint32_t *adj, pdl_split *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, Lock::held, [&]() -> int {
+        if (n_graphs == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_split_first_level: no graph");
+        if (!node_off || !adj_off) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_split_first_level: NULL pointer");
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_split_result r;
+        pdl_run_split(c, n_graphs, node_off, adj_off, adj, r);
+        out->graphs = r.graphs; out->chunks = r.chunks; out->nodes = r.nodes; out->edges = r.edges;
+        out->removals = r.removed_u.size(); out->rounds = r.rounds; out->device_ms = r.device_ms;
+        out->removed_off = dup_vec(r.removed_off); out->removed_u = dup_vec(r.removed_u); out->removed_v = dup_vec(r.removed_v);
+        return PDL_OK;
+    }, [&] { pdl_free_split(out); });
+}
+
 // ---- K-place (pdl_place.h) ---------------------------------------------------------------------------------------------------
 void pdl_free_placement(pdl_placement *p) {
     if (!p) return;
@@ -864,6 +888,11 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
         if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "query_batch_bytes: a positive byte count");
         c->opt_query_batch_bytes = (uint64_t) value;
         return PDL_OK;        // (no bearing on a scoring pass: the context's scores stay)
+    }
+    else if (n == "split_scratch_bytes") {
+        if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "split_scratch_bytes: a positive byte count");
+        c->opt_split_scratch_bytes = (uint64_t) value;
+        return PDL_OK;        // (nor has this one)
     }
     else if (n == "query_rekey") {
         if (value != 0 && value != 1) PDL_FAIL(PDL_ERR_ARGUMENT, "query_rekey: 0 or 1");

@@ -594,6 +594,12 @@ struct pdl_ctx {
         DevBuf ek_a, ek_b, ev_a, ev_b;              // a caller's edges: query-query (lo, hi) keys
         QSpans spans;                               // up to three stretches of device work
     } pb;
+    // K-split (pdl_split.h): the packed graphs of one chunk on the device, its workgroups' scratch, and the timer of the launches
+    struct SplitBufs {
+        DevBuf desc, adj_off, adj, eid, ends, slots, out_edge, out_count, scratch;
+        EventSpans<1> spans;
+    } sb;
+    uint64_t opt_split_scratch_bytes = 1ull << 30;  // pdl_split_first_level: scratch one launch may take
     EventSpans<2> set_spans;          // pdl_append_genomes, pdl_remove_genomes (they exclude each other): the call's two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
@@ -778,6 +784,15 @@ void pdl_run_bbh_all(pdl_ctx *c);
 void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *const dst[2], const uint64_t n_edges[2], bool mirrored0, bool check_ids,
                       bool dedupe_intra, const uint32_t *d_gen, uint32_t N, uint32_t genome_bits, pdl_fam_result &out);
 void pdl_run_families_of_context(pdl_ctx *c);       // ... over the context's own edges (K-bbh has run) -> c->fam
+// K-split (pdl_split.h, pdl_bbh.hip): the first level of Girvan-Newman on every graph of a packed batch; pdl_split without the C allocation
+struct pdl_split_result {
+    uint32_t graphs = 0, chunks = 0;
+    uint64_t nodes = 0, edges = 0, rounds = 0;
+    std::vector<uint64_t> removed_off;
+    std::vector<uint32_t> removed_u, removed_v;
+    float device_ms = 0.f;
+};
+void pdl_run_split(pdl_ctx *c, uint32_t n_graphs, const uint64_t *node_off, const uint64_t *adj_off, const uint32_t *adj, pdl_split_result &out);
 void pdl_ensure_costs(pdl_ctx *c);
 void pdl_input_arrived(pdl_ctx *c);      // deferred device input: waits for the genome ids / offset ends and checks them
 void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on the host

@@ -62,6 +62,18 @@ def read_net(net_path) -> Adj:
     return adj
 
 
+def read_net_edges(net_path) -> Tuple[List[int], List[int]]:
+    """The lines of a ``.net`` as edge lists in file order (the lines ``read_net`` reads, self edges included)."""
+    src, dst = [], []
+    with open(net_path, "r") as f:
+        for line in f:
+            cols = line.strip().split("\t")
+            if len(cols) >= 2 and cols[0]:
+                src.append(int(cols[0]))
+                dst.append(int(cols[1]))
+    return src, dst
+
+
 def view_filter(nodes: Iterable[int], member) -> set:
     """The node filter of ``G.subgraph(nodes)``: a NEW set filled in the iteration order of ``nodes`` (networkx:
     ``show_nodes(self.nbunch_iter(nodes))``).  Its own iteration order (CPython's, a function of the insertion sequence)
@@ -209,6 +221,88 @@ def split_until_clean(filt: set, root: Adj, genome_of: Sequence[str], root_len: 
     return out
 
 
+# ---- the same recursion level by level: every graph pending at one level goes to the splitter in ONE call (the device's:
+# PangeneNative.split_first_level, pdl_split_first_level) ---------------------------------------------------------------------
+
+def pack_graphs(graphs: Sequence[Adj]):
+    """Ordered adjacencies flattened for ``pdl_split_first_level``: -> (node_off [graphs + 1], adj_off [nodes + 1], adj [slots],
+    keys).  Local node i of graph j is the i-th key of its dict (``keys[j][i]`` is the gene); a node's neighbours follow in dict
+    order, as LOCAL indices."""
+    import numpy as np
+    node_off, adj_off, adj, keys = [0], [0], [], []
+    for g in graphs:
+        ks = list(g)
+        local = {u: i for i, u in enumerate(ks)}
+        for u in ks:
+            adj.extend(local[v] for v in g[u])
+            adj_off.append(len(adj))
+        node_off.append(node_off[-1] + len(ks))
+        keys.append(ks)
+    return np.asarray(node_off, np.uint64), np.asarray(adj_off, np.uint64), np.asarray(adj, np.uint32), keys
+
+
+def unpack_graphs(node_off, adj_off, adj, keys) -> List[Adj]:
+    """The adjacencies ``pack_graphs`` flattened, orders and all."""
+    out: List[Adj] = []
+    for j, ks in enumerate(keys):
+        a = int(node_off[j])
+        out.append({u: {ks[int(v)]: None for v in adj[int(adj_off[a + i]):int(adj_off[a + i + 1])]} for i, u in enumerate(ks)})
+    return out
+
+
+def first_level_removals(g: Adj) -> List[Tuple[int, int]]:
+    """The edges the loop of ``girvan_newman_first_level`` removes from ``g = rebuilt(rebuilt(view))``, in removal order, each
+    as ``edge_list`` names it.  ``g`` is left as it came."""
+    g = {u: dict(nbrs) for u, nbrs in g.items()}
+    removed: List[Tuple[int, int]] = []
+    if not any(g[u] for u in g):
+        return removed
+    start = len(connected_components(g))
+    while True:
+        u, v = most_central_edge(g)
+        del g[u][v]
+        del g[v][u]
+        removed.append((u, v))
+        if len(connected_components(g)) > start:
+            return removed
+
+
+def host_first_level(graphs: Sequence[Adj]) -> List[List[Tuple[int, int]]]:
+    """The host's splitter in the shape ``split_all_until_clean`` asks for: one list of removed edges per graph."""
+    return [first_level_removals(g) for g in graphs]
+
+
+def split_all_until_clean(filters: Sequence[set], root: Adj, genome_of: Sequence[str], root_len: Optional[int] = None,
+                          first_level=None) -> List[List[List[int]]]:
+    """``split_until_clean`` for every filter of ``filters``, the recursion done level by level: the graphs of all views pending
+    at one level go to ``first_level(graphs) -> removed edges per graph`` in one call (default: ``host_first_level``), the
+    removals are applied, and what ``connected_components`` then finds with a collision is the next level.  -> per filter its
+    parts, in the order ``split_until_clean`` lists them."""
+    first_level = host_first_level if first_level is None else first_level
+    done: List[List[Tuple[tuple, List[int]]]] = [[] for _ in filters]           # per filter: (path in the recursion, part)
+    pending = [(i, (), filt) for i, filt in enumerate(filters)]
+    while pending:
+        graphs = [rebuilt(rebuilt(view_adjacency(root, filt, root_len))) for _, _, filt in pending]
+        removals = first_level(graphs)
+        if len(removals) != len(graphs):
+            raise ValueError(f"the splitter answered {len(removals)} graphs of {len(graphs)}")
+        nxt = []
+        for (i, path, filt), g, rem in zip(pending, graphs, removals):
+            for u, v in rem:
+                del g[u][v]
+                del g[v][u]
+            comps = connected_components(g)
+            if len(comps) == 1 and len(g) > 1:
+                raise ValueError(f"the splitter left a graph of {len(g)} nodes in one piece")
+            for j, com in enumerate(sorted(c) for c in comps):
+                if max_collision(com, root, genome_of) > 0:
+                    nxt.append((i, path + (j,), view_filter(com, filt.__contains__)))
+                else:
+                    done[i].append((path + (j,), com))
+        pending = nxt
+    return [[part for _, part in sorted(parts, key=lambda p: p[0])] for parts in done]
+
+
 def families(names: Sequence[str], genome_of: Sequence[str], adj: Adj) -> Tuple[List[List[int]], List[int]]:
     """-> (families that come from network components, genes that are in no component)."""
     fams: List[List[int]] = []
@@ -225,14 +319,16 @@ def families(names: Sequence[str], genome_of: Sequence[str], adj: Adj) -> Tuple[
 
 
 def families_from_components(names: Sequence[str], genome_of: Sequence, fam: dict, src, dst,
-                             net_ordered: bool = False) -> Tuple[List[List[int]], List[int]]:
+                             net_ordered: bool = False, first_level=None) -> Tuple[List[List[int]], List[int]]:
     """``families`` from the components the device found (``pdl_families`` as ``PangeneNative.generate_families`` returns it:
     ``family_off``, ``family_genes``, ``collides``, ``is_node``, ``component_of``, ``nodes``) and the edges (``src``, ``dst``) in
     insertion order.  A clean component is a family as it comes.  The genes of the colliding components are split by
     ``split_until_clean`` on the sub-network of just those components: its adjacency is filled in ``.net`` line order
     (``pangenes.net_line_order``), so every component of it has the node and neighbour orders it has in the whole network,
     and the one place where the whole network's size shows (``view_adjacency``) is handed ``nodes``.  ``net_ordered``: the
-    edges ARE the lines of a ``.net``, in its order (a network read back from disk), so no order is derived."""
+    edges ARE the lines of a ``.net``, in its order (a network read back from disk), so no order is derived.  ``first_level``:
+    a splitter for ``split_all_until_clean`` (the device's: ``PangeneNative.split_first_level``) — all colliding components
+    then go through the recursion together, level by level; None keeps ``split_until_clean``."""
     import numpy as np
     from .pangenes import net_line_order
     off, genes = np.asarray(fam["family_off"]), np.asarray(fam["family_genes"])
@@ -253,8 +349,13 @@ def families_from_components(names: Sequence[str], genome_of: Sequence, fam: dic
                     sub[b] = {}
                 sub[a][b] = None
                 sub[b][a] = None
-        for comp in connected_components(sub):
-            fams += [sorted(part) for part in split_until_clean(view_filter(comp, sub.__contains__), sub, genome_of, int(fam["nodes"]))]
+        filters = [view_filter(comp, sub.__contains__) for comp in connected_components(sub)]
+        if first_level is None:
+            for filt in filters:
+                fams += [sorted(part) for part in split_until_clean(filt, sub, genome_of, int(fam["nodes"]))]
+        else:
+            for parts in split_all_until_clean(filters, sub, genome_of, int(fam["nodes"]), first_level):
+                fams += [sorted(part) for part in parts]
     return fams, np.nonzero(np.asarray(fam["is_node"]) == 0)[0].tolist()
 
 

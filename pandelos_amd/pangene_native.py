@@ -342,6 +342,36 @@ class PangeneNative:
             self._lib.pdl_free_families(C.byref(f))
         return out
 
+    def split_packed(self, node_off, adj_off, adj) -> list:
+        """``pdl_split_first_level`` on arrays as ``netclu.pack_graphs`` makes them -> per graph the removed edges, in removal
+        order, as (u, v) pairs of LOCAL indices.  ``last_split_info`` holds graphs, nodes, edges, removals, rounds, chunks and the
+        device time of the call."""
+        no = np.ascontiguousarray(node_off, dtype=np.uint64)
+        ao = np.ascontiguousarray(adj_off, dtype=np.uint64)
+        ad = np.ascontiguousarray(adj, dtype=np.uint32)
+        s = _lib.PdlSplit()
+        self._check(self._lib.pdl_split_first_level(self._ctx, max(len(no) - 1, 0), no.ctypes.data if no.size else None,
+                                                    ao.ctypes.data if ao.size else None, ad.ctypes.data if ad.size else None, C.byref(s)))
+        try:
+            off = _np_copy(s.removed_off, np.uint64, s.graphs + 1)
+            u, v = _np_copy(s.removed_u, np.uint32, s.removals).tolist(), _np_copy(s.removed_v, np.uint32, s.removals).tolist()
+            self.last_split_info = {"graphs": s.graphs, "nodes": s.nodes, "edges": s.edges, "removals": s.removals, "rounds": s.rounds,
+                                    "chunks": s.chunks, "device_ms": s.device_ms}
+        finally:
+            self._lib.pdl_free_split(C.byref(s))
+        return [list(zip(u[int(off[j]):int(off[j + 1])], v[int(off[j]):int(off[j + 1])])) for j in range(len(off) - 1)]
+
+    def split_first_level(self, graphs) -> list:
+        """The first level of Girvan-Newman on every graph of ``graphs`` (ordered adjacencies, ``g = rebuilt(rebuilt(view))`` of
+        ``netclu.girvan_newman_first_level``) in one call on the device -> per graph the removed edges in removal order, named by
+        their nodes as ``netclu.edge_list`` names them.  The splitter ``netclu.split_all_until_clean`` takes.  Needs no
+        preprocess and leaves the context's own state alone."""
+        from . import netclu
+        if not graphs:
+            return []
+        node_off, adj_off, adj, keys = netclu.pack_graphs(graphs)
+        return [[(ks[u], ks[v]) for u, v in rem] for ks, rem in zip(keys, self.split_packed(node_off, adj_off, adj))]
+
     def place_query(self, residues, offsets) -> dict:
         """One new genome placed into this context's gene families, without a commit (``pdl_place_query``): the query's edges
         (``src``, ``dst``, ``score`` in the host's insertion order, ``edges_phase1`` of them phase 1) and, per query gene and per
