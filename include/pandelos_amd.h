@@ -442,6 +442,61 @@ PDL_API int pdl_split_first_level(pdl_ctx *, uint32_t n_graphs, const uint64_t *
                                   const uint64_t *adj_off /* [nodes + 1] */, const uint32_t *adj, pdl_split *out);
 PDL_API void pdl_free_split(pdl_split *);
 
+/* ---- Pan-genome profile: the family table of a labelling, and pan / core accumulation curves over genome orders -------------
+ * What example/quality.py counts over a .clus, and the curve every pan-genome study draws behind it.  pdl_family_profile takes a
+ * caller's labelling: a family is the set of genes with equal family_of; any label in [0, n_sequences) is accepted, it need not
+ * be the smallest member, a gene in no family carries a label of its own.  The F families come in ascending label order; per
+ * family its label, size (genes) and spread (distinct genomes), and as a CSR the genomes it has a gene in (ascending inside a
+ * family) with the copies it has there: genomes / copies [genome_off[f] .. genome_off[f + 1]).  Over the set: size_hist[s] =
+ * families of s genes (s <= max_size), spread_hist[s] = families in s genomes (s <= G), spread_by_genome[s * G + g] = families
+ * of spread s that genome g takes part in; core (spread = G), single_copy_core (spread = G = size), unique (spread = 1),
+ * accessory (neither; with one genome a family is core and unique at once).  Per genome: its genes, and those of them in core,
+ * accessory and unique families.
+ * PDL_ERR_ARGUMENT: NULL pointers, n_sequences == 0, n_genomes == 0, a label >= n_sequences or a genome id >= n_genomes (counted
+ * on the device and read by the host before any id indexes anything; the message names the count).  PDL_ERR_UNSUPPORTED: 2^31
+ * genes and more, more than 8192 genomes (spread_by_genome has (G + 1) * G entries).  Any state of the context is accepted and
+ * nothing of it changes: scores, edges, families and pdl_timings stay as they were.  Free with pdl_free_profile. */
+typedef struct {
+    uint32_t n_sequences, n_genomes;  /* N, G of the call */
+    uint32_t families;                /* F */
+    uint32_t incidences;              /* genome_off[F]: (family, genome) pairs with a gene */
+    uint32_t max_size;
+    uint32_t core, single_copy_core, unique, accessory;
+    uint32_t *label, *size, *spread;  /* [F] */
+    uint32_t *genome_off;             /* [F + 1] */
+    uint32_t *genomes, *copies;       /* [incidences] */
+    uint32_t *size_hist;              /* [max_size + 1] */
+    uint32_t *spread_hist;            /* [G + 1] */
+    uint32_t *spread_by_genome;       /* [(G + 1) * G] */
+    uint32_t *genome_genes, *genome_core, *genome_accessory, *genome_unique;     /* [G] genes of the genome; ... in families of that class */
+    float device_ms;                  /* the launches, between HIP event pairs; uploads and the copies back are not in it */
+} pdl_profile;
+PDL_API int pdl_family_profile(pdl_ctx *, const uint32_t *family_of /* [n_sequences] */, const uint32_t *genome_of /* [n_sequences] */,
+                               uint32_t n_sequences, uint32_t n_genomes, pdl_profile *out);
+PDL_API void pdl_free_profile(pdl_profile *);
+
+/* pdl_pan_curves: for every one of n_orders genome orders (orders[o * G .. o * G + G), each a permutation of 0..G-1; G =
+ * profile->n_genomes) pan[o * G + i] = families with a gene in at least one of the genomes orders[o][0..i], core[o * G + i] =
+ * families with a gene in every one of them.  Exact integers: pan[o][G-1] = F, core[o][G-1] = profile->core, pan[o][0] =
+ * core[o][0].  Of the profile the call reads n_genomes, families, incidences, core, spread, genome_off and genomes.  The device
+ * takes no random numbers: the orders are the caller's.
+ * PDL_ERR_ARGUMENT: NULL pointers, n_orders == 0; a profile whose fields contradict each other (no family or genome, offsets
+ * that do not run from 0 to incidences, a row that is not spread[f] ascending genome ids below G, a core count that is not the
+ * number of rows of G genomes); an order that is no permutation (an id >= G or an id named twice: counted on the device before
+ * an order indexes anything, the message names the first failing order).  PDL_ERR_UNSUPPORTED: G above PDL_PAN_MAX_GENOMES (the
+ * order, its inverse and two histograms of G + 1 bins sit in one workgroup's LDS), 2^31 values per curve and more.  Any state of
+ * the context, nothing of it changes.  Free with pdl_free_curves. */
+#define PDL_PAN_MAX_GENOMES 4096
+typedef struct {
+    uint32_t n_genomes, n_orders, families;
+    uint32_t incidences;
+    uint32_t *pan, *core;             /* [n_orders * n_genomes] */
+    float device_ms;
+} pdl_curves;
+PDL_API int pdl_pan_curves(pdl_ctx *, const pdl_profile *profile, const uint32_t *orders /* [n_orders * G] */, uint32_t n_orders,
+                           pdl_curves *out);
+PDL_API void pdl_free_curves(pdl_curves *);
+
 /* ---- place: a new genome's genes in the gene families already built, without a commit -------------------------------------
  * pdl_place_query: the base context holds N genes in G genomes; the query is n_query genes taken as genome G with ids
  * N..N+n_query-1 in union numbering, exactly as pdl_query_scores does.

@@ -152,6 +152,26 @@ class PdlSplit(C.Structure):
                 ("removed_v", C.POINTER(C.c_uint32)), ("device_ms", C.c_float)]
 
 
+_pu32 = C.POINTER(C.c_uint32)
+
+
+class PdlProfile(C.Structure):
+    _fields_ = [("n_sequences", C.c_uint32), ("n_genomes", C.c_uint32), ("families", C.c_uint32), ("incidences", C.c_uint32),
+                ("max_size", C.c_uint32), ("core", C.c_uint32), ("single_copy_core", C.c_uint32), ("unique", C.c_uint32),
+                ("accessory", C.c_uint32), ("label", _pu32), ("size", _pu32), ("spread", _pu32), ("genome_off", _pu32),
+                ("genomes", _pu32), ("copies", _pu32), ("size_hist", _pu32), ("spread_hist", _pu32), ("spread_by_genome", _pu32),
+                ("genome_genes", _pu32), ("genome_core", _pu32), ("genome_accessory", _pu32), ("genome_unique", _pu32),
+                ("device_ms", C.c_float)]
+
+
+class PdlCurves(C.Structure):
+    _fields_ = [("n_genomes", C.c_uint32), ("n_orders", C.c_uint32), ("families", C.c_uint32), ("incidences", C.c_uint32),
+                ("pan", _pu32), ("core", _pu32), ("device_ms", C.c_float)]
+
+
+PDL_PAN_MAX_GENOMES = 4096
+
+
 class PdlPlacement(C.Structure):
     _fields_ = [("sequences", C.c_uint32), ("n_query", C.c_uint32), ("genomes", C.c_uint32), ("edges", C.c_uint32),
                 ("edges_phase1", C.c_uint32), ("groups", C.c_uint32), ("novel", C.c_uint32), ("joined", C.c_uint32),
@@ -176,7 +196,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
-           "pdl_split_first_level", "pdl_free_split", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
+           "pdl_split_first_level", "pdl_free_split", "pdl_family_profile", "pdl_free_profile", "pdl_pan_curves", "pdl_free_curves", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
            "pdl_test_scan", "pdl_test_radix_offsets", "pdl_test_sort_pairs", "pdl_test_merge")
 
 _lib = None
@@ -241,6 +261,10 @@ def load():
     lib.pdl_free_families.argtypes = [C.POINTER(PdlFamilies)]; lib.pdl_free_families.restype = None
     lib.pdl_split_first_level.argtypes = [vp, u32, vp, vp, vp, C.POINTER(PdlSplit)]; lib.pdl_split_first_level.restype = i32
     lib.pdl_free_split.argtypes = [C.POINTER(PdlSplit)]; lib.pdl_free_split.restype = None
+    lib.pdl_family_profile.argtypes = [vp, vp, vp, u32, u32, C.POINTER(PdlProfile)]; lib.pdl_family_profile.restype = i32
+    lib.pdl_free_profile.argtypes = [C.POINTER(PdlProfile)]; lib.pdl_free_profile.restype = None
+    lib.pdl_pan_curves.argtypes = [vp, C.POINTER(PdlProfile), vp, u32, C.POINTER(PdlCurves)]; lib.pdl_pan_curves.restype = i32
+    lib.pdl_free_curves.argtypes = [C.POINTER(PdlCurves)]; lib.pdl_free_curves.restype = None
     lib.pdl_place_query.argtypes = [vp, vp, vp, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo)]; lib.pdl_place_query.restype = i32
     lib.pdl_placement_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, u64, C.POINTER(PdlPlacement)]
     lib.pdl_placement_of_edges.restype = i32

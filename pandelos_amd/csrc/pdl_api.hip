@@ -649,6 +649,61 @@ int pdl_split_first_level(pdl_ctx *c, uint32_t n_graphs, const uint64_t *node_of
     }, [&] { pdl_free_split(out); });
 }
 
+// ---- Pan-genome profile (pdl_profile.h) -------------------------------------------------------------------------------------
+void pdl_free_profile(pdl_profile *p) {
+    if (!p) return;
+    free(p->label); free(p->size); free(p->spread); free(p->genome_off); free(p->genomes); free(p->copies);
+    free(p->size_hist); free(p->spread_hist); free(p->spread_by_genome);
+    free(p->genome_genes); free(p->genome_core); free(p->genome_accessory); free(p->genome_unique);
+    memset(p, 0, sizeof(*p));
+}
+
+int pdl_family_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *genome_of, uint32_t n_sequences, uint32_t n_genomes, pdl_profile *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, Lock::held, [&]() -> int {
+        if (!family_of || !genome_of) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_family_profile: NULL pointer");
+        if (n_sequences == 0 || n_genomes == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_family_profile: %u genes in %u genomes", n_sequences, n_genomes);
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_profile_result r;
+        pdl_run_profile(c, family_of, genome_of, n_sequences, n_genomes, r);
+        const size_t G = n_genomes;
+        const auto part = [&](size_t at, size_t n) { return std::vector<uint32_t>(r.hist.begin() + at, r.hist.begin() + at + n); };
+        out->n_sequences = r.n_sequences; out->n_genomes = r.n_genomes; out->families = r.families; out->incidences = r.incidences; out->max_size = r.max_size;
+        out->core = r.core; out->single_copy_core = r.single_copy_core; out->unique = r.unique; out->accessory = r.accessory; out->device_ms = r.device_ms;
+        out->label = dup_vec(r.label); out->size = dup_vec(r.size); out->spread = dup_vec(r.spread);
+        out->genome_off = dup_vec(r.genome_off); out->genomes = dup_vec(r.genomes); out->copies = dup_vec(r.copies);
+        out->size_hist = dup_vec(r.size_hist); out->spread_hist = dup_vec(part(0, G + 1)); out->spread_by_genome = dup_vec(part(G + 1, (G + 1) * G));
+        const size_t per_genome = (G + 1) + (G + 1) * G;
+        out->genome_genes = dup_vec(part(per_genome, G)); out->genome_core = dup_vec(part(per_genome + G, G));
+        out->genome_accessory = dup_vec(part(per_genome + 2 * G, G)); out->genome_unique = dup_vec(part(per_genome + 3 * G, G));
+        return PDL_OK;
+    }, [&] { pdl_free_profile(out); });
+}
+
+void pdl_free_curves(pdl_curves *p) {
+    if (!p) return;
+    free(p->pan); free(p->core);
+    memset(p, 0, sizeof(*p));
+}
+
+int pdl_pan_curves(pdl_ctx *c, const pdl_profile *profile, const uint32_t *orders, uint32_t n_orders, pdl_curves *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, Lock::held, [&]() -> int {
+        if (!profile || !orders) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: NULL pointer");
+        if (n_orders == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: no order");
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_curves_result r;
+        pdl_run_pan_curves(c, profile, orders, n_orders, r);
+        out->n_genomes = r.n_genomes; out->n_orders = r.n_orders; out->families = r.families; out->incidences = r.incidences; out->device_ms = r.device_ms;
+        out->pan = dup_vec(r.pan); out->core = dup_vec(r.core);
+        return PDL_OK;
+    }, [&] { pdl_free_curves(out); });
+}
+
 // ---- K-place (pdl_place.h) ---------------------------------------------------------------------------------------------------
 void pdl_free_placement(pdl_placement *p) {
     if (!p) return;

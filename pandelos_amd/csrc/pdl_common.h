@@ -600,6 +600,15 @@ struct pdl_ctx {
         EventSpans<1> spans;
     } sb;
     uint64_t opt_split_scratch_bytes = 1ull << 30;  // pdl_split_first_level: scratch one launch may take
+    // Pan-genome profile (pdl_profile.h): a caller's labelling and its sorted keys, the runs, the histograms; a caller's profile
+    // and orders, the presence bits, the orders' histograms and curves.  Work buffers of one call, grown as needed.
+    struct ProfileBufs {
+        DevBuf ctl;                                 // u64 [PDL_PF_WORDS]
+        DevBuf up_fam, up_gen, k_a, k_b, v_a, v_b;  // (label, genome) keys and the sort's values
+        DevBuf inc_start, inc_genome, inc_label, inc_of_pos, fam_start, label, genome_off, fam_of_label, size, spread, copies, size_hist, hist;
+        DevBuf up_orders, up_off, up_genomes, bits, order_hist, pan, core;
+        EventSpans<2> spans;                        // the check and the rest
+    } pf;
     EventSpans<2> set_spans;          // pdl_append_genomes, pdl_remove_genomes (they exclude each other): the call's two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
@@ -793,6 +802,20 @@ struct pdl_split_result {
     float device_ms = 0.f;
 };
 void pdl_run_split(pdl_ctx *c, uint32_t n_graphs, const uint64_t *node_off, const uint64_t *adj_off, const uint32_t *adj, pdl_split_result &out);
+// Pan-genome profile (pdl_profile.h, pdl_bbh.hip): pdl_profile and pdl_curves without the C allocation.  hist: spread_hist [G + 1] |
+// spread_by_genome [(G + 1) * G] | the genomes' genes [G] | ... in core, accessory, unique families [3][G]
+struct pdl_profile_result {
+    uint32_t n_sequences = 0, n_genomes = 0, families = 0, incidences = 0, max_size = 0, core = 0, single_copy_core = 0, unique = 0, accessory = 0;
+    std::vector<uint32_t> label, size, spread, genome_off, genomes, copies, size_hist, hist;
+    float device_ms = 0.f;
+};
+struct pdl_curves_result {
+    uint32_t n_genomes = 0, n_orders = 0, families = 0, incidences = 0;
+    std::vector<uint32_t> pan, core;
+    float device_ms = 0.f;
+};
+void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *genome_of, uint32_t N, uint32_t G, pdl_profile_result &out);
+void pdl_run_pan_curves(pdl_ctx *c, const pdl_profile *profile, const uint32_t *orders, uint32_t n_orders, pdl_curves_result &out);
 void pdl_ensure_costs(pdl_ctx *c);
 void pdl_input_arrived(pdl_ctx *c);      // deferred device input: waits for the genome ids / offset ends and checks them
 void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on the host

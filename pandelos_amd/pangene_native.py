@@ -372,6 +372,58 @@ class PangeneNative:
         node_off, adj_off, adj, keys = netclu.pack_graphs(graphs)
         return [[(ks[u], ks[v]) for u, v in rem] for ks, rem in zip(keys, self.split_packed(node_off, adj_off, adj))]
 
+    def family_profile(self, family_of, genome_of, n_genomes: int) -> dict:
+        """The pan-genome profile of a labelling (``pdl_family_profile``): a family is the set of genes with equal
+        ``family_of`` (any label below the gene count; a gene in no family carries a label of its own) -> the fields of
+        ``pdl_profile`` as a dict: counts as ints, arrays as numpy (``spread_by_genome`` as a (G + 1, G) table).  Needs no
+        preprocess and leaves the context's own state alone.  ``last_profile_info`` holds families, incidences and the device
+        time of the call."""
+        fam = np.ascontiguousarray(family_of, dtype=np.uint32)
+        gen = np.ascontiguousarray(genome_of, dtype=np.uint32)
+        if fam.shape != gen.shape or fam.ndim != 1:
+            raise ValueError("family_of and genome_of: one label and one genome id per gene")
+        p = _lib.PdlProfile()
+        self._check(self._lib.pdl_family_profile(self._ctx, fam.ctypes.data if fam.size else None, gen.ctypes.data if gen.size else None,
+                                                 len(fam), int(n_genomes), C.byref(p)))
+        try:
+            F, Z, G = p.families, p.incidences, p.n_genomes
+            out = {n: getattr(p, n) for n in ("n_sequences", "n_genomes", "families", "incidences", "max_size", "core", "single_copy_core",
+                                              "unique", "accessory")}
+            for name, count in (("label", F), ("size", F), ("spread", F), ("genome_off", F + 1), ("genomes", Z), ("copies", Z),
+                                ("size_hist", p.max_size + 1), ("spread_hist", G + 1), ("spread_by_genome", (G + 1) * G),
+                                ("genome_genes", G), ("genome_core", G), ("genome_accessory", G), ("genome_unique", G)):
+                out[name] = _np_copy(getattr(p, name), np.uint32, count)
+            out["spread_by_genome"] = out["spread_by_genome"].reshape(G + 1, G)
+            self.last_profile_info = {"families": F, "incidences": Z, "device_ms": p.device_ms}
+        finally:
+            self._lib.pdl_free_profile(C.byref(p))
+        return out
+
+    def pan_curves(self, profile: dict, orders) -> dict:
+        """Pan and core accumulation curves of a profile (``family_profile``'s dict) over genome orders (``pdl_pan_curves``):
+        ``orders`` is (n_orders, G), every row a permutation of 0..G-1 (``pangenome.random_orders`` makes them on the host) ->
+        {"pan", "core"}: (n_orders, G) exact counts, pan[o, i] = families with a gene in at least one of the first i + 1 genomes
+        of order o, core[o, i] = in every one of them.  ``last_curves_info`` holds families, incidences, orders and the device
+        time of the call."""
+        o = np.ascontiguousarray(orders, dtype=np.uint32)
+        G = int(profile["n_genomes"])
+        if o.ndim != 2 or o.shape[1] != G:
+            raise ValueError(f"orders: (n_orders, {G})")
+        keep = {n: np.ascontiguousarray(profile[n], dtype=np.uint32) for n in ("spread", "genome_off", "genomes")}
+        p = _lib.PdlProfile(n_genomes=G, families=int(profile["families"]), incidences=int(profile["incidences"]), core=int(profile["core"]))
+        for n, a in keep.items():
+            setattr(p, n, a.ctypes.data_as(_lib._pu32))
+        cv = _lib.PdlCurves()
+        self._check(self._lib.pdl_pan_curves(self._ctx, C.byref(p), o.ctypes.data if o.size else None, o.shape[0], C.byref(cv)))
+        try:
+            cells = cv.n_orders * cv.n_genomes
+            out = {"pan": _np_copy(cv.pan, np.uint32, cells).reshape(cv.n_orders, cv.n_genomes),
+                   "core": _np_copy(cv.core, np.uint32, cells).reshape(cv.n_orders, cv.n_genomes)}
+            self.last_curves_info = {"families": cv.families, "incidences": cv.incidences, "orders": cv.n_orders, "device_ms": cv.device_ms}
+        finally:
+            self._lib.pdl_free_curves(C.byref(cv))
+        return out
+
     def place_query(self, residues, offsets) -> dict:
         """One new genome placed into this context's gene families, without a commit (``pdl_place_query``): the query's edges
         (``src``, ``dst``, ``score`` in the host's insertion order, ``edges_phase1`` of them phase 1) and, per query gene and per
