@@ -103,7 +103,7 @@ void pdl_destroy(pdl_ctx *c) {
     if (c->own_stream && c->stream) (void) hipStreamDestroy(c->stream);
     if (c->pin) (void) hipHostFree(c->pin);
     if (c->mirror) (void) hipHostFree(c->mirror);
-    if (c->edge_mirror) (void) hipHostFree(c->edge_mirror);
+    c->edge_mirror.release();
     if (c->task_pin) (void) hipHostFree(c->task_pin);
     if (c->ev_tasks) (void) hipEventDestroy(c->ev_tasks);
     if (c->ev_entry) (void) hipEventDestroy(c->ev_entry);
@@ -543,7 +543,7 @@ int pdl_compute_edges(pdl_ctx *c, uint32_t genome, pdl_edges *out) {
     const uint32_t cnt = (uint32_t) ((b1 - a1) + (b2 - a2));
     out->count = cnt;
     out->src = xalloc<int32_t>(cnt); out->dst = xalloc<int32_t>(cnt); out->score = xalloc<float>(cnt);
-    const uint8_t *m = c->edge_mirror;
+    const uint8_t *m = c->edge_mirror.p;
     const size_t k1 = (size_t) (b1 - a1), k2 = (size_t) (b2 - a2);
     if (k1) {
         memcpy(out->src, m + a1 * 4, k1 * 4); memcpy(out->dst, m + n1 * 4 + a1 * 4, k1 * 4); memcpy(out->score, m + n1 * 8 + a1 * 4, k1 * 4);
@@ -565,14 +565,8 @@ void pdl_free_families(pdl_families *f) {
 
 static void fill_families(const pdl_fam_result &r, pdl_families *out) {
     out->sequences = r.sequences; out->nodes = r.nodes; out->families = r.families; out->colliding = r.colliding; out->device_ms = r.device_ms;
-    out->component_of = xalloc<uint32_t>(r.component_of.size()); out->is_node = xalloc<uint8_t>(r.is_node.size());
-    out->family_off = xalloc<uint32_t>(r.family_off.size()); out->family_genes = xalloc<uint32_t>(r.family_genes.size());
-    out->collides = xalloc<uint8_t>(r.collides.size());
-    if (!r.component_of.empty()) memcpy(out->component_of, r.component_of.data(), r.component_of.size() * 4);
-    if (!r.is_node.empty()) memcpy(out->is_node, r.is_node.data(), r.is_node.size());
-    memcpy(out->family_off, r.family_off.data(), r.family_off.size() * 4);
-    if (!r.family_genes.empty()) memcpy(out->family_genes, r.family_genes.data(), r.family_genes.size() * 4);
-    if (!r.collides.empty()) memcpy(out->collides, r.collides.data(), r.collides.size());
+    out->component_of = dup_vec(r.component_of); out->is_node = dup_vec(r.is_node); out->family_off = dup_vec(r.family_off);
+    out->family_genes = dup_vec(r.family_genes); out->collides = dup_vec(r.collides);
 }
 
 // the context's families, computed on first use: scored, then the edges, then the families (the device is the context's then)
@@ -712,14 +706,13 @@ void pdl_free_placement(pdl_placement *p) {
     memset(p, 0, sizeof(*p));
 }
 
-// (a batch's edges are the C arrays themselves: they change hands)
+// (a query's edges are the C arrays themselves: they change hands)
 static void fill_placement(pdl_place_result &r, bool with_edges, pdl_placement *out) {
     out->sequences = r.sequences; out->n_query = r.n_query; out->genomes = r.genomes;
-    out->edges = (uint32_t) (r.c_edges.set ? r.c_edges.n : r.src.size()); out->edges_phase1 = r.edges_phase1; out->groups = r.groups;
+    out->edges = (uint32_t) r.c_edges.n; out->edges_phase1 = r.edges_phase1; out->groups = r.groups;
     out->novel = r.novel; out->joined = r.joined; out->bridging = r.bridging; out->colliding = r.colliding; out->unplaced = r.unplaced;
     out->device_ms = r.device_ms;
-    if (with_edges && r.c_edges.set) { out->src = r.c_edges.src; out->dst = r.c_edges.dst; out->score = r.c_edges.score; r.c_edges.release(); }
-    else if (with_edges) { out->src = dup_vec(r.src); out->dst = dup_vec(r.dst); out->score = dup_vec(r.score); }
+    if (with_edges) { out->src = r.c_edges.src; out->dst = r.c_edges.dst; out->score = r.c_edges.score; r.c_edges.release(); }
     out->family_of = dup_vec(r.family_of); out->is_node = dup_vec(r.is_node); out->group_label = dup_vec(r.group_label);
     out->group_query_off = dup_vec(r.group_query_off); out->group_query = dup_vec(r.group_query);
     out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
@@ -755,7 +748,7 @@ int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets
     }, [&] { if (out) pdl_free_placement(out); if (info) memset(info, 0, sizeof(*info)); });
 }
 
-// A caller's base families behind their checks, on the device (c->pb.up_*) with n_edges edges of the caller's: what
+// A caller's base families behind their checks, on the device (c->pb.up through pdl_upload_base, the one upload of base families; up_gen, up_src, up_dst) with n_edges edges of the caller's: what
 // pdl_placement_of_edges and its batch form share.  The base is indexed by its own fields on the device: they must be what K-fam
 // writes (labels are smallest members, families in label order, members ascending, every node in exactly one family).
 static void check_base_pointers(const char *who, const pdl_families *base, const uint32_t *genome_of, const int32_t *src, const int32_t *dst, uint64_t n_edges) {
@@ -764,12 +757,9 @@ static void check_base_pointers(const char *who, const pdl_families *base, const
     if (N && (!genome_of || !base->component_of || !base->is_node)) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer", who);
     if (!base->family_off || (nodes && !base->family_genes) || (F && !base->collides)) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: NULL pointer in the base families", who);
 }
-// `of_label` is the caller's: the copy that reads it is waited for by the placement behind it.
-static PlaceBase upload_base(pdl_ctx *c, const char *who, const pdl_families *base, const uint32_t *genome_of, const int32_t *src, const int32_t *dst, uint64_t n_edges,
-                             std::vector<uint32_t> &of_label) {
+static PlaceBase upload_base(pdl_ctx *c, const char *who, const pdl_families *base, const uint32_t *genome_of, const int32_t *src, const int32_t *dst, uint64_t n_edges) {
     const uint32_t N = base->sequences, F = base->families, nodes = base->nodes;
     if (nodes > N || F > nodes || base->family_off[0] != 0 || base->family_off[F] != nodes) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (counts)", who);
-    of_label.assign(N, 0);
     std::vector<uint8_t> listed(N, 0);             // the gene is a member of exactly one family
     for (uint32_t f = 0; f < F; f++) {
         const uint32_t a = base->family_off[f], b = base->family_off[f + 1];
@@ -783,7 +773,6 @@ static PlaceBase upload_base(pdl_ctx *c, const char *who, const pdl_families *ba
                 PDL_FAIL(PDL_ERR_ARGUMENT, "%s: inconsistent base families (member %u of family %u)", who, j - a, f);
             listed[g] = 1;
         }
-        of_label[label] = f;
     }
     uint32_t g_max = 0;
     for (uint32_t i = 0; i < N; i++) {
@@ -796,27 +785,15 @@ static PlaceBase upload_base(pdl_ctx *c, const char *who, const pdl_families *ba
     PDL_HIP(hipSetDevice(c->device));
     pdl_ctx::PlaceBufs &b = c->pb;
     hipStream_t st = c->stream;
-    b.up_comp.alloc((size_t) N * 4); b.up_is_node.alloc(N); b.up_fam_of_label.alloc((size_t) N * 4); b.up_gen.alloc((size_t) N * 4);
-    b.up_fam_off.alloc(((size_t) F + 1) * 4); b.up_fam_genes.alloc((size_t) nodes * 4); b.up_collides.alloc(F);
-    if (N) {
-        PDL_HIP(hipMemcpyAsync(b.up_comp.p, base->component_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.up_is_node.p, base->is_node, N, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.up_fam_of_label.p, of_label.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
-    }
-    PDL_HIP(hipMemcpyAsync(b.up_fam_off.p, base->family_off, ((size_t) F + 1) * 4, hipMemcpyHostToDevice, st));
-    if (nodes) PDL_HIP(hipMemcpyAsync(b.up_fam_genes.p, base->family_genes, (size_t) nodes * 4, hipMemcpyHostToDevice, st));
-    if (F) PDL_HIP(hipMemcpyAsync(b.up_collides.p, base->collides, F, hipMemcpyHostToDevice, st));
+    b.up_gen.alloc((size_t) N * 4);
+    if (N) PDL_HIP(hipMemcpyAsync(b.up_gen.p, genome_of, (size_t) N * 4, hipMemcpyHostToDevice, st));
     if (n_edges) {
         b.up_src.alloc(n_edges * 4); b.up_dst.alloc(n_edges * 4);
         PDL_HIP(hipMemcpyAsync(b.up_src.p, src, n_edges * 4, hipMemcpyHostToDevice, st));
         PDL_HIP(hipMemcpyAsync(b.up_dst.p, dst, n_edges * 4, hipMemcpyHostToDevice, st));
     }
-    PlaceBase B;
-    B.comp = b.up_comp.as<uint32_t>(); B.is_node = b.up_is_node.as<uint8_t>(); B.collides = b.up_collides.as<uint8_t>();
-    B.fam_off = b.up_fam_off.as<uint32_t>(); B.fam_genes = b.up_fam_genes.as<uint32_t>(); B.fam_of_label = b.up_fam_of_label.as<uint32_t>();
-    B.genome_of = b.up_gen.as<uint32_t>(); B.N = N; B.G = N ? g_max + 1 : 0;
-    return B;
+    return pdl_upload_base(c, FamView{N, F, nodes, base->component_of, base->family_off, base->family_genes, base->is_node, base->collides}, b.up,
+                           b.up_gen.as<uint32_t>(), N ? g_max + 1 : 0);
 }
 
 int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t *genome_of, uint32_t n_query, const int32_t *src, const int32_t *dst,
@@ -828,8 +805,7 @@ int pdl_placement_of_edges(pdl_ctx *c, const pdl_families *base, const uint32_t 
         check_base_pointers("pdl_placement_of_edges", base, genome_of, src, dst, n_edges);
         if (n_query == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_placement_of_edges: no query gene");
         if (n_edges >= 0x7fffffffull || (uint64_t) base->sequences + n_query >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_placement_of_edges: 2^31 genes or edges and more");
-        std::vector<uint32_t> of_label;
-        const PlaceBase B = upload_base(c, "pdl_placement_of_edges", base, genome_of, src, dst, n_edges, of_label);
+        const PlaceBase B = upload_base(c, "pdl_placement_of_edges", base, genome_of, src, dst, n_edges);
         pdl_ctx::PlaceBufs &b = c->pb;
         pdl_place_result r;
         pdl_run_place_edges(c, B, n_query, b.up_src.as<int32_t>(), b.up_dst.as<int32_t>(), n_edges, r);
@@ -888,8 +864,7 @@ int pdl_placement_batch_of_edges(pdl_ctx *c, const pdl_families *base, const uin
         check_base_pointers(who, base, genome_of, src, dst, E);
         std::vector<uint64_t> rel((size_t) n_queries + 1);
         for (uint32_t q = 0; q <= n_queries; q++) rel[q] = edge_begin[q] - e0;
-        std::vector<uint32_t> of_label;
-        const PlaceBase B = upload_base(c, who, base, genome_of, src ? src + e0 : nullptr, dst ? dst + e0 : nullptr, E, of_label);
+        const PlaceBase B = upload_base(c, who, base, genome_of, src ? src + e0 : nullptr, dst ? dst + e0 : nullptr, E);
         std::vector<pdl_place_result> r;
         pdl_run_place_batch_edges(c, B, n_queries, n_query, rel.data(), c->pb.up_src.as<int32_t>(), c->pb.up_dst.as<int32_t>(), r);
         for (uint32_t q = 0; q < n_queries; q++) fill_placement(r[q], false, &out[q]);

@@ -12,6 +12,8 @@
 // All comparisons are on the float32 values as computed (bit-identical to the reference's, see pdl_join.hip).
 // Edges leave in the host's insertion order: per genome task, phase-1 edges cell by cell ((row, col) then (col, row)),
 // then the phase-2 edges.
+// The host side is one body for every owner of cells (the context's tasks, a query block, a chunk of queries), each over its own
+// BbhBufs: bbh_edges, bbh_read_counts, bbh_copy_out.
 #include "pdl_common.h"
 #include "pdl_scan.h"
 
@@ -69,15 +71,6 @@ __global__ __launch_bounds__(256) void k_bbh_intra(BbhArgs<L> a) {
     const float s = a.score[i];
     if (s == a.MS[(size_t) p * a.G + g] && s == a.MS[(size_t) pc * a.G + g] && s >= __uint_as_float(a.thr[p])) a.kind[i] = 2;
 }
-// mark, threshold, intra over Z cells (0 < Z < 2^31)
-template <class L>
-static void bbh_filter(hipStream_t st, const BbhArgs<L> &a) {
-    const uint32_t zb = (a.Z + 255) / 256;
-    hipLaunchKernelGGL(k_bbh_mark<L>, dim3(zb), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_bbh_threshold<L>, dim3(zb), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_bbh_intra<L>, dim3(zb), dim3(256), 0, st, a);
-    PDL_HIP(hipGetLastError());
-}
 
 struct KindFlag {
     const uint8_t *kind; uint8_t want;
@@ -101,79 +94,85 @@ __global__ void k_pick_prefixes(const uint32_t *pre1, const uint32_t *pre2, cons
     if (i < n && at[i] < z) { out[i] = pre1[at[i]]; out[n + i] = pre2[at[i]]; }
 }
 
+// From cells to edges: the filter (mark, threshold, intra) over the Z cells (0 < Z < 2^31) of `tasks` tasks with `rows` rows in all —
+// MS [rows][max_stride], a task's CM slice per cm_stride floats —, then the two kinds compacted in cell order into b's edge lists
+// (phase 1: two edges per cell), their totals of cells to d_tot[0] / [1].  block_at [nb + 1] (host, alive until the counts have
+// been read; nullptr: one block): the blocks' first cells go to the device — make_at(that copy) is the locator — and for more than
+// one block the cells of each kind before each are picked.  -> the two edge lists and the picks [2][nb + 1], on the device
+struct BbhEdges { int32_t *src[2], *dst[2]; float *sc[2]; uint32_t *pick; };
+template <class MakeAt, class L = std::invoke_result_t<MakeAt, const uint32_t *>>
+static BbhEdges bbh_edges(pdl_ctx *c, const float *score, const int32_t *row, const int32_t *col, const MakeAt &make_at, const float *MS, const float *CM,
+                          uint32_t cm_stride, uint32_t max_stride, uint32_t tasks, uint32_t rows, uint64_t Z, BbhBufs &b, uint64_t *d_tot,
+                          const uint32_t *block_at, uint32_t nb) {
+    hipStream_t st = c->stream;
+    const size_t n_max = (size_t) tasks * max_stride;
+    b.kind.alloc(Z + 16);
+    b.tab.alloc((n_max + rows + 2 * (Z + 1) + 3 * ((size_t) nb + 1)) * sizeof(uint32_t));
+    b.e_src.alloc(3 * Z * sizeof(int32_t)); b.e_dst.alloc(3 * Z * sizeof(int32_t)); b.e_score.alloc(3 * Z * sizeof(float));
+    uint32_t *inter_max = b.tab.as<uint32_t>(), *thr = inter_max + n_max, *pre1 = thr + rows, *pre2 = pre1 + (Z + 1), *d_at = pre2 + (Z + 1);
+    if (block_at) PDL_HIP(hipMemcpyAsync(d_at, block_at, ((size_t) nb + 1) * 4, hipMemcpyHostToDevice, st));
+    PDL_HIP(hipMemsetAsync(inter_max, 0, n_max * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_fill_u32, grid256(rows), dim3(256), 0, st, thr, rows, 0x7f800000u);
+    const BbhArgs<L> a{score, row, col, make_at((const uint32_t *) d_at), MS, CM, cm_stride, max_stride, (uint32_t) Z, inter_max, thr, b.kind.as<uint8_t>()};
+    hipLaunchKernelGGL(k_bbh_mark<L>, grid256(Z), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_bbh_threshold<L>, grid256(Z), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_bbh_intra<L>, grid256(Z), dim3(256), 0, st, a);
+    PDL_HIP(hipGetLastError());
+    int32_t *src = b.e_src.as<int32_t>(), *dst = b.e_dst.as<int32_t>(); float *sc = b.e_score.as<float>();
+    BbhEdges e{{src, src + 2 * Z}, {dst, dst + 2 * Z}, {sc, sc + 2 * Z}, nullptr};
+    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{score, row, col, e.src[0], e.dst[0], e.sc[0], pre1, 2}, d_tot);
+    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{score, row, col, e.src[1], e.dst[1], e.sc[1], pre2, 1}, d_tot + 1);
+    if (nb > 1) {           // the prefixes at every block's first cell (the totals close the lists)
+        e.pick = d_at + (nb + 1);
+        hipLaunchKernelGGL(k_pick_prefixes, grid256((uint64_t) nb + 1), dim3(256), 0, st, pre1, pre2, d_at, nb + 1, (uint32_t) Z, e.pick);
+        PDL_HIP(hipGetLastError());
+    }
+    return e;
+}
+// The counts of that run in one read, totals and picks -> every block's first phase-1 and first phase-2 edge (bbh_cut_blocks)
+static void bbh_read_counts(pdl_ctx *c, const char *who, const uint64_t *d_tot, const BbhEdges &e, const uint32_t *block_at, uint32_t nb, uint64_t Z, uint32_t block0,
+                            std::vector<uint64_t> &e1, std::vector<uint64_t> &e2) {
+    PinRead rd(c);
+    const uint64_t *pt = rd.add<uint64_t>(d_tot, 2);
+    const uint32_t *pp = e.pick ? rd.add<uint32_t>(e.pick, 2 * ((size_t) nb + 1)) : nullptr;
+    rd.sync();
+    bbh_cut_blocks(who, pt[0], pt[1], pp, block_at, nb, Z, block0, e1, e2);
+}
+// The n[0] + n[1] edges come down (queued): src, dst, score of phase 1 to h[0..2], of phase 2 to h[3..5] — which, given m, are
+// first laid out in that one pinned piece: src1 | dst1 | sc1 | src2 | dst2 | sc2
+static void bbh_copy_out(hipStream_t st, const BbhEdges &e, const uint64_t n[2], uint8_t *h[6], uint8_t *m = nullptr) {
+    const void *d[6] = {e.src[0], e.dst[0], e.sc[0], e.src[1], e.dst[1], e.sc[1]};
+    for (int i = 0; i < 6; i++) {
+        if (m) h[i] = m + (i < 3 ? i * n[0] : 3 * n[0] + (i - 3) * n[1]) * 4;
+        if (n[i / 3]) PDL_HIP(hipMemcpyAsync(h[i], d[i], n[i / 3] * 4, hipMemcpyDeviceToHost, st));
+    }
+}
+
 // Runs the filter for every genome task of the context; leaves the edges on the host (pinned), per genome
 // [phase-1 edges | phase-2 edges].
 void pdl_run_bbh_all(pdl_ctx *c) {
     hipStream_t st = c->stream;
-    const uint32_t S = (uint32_t) c->shard.size(), n_rows = c->n_task_rows, G = c->G;
+    const uint32_t S = (uint32_t) c->shard.size(), n_rows = c->n_task_rows;
     const uint64_t Z = c->h_cell_off.empty() ? 0 : c->h_cell_off.back();
-    c->h_edge_off.assign((size_t) S + 1, 0);
-    c->h_edge1.assign((size_t) S + 1, 0);
+    c->h_edge1.assign((size_t) S + 1, 0); c->h_edge_off.assign((size_t) S + 1, 0);
     c->edges_valid = true;
     c->fam_valid = false;              // (K-fam's answer was for the edges before these)
     if (Z == 0 || n_rows == 0) { c->n_edges = 0; return; }
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells on one device");
-    c->bbh_kind.alloc(Z + 16);
-    c->bbh_tab.alloc(((size_t) S * G + n_rows + 2 * (Z + 1) + 3 * ((size_t) S + 1)) * sizeof(uint32_t));
-    uint32_t *inter_max = c->bbh_tab.as<uint32_t>(), *thr = inter_max + (size_t) S * G, *pre1 = thr + n_rows, *pre2 = pre1 + (Z + 1);
-    uint32_t *d_at = pre2 + (Z + 1), *d_pick = d_at + (S + 1);
-    PDL_HIP(hipMemsetAsync(inter_max, 0, (size_t) S * G * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_fill_u32, dim3((n_rows + 255) / 256), dim3(256), 0, st, thr, n_rows, 0x7f800000u);
-    BbhArgs<BbhTasks> a{};
-    a.score = c->c_score.as<float>(); a.row = c->c_row.as<int32_t>(); a.col = c->c_col.as<int32_t>();
-    a.at = BbhTasks{c->taskpos_of.as<uint32_t>(), c->task_lg.as<uint32_t>(), c->d_gen};
-    a.MS = c->MS.as<float>(); a.CM = c->CM.as<float>(); a.N = c->N; a.G = G; a.Z = (uint32_t) Z;
-    a.inter_max = inter_max; a.thr = thr; a.kind = c->bbh_kind.as<uint8_t>();
-    bbh_filter(st, a);
-    // compaction: phase-1 cells (two edges each) and phase-2 cells (one each), both in cell order
-    c->e_src.alloc((2 * Z + Z) * sizeof(int32_t)); c->e_dst.alloc((2 * Z + Z) * sizeof(int32_t)); c->e_score.alloc((2 * Z + Z) * sizeof(float));
-    int32_t *src1 = c->e_src.as<int32_t>(), *dst1 = c->e_dst.as<int32_t>(); float *sc1 = c->e_score.as<float>();
-    int32_t *src2 = src1 + 2 * Z, *dst2 = dst1 + 2 * Z; float *sc2 = sc1 + 2 * Z;
-    uint64_t *d_scal = c->scalars.as<uint64_t>();
-    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, src1, dst1, sc1, pre1, 2}, d_scal + PDL_CTL_EDGES_1);
-    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, src2, dst2, sc2, pre2, 1}, d_scal + PDL_CTL_EDGES_2);
-    // cells of each kind before every genome block: prefix at the block's first cell (the totals close the lists)
-    uint64_t tot[2];
-    std::vector<uint32_t> h1(S + 1), h2(S + 1);
-    c->h_bbh_at.resize(S + 1);
-    for (uint32_t i = 0; i <= S; i++) c->h_bbh_at[i] = (uint32_t) c->h_cell_off[i];
-    PDL_HIP(hipMemcpyAsync(d_at, c->h_bbh_at.data(), ((size_t) S + 1) * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pick_prefixes, dim3((S + 1 + 255) / 256), dim3(256), 0, st, pre1, pre2, d_at, S + 1, (uint32_t) Z, d_pick);
-    {
-        PinRead rd(c);
-        const uint64_t *pt = rd.add<uint64_t>(d_scal + PDL_CTL_EDGES_1, PDL_CTL_EDGES_2 - PDL_CTL_EDGES_1 + 1);
-        const uint32_t *pp = rd.add<uint32_t>(d_pick, 2 * ((size_t) S + 1));
-        rd.sync();
-        tot[0] = pt[0]; tot[1] = pt[PDL_CTL_EDGES_2 - PDL_CTL_EDGES_1];
-        for (uint32_t i = 0; i <= S; i++) {
-            const bool past = c->h_cell_off[i] >= Z;
-            h1[i] = past ? (uint32_t) tot[0] : pp[i];
-            h2[i] = past ? (uint32_t) tot[1] : pp[S + 1 + i];
-        }
-    }
-    const uint64_t n1 = 2 * tot[0], n2 = tot[1];
-    c->n_edges = n1 + n2;
-    const size_t need = (size_t) (n1 + n2) * 12 + 64;
-    if (c->edge_mirror_bytes < need) {
-        if (c->edge_mirror) (void) hipHostFree(c->edge_mirror);
-        c->edge_mirror = nullptr; c->edge_mirror_bytes = 0;
-        PDL_HIP(hipHostMalloc((void **) &c->edge_mirror, need + need / 4, hipHostMallocDefault));
-        c->edge_mirror_bytes = need + need / 4;
-    }
-    uint8_t *m = c->edge_mirror;      // layout: src1 | dst1 | sc1 | src2 | dst2 | sc2
-    if (n1) {
-        PDL_HIP(hipMemcpyAsync(m, src1, n1 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(m + n1 * 4, dst1, n1 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(m + n1 * 8, sc1, n1 * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (n2) {
-        PDL_HIP(hipMemcpyAsync(m + n1 * 12, src2, n2 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(m + n1 * 12 + n2 * 4, dst2, n2 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(m + n1 * 12 + n2 * 8, sc2, n2 * 4, hipMemcpyDeviceToHost, st));
-    }
+    const std::vector<uint32_t> at(c->h_cell_off.begin(), c->h_cell_off.end());       // [S + 1] every genome block's first cell
+    uint64_t *d_tot = c->scalars.as<uint64_t>() + PDL_CTL_EDGES_1;
+    const BbhEdges e = bbh_edges(c, c->c_score.as<float>(), c->c_row.as<int32_t>(), c->c_col.as<int32_t>(),
+                                 [&](const uint32_t *) { return BbhTasks{c->taskpos_of.as<uint32_t>(), c->task_lg.as<uint32_t>(), c->d_gen}; },
+                                 c->MS.as<float>(), c->CM.as<float>(), c->N, c->G, S, n_rows, Z, c->bbh, d_tot, at.data(), S);
+    std::vector<uint64_t> e1, e2;                      // phase-1 edge offsets, phase-2 edge offsets
+    bbh_read_counts(c, "K-bbh", d_tot, e, at.data(), S, Z, 0, e1, e2);
+    const uint64_t n[2] = {e1[S], e2[S]};
+    uint8_t *h[6];
+    c->n_edges = n[0] + n[1];
+    c->edge_mirror.alloc((size_t) c->n_edges * 12 + 64);
+    bbh_copy_out(st, e, n, h, c->edge_mirror.p);
     PDL_HIP(hipStreamSynchronize(st));
-    c->n_edges1 = n1;
-    for (uint32_t i = 0; i <= S; i++) { c->h_edge1[i] = 2ull * h1[i]; c->h_edge_off[i] = h2[i]; }      // phase-1 edge offsets, phase-2 edge offsets
+    c->n_edges1 = n[0]; c->h_edge1.swap(e1); c->h_edge_off.swap(e2);
 }
 
 #include "pdl_families.h"        // K-fam: components, families and collision flags from these edges (pdl_compute_families)
@@ -183,7 +182,7 @@ void pdl_run_bbh_all(pdl_ctx *c) {
 void pdl_run_families_of_context(pdl_ctx *c) {
     const uint64_t Z = c->h_cell_off.empty() ? 0 : c->h_cell_off.back();
     const uint64_t n1 = c->n_edges ? c->n_edges1 : 0, n2 = c->n_edges - n1;          // (a context without a cell has no edge list at all)
-    const int32_t *src[2] = {c->e_src.as<int32_t>(), c->e_src.as<int32_t>() + 2 * Z}, *dst[2] = {c->e_dst.as<int32_t>(), c->e_dst.as<int32_t>() + 2 * Z};
+    const int32_t *src[2] = {c->bbh.e_src.as<int32_t>(), c->bbh.e_src.as<int32_t>() + 2 * Z}, *dst[2] = {c->bbh.e_dst.as<int32_t>(), c->bbh.e_dst.as<int32_t>() + 2 * Z};
     const uint64_t n[2] = {n1, n2};
     pdl_run_families(c, src, dst, n, true, false, false, c->d_gen, c->N, bit_length64(c->G ? c->G - 1 : 0), c->fam);
     c->fam_valid = true;

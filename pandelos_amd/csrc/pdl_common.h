@@ -131,6 +131,9 @@ enum : size_t {
     PDL_PB_WORDS = 4,
 };
 
+static_assert(PDL_CTL_EDGES_2 == PDL_CTL_EDGES_1 + 1 && PDL_PL_EDGES_2 == PDL_PL_EDGES_1 + 1 && PDL_PB_EDGES_2 == PDL_PB_EDGES_1 + 1,
+              "K-bbh's two totals are neighbours: one pointer names them (bbh_edges, bbh_read_counts)");
+
 // ---- layout of pdl_ctx::join_ctr (u32 words): cursors and counters of one scoring pass, cleared by score_join ---------------
 // A tier draws rows through its cursor and lists the rows it hands on; the count of that list is the next tier's work size.
 enum : uint32_t {
@@ -216,6 +219,59 @@ struct DevBuf {
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
 };
+
+// ---- pinned host buffer: grows only, with a quarter of headroom (a need that creeps up does not allocate every time); contents
+// undefined.  A DMA target: no staging by the runtime and no page of a fresh vector to touch.
+struct PinBuf {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    void alloc(size_t n) {
+        if (n <= bytes) return;
+        release();
+        PDL_HIP(hipHostMalloc((void **) &p, n + n / 4, hipHostMallocDefault));
+        bytes = n + n / 4;
+    }
+    void release() {
+        if (p) (void) hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    ~PinBuf() { release(); }
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+};
+
+// workgroups of 256 threads over n items
+inline dim3 grid256(uint64_t n) { return dim3((uint32_t) ((n + 255) / 256)); }
+
+// v = the `count` values at d, once the stream gets there: sizes the vector and queues the copy
+template <class T> inline void copy_down(hipStream_t st, std::vector<T> &v, const void *d, size_t count) {
+    v.resize(count);
+    if (count) PDL_HIP(hipMemcpyAsync(v.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, st));
+}
+
+// K-bbh's buffers (pdl_bbh.hip), one set per owner — the context's for its genome tasks, K-place's for a query block or a chunk:
+// kind u8 [Z] | tab: inter_max, thr, the two prefix lists [Z + 1] and the blocks' first cells with their picked prefixes |
+// e_*: the edges, phase 1 from 0 (room for 2 Z), phase 2 from 2 Z (room for Z).  The context's e_src / e_dst are read by K-fam long
+// after a placement has run over its own set.
+struct BbhBufs { DevBuf kind, tab, e_src, e_dst, e_score; };
+
+// K-bbh's counts as one read brings them — t1 / t2: the cells of the two kinds; picks [2][nb + 1] (nullptr: one block): the cells
+// of each kind before every block's first cell at[i], of Z — to every block's first phase-1 edge (two per cell) and first phase-2
+// edge, e1 / e2 [nb + 1]; a block that starts at Z takes the totals.  PDL_ERR_DEVICE for counts that cannot be: totals above Z,
+// offsets that decrease or pass the totals (block0: the caller's index of block 0, for the message).
+inline void bbh_cut_blocks(const char *who, uint64_t t1, uint64_t t2, const uint32_t *picks, const uint32_t *at, uint32_t nb, uint64_t Z, uint32_t block0,
+                           std::vector<uint64_t> &e1, std::vector<uint64_t> &e2) {
+    if (t1 > Z || t2 > Z) PDL_FAIL(PDL_ERR_DEVICE, "%s: %llu + %llu edge cells of %llu cells", who, (unsigned long long) t1, (unsigned long long) t2, (unsigned long long) Z);
+    e1.assign((size_t) nb + 1, 0); e2.assign((size_t) nb + 1, 0);
+    for (uint32_t i = 0; i <= nb; i++) {
+        const bool past = !picks ? i == nb : at[i] >= Z;
+        e1[i] = 2 * (past ? t1 : picks ? (uint64_t) picks[i] : 0); e2[i] = past ? t2 : picks ? (uint64_t) picks[nb + 1 + i] : 0;
+    }
+    for (uint32_t i = 0; i < nb; i++)
+        if (e1[i + 1] < e1[i] || e2[i + 1] < e2[i] || e1[i + 1] > 2 * t1 || e2[i + 1] > t2) PDL_FAIL(PDL_ERR_DEVICE, "%s: inconsistent edge offsets at block %u", who, block0 + i);
+}
 
 // a typed window into someone else's device allocation
 struct DevView {
@@ -303,24 +359,23 @@ struct pdl_fam_result {
 struct pdl_place_result {
     uint32_t sequences = 0, n_query = 0, genomes = 0, edges_phase1 = 0, groups = 0;
     uint32_t novel = 0, joined = 0, bridging = 0, colliding = 0, unplaced = 0;
-    std::vector<int32_t> src, dst;
-    std::vector<float> score;
     std::vector<uint32_t> family_of, group_label, group_query_off, group_query, group_base_off, group_base;
     std::vector<uint8_t> is_node, group_collides;
     float device_ms = 0.f;
-    // A batch hands a query's edges over as the C arrays themselves (malloc, `n` entries each; pdl_api.hip's fill_placement takes
-    // them), cut out of the chunk's pinned staging in one pass: src / dst / score above stay empty then.
+    // A query's edges are the C arrays the caller gets (malloc, `n` entries each, phase 1 then phase 2; pdl_api.hip's fill_placement
+    // takes them): a single query's come down into them, a batch's are cut out of the chunk's pinned staging in one pass.  A
+    // caller's list leaves them empty.
     struct CEdges {
-        int32_t *src = nullptr, *dst = nullptr; float *score = nullptr; uint64_t n = 0; bool set = false;
+        int32_t *src = nullptr, *dst = nullptr; float *score = nullptr; uint64_t n = 0;
         CEdges() = default;
         CEdges(const CEdges &) = delete;
         CEdges &operator=(const CEdges &) = delete;
         CEdges(CEdges &&o) noexcept { *this = std::move(o); }
         CEdges &operator=(CEdges &&o) noexcept {
-            if (this != &o) { drop(); src = o.src; dst = o.dst; score = o.score; n = o.n; set = o.set; o.release(); }
+            if (this != &o) { drop(); src = o.src; dst = o.dst; score = o.score; n = o.n; o.release(); }
             return *this;
         }
-        void release() { src = dst = nullptr; score = nullptr; n = 0; set = false; }      // (the arrays have a new owner)
+        void release() { src = dst = nullptr; score = nullptr; n = 0; }      // (the arrays have a new owner)
         void drop() { free(src); free(dst); free(score); release(); }
         ~CEdges() { drop(); }
     } c_edges;
@@ -331,6 +386,29 @@ struct PlaceBase {
     const uint8_t *is_node = nullptr, *collides = nullptr;
     uint32_t N = 0, G = 0;      // G: the query's genome id (every base genome id is below it)
 };
+// ... where they lie on the device, with the family of every label as the host derived it (kept alive for the asynchronous copy)
+struct BaseBufs {
+    DevBuf comp, is_node, collides, fam_off, fam_genes, fam_of_label;
+    std::vector<uint32_t> of_label;
+    PlaceBase view(uint32_t N, const uint32_t *genome_of, uint32_t G) const {
+        PlaceBase B;
+        B.comp = comp.as<uint32_t>(); B.is_node = is_node.as<uint8_t>(); B.collides = collides.as<uint8_t>();
+        B.fam_off = fam_off.as<uint32_t>(); B.fam_genes = fam_genes.as<uint32_t>(); B.fam_of_label = fam_of_label.as<uint32_t>();
+        B.genome_of = genome_of; B.N = N; B.G = G;
+        return B;
+    }
+};
+// ... and as the host holds them: a pdl_fam_result's vectors or a caller's pdl_families
+struct FamView {
+    uint32_t N, families, nodes;
+    const uint32_t *component_of, *family_off, *family_genes;
+    const uint8_t *is_node, *collides;
+};
+// of_label[label] = the family whose smallest member (its first) the label is; 0 for every other gene
+inline void fam_of_label(const FamView &f, std::vector<uint32_t> &of_label) {
+    of_label.assign(f.N, 0);
+    for (uint32_t i = 0; i < f.families; i++) of_label[f.family_genes[f.family_off[i]]] = i;
+}
 // what the device half of a single query (pdl_query.h, pdl_run_query_device) leaves: Z cells in c->qb.cells (five arrays of `cap`),
 // the maxima in c->qb.MS / c->qb.CM, the stretches of device work in c->qb.spans
 struct pdl_query_run {
@@ -482,11 +560,9 @@ struct pdl_ctx {
 
     // K-bbh (pdl_bbh.hip): network edges of every genome task, on the host after the first pdl_compute_edges
     bool edges_valid = false;
-    DevBuf bbh_kind, bbh_tab, e_src, e_dst, e_score;
-    uint8_t *edge_mirror = nullptr;           // pinned: src1 | dst1 | score1 (phase 1) | src2 | dst2 | score2 (phase 2)
-    size_t edge_mirror_bytes = 0;
+    BbhBufs bbh;
+    PinBuf edge_mirror;                       // src1 | dst1 | score1 (phase 1) | src2 | dst2 | score2 (phase 2)
     uint64_t n_edges = 0, n_edges1 = 0;
-    std::vector<uint32_t> h_bbh_at;
     std::vector<uint64_t> h_edge1, h_edge_off;   // [shard+1] first phase-1 / phase-2 edge of every genome task
 
     // tuning / test switches (pdl_set_option)
@@ -559,8 +635,7 @@ struct pdl_ctx {
         DevBuf res, off, koff, kseq, gene_begin, res_begin, gene_query, keys_a, keys_b, vals_a, vals_b, recpos, post, qkey, perm, srank, spost,
                seg_off, folds, desc, gkey, rec_sorted, row_lookups, row_off, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells;
         QSpans spans;                                // up to three stretches of device work per chunk
-        uint8_t *stage = nullptr; size_t stage_bytes = 0;     // pinned host staging of a chunk's cells and maxima (the blocks are cut out of it)
-        ~QueryBatchBufs() { if (stage) (void) hipHostFree(stage); }
+        PinBuf stage;                                // host staging of a chunk's cells and maxima, or of its edges (the blocks are cut out of it)
     } qbb;
     uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
     bool opt_query_rekey = false;                   // queries and placements accept letters the base lacks (pdl_query.h, Q-rebase)
@@ -581,13 +656,14 @@ struct pdl_ctx {
     // K-place (pdl_place.h): the context's own families on the device (uploaded once per K-fam run: fb's buffers are work buffers that
     // pdl_families_of_edges overwrites), a caller's base, and the work buffers of one placement
     struct PlaceBufs {
-        DevBuf base_comp, base_is_node, base_collides, base_fam_off, base_fam_genes, base_fam_of_label;     // the context's own
+        BaseBufs base;                              // the context's own
         uint64_t base_serial = 0;                   // c->fam_serial the copy was made at (0: none)
-        DevBuf up_comp, up_is_node, up_collides, up_fam_off, up_fam_genes, up_fam_of_label, up_gen, up_src, up_dst;   // a caller's base and edges
+        BaseBufs up;                                // a caller's base ...
+        DevBuf up_gen, up_src, up_dst;              // ... its genome ids and the caller's edges
         DevBuf ctl;                                 // u64 [PDL_PL_WORDS]
-        DevBuf bctl, btab, blay, up_edge_begin, up_n_query;   // a batch: u64 [PDL_PB_WORDS]; cell offsets and picked prefixes; the queries' layout; the callers' lists'
+        DevBuf bctl, blay, up_edge_begin, up_n_query;   // a batch: u64 [PDL_PB_WORDS]; the queries' layout; the callers' lists'
         QSpans bspans;                              // ... and the stretch of device work of a chunk's K-bbh
-        DevBuf kind, tab, e_src, e_dst, e_score;    // K-bbh over the query block: as bbh_kind, bbh_tab, e_* of the context
+        BbhBufs bbh;                                // K-bbh over the query block or the chunk: K-place's own set, never the context's
         DevBuf parent, is_node, same_deg, family_of, gcol, grp_of_label, gq_off, gb_off, group_base, mpre;
         DevBuf mk_a, mk_b, mv_a, mv_b;              // (root, query gene) sort
         DevBuf bk_a, bk_b, bv_a, bv_b, uniq;        // (group, base component) keys; then (group, genome) keys of the bridged members
@@ -776,6 +852,23 @@ struct PinRead {
     }
     ~PinRead() { for (auto &e : spill) free(e.first); }
 };
+// A counted gate: what a checking kernel left at d_word comes to the host in a read of its own; the caller words the refusal.
+// With `spans`: the stretch of device work it has open ends in front of the read and the next one opens behind it.
+inline uint64_t pdl_gate(pdl_ctx *c, const uint64_t *d_word) {
+    PDL_HIP(hipGetLastError());
+    PinRead rd(c);
+    const uint64_t *w = rd.add<uint64_t>(d_word, 1);
+    rd.sync();
+    return *w;
+}
+template <class Spans> inline uint64_t pdl_gate(pdl_ctx *c, Spans &spans, const uint64_t *d_word) {
+    spans.end();
+    const uint64_t v = pdl_gate(c, d_word);
+    spans.begin();
+    return v;
+}
+// the control block of a context that has built nothing yet: the sort's word (and K-fam's) is all a call on it needs
+inline void pdl_ctl_ready(pdl_ctx *c) { if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t)); }
 
 // stage entry points (pdl_dict.hip / pdl_join.hip)
 void pdl_run_preprocess(pdl_ctx *c, int kvalue, bool only_complexity);
@@ -843,6 +936,8 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
 // K-place (pdl_place.h, pdl_bbh.hip): the query's edges (K-bbh over the query block) and their placement on the context's families;
 // the placement of a caller's edge list (device pointers, union ids) on a base
 void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_place_result &out, pdl_query_info *info);
+// a base's families (the context's own or a caller's, checked) on their way to the device, into `b` -> the device view
+PlaceBase pdl_upload_base(pdl_ctx *c, const FamView &f, BaseBufs &b, const uint32_t *d_genome_of, uint32_t G);
 void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, const int32_t *d_src, const int32_t *d_dst, uint64_t n_edges,
                          pdl_place_result &out);
 // K-query for a batch (pdl_query_batch.h): q genomes, each scored on its own; gene_begin [n_queries + 1] cuts the n genes

@@ -181,8 +181,6 @@ __global__ __launch_bounds__(256) void k_fam_count(const uint8_t *collides, uint
     if (threadIdx.x == 0 && s_cnt) atomicAdd(reinterpret_cast<unsigned long long *>(d_colliding), (unsigned long long) s_cnt);
 }
 
-static inline dim3 fam_grid(uint64_t n) { return dim3((uint32_t) ((n + 255) / 256)); }
-
 // One run of K-fam.  list[0] / list[1]: device edge lists (K-bbh's two phases, or a caller's list and nothing).  mirrored0: list 0
 // holds every pair in both directions.  check_ids / dedupe_intra: a caller's list — ids are checked first, and the intra-genome
 // edges (looked for in list 0) may repeat; otherwise they are list 1's, distinct.
@@ -199,7 +197,7 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     if (N >= 0x7fffffffu || n_edges[0] >= 0x7fffffffull || n_edges[1] >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "K-fam: 2^31 genes or edges and more");
     pdl_ctx::FamBufs &b = c->fb;
     b.spans.start(st);
-    if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t));      // (a context that has built nothing yet: the sort's and K-fam's words are all it needs)
+    pdl_ctl_ready(c);
     uint64_t *ctl = c->scalars.as<uint64_t>();
     const size_t n4 = (size_t) N * sizeof(uint32_t);
     b.parent.alloc(n4); b.comp.alloc(n4); b.same_deg.alloc(n4); b.is_node.alloc(N); b.collides.alloc(N);
@@ -209,23 +207,18 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     uint8_t *is_node = b.is_node.as<uint8_t>(), *collides = b.collides.as<uint8_t>();
 
     b.spans.begin();
-    hipLaunchKernelGGL(k_fam_init, fam_grid(std::max<uint32_t>(N, PDL_CTL_FAM_LAST + 1)), dim3(256), 0, st, parent, same_deg, is_node, collides, N, ctl);
+    hipLaunchKernelGGL(k_fam_init, grid256(std::max<uint32_t>(N, PDL_CTL_FAM_LAST + 1)), dim3(256), 0, st, parent, same_deg, is_node, collides, N, ctl);
     if (check_ids && n_edges[0]) {
-        hipLaunchKernelGGL(k_fam_check, fam_grid(n_edges[0]), dim3(256), 0, st, src[0], dst[0], (uint32_t) n_edges[0], N, ctl + PDL_CTL_FAM_BAD_IDS);
-        PDL_HIP(hipGetLastError());
-        b.spans.end();
-        PinRead rd(c);
-        const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_CTL_FAM_BAD_IDS, 1);
-        rd.sync();
-        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-fam: %llu edges name a gene id outside [0, %u)", (unsigned long long) *bad, N);
-        b.spans.begin();
+        hipLaunchKernelGGL(k_fam_check, grid256(n_edges[0]), dim3(256), 0, st, src[0], dst[0], (uint32_t) n_edges[0], N, ctl + PDL_CTL_FAM_BAD_IDS);
+        const uint64_t bad = pdl_gate(c, b.spans, ctl + PDL_CTL_FAM_BAD_IDS);
+        if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-fam: %llu edges name a gene id outside [0, %u)", (unsigned long long) bad, N);
     }
     // F-cc
     for (int l = 0; l < 2; l++)
-        if (n_edges[l]) hipLaunchKernelGGL(k_fam_union, fam_grid(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), parent, is_node);
+        if (n_edges[l]) hipLaunchKernelGGL(k_fam_union, grid256(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), parent, is_node);
     uint32_t *mk_in = b.mk_a.as<uint32_t>(), *mk_out = b.mk_b.as<uint32_t>(), *mv_in = b.mv_a.as<uint32_t>(), *mv_out = b.mv_b.as<uint32_t>();
     uint32_t *ck_in = b.ck_a.as<uint32_t>(), *ck_out = b.ck_b.as<uint32_t>(), *cv_in = b.cv_a.as<uint32_t>(), *cv_out = b.cv_b.as<uint32_t>();
-    hipLaunchKernelGGL(k_fam_flatten, fam_grid(N), dim3(256), 0, st, parent, is_node, d_gen, N, comp, mk_in, ck_in);
+    hipLaunchKernelGGL(k_fam_flatten, grid256(N), dim3(256), 0, st, parent, is_node, d_gen, N, comp, mk_in, ck_in);
     PDL_HIP(hipGetLastError());
     // F-degree
     if (dedupe_intra) {
@@ -238,10 +231,10 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
             scan_and_apply(c, E, FamIntraFlag{src[0], dst[0], d_gen}, FamIntraApply{src[0], dst[0], ek_in}, d_intra);
             uint64_t *k_in = reinterpret_cast<uint64_t *>(ek_in), *k_out = reinterpret_cast<uint64_t *>(ek_out);
             pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, ev_in, ev_out, E, 32 + bit_length64(N - 1), true, d_intra, 0, true);
-            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
+            hipLaunchKernelGGL(k_fam_intra_sorted, grid256(E), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
         }
     } else if (n_edges[1]) {
-        hipLaunchKernelGGL(k_fam_intra, fam_grid(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], d_gen, same_deg);
+        hipLaunchKernelGGL(k_fam_intra, grid256(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], d_gen, same_deg);
     }
     PDL_HIP(hipGetLastError());
     // F-members: (label, gene)
@@ -252,13 +245,13 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
                    ctl + PDL_CTL_FAM_FAMILIES);
     // F-collide: (label, genome) runs
     pdl_sort_pairs<uint32_t, uint32_t>(c, ck_in, ck_out, cv_in, cv_out, N, genome_bits, true, nullptr, 0, true);
-    hipLaunchKernelGGL(k_fam_gather_keys, fam_grid(N), dim3(256), 0, st, cv_out, comp, is_node, N, ck_in);        // (ck_in is free: the sorted genes are in cv_out)
+    hipLaunchKernelGGL(k_fam_gather_keys, grid256(N), dim3(256), 0, st, cv_out, comp, is_node, N, ck_in);        // (ck_in is free: the sorted genes are in cv_out)
     std::swap(cv_in, cv_out);                                                                                     // in: genes by genome; out: the free half (ck_out: the genome keys, done with)
     pdl_sort_pairs<uint32_t, uint32_t>(c, ck_in, ck_out, cv_in, cv_out, N, label_bits, false, nullptr, 0, true);
     uint32_t *run_off = b.run_off.as<uint32_t>(), *run_of = b.run_of.as<uint32_t>();
     scan_and_apply(c, N, FamHeadFlag{ck_out, cv_out, d_gen, N}, FamHeadApply{ck_out, d_gen, N, N, run_off, run_of, nullptr}, ctl + PDL_CTL_FAM_RUNS);
-    hipLaunchKernelGGL(k_fam_collide, fam_grid(N), dim3(256), 0, st, ck_out, cv_out, run_of, run_off, same_deg, fam_of_label, N, collides);
-    hipLaunchKernelGGL(k_fam_count, fam_grid(N), dim3(256), 0, st, collides, N, ctl + PDL_CTL_FAM_FAMILIES, ctl + PDL_CTL_FAM_COLLIDING);
+    hipLaunchKernelGGL(k_fam_collide, grid256(N), dim3(256), 0, st, ck_out, cv_out, run_of, run_off, same_deg, fam_of_label, N, collides);
+    hipLaunchKernelGGL(k_fam_count, grid256(N), dim3(256), 0, st, collides, N, ctl + PDL_CTL_FAM_FAMILIES, ctl + PDL_CTL_FAM_COLLIDING);
     PDL_HIP(hipGetLastError());
     b.spans.end();
     // F-out: the counts in one read, then the arrays
@@ -271,15 +264,8 @@ void pdl_run_families(pdl_ctx *c, const int32_t *const src[2], const int32_t *co
     }
     if (out.nodes > N || out.families > out.nodes || out.colliding > out.families)
         PDL_FAIL(PDL_ERR_DEVICE, "K-fam: inconsistent counts (%u nodes, %u families, %u colliding of %u genes)", out.nodes, out.families, out.colliding, N);
-    out.component_of.resize(N); out.is_node.resize(N);
-    out.family_off.assign((size_t) out.families + 1, 0); out.family_genes.resize(out.nodes); out.collides.resize(out.families);
-    PDL_HIP(hipMemcpyAsync(out.component_of.data(), comp, n4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.is_node.data(), is_node, N, hipMemcpyDeviceToHost, st));
-    if (out.families) {
-        PDL_HIP(hipMemcpyAsync(out.family_off.data(), fam_off, ((size_t) out.families + 1) * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.family_genes.data(), mv_out, (size_t) out.nodes * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.collides.data(), collides, out.families, hipMemcpyDeviceToHost, st));
-    }
+    copy_down(st, out.component_of, comp, N); copy_down(st, out.is_node, is_node, N);
+    if (out.families) { copy_down(st, out.family_off, fam_off, (size_t) out.families + 1); copy_down(st, out.family_genes, mv_out, out.nodes); copy_down(st, out.collides, collides, out.families); }
     PDL_HIP(hipStreamSynchronize(st));
     out.device_ms = b.spans.total_ms();
 }

@@ -40,7 +40,7 @@ int hook(pdl_ctx *c, const char *who, bool bad_argument, Body &&body) {
         if (c->preprocessed || c->dist_stage != DistStage::none)
             PDL_FAIL(PDL_ERR_STATE, "%s: the context holds a build, whose work buffers the hook would grow (use a context without one)", who);
         PDL_HIP(hipSetDevice(c->device));
-        if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t));
+        pdl_ctl_ready(c);
         body();
         PDL_HIP(hipStreamSynchronize(c->stream));
         return PDL_OK;

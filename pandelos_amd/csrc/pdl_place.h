@@ -10,9 +10,9 @@
 // flat(0, x) = x, gene x - N, constants to the compiler and nothing on the device.  PlaceChunk (pdl_place_batch.h) is a chunk
 // of a batch.
 //
-//   P-bbh      place_bbh: k_bbh_mark/_threshold/_intra (pdl_bbh.hip) with the caller's policy (BbhQueryBlock: row p = gene - N, one
-//              task, genome G for ids >= N); the two kinds compacted in cell order (KindFlag / EdgeApply): phase 1 ((row, col)
-//              then (col, row)), phase 2.  The reads of the totals and the copy-out of the edges are the caller's
+//   P-bbh      bbh_edges (pdl_bbh.hip): k_bbh_mark/_threshold/_intra with the caller's locator (BbhQueryBlock: row p = gene - N, one
+//              task, genome G for ids >= N) over K-place's own BbhBufs; the two kinds compacted in cell order (KindFlag /
+//              EdgeApply): phase 1 ((row, col) then (col, row)), phase 2.  bbh_read_counts brings the totals, bbh_copy_out the edges
 //   P-check    k_place_check    (a caller's list only, by its entry point) ids outside [0, N + n) and base-base edges counted; read
 //              BEFORE anything below
 //   P-cc       k_place_init: every query's copy of the base's component_of moved to its flat ids (the only O(N) step), its genes
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void k_place_clique(const uint32_t *key, const
 }
 
 static uint64_t *place_begin(pdl_ctx *c) {
-    if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t));      // (a context that has built nothing yet: the sort's word is all it needs)
+    pdl_ctl_ready(c);
     c->pb.ctl.alloc(PDL_PL_WORDS * sizeof(uint64_t));
     PDL_HIP(hipMemsetAsync(c->pb.ctl.p, 0, PDL_PL_WORDS * sizeof(uint64_t), c->stream));
     return c->pb.ctl.as<uint64_t>();
@@ -272,11 +272,11 @@ static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, co
     Lay::lists(c, Q, N, lay);
     const Lay &L = lay[0];
     // P-cc
-    hipLaunchKernelGGL(k_place_init<Lay>, fam_grid(F), dim3(256), 0, st, L, B.comp, F, NT, parent, same_deg, is_node, gcol);
+    hipLaunchKernelGGL(k_place_init<Lay>, grid256(F), dim3(256), 0, st, L, B.comp, F, NT, parent, same_deg, is_node, gcol);
     for (int l = 0; l < 2; l++)
-        if (n_edges[l]) hipLaunchKernelGGL(k_place_union<Lay>, fam_grid(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), lay[l], parent, is_node);
+        if (n_edges[l]) hipLaunchKernelGGL(k_place_union<Lay>, grid256(n_edges[l]), dim3(256), 0, st, src[l], dst[l], (uint32_t) n_edges[l], (uint32_t) (l == 0 && mirrored0), lay[l], parent, is_node);
     uint32_t *mk_in = b.mk_a.as<uint32_t>(), *mk_out = b.mk_b.as<uint32_t>(), *mv_in = b.mv_a.as<uint32_t>(), *mv_out = b.mv_b.as<uint32_t>();
-    hipLaunchKernelGGL(k_place_roots<Lay>, fam_grid(NT), dim3(256), 0, st, parent, (const uint8_t *) is_node, L, F, NT, family, mk_in);
+    hipLaunchKernelGGL(k_place_roots<Lay>, grid256(NT), dim3(256), 0, st, parent, (const uint8_t *) is_node, L, F, NT, family, mk_in);
     PDL_HIP(hipGetLastError());
     // P-degree
     const uint64_t E0 = n_edges[0];
@@ -289,10 +289,10 @@ static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, co
             scan_and_apply(c, E0, PlaceIntraFlag{src[0], dst[0], N}, PlaceIntraApply<Lay>{src[0], dst[0], L, ek_in}, d_intra);
             uint64_t *k_in = reinterpret_cast<uint64_t *>(ek_in), *k_out = b.ek_b.as<uint64_t>();
             pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, ev_in, ev_out, E0, 32 + bit_length64(NT - 1), true, d_intra, 0, true);
-            hipLaunchKernelGGL(k_fam_intra_sorted, fam_grid(E0), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
+            hipLaunchKernelGGL(k_fam_intra_sorted, grid256(E0), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), d_intra, same_deg, 0u);
         }
     } else if (n_edges[1]) {
-        hipLaunchKernelGGL(k_place_intra<Lay>, fam_grid(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], lay[1], same_deg);
+        hipLaunchKernelGGL(k_place_intra<Lay>, grid256(n_edges[1]), dim3(256), 0, st, src[1], dst[1], (uint32_t) n_edges[1], lay[1], same_deg);
     }
     PDL_HIP(hipGetLastError());
     // P-groups: (flat root, chunk gene), chunk genes ascending in
@@ -314,11 +314,11 @@ static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, co
         pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, v_in, v_out, E0, label_bits + group_bits, true, d_base, 0, true);
         const unsigned long long *sorted = reinterpret_cast<const unsigned long long *>(k_out);
         scan_and_apply(c, E0, PlaceUniqFlag{sorted}, PlaceUniqApply{sorted, uniq, group_base, gcol, B, label_bits}, d_pairs, nullptr, d_base);
-        hipLaunchKernelGGL(k_place_base_off, fam_grid((uint64_t) NT + 1), dim3(256), 0, st, uniq, d_pairs, ctl + PDL_PL_GROUPS, NT, label_bits, gb_off);
+        hipLaunchKernelGGL(k_place_base_off, grid256((uint64_t) NT + 1), dim3(256), 0, st, uniq, d_pairs, ctl + PDL_PL_GROUPS, NT, label_bits, gb_off);
         scan_and_apply(c, E0, PlaceMemberFlag{uniq, gb_off, B, label_bits}, PlaceMemberApply{mpre}, ctl + PDL_PL_MEMBERS, nullptr, d_pairs);
     }
     // P-clique
-    hipLaunchKernelGGL(k_place_clique, fam_grid(NT), dim3(256), 0, st, mk_out, mv_out, grp_of_label, gq_off, same_deg, ctl + PDL_PL_NODES, NT, gcol);
+    hipLaunchKernelGGL(k_place_clique, grid256(NT), dim3(256), 0, st, mk_out, mv_out, grp_of_label, gq_off, same_deg, ctl + PDL_PL_NODES, NT, gcol);
     PDL_HIP(hipGetLastError());
     spans.end();
     // P-out: the counts in one read ...
@@ -338,24 +338,21 @@ static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, co
         b.bk_a.alloc(members * 8); b.bk_b.alloc(members * 8); b.bv_a.alloc(members * 4); b.bv_b.alloc(members * 4);
         uint64_t *k_in = b.bk_a.as<uint64_t>(), *k_out = b.bk_b.as<uint64_t>();
         uint32_t *v_in = b.bv_a.as<uint32_t>(), *v_out = b.bv_b.as<uint32_t>();
-        hipLaunchKernelGGL(k_place_gather, fam_grid(members), dim3(256), 0, st, uniq, mpre, (uint32_t) pairs, (uint32_t) members, B, label_bits, genome_bits,
+        hipLaunchKernelGGL(k_place_gather, grid256(members), dim3(256), 0, st, uniq, mpre, (uint32_t) pairs, (uint32_t) members, B, label_bits, genome_bits,
                            reinterpret_cast<unsigned long long *>(k_in), v_in);
         pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, v_in, v_out, members, genome_bits + group_bits, false, nullptr, 0, true);
-        hipLaunchKernelGGL(k_place_bridge, fam_grid(members), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), v_out, (uint32_t) members, genome_bits, gcol);
+        hipLaunchKernelGGL(k_place_bridge, grid256(members), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(k_out), v_out, (uint32_t) members, genome_bits, gcol);
         PDL_HIP(hipGetLastError());
         spans.end();
     }
     // ... then the arrays, whole
     std::vector<uint32_t> h_family(NT), h_gq_off(groups + 1, 0), h_gb_off(groups + 1, 0), h_gene(nodes), h_base(pairs);
     std::vector<uint8_t> h_is_node(NT), h_gcol(groups);
-    PDL_HIP(hipMemcpyAsync(h_family.data(), family, n4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(h_is_node.data(), is_node, NT, hipMemcpyDeviceToHost, st));
+    copy_down(st, h_family, family, NT); copy_down(st, h_is_node, is_node, NT);
     if (groups) {
-        PDL_HIP(hipMemcpyAsync(h_gq_off.data(), gq_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(h_gene.data(), mv_out, nodes * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(h_gcol.data(), gcol, groups, hipMemcpyDeviceToHost, st));
-        if (E0) PDL_HIP(hipMemcpyAsync(h_gb_off.data(), gb_off, (groups + 1) * 4, hipMemcpyDeviceToHost, st));
-        if (pairs) PDL_HIP(hipMemcpyAsync(h_base.data(), group_base, pairs * 4, hipMemcpyDeviceToHost, st));
+        copy_down(st, h_gq_off, gq_off, groups + 1); copy_down(st, h_gene, mv_out, nodes); copy_down(st, h_gcol, gcol, groups);
+        if (E0) copy_down(st, h_gb_off, gb_off, groups + 1);
+        copy_down(st, h_base, group_base, pairs);
     }
     PDL_HIP(hipStreamSynchronize(st));
     if (groups && (h_gq_off[0] != 0 || h_gq_off[groups] != nodes || h_gb_off[groups] != pairs)) PDL_FAIL(PDL_ERR_DEVICE, "K-place: inconsistent group offsets");
@@ -405,6 +402,20 @@ static float place_run(pdl_ctx *c, const PlaceBase &B, const PlaceQueries &Q, co
     return spans.total_ms();
 }
 
+// A base network's families (host view f) on their way to the device, into `b`: the six arrays queued on the stream, of_label
+// derived on the host and kept in b while its copy is under way.  -> the device view, with the caller's genome ids (on the device)
+PlaceBase pdl_upload_base(pdl_ctx *c, const FamView &f, BaseBufs &b, const uint32_t *d_genome_of, uint32_t G) {
+    hipStream_t st = c->stream;
+    const size_t N = f.N, F = f.families, nodes = f.nodes;
+    fam_of_label(f, b.of_label);
+    b.comp.alloc(N * 4); b.is_node.alloc(N); b.fam_of_label.alloc(N * 4); b.fam_off.alloc((F + 1) * 4); b.fam_genes.alloc(nodes * 4); b.collides.alloc(F);
+    const struct { DevBuf &d; const void *h; size_t bytes; } up[6] = {{b.comp, f.component_of, N * 4}, {b.is_node, f.is_node, N}, {b.fam_of_label, b.of_label.data(), N * 4},
+                                                                      {b.fam_off, f.family_off, (F + 1) * 4}, {b.fam_genes, f.family_genes, nodes * 4}, {b.collides, f.collides, F}};
+    for (const auto &u : up)
+        if (u.bytes) PDL_HIP(hipMemcpyAsync(u.d.p, u.h, u.bytes, hipMemcpyHostToDevice, st));
+    return b.view(f.N, d_genome_of, G);
+}
+
 // the context's own families on the device: uploaded once per run of K-fam (c->fam is its answer on the host)
 static PlaceBase place_context_base(pdl_ctx *c) {
     pdl_ctx::PlaceBufs &b = c->pb;
@@ -412,58 +423,27 @@ static PlaceBase place_context_base(pdl_ctx *c) {
     const uint32_t N = c->N;
     if (f.sequences != N || f.component_of.size() != N) PDL_FAIL(PDL_ERR_STATE, "K-place: the context's families are not those of its %u genes", N);
     if (b.base_serial != c->fam_serial) {
-        hipStream_t st = c->stream;
         b.base_serial = 0;
-        std::vector<uint32_t> of_label(N, 0);
-        for (uint32_t i = 0; i < f.families; i++) of_label[f.family_genes[f.family_off[i]]] = i;
-        b.base_comp.alloc((size_t) N * 4); b.base_is_node.alloc(N); b.base_fam_of_label.alloc((size_t) N * 4);
-        b.base_fam_off.alloc(((size_t) f.families + 1) * 4); b.base_fam_genes.alloc((size_t) f.nodes * 4); b.base_collides.alloc(f.families);
-        PDL_HIP(hipMemcpyAsync(b.base_comp.p, f.component_of.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.base_is_node.p, f.is_node.data(), N, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.base_fam_of_label.p, of_label.data(), (size_t) N * 4, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipMemcpyAsync(b.base_fam_off.p, f.family_off.data(), ((size_t) f.families + 1) * 4, hipMemcpyHostToDevice, st));
-        if (f.nodes) PDL_HIP(hipMemcpyAsync(b.base_fam_genes.p, f.family_genes.data(), (size_t) f.nodes * 4, hipMemcpyHostToDevice, st));
-        if (f.families) PDL_HIP(hipMemcpyAsync(b.base_collides.p, f.collides.data(), f.families, hipMemcpyHostToDevice, st));
-        PDL_HIP(hipStreamSynchronize(st));
+        pdl_upload_base(c, FamView{N, f.families, f.nodes, f.component_of.data(), f.family_off.data(), f.family_genes.data(), f.is_node.data(), f.collides.data()}, b.base,
+                          c->d_gen, c->G);
+        PDL_HIP(hipStreamSynchronize(c->stream));      // (c->fam may change under a later call, before the stream is waited for)
         b.base_serial = c->fam_serial;
     }
-    PlaceBase B;
-    B.comp = b.base_comp.as<uint32_t>(); B.is_node = b.base_is_node.as<uint8_t>(); B.collides = b.base_collides.as<uint8_t>();
-    B.fam_off = b.base_fam_off.as<uint32_t>(); B.fam_genes = b.base_fam_genes.as<uint32_t>(); B.fam_of_label = b.base_fam_of_label.as<uint32_t>();
-    B.genome_of = c->d_gen; B.N = N; B.G = c->G;
-    return B;
+    return b.base.view(N, c->d_gen, c->G);
 }
 
-// P-bbh over the Z > 0 ordered cells of `tasks` query blocks with `genes` rows in all (w: the buffers K-query left them in, the
-// cells' arrays `cap` apart; `at`: where a cell finds its block; cm_n: what a block's CM slice starts at a multiple of): K-bbh's
-// filter, then the two kinds compacted in cell order (phase 1 leaves two edges per cell); the totals of cells go to d_n1 / d_n2.
-// -> the edges of the two phases and, per cell, the cells of each kind before it (pre [Z + 1]), on the device
-struct PlaceEdges { int32_t *src[2], *dst[2]; float *sc[2]; uint32_t *pre[2]; };
-template <class At, class W>
-static PlaceEdges place_bbh(pdl_ctx *c, W &w, uint64_t cap, const At &at, uint32_t cm_n, uint32_t tasks, uint32_t genes, uint64_t Z, uint64_t *d_n1, uint64_t *d_n2) {
-    hipStream_t st = c->stream;
-    pdl_ctx::PlaceBufs &b = c->pb;
-    const uint32_t G1 = c->G + 1;
-    b.kind.alloc(Z + 16);
-    b.tab.alloc(((size_t) tasks * G1 + genes + 2 * (Z + 1)) * sizeof(uint32_t));
-    uint32_t *inter_max = b.tab.as<uint32_t>(), *thr = inter_max + (size_t) tasks * G1;
-    PlaceEdges e{};
-    e.pre[0] = thr + genes; e.pre[1] = e.pre[0] + (Z + 1);
-    PDL_HIP(hipMemsetAsync(inter_max, 0, (size_t) tasks * G1 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_fill_u32, dim3((genes + 255) / 256), dim3(256), 0, st, thr, genes, 0x7f800000u);
-    const float *cf = w.cells.template as<float>();
-    BbhArgs<At> a{};
-    a.score = cf; a.row = reinterpret_cast<const int32_t *>(cf + 3 * cap); a.col = reinterpret_cast<const int32_t *>(cf + 4 * cap);
-    a.at = at;
-    a.MS = w.MS.template as<float>(); a.CM = w.CM.template as<float>(); a.N = cm_n; a.G = G1; a.Z = (uint32_t) Z;
-    a.inter_max = inter_max; a.thr = thr; a.kind = b.kind.as<uint8_t>();
-    bbh_filter(st, a);
-    b.e_src.alloc(3 * Z * sizeof(int32_t)); b.e_dst.alloc(3 * Z * sizeof(int32_t)); b.e_score.alloc(3 * Z * sizeof(float));
-    e.src[0] = b.e_src.as<int32_t>(); e.dst[0] = b.e_dst.as<int32_t>(); e.sc[0] = b.e_score.as<float>();
-    e.src[1] = e.src[0] + 2 * Z; e.dst[1] = e.dst[0] + 2 * Z; e.sc[1] = e.sc[0] + 2 * Z;
-    scan_and_apply(c, Z, KindFlag{a.kind, 1}, EdgeApply{a.score, a.row, a.col, e.src[0], e.dst[0], e.sc[0], e.pre[0], 2}, d_n1);
-    scan_and_apply(c, Z, KindFlag{a.kind, 2}, EdgeApply{a.score, a.row, a.col, e.src[1], e.dst[1], e.sc[1], e.pre[1], 1}, d_n2);
-    return e;
+// A query's edges as the C arrays the caller gets, in the host's insertion order: n[0] of phase 1, then n[1] of phase 2.
+// -> h: where src, dst, score of phase 1 (h[0..2]) and of phase 2 (h[3..5]) go
+static void place_c_edges(pdl_place_result &r, const uint64_t n[2], uint8_t *h[6]) {
+    pdl_place_result::CEdges &ce = r.c_edges;
+    ce.drop();
+    ce.n = n[0] + n[1];
+    const size_t bytes = std::max<size_t>(ce.n, 1) * 4;
+    ce.src = static_cast<int32_t *>(malloc(bytes)); ce.dst = static_cast<int32_t *>(malloc(bytes)); ce.score = static_cast<float *>(malloc(bytes));
+    if (!ce.src || !ce.dst || !ce.score) throw std::bad_alloc();
+    uint8_t *const arr[3] = {reinterpret_cast<uint8_t *>(ce.src), reinterpret_cast<uint8_t *>(ce.dst), reinterpret_cast<uint8_t *>(ce.score)};
+    for (int i = 0; i < 6; i++) h[i] = arr[i % 3] + (i < 3 ? 0 : n[0] * 4);
+    r.edges_phase1 = (uint32_t) n[0];
 }
 
 // pdl_place_query behind its refusals: the families of the context are valid (c->fam)
@@ -475,35 +455,29 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     const uint32_t N = c->N;
     const uint64_t Z = run.Z;
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells in the query block");
-    uint64_t *ctl = place_begin(c);
+    uint64_t *d_tot = place_begin(c) + PDL_PL_EDGES_1;
     QSpans &spans = c->pb.spans;
     spans.start(st);
     spans.begin();
     uint64_t ne[2] = {0, 0};
-    PlaceEdges e{};
-    if (Z) {
-        e = place_bbh(c, c->qb, run.cap, BbhQueryBlock{c->d_gen, N, c->G}, N + n, 1, n, Z, ctl + PDL_PL_EDGES_1, ctl + PDL_PL_EDGES_2);
+    BbhEdges e{};
+    if (Z) {                                          // P-bbh: one block, one task
+        const float *cf = c->qb.cells.as<float>();
+        e = bbh_edges(c, cf, reinterpret_cast<const int32_t *>(cf + 3 * run.cap), reinterpret_cast<const int32_t *>(cf + 4 * run.cap),
+                      [&](const uint32_t *) { return BbhQueryBlock{c->d_gen, N, c->G}; }, c->qb.MS.as<float>(), c->qb.CM.as<float>(), N + n, c->G + 1, 1, n, Z, c->pb.bbh,
+                      d_tot, nullptr, 1);
         spans.end();
-        PinRead rd(c);
-        const uint64_t *pt = rd.add<uint64_t>(ctl + PDL_PL_EDGES_1, PDL_PL_EDGES_2 - PDL_PL_EDGES_1 + 1);
-        rd.sync();
-        ne[0] = 2 * pt[0]; ne[1] = pt[PDL_PL_EDGES_2 - PDL_PL_EDGES_1];
-        if (ne[0] > 2 * Z || ne[1] > Z) PDL_FAIL(PDL_ERR_DEVICE, "K-place: %llu + %llu edges of %llu cells", (unsigned long long) ne[0], (unsigned long long) ne[1], (unsigned long long) Z);
+        std::vector<uint64_t> e1, e2;
+        bbh_read_counts(c, "K-place", d_tot, e, nullptr, 1, Z, 0, e1, e2);
+        ne[0] = e1[1]; ne[1] = e2[1];
         spans.begin();
     }
     out.device_ms = place_run<PlaceOne>(c, B, PlaceQueries::one(N, n, ne[0], ne[1]), e.src, e.dst, true, false, spans, &out) + c->qb.spans.total_ms();
-    // the edges themselves, in the host's insertion order: phase 1, then phase 2
-    const uint64_t E = ne[0] + ne[1];
-    out.src.resize(E); out.dst.resize(E); out.score.resize(E);
-    for (int l = 0; l < 2; l++) {
-        if (!ne[l]) continue;
-        const uint64_t at = l ? ne[0] : 0;
-        PDL_HIP(hipMemcpyAsync(out.src.data() + at, e.src[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.dst.data() + at, e.dst[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(out.score.data() + at, e.sc[l], ne[l] * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (E) PDL_HIP(hipStreamSynchronize(st));
-    out.edges_phase1 = (uint32_t) ne[0];
+    // the edges themselves, straight into the caller's arrays
+    uint8_t *h[6];
+    place_c_edges(out, ne, h);
+    bbh_copy_out(st, e, ne, h);
+    if (ne[0] + ne[1]) PDL_HIP(hipStreamSynchronize(st));
     if (info) {
         memset(info, 0, sizeof(*info));
         info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
@@ -521,14 +495,9 @@ void pdl_run_place_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_query, co
     spans.begin();
     if (n_edges) {                                    // P-check
         const uint32_t N = base.N, NC = N + n_query;
-        hipLaunchKernelGGL(k_place_check, fam_grid(n_edges), dim3(256), 0, st, d_src, d_dst, (uint32_t) n_edges, N, NC, ctl + PDL_PL_BAD_EDGES);
-        PDL_HIP(hipGetLastError());
-        spans.end();
-        PinRead rd(c);
-        const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_PL_BAD_EDGES, 1);
-        rd.sync();
-        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-place: %llu edges name a gene id outside [0, %u) or join two base genes (ids below %u)", (unsigned long long) *bad, NC, N);
-        spans.begin();
+        hipLaunchKernelGGL(k_place_check, grid256(n_edges), dim3(256), 0, st, d_src, d_dst, (uint32_t) n_edges, N, NC, ctl + PDL_PL_BAD_EDGES);
+        const uint64_t bad = pdl_gate(c, spans, ctl + PDL_PL_BAD_EDGES);
+        if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "K-place: %llu edges name a gene id outside [0, %u) or join two base genes (ids below %u)", (unsigned long long) bad, NC, N);
     }
     const int32_t *src[2] = {d_src, nullptr}, *dst[2] = {d_dst, nullptr};
     out.device_ms = place_run<PlaceOne>(c, base, PlaceQueries::one(base.N, n_query, n_edges, 0), src, dst, false, true, spans, &out);

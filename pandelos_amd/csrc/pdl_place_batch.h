@@ -11,7 +11,8 @@
 //   P-bbh      with BbhQueryChunk over all cells of the chunk: a cell's row is an id of its own query's union, so the query comes
 //              from the cell's index against the per-query cell offsets; MS row = gene_begin[q] + (row - N), the CM slice at
 //              q * N + gene_begin[q], inter_max [q][G + 1], thr [chunk gene].  A query's phase-1 and phase-2 edges are one
-//              stretch each, its counts the prefixes at its first cell (k_pick_prefixes); one PinRead
+//              stretch each, its counts the prefixes at its first cell (k_pick_prefixes); one PinRead.  All of it is
+//              bbh_edges / bbh_read_counts / bbh_copy_out of pdl_bbh.hip with the queries as blocks, over K-place's own BbhBufs
 //   PB-check   k_place_check_batch (callers' lists only): every list against its OWN [0, N + n_q) and for base-base edges, in one
 //              launch, before any id indexes anything; the first failing query leaves by an atomicMax
 //   flat ids   query q's own id x is shift[q] + x, shift[q] = q * N + gene_begin[q] — the queries' unions [N + n_q] one behind the
@@ -99,56 +100,24 @@ static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuer
         h_cb[q + 1] = h_cb[q] + (uint32_t) ch.cells[q];
     }
     if (h_cb[nq] != Z) PDL_FAIL(PDL_ERR_DEVICE, "place batch: the queries' cells (%u) are not the emitted total %llu", h_cb[nq], (unsigned long long) Z);
-    uint64_t *bctl = place_batch_begin(c);
+    uint64_t *d_tot = place_batch_begin(c) + PDL_PB_EDGES_1;
     std::vector<uint64_t> e1(nq + 1, 0), e2(nq + 1, 0);             // first phase-1 / phase-2 edge of every query
     uint8_t *h_edges[6] = {};                                       // the chunk's edges on the host: src, dst, score of phase 1, then of phase 2
-    PlaceEdges e{};
+    BbhEdges e{};
     b.bspans.start(st);
-    if (Z) {                                                       // P-bbh
+    if (Z) {                                                       // P-bbh: a block and a task per query
         b.bspans.begin();
-        b.btab.alloc(3 * ((size_t) nq + 1) * sizeof(uint32_t));
-        uint32_t *d_cb = b.btab.as<uint32_t>(), *d_pick = d_cb + (nq + 1);
-        PDL_HIP(hipMemcpyAsync(d_cb, h_cb.data(), ((size_t) nq + 1) * 4, hipMemcpyHostToDevice, st));
-        e = place_bbh(c, c->qbb, ch.cap, BbhQueryChunk{c->d_gen, c->qbb.gene_begin.as<uint32_t>(), d_cb, N, c->G, nq}, N, nq, NT, Z, bctl + PDL_PB_EDGES_1,
-                      bctl + PDL_PB_EDGES_2);
-        // cells of each kind before every query: the prefixes at its first cell (the totals close the lists)
-        hipLaunchKernelGGL(k_pick_prefixes, dim3((nq + 1 + 255) / 256), dim3(256), 0, st, e.pre[0], e.pre[1], d_cb, nq + 1, (uint32_t) Z, d_pick);
-        PDL_HIP(hipGetLastError());
+        const float *cf = c->qbb.cells.as<float>();
+        e = bbh_edges(c, cf, reinterpret_cast<const int32_t *>(cf + 3 * ch.cap), reinterpret_cast<const int32_t *>(cf + 4 * ch.cap),
+                      [&](const uint32_t *d_cb) { return BbhQueryChunk{c->d_gen, c->qbb.gene_begin.as<uint32_t>(), d_cb, N, c->G, nq}; },
+                      c->qbb.MS.as<float>(), c->qbb.CM.as<float>(), N, c->G + 1, nq, NT, Z, b.bbh, d_tot, h_cb.data(), nq);
         b.bspans.end();
-        uint64_t n1, n2;
-        {
-            PinRead rd(c);
-            const uint64_t *pt = rd.add<uint64_t>(bctl + PDL_PB_EDGES_1, PDL_PB_EDGES_2 - PDL_PB_EDGES_1 + 1);
-            const uint32_t *pp = rd.add<uint32_t>(d_pick, 2 * ((size_t) nq + 1));
-            rd.sync();
-            const uint64_t t1 = pt[PDL_PB_EDGES_1 - PDL_PB_EDGES_1], t2 = pt[PDL_PB_EDGES_2 - PDL_PB_EDGES_1];
-            if (t1 > Z || t2 > Z) PDL_FAIL(PDL_ERR_DEVICE, "place batch: %llu + %llu edge cells of %llu cells", (unsigned long long) t1, (unsigned long long) t2, (unsigned long long) Z);
-            for (uint32_t q = 0; q <= nq; q++) {
-                const bool past = h_cb[q] >= Z;
-                e1[q] = 2 * (past ? t1 : (uint64_t) pp[q]); e2[q] = past ? t2 : (uint64_t) pp[nq + 1 + q];
-            }
-            n1 = 2 * t1; n2 = t2;
-        }
-        for (uint32_t q = 0; q < nq; q++)
-            if (e1[q + 1] < e1[q] || e2[q + 1] < e2[q] || e1[q + 1] > n1 || e2[q + 1] > n2) PDL_FAIL(PDL_ERR_DEVICE, "place batch: inconsistent edge offsets at query %u", qa + q);
-        // the edges themselves: the chunk's in one piece per array, into the batch's pinned staging (a DMA, no staging by the
-        // runtime and no page of a fresh vector to touch); they are cut out once the placement stages have waited for the stream
-        const size_t stage_bytes = (size_t) (n1 + n2) * 12;
-        auto &w = c->qbb;
-        if (w.stage_bytes < stage_bytes) {
-            if (w.stage) { (void) hipHostFree(w.stage); w.stage = nullptr; w.stage_bytes = 0; }
-            PDL_HIP(hipHostMalloc((void **) &w.stage, stage_bytes + stage_bytes / 4, hipHostMallocDefault));
-            w.stage_bytes = stage_bytes + stage_bytes / 4;
-        }
-        uint8_t *m = w.stage;                // layout: src1 | dst1 | sc1 | src2 | dst2 | sc2
-        h_edges[0] = m; h_edges[1] = m + n1 * 4; h_edges[2] = m + n1 * 8; h_edges[3] = m + n1 * 12; h_edges[4] = m + n1 * 12 + n2 * 4; h_edges[5] = m + n1 * 12 + n2 * 8;
-        for (int l = 0; l < 2; l++) {
-            const size_t bytes = (l ? n2 : n1) * 4;
-            if (!bytes) continue;
-            PDL_HIP(hipMemcpyAsync(h_edges[3 * l], e.src[l], bytes, hipMemcpyDeviceToHost, st));
-            PDL_HIP(hipMemcpyAsync(h_edges[3 * l + 1], e.dst[l], bytes, hipMemcpyDeviceToHost, st));
-            PDL_HIP(hipMemcpyAsync(h_edges[3 * l + 2], e.sc[l], bytes, hipMemcpyDeviceToHost, st));
-        }
+        bbh_read_counts(c, "place batch", d_tot, e, h_cb.data(), nq, Z, qa, e1, e2);
+        // the edges themselves: the chunk's in one piece per array, into the batch's pinned staging; they are cut out once the
+        // placement stages have waited for the stream
+        const uint64_t n[2] = {e1[nq], e2[nq]};
+        c->qbb.stage.alloc((size_t) (n[0] + n[1]) * 12);
+        bbh_copy_out(st, e, n, h_edges, c->qbb.stage.p);
     }
     // P-cc .. P-out once over the chunk
     PlaceQueries Q;
@@ -162,23 +131,10 @@ static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuer
     for (uint32_t q = 0; q < nq; q++) {
         pdl_place_result &r = out[qa + q];
         const uint64_t ne[2] = {e1[q + 1] - e1[q], e2[q + 1] - e2[q]};
-        // its edges as the C arrays the caller gets, in the host's insertion order: phase 1, then phase 2 — one pass out of the staging
-        pdl_place_result::CEdges &ce = r.c_edges;
-        ce.drop();
-        ce.n = ne[0] + ne[1]; ce.set = true;
-        const size_t bytes = std::max<size_t>(ce.n, 1) * 4;
-        ce.src = static_cast<int32_t *>(malloc(bytes)); ce.dst = static_cast<int32_t *>(malloc(bytes)); ce.score = static_cast<float *>(malloc(bytes));
-        if (!ce.src || !ce.dst || !ce.score) throw std::bad_alloc();
-        uint64_t at_out = 0;
-        for (int l = 0; l < 2; l++) {
-            if (!ne[l]) continue;
-            const uint64_t at = l ? e2[q] : e1[q];
-            memcpy(ce.src + at_out, h_edges[3 * l] + at * 4, ne[l] * 4);
-            memcpy(ce.dst + at_out, h_edges[3 * l + 1] + at * 4, ne[l] * 4);
-            memcpy(ce.score + at_out, h_edges[3 * l + 2] + at * 4, ne[l] * 4);
-            at_out += ne[l];
-        }
-        r.edges_phase1 = (uint32_t) ne[0];
+        uint8_t *h[6];                                              // its edges, cut out of the staging in one pass
+        place_c_edges(r, ne, h);
+        for (int i = 0; i < 6; i++)
+            if (ne[i / 3]) memcpy(h[i], h_edges[i] + (i < 3 ? e1[q] : e2[q]) * 4, ne[i / 3] * 4);
     }
     // (place_run has waited for the stream: the chunk's events have all been reached)
     const float query_ms = c->qbb.spans.total_ms(), total_ms = query_ms + b.bspans.total_ms() + place_ms;
@@ -236,12 +192,9 @@ void pdl_run_place_batch_edges(pdl_ctx *c, const PlaceBase &base, uint32_t n_que
         hipLaunchKernelGGL(k_place_check_batch, dim3((uint32_t) std::min<uint64_t>((E + 255) / 256, 4096)), dim3(256), 0, st, d_src, d_dst,
                            (const uint64_t *) b.up_edge_begin.as<uint64_t>(), (const uint32_t *) b.up_n_query.as<uint32_t>(), n_queries, base.N,
                            reinterpret_cast<unsigned long long *>(bctl + PDL_PB_BAD_QUERY));
-        PDL_HIP(hipGetLastError());
-        PinRead rd(c);
-        const uint64_t *bad = rd.add<uint64_t>(bctl + PDL_PB_BAD_QUERY, 1);
-        rd.sync();
-        if (*bad) {
-            const uint32_t j = n_queries - (uint32_t) *bad;
+        const uint64_t bad = pdl_gate(c, bctl + PDL_PB_BAD_QUERY);
+        if (bad) {
+            const uint32_t j = n_queries - (uint32_t) bad;
             PDL_FAIL(PDL_ERR_ARGUMENT, "K-place: query %u: its edges name a gene id outside [0, %u) or join two base genes (ids below %u)", j, base.N + n_query[j], base.N);
         }
     }

@@ -128,8 +128,6 @@ __global__ __launch_bounds__(256) void k_prof_incidences(const uint32_t *inc_sta
     if (sp != G && sp != 1) atomicAdd(cls + (size_t) G + g, cp);
 }
 
-static inline dim3 prof_grid(uint64_t n) { return dim3((uint32_t) ((n + 255) / 256)); }
-
 void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *genome_of, uint32_t N, uint32_t G, pdl_profile_result &out) {
     hipStream_t st = c->stream;
     out = pdl_profile_result{};
@@ -137,7 +135,7 @@ void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *geno
     if (G > PDL_PROFILE_MAX_GENOMES) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_family_profile: %u genomes, the per-genome spread table is kept for at most %u", G, PDL_PROFILE_MAX_GENOMES);
     pdl_ctx::ProfileBufs &b = c->pf;
     b.spans.start(st);
-    if (!c->scalars.p) c->scalars.alloc((PDL_CTL_LAST + 1) * sizeof(uint64_t));      // (a context that has built nothing yet: the sort's word is all it needs)
+    pdl_ctl_ready(c);
     const size_t n4 = (size_t) N * sizeof(uint32_t);
     const size_t hist_words = (size_t) (G + 1) + (size_t) (G + 1) * G + 4 * (size_t) G;      // spread_hist | spread_by_genome | genes | core | accessory | unique
     b.ctl.alloc(PDL_PF_WORDS * sizeof(uint64_t));
@@ -154,22 +152,15 @@ void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *geno
 
     b.spans.begin();
     PDL_HIP(hipMemsetAsync(ctl, 0, PDL_PF_WORDS * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_prof_check, prof_grid(N), dim3(256), 0, st, fam, gen, N, G, ctl + PDL_PF_BAD);
-    PDL_HIP(hipGetLastError());
-    b.spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *bad = rd.add<uint64_t>(ctl + PDL_PF_BAD, 1);
-        rd.sync();
-        if (*bad) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_family_profile: %llu genes carry a label outside [0, %u) or a genome id outside [0, %u)", (unsigned long long) *bad, N, G);
-    }
-    b.spans.begin();
+    hipLaunchKernelGGL(k_prof_check, grid256(N), dim3(256), 0, st, fam, gen, N, G, ctl + PDL_PF_BAD);
+    const uint64_t bad = pdl_gate(c, b.spans, ctl + PDL_PF_BAD);
+    if (bad) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_family_profile: %llu genes carry a label outside [0, %u) or a genome id outside [0, %u)", (unsigned long long) bad, N, G);
     PDL_HIP(hipMemsetAsync(b.hist.p, 0, hist_words * 4, st));
     PDL_HIP(hipMemsetAsync(b.size_hist.p, 0, n4 + 4, st));
     const uint32_t gbits = bit_length64(G - 1);
     uint64_t *k_in = b.k_a.as<uint64_t>(), *k_out = b.k_b.as<uint64_t>();
     uint32_t *v_in = b.v_a.as<uint32_t>(), *v_out = b.v_b.as<uint32_t>();
-    hipLaunchKernelGGL(k_prof_keys, prof_grid(N), dim3(256), 0, st, fam, gen, N, gbits, k_in, genome_genes);
+    hipLaunchKernelGGL(k_prof_keys, grid256(N), dim3(256), 0, st, fam, gen, N, gbits, k_in, genome_genes);
     PDL_HIP(hipGetLastError());
     pdl_sort_pairs<uint64_t, uint32_t>(c, k_in, k_out, v_in, v_out, N, gbits + bit_length64(N - 1), true, nullptr, 0, true);
     uint32_t *inc_start = b.inc_start.as<uint32_t>(), *inc_genome = b.inc_genome.as<uint32_t>(), *inc_label = b.inc_label.as<uint32_t>();
@@ -179,8 +170,8 @@ void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *geno
     scan_and_apply(c, N, ProfIncFlag{k_out}, ProfIncApply{k_out, gbits, N, inc_start, inc_genome, inc_label, inc_of_pos}, ctl + PDL_PF_INCIDENCES);
     scan_and_apply(c, N, ProfFamFlag{k_out, gbits}, ProfFamApply{k_out, gbits, N, inc_of_pos, ctl + PDL_PF_INCIDENCES, fam_start, label, genome_off, fam_of_label},
                    ctl + PDL_PF_FAMILIES);
-    hipLaunchKernelGGL(k_prof_families, prof_grid(N), dim3(256), 0, st, fam_start, genome_off, N, G, ctl, size, spread, size_hist, spread_hist);
-    hipLaunchKernelGGL(k_prof_incidences, prof_grid(N), dim3(256), 0, st, inc_start, inc_genome, inc_label, fam_of_label, genome_off, N, G, ctl, copies, by_genome, cls);
+    hipLaunchKernelGGL(k_prof_families, grid256(N), dim3(256), 0, st, fam_start, genome_off, N, G, ctl, size, spread, size_hist, spread_hist);
+    hipLaunchKernelGGL(k_prof_incidences, grid256(N), dim3(256), 0, st, inc_start, inc_genome, inc_label, fam_of_label, genome_off, N, G, ctl, copies, by_genome, cls);
     PDL_HIP(hipGetLastError());
     b.spans.end();
     {
@@ -195,16 +186,9 @@ void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *geno
     }
     out.n_sequences = N; out.n_genomes = G;
     const size_t F = out.families, Z = out.incidences;
-    out.label.resize(F); out.size.resize(F); out.spread.resize(F); out.genome_off.resize(F + 1); out.genomes.resize(Z); out.copies.resize(Z);
-    out.size_hist.resize((size_t) out.max_size + 1); out.hist.resize(hist_words);
-    PDL_HIP(hipMemcpyAsync(out.label.data(), label, F * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.size.data(), size, F * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.spread.data(), spread, F * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.genome_off.data(), genome_off, (F + 1) * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.genomes.data(), inc_genome, Z * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.copies.data(), copies, Z * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.size_hist.data(), size_hist, out.size_hist.size() * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.hist.data(), b.hist.p, hist_words * 4, hipMemcpyDeviceToHost, st));
+    copy_down(st, out.label, label, F); copy_down(st, out.size, size, F); copy_down(st, out.spread, spread, F); copy_down(st, out.genome_off, genome_off, F + 1);
+    copy_down(st, out.genomes, inc_genome, Z); copy_down(st, out.copies, copies, Z);
+    copy_down(st, out.size_hist, size_hist, (size_t) out.max_size + 1); copy_down(st, out.hist, b.hist.p, hist_words);
     PDL_HIP(hipStreamSynchronize(st));
     const uint32_t *sh = out.hist.data();
     out.core = sh[G]; out.unique = sh[1];
@@ -358,17 +342,10 @@ void pdl_run_pan_curves(pdl_ctx *c, const pdl_profile *p, const uint32_t *orders
     PDL_HIP(hipMemsetAsync(ctl, 0, PDL_PF_WORDS * sizeof(uint64_t), st));
     PDL_HIP(hipMemsetAsync(ctl + PDL_PF_FIRST_BAD, 0xff, sizeof(uint64_t), st));
     hipLaunchKernelGGL(k_pan_check, dim3(n_orders), dim3(256), 0, st, d_orders, G, ctl);
-    PDL_HIP(hipGetLastError());
-    b.spans.end();
-    {
-        PinRead rd(c);
-        const uint64_t *w = rd.add<uint64_t>(ctl, PDL_PF_WORDS);
-        rd.sync();
-        if (w[PDL_PF_BAD])
-            PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: order %llu is the first that is no permutation of 0..%u (%llu entries of the orders are %u and more or name a genome again)",
-                     (unsigned long long) w[PDL_PF_FIRST_BAD], G - 1, (unsigned long long) w[PDL_PF_BAD], G);
-    }
-    b.spans.begin();
+    const uint64_t bad = pdl_gate(c, b.spans, ctl + PDL_PF_BAD);
+    if (bad)            // (the refusal alone reads a second word)
+        PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: order %llu is the first that is no permutation of 0..%u (%llu entries of the orders are %u and more or name a genome again)",
+                 (unsigned long long) pdl_gate(c, ctl + PDL_PF_FIRST_BAD), G - 1, (unsigned long long) bad, G);
     PDL_HIP(hipMemsetAsync(b.bits.p, 0, bits_bytes, st));
     PDL_HIP(hipMemsetAsync(b.order_hist.p, 0, hist_bytes, st));
     unsigned long long *bits = b.bits.as<unsigned long long>();
@@ -380,9 +357,7 @@ void pdl_run_pan_curves(pdl_ctx *c, const pdl_profile *p, const uint32_t *orders
     PDL_HIP(hipGetLastError());
     b.spans.end();
     out.n_genomes = G; out.n_orders = n_orders; out.families = F; out.incidences = Z;
-    out.pan.resize(cells); out.core.resize(cells);
-    PDL_HIP(hipMemcpyAsync(out.pan.data(), pan, cells * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(out.core.data(), core, cells * 4, hipMemcpyDeviceToHost, st));
+    copy_down(st, out.pan, pan, cells); copy_down(st, out.core, core, cells);
     PDL_HIP(hipStreamSynchronize(st));
     out.device_ms = b.spans.total_ms();
 }

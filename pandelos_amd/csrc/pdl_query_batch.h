@@ -478,16 +478,12 @@ static void qb_copy_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t q
     const uint64_t Z = ch.Z, cap = ch.cap;
     const size_t ms_floats = (size_t) ch.genes * G1, cm_floats = (size_t) nq * N + ch.genes;
     const size_t stage_words = (size_t) Z * 5 + ms_floats + cm_floats;
-    if (w.stage_bytes < stage_words * 4) {
-        if (w.stage) { (void) hipHostFree(w.stage); w.stage = nullptr; w.stage_bytes = 0; }
-        PDL_HIP(hipHostMalloc((void **) &w.stage, stage_words * 4 + (stage_words * 4) / 4, hipHostMallocDefault));
-        w.stage_bytes = stage_words * 4 + (stage_words * 4) / 4;
-    }
-    const uint32_t *h_cells = reinterpret_cast<const uint32_t *>(w.stage);
-    const float *h_ms = reinterpret_cast<const float *>(w.stage) + (size_t) Z * 5, *h_cm = h_ms + ms_floats;
+    w.stage.alloc(stage_words * 4);
+    const uint32_t *h_cells = reinterpret_cast<const uint32_t *>(w.stage.p);
+    const float *h_ms = reinterpret_cast<const float *>(w.stage.p) + (size_t) Z * 5, *h_cm = h_ms + ms_floats;
     if (Z) {
         const float *cf = w.cells.as<float>();
-        for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(w.stage + (size_t) i * Z * 4, cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
+        for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(w.stage.p + (size_t) i * Z * 4, cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
     }
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_ms), w.MS.p, ms_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_cm), w.CM.p, cm_floats * 4, hipMemcpyDeviceToHost, st));

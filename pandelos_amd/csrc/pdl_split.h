@@ -299,9 +299,8 @@ void pdl_run_split(pdl_ctx *c, uint32_t n_graphs, const uint64_t *node_off, cons
         out.chunks++;
     }
     b.spans.end();
-    std::vector<uint32_t> h_count(n_graphs), h_edge(edges);
-    PDL_HIP(hipMemcpyAsync(h_count.data(), b.out_count.p, (size_t) n_graphs * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(h_edge.data(), b.out_edge.p, edges * 4, hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> h_count, h_edge;
+    copy_down(st, h_count, b.out_count.p, n_graphs); copy_down(st, h_edge, b.out_edge.p, edges);
     PDL_HIP(hipStreamSynchronize(st));
     out.device_ms = b.spans.total_ms();
     for (uint32_t j = 0; j < n_graphs; j++) {

@@ -174,7 +174,7 @@ static Words read(const pdl_ctx &c) {
     memset(&w, 0, sizeof(w));
     w.preprocessed = c.preprocessed; w.tasks_ready = c.tasks_ready; w.reshard_pending = c.reshard_pending; w.scored = c.scored;
     w.mirror = c.mirror_valid; w.edges = c.edges_valid; w.fam = c.fam_valid;
-    w.plans = c.qb.hbm_cols == 7 && c.qbb.stage_bytes == 7 && c.pb.base_serial == 7;
+    w.plans = c.qb.hbm_cols == 7 && c.qbb.stage.bytes == 7 && c.pb.base_serial == 7;
     w.dist = c.dist; w.sender = c.dist_sender; w.shard_set = c.shard_set; w.ingested = c.ingested; w.only_complexity = c.only_complexity;
     w.layout_deferred = c.layout_deferred; w.short_valid = c.short_valid;
     w.U = c.U; w.Ushared = c.Ushared; w.NG = c.NG; w.P = c.P; w.M = c.M; w.R = c.R; w.N = c.N; w.G = c.G;
@@ -187,7 +187,7 @@ static void check_reset(pdl_ctx &c) {
             put(c, s);
             // everything a reset can drop is up, whatever the state, so that a member it should have left alone shows
             c.tasks_ready = c.reshard_pending = c.mirror_valid = c.edges_valid = c.fam_valid = true;
-            c.qb.hbm_cols = 7; c.qbb.stage_bytes = 7; c.pb.base_serial = 7;
+            c.qb.hbm_cols = 7; c.qbb.stage.bytes = 7; c.pb.base_serial = 7;
             c.U = 11; c.Ushared = 12; c.NG = 13; c.P = 14; c.M = 15; c.R = 16; c.N = 17; c.G = 4;
             c.layout_deferred = true; c.short_valid = true;
             Words want = read(c);
@@ -204,7 +204,7 @@ static void check_reset(pdl_ctx &c) {
             const Words got = read(c);
             CHECK(got == want, "pdl_stale, depth %d on \"%s\": other members changed than the table names", (int) depth, s.name);
             CHECK(got.scored || !(got.mirror || got.edges || got.fam), "pdl_stale, depth %d on \"%s\": a derived product is valid on a context that is not scored", (int) depth, s.name);
-            c.qbb.stage_bytes = 0;
+            c.qbb.stage.bytes = 0;
         }
 }
 
