@@ -169,6 +169,26 @@ def _as_gene_set(genes, genome_of, family_of):
     return GeneSet(np.concatenate(genes).astype(np.uint8), offsets, np.asarray(genome_of, np.uint32), np.asarray(family_of, np.int64))
 
 
+as_gene_set = _as_gene_set
+
+
+SIFT_T_MIN = 4                                           # PT_SIFT_T_MIN in pdl_join_part.h: below it the partition tier runs its bitmap form
+
+
+def min_numerator(denom: int, k: int) -> int:
+    """smallest n with n / denom >= 1 / 2k in float32 (min_numerator in pdl_join.hip)"""
+    thr, d, n = np.float32(1.0) / np.float32(2.0 * k), np.float32(denom), 0
+    while np.float32(n) / d < thr:
+        n += 1
+    return n
+
+
+def sift_form(kseq_min: int, k: int, sift_threshold: int = 1) -> str:
+    """the form of the partition tier the host launches for a set (score_plan, pdl_join.hip:1739-1741): "counters" when the set's
+    threshold clamp(tc_min, 2, 255) reaches SIFT_T_MIN or option "sift_threshold" is 0, and "bitmaps" otherwise"""
+    return "counters" if sift_threshold == 0 or max(2, min(255, min_numerator(kseq_min, k))) >= SIFT_T_MIN else "bitmaps"
+
+
 def stretch(unit, repeats: int, k: int) -> np.ndarray:
     """`unit` repeated until every k-mer inside the stretch occurs `repeats` times: repeats * len(unit) + k - 1 residues"""
     unit = np.asarray(unit, np.uint8)
