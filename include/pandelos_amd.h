@@ -223,6 +223,21 @@ typedef struct {
 PDL_API int pdl_query_scores(pdl_ctx *, const uint8_t *residues, const uint64_t *offsets /* [n_query+1] */,
                              uint32_t n_query, pdl_scores *out, pdl_query_info *info /* may be NULL */);
 
+/* pdl_get_query_join_info: which way the rows of the last successful pdl_query_scores, pdl_query_batch, pdl_place_query or
+ * pdl_place_batch took through the query's join (all of a batch's chunks together).  A query gene is one row: one workgroup on a
+ * table in LDS, and, when its columns do not fit that table, one of at most 16 workgroups on dense tables in HBM that the context
+ * keeps between calls.  Everything here is what the host already held when the call returned; a refused call leaves the report
+ * of the last successful one. */
+typedef struct {
+    uint64_t rows;              /* query genes handed to the join (none for a query or chunk without a k-mer) */
+    uint64_t may_overflow_rows; /* rows with more lookups than the LDS table takes keys: the host then looks whether one left it */
+    uint64_t overflow_rows;     /* rows that did leave the LDS table and ran on the tables in HBM */
+    uint32_t hbm_launches;      /* launches of the HBM kernel (one per query or chunk with such a row) */
+    uint32_t hbm_workgroups;    /* the most workgroups one of them had */
+    uint32_t hbm_clears;        /* launches for which the tables were allocated or cleared rather than taken as they were */
+} pdl_query_join_info;
+PDL_API int pdl_get_query_join_info(pdl_ctx *, pdl_query_join_info *out);
+
 /* ---- query batch: q new genomes against the dictionary already built, each on its own, in one pass -------------------
  * The n genes of residues/offsets are cut into n_queries genomes by gene_begin: the genes of query j are
  * [gene_begin[j], gene_begin[j+1]).  out[j] is, bit for bit and in emission order, the block pdl_query_scores returns for the

@@ -140,6 +140,14 @@ class PdlQueryRekeyInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PdlQueryJoinInfo(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("may_overflow_rows", C.c_uint64), ("overflow_rows", C.c_uint64), ("hbm_launches", C.c_uint32),
+                ("hbm_workgroups", C.c_uint32), ("hbm_clears", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class PdlFamilies(C.Structure):
     _fields_ = [("sequences", C.c_uint32), ("nodes", C.c_uint32), ("families", C.c_uint32), ("colliding", C.c_uint32),
                 ("component_of", C.POINTER(C.c_uint32)), ("is_node", C.POINTER(C.c_uint8)), ("family_off", C.POINTER(C.c_uint32)),
@@ -195,7 +203,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_dist_genome_owner", "pdl_dist_score_begin", "pdl_dist_score_finish", "pdl_copy_device",
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
-           "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
+           "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_get_query_join_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
            "pdl_split_first_level", "pdl_free_split", "pdl_family_profile", "pdl_free_profile", "pdl_pan_curves", "pdl_free_curves", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
            "pdl_test_scan", "pdl_test_radix_offsets", "pdl_test_sort_pairs", "pdl_test_merge")
 
@@ -256,6 +264,7 @@ def load():
     lib.pdl_remove_genomes.restype = i32
     lib.pdl_get_rekey_info.argtypes = [vp, C.POINTER(PdlRekeyInfo)]; lib.pdl_get_rekey_info.restype = i32
     lib.pdl_get_query_rekey_info.argtypes = [vp, C.POINTER(PdlQueryRekeyInfo)]; lib.pdl_get_query_rekey_info.restype = i32
+    lib.pdl_get_query_join_info.argtypes = [vp, C.POINTER(PdlQueryJoinInfo)]; lib.pdl_get_query_join_info.restype = i32
     lib.pdl_compute_families.argtypes = [vp, C.POINTER(PdlFamilies)]; lib.pdl_compute_families.restype = i32
     lib.pdl_families_of_edges.argtypes = [vp, vp, vp, u64, vp, u32, C.POINTER(PdlFamilies)]; lib.pdl_families_of_edges.restype = i32
     lib.pdl_free_families.argtypes = [C.POINTER(PdlFamilies)]; lib.pdl_free_families.restype = None

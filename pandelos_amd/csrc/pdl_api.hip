@@ -718,14 +718,15 @@ static void fill_placement(pdl_place_result &r, bool with_edges, pdl_placement *
     out->group_base_off = dup_vec(r.group_base_off); out->group_base = dup_vec(r.group_base); out->group_collides = dup_vec(r.group_collides);
 }
 
-// pdl_get_query_rekey_info's books over one call of the four that score a query: opened behind the call's refusals of state and
-// argument, closed — the report becomes the context's — only when the call went through.
+// pdl_get_query_rekey_info's and pdl_get_query_join_info's books over one call of the four that score a query: opened behind the
+// call's refusals of state and argument, closed — the reports become the context's — only when the call went through.
 static void query_rekey_open(pdl_ctx *c) {
+    c->qj_call = pdl_query_join_info{};
     c->qrk_call = pdl_query_rekey_info{};
     c->qrk_call.letters_base = c->qrk_call.letters_max = c->rp.base;
     c->qrk_call.key_bits_base = c->qrk_call.key_bits_max = c->rp.rank_bits;
 }
-static void query_rekey_close(pdl_ctx *c) { c->last_query_rekey = c->qrk_call; }
+static void query_rekey_close(pdl_ctx *c) { c->last_query_rekey = c->qrk_call; c->last_query_join = c->qj_call; }
 
 int pdl_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n_query, pdl_placement *out, pdl_query_info *info) {
     if (!c) return PDL_ERR_ARGUMENT;
@@ -1192,6 +1193,15 @@ int pdl_get_query_rekey_info(pdl_ctx *c, pdl_query_rekey_info *out) {
     std::lock_guard<std::mutex> lk(c->mu);
     return guarded(c, [&]() -> int {
     *out = c->last_query_rekey;
+    return PDL_OK;
+    });
+}
+
+int pdl_get_query_join_info(pdl_ctx *c, pdl_query_join_info *out) {
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, [&]() -> int {
+    *out = c->last_query_join;
     return PDL_OK;
     });
 }

@@ -640,6 +640,7 @@ struct pdl_ctx {
     uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
     bool opt_query_rekey = false;                   // queries and placements accept letters the base lacks (pdl_query.h, Q-rebase)
     pdl_query_rekey_info qrk_call{}, last_query_rekey{};    // what the call under way / the last successful one of the four did about letters
+    pdl_query_join_info qj_call{}, last_query_join{};       // ... and which way its rows took through the join (pdl_query.h, Q-join)
     // K-fam (pdl_families.h): work buffers of a run (grown as needed, shared by pdl_compute_families and pdl_families_of_edges) and
     // the context's own families, kept on the host until the edges change (pdl_run_bbh_all drops them)
     struct FamBufs {

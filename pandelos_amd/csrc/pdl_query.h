@@ -609,7 +609,7 @@ static void q_read_words(pdl_ctx *c, QSpans &spans, const void *d_src, size_t n,
 // (*d_n_over); if so, tables (c->qb.hbm, shared by the single query and the batch) for W = min(rows, QH_WG) workgroups laid out for
 // n_cols columns — clean tables of exactly that layout are taken as they are, any other are cleared, and the bookkeeping says what
 // a later query will find (not clean from before the allocation until the clear is queued, so a throwing allocation leaves no
-// stale claim) — then launch(tables, W).
+// stale claim) — then launch(tables, W).  The call's books (pdl_get_query_join_info) take the launch, its W and whether it cleared.
 template <class LaunchF>
 static void q_join_hbm_tier(pdl_ctx *c, QSpans &spans, const unsigned long long *d_n_over, uint32_t n_cols, LaunchF launch) {
     auto &q = c->qb;
@@ -623,7 +623,10 @@ static void q_join_hbm_tier(pdl_ctx *c, QSpans &spans, const unsigned long long 
         hipLaunchKernelGGL(k_q_hbm_clear, dim3((uint32_t) std::min<uint64_t>(((uint64_t) W * n_cols + 255) / 256, 4096)), dim3(256), 0, c->stream,
                            q.hbm.as<uint8_t>(), n_cols, W);
         q.hbm_cols = n_cols; q.hbm_slots = W; q.hbm_clean = true;
+        c->qj_call.hbm_clears++;
     }
+    c->qj_call.hbm_launches++;
+    c->qj_call.hbm_workgroups = std::max(c->qj_call.hbm_workgroups, W);
     launch(q.hbm.as<uint8_t>(), W);
     PDL_HIP(hipGetLastError());
 }
@@ -836,6 +839,7 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
         const uint64_t staged = tail[Q_CTL_CELL_CURSOR - Q_CTL_OVERFLOW_ROWS];
         Z = tail[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS];
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
+        c->qj_call.rows += n; c->qj_call.may_overflow_rows += may_overflow; c->qj_call.overflow_rows += tail[0];
     } else {
         spans.end();
     }

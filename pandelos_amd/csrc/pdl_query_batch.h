@@ -455,6 +455,7 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         const uint64_t staged = h_ctl[QBG_CELL_CURSOR];
         Z = h_ctl[QBG_EMITTED];
         if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query batch join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
+        c->qj_call.rows += NT; c->qj_call.may_overflow_rows += may_overflow; c->qj_call.overflow_rows += h_ctl[QBG_OVERFLOW_ROWS];
     } else {
         spans.end();
     }

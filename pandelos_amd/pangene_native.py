@@ -283,6 +283,15 @@ class PangeneNative:
         self._check(self._lib.pdl_get_query_rekey_info(self._ctx, C.byref(info)))
         return info.as_dict()
 
+    @property
+    def last_query_join_info(self) -> dict:
+        """Which way the rows of the last successful ``query_scores`` / ``query_batch`` / ``place_query`` / ``place_batch`` took
+        through the query's join (``pdl_get_query_join_info``): rows joined, rows that might have left the LDS table and rows that
+        did, launches of the HBM kernel, the most workgroups one had, and how often its tables were cleared instead of reused."""
+        info = _lib.PdlQueryJoinInfo()
+        self._check(self._lib.pdl_get_query_join_info(self._ctx, C.byref(info)))
+        return info.as_dict()
+
     def _take_scores(self, s) -> Scores:
         try:
             z, rows, g, n = s.scoresCount, s.rows, s.genomes, s.sequences
