@@ -512,6 +512,34 @@ PDL_API int pdl_pan_curves(pdl_ctx *, const pdl_profile *profile, const uint32_t
                            pdl_curves *out);
 PDL_API void pdl_free_curves(pdl_curves *);
 
+/* ---- Genome-by-genome shared-family matrices of a profile ------------------------------------------------------------------
+ * How much gene content any two genomes share — what gene-content trees and heat maps are drawn from.  With G =
+ * profile->n_genomes, both matrices row-major with both triangles filled:
+ *   shared[g * G + h]         families with a gene in g and in h; the diagonal: the families genome g takes part in
+ *   shared_copies[g * G + h]  sum over the families of min(copies in g, copies in h), the multiset Jaccard's numerator over the
+ *                             families' copy numbers; the diagonal: the genes of g (the profile's genome_genes[g])
+ * A genome without a gene has a zero row and a zero column.  Exact integers: with the copy counts in unary bit columns
+ * (min(a, b) = sum over t >= 1 of [a >= t][b >= t]) both are AND-popcount products of one bit matrix of levels = 64 * ceil(F / 64)
+ * + sum over the families of (largest copy count - 1) columns per genome, worked through in slabs of at most option
+ * "matrix_slab_bytes" (default 2^28; a slab is at least one 64-bit word per genome wide) and, inside a slab, in `splits` parts of
+ * its words per pair of 64-genome tiles.  Of the profile the call reads n_sequences, n_genomes, families, incidences, core, size,
+ * spread, genome_off, genomes and copies.
+ * PDL_ERR_ARGUMENT (out is zeroed): NULL pointers; a profile whose fields contradict each other — what pdl_pan_curves refuses,
+ * and a copy count of 0, a row whose copies do not add up to size[f], sizes that do not add up to n_sequences.
+ * PDL_ERR_UNSUPPORTED: more than 8192 genomes, 2^31 incidences and more, 2^32 bit columns and more.  Any state of the context,
+ * nothing of it changes.  Free with pdl_free_genome_matrix.  (The struct carries the call's name as its tag: C keeps tags apart
+ * from functions, so it is written `struct pdl_genome_matrix`.) */
+struct pdl_genome_matrix {
+    uint32_t n_genomes, families, incidences;
+    uint32_t levels;                  /* L: bit columns per genome */
+    uint32_t slabs;                   /* slabs that were run */
+    uint32_t splits;                  /* the largest number of parts a slab's words were cut into */
+    uint32_t *shared, *shared_copies; /* [n_genomes * n_genomes] */
+    float device_ms;                  /* the launches, between a HIP event pair; validation, uploads and the copies back are not in it */
+};
+PDL_API int pdl_genome_matrix(pdl_ctx *, const pdl_profile *profile, struct pdl_genome_matrix *out);
+PDL_API void pdl_free_genome_matrix(struct pdl_genome_matrix *);
+
 /* ---- place: a new genome's genes in the gene families already built, without a commit -------------------------------------
  * pdl_place_query: the base context holds N genes in G genomes; the query is n_query genes taken as genome G with ids
  * N..N+n_query-1 in union numbering, exactly as pdl_query_scores does.
@@ -642,7 +670,8 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * between dispatches, a few microseconds of idle stream on a two-millisecond step), "low_memory" 0|1 (for genome batches on a large set: the buffers only the dictionary build needed are released after it —
  * pdl_get_dictionary is then not available — and tier 3's tables in HBM take 1 GB instead of 8), "query_batch_bytes" n > 0
  * (device bytes one chunk of pdl_query_batch / pdl_place_batch may take before its join, default 2^30), "split_scratch_bytes" n > 0 (device bytes of scratch one launch of
- * pdl_split_first_level may take, default 2^30; it too leaves the context's scores in place), "onepass_scan" 0|1 (prefix scans
+ * pdl_split_first_level may take, default 2^30; it too leaves the context's scores in place), "matrix_slab_bytes" n > 0 (device bytes the genomes' bit rows of
+ * one slab of pdl_genome_matrix may take, default 2^28; at least one word per genome; it too leaves the scores in place), "onepass_scan" 0|1 (prefix scans
  * in one launch with decoupled look-back instead of three launches; measured slower on MI355X, default 0), "lean_radix" 0|1
  * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"

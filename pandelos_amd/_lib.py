@@ -180,6 +180,14 @@ class PdlCurves(C.Structure):
 PDL_PAN_MAX_GENOMES = 4096
 
 
+class PdlGenomeMatrix(C.Structure):
+    _fields_ = [("n_genomes", C.c_uint32), ("families", C.c_uint32), ("incidences", C.c_uint32), ("levels", C.c_uint32),
+                ("slabs", C.c_uint32), ("splits", C.c_uint32), ("shared", _pu32), ("shared_copies", _pu32), ("device_ms", C.c_float)]
+
+
+PDL_PROFILE_MAX_GENOMES = 8192
+
+
 class PdlPlacement(C.Structure):
     _fields_ = [("sequences", C.c_uint32), ("n_query", C.c_uint32), ("genomes", C.c_uint32), ("edges", C.c_uint32),
                 ("edges_phase1", C.c_uint32), ("groups", C.c_uint32), ("novel", C.c_uint32), ("joined", C.c_uint32),
@@ -204,7 +212,7 @@ EXPORTS = ("pdl_create", "pdl_destroy", "pdl_last_error", "pdl_preprocess", "pdl
            "pdl_compute_edges", "pdl_free_edges", "pdl_ingest_faa", "pdl_ingest_genome_name", "pdl_preprocess_ingested",
            "pdl_scan_faa", "pdl_pin_arrived", "pdl_pin_checksum", "pdl_query_scores", "pdl_query_batch", "pdl_append_genomes", "pdl_remove_genomes",
            "pdl_get_rekey_info", "pdl_get_query_rekey_info", "pdl_get_query_join_info", "pdl_compute_families", "pdl_families_of_edges", "pdl_free_families",
-           "pdl_split_first_level", "pdl_free_split", "pdl_family_profile", "pdl_free_profile", "pdl_pan_curves", "pdl_free_curves", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
+           "pdl_split_first_level", "pdl_free_split", "pdl_family_profile", "pdl_free_profile", "pdl_pan_curves", "pdl_free_curves", "pdl_genome_matrix", "pdl_free_genome_matrix", "pdl_place_query", "pdl_placement_of_edges", "pdl_free_placement", "pdl_place_batch", "pdl_placement_batch_of_edges",
            "pdl_test_scan", "pdl_test_radix_offsets", "pdl_test_sort_pairs", "pdl_test_merge")
 
 _lib = None
@@ -274,6 +282,8 @@ def load():
     lib.pdl_free_profile.argtypes = [C.POINTER(PdlProfile)]; lib.pdl_free_profile.restype = None
     lib.pdl_pan_curves.argtypes = [vp, C.POINTER(PdlProfile), vp, u32, C.POINTER(PdlCurves)]; lib.pdl_pan_curves.restype = i32
     lib.pdl_free_curves.argtypes = [C.POINTER(PdlCurves)]; lib.pdl_free_curves.restype = None
+    lib.pdl_genome_matrix.argtypes = [vp, C.POINTER(PdlProfile), C.POINTER(PdlGenomeMatrix)]; lib.pdl_genome_matrix.restype = i32
+    lib.pdl_free_genome_matrix.argtypes = [C.POINTER(PdlGenomeMatrix)]; lib.pdl_free_genome_matrix.restype = None
     lib.pdl_place_query.argtypes = [vp, vp, vp, u32, C.POINTER(PdlPlacement), C.POINTER(PdlQueryInfo)]; lib.pdl_place_query.restype = i32
     lib.pdl_placement_of_edges.argtypes = [vp, C.POINTER(PdlFamilies), vp, u32, vp, vp, u64, C.POINTER(PdlPlacement)]
     lib.pdl_placement_of_edges.restype = i32

@@ -698,6 +698,29 @@ int pdl_pan_curves(pdl_ctx *c, const pdl_profile *profile, const uint32_t *order
     }, [&] { pdl_free_curves(out); });
 }
 
+// ---- Genome-by-genome shared-family matrices (pdl_matrix.h) -----------------------------------------------------------------
+void pdl_free_genome_matrix(struct pdl_genome_matrix *m) {
+    if (!m) return;
+    free(m->shared); free(m->shared_copies);
+    memset(m, 0, sizeof(*m));
+}
+
+int pdl_genome_matrix(pdl_ctx *c, const pdl_profile *profile, struct pdl_genome_matrix *out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!c || !out) return PDL_ERR_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return guarded(c, Lock::held, [&]() -> int {
+        if (!profile) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_genome_matrix: NULL pointer");
+        PDL_HIP(hipSetDevice(c->device));
+        pdl_matrix_result r;
+        pdl_run_genome_matrix(c, profile, r);
+        out->n_genomes = r.n_genomes; out->families = r.families; out->incidences = r.incidences; out->levels = r.levels;
+        out->slabs = r.slabs; out->splits = r.splits; out->device_ms = r.device_ms;
+        out->shared = dup_vec(r.shared); out->shared_copies = dup_vec(r.shared_copies);
+        return PDL_OK;
+    }, [&] { pdl_free_genome_matrix(out); });
+}
+
 // ---- K-place (pdl_place.h) ---------------------------------------------------------------------------------------------------
 void pdl_free_placement(pdl_placement *p) {
     if (!p) return;
@@ -923,6 +946,11 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     else if (n == "split_scratch_bytes") {
         if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "split_scratch_bytes: a positive byte count");
         c->opt_split_scratch_bytes = (uint64_t) value;
+        return PDL_OK;        // (nor has this one)
+    }
+    else if (n == "matrix_slab_bytes") {
+        if (value <= 0) PDL_FAIL(PDL_ERR_ARGUMENT, "matrix_slab_bytes: a positive byte count");
+        c->opt_matrix_slab_bytes = (uint64_t) value;
         return PDL_OK;        // (nor has this one)
     }
     else if (n == "query_rekey") {

@@ -193,3 +193,4 @@ void pdl_run_families_of_context(pdl_ctx *c) {
 #include "pdl_place_batch.h"     // ... for a batch of queries (pdl_place_batch)
 #include "pdl_split.h"           // K-split: Girvan-Newman's first level on the components K-fam flagged (pdl_split_first_level)
 #include "pdl_profile.h"         // the pan-genome profile of a labelling and pan / core curves over genome orders (pdl_family_profile, pdl_pan_curves)
+#include "pdl_matrix.h"          // genome-by-genome shared-family matrices of a profile (pdl_genome_matrix)

@@ -686,7 +686,15 @@ struct pdl_ctx {
         DevBuf up_orders, up_off, up_genomes, bits, order_hist, pan, core;
         EventSpans<2> spans;                        // the check and the rest
     } pf;
-    EventSpans<2> set_spans;          // pdl_append_genomes, pdl_remove_genomes (they exclude each other): the call's two stretches of device work
+    // Genome-by-genome shared-family matrices (pdl_matrix.h): a caller's profile, the families' extra bit columns and where they
+    // start, one slab of the genomes' bit rows, the two matrices.  Work buffers of one call, grown as needed.
+    struct MatrixBufs {
+        DevBuf ctl;                                 // u64 [PDL_MX_WORDS]
+        DevBuf up_off, up_genomes, up_copies, extra, extra_off, bits, shared, shared_copies;
+        EventSpans<1> spans;
+    } mx;
+    uint64_t opt_matrix_slab_bytes = 1ull << 28;    // pdl_genome_matrix: bytes the bit rows of one slab may take
+    EventSpans<2> set_spans;         // pdl_append_genomes, pdl_remove_genomes (they exclude each other): the call's two stretches of device work
     // pdl_remove_genomes (pdl_remove.h): work buffers — until the host has read `ctl` the context itself is only read
     struct RemoveBufs {
         DevBuf gmap;                  // u32 [G] new genome id, RM_GONE for a genome that leaves
@@ -910,6 +918,13 @@ struct pdl_curves_result {
 };
 void pdl_run_profile(pdl_ctx *c, const uint32_t *family_of, const uint32_t *genome_of, uint32_t N, uint32_t G, pdl_profile_result &out);
 void pdl_run_pan_curves(pdl_ctx *c, const pdl_profile *profile, const uint32_t *orders, uint32_t n_orders, pdl_curves_result &out);
+// Genome-by-genome shared-family matrices (pdl_matrix.h, pdl_bbh.hip): pdl_genome_matrix's struct without the C allocation
+struct pdl_matrix_result {
+    uint32_t n_genomes = 0, families = 0, incidences = 0, levels = 0, slabs = 0, splits = 0;
+    std::vector<uint32_t> shared, shared_copies;
+    float device_ms = 0.f;
+};
+void pdl_run_genome_matrix(pdl_ctx *c, const pdl_profile *profile, pdl_matrix_result &out);
 void pdl_ensure_costs(pdl_ctx *c);
 void pdl_input_arrived(pdl_ctx *c);      // deferred device input: waits for the genome ids / offset ends and checks them
 void pdl_finish_layout(pdl_ctx *c);      // ... then builds the genome layout on the host

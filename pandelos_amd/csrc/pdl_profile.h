@@ -304,24 +304,46 @@ __global__ __launch_bounds__(256) void k_pan_finish(const uint32_t *hist, uint32
     }
 }
 
+// The profile's fields against each other, on the host, before anything of it is indexed by anything of it: what pdl_pan_curves and
+// pdl_genome_matrix ask of a caller's profile (`who` names the call in the messages).  with_copies: the rows' copies and the sizes
+// as well (no copy count of 0, a row's copies add up to its size, the sizes to n_sequences) -> the sum over the families of their
+// largest copy count - 1 (pdl_matrix.h's extra bit columns); without: 0.
+uint64_t pdl_check_profile(const pdl_profile *p, const char *who, bool with_copies) {
+    const uint32_t G = p->n_genomes, F = p->families, Z = p->incidences;
+    if (G == 0 || F == 0 || Z < F) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: a profile of %u genomes, %u families and %u incidences", who, G, F, Z);
+    if (!p->genome_off || !p->genomes || !p->spread) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's genome_off, genomes or spread is NULL", who);
+    if (with_copies && (!p->copies || !p->size)) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's copies or size is NULL", who);
+    if (Z >= 0x7fffffffu) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%s: 2^31 incidences and more", who);
+    if (p->genome_off[0] != 0 || p->genome_off[F] != Z) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's genome_off runs from %u to %u, not from 0 to its %u incidences", who, p->genome_off[0], p->genome_off[F], Z);
+    uint32_t n_core = 0;
+    uint64_t extras = 0, genes = 0;
+    for (uint32_t f = 0; f < F; f++) {
+        const uint32_t a = p->genome_off[f], e = p->genome_off[f + 1];
+        if (e <= a || e > Z || e - a > G || e - a != p->spread[f]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's family %u has the row [%u, %u) and spread %u (%u genomes)", who, f, a, e, p->spread[f], G);
+        for (uint32_t i = a; i < e; i++)
+            if (p->genomes[i] >= G || (i > a && p->genomes[i] <= p->genomes[i - 1])) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's family %u names genome %u at place %u of its row (ascending ids below %u)", who, f, p->genomes[i], i - a, G);
+        n_core += e - a == G;
+        if (with_copies) {
+            uint64_t sum = 0;
+            uint32_t most = 0;
+            for (uint32_t i = a; i < e; i++) {
+                if (p->copies[i] == 0) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile's family %u has 0 copies in genome %u", who, f, p->genomes[i]);
+                sum += p->copies[i]; most = std::max(most, p->copies[i]);
+            }
+            if (sum != p->size[f]) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the copies of the profile's family %u add up to %llu, its size is %u", who, f, (unsigned long long) sum, p->size[f]);
+            extras += most - 1; genes += sum;
+        }
+    }
+    if (n_core != p->core) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the profile says %u core families, its rows hold %u", who, p->core, n_core);
+    if (with_copies && genes != p->n_sequences) PDL_FAIL(PDL_ERR_ARGUMENT, "%s: the sizes of the profile's families add up to %llu, it says %u genes", who, (unsigned long long) genes, p->n_sequences);
+    return extras;
+}
+
 void pdl_run_pan_curves(pdl_ctx *c, const pdl_profile *p, const uint32_t *orders, uint32_t n_orders, pdl_curves_result &out) {
     hipStream_t st = c->stream;
     out = pdl_curves_result{};
     const uint32_t G = p->n_genomes, F = p->families, Z = p->incidences;
-    // the profile's fields against each other, before anything of it is indexed by anything of it
-    if (G == 0 || F == 0 || Z < F) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: a profile of %u genomes, %u families and %u incidences", G, F, Z);
-    if (!p->genome_off || !p->genomes || !p->spread) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: the profile's genome_off, genomes or spread is NULL");
-    if (Z >= 0x7fffffffu) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_pan_curves: 2^31 incidences and more");
-    if (p->genome_off[0] != 0 || p->genome_off[F] != Z) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: the profile's genome_off runs from %u to %u, not from 0 to its %u incidences", p->genome_off[0], p->genome_off[F], Z);
-    uint32_t n_core = 0;
-    for (uint32_t f = 0; f < F; f++) {
-        const uint32_t a = p->genome_off[f], e = p->genome_off[f + 1];
-        if (e <= a || e > Z || e - a > G || e - a != p->spread[f]) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: the profile's family %u has the row [%u, %u) and spread %u (%u genomes)", f, a, e, p->spread[f], G);
-        for (uint32_t i = a; i < e; i++)
-            if (p->genomes[i] >= G || (i > a && p->genomes[i] <= p->genomes[i - 1])) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: the profile's family %u names genome %u at place %u of its row (ascending ids below %u)", f, p->genomes[i], i - a, G);
-        n_core += e - a == G;
-    }
-    if (n_core != p->core) PDL_FAIL(PDL_ERR_ARGUMENT, "pdl_pan_curves: the profile says %u core families, its rows hold %u", p->core, n_core);
+    pdl_check_profile(p, "pdl_pan_curves", false);
     if (G > PDL_PAN_MAX_GENOMES) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_pan_curves: %u genomes, the kernel's LDS holds an order of at most %u", G, (uint32_t) PDL_PAN_MAX_GENOMES);
     const uint64_t cells = (uint64_t) n_orders * G, tiles = (F + PAN_TILE - 1) / PAN_TILE, W = (G + 63) / 64;
     if (cells >= 0x7fffffffull || tiles * n_orders >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "pdl_pan_curves: %u orders of %u genomes over %u families exceed 2^31 values or workgroups", n_orders, G, F);

@@ -69,7 +69,8 @@ struct GateRow { Entry entry; const char *who; const char *edge_form; GateNeed n
 //   pdl_ingest_faa, pdl_set_option       -         -      -        -           -        -         -          -              -
 //   pdl_families_of_edges,               -         -      -        -           -        -         -          -              -     (any state: a caller's edges, graphs,
 //     pdl_split_first_level,                                                                                                       labels or orders; the context's own state
-//     pdl_family_profile, pdl_pan_curves                                                                                           is not touched)
+//     pdl_family_profile, pdl_pan_curves,                                                                                          is not touched)
+//     pdl_genome_matrix
 //   pdl_preprocess_ingested             yes        -      -        -           -        -         -          -              -
 //   pdl_genome_cost                      -        yes     -        -           -        -         -          -              -
 //   pdl_sequence_costs                   -        yes     -        -           -        -        yes         -              -

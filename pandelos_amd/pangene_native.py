@@ -433,6 +433,29 @@ class PangeneNative:
             self._lib.pdl_free_curves(C.byref(cv))
         return out
 
+    def genome_matrix(self, profile: dict) -> dict:
+        """The genome-by-genome shared-family matrices of a profile (``family_profile``'s dict; ``pdl_genome_matrix``) ->
+        {"shared", "shared_copies"}: (G, G) uint32, exact — shared[g, h] = families with a gene in g and in h, shared_copies[g, h]
+        = the sum over the families of min(copies in g, copies in h) — and the scalars n_genomes, families, incidences, levels,
+        slabs, splits and device_ms, which ``last_matrix_info`` holds as well.  ``pangenome.jaccard_distance`` and
+        ``pair_pan_core`` take the matrices.  Needs no preprocess and leaves the context's own state alone."""
+        G = int(profile["n_genomes"])
+        keep = {n: np.ascontiguousarray(profile[n], dtype=np.uint32) for n in ("size", "spread", "genome_off", "genomes", "copies")}
+        p = _lib.PdlProfile(n_sequences=int(profile["n_sequences"]), n_genomes=G, families=int(profile["families"]),
+                            incidences=int(profile["incidences"]), core=int(profile["core"]))
+        for n, a in keep.items():
+            setattr(p, n, a.ctypes.data_as(_lib._pu32))
+        m = _lib.PdlGenomeMatrix()
+        self._check(self._lib.pdl_genome_matrix(self._ctx, C.byref(p), C.byref(m)))
+        try:
+            info = {n: getattr(m, n) for n in ("n_genomes", "families", "incidences", "levels", "slabs", "splits", "device_ms")}
+            out = {"shared": _np_copy(m.shared, np.uint32, G * G).reshape(G, G),
+                   "shared_copies": _np_copy(m.shared_copies, np.uint32, G * G).reshape(G, G), **info}
+            self.last_matrix_info = info
+        finally:
+            self._lib.pdl_free_genome_matrix(C.byref(m))
+        return out
+
     def place_query(self, residues, offsets) -> dict:
         """One new genome placed into this context's gene families, without a commit (``pdl_place_query``): the query's edges
         (``src``, ``dst``, ``score`` in the host's insertion order, ``edges_phase1`` of them phase 1) and, per query gene and per

@@ -4,13 +4,16 @@ pan / core accumulation curves over random genome orders, all from one pass over
 
     python -m pandelos_amd.pangenome -i in.faa (--clus in.clus | -k K|auto) [-o out.clus]
         [--quality out.txt] [--matrix out.tsv] [--curves out.tsv --orders 1000 --seed 1]
+        [--shared out.tsv] [--shared-copies out.tsv] [--distance out.tsv] [--distance-copies out.tsv]
 
 With ``--clus`` the families are read from a ``.clus``; with ``-k`` the command takes the road of ``python -m
 pandelos_amd.families`` on the same context (ingest, dictionary, scores, best hits, K-fam, K-split) and profiles what comes out
 (``-o`` also writes that ``.clus``).  ``--quality`` writes the stdout of the reference's ``example/quality.py`` byte for byte,
 ``--matrix`` the family x genome copy counts, ``--curves`` per prefix length the mean, minimum and maximum of pan, core and new
 families over ``--orders`` random genome orders (numpy's ``Generator(PCG64(seed))``, made on the host: the device takes no random
-numbers).
+numbers).  ``--shared`` and ``--shared-copies`` write the genome x genome matrices of ``pdl_genome_matrix`` (DESIGN.md section 21:
+families two genomes share; the sum of the smaller copy number over the families), ``--distance`` and ``--distance-copies`` the
+Jaccard distances made of them in float64.
 """
 from __future__ import annotations
 
@@ -119,6 +122,62 @@ def presence_matrix(profile: dict) -> np.ndarray:
     return present
 
 
+def copies_matrix(profile: dict) -> np.ndarray:
+    """(F, G) int64: the genes family f has in genome g."""
+    F, G = int(profile["families"]), int(profile["n_genomes"])
+    copies = np.zeros((F, G), np.int64)
+    copies[np.repeat(np.arange(F), np.diff(profile["genome_off"].astype(np.int64))), profile["genomes"]] = profile["copies"]
+    return copies
+
+
+def genome_matrix_host(profile: dict) -> dict:
+    """``PangeneNative.genome_matrix`` in numpy, the tests' reference and the timing baseline, as fast as numpy makes it: per copy
+    level t the plane [copies >= t] of the families that reach t, against itself as a matrix product — shared is the product of
+    level 1, shared_copies the sum over the levels (min(a, b) = the levels both reach).  The products run in float64 through the
+    BLAS numpy is linked with (an integer ``@`` has no such road and takes a hundred times as long); every entry is a sum of
+    ones and stays far below 2^53, so the integers are exact."""
+    copies = copies_matrix(profile)
+    most = copies.max(axis=1)
+    G = copies.shape[1]
+    shared, shared_copies = None, np.zeros((G, G), np.float64)
+    for t in range(1, int(most.max()) + 1):
+        plane = (copies[most >= t] >= t).astype(np.float64)
+        product = plane.T @ plane
+        shared = product if t == 1 else shared
+        shared_copies += product
+    return {"shared": shared.astype(np.uint32), "shared_copies": shared_copies.astype(np.uint32)}
+
+
+def jaccard_distance(m) -> np.ndarray:
+    """Gene-content distance from either matrix of ``genome_matrix``: 1 - m[g, h] / (m[g, g] + m[h, h] - m[g, h]) in float64
+    from the exact integers, 0.0 where the union is 0 (two genomes without a gene)."""
+    m = np.asarray(m).astype(np.int64)
+    d = np.diag(m)
+    union = d[:, None] + d[None, :] - m
+    out = np.zeros(m.shape, np.float64)
+    np.divide(m, union, out=out, where=union != 0)
+    return np.where(union != 0, 1.0 - out, 0.0)
+
+
+def pair_pan_core(shared) -> tuple:
+    """Pan and core of every pair of genomes from ``shared``: pan2[g, h] = s[g, g] + s[h, h] - s[g, h] families in g or h,
+    core2[g, h] = s[g, h] in both (int64)."""
+    s = np.asarray(shared).astype(np.int64)
+    d = np.diag(s)
+    return d[:, None] + d[None, :] - s, s.copy()
+
+
+def matrix_tsv(m, genome_names: Sequence[str]) -> str:
+    """A square table: a header row and a first column of genome names; integers as integers, floats by ``repr``."""
+    m = np.asarray(m)
+    if m.ndim != 2 or m.shape != (len(genome_names), len(genome_names)):
+        raise ValueError(f"a ({len(genome_names)}, {len(genome_names)}) matrix wanted")
+    cell = repr if m.dtype.kind == "f" else str
+    lines = ["\t" + "\t".join(genome_names) + "\n"]
+    lines += [name + "\t" + "\t".join(cell(v) for v in row) + "\n" for name, row in zip(genome_names, m.tolist())]
+    return "".join(lines)
+
+
 def pan_curves_host(profile: dict, orders) -> dict:
     """``PangeneNative.pan_curves`` in numpy, the tests' reference and the timing baseline: per order the presence matrix with its
     columns in that order, every family's first present and first absent column, and the running counts of both."""
@@ -157,6 +216,10 @@ def main(argv: Sequence[str] | None = None) -> int:
     ap.add_argument("--curves", default=None, help="Write the pan / core accumulation curves (.tsv)")
     ap.add_argument("--orders", type=int, default=1000, help="Random genome orders of the curves")
     ap.add_argument("--seed", type=int, default=1, help="Seed of the orders")
+    ap.add_argument("--shared", default=None, help="Write the genome x genome matrix of shared families (.tsv)")
+    ap.add_argument("--shared-copies", default=None, help="Write the genome x genome matrix of shared gene copies, the sum of min(copies) over the families (.tsv)")
+    ap.add_argument("--distance", default=None, help="Write the Jaccard distance of the genomes' family sets (.tsv)")
+    ap.add_argument("--distance-copies", default=None, help="Write the multiset Jaccard distance over the families' copy numbers (.tsv)")
     args = ap.parse_args(argv)
     if (args.clus is None) == (args.kvalue is None):
         ap.error("one of --clus and -k/--kvalue")
@@ -199,6 +262,16 @@ def main(argv: Sequence[str] | None = None) -> int:
         with open(args.curves, "w") as f:
             f.write(curves_tsv(curves))
         print(f"{args.orders} orders: pan and core curves in {nativ.last_curves_info['device_ms']:.3f} ms on the device -> {args.curves}")
+    wanted = [(args.shared, "shared", False), (args.shared_copies, "shared_copies", False), (args.distance, "shared", True),
+              (args.distance_copies, "shared_copies", True)]
+    if any(path is not None for path, _, _ in wanted):
+        mats = nativ.genome_matrix(prof)
+        for path, which, distance in wanted:
+            if path is not None:
+                with open(path, "w") as f:
+                    f.write(matrix_tsv(jaccard_distance(mats[which]) if distance else mats[which], genome_names))
+        print(f"{prof['n_genomes']} x {prof['n_genomes']} genomes: shared families and copies over {mats['levels']} bit columns in "
+              f"{mats['device_ms']:.3f} ms on the device")
     nativ.close()
     return 0
 
