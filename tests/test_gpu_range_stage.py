@@ -3,7 +3,8 @@ paths: a shard that builds no range at all (buffers for max(count, 1)), a run th
 no genome.  The sets are tests/range_stage_sets.py; tests/test_range_stage_sets_cpu.py shows on the oracle that they reach the cases.
 
 Every path: each genome's Scores block, the per-genome costs, the total cost, the groups and the shared records equal the CPU
-oracle's, bit for bit.  (Tuples of 16 bytes in mode 2 need 2^22 genes or more: not reachable in a test of seconds.)"""
+oracle's, bit for bit.  (Tuples of 16 bytes in modes 1 and 2 need 2^22 genes or more: tests/test_gpu_wide_ids.py builds such sets,
+almost all of their genes shorter than k.)"""
 import numpy as np
 import pytest
 
