@@ -409,25 +409,32 @@ inline void fam_of_label(const FamView &f, std::vector<uint32_t> &of_label) {
     of_label.assign(f.N, 0);
     for (uint32_t i = 0; i < f.families; i++) of_label[f.family_genes[f.family_off[i]]] = i;
 }
-// what the device half of a single query (pdl_query.h, pdl_run_query_device) leaves: Z cells in c->qb.cells (five arrays of `cap`),
-// the maxima in c->qb.MS / c->qb.CM, the stretches of device work in c->qb.spans
-struct pdl_query_run {
-    uint64_t Z = 0, cap = 1, residues = 0, kmers = 0, records = 0, matched = 0, cost = 0;
-};
 // what the host knows of one query of a batch before the device is asked (pdl_query_batch.h)
 struct QBQuery {
     uint32_t g0, n;                 // its genes in the caller's arrays
     uint64_t Rq, Mq;                // residues, k-mers
     uint64_t bytes;                 // device memory the stages before the join need for it (the chunking's weight)
 };
-// what the device half of a chunk of a query batch (pdl_query_batch.h, pdl_run_query_chunk_device) leaves: Z ordered cells in
-// c->qbb.cells (five arrays of `cap`), query after query; MS [genes][G + 1] by chunk gene and the queries' CM slices [N + n_q] at
-// q * N + gene_begin[q] in c->qbb.MS / c->qbb.CM; gene_begin also on the device (c->qbb.gene_begin)
-struct pdl_query_chunk {
-    uint32_t nq = 0, genes = 0;
+// What the device half of a single query (pdl_query.h, pdl_run_query_device) or of a chunk of a query batch (pdl_query_batch.h,
+// pdl_run_query_chunk_device) leaves in HBM, until the context's next query: Z ordered cells, query after query, in five arrays of
+// `cap` (scores, percs, tr_percs, row, column) at `cells`; MS [genes][G + 1] by the run's gene; the queries' CM slices [N + n_q], query
+// q's at q * N + gene_begin[q].  A single query is the run of one query, gene_begin = {0, n}, which nothing on the device asks for.
+struct pdl_query_cells {
+    const float *cells = nullptr, *MS = nullptr, *CM = nullptr;
     uint64_t Z = 0, cap = 1;
-    std::vector<uint32_t> gene_begin;                            // [nq + 1] first chunk gene of every query
-    std::vector<uint64_t> cells, records, matched, cost;         // [nq]
+    uint32_t nq = 0, genes = 0;
+    std::vector<uint32_t> gene_begin;                            // [nq + 1] first gene of every query ...
+    const uint32_t *d_gene_begin = nullptr;                      // ... and on the device (a chunk's)
+    std::vector<uint64_t> cells_of, records, matched, cost;      // [nq]
+    uint64_t residues = 0, kmers = 0;                            // of the whole run
+    const QSpans *spans = nullptr;                       // the run's stretches of device work ...
+    float device_ms() const { return spans->total_ms(); }        // ... their time, once the stream has been waited for
+    // query q as the caller's pdl_query_info reports it, with the sizes the host knew of it and its share of the device time
+    void info_of(uint32_t q, uint64_t q_residues, uint64_t q_kmers, float ms, pdl_query_info *fi) const {
+        *fi = pdl_query_info{};
+        fi->residues = q_residues; fi->kmer_occurrences = q_kmers; fi->records = records[q]; fi->matched_records = matched[q];
+        fi->genome_cost = cost[q]; fi->device_ms = ms;
+    }
 };
 
 // The stages of a multi-GPU build and pass, in the order the pdl_dist_* calls walk them (DESIGN.md section 16 has who sets and
@@ -606,14 +613,18 @@ struct pdl_ctx {
     uint64_t n_inbox = 0;
     uint32_t order_grid1 = 0;
 
-    // pdl_query_scores (pdl_query.h): the query's own buffers, reused across queries, released at the next preprocess or destroy
-    struct QueryBufs {
+    // K-query: what the stages a single query and a chunk of a batch share (pdl_query.h: q_dictionary .. q_join_and_order) work on —
+    // the run's genes, its dictionary, the match's output, the rows, the control words, the maxima, the join's staging, the cells
+    struct QStageBufs {
         DevBuf res, off, koff, kseq, keys_a, keys_b, vals_a, vals_b, recpos, post, desc, gkey, rec_sorted, row_lookups, row_off,
-               fold, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells, hbm;
+               ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells;
+        QSpans spans;                                // up to three stretches of device work (four with option "query_rekey")
+    };
+    // pdl_query_scores (pdl_query.h): the query's own buffers, reused across queries, released at the next preprocess or destroy
+    struct QueryBufs : QStageBufs {
+        DevBuf fold, hbm;
         bool hbm_clean = false;                      // hbm holds hbm_slots tables laid out for hbm_cols columns, in their clean state
         uint32_t hbm_cols = 0, hbm_slots = 0;
-        const uint32_t *rec_sorted_at = nullptr;     // (inside rec_sorted: the half the gene sort left its output in)
-        QSpans spans;                                // up to three stretches of device work (four with option "query_rekey")
         // option "query_rekey" (a single query's and a chunk's alike): the union's rank table and the two plans between the base's
         // alphabet and the union's, as the host decided them (pdl_query_rekey_plan, pdl_dict.hip), and Q-rebase's output
         struct Rekey {
@@ -631,11 +642,9 @@ struct pdl_ctx {
     } qb;
     // pdl_query_batch (pdl_query_batch.h): the buffers of one chunk of queries, reused across chunks and calls, released with qb's
     // (the HBM tables of the join's last tier and their bookkeeping are qb's: a batch and a single query find each other's clean)
-    struct QueryBatchBufs {
-        DevBuf res, off, koff, kseq, gene_begin, res_begin, gene_query, keys_a, keys_b, vals_a, vals_b, recpos, post, qkey, perm, srank, spost,
-               seg_off, folds, desc, gkey, rec_sorted, row_lookups, row_off, ctl, MS, CM, row_base, row_cnt, fin_off, rowid, overflow, st, cells;
-        QSpans spans;                                // up to three stretches of device work per chunk
-        PinBuf stage;                                // host staging of a chunk's cells and maxima, or of its edges (the blocks are cut out of it)
+    struct QueryBatchBufs : QStageBufs {
+        DevBuf gene_begin, res_begin, gene_query, qkey, perm, srank, spost, seg_off, folds;      // the layout; the segments
+        PinBuf stage;                               // host staging of a chunk's cells and maxima, or of its edges (the blocks are cut out of it)
     } qbb;
     uint64_t opt_query_batch_bytes = 1ull << 30;    // pdl_query_batch: device bytes one chunk of queries may take before its join
     bool opt_query_rekey = false;                   // queries and placements accept letters the base lacks (pdl_query.h, Q-rebase)
@@ -946,9 +955,8 @@ bool pdl_query_rekey_base_exact(const pdl_ctx *c, const char **why);
 bool pdl_query_rekey_plan(pdl_ctx *c, const uint32_t letters[8], bool adopt, const char **why);
 void pdl_query_rebase(pdl_ctx *c, const void *qkeys, const uint32_t *recpos, const unsigned long long *d_records, uint64_t bound);
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info);
-// ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there); the device time
-// of its stretches is c->qb.spans.total_ms() once the stream has been waited for
-pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n);
+// ... its device half alone: everything up to the ordered cells, which stay in HBM (K-place filters them there)
+pdl_query_cells pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n);
 // K-place (pdl_place.h, pdl_bbh.hip): the query's edges (K-bbh over the query block) and their placement on the context's families;
 // the placement of a caller's edge list (device pointers, union ids) on a base
 void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_place_result &out, pdl_query_info *info);
@@ -965,7 +973,7 @@ void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
 uint32_t pdl_query_batch_plan(pdl_ctx *c, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries, std::vector<QBQuery> &qs,
                               uint64_t column_bytes);
 uint32_t pdl_query_batch_chunk_end(const pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa);
-pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
+pdl_query_cells pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
                                            uint32_t hbm_cols);
 // K-place for a batch (pdl_place_batch.h, pdl_bbh.hip): out [n_queries]; info [n_queries] or NULL
 void pdl_run_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const uint32_t *gene_begin, uint32_t n, uint32_t n_queries,

@@ -451,7 +451,7 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     hipStream_t st = c->stream;
     out = pdl_place_result{};
     const PlaceBase B = place_context_base(c);
-    const pdl_query_run run = pdl_run_query_device(c, residues, offsets, n);          // (its argument and domain refusals leave from here)
+    const pdl_query_cells run = pdl_run_query_device(c, residues, offsets, n);        // (its argument and domain refusals leave from here)
     const uint32_t N = c->N;
     const uint64_t Z = run.Z;
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells in the query block");
@@ -462,9 +462,9 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     uint64_t ne[2] = {0, 0};
     BbhEdges e{};
     if (Z) {                                          // P-bbh: one block, one task
-        const float *cf = c->qb.cells.as<float>();
+        const float *cf = run.cells;
         e = bbh_edges(c, cf, reinterpret_cast<const int32_t *>(cf + 3 * run.cap), reinterpret_cast<const int32_t *>(cf + 4 * run.cap),
-                      [&](const uint32_t *) { return BbhQueryBlock{c->d_gen, N, c->G}; }, c->qb.MS.as<float>(), c->qb.CM.as<float>(), N + n, c->G + 1, 1, n, Z, c->pb.bbh,
+                      [&](const uint32_t *) { return BbhQueryBlock{c->d_gen, N, c->G}; }, run.MS, run.CM, N + n, c->G + 1, 1, n, Z, c->pb.bbh,
                       d_tot, nullptr, 1);
         spans.end();
         std::vector<uint64_t> e1, e2;
@@ -472,17 +472,13 @@ void pdl_run_place_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
         ne[0] = e1[1]; ne[1] = e2[1];
         spans.begin();
     }
-    out.device_ms = place_run<PlaceOne>(c, B, PlaceQueries::one(N, n, ne[0], ne[1]), e.src, e.dst, true, false, spans, &out) + c->qb.spans.total_ms();
+    out.device_ms = place_run<PlaceOne>(c, B, PlaceQueries::one(N, n, ne[0], ne[1]), e.src, e.dst, true, false, spans, &out) + run.device_ms();
     // the edges themselves, straight into the caller's arrays
     uint8_t *h[6];
     place_c_edges(out, ne, h);
     bbh_copy_out(st, e, ne, h);
     if (ne[0] + ne[1]) PDL_HIP(hipStreamSynchronize(st));
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
-        info->genome_cost = run.cost; info->device_ms = c->qb.spans.total_ms();
-    }
+    if (info) run.info_of(0, run.residues, run.kmers, run.device_ms(), info);
 }
 
 // pdl_placement_of_edges behind its argument checks: the same stages over a caller's list on a caller's base (device pointers)

@@ -7,7 +7,7 @@
 // Per chunk of the query batch (pdl_query_batch.h cuts the chunks), on one stream, no cell crosses PCIe; the stages of pdl_place.h
 // run ONCE over the chunk (place_run with the chunk's layout).  What a chunk adds to them:
 //
-//   B-alpha .. B-order   pdl_run_query_chunk_device: the chunk's ordered cells, MS and CM stay in c->qbb, query after query
+//   B-alpha .. B-order   pdl_run_query_chunk_device: the chunk's ordered cells, MS and CM stay in HBM, query after query (pdl_query_cells)
 //   P-bbh      with BbhQueryChunk over all cells of the chunk: a cell's row is an id of its own query's union, so the query comes
 //              from the cell's index against the per-query cell offsets; MS row = gene_begin[q] + (row - N), the CM slice at
 //              q * N + gene_begin[q], inter_max [q][G + 1], thr [chunk gene].  A query's phase-1 and phase-2 edges are one
@@ -87,7 +87,7 @@ static uint64_t *place_batch_begin(pdl_ctx *c) {
 }
 
 // One chunk behind its device half: K-bbh over all its cells, then the placement stages over all its edges; the placements go to out[qa..).
-static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuery> &qs, uint32_t qa, const pdl_query_chunk &ch,
+static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuery> &qs, uint32_t qa, const pdl_query_cells &ch,
                         std::vector<pdl_place_result> &out, pdl_query_info *info, float *device_ms) {
     hipStream_t st = c->stream;
     pdl_ctx::PlaceBufs &b = c->pb;
@@ -96,8 +96,8 @@ static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuer
     if (Z >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "more than 2^31 cells in one chunk of the query batch (option query_batch_bytes cuts smaller chunks)");
     std::vector<uint32_t> h_cb(nq + 1, 0);
     for (uint32_t q = 0; q < nq; q++) {
-        if (h_cb[q] + ch.cells[q] > Z) PDL_FAIL(PDL_ERR_DEVICE, "place batch: the queries' cells pass the emitted total %llu", (unsigned long long) Z);
-        h_cb[q + 1] = h_cb[q] + (uint32_t) ch.cells[q];
+        if (h_cb[q] + ch.cells_of[q] > Z) PDL_FAIL(PDL_ERR_DEVICE, "place batch: the queries' cells pass the emitted total %llu", (unsigned long long) Z);
+        h_cb[q + 1] = h_cb[q] + (uint32_t) ch.cells_of[q];
     }
     if (h_cb[nq] != Z) PDL_FAIL(PDL_ERR_DEVICE, "place batch: the queries' cells (%u) are not the emitted total %llu", h_cb[nq], (unsigned long long) Z);
     uint64_t *d_tot = place_batch_begin(c) + PDL_PB_EDGES_1;
@@ -107,10 +107,10 @@ static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuer
     b.bspans.start(st);
     if (Z) {                                                       // P-bbh: a block and a task per query
         b.bspans.begin();
-        const float *cf = c->qbb.cells.as<float>();
+        const float *cf = ch.cells;
         e = bbh_edges(c, cf, reinterpret_cast<const int32_t *>(cf + 3 * ch.cap), reinterpret_cast<const int32_t *>(cf + 4 * ch.cap),
-                      [&](const uint32_t *d_cb) { return BbhQueryChunk{c->d_gen, c->qbb.gene_begin.as<uint32_t>(), d_cb, N, c->G, nq}; },
-                      c->qbb.MS.as<float>(), c->qbb.CM.as<float>(), N, c->G + 1, nq, NT, Z, b.bbh, d_tot, h_cb.data(), nq);
+                      [&](const uint32_t *d_cb) { return BbhQueryChunk{c->d_gen, ch.d_gene_begin, d_cb, N, c->G, nq}; },
+                      ch.MS, ch.CM, N, c->G + 1, nq, NT, Z, b.bbh, d_tot, h_cb.data(), nq);
         b.bspans.end();
         bbh_read_counts(c, "place batch", d_tot, e, h_cb.data(), nq, Z, qa, e1, e2);
         // the edges themselves: the chunk's in one piece per array, into the batch's pinned staging; they are cut out once the
@@ -137,18 +137,11 @@ static void place_chunk(pdl_ctx *c, const PlaceBase &B, const std::vector<QBQuer
             if (ne[i / 3]) memcpy(h[i], h_edges[i] + (i < 3 ? e1[q] : e2[q]) * 4, ne[i / 3] * 4);
     }
     // (place_run has waited for the stream: the chunk's events have all been reached)
-    const float query_ms = c->qbb.spans.total_ms(), total_ms = query_ms + b.bspans.total_ms() + place_ms;
+    const float query_ms = ch.device_ms(), total_ms = query_ms + b.bspans.total_ms() + place_ms;
     *device_ms += total_ms;
     for (uint32_t q = 0; q < nq; q++) {
         out[qa + q].device_ms = total_ms / (float) nq;
-        if (info) {
-            const QBQuery &one = qs[qa + q];
-            pdl_query_info &fi = info[qa + q];
-            memset(&fi, 0, sizeof(fi));
-            fi.residues = one.Rq; fi.kmer_occurrences = one.Mq; fi.records = ch.records[q]; fi.matched_records = ch.matched[q];
-            fi.genome_cost = ch.cost[q];
-            fi.device_ms = query_ms / (float) nq;
-        }
+        if (info) ch.info_of(q, qs[qa + q].Rq, qs[qa + q].Mq, query_ms / (float) nq, &info[qa + q]);
     }
 }
 
@@ -169,7 +162,7 @@ void pdl_run_place_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
             genes += qs[q].n;
             if (q > qa && place_flat_ids(c->N, q - qa + 1, genes) >= 0x7fffffffull) { qe = q; break; }
         }
-        const pdl_query_chunk ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);       // (its argument and domain refusals leave from here)
+        const pdl_query_cells ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);       // (its argument and domain refusals leave from here)
         place_chunk(c, B, qs, qa, ch, out, info, device_ms);
         (*chunks)++;
         qa += ch.nq;                                                 // (option "query_rekey" may have cut the chunk short of qe)

@@ -44,6 +44,12 @@
 //   qmax <  bmax         L is the base's last record; if it was alone it joins max(r2, qmax): a query group when qmax > r2
 //                        (p leaves [gs, U)) — case (c) — or r2 as in the base
 // A group is described by {base slice, base record skipped, extra base record, query slice, extra query record}.
+//
+// Host side.  A single query is a run of ONE query and a chunk of a batch (pdl_query_batch.h) a run of several: both drivers are
+// entry functions over the same stage functions — q_dictionary, q_match_out, q_gene_rows, q_join_and_order — which work on the
+// run's QStageBufs (pdl_common.h: c->qb here, c->qbb there) and its QRun, index one control-word layout (Q_RUN_*, then Q_QRY_* per
+// query) and leave one result view, pdl_query_cells.  pdl_run_query_device keeps what is a single query's own: the domain
+// refusals, NewGenes, the single verdict of option "query_rekey", k_q_rowids, k_q_fold / k_q_match.
 #pragma once
 #include "pdl_sort.h"
 
@@ -71,22 +77,30 @@ struct QFold {
     uint32_t has_extra;     // p joins the query group of rank extra_target
 };
 
-// control words of a query (q.ctl, u64), cleared at the start of every query; each word has one life
+// Control words of a run — a single query (one query) or a chunk of a batch — in the run's `ctl` (u64): Q_RUN_WORDS for the run,
+// then Q_QRY_WORDS per query; cleared at the start of every run, each word has one life.  q_query_ctl is the one accessor, for the
+// kernels and for the host's copy (QCtlHost below).
 enum : uint32_t {
-    Q_CTL_RECORDS = 0,          // records of the query's dictionary (total of its dedup scan)
-    Q_CTL_BAD_BYTE = 1,         // 256 - smallest byte that is not in the base's alphabet (0: none)
-    Q_CTL_COST = 2,             // genome cost
-    Q_CTL_MATCHED = 3,          // matched records
-    Q_CTL_BOUND = 4,            // staging bound
-    Q_CTL_OVERFLOW_ROWS = 5,    // rows the LDS join handed to the HBM join
-    Q_CTL_CELL_CURSOR = 6,      // staging cursor
-    Q_CTL_EMITTED = 7,          // emitted cells (total of the row-count scan)
-    Q_CTL_WIDE_ROWS = 8,        // order: rows of more than 256 cells
-    Q_CTL_MAY_OVERFLOW = 9,     // rows that may overflow (more lookups than the LDS table holds keys)
-    Q_CTL_USED = 10,            // (the words above: what the look behind the match reads)
-    Q_CTL_LETTERS = 10,         // option "query_rekey": 256 bits, the query bytes that are not in the base's alphabet (4 words)
-    Q_CTL_WORDS = 16,
+    Q_RUN_RECORDS = 0,          // records of the run's dictionary (total of its dedup scan)
+    Q_RUN_OVERFLOW_ROWS = 1,    // rows the LDS join handed to the HBM join
+    Q_RUN_CELL_CURSOR = 2,      // staging cursor
+    Q_RUN_EMITTED = 3,          // emitted cells (total of the row-count scan)
+    Q_RUN_WIDE_ROWS = 4,        // order: rows of more than 256 cells
+    Q_RUN_WORDS = 8,
 };
+enum : uint32_t {
+    Q_QRY_RECORDS = 0,          // records of the query (a chunk's: its segment; the single query's are the run's)
+    Q_QRY_BAD_BYTE = 1,         // 256 - smallest byte that is not in the base's alphabet (0: none)
+    Q_QRY_COST = 2,             // genome cost
+    Q_QRY_MATCHED = 3,          // matched records
+    Q_QRY_BOUND = 4,            // staging bound
+    Q_QRY_MAY_OVERFLOW = 5,     // rows that may overflow (more lookups than the LDS table holds keys)
+    Q_QRY_EMITTED = 6,          // emitted cells (a chunk's; the single query's are the run's)
+    Q_QRY_LETTERS = 8,          // option "query_rekey": 256 bits, the query's bytes that are not in the base's alphabet (4 words)
+    Q_QRY_WORDS = 12,
+};
+template <class T> __host__ __device__ __forceinline__ T *q_query_ctl(T *ctl, uint32_t q) { return ctl + Q_RUN_WORDS + (size_t) q * Q_QRY_WORDS; }
+constexpr size_t q_ctl_words(uint32_t nq) { return Q_RUN_WORDS + (size_t) nq * Q_QRY_WORDS; }
 
 // Q-alpha: the bytes of `res` that the base's alphabet lacks — rare, so everything but the table test sits behind it.
 //   LETTERS   false: the word at `words` is raised to 256 - byte, i.e. it ends as 256 - the smallest absent byte (0: none)
@@ -239,7 +253,7 @@ __global__ void k_q_fold(QView<KeyB, KeyQ, RK> v, const unsigned long long *ctl,
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     bool lonely, has_r2;
     QFold f = q_fold_base(v.b, lonely, has_r2, v.up3());
-    q_fold_union(f, lonely, has_r2, v, 0u, (uint32_t) ctl[Q_CTL_RECORDS]);
+    q_fold_union(f, lonely, has_r2, v, 0u, (uint32_t) ctl[Q_RUN_RECORDS]);
     *out = f;
 }
 
@@ -280,6 +294,7 @@ __device__ __forceinline__ QDesc q_describe(const QFold &f, const View &v, uint3
     return d;
 }
 
+// what the match (k_q_match, and k_qb_match of pdl_query_batch.h) leaves
 struct QMatchOut {
     QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
     unsigned long long *ctl;
@@ -288,7 +303,7 @@ struct QMatchOut {
 template <class KeyB, class KeyQ, bool RK>
 __global__ __launch_bounds__(256) void k_q_match(QView<KeyB, KeyQ, RK> v, const QFold *pf, QMatchOut o, uint64_t bound) {
     const QFold f = *pf;
-    const uint32_t Uq = (uint32_t) o.ctl[Q_CTL_RECORDS];
+    const uint32_t Uq = (uint32_t) o.ctl[Q_RUN_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     if (j < Uq && j < bound) {
@@ -303,8 +318,8 @@ __global__ __launch_bounds__(256) void k_q_match(QView<KeyB, KeyQ, RK> v, const 
 #pragma unroll
     for (int s = PDL_WAVE / 2; s > 0; s >>= 1) { cost += __shfl_down(cost, s, PDL_WAVE); matched += __shfl_down(matched, s, PDL_WAVE); }
     if ((threadIdx.x & (PDL_WAVE - 1)) == 0) {
-        if (cost) atomicAdd(&o.ctl[Q_CTL_COST], cost);
-        if (matched) atomicAdd(&o.ctl[Q_CTL_MATCHED], matched);
+        if (cost) atomicAdd(q_query_ctl(o.ctl, 0) + Q_QRY_COST, cost);
+        if (matched) atomicAdd(q_query_ctl(o.ctl, 0) + Q_QRY_MATCHED, matched);
     }
 }
 
@@ -314,7 +329,7 @@ __global__ __launch_bounds__(256) void k_q_row_off(const uint32_t *gene_sorted, 
                                                    const uint32_t *row_lookups, uint32_t n_cols, uint32_t limit, unsigned long long *bound,
                                                    unsigned long long *wide) {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t Uq = (uint32_t) ctl[Q_CTL_RECORDS];
+    const uint32_t Uq = (uint32_t) ctl[Q_RUN_RECORDS];
     unsigned long long b = 0, w = 0;
     if (g <= n) {
         uint32_t lo = 0, hi = Uq;
@@ -578,7 +593,19 @@ __global__ __launch_bounds__(256) void k_q_rowids(uint32_t *ids, uint32_t base, 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// What pdl_run_query and the batch's qb_run_chunk (pdl_query_batch.h) both do behind the match.
+// The stages pdl_run_query_device and the batch's pdl_run_query_chunk_device (pdl_query_batch.h) share, over the run's QStageBufs
+// (c->qb, c->qbb) and its description: q_dictionary, q_match_out, q_gene_rows, and everything behind the match, q_join_and_order.
+struct QRun {
+    uint32_t rows, queries;                         // genes of the run (the join's rows); queries
+    const uint32_t *gene_begin, *d_gene_begin;      // [queries + 1] the queries' first rows: on the host, and (a chunk) on the device
+    uint64_t residues, kmers;
+    uint64_t max_cols;                              // columns of the widest union
+    uint32_t hbm_cols;                              // columns the HBM tables are laid out for
+    bool rekey;                                     // option "query_rekey": the run is ranked with the plan of c->qb.rk
+    const char *who;                                // "query" / "query batch", and in a refusal query q is ...
+    int64_t qa;                                     // ... "query <qa + q>:", the chunk's place in the caller's batch (-1: the single query, "query")
+    bool single() const { return qa < 0; }
+};
 
 // the join's arguments as far as the base and the staging (five arrays of `cap` cells at `stf`) set them; the caller adds its own
 // buffers, the query genes' count and the counters
@@ -604,6 +631,14 @@ static void q_read_words(pdl_ctx *c, QSpans &spans, const void *d_src, size_t n,
     }
     if (more_work) spans.begin();
 }
+// ... at all control words of a run of nq queries: the host's copy, indexed as the device's (q_query_ctl)
+struct QCtlHost {
+    std::vector<uint64_t> w;
+    explicit QCtlHost(uint32_t nq) : w(q_ctl_words(nq)) {}
+    void read(pdl_ctx *c, QSpans &spans, const void *d_ctl, bool more_work = true) { q_read_words(c, spans, d_ctl, w.size(), w.data(), more_work); }
+    uint64_t run(uint32_t word) const { return w[word]; }
+    uint64_t of(uint32_t q, uint32_t word) const { return q_query_ctl(w.data(), q)[word]; }
+};
 
 // The HBM tier, when some row has more lookups than the LDS table holds keys: the host looks whether a row left the table
 // (*d_n_over); if so, tables (c->qb.hbm, shared by the single query and the batch) for W = min(rows, QH_WG) workgroups laid out for
@@ -730,12 +765,115 @@ static QView<KeyB, KeyQ, RK> q_view(pdl_ctx *c, const void *qkeys) {
     return v;
 }
 
+// Q-dict over the genes a run has uploaded into w (res, off, koff), sized by the bound Mq; the record count stays on the device, at
+// Q_RUN_RECORDS.  -> the buffer that holds the sorted keys, of q_key_bytes each.
+static size_t q_key_bytes(const pdl_ctx *c, bool rekey) { return (rekey ? c->qb.rk.key64 : c->key64) ? 8 : 4; }
+static const void *q_dictionary(pdl_ctx *c, pdl_ctx::QStageBufs &w, const QRun &r) {
+    const uint64_t Mq = r.kmers;
+    const size_t kb = q_key_bytes(c, r.rekey);
+    w.keys_a.alloc(Mq * kb); w.keys_b.alloc(Mq * kb); w.vals_a.alloc(Mq * 4); w.vals_b.alloc(Mq * 4);
+    w.recpos.alloc((Mq + 1) * 4); w.post.alloc(Mq * 8);
+    return pdl_query_dictionary(c, r.rekey ? c->qb.rk.rp : c->rp, kb == 8, w.res.as<uint8_t>(), w.off.as<uint64_t>(), w.koff.as<uint64_t>(), r.rows, Mq, r.residues,
+                                w.keys_a.p, w.keys_b.p, w.vals_a.as<uint32_t>(), w.vals_b.as<uint32_t>(), w.recpos.as<uint32_t>(), w.post.as<uint2>(),
+                                reinterpret_cast<uint64_t *>(w.ctl.as<unsigned long long>() + Q_RUN_RECORDS));
+}
+// where the match writes: a description and a gene key per record, the rows' lookups (cleared) — and the rows' offsets behind them
+static QMatchOut q_match_out(pdl_ctx *c, pdl_ctx::QStageBufs &w, const QRun &r) {
+    w.desc.alloc(r.kmers * sizeof(QDesc)); w.gkey.alloc(r.kmers * 8); w.rec_sorted.alloc(r.kmers * 8);
+    w.row_lookups.alloc(r.rows * 4ull); w.row_off.alloc((r.rows + 1) * 4ull);
+    PDL_HIP(hipMemsetAsync(w.row_lookups.p, 0, r.rows * 4ull, c->stream));
+    return QMatchOut{w.desc.as<QDesc>(), w.gkey.as<uint32_t>(), w.row_lookups.as<uint32_t>(), w.ctl.as<unsigned long long>()};
+}
+// Q-rows: each gene's records in rank order — a stable sort of the record indices by the gene key the match left (the records are in
+// (rank, gene) order) — then row_off(gene keys, sorted) launches the run's row-offset kernel.  -> the sorted record indices
+template <class RowOffF>
+static const uint32_t *q_gene_rows(pdl_ctx *c, pdl_ctx::QStageBufs &w, const QRun &r, RowOffF row_off) {
+    uint32_t *gk_in = w.gkey.as<uint32_t>(), *gk_out = gk_in + r.kmers;
+    uint32_t *ix_in = w.rec_sorted.as<uint32_t>(), *ix_out = ix_in + r.kmers;
+    pdl_sort_pairs<uint32_t, uint32_t>(c, gk_in, gk_out, ix_in, ix_out, r.kmers, std::max<uint32_t>(1, bit_length64(r.rows)), true,
+                                       reinterpret_cast<const uint64_t *>(w.ctl.as<unsigned long long>() + Q_RUN_RECORDS), 0, true);
+    row_off((const uint32_t *) gk_out);
+    PDL_HIP(hipGetLastError());
+    return ix_out;
+}
+
+// Everything behind the match: the host's look at the control words (a query's absent byte is refused here), the maxima cleared,
+// Q-join — join(a) launches the LDS join over the run's rows, join_hbm(a, W) the HBM join of W workgroups —, Q-order, counts() for
+// whatever the run counts per query behind it, and the closing look: one PinRead of the whole block.  qpost: the query records'
+// postings as the row program indexes them; rec_sorted: q_gene_rows' (null: no k-mer); w.rowid, the rows' gene ids in their unions,
+// is the caller's to fill before Q-order reads it — join(a) at the latest; it holds the run's rows from here on, and a caller that
+// filled it earlier (a chunk's row offsets do) sized it so.  -> what the run leaves.
+template <class JoinF, class JoinHbmF, class CountsF>
+static pdl_query_cells q_join_and_order(pdl_ctx *c, pdl_ctx::QStageBufs &w, const QRun &r, const uint2 *qpost, const uint32_t *rec_sorted,
+                                        JoinF join, JoinHbmF join_hbm, CountsF counts) {
+    hipStream_t st = c->stream;
+    QSpans &spans = w.spans;
+    unsigned long long *ctl = w.ctl.as<unsigned long long>();
+    const uint32_t N = c->N, G1 = c->G + 1, nq = r.queries, NT = r.rows;
+    QCtlHost h(nq);
+    h.read(c, spans, ctl);
+    uint64_t bound = 0, may_overflow = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (h.of(q, Q_QRY_BAD_BYTE)) {
+            char who[48] = "query";
+            if (!r.single()) snprintf(who, sizeof(who), "query %u:", (uint32_t) r.qa + q);
+            pdl_fail_absent_byte(h.of(q, Q_QRY_BAD_BYTE), who);
+        }
+        bound += h.of(q, Q_QRY_BOUND); may_overflow += h.of(q, Q_QRY_MAY_OVERFLOW);
+    }
+    const uint64_t Ut = h.run(Q_RUN_RECORDS);
+    if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);
+
+    const size_t ms_floats = (size_t) NT * G1, cm_floats = (size_t) nq * N + NT;
+    w.MS.alloc(ms_floats * 4); w.CM.alloc(cm_floats * 4);
+    PDL_HIP(hipMemsetAsync(w.MS.p, 0, ms_floats * 4, st));
+    PDL_HIP(hipMemsetAsync(w.CM.p, 0, cm_floats * 4, st));
+    const uint64_t cap = std::max<uint64_t>(bound, 1);
+    uint64_t Z = 0;
+    if (Ut) {
+        w.row_base.alloc(NT * 4ull); w.row_cnt.alloc(NT * 4ull); w.fin_off.alloc((NT + 1) * 4ull); w.rowid.alloc(NT * 4ull); w.overflow.alloc(NT * 4ull);
+        w.st.alloc(cap * 20); w.cells.alloc(cap * 20);
+        QJoinArgs a = q_join_args(c, w.st.as<float>(), cap);
+        a.qpost = qpost; a.desc = w.desc.as<QDesc>(); a.rec_sorted = rec_sorted; a.row_off = w.row_off.as<uint32_t>();
+        a.kseq_q = w.kseq.as<uint32_t>(); a.n = NT; a.MS = w.MS.as<float>(); a.CM = w.CM.as<float>();      // (a.n: a chunk's rows take their own query's, qb_row_args)
+        a.row_base = w.row_base.as<uint32_t>(); a.row_cnt = w.row_cnt.as<uint32_t>();
+        a.cell_cursor = ctl + Q_RUN_CELL_CURSOR; a.overflow_rows = w.overflow.as<uint32_t>(); a.n_overflow = ctl + Q_RUN_OVERFLOW_ROWS;
+        join(a);
+        PDL_HIP(hipGetLastError());
+        // (tables laid out for hbm_cols columns — the query's own count, a batch's widest union: those cleaned for another count are cleared again)
+        if (may_overflow) q_join_hbm_tier(c, spans, a.n_overflow, r.hbm_cols, [&](uint8_t *hbm, uint32_t W) { a.hbm = hbm; join_hbm(a, W); });
+        q_order_rows(c, a, w.fin_off.as<uint32_t>(), w.rowid.as<uint32_t>(), w.cells.as<float>(), NT, cap, r.max_cols, ctl + Q_RUN_EMITTED, ctl + Q_RUN_WIDE_ROWS);
+        counts();
+        PDL_HIP(hipGetLastError());
+        h.read(c, spans, ctl, false);                             // the cursors and the per-query counts: one read
+        const uint64_t staged = h.run(Q_RUN_CELL_CURSOR);
+        Z = h.run(Q_RUN_EMITTED);
+        if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "%s join: %llu cells staged, bound %llu", r.who, (unsigned long long) staged, (unsigned long long) bound);
+        c->qj_call.rows += NT; c->qj_call.may_overflow_rows += may_overflow; c->qj_call.overflow_rows += h.run(Q_RUN_OVERFLOW_ROWS);
+    } else {
+        spans.end();
+    }
+    if (r.rekey) q_rekey_report(c, Ut, r.kmers != 0);
+    pdl_query_cells out;
+    out.cells = w.cells.as<float>(); out.MS = w.MS.as<float>(); out.CM = w.CM.as<float>();
+    out.Z = Z; out.cap = cap; out.nq = nq; out.genes = NT;
+    out.gene_begin.assign(r.gene_begin, r.gene_begin + nq + 1); out.d_gene_begin = r.d_gene_begin;
+    out.residues = r.residues; out.kmers = r.kmers; out.spans = &spans;
+    out.cells_of.assign(nq, 0); out.records.resize(nq); out.matched.resize(nq); out.cost.resize(nq);
+    for (uint32_t q = 0; q < nq; q++) {
+        out.cells_of[q] = Ut ? h.of(q, Q_QRY_EMITTED) : 0;
+        out.records[q] = h.of(q, Q_QRY_RECORDS); out.matched[q] = h.of(q, Q_QRY_MATCHED); out.cost[q] = h.of(q, Q_QRY_COST);
+    }
+    if (r.single()) { out.cells_of[0] = Z; out.records[0] = Ut; }       // (no segments, no per-query counts: the one query's are the run's)
+    return out;
+}
+
 // The device half of a query: every stage up to the ordered cells, which stay where they are (pdl_run_query copies them out,
 // K-place — pdl_place.h — filters them in HBM).
-pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
+pdl_query_cells pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n) {
     hipStream_t st = c->stream;
     auto &q = c->qb;
-    const uint32_t N = c->N, G = c->G, G1 = G + 1;
+    const uint32_t N = c->N;
     const uint64_t NC64 = (uint64_t) N + n;
     if (NC64 >= 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu genes in the union exceed the 31-bit gene ids", (unsigned long long) NC64);
     const uint32_t NC = (uint32_t) NC64;
@@ -752,108 +890,61 @@ pdl_query_run pdl_run_query_device(pdl_ctx *c, const uint8_t *residues, const ui
     spans.begin();
 
     // Q-alpha
-    q.ctl.alloc(Q_CTL_WORDS * sizeof(uint64_t));
-    unsigned long long *ctl = q.ctl.as<unsigned long long>();
-    PDL_HIP(hipMemsetAsync(ctl, 0, Q_CTL_WORDS * sizeof(uint64_t), st));
+    q.ctl.alloc(q_ctl_words(1) * sizeof(uint64_t));
+    unsigned long long *ctl = q.ctl.as<unsigned long long>(), *qctl = q_query_ctl(ctl, 0);
+    PDL_HIP(hipMemsetAsync(ctl, 0, q_ctl_words(1) * sizeof(uint64_t), st));
     genes.upload(c, residues);
     // option "query_rekey": the letters themselves come to the host before the dictionary is made; a query that brings one is
     // ranked with the union's table (base letters + ALL its letters, genes shorter than k included, as a build counts them)
     bool rekey = false;
     if (c->opt_query_rekey && Rq) {
-        q_scan_absent<true, false>(c, q.res.as<uint8_t>(), Rq, nullptr, 1, 0, ctl + Q_CTL_LETTERS);
+        q_scan_absent<true, false>(c, q.res.as<uint8_t>(), Rq, nullptr, 1, 0, qctl + Q_QRY_LETTERS);
         uint32_t letters[8];
-        q_read_words(c, spans, ctl + Q_CTL_LETTERS, 8, letters);
+        q_read_words(c, spans, qctl + Q_QRY_LETTERS, 8, letters);
         if (q_any_letter(letters)) { q_rekey_verdict(c, letters, "query", true); rekey = true; }
     }
-    if (!rekey) pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, ctl + Q_CTL_BAD_BYTE);
-    const bool qkey64 = rekey ? q.rk.key64 : c->key64;
+    if (!rekey) pdl_check_alphabet(c, q.res.as<uint8_t>(), Rq, qctl + Q_QRY_BAD_BYTE);
+    const uint32_t gene_begin[2] = {0, n};
+    // (tables laid out for THIS query's column count)
+    const QRun run{n, 1, gene_begin, nullptr, Rq, Mq, NC, NC, rekey, "query", -1};
 
-    // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look below)
-    const void *qkeys = nullptr;
+    // Q-dict, Q-fold, Q-match, Q-rows (sized by the bound Mq; the record count stays on the device until the look behind them)
+    const uint32_t *rec_sorted = nullptr;
     if (Mq) {
-        const size_t kb = qkey64 ? 8 : 4;
-        q.keys_a.alloc(Mq * kb); q.keys_b.alloc(Mq * kb); q.vals_a.alloc(Mq * 4); q.vals_b.alloc(Mq * 4);
-        q.recpos.alloc((Mq + 1) * 4); q.post.alloc(Mq * 8);
-        qkeys = pdl_query_dictionary(c, rekey ? q.rk.rp : c->rp, qkey64, q.res.as<uint8_t>(), q.off.as<uint64_t>(), q.koff.as<uint64_t>(), n, Mq, Rq,
-                                     q.keys_a.p, q.keys_b.p, q.vals_a.as<uint32_t>(), q.vals_b.as<uint32_t>(), q.recpos.as<uint32_t>(), q.post.as<uint2>(),
-                                     reinterpret_cast<uint64_t *>(ctl + Q_CTL_RECORDS));
-        q.fold.alloc(sizeof(QFold)); q.desc.alloc(Mq * sizeof(QDesc)); q.gkey.alloc(Mq * 8); q.rec_sorted.alloc(Mq * 8);
-        q.row_lookups.alloc(n * 4ull); q.row_off.alloc((n + 1) * 4ull);
-        PDL_HIP(hipMemsetAsync(q.row_lookups.p, 0, n * 4ull, st));
-        QMatchOut mo{q.desc.as<QDesc>(), q.gkey.as<uint32_t>(), q.row_lookups.as<uint32_t>(), ctl};
+        const void *qkeys = q_dictionary(c, q, run);
+        q.fold.alloc(sizeof(QFold));
+        const QMatchOut mo = q_match_out(c, q, run);
         const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
         // (re-keyed: Q-rebase first, then fold and match in two alphabets — the base's key type for its keys, the union's for the query's)
         q_with_keys(c, rekey, [&](auto key_b, auto key_q, auto rk) {
             using KeyB = decltype(key_b);
             using KeyQ = decltype(key_q);
             constexpr bool RK = decltype(rk)::value;
-            if constexpr (RK) pdl_query_rebase(c, qkeys, q.recpos.as<uint32_t>(), ctl + Q_CTL_RECORDS, Mq);
+            if constexpr (RK) pdl_query_rebase(c, qkeys, q.recpos.as<uint32_t>(), ctl + Q_RUN_RECORDS, Mq);
             const QView<KeyB, KeyQ, RK> v = q_view<KeyB, KeyQ, RK>(c, qkeys);
             hipLaunchKernelGGL((k_q_fold<KeyB, KeyQ, RK>), dim3(1), dim3(64), 0, st, v, (const unsigned long long *) ctl, q.fold.as<QFold>());
             hipLaunchKernelGGL((k_q_match<KeyB, KeyQ, RK>), grid_m, dim3(256), 0, st, v, (const QFold *) q.fold.as<QFold>(), mo, Mq);
         });
         PDL_HIP(hipGetLastError());
-        // each gene's records in rank order: a stable sort of the record indices by gene (the records are in (rank, gene) order)
-        uint32_t *gk_in = q.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
-        uint32_t *ix_in = q.rec_sorted.as<uint32_t>(), *ix_out = ix_in + Mq;
-        pdl_sort_pairs<uint32_t, uint32_t>(c, gk_in, gk_out, ix_in, ix_out, Mq, std::max<uint32_t>(1, bit_length64(n)), true,
-                                           reinterpret_cast<const uint64_t *>(ctl + Q_CTL_RECORDS), 0, true);
-        hipLaunchKernelGGL(k_q_row_off, dim3((n + 1 + 255) / 256), dim3(256), 0, st, gk_out, (const unsigned long long *) ctl, n,
-                           q.row_off.as<uint32_t>(), (const uint32_t *) q.row_lookups.as<uint32_t>(), NC, QJ_LIMIT, ctl + Q_CTL_BOUND, ctl + Q_CTL_MAY_OVERFLOW);
-        PDL_HIP(hipGetLastError());
-        q.rec_sorted_at = ix_out;
-    }
-    uint64_t h_ctl[Q_CTL_USED] = {};
-    q_read_words(c, spans, ctl, Q_CTL_USED, h_ctl);
-    if (h_ctl[Q_CTL_BAD_BYTE]) pdl_fail_absent_byte(h_ctl[Q_CTL_BAD_BYTE], "query");
-    const uint64_t Uq = h_ctl[Q_CTL_RECORDS], cost = h_ctl[Q_CTL_COST], matched = h_ctl[Q_CTL_MATCHED], bound = h_ctl[Q_CTL_BOUND],
-                   may_overflow = h_ctl[Q_CTL_MAY_OVERFLOW];
-    if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);
-
-    // Q-join, Q-order
-    q.MS.alloc((size_t) n * G1 * 4); q.CM.alloc((size_t) NC * 4);
-    PDL_HIP(hipMemsetAsync(q.MS.p, 0, (size_t) n * G1 * 4, st));
-    PDL_HIP(hipMemsetAsync(q.CM.p, 0, (size_t) NC * 4, st));
-    uint64_t Z = 0;
-    if (Uq) {
-        q.row_base.alloc(n * 4ull); q.row_cnt.alloc(n * 4ull); q.fin_off.alloc((n + 1) * 4ull); q.rowid.alloc(n * 4ull); q.overflow.alloc(n * 4ull);
-        q.st.alloc(std::max<uint64_t>(bound, 1) * 20); q.cells.alloc(std::max<uint64_t>(bound, 1) * 20);
-        hipLaunchKernelGGL(k_q_rowids, dim3((n + 255) / 256), dim3(256), 0, st, q.rowid.as<uint32_t>(), N, n);
-        const uint64_t cap = std::max<uint64_t>(bound, 1);
-        QJoinArgs a = q_join_args(c, q.st.as<float>(), cap);
-        a.qpost = q.post.as<uint2>(); a.desc = q.desc.as<QDesc>(); a.rec_sorted = q.rec_sorted_at; a.row_off = q.row_off.as<uint32_t>();
-        a.kseq_q = q.kseq.as<uint32_t>(); a.n = n; a.MS = q.MS.as<float>(); a.CM = q.CM.as<float>();
-        a.row_base = q.row_base.as<uint32_t>(); a.row_cnt = q.row_cnt.as<uint32_t>();
-        a.cell_cursor = ctl + Q_CTL_CELL_CURSOR; a.overflow_rows = q.overflow.as<uint32_t>(); a.n_overflow = ctl + Q_CTL_OVERFLOW_ROWS;
-        hipLaunchKernelGGL(k_q_join, dim3(n), dim3(QJ_T), 0, st, a);
-        PDL_HIP(hipGetLastError());
-        // (tables laid out for THIS query's column count: those cleaned for another count are cleared again)
-        if (may_overflow) q_join_hbm_tier(c, spans, a.n_overflow, NC, [&](uint8_t *hbm, uint32_t W) {
-            a.hbm = hbm;
-            hipLaunchKernelGGL(k_q_join_hbm, dim3(W), dim3(QJ_T), 0, st, a);
+        rec_sorted = q_gene_rows(c, q, run, [&](const uint32_t *gene_sorted) {
+            hipLaunchKernelGGL(k_q_row_off, dim3((n + 1 + 255) / 256), dim3(256), 0, st, gene_sorted, (const unsigned long long *) ctl, n, q.row_off.as<uint32_t>(),
+                               (const uint32_t *) q.row_lookups.as<uint32_t>(), NC, QJ_LIMIT, qctl + Q_QRY_BOUND, qctl + Q_QRY_MAY_OVERFLOW);
         });
-        q_order_rows(c, a, q.fin_off.as<uint32_t>(), q.rowid.as<uint32_t>(), q.cells.as<float>(), n, cap, NC, ctl + Q_CTL_EMITTED, ctl + Q_CTL_WIDE_ROWS);
-        PDL_HIP(hipGetLastError());
-        uint64_t tail[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1];
-        q_read_words(c, spans, ctl + Q_CTL_OVERFLOW_ROWS, Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS + 1, tail, false);
-        const uint64_t staged = tail[Q_CTL_CELL_CURSOR - Q_CTL_OVERFLOW_ROWS];
-        Z = tail[Q_CTL_EMITTED - Q_CTL_OVERFLOW_ROWS];
-        if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
-        c->qj_call.rows += n; c->qj_call.may_overflow_rows += may_overflow; c->qj_call.overflow_rows += tail[0];
-    } else {
-        spans.end();
     }
-    if (rekey) q_rekey_report(c, Uq, Mq != 0);
-    pdl_query_run run;
-    run.Z = Z; run.cap = std::max<uint64_t>(bound, 1); run.residues = Rq; run.kmers = Mq; run.records = Uq; run.matched = matched; run.cost = cost;
-    return run;
+    // the look, Q-join, Q-order: the rows are the query's genes N.., their arguments the same for all
+    return q_join_and_order(c, q, run, q.post.as<uint2>(), rec_sorted,
+        [&](const QJoinArgs &a) {
+            hipLaunchKernelGGL(k_q_rowids, dim3((n + 255) / 256), dim3(256), 0, st, q.rowid.as<uint32_t>(), N, n);
+            hipLaunchKernelGGL(k_q_join, dim3(n), dim3(QJ_T), 0, st, a);
+        },
+        [&](const QJoinArgs &a, uint32_t W) { hipLaunchKernelGGL(k_q_join_hbm, dim3(W), dim3(QJ_T), 0, st, a); },
+        [] {});
 }
 
 void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, uint32_t n, pdl_scores *out, pdl_query_info *info) {
     hipStream_t st = c->stream;
-    auto &q = c->qb;
     const uint32_t G1 = c->G + 1, NC = c->N + n;
-    const pdl_query_run run = pdl_run_query_device(c, residues, offsets, n);
+    const pdl_query_cells run = pdl_run_query_device(c, residues, offsets, n);
     const uint64_t Z = run.Z;
 
     // Q-copy: straight into the block's arrays
@@ -861,21 +952,14 @@ void pdl_run_query(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets,
     try {
         q_block_alloc(c, r, Z, n);
         if (Z) {
-            const uint64_t cap = run.cap;
-            const float *cf = q.cells.as<float>();
             void *dst[5] = {r.scores, r.percs, r.tr_percs, r.row, r.column};
-            for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(dst[i], cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
+            for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(dst[i], run.cells + (size_t) i * run.cap, Z * 4, hipMemcpyDeviceToHost, st));
         }
-        PDL_HIP(hipMemcpyAsync(r.max_genome_score, q.MS.p, (size_t) n * G1 * 4, hipMemcpyDeviceToHost, st));
-        PDL_HIP(hipMemcpyAsync(r.max_genome_score_col, q.CM.p, (size_t) NC * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(r.max_genome_score, run.MS, (size_t) n * G1 * 4, hipMemcpyDeviceToHost, st));
+        PDL_HIP(hipMemcpyAsync(r.max_genome_score_col, run.CM, (size_t) NC * 4, hipMemcpyDeviceToHost, st));
         PDL_HIP(hipStreamSynchronize(st));
     } catch (...) { pdl_free_scores(&r); throw; }
     q_block_ids(c, r);
     *out = r;
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->residues = run.residues; info->kmer_occurrences = run.kmers; info->records = run.records; info->matched_records = run.matched;
-        info->genome_cost = run.cost;
-        info->device_ms = q.spans.total_ms();
-    }
+    if (info) run.info_of(0, run.residues, run.kmers, run.device_ms(), info);
 }

@@ -1,7 +1,9 @@
 // pdl_query_batch.h — K-query for a batch: q new genomes scored against the dictionary that is already in HBM, each on its own
 // (pdl_query_batch, include/pandelos_amd.h), included from pdl_join.hip behind pdl_query.h.  The fold (q_fold_base,
-// q_fold_union), the group description (q_describe), the row program (q_row_lds, q_row_hbm) and the host's tail (join arguments,
-// HBM tier, order, block) are the single query's: the kernels here give them a query's segment and a row's own arguments.
+// q_fold_union), the group description (q_describe) and the row program (q_row_lds, q_row_hbm) are the single query's: the kernels
+// here give them a query's segment and a row's own arguments.  So are the host's stages — q_dictionary, q_match_out, q_gene_rows,
+// q_join_and_order over c->qbb as QStageBufs —, the control words (Q_RUN_*, Q_QRY_*) and the result view (pdl_query_cells):
+// pdl_run_query_chunk_device keeps what is a chunk's own, the staging, the verdicts of option "query_rekey", B-seg, and its launches.
 //
 // Contract: block j is what pdl_query_scores returns for genome j alone — computeScores(G) of base + genome j.  The queries
 // never see each other; the base context is only read.
@@ -25,7 +27,7 @@
 //
 //   B-copy   the chunk's cells and maxima to the host in one piece each, every query's block cut out there
 //
-// B-alpha .. B-order and the per-query counts are pdl_run_query_chunk_device: the cells stay in HBM.  pdl_query_batch follows
+// B-alpha .. B-order and the per-query counts are pdl_run_query_chunk_device: the cells stay in HBM (pdl_query_cells).  pdl_query_batch follows
 // it with B-copy; K-place for a batch (pdl_place_batch.h) filters the cells where they lie instead.
 //
 // Fold and match run over one view, QBView<KeyB, KeyQ, RK> (QView's accessors over segment positions), chosen by q_with_keys.
@@ -41,28 +43,7 @@
 #pragma once
 #include "pdl_query.h"
 
-// control words of a chunk (qbb.ctl, u64): QBG_WORDS for the chunk, then QB_CTL_WORDS per query; cleared at the start of every
-// chunk, each word has one life
-enum : uint32_t {
-    QBG_RECORDS = 0,            // records of the chunk's dictionary (total of its dedup scan)
-    QBG_OVERFLOW_ROWS = 1,      // rows the LDS join handed to the HBM join
-    QBG_CELL_CURSOR = 2,        // staging cursor
-    QBG_EMITTED = 3,            // emitted cells (total of the row-count scan)
-    QBG_WIDE_ROWS = 4,          // order: rows of more than 256 cells
-    QBG_WORDS = 8,
-};
-enum : uint32_t {
-    QB_CTL_RECORDS = 0,         // records of the query (its segment)
-    QB_CTL_BAD_BYTE = 1,        // 256 - smallest byte that is not in the base's alphabet (0: none)
-    QB_CTL_COST = 2,            // genome cost
-    QB_CTL_MATCHED = 3,         // matched records
-    QB_CTL_BOUND = 4,           // staging bound
-    QB_CTL_MAY_OVERFLOW = 5,    // rows that may overflow (more lookups than the LDS table holds keys)
-    QB_CTL_EMITTED = 6,         // emitted cells
-    QB_CTL_LETTERS = 8,         // option "query_rekey": 256 bits, the query's bytes that are not in the base's alphabet (4 words)
-    QB_CTL_WORDS = 12,
-};
-__device__ __forceinline__ unsigned long long *qb_ctl(unsigned long long *ctl, uint32_t q) { return ctl + QBG_WORDS + (size_t) q * QB_CTL_WORDS; }
+// (the chunk's control words, qbb.ctl: Q_RUN_* for the chunk, Q_QRY_* per query — pdl_query.h)
 
 // the chunk's layout: genes [gene_begin[q], gene_begin[q + 1]) and bytes [res_begin[q], res_begin[q + 1]) belong to query q
 struct QBLayout {
@@ -75,7 +56,7 @@ struct QBLayout {
 // key of the segment sort: the query of every record of the chunk's dictionary
 __global__ __launch_bounds__(256) void k_qb_seg_key(const uint2 *post, const unsigned long long *ctl, QBLayout lay, uint32_t *key) {
     const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-    if (u < (uint32_t) ctl[QBG_RECORDS]) key[u] = lay.gene_query[post[u].x];
+    if (u < (uint32_t) ctl[Q_RUN_RECORDS]) key[u] = lay.gene_query[post[u].x];
 }
 
 // Records in segment order: rank and {local gene, count} of position j, and seg_off[q] = first position of query q (a query
@@ -84,7 +65,7 @@ template <class KeyT>
 __global__ __launch_bounds__(256) void k_qb_gather(const KeyT *keys, const uint32_t *recpos, const uint2 *post, const uint32_t *perm,
                                                    const uint32_t *qid_sorted, const unsigned long long *ctl, QBLayout lay,
                                                    KeyT *srank, uint2 *spost, uint32_t *seg_off) {
-    const uint32_t U = (uint32_t) ctl[QBG_RECORDS];
+    const uint32_t U = (uint32_t) ctl[Q_RUN_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= U) return;
     const uint32_t src = perm[j], q = qid_sorted[j];
@@ -118,7 +99,7 @@ __global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyB, KeyQ, RK> v, uint32
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
     const uint32_t s0 = v.seg_off[q], s1 = v.seg_off[q + 1];
-    qb_ctl(ctl, q)[QB_CTL_RECORDS] = s1 - s0;
+    q_query_ctl(ctl, q)[Q_QRY_RECORDS] = s1 - s0;
     if (s0 == s1) {                                               // no k-mer: no record reads the fold
         QFold f{};
         f.p = Q_NONE; f.qL = Q_NONE;
@@ -131,14 +112,10 @@ __global__ __launch_bounds__(64) void k_qb_fold(QBView<KeyB, KeyQ, RK> v, uint32
     out[q] = f;
 }
 
-struct QBMatchOut {
-    QDesc *desc; uint32_t *gene_key; uint32_t *row_lookups;
-    unsigned long long *ctl;
-};
 // One thread per record of the chunk: k_q_match inside the record's own segment; cost and matched count per query
 template <class KeyB, class KeyQ, bool RK>
-__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyB, KeyQ, RK> v, const QFold *folds, QBLayout lay, QBMatchOut o, uint64_t bound) {
-    const uint32_t Ut = (uint32_t) o.ctl[QBG_RECORDS];
+__global__ __launch_bounds__(256) void k_qb_match(QBView<KeyB, KeyQ, RK> v, const QFold *folds, QBLayout lay, QMatchOut o, uint64_t bound) {
+    const uint32_t Ut = (uint32_t) o.ctl[Q_RUN_RECORDS];
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     unsigned long long cost = 0, matched = 0;
     uint32_t q = Q_NONE;
@@ -162,8 +139,8 @@ __global__ __launch_bounds__(256) void k_qb_match(QBView<KeyB, KeyQ, RK> v, cons
         if ((threadIdx.x & (PDL_WAVE - 1)) != 0) return;
     }
     if (q == Q_NONE) return;
-    if (cost) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_COST, cost);
-    if (matched) atomicAdd(qb_ctl(o.ctl, q) + QB_CTL_MATCHED, matched);
+    if (cost) atomicAdd(q_query_ctl(o.ctl, q) + Q_QRY_COST, cost);
+    if (matched) atomicAdd(q_query_ctl(o.ctl, q) + Q_QRY_MATCHED, matched);
 }
 
 // row_off[g] = first position of chunk gene g in the gene-sorted records; per query: staging bound = sum of
@@ -171,7 +148,7 @@ __global__ __launch_bounds__(256) void k_qb_match(QBView<KeyB, KeyQ, RK> v, cons
 __global__ __launch_bounds__(256) void k_qb_row_off(const uint32_t *gene_sorted, unsigned long long *ctl, QBLayout lay, uint32_t N, uint32_t *row_off,
                                                     const uint32_t *row_lookups, uint32_t limit, uint32_t *rowid) {
     const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t Ut = (uint32_t) ctl[QBG_RECORDS];
+    const uint32_t Ut = (uint32_t) ctl[Q_RUN_RECORDS];
     if (g > lay.genes) return;
     uint32_t lo = 0, hi = Ut;
     while (lo < hi) { const uint32_t m = lo + ((hi - lo) >> 1); if (gene_sorted[m] < g) lo = m + 1; else hi = m; }
@@ -180,8 +157,8 @@ __global__ __launch_bounds__(256) void k_qb_row_off(const uint32_t *gene_sorted,
     const uint32_t q = lay.gene_query[g], g0 = lay.gene_begin[q];
     rowid[g] = N + (g - g0);
     const uint32_t n_cols = N + (lay.gene_begin[q + 1] - g0), l = row_lookups[g];
-    if (l) atomicAdd(qb_ctl(ctl, q) + QB_CTL_BOUND, (unsigned long long) min(l, n_cols));
-    if (l > limit) atomicAdd(qb_ctl(ctl, q) + QB_CTL_MAY_OVERFLOW, 1ull);
+    if (l) atomicAdd(q_query_ctl(ctl, q) + Q_QRY_BOUND, (unsigned long long) min(l, n_cols));
+    if (l > limit) atomicAdd(q_query_ctl(ctl, q) + Q_QRY_MAY_OVERFLOW, 1ull);
 }
 
 // ---- B-join ------------------------------------------------------------------------------------------------------------
@@ -228,8 +205,8 @@ __global__ __launch_bounds__(64) void k_qb_counts(const uint32_t *fin_off, QBLay
     const uint32_t q = blockIdx.x * 64 + threadIdx.x;
     if (q >= lay.nq) return;
     const uint32_t g1 = lay.gene_begin[q + 1];
-    const uint32_t end = g1 == lay.genes ? (uint32_t) ctl[QBG_EMITTED] : fin_off[g1];      // (fin_off holds the rows' starts; the scan's total closes it)
-    qb_ctl(ctl, q)[QB_CTL_EMITTED] = end - fin_off[lay.gene_begin[q]];
+    const uint32_t end = g1 == lay.genes ? (uint32_t) ctl[Q_RUN_EMITTED] : fin_off[g1];      // (fin_off holds the rows' starts; the scan's total closes it)
+    q_query_ctl(ctl, q)[Q_QRY_EMITTED] = end - fin_off[lay.gene_begin[q]];
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -250,7 +227,7 @@ struct QBStage {
     uint64_t Rq = 0, Mq = 0;                        // residues, k-mers
     std::vector<uint64_t> off, koff, rbeg;
     std::vector<uint32_t> kseq, gq, gbeg;
-    size_t ctl_words() const { return QBG_WORDS + (size_t) nq * QB_CTL_WORDS; }
+    size_t ctl_words() const { return q_ctl_words(nq); }
     // The counts of the first n queries [qa, qa + n).  Every staged array is valid as a prefix — off[NT'] = Rq', koff[NT'] = Mq',
     // gene_begin[n] = NT', res_begin[n] = Rq', the control words lie query by query — so a chunk that is cut stages nothing again.
     void take(const std::vector<QBQuery> &qs, uint32_t qa, uint32_t n) {
@@ -310,15 +287,15 @@ static void qb_rekey_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t 
     rekey = false;
     if (!s.Rq) return;
     unsigned long long *ctl = w.ctl.as<unsigned long long>();
-    q_scan_absent<true, true>(c, w.res.as<uint8_t>(), s.Rq, w.res_begin.as<uint64_t>(), s.nq, QB_CTL_WORDS, ctl + QBG_WORDS + QB_CTL_LETTERS);
-    std::vector<uint64_t> h_ctl(s.ctl_words());
-    q_read_words(c, w.spans, ctl, h_ctl.size(), h_ctl.data(), false);
+    q_scan_absent<true, true>(c, w.res.as<uint8_t>(), s.Rq, w.res_begin.as<uint64_t>(), s.nq, Q_QRY_WORDS, ctl + Q_RUN_WORDS + Q_QRY_LETTERS);
+    QCtlHost h(s.nq);
+    h.read(c, w.spans, ctl, false);
     uint32_t joint[8] = {};
     const char *why = "";
     const bool base_exact = pdl_query_rekey_base_exact(c, &why);
     for (uint32_t q = 0; q < s.nq; q++) {
         uint32_t own[8], with[8];
-        memcpy(own, &h_ctl[QBG_WORDS + (size_t) q * QB_CTL_WORDS + QB_CTL_LETTERS], sizeof(own));
+        memcpy(own, q_query_ctl(h.w.data(), q) + Q_QRY_LETTERS, sizeof(own));
         if (!q_any_letter(own)) continue;
         bool grows = false;
         for (int i = 0; i < 8; i++) { with[i] = joint[i] | own[i]; grows = grows || with[i] != joint[i]; }
@@ -336,42 +313,34 @@ static void qb_rekey_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t 
 }
 
 // The device half of one chunk, queries [qa, qe) of `qs` — with option "query_rekey" a prefix of them (qb_rekey_chunk), the
-// chunk's nq says how many: B-alpha ... B-order and the per-query counts.  The ordered cells (five
-// arrays of `cap`), MS and CM stay in c->qbb; the stretches of device work are c->qbb.spans (read once the stream has been waited for).
-pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
+// chunk's nq says how many: B-alpha ... B-order and the per-query counts.  The ordered cells, MS and CM stay in HBM.
+pdl_query_cells pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, const uint64_t *offsets, const std::vector<QBQuery> &qs, uint32_t qa, uint32_t qe,
                                            uint32_t hbm_cols) {
     hipStream_t st = c->stream;
     auto &w = c->qbb;
-    QSpans &spans = w.spans;
 
     // B-alpha (and the chunk on its way to the device)
     QBStage s = qb_stage_chunk(c, residues, offsets, qs, qa, qe);
     bool rekey = false;
     if (c->opt_query_rekey) qb_rekey_chunk(c, qs, qa, s, rekey);
-    const uint32_t N = c->N, G1 = c->G + 1, nq = s.nq, NT = s.NT, n_max = s.n_max;
-    const uint64_t Rq = s.Rq, Mq = s.Mq;
-    const size_t ctl_words = s.ctl_words();
+    const uint32_t N = c->N, nq = s.nq, NT = s.NT;
+    const uint64_t Mq = s.Mq;
     unsigned long long *ctl = w.ctl.as<unsigned long long>();
     const QBLayout lay{w.gene_begin.as<uint32_t>(), w.res_begin.as<uint64_t>(), w.gene_query.as<uint32_t>(), nq, NT};
     // (a chunk that is re-keyed has had its verdicts)
-    if (!rekey) q_scan_absent<false, true>(c, w.res.as<uint8_t>(), Rq, lay.res_begin, nq, QB_CTL_WORDS, ctl + QBG_WORDS + QB_CTL_BAD_BYTE);
+    if (!rekey) q_scan_absent<false, true>(c, w.res.as<uint8_t>(), s.Rq, lay.res_begin, nq, Q_QRY_WORDS, q_query_ctl(ctl, 0) + Q_QRY_BAD_BYTE);
+    // (tables laid out for the batch's widest union, which every query's columns fit)
+    const QRun run{NT, nq, s.gbeg.data(), lay.gene_begin, s.Rq, Mq, (uint64_t) N + s.n_max, hbm_cols, rekey, "query batch", qa};
 
-    // B-dict, B-seg, B-fold, B-match, B-rows (sized by the bound Mq; the record count stays on the device until the look below)
+    // B-dict, B-seg, B-fold, B-match, B-rows (sized by the bound Mq; the record count stays on the device until the look behind them)
     w.rowid.alloc(NT * 4ull);
     const uint32_t *rec_sorted = nullptr;
     if (Mq) {
-        const bool qkey64 = rekey ? c->qb.rk.key64 : c->key64;
-        const size_t kb = qkey64 ? 8 : 4;
-        w.keys_a.alloc(Mq * kb); w.keys_b.alloc(Mq * kb); w.vals_a.alloc(Mq * 4); w.vals_b.alloc(Mq * 4);
-        w.recpos.alloc((Mq + 1) * 4); w.post.alloc(Mq * 8);
-        const uint64_t *d_u = reinterpret_cast<const uint64_t *>(ctl + QBG_RECORDS);
-        const void *qkeys = pdl_query_dictionary(c, rekey ? c->qb.rk.rp : c->rp, qkey64, w.res.as<uint8_t>(), w.off.as<uint64_t>(), w.koff.as<uint64_t>(), NT, Mq, Rq,
-                                                 w.keys_a.p, w.keys_b.p, w.vals_a.as<uint32_t>(), w.vals_b.as<uint32_t>(), w.recpos.as<uint32_t>(),
-                                                 w.post.as<uint2>(), reinterpret_cast<uint64_t *>(ctl + QBG_RECORDS));
-        w.qkey.alloc(Mq * 8); w.perm.alloc(Mq * 8); w.srank.alloc(Mq * kb); w.spost.alloc(Mq * 8); w.seg_off.alloc((nq + 1) * 4ull);
-        w.folds.alloc(nq * sizeof(QFold)); w.desc.alloc(Mq * sizeof(QDesc)); w.gkey.alloc(Mq * 8); w.rec_sorted.alloc(Mq * 8);
-        w.row_lookups.alloc(NT * 4ull); w.row_off.alloc((NT + 1) * 4ull);
-        PDL_HIP(hipMemsetAsync(w.row_lookups.p, 0, NT * 4ull, st));
+        const uint64_t *d_u = reinterpret_cast<const uint64_t *>(ctl + Q_RUN_RECORDS);
+        const void *qkeys = q_dictionary(c, w, run);
+        w.qkey.alloc(Mq * 8); w.perm.alloc(Mq * 8); w.srank.alloc(Mq * q_key_bytes(c, rekey)); w.spost.alloc(Mq * 8); w.seg_off.alloc((nq + 1) * 4ull);
+        w.folds.alloc(nq * sizeof(QFold));
+        const QMatchOut mo = q_match_out(c, w, run);
         PDL_HIP(hipMemsetAsync(w.seg_off.p, 0, (nq + 1) * 4ull, st));
         const dim3 grid_m((uint32_t) ((Mq + 255) / 256));
         // every query's records as one segment, in (rank, gene) order: a stable sort of the record indices by query
@@ -380,7 +349,6 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
         hipLaunchKernelGGL(k_qb_seg_key, grid_m, dim3(256), 0, st, (const uint2 *) w.post.as<uint2>(), (const unsigned long long *) ctl, lay, qk_in);
         PDL_HIP(hipGetLastError());
         pdl_sort_pairs<uint32_t, uint32_t>(c, qk_in, qk_out, pm_in, pm_out, Mq, std::max<uint32_t>(1, bit_length64(nq)), true, d_u, 0, true);
-        QBMatchOut mo{w.desc.as<QDesc>(), w.gkey.as<uint32_t>(), w.row_lookups.as<uint32_t>(), ctl};
         // the segments in the alphabet the chunk is ranked in; re-keyed: Q-rebase over the segment positions, fold and match in two alphabets
         q_with_keys(c, rekey, [&](auto key_b, auto key_q, auto rk) {
             using KeyB = decltype(key_b);
@@ -390,111 +358,50 @@ pdl_query_chunk pdl_run_query_chunk_device(pdl_ctx *c, const uint8_t *residues, 
                                (const uint2 *) w.post.as<uint2>(), (const uint32_t *) pm_out, (const uint32_t *) qk_out, (const unsigned long long *) ctl, lay,
                                w.srank.as<KeyQ>(), w.spost.as<uint2>(), w.seg_off.as<uint32_t>());
             PDL_HIP(hipGetLastError());
-            if constexpr (RK) pdl_query_rebase(c, w.srank.p, nullptr, ctl + QBG_RECORDS, Mq);
+            if constexpr (RK) pdl_query_rebase(c, w.srank.p, nullptr, ctl + Q_RUN_RECORDS, Mq);
             const QBView<KeyB, KeyQ, RK> v = qb_view<KeyB, KeyQ, RK>(c, qk_out);
             hipLaunchKernelGGL((k_qb_fold<KeyB, KeyQ, RK>), dim3((nq + 63) / 64), dim3(64), 0, st, v, nq, ctl, w.folds.as<QFold>());
             hipLaunchKernelGGL((k_qb_match<KeyB, KeyQ, RK>), grid_m, dim3(256), 0, st, v, (const QFold *) w.folds.as<QFold>(), lay, mo, Mq);
         });
         PDL_HIP(hipGetLastError());
-        // each gene's records in rank order: a stable sort of the segment positions by chunk gene
-        uint32_t *gk_in = w.gkey.as<uint32_t>(), *gk_out = gk_in + Mq;
-        uint32_t *ix_in = w.rec_sorted.as<uint32_t>(), *ix_out = ix_in + Mq;
-        pdl_sort_pairs<uint32_t, uint32_t>(c, gk_in, gk_out, ix_in, ix_out, Mq, std::max<uint32_t>(1, bit_length64(NT)), true, d_u, 0, true);
-        hipLaunchKernelGGL(k_qb_row_off, dim3((NT + 1 + 255) / 256), dim3(256), 0, st, (const uint32_t *) gk_out, ctl, lay, N, w.row_off.as<uint32_t>(),
-                           (const uint32_t *) w.row_lookups.as<uint32_t>(), QJ_LIMIT, w.rowid.as<uint32_t>());
-        PDL_HIP(hipGetLastError());
-        rec_sorted = ix_out;
-    }
-    std::vector<uint64_t> h_ctl(ctl_words);
-    q_read_words(c, spans, ctl, ctl_words, h_ctl.data());
-    auto hq = [&](uint32_t q, uint32_t word) -> uint64_t { return h_ctl[QBG_WORDS + (size_t) q * QB_CTL_WORDS + word]; };
-    for (uint32_t q = 0; q < nq; q++)
-        if (hq(q, QB_CTL_BAD_BYTE)) {
-            char who[48];
-            snprintf(who, sizeof(who), "query %u:", qa + q);
-            pdl_fail_absent_byte(hq(q, QB_CTL_BAD_BYTE), who);
-        }
-    const uint64_t Ut = h_ctl[QBG_RECORDS];
-    uint64_t bound = 0, may_overflow = 0;
-    for (uint32_t q = 0; q < nq; q++) { bound += hq(q, QB_CTL_BOUND); may_overflow += hq(q, QB_CTL_MAY_OVERFLOW); }
-    if (bound >= 0xffffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "%llu candidate cells exceed 32-bit cell positions", (unsigned long long) bound);
-
-    // B-join, B-order
-    const size_t ms_floats = (size_t) NT * G1, cm_floats = (size_t) nq * N + NT;
-    w.MS.alloc(ms_floats * 4); w.CM.alloc(cm_floats * 4);
-    PDL_HIP(hipMemsetAsync(w.MS.p, 0, ms_floats * 4, st));
-    PDL_HIP(hipMemsetAsync(w.CM.p, 0, cm_floats * 4, st));
-    const uint64_t cap = std::max<uint64_t>(bound, 1);
-    uint64_t Z = 0;
-    pdl_query_chunk ch;
-    ch.nq = nq; ch.genes = NT; ch.cap = cap;
-    ch.gene_begin.assign(s.gbeg.begin(), s.gbeg.begin() + nq + 1);
-    ch.cells.assign(nq, 0); ch.records.resize(nq); ch.matched.resize(nq); ch.cost.resize(nq);
-    if (Ut) {
-        w.row_base.alloc(NT * 4ull); w.row_cnt.alloc(NT * 4ull); w.fin_off.alloc((NT + 1) * 4ull); w.overflow.alloc(NT * 4ull);
-        w.st.alloc(cap * 20); w.cells.alloc(cap * 20);
-        QBJoinArgs b{};
-        QJoinArgs &a = b.a;
-        b.lay = lay; b.hbm_cols = hbm_cols;
-        a = q_join_args(c, w.st.as<float>(), cap);          // (a.n stays 0: qb_row_args sets it per row)
-        a.qpost = w.spost.as<uint2>(); a.desc = w.desc.as<QDesc>(); a.rec_sorted = rec_sorted; a.row_off = w.row_off.as<uint32_t>();
-        a.kseq_q = w.kseq.as<uint32_t>(); a.MS = w.MS.as<float>(); a.CM = w.CM.as<float>();
-        a.row_base = w.row_base.as<uint32_t>(); a.row_cnt = w.row_cnt.as<uint32_t>();
-        a.cell_cursor = ctl + QBG_CELL_CURSOR; a.overflow_rows = w.overflow.as<uint32_t>(); a.n_overflow = ctl + QBG_OVERFLOW_ROWS;
-        hipLaunchKernelGGL(k_qb_join, dim3(NT), dim3(QJ_T), 0, st, b);
-        PDL_HIP(hipGetLastError());
-        // (tables laid out for the batch's widest union, which every query's columns fit)
-        if (may_overflow) q_join_hbm_tier(c, spans, a.n_overflow, hbm_cols, [&](uint8_t *hbm, uint32_t W) {
-            a.hbm = hbm;
-            hipLaunchKernelGGL(k_qb_join_hbm, dim3(W), dim3(QJ_T), 0, st, b);
+        // (the records are segment positions now; every row's id in its own union comes with the offsets)
+        rec_sorted = q_gene_rows(c, w, run, [&](const uint32_t *gene_sorted) {
+            hipLaunchKernelGGL(k_qb_row_off, dim3((NT + 1 + 255) / 256), dim3(256), 0, st, gene_sorted, ctl, lay, N, w.row_off.as<uint32_t>(),
+                               (const uint32_t *) w.row_lookups.as<uint32_t>(), QJ_LIMIT, w.rowid.as<uint32_t>());
         });
-        q_order_rows(c, a, w.fin_off.as<uint32_t>(), w.rowid.as<uint32_t>(), w.cells.as<float>(), NT, cap, (uint64_t) N + n_max, ctl + QBG_EMITTED, ctl + QBG_WIDE_ROWS);
-        hipLaunchKernelGGL(k_qb_counts, dim3((nq + 63) / 64), dim3(64), 0, st, (const uint32_t *) w.fin_off.as<uint32_t>(), lay, ctl);
-        PDL_HIP(hipGetLastError());
-        q_read_words(c, spans, ctl, ctl_words, h_ctl.data(), false);       // the per-query counts (and the cursors beside them): one read
-        const uint64_t staged = h_ctl[QBG_CELL_CURSOR];
-        Z = h_ctl[QBG_EMITTED];
-        if (Z > bound || staged > bound) PDL_FAIL(PDL_ERR_DEVICE, "query batch join: %llu cells staged, bound %llu", (unsigned long long) staged, (unsigned long long) bound);
-        c->qj_call.rows += NT; c->qj_call.may_overflow_rows += may_overflow; c->qj_call.overflow_rows += h_ctl[QBG_OVERFLOW_ROWS];
-    } else {
-        spans.end();
     }
-    ch.Z = Z;
-    if (rekey) q_rekey_report(c, Ut, Mq != 0);
-    for (uint32_t q = 0; q < nq; q++) {
-        ch.cells[q] = Ut ? hq(q, QB_CTL_EMITTED) : 0;
-        ch.records[q] = hq(q, QB_CTL_RECORDS); ch.matched[q] = hq(q, QB_CTL_MATCHED); ch.cost[q] = hq(q, QB_CTL_COST);
-    }
-    return ch;
+    // the look, B-join, B-order: a row's arguments are those of its gene's query (qb_row_args); cells per query behind the order
+    return q_join_and_order(c, w, run, w.spost.as<uint2>(), rec_sorted,
+        [&](const QJoinArgs &a) { hipLaunchKernelGGL(k_qb_join, dim3(NT), dim3(QJ_T), 0, st, QBJoinArgs{a, lay, hbm_cols}); },
+        [&](const QJoinArgs &a, uint32_t W) { hipLaunchKernelGGL(k_qb_join_hbm, dim3(W), dim3(QJ_T), 0, st, QBJoinArgs{a, lay, hbm_cols}); },
+        [&] { hipLaunchKernelGGL(k_qb_counts, dim3((nq + 63) / 64), dim3(64), 0, st, (const uint32_t *) w.fin_off.as<uint32_t>(), lay, ctl); });
 }
 
 // B-copy: the chunk's cells and maxima come over in one piece each (7 copies per chunk, not per query) into pinned host
 // memory — a DMA, no staging by the runtime — then every query's block is cut out on the host.  Appends the blocks to
 // out[qa..) / info (a failure leaves the freeing to the caller).
-static void qb_copy_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa, const pdl_query_chunk &ch, pdl_scores *out, pdl_query_info *info,
+static void qb_copy_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t qa, const pdl_query_cells &ch, pdl_scores *out, pdl_query_info *info,
                           float *device_ms) {
     hipStream_t st = c->stream;
-    auto &w = c->qbb;
+    PinBuf &stage = c->qbb.stage;
     const uint32_t N = c->N, G1 = c->G + 1, nq = ch.nq;
     const uint64_t Z = ch.Z, cap = ch.cap;
     const size_t ms_floats = (size_t) ch.genes * G1, cm_floats = (size_t) nq * N + ch.genes;
     const size_t stage_words = (size_t) Z * 5 + ms_floats + cm_floats;
-    w.stage.alloc(stage_words * 4);
-    const uint32_t *h_cells = reinterpret_cast<const uint32_t *>(w.stage.p);
-    const float *h_ms = reinterpret_cast<const float *>(w.stage.p) + (size_t) Z * 5, *h_cm = h_ms + ms_floats;
-    if (Z) {
-        const float *cf = w.cells.as<float>();
-        for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(w.stage.p + (size_t) i * Z * 4, cf + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
-    }
-    PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_ms), w.MS.p, ms_floats * 4, hipMemcpyDeviceToHost, st));
-    PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_cm), w.CM.p, cm_floats * 4, hipMemcpyDeviceToHost, st));
+    stage.alloc(stage_words * 4);
+    const uint32_t *h_cells = reinterpret_cast<const uint32_t *>(stage.p);
+    const float *h_ms = reinterpret_cast<const float *>(stage.p) + (size_t) Z * 5, *h_cm = h_ms + ms_floats;
+    if (Z)
+        for (int i = 0; i < 5; i++) PDL_HIP(hipMemcpyAsync(stage.p + (size_t) i * Z * 4, ch.cells + (size_t) i * cap, Z * 4, hipMemcpyDeviceToHost, st));
+    PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_ms), ch.MS, ms_floats * 4, hipMemcpyDeviceToHost, st));
+    PDL_HIP(hipMemcpyAsync(const_cast<float *>(h_cm), ch.CM, cm_floats * 4, hipMemcpyDeviceToHost, st));
     PDL_HIP(hipStreamSynchronize(st));
-    const float ms_total = w.spans.total_ms();
+    const float ms_total = ch.device_ms();
     *device_ms += ms_total;
     uint64_t z0 = 0;
     for (uint32_t q = 0; q < nq; q++) {
         const QBQuery &Q = qs[qa + q];
-        const uint64_t Zq = ch.cells[q];
+        const uint64_t Zq = ch.cells_of[q];
         const uint32_t n = Q.n, NC = N + n;
         if (z0 + Zq > Z) PDL_FAIL(PDL_ERR_DEVICE, "query batch: the queries' cells (%llu) pass the emitted total %llu", (unsigned long long) (z0 + Zq), (unsigned long long) Z);
         pdl_scores &r = out[qa + q];                             // (filled in place: a throw leaves what is allocated to the caller's pdl_free_scores)
@@ -505,13 +412,7 @@ static void qb_copy_chunk(pdl_ctx *c, const std::vector<QBQuery> &qs, uint32_t q
         memcpy(r.max_genome_score_col, h_cm + (size_t) q * N + ch.gene_begin[q], (size_t) NC * 4);
         q_block_ids(c, r);
         z0 += Zq;
-        if (info) {
-            pdl_query_info &fi = info[qa + q];
-            memset(&fi, 0, sizeof(fi));
-            fi.residues = Q.Rq; fi.kmer_occurrences = Q.Mq; fi.records = ch.records[q]; fi.matched_records = ch.matched[q];
-            fi.genome_cost = ch.cost[q];
-            fi.device_ms = ms_total / (float) nq;
-        }
+        if (info) ch.info_of(q, Q.Rq, Q.Mq, ms_total / (float) nq, &info[qa + q]);
     }
 }
 
@@ -562,7 +463,7 @@ void pdl_run_query_batch(pdl_ctx *c, const uint8_t *residues, const uint64_t *of
     uint32_t chunks = 0;
     for (uint32_t qa = 0; qa < n_queries;) {
         const uint32_t qe = pdl_query_batch_chunk_end(c, qs, qa);
-        const pdl_query_chunk ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);
+        const pdl_query_cells ch = pdl_run_query_chunk_device(c, residues, offsets, qs, qa, qe, hbm_cols);
         qb_copy_chunk(c, qs, qa, ch, out, info, &device_ms);
         chunks++;
         qa += ch.nq;                                              // (option "query_rekey" may have cut the chunk short of qe)

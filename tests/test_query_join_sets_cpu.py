@@ -31,7 +31,7 @@ def test_the_constants_are_the_kernels():
     # the limit is read before the atomicCAS, by up to QJ_T threads at once: MUST_LEAVE rests on this line
     assert re.search(r"if \(\*\(volatile uint32_t \*\) &s_nkeys >= QJ_LIMIT\) return false;\s*\n\s*const uint32_t old = atomicCAS", text)
     # the prefilter holds a row's lookups against the same limit, in the single query and in the batch
-    assert re.search(r"row_lookups\[g\] > limit", text) and text.count("QJ_LIMIT, ctl + Q_CTL_BOUND") == 1
+    assert re.search(r"row_lookups\[g\] > limit", text) and text.count("QJ_LIMIT, qctl + Q_QRY_BOUND") == 1
     assert "QJ_LIMIT, w.rowid" in (CSRC / "pdl_query_batch.h").read_text()
     # the guard in front of the accumulator's 21-bit fields, at both doors
     assert f"<< {S.FIELD_BITS})" in text and "<< 42)" in text
