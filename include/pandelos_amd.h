@@ -676,6 +676,10 @@ PDL_API int pdl_get_timings(pdl_ctx *, pdl_timings *out);
  * (default 1: the offsets of a radix pass come from one launch, a workgroup per digit, and the kernel that ranks the k-mers files
  * the rank sort's first histogram — whole-stream single-GPU builds with exact ranks, tables of at most 65 536 tiles, "onepass_scan"
  * off; 0: a histogram kernel and a three-launch scan for every pass.  Same results either way: for parity tests and A/B timing),
+ * "lean_records" 0|1 (default 1: the passes of a build that run once over the sorted k-mers and over the records load each of them
+ * once and take a neighbour's value from the neighbouring lane — the run-length pass in kernels of its own, the range count on bit
+ * masks — and the one-workgroup launch in the middle of a three-launch scan stages its sums through LDS; 0: the former kernels.
+ * Same results either way: for parity tests and A/B timing),
  * "order_offsets" 0|1|2 (default 2: the cell offsets of a scoring pass with upper-triangle range lists come from one launch of
  * several workgroups; 1: of one workgroup; 0: from two prefix scans, four launches.  Same results: for parity tests and A/B timing),
  * "order_offsets_rows" n (that launch serves at most n task rows, default and maximum 131 072; tests lower it),
@@ -805,7 +809,7 @@ PDL_API uint32_t pdl_pin_checksum(const uint32_t *payload, const uint32_t *dst_w
 
 /* Test hooks of the generic device primitives (pandelos_amd/csrc/pdl_hooks.hip): each runs one primitive as the library calls
  * it, on the caller's device buffers, on the context's stream, and waits for it.  The form taken follows the options
- * onepass_scan and lean_radix.  For a context that holds no build: PDL_ERR_STATE on one that does (the scratch buffers the hooks
+ * onepass_scan, lean_radix and lean_records.  For a context that holds no build: PDL_ERR_STATE on one that does (the scratch buffers the hooks
  * grow are the build's); PDL_ERR_ARGUMENT for a NULL where a pointer is needed or a width that is not listed.
  *
  * pdl_test_scan: scan_and_apply over d_flags[0 .. min(*d_n, n_bound)) — d_prefix[i] = exclusive prefix, d_seen_flag[i] = the flag

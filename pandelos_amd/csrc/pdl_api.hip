@@ -917,6 +917,7 @@ int pdl_set_option(pdl_ctx *c, const char *name, int64_t value) {
     else if (n == "aside_test_reload") c->opt_aside_test_reload = value != 0;
     else if (n == "onepass_scan") c->opt_onepass_scan = value != 0;
     else if (n == "lean_radix") c->opt_lean_radix = value != 0;
+    else if (n == "lean_records") c->opt_lean_records = value != 0;
     else if (n == "order_offsets") {
         if (value < 0 || value > 2) PDL_FAIL(PDL_ERR_ARGUMENT, "order_offsets: 0 (two scans), 1 (one workgroup) or 2 (several)");
         c->opt_order_offsets = (int) value;

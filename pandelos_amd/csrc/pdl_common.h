@@ -39,6 +39,18 @@ __device__ __forceinline__ void pdl_sync() {
 #endif
     __syncthreads();
 }
+// A lane's neighbour in the wave without a trip through the LDS crossbar: one DPP move (wave_shr:1 / wave_shl:1, gfx9).
+// wave_prev_u32: lane l > 0 gets lane l - 1's v, lane 0 gets `first`; wave_next_u32: lane l < 63 gets lane l + 1's v, lane 63
+// gets `last`.  Called with all 64 lanes active.
+__device__ __forceinline__ uint32_t wave_prev_u32(uint32_t v, uint32_t first) {
+    return (uint32_t) __builtin_amdgcn_update_dpp((int) first, (int) v, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint32_t wave_next_u32(uint32_t v, uint32_t last) {
+    return (uint32_t) __builtin_amdgcn_update_dpp((int) last, (int) v, 0x130, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint64_t wave_prev_u64(uint64_t v, uint64_t first) {
+    return (uint64_t) wave_prev_u32((uint32_t) (v >> 32), (uint32_t) (first >> 32)) << 32 | wave_prev_u32((uint32_t) v, (uint32_t) first);
+}
 #endif
 
 // ---- layout of the control block (pdl_ctx::scalars, u64 words): totals [16] | residue histogram [256] | per-genome cost ------
@@ -512,6 +524,7 @@ struct pdl_ctx {
     bool opt_order_wide_merged = true;    // ... with the wide rows' workgroups behind them in the same launch; 0: k_order_rows in a launch of its own
     int opt_fused_glue = 1;               // small launches that share one: row descriptors + clearing (scoring), K-cost + K-seq-offsets (build); n > 1: also K-len with the control block's clearing, for up to min(n, KL_MAX_GENES) genes (measured: does not pay); 0: each its own
     bool opt_lean_radix = true;          // radix passes: offsets in one launch (k_rs_offsets), the rank sort's first histogram filed by K-rank; 0: a histogram and a three-launch scan per pass
+    bool opt_lean_records = true;        // the build's record passes load each k-mer once: K-rle in kernels of its own (k_rle_tile_sums / k_rle_apply), the middle launch of a three-launch scan with its sums staged through LDS (k_scan_tile_scan_lds); 0: the former kernels
     DevBuf scratch;       // transient buffers of the range build
     DevBuf scalars;       // control block, u64: totals [16] | residue histogram [256] | per-genome cost [G] (PDL_CTL_*, above)
 

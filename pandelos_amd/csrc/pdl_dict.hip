@@ -6,7 +6,7 @@
 //   K-len     k_kseq_len          kseq_lengths + k-mer stream offsets        library.cpp:250-262
 //   K-rank    k_rank / k_rank_hash   per-gene k-mer ranks                    library.cpp:75-86,134-150
 //   K-sort    pdl_sort_pairs      stable LSD radix sort by rank              library.cpp:172-187,270-278
-//   K-rle     RecHead/RecScatter scan (records built in the apply)   dedup -> (rank,gene,count)   library.cpp:280-287
+//   K-rle     k_rle_tile_sums / k_rle_apply (or RecHead/RecScatter through the generic scan)   dedup -> (rank,gene,count)   library.cpp:280-287
 //   K-groups  k_fold_last_record, then per tile from the head bits: costs / count / write (pdl_groups.h)   library.cpp:297-335
 //   K-ranges  k_group_write or k_range_scatter (ranges), sort by gene, k_gather_ranges (+ per-gene cost), k_seq_offsets   library.cpp:312-327
 //   K-cost    k_genome_cost       per-genome and total lookups               library.cpp:337-350,535-538
@@ -450,6 +450,162 @@ template <class KeyT> struct RecScatter {
     }
 };
 
+// K-rle in kernels of its own (option "lean_records"): key and value of a k-mer are loaded ONCE per pass, where RecHead and
+// RecScatter behind the generic scan load nine words per k-mer.  A wave owns RLE_ROUNDS x 64 consecutive k-mers and reads them
+// 64 at a time (lane l, round j: k-mer w0 + 64 j + l — 256 contiguous bytes per load, and the heads of a round go out as one
+// contiguous run of records; four consecutive k-mers per lane with 16-byte loads would split every store instruction into 64
+// separate 8- and 4-byte pieces four records apart).  The predecessor's key and value come from the lane below by a DPP move,
+// for lane 0 from lane 63 of the round before, for the wave's first k-mer from one extra load.  "My successor repeats me" needs
+// no key: a lane keeps its eight head bits in one word, ONE DPP move hands down the word of the lane above, lane 63 takes lane
+// 0's shifted by a round, and the k-mer behind the wave is one extra load
+// compared with lane 63's.  The prefix of a head is (heads of the tiles, waves and rounds before: scalars) + mbcnt of its
+// round's ballot: no flag and no prefix goes through LDS.  rle_wave_heads is the body both kernels share.
+constexpr int RLE_ROUNDS = 8, RLE_WAVES = SCAN_THREADS / PDL_WAVE;
+constexpr uint32_t RLE_SPAN = RLE_ROUNDS * PDL_WAVE, RLE_TILE = RLE_WAVES * RLE_SPAN;
+static_assert(RLE_TILE == (uint32_t) SCAN_TILE, "K-rle's tile sums are scanned like any scan's");
+
+__device__ __forceinline__ uint32_t wave_prev_key(uint32_t v, uint32_t first) { return wave_prev_u32(v, first); }
+__device__ __forceinline__ uint64_t wave_prev_key(uint64_t v, uint64_t first) { return wave_prev_u64(v, first); }
+__device__ __forceinline__ uint32_t lane63_of(uint32_t v) { return (uint32_t) __builtin_amdgcn_readlane((int) v, PDL_WAVE - 1); }
+__device__ __forceinline__ uint64_t lane63_of(uint64_t v) { return (uint64_t) lane63_of((uint32_t) (v >> 32)) << 32 | lane63_of((uint32_t) v); }
+
+// The wave's k-mers [w0, w0 + RLE_SPAN) of the m in the stream (w0 < m): key[j], val[j] of this lane's k-mer of round j (index
+// clamped to m - 1), mh[j] = ballot of "is a record head" (false past m), heads = the lane's own bits of those (bit j: round j);
+// returns bit j = the k-mer opens a rank-group.
+template <class KeyT>
+__device__ __forceinline__ uint32_t rle_wave_heads(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t w0, uint64_t m, uint32_t lane,
+                                                   KeyT (&key)[RLE_ROUNDS], uint32_t (&val)[RLE_ROUNDS], unsigned long long (&mh)[RLE_ROUNDS], uint32_t &heads) {
+    const uint32_t rem = (uint32_t) min(m - w0, (uint64_t) RLE_SPAN);            // live k-mers of the wave
+    const uint64_t qp = w0 ? w0 - 1 : 0;
+    KeyT kfirst = keys[qp];                                                      // the predecessor of the wave's first k-mer (uniform)
+    uint32_t vfirst = vals[qp];
+    const KeyT *kw = keys + w0;                                                  // (uniform bases, 32-bit lane offsets)
+    const uint32_t *vw = vals + w0;
+#pragma unroll
+    for (int j = 0; j < RLE_ROUNDS; j++) {                                       // all loads first, branch-free
+        const uint32_t e = j * PDL_WAVE + lane;
+        const uint32_t ec = e < rem ? e : rem - 1;
+        key[j] = kw[ec]; val[j] = vw[ec];
+    }
+    uint32_t rank_heads = 0;
+    heads = 0;
+#pragma unroll
+    for (int j = 0; j < RLE_ROUNDS; j++) {
+        const uint32_t e = j * PDL_WAVE + lane;
+        const KeyT kprev = wave_prev_key(key[j], kfirst);
+        const uint32_t vprev = wave_prev_u32(val[j], vfirst);
+        const bool rank_head = (w0 == 0 && e == 0) || kprev != key[j];
+        const bool head = e < rem && (rank_head || vprev != val[j]);
+        mh[j] = __ballot(head);
+        rank_heads |= (uint32_t) rank_head << j;
+        heads |= (uint32_t) head << j;
+        kfirst = lane63_of(key[j]); vfirst = lane63_of(val[j]);
+    }
+    return rank_heads;
+}
+
+template <class KeyT>
+__global__ __launch_bounds__(SCAN_THREADS) void k_rle_tile_sums(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t m,
+                                                                uint32_t *__restrict__ tile_sums) {
+    __shared__ uint32_t s_wt[RLE_WAVES];
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1), wave = threadIdx.x / PDL_WAVE;
+    const uint64_t w0 = (uint64_t) blockIdx.x * RLE_TILE + (uint64_t) wave * RLE_SPAN;
+    uint32_t cnt = 0;
+    if (w0 < m) {                                                                // (wave-uniform)
+        KeyT key[RLE_ROUNDS]; uint32_t val[RLE_ROUNDS]; unsigned long long mh[RLE_ROUNDS];
+        uint32_t heads;
+        (void) rle_wave_heads(keys, vals, w0, m, lane, key, val, mh, heads);
+#pragma unroll
+        for (int j = 0; j < RLE_ROUNDS; j++) cnt += (uint32_t) __popcll(mh[j]);
+    }
+    if (lane == 0) s_wt[wave] = cnt;
+    pdl_sync();
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int w = 0; w < RLE_WAVES; w++) total += s_wt[w];
+        tile_sums[blockIdx.x] = total;
+    }
+}
+
+// recpos[u] = position of record u's first k-mer, post[u] = {gene, run | head of a rank-group << 31}: what RecScatter writes.
+// INLINE_PREFIX as in k_scan_apply: tile_sums holds the raw sums and the workgroup adds up the ones before its own.
+template <class KeyT, bool INLINE_PREFIX>
+__global__ __launch_bounds__(SCAN_THREADS) void k_rle_apply(const KeyT *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t m,
+                                                            const uint32_t *__restrict__ tile_sums, uint32_t *__restrict__ recpos, uint2 *__restrict__ post,
+                                                            uint64_t *d_total, uint64_t *d_total2) {
+    __shared__ uint32_t s_wt[RLE_WAVES];
+    __shared__ uint32_t s_wave[17];
+    const uint32_t lane = threadIdx.x & (PDL_WAVE - 1), wave = threadIdx.x / PDL_WAVE;
+    uint32_t tile_prefix = 0;
+    if constexpr (INLINE_PREFIX) {
+        const uint32_t upto = blockIdx.x == 0 ? gridDim.x : blockIdx.x;          // workgroup 0 adds up everything: the total
+        uint32_t part = 0;
+        for (uint32_t i = threadIdx.x; i < upto; i += SCAN_THREADS) part += tile_sums[i];
+        uint32_t all;
+        (void) block_exclusive_scan_u32(part, s_wave, all);
+        if (blockIdx.x == 0) { if (threadIdx.x == 0) scan_write_totals(all, d_total, d_total2); }
+        else tile_prefix = all;
+    } else {
+        tile_prefix = tile_sums[blockIdx.x];
+    }
+    const uint64_t w0 = (uint64_t) blockIdx.x * RLE_TILE + (uint64_t) wave * RLE_SPAN;
+    const bool live_wave = w0 < m;                                               // (wave-uniform)
+    KeyT key[RLE_ROUNDS]; uint32_t val[RLE_ROUNDS]; unsigned long long mh[RLE_ROUNDS];
+    uint32_t rank_heads = 0, heads = 0, cnt = 0;
+    bool last_repeats = false;                                                   // the k-mer behind the wave's last repeats it (uniform)
+    if (live_wave) {
+        const uint64_t qn = w0 + RLE_SPAN;
+        const bool has_next = qn < m;
+        const KeyT knext = keys[has_next ? qn : m - 1];
+        const uint32_t vnext = vals[has_next ? qn : m - 1];
+        rank_heads = rle_wave_heads(keys, vals, w0, m, lane, key, val, mh, heads);
+        last_repeats = has_next && knext == lane63_of(key[RLE_ROUNDS - 1]) && vnext == lane63_of(val[RLE_ROUNDS - 1]);
+#pragma unroll
+        for (int j = 0; j < RLE_ROUNDS; j++) cnt += (uint32_t) __popcll(mh[j]);
+    }
+    if (lane == 0) s_wt[wave] = cnt;
+    pdl_sync();
+    if (!live_wave) return;
+    uint32_t at0 = tile_prefix;                                                  // records before the wave's first k-mer
+#pragma unroll
+    for (int w = 0; w < RLE_WAVES; w++) at0 += w < (int) wave ? s_wt[w] : 0u;
+    // bit j: the successor of this lane's k-mer of round j is a head — the lane above holds it; lane 63: lane 0's next round, or
+    // the k-mer behind the wave — or the end of the stream
+    const uint32_t first_heads = (uint32_t) __builtin_amdgcn_readfirstlane((int) heads);
+    uint32_t next_heads = wave_next_u32(heads, first_heads >> 1 | (last_repeats ? 0u : 1u) << (RLE_ROUNDS - 1));
+    const uint32_t remn = (uint32_t) min(m - w0, (uint64_t) RLE_SPAN + 1);       // k-mer e of the wave has a successor iff e + 1 < remn
+    if (remn <= RLE_SPAN) {                                                      // (uniform) the stream ends in this wave
+#pragma unroll
+        for (int j = 0; j < RLE_ROUNDS; j++) next_heads |= (uint32_t) (j * PDL_WAVE + lane + 1 >= remn) << j;
+    }
+    uint32_t run[RLE_ROUNDS];
+#pragma unroll
+    for (int j = 0; j < RLE_ROUNDS; j++) run[j] = 1;
+    const uint32_t walks = heads & ~next_heads;                                  // a k-mer repeated inside its gene: the head walks its run
+    if (walks) {                                                                 // (rare; its loads stand before every store)
+#pragma unroll
+        for (int j = 0; j < RLE_ROUNDS; j++) {
+            if ((walks >> j) & 1u) {
+                const uint64_t q = w0 + j * PDL_WAVE + lane;
+                uint64_t jx = q + 2;
+                while (jx < m && keys[jx] == key[j] && vals[jx] == val[j]) jx++;
+                run[j] = (uint32_t) (jx - q);
+            }
+        }
+    }
+    const uint32_t q0 = (uint32_t) w0 + lane;                                    // (stream positions fit 32 bits: recpos)
+#pragma unroll
+    for (int j = 0; j < RLE_ROUNDS; j++) {
+        if ((heads >> j) & 1u) {
+            const uint32_t at = at0 + __builtin_amdgcn_mbcnt_hi((uint32_t) (mh[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mh[j], 0u));
+            recpos[at] = q0 + j * PDL_WAVE;
+            post[at] = make_uint2(val[j], run[j] | ((rank_heads >> j) & 1u) << 31);
+        }
+        at0 += (uint32_t) __popcll(mh[j]);
+    }
+}
+
 // Interval selection of the multi-GPU build: the k-mers whose rank falls into this GPU's bins, in stream order.
 template <class KeyT> struct SelFlag {
     const KeyT *keys; uint32_t shift, b_lo, b_hi;
@@ -714,6 +870,29 @@ static bool stage_rank(pdl_ctx *c, uint32_t *d_bins = nullptr, uint32_t bin_shif
     return false;
 }
 
+// K-rle of the sorted stream (keys, vals)[0 .. m): recpos, post and the record count at d_total.  Three launches (two for a
+// short stream), as the generic scan it replaces under option "lean_records".
+template <class KeyT>
+static void rle_records(pdl_ctx *c, const KeyT *keys, const uint32_t *vals, uint64_t m, uint32_t *recpos, uint2 *post, uint64_t *d_total) {
+    if (!c->opt_lean_records || c->opt_onepass_scan || m == 0) {
+        scan_and_apply(c, m, RecHead<KeyT>{keys, vals}, RecScatter<KeyT>{keys, vals, m, recpos, post}, d_total);
+        return;
+    }
+    const uint64_t tiles64 = (m + RLE_TILE - 1) / RLE_TILE;
+    if (tiles64 > 0x7fffffffull) PDL_FAIL(PDL_ERR_UNSUPPORTED, "scan of %llu elements exceeds the grid limit", (unsigned long long) m);
+    const uint32_t tiles = (uint32_t) tiles64;
+    c->scan_tmp.alloc((size_t) tiles * sizeof(uint32_t));
+    uint32_t *ts = c->scan_tmp.as<uint32_t>();
+    hipLaunchKernelGGL(k_rle_tile_sums<KeyT>, dim3(tiles), dim3(SCAN_THREADS), 0, c->stream, keys, vals, m, ts);
+    if (tiles <= SCAN_INLINE_TILES) {
+        hipLaunchKernelGGL((k_rle_apply<KeyT, true>), dim3(tiles), dim3(SCAN_THREADS), 0, c->stream, keys, vals, m, (const uint32_t *) ts, recpos, post, d_total, (uint64_t *) nullptr);
+    } else {
+        launch_tile_scan(c, ts, tiles, d_total, nullptr);
+        hipLaunchKernelGGL((k_rle_apply<KeyT, false>), dim3(tiles), dim3(SCAN_THREADS), 0, c->stream, keys, vals, m, (const uint32_t *) ts, recpos, post, d_total, (uint64_t *) nullptr);
+    }
+    PDL_HIP(hipGetLastError());
+}
+
 // K-rle over the sorted stream (keys_b, vals_b)[0 .. m): records into c->post / recpos, their count into scalars[PDL_CTL_RECORDS].
 template <class KeyT>
 static void stage_dedup(pdl_ctx *c, uint64_t m) {
@@ -723,8 +902,7 @@ static void stage_dedup(pdl_ctx *c, uint64_t m) {
     ev_begin(c, EV_DICT);                                       // (ended by the caller, behind K-groups where it runs them)
     c->recpos.alloc((m + 1) * sizeof(uint32_t));
     c->post.alloc(m * sizeof(uint2));                           // U <= m records (sized before U is known)
-    scan_and_apply(c, m, RecHead<KeyT>{skeys, svals},
-                   RecScatter<KeyT>{skeys, svals, m, c->recpos.as<uint32_t>(), c->post.as<uint2>()}, d_scal + PDL_CTL_RECORDS);
+    rle_records<KeyT>(c, skeys, svals, m, c->recpos.as<uint32_t>(), c->post.as<uint2>(), d_scal + PDL_CTL_RECORDS);
 }
 
 // K-sort + K-rle over the first m elements of (keys_in, vals_in): records into c->post / recpos.
@@ -904,7 +1082,8 @@ static void build_ranges(pdl_ctx *c, GroupTileArgs &ga, uint32_t grid, int mode,
             uint32_t *counts = c->sort_tmp.as<uint32_t>(), *offs = counts + table, *digit_total = offs + table;
             ga.tile_sums = digit_total + PDL_RADIX_BINS; ga.th_first = ga.tile_sums + tiles; ga.th_last = ga.th_first + tiles; ga.chunk_sums = nullptr;
             const uint32_t grid4 = std::max<uint32_t>(1, std::min<uint32_t>(n_tiles4, (uint32_t) c->cus * 8));
-            hipLaunchKernelGGL(k_range_count_hist, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
+            if (c->opt_lean_records) hipLaunchKernelGGL(k_range_count_hist<true>, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
+            else hipLaunchKernelGGL(k_range_count_hist<false>, dim3(grid4), dim3(GW_THREADS), 0, st, ga, n_tiles4, counts);
             const uint32_t *totals = pdl_radix_offsets(c, counts, offs, n_tiles4, d_scal + PDL_CTL_RANGES, digit_total);
             hipLaunchKernelGGL(k_range_scatter, dim3(n_tiles4), dim3(GW_THREADS), 0, st, ga, n_tiles4, offs, b.k2b, b.pay_b, totals, d_scal + PDL_CTL_RANGES);
             PDL_HIP(hipGetLastError());
@@ -1138,7 +1317,7 @@ const void *pdl_query_dictionary(pdl_ctx *c, const RankParams &rp, bool key64, c
         KeyT *keys_in = static_cast<KeyT *>(keys_a), *keys_out = static_cast<KeyT *>(keys_b);
         rank_new_genes<KeyT>(c, rp, res, off, kmer_off, n, m, n_res, keys_in, vals_a);
         pdl_sort_pairs<KeyT>(c, keys_in, keys_out, vals_a, vals_b, m, rp.rank_bits, false, nullptr, 0, rp.key_bits == rp.rank_bits);
-        scan_and_apply(c, m, RecHead<KeyT>{keys_out, vals_b}, RecScatter<KeyT>{keys_out, vals_b, m, recpos, post}, d_u);
+        rle_records<KeyT>(c, keys_out, vals_b, m, recpos, post, d_u);
         return keys_out;
     });
 }

@@ -123,7 +123,7 @@ struct GroupTileArgs {
 
 // ---- bodies shared by the kernels ------------------------------------------------------------------------------------------
 
-// A tile's sixteen records per lane: all loads first, branch-free.  (costs, write, k_range_scatter; the count loads its own)
+// A tile's sixteen records per lane: all loads first, branch-free.  (costs, write, k_range_scatter, the lean count; the plain count loads its own)
 __device__ __forceinline__ void gt_load_tile(const uint2 *post, uint32_t t0, uint32_t n, uint32_t lane, uint2 (&po)[GW_ROUNDS]) {
 #pragma unroll
     for (int j = 0; j < GW_ROUNDS; j++) {
@@ -167,33 +167,74 @@ __device__ __forceinline__ uint32_t gt_shard_mask(const GroupTileArgs &a, const 
 // the shard]; MODE 0: iff it is not alone in its group.  Leaves the tile's ranges (HIST: each also counted in s_h by the low
 // byte of its gene) and its first / last head for the write pass; n_rec / n_grp / n_rep grow by the shared records, the shared
 // groups and (every eighth tile, a statistic) the records whose k-mer repeats inside its gene.  (k_range_count, k_range_count_hist)
-template <int MODE, bool HIST>
+// LEAN (option "lean_records"): sixteen records of a lane are sixteen BITS.  The successor's head bit is not loaded a second
+// time — the lane above holds it in the same round, lane 0 in the next round for lane 63: ONE DPP move hands over all sixteen;
+// only the tile's last record loads its successor's (17 loads per lane, not 32) — and shared / range / group are mask
+// arithmetic and three popcounts per tile where the plain form spends about forty vector instructions per record.
+template <int MODE, bool HIST, bool LEAN>
 __device__ __forceinline__ void gt_count_tile(const GroupTileArgs &a, uint32_t tile, uint32_t n, uint32_t lane, const uint2 *s_iv, uint32_t n_iv, uint32_t *s_h,
                                               uint32_t &n_rec, uint32_t &n_grp, uint32_t &n_rep) {
     const uint32_t t0 = tile * GW_TILE;
     uint2 po[GW_ROUNDS];
-    uint32_t ynext[GW_ROUNDS];
-#pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {                // all loads first, branch-free
-        const uint32_t u = t0 + j * PDL_WAVE + lane;
-        po[j] = a.post[u < n ? u : n - 1];
-        ynext[j] = a.post[u + 1 < n ? u + 1 : n - 1].y;
-    }
-    const uint32_t ins = gt_shard_mask<MODE>(a, s_iv, n_iv, po);
     uint32_t cnt = 0, first_h = GT_NONE, last_h = 0, any_h = 0;
+    if constexpr (LEAN) {
+        gt_load_tile(a.post, t0, n, lane, po);
+        const uint32_t ub = t0 + GW_TILE;                // the successor of the tile's last record (clamped as every index)
+        const uint32_t ylast = a.post[ub < n ? ub : n - 1].y;
+        const uint32_t ins = gt_shard_mask<MODE>(a, s_iv, n_iv, po);
+        uint32_t headm = 0;                              // bit j: this lane's record of round j opens a group
 #pragma unroll
-    for (int j = 0; j < GW_ROUNDS; j++) {
-        const uint32_t u = t0 + j * PDL_WAVE + lane;
-        const bool live = u < n;
-        const bool head = live && (po[j].y >> 31);
-        const bool next_head = u + 1 >= n || (ynext[j] >> 31);           // the successor opens a group, or is the end
-        const bool shared = live && !(head && next_head);
-        bool r = MODE == 0 ? shared : (live && !next_head);
-        if constexpr (MODE == 0 || MODE == 2) r = r && ((ins >> j) & 1u);
-        if constexpr (HIST) { if (r) atomicAdd(&s_h[po[j].x & (PDL_RADIX_BINS - 1)], 1u); }
-        cnt += r;
-        n_rec += shared; n_grp += head && !next_head;
-        if (head) { first_h = min(first_h, u); last_h = max(last_h, u); any_h = 1; }
+        for (int j = 0; j < GW_ROUNDS; j++) headm |= (po[j].y >> 31) << j;
+        const uint32_t first_lane = (uint32_t) __builtin_amdgcn_readfirstlane((int) headm);
+        uint32_t nextm = wave_next_u32(headm, first_lane >> 1 | (ylast >> 31) << (GW_ROUNDS - 1));      // bit j: its successor does
+        uint32_t livem = (1u << GW_ROUNDS) - 1u;
+        if (ub >= n) {                                   // (uniform) the last tile: records past the end, and the end as a successor
+            livem = 0;
+#pragma unroll
+            for (int j = 0; j < GW_ROUNDS; j++) {
+                const uint32_t u = t0 + j * PDL_WAVE + lane;
+                livem |= (uint32_t) (u < n) << j;
+                nextm |= (uint32_t) (u + 1 >= n) << j;
+            }
+        }
+        const uint32_t head = headm & livem;
+        const uint32_t shared = livem & ~(head & nextm);                      // not alone in its group
+        uint32_t r = MODE == 0 ? shared : livem & ~nextm;
+        if constexpr (MODE == 0 || MODE == 2) r &= ins;
+        if constexpr (HIST) {
+#pragma unroll
+            for (int j = 0; j < GW_ROUNDS; j++) { if ((r >> j) & 1u) atomicAdd(&s_h[po[j].x & (PDL_RADIX_BINS - 1)], 1u); }
+        }
+        cnt = (uint32_t) __builtin_popcount(r);
+        n_rec += (uint32_t) __builtin_popcount(shared); n_grp += (uint32_t) __builtin_popcount(head & ~nextm);
+        if (head) {
+            first_h = t0 + (uint32_t) __builtin_ctz(head) * PDL_WAVE + lane;
+            last_h = t0 + (31u - (uint32_t) __builtin_clz(head)) * PDL_WAVE + lane;
+            any_h = 1;
+        }
+    } else {
+        uint32_t ynext[GW_ROUNDS];
+#pragma unroll
+        for (int j = 0; j < GW_ROUNDS; j++) {            // all loads first, branch-free
+            const uint32_t u = t0 + j * PDL_WAVE + lane;
+            po[j] = a.post[u < n ? u : n - 1];
+            ynext[j] = a.post[u + 1 < n ? u + 1 : n - 1].y;
+        }
+        const uint32_t ins = gt_shard_mask<MODE>(a, s_iv, n_iv, po);
+#pragma unroll
+        for (int j = 0; j < GW_ROUNDS; j++) {
+            const uint32_t u = t0 + j * PDL_WAVE + lane;
+            const bool live = u < n;
+            const bool head = live && (po[j].y >> 31);
+            const bool next_head = u + 1 >= n || (ynext[j] >> 31);       // the successor opens a group, or is the end
+            const bool shared = live && !(head && next_head);
+            bool r = MODE == 0 ? shared : (live && !next_head);
+            if constexpr (MODE == 0 || MODE == 2) r = r && ((ins >> j) & 1u);
+            if constexpr (HIST) { if (r) atomicAdd(&s_h[po[j].x & (PDL_RADIX_BINS - 1)], 1u); }
+            cnt += r;
+            n_rec += shared; n_grp += head && !next_head;
+            if (head) { first_h = min(first_h, u); last_h = max(last_h, u); any_h = 1; }
+        }
     }
     if ((tile & 7u) == 0) {                              // (uniform)
 #pragma unroll
@@ -402,7 +443,7 @@ __global__ __launch_bounds__(256) void k_gene_costs_lazy(const uint2 *__restrict
 // ---- count ---------------------------------------------------------------------------------------------------------------------
 // Per-thread code (the mask arithmetic of the costs / write kernels keeps a wave's uniform values in vector registers and
 // ran at a quarter of the streaming rate).  One wave per tile, tiles dealt round-robin over the waves.
-template <int MODE>
+template <int MODE, bool LEAN>
 __global__ __launch_bounds__(GW_THREADS) void k_range_count(GroupTileArgs a) {
     extern __shared__ unsigned long long s_dyn[];        // shard modes: the intervals
     __shared__ uint32_t s_red[2];
@@ -417,7 +458,7 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_count(GroupTileArgs a) {
     const uint32_t tiles = (n + GW_TILE - 1) / GW_TILE;
     uint32_t n_rec = 0, n_grp = 0, n_rep = 0;
     for (uint32_t tile = gw; tile < tiles; tile += gridDim.x * GW_WAVES)
-        gt_count_tile<MODE, false>(a, tile, n, lane, s_iv, n_iv, nullptr, n_rec, n_grp, n_rep);
+        gt_count_tile<MODE, false, LEAN>(a, tile, n, lane, s_iv, n_iv, nullptr, n_rec, n_grp, n_rep);
     gt_flush_counts<true>(a, s_red, n_rec, n_grp, n_rep);
 }
 
@@ -429,6 +470,7 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_count(GroupTileArgs a) {
 // k_range_scatter makes the ranges as k_group_write<1> does and files them as k_rs_scatter does (ballot ranks, digit-sorted
 // in LDS, coalesced runs out).  Saves the ranges' trip through HBM (12 B written + 16 B read per range) and three launches.
 static_assert(GW_WAVES * GW_TILE == (int) PDL_RADIX_TILE && GW_THREADS == (int) PDL_RADIX_BINS, "a workgroup's four tiles are one tile of the radix pass");
+template <bool LEAN>
 __global__ __launch_bounds__(GW_THREADS) void k_range_count_hist(GroupTileArgs a, uint32_t n_tiles4, uint32_t *__restrict__ counts) {
     __shared__ uint32_t s_h[PDL_RADIX_BINS];
     __shared__ uint32_t s_red[2];
@@ -440,7 +482,7 @@ __global__ __launch_bounds__(GW_THREADS) void k_range_count_hist(GroupTileArgs a
         s_h[tid] = 0;
         pdl_sync();
         const uint32_t tile = blk * GW_WAVES + wave;
-        if (tile * GW_TILE < n) gt_count_tile<1, true>(a, tile, n, lane, nullptr, 0u, s_h, n_rec, n_grp, n_rep);      // (wave-uniform)
+        if (tile * GW_TILE < n) gt_count_tile<1, true, LEAN>(a, tile, n, lane, nullptr, 0u, s_h, n_rec, n_grp, n_rep);      // (wave-uniform)
         pdl_sync();
         counts[(size_t) tid * n_tiles4 + blk] = s_h[tid];
     }
@@ -633,9 +675,12 @@ static void with_range_mode(int mode, F &&f) {
 // count + the scan of the tile counts; their total (the ranges the write pass will make) lands in scalars[PDL_CTL_RANGES]
 static void launch_range_count(pdl_ctx *c, const GroupTileArgs &a, uint32_t grid, int mode) {
     const size_t dyn = (size_t) a.n_own_iv * sizeof(uint2);      // (mode 1: no shard, no intervals)
-    with_range_mode(mode, [&](auto m) { hipLaunchKernelGGL(k_range_count<decltype(m)::value>, dim3(grid), dim3(GW_THREADS), dyn, c->stream, a); });
+    with_range_mode(mode, [&](auto m) {
+        if (c->opt_lean_records) hipLaunchKernelGGL((k_range_count<decltype(m)::value, true>), dim3(grid), dim3(GW_THREADS), dyn, c->stream, a);
+        else hipLaunchKernelGGL((k_range_count<decltype(m)::value, false>), dim3(grid), dim3(GW_THREADS), dyn, c->stream, a);
+    });
     hipLaunchKernelGGL(k_tile_prefix, dim3((a.n_blocks + 3) / 4), dim3(256), 0, c->stream, a.tile_sums, a.d_n, a.n_bound, a.chunk_sums, a.n_blocks);
-    hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, c->stream, a.chunk_sums, a.n_blocks, c->scalars.as<uint64_t>() + PDL_CTL_RANGES, (uint64_t *) nullptr);
+    launch_tile_scan(c, a.chunk_sums, a.n_blocks, c->scalars.as<uint64_t>() + PDL_CTL_RANGES, nullptr);
     PDL_HIP(hipGetLastError());
 }
 static void launch_range_write(pdl_ctx *c, const GroupTileArgs &a, uint32_t grid, int mode) {

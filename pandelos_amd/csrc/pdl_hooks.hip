@@ -1,7 +1,7 @@
 // pdl_hooks.hip — test hooks: the three generic device primitives (scan_and_apply, pdl_scan.h; pdl_radix_offsets and
 // pdl_sort_pairs, pdl_sort.h; pdl_merge_streams, pdl_append.h) on a caller's device buffers, so that a test can hold each of
 // them against numpy at the sizes where they change their code path (tests/primitive_cases.py, tests/test_gpu_primitives.py).
-// The primitives are called as they are; which form runs follows the context's options onepass_scan and lean_radix.
+// The primitives are called as they are; which form runs follows the context's options onepass_scan, lean_radix and lean_records.
 //
 // Every hook: the lock and `guarded` like every other entry point; the context's stream, waited for before the return (as
 // pdl_copy_device does); PDL_ERR_ARGUMENT for a NULL where a pointer is needed or a width that is not instantiated, then

@@ -5,7 +5,7 @@
 // materialised, so the only extra HBM traffic is one u32 per 2048-element tile.
 //
 //   pass 1  k_scan_tile_sums   tile sums of flag(i)                 -> tile_sums[t]
-//   pass 2  k_scan_tile_scan   exclusive scan of the tile sums (one workgroup), total -> *d_total
+//   pass 2  k_scan_tile_scan   exclusive scan of the tile sums (one workgroup), total -> *d_total   (k_scan_tile_scan_lds: launch_tile_scan)
 //   pass 3  k_scan_apply       per tile: flags staged in LDS, workgroup exclusive scan, per-item prefixes
 //                              back through LDS so that apply(i, flag, exclusive_prefix) runs lane-coalesced
 //
@@ -156,6 +156,46 @@ static __global__ __launch_bounds__(1024) void k_scan_tile_scan(uint32_t *tile_s
         pdl_sync();
     }
     if (threadIdx.x == 0) scan_write_totals(s_carry, d_total, d_total2);
+}
+
+// The same scan with the sums staged through LDS (option "lean_records"): a thread's TS_ITEMS consecutive sums lie 64 bytes from
+// its neighbour's, so the loads and stores above are one line request per lane and instruction, about 16 k of them from one CU.
+// Here the workgroup reads and writes the sums coalesced (lane after lane, 256 bytes per wave and instruction) and a thread
+// takes its TS_ITEMS sums from LDS in 16-byte pieces.  At most 1024 x TS_ITEMS sums (64 KB of LDS; the 17 words of the block
+// scan lie at the end of the staged array, whose values are in registers by then); more: the trips of k_scan_tile_scan's carry path.
+static __global__ __launch_bounds__(1024) void k_scan_tile_scan_lds(uint32_t *tile_sums, uint32_t n_tiles, uint64_t *d_total, uint64_t *d_total2) {
+    __shared__ uint4 s_sums4[1024 * TS_ITEMS / 4];
+    uint32_t *s_sums = reinterpret_cast<uint32_t *>(s_sums4);
+    const uint32_t padded = (n_tiles + TS_ITEMS - 1) / TS_ITEMS * TS_ITEMS;      // (at most 1024 x TS_ITEMS: the host takes the carry path above that)
+    for (uint32_t i = threadIdx.x; i < padded; i += 1024) s_sums[i] = i < n_tiles ? tile_sums[i] : 0u;
+    pdl_sync();
+    const uint32_t i0 = threadIdx.x * TS_ITEMS;
+    uint32_t v[TS_ITEMS], sum = 0;
+#pragma unroll
+    for (int j = 0; j < TS_ITEMS; j += 4) {
+        const uint4 q = i0 < padded ? s_sums4[(i0 + j) / 4] : make_uint4(0u, 0u, 0u, 0u);
+        v[j] = q.x; v[j + 1] = q.y; v[j + 2] = q.z; v[j + 3] = q.w;
+        sum += q.x + q.y + q.z + q.w;
+    }
+    pdl_sync();                                          // (every thread holds its sums: the array's last words serve the block scan)
+    uint32_t total;
+    uint32_t ex = block_exclusive_scan_u32(sum, s_sums + 1024 * TS_ITEMS - 32, total);
+    if (i0 < padded) {
+#pragma unroll
+        for (int j = 0; j < TS_ITEMS; j += 4) {
+            uint4 q;
+            q.x = ex; ex += v[j]; q.y = ex; ex += v[j + 1]; q.z = ex; ex += v[j + 2]; q.w = ex; ex += v[j + 3];
+            s_sums4[(i0 + j) / 4] = q;
+        }
+    }
+    pdl_sync();
+    for (uint32_t i = threadIdx.x; i < n_tiles; i += 1024) tile_sums[i] = s_sums[i];
+    if (threadIdx.x == 0) scan_write_totals(total, d_total, d_total2);
+}
+// the middle launch of a three-launch scan
+inline void launch_tile_scan(pdl_ctx *c, uint32_t *tile_sums, uint32_t n_tiles, uint64_t *d_total, uint64_t *d_total2) {
+    if (c->opt_lean_records && n_tiles <= 1024u * TS_ITEMS) hipLaunchKernelGGL(k_scan_tile_scan_lds, dim3(1), dim3(1024), 0, c->stream, tile_sums, n_tiles, d_total, d_total2);
+    else hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, c->stream, tile_sums, n_tiles, d_total, d_total2);
 }
 
 // INLINE_PREFIX (short scans, <= SCAN_INLINE_TILES tiles): tile_sums holds the raw sums and every workgroup adds up the
@@ -443,7 +483,7 @@ inline void scan_and_apply(pdl_ctx *c, uint64_t n, FlagF flag, ApplyF apply, uin
     if (tiles <= SCAN_INLINE_TILES) {
         hipLaunchKernelGGL((k_scan_apply<FlagF, ApplyF, true>), dim3(tiles), dim3(SCAN_THREADS), 0, c->stream, flag, apply, n, d_n, ts, d_total, d_total2);
     } else {
-        hipLaunchKernelGGL(k_scan_tile_scan, dim3(1), dim3(1024), 0, c->stream, ts, tiles, d_total, d_total2);
+        launch_tile_scan(c, ts, tiles, d_total, d_total2);
         hipLaunchKernelGGL((k_scan_apply<FlagF, ApplyF, false>), dim3(tiles), dim3(SCAN_THREADS), 0, c->stream, flag, apply, n, d_n, ts, d_total, d_total2);
     }
     PDL_HIP(hipGetLastError());
