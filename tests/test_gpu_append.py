@@ -53,25 +53,26 @@ def _assert_same_context(a, b, label, edges=True):
                 assert np.array_equal(H.raw(x), H.raw(y)), f"{label}: edges of genome {g}"
 
 
-def _assert_oracle(nat, res, off, gen, k, label):
+def _assert_oracle(nat, res, off, gen, k, label, ora=None):
     from oracle import binding as ob
-    ora = ob.Oracle(res, off, gen, k)
+    ora = ora or ob.Oracle(res, off, gen, k)
     assert nat.cost.genomes == ora.genomes and nat.cost.total_cost == ora.total_cost, label
     for g in range(ora.genomes):
         H.assert_scores_equal(nat.generate_scores_part(g).as_dict(), ora.scores(g), f"{label} genome {g} vs oracle")
         assert nat.genome_cost(g) == ora.genome_cost(g), f"{label} genome {g} cost"
 
 
-def _append_vs_union(base, query, k, label, flags=0, options=(), oracle=True, edges=True):
+def _append_vs_union(base, query, k, label, flags=0, options=(), oracle=True, edges=True, late=(), ora=None):
+    """`late`: options set between the base's build and the append; the union is built under what is in force at the end."""
     res, off, gen, G = _union(base, query)
-    nat = _native(k, *base, flags=flags, options=options)
+    nat = _native(k, *base, flags=flags, options=options, late=late)
     base_records = nat.cost.dictionary_records
     nat.append(*query)
     assert nat.cost.genomes == G + 1 and nat.cost.sequences == len(gen), label
-    uni = _native(k, res, off, gen, flags=flags, options=options)
+    uni = _native(k, res, off, gen, flags=flags, options=tuple(options) + tuple(late))
     _assert_same_context(nat, uni, label, edges=edges)
     if oracle and not flags:
-        _assert_oracle(nat, res, off, gen, k, label)
+        _assert_oracle(nat, res, off, gen, k, label, ora=ora)
     info = nat.last_append_info
     assert info["residues"] == len(query[0]) and info["records"] == uni.cost.dictionary_records - base_records, label
     uni.close()

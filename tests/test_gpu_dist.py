@@ -26,10 +26,13 @@ def _device_inputs(res, off, gen):
     return t_res, t_off, t_gen
 
 
-def _local(world, res, off, gen, k, flags=0, exchange_weights=True, sender_ranges=True):
+def _local(world, res, off, gen, k, flags=0, exchange_weights=True, sender_ranges=True, options=()):
     from pandelos_amd.distributed import LocalRanks
     t = _device_inputs(res, off, gen)
     lr = LocalRanks(world, flags=flags, exchange_weights=exchange_weights, sender_ranges=sender_ranges)
+    for n in lr.ranks:
+        for name, v in options:
+            n.set_option(name, v)
     cost = lr.preprocess(k, *t, len(gen), len(res))
     return lr, cost
 

@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 N_SEEDS = int(os.environ.get("PDL_QUERY_SEEDS", "120"))
 
 
-def _native(k, res, off, gen, flags=0, options=(), shard=None):
+def _native(k, res, off, gen, flags=0, options=(), shard=None, late=()):
+    """`late`: options set on the built context, behind one scoring pass (tests/option_forms.py)."""
     from pandelos_amd.pangene_native import PangeneNative
     nat = PangeneNative.open(flags=flags)
     for name, v in options:
@@ -20,6 +21,10 @@ def _native(k, res, off, gen, flags=0, options=(), shard=None):
     if shard is not None:
         nat.set_genome_shard(shard)
     nat.preprocess(k, res, off, gen)
+    if late:
+        nat.score_all()
+        for name, v in late:
+            nat.set_option(name, v)
     return nat
 
 
@@ -54,10 +59,11 @@ def _union(base, query):
     return res, off, gen, G
 
 
-def _check_against_oracle(nat, base, query, k, label):
+def _check_against_oracle(nat, base, query, k, label, ora=None):
+    """`ora`: the oracle on the union where the caller has it already"""
     from oracle import binding as ob
     res, off, gen, G = _union(base, query)
-    ora = ob.Oracle(res, off, gen, k)
+    ora = ora or ob.Oracle(res, off, gen, k)
     got = nat.query_scores(*query).as_dict()
     H.assert_scores_equal(got, ora.scores(G), label)
     assert nat.last_query_info["genome_cost"] == ora.genome_cost(G), label

@@ -50,57 +50,68 @@ def _genes(seqs):
     return pack(seqs, [0] * len(seqs))[:2]
 
 
-def _assert_dictionary_is_the_oracles(nat, res, off, gen, k, label):
+def _assert_dictionary_is_the_oracles(nat, res, off, gen, k, label, ora=None):
     from oracle import binding as ob
-    d = ob.Oracle(res, off, gen, k).dictionary()
+    d = (ora or ob.Oracle(res, off, gen, k)).dictionary()
     ranks, seqs, counts = nat.dictionary()
     assert np.array_equal(ranks, d["rank"]) and np.array_equal(seqs, d["seq"]) and np.array_equal(counts, d["count"]), f"{label}: dictionary vs oracle"
 
 
-def _check_info(nat, rekeyed, before, after, m, label):
-    """last_rekey_info against the letters and rank_bits of the two sets and the length of the re-keyed stream."""
+def _check_info(nat, rekeyed, before, after, m, label, timed=True):
+    """last_rekey_info against the letters and rank_bits of the two sets and the length of the re-keyed stream.  `timed`: the
+    stages' events are on (option "stage_timers", the default); without them the re-key reports no time."""
     ri = nat.last_rekey_info
     assert ri["rekeyed"] == int(rekeyed), (label, ri)
     assert ri["letters_before"] == before[0] and ri["key_bits_before"] == before[1], (label, ri)
     assert ri["letters_after"] == after[0] and ri["key_bits_after"] == after[1], (label, ri)
     assert ri["keys_rewritten"] == (m if rekeyed else 0), (label, ri)
-    assert (ri["rekey_ms"] > 0) == bool(rekeyed), (label, ri)
+    assert (ri["rekey_ms"] > 0) == bool(rekeyed and timed), (label, ri)
 
 
-def _append_vs_union(base, query, k, label, rekeyed=True, options=ON):
+def _fresh_options(options, late):
+    """what the context to compare with is built under: everything in force at the end but "alphabet_rekey", which a build of
+    the final set has no use for"""
+    return tuple(o for o in tuple(options) + tuple(late) if o[0] != "alphabet_rekey")
+
+
+def _append_vs_union(base, query, k, label, rekeyed=True, options=ON, late=(), ora=None):
+    """`late`: options set between the base's build and the append (tests/option_forms.py); `ora`: the oracle on the union where
+    the caller has it.  With "stage_timers" 0 in force the stages report no times: only the total is compared."""
+    timed = dict(_fresh_options(options, late)).get("stage_timers", 1) != 0
     res, off, gen, G = _union(base, query)
-    nat = _native(k, *base, options=options)
+    nat = _native(k, *base, options=options, late=late)
     before = (len(np.unique(base[0])), nat.cost.rank_bits)
     m0 = nat.cost.kmer_occurrences
     nat.append(*query)
-    uni = _native(k, res, off, gen)
+    uni = _native(k, res, off, gen, options=_fresh_options(options, late))
     _assert_same_context(nat, uni, label)
-    _assert_oracle(nat, res, off, gen, k, label)
-    _assert_dictionary_is_the_oracles(nat, res, off, gen, k, label)
-    _check_info(nat, rekeyed, before, (len(np.unique(res)), uni.cost.rank_bits), m0, label)
+    _assert_oracle(nat, res, off, gen, k, label, ora=ora)
+    _assert_dictionary_is_the_oracles(nat, res, off, gen, k, label, ora=ora)
+    _check_info(nat, rekeyed, before, (len(np.unique(res)), uni.cost.rank_bits), m0, label, timed)
     tm, info, ri = nat.timings(), nat.last_append_info, nat.last_rekey_info
     assert tm["preprocess_total_ms"] == info["device_ms"], label
     # the re-key's time is part of the sort's share: rank + (sort + merge + re-key) = what the infos report; K-hist is the build's alone
-    assert abs(tm["sort_rank_ms"] + tm["rank_ms"] - info["rank_sort_ms"] - info["merge_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
+    assert not timed or abs(tm["sort_rank_ms"] + tm["rank_ms"] - info["rank_sort_ms"] - info["merge_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
     assert tm["hist_ms"] == 0, (label, tm)
     uni.close()
     return nat
 
 
-def _remove_vs_rebuild(res, off, gen, k, removed, label, rekeyed=True, options=ON):
-    nat = _native(k, res, off, gen, options=options)
+def _remove_vs_rebuild(res, off, gen, k, removed, label, rekeyed=True, options=ON, late=(), ora=None):
+    timed = dict(_fresh_options(options, late)).get("stage_timers", 1) != 0
+    nat = _native(k, res, off, gen, options=options, late=late)
     before = (len(np.unique(res)), nat.cost.rank_bits)
     nat.remove(removed)
     rest = _remaining(res, off, gen, removed)
-    reb = _native(k, *rest)
+    reb = _native(k, *rest, options=_fresh_options(options, late))
     _assert_same_context(nat, reb, label)
-    _assert_oracle(nat, *rest, k, label)
-    _assert_dictionary_is_the_oracles(nat, *rest, k, label)
-    _check_info(nat, rekeyed, before, (len(np.unique(rest[0])), reb.cost.rank_bits), reb.cost.kmer_occurrences, label)
+    _assert_oracle(nat, *rest, k, label, ora=ora)
+    _assert_dictionary_is_the_oracles(nat, *rest, k, label, ora=ora)
+    _check_info(nat, rekeyed, before, (len(np.unique(rest[0])), reb.cost.rank_bits), reb.cost.kmer_occurrences, label, timed)
     tm, info, ri = nat.timings(), nat.last_remove_info, nat.last_rekey_info
     assert tm["preprocess_total_ms"] == info["device_ms"], label
     # the compaction and the re-key are the removal's "sort"; nothing is ranked or counted
-    assert abs(tm["sort_rank_ms"] - info["compact_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
+    assert not timed or abs(tm["sort_rank_ms"] - info["compact_ms"] - ri["rekey_ms"]) < 1e-3, (label, tm, info, ri)
     assert tm["hist_ms"] == 0 and tm["rank_ms"] == 0, (label, tm)
     reb.close()
     return nat

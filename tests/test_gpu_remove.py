@@ -35,16 +35,17 @@ def _remaining(res, off, gen, removed):
     return remaining_input(res, off, gen, removed)
 
 
-def _remove_vs_rebuild(res, off, gen, k, removed, label, flags=0, options=(), oracle=True, edges=True):
-    """Build the whole set, remove `removed`, compare with a build of the remaining set (and the oracle on it)."""
-    nat = _native(k, res, off, gen, flags=flags, options=options)
+def _remove_vs_rebuild(res, off, gen, k, removed, label, flags=0, options=(), oracle=True, edges=True, late=(), ora=None):
+    """Build the whole set, remove `removed`, compare with a build of the remaining set (and the oracle on it).  `late`: options
+    set between the build and the removal; the remaining set is built under what is in force at the end."""
+    nat = _native(k, res, off, gen, flags=flags, options=options, late=late)
     whole = nat.cost.as_dict()
     nat.remove(removed)
     rest = _remaining(res, off, gen, removed)
-    reb = _native(k, *rest, flags=flags, options=options)
+    reb = _native(k, *rest, flags=flags, options=tuple(options) + tuple(late))
     _assert_same_context(nat, reb, label, edges=edges)
     if oracle and not flags:
-        _assert_oracle(nat, *rest, k, label)
+        _assert_oracle(nat, *rest, k, label, ora=ora)
     info = nat.last_remove_info
     assert info["sequences"] == whole["sequences"] - reb.cost.sequences and info["residues"] == len(res) - len(rest[0]), label
     assert info["kmer_occurrences"] == whole["kmer_occurrences"] - reb.cost.kmer_occurrences, label
